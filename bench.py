@@ -10,10 +10,14 @@ the default K=282 steps is ~1 h of stereo.  Inputs are resident in HBM before th
 `value` = hours of (stereo) audio encoded per wall-clock hour, summed over all ranks (the path
 shards by chunk range with no collective: weak scaling, "replicas only" for RCCL).
 
-The same line carries the duplex-stream leg (BASELINE configs[2]/[3]: ~1B random-init
-codec-LM, 80 ms frames) as `duplex`: xRT and p50 frame-step latency, plus `roofline` for the
-dominant kernel of the headline workload and `cpu_baseline` (the CPU oracle timed on the host
-cores on a bounded sample, rank 0, N=1 only).
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.
+With --full the same line also carries the duplex-stream leg (BASELINE configs[2]/[3]: ~1B
+random-init codec-LM, 80 ms frames) as `duplex`: xRT and p50 frame-step latency, plus `roofline`
+for the dominant kernel of the headline workload, the trimmed / bf16 / batch-CLI legs and
+`cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample, rank 0, N=1 only).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's code ids of that step, as
+float64) to DIR/codes.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -187,6 +191,10 @@ def main():
     ap.add_argument("--duplex-secs", type=float, default=125.0,
                     help="audio seconds of the duplex leg; >= 110 puts two sliding-window trims (80 s context, trim by 20 s) inside the timed window")
     ap.add_argument("--variant", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: per-kernel roofline, trimmed / bf16 / batch-CLI / duplex legs, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the code ids of the last timed step to DIR/codes.npy (float64)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -242,7 +250,7 @@ def main():
     torch.cuda.synchronize(dev)
     cp.barrier()
     torch.cuda.synchronize(dev)
-    hip.profile(True)
+    hip.profile(args.full)           # HIP-event pairs around each launch, for the roofline of --full only
     t0 = time.perf_counter()
     for i in range(args.warmup, total_steps):
         step(i)
@@ -254,10 +262,16 @@ def main():
     prof = {k: hip.profile_read(k) for k in (0, 1, 2, 3)}       # the headline's launches (later legs profile on their own)
     elapsed = cp.max(elapsed)
 
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path receives from its last step: the code ids of that step's chunk range, both channels
+        last = codes[:, (total_steps - 1) * chunks_per_step * fpc:total_steps * chunks_per_step * fpc]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "codes.npy"), last.cpu().numpy().astype(np.float64))
+
     # SURVEY 8f-1 leg (reported beside the headline, never as `value`): the same steps with every window cut down
     # to the receptive field of its kept frames -- identical codes (checked), ~10x less encoder work
     elapsed_trim, trim_identical = None, None
-    if not args.no_trim_leg:
+    if args.full and not args.no_trim_leg:
         codes_full = codes.clone()
         hip.set_window_trim(True)
         for i in range(args.warmup):
@@ -280,7 +294,7 @@ def main():
     # (mode 1, audio_tokenizer.py:24,78-82).  Not bit-exact: the fraction of code ids equal to the f32 path is measured here.
     bf16_legs, roofline_bf16 = None, None
     conv_bytes_f32 = prof[0]["bytes"]
-    if not args.no_bf16_leg:
+    if args.full and not args.no_bf16_leg:
         bf16_legs = {}
         codes_f32 = codes.clone()
         for mode, name in ((3, "bf16_hi_lo_split"), (1, "bf16_rounded")):
@@ -321,13 +335,6 @@ def main():
 
     audio_secs = args.steps * chunks_per_step * chunk / cfg.sample_rate  # per rank, stereo seconds
     value = world * audio_secs / elapsed
-    conv = prof[0]
-    achieved = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
-    # sanity: emitted ids are in range and not constant
-    sample = codes[:, : 64 * fpc].cpu().numpy()
-    assert sample.min() >= 0 and sample.max() < cfg.codebook_size
-
-    traffic, traffic_src = latest_profile_traffic()
     out = {
         "metric": "batch-encode audio-hours/hour (+ xRT and p50 frame-step latency of 1 duplex stream in `duplex`)",
         "value": value,
@@ -355,14 +362,22 @@ def main():
             "sharding": "chunk ranges per rank, no collective (replicas only)",
             "control_plane": cp.describe(),
             "bf16_mfma_opt_in": bf16_legs,
-            "receptive_field_trimmed": None if args.no_trim_leg else {
+            "receptive_field_trimmed": None if elapsed_trim is None else {
                 "value": world * audio_secs / elapsed_trim, "unit": "audio-hours/hour", "ms_per_step": 1e3 * elapsed_trim / args.steps,
                 "codes_identical_to_full_windows": trim_identical,
                 "note": "same steps with rca_codec_set_window_trim(1): each window cut to the kept frames + their receptive "
                         "field (SURVEY 8f-1); valid for this build's conv codec only, so it is not the headline value",
             },
         },
-        "roofline": {
+    }
+    if args.full:
+        conv = prof[0]
+        achieved = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
+        # sanity: emitted ids are in range and not constant
+        sample = codes[:, : 64 * fpc].cpu().numpy()
+        assert sample.min() >= 0 and sample.max() < cfg.codebook_size
+        traffic, traffic_src = latest_profile_traffic()
+        out["roofline"] = {
             "kernel": "conv1d_mfma_kernel (implicit-GEMM conv, v_mfma_f32_32x32x2_f32)",
             "bound": "mfma",
             "achieved": achieved,
@@ -384,14 +399,13 @@ def main():
             # algorithmic bytes / launch time is ~1/9 of 8 TB/s
             "hbm": {"achieved_gbs": conv["bytes"] / (conv["ms"] * 1e-3) / 1e9 if conv["ms"] > 0 else None, "peak_gbs": HBM_PEAK_GBS,
                     "frac": conv["bytes"] / (conv["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if conv["ms"] > 0 else None},
-        },
-    }
+        }
     if roofline_bf16 is not None:
         out["roofline_bf16"] = roofline_bf16
     # The duplex legs run BEFORE the batch-CLI and CPU-baseline legs: a session that started behind them (256 OpenMP threads, 32 torch
     # threads, a 5 GB host model, the CLI's reader / writer threads and pinned ring, all just released) showed one 27-35 ms frame in
     # three of five default runs and in none of 17 runs without those legs in front of it (scripts/duplex_outlier_ab.sh).
-    if not args.no_duplex:
+    if args.full and not args.no_duplex:
         # one independent duplex session per GPU (BASELINE configs[3]/[4]; no exchange between sessions)
         from realtime_codec_agent_amd.duplex_bench import run_duplex_bench
         mine = run_duplex_bench(dev, secs=args.duplex_secs if world == 1 else min(args.duplex_secs, 10.0))
@@ -411,9 +425,9 @@ def main():
                 out[f"duplex_{fmt}"] = {k: q[k] for k in ("workload", "xRT", "p50_frame_step_ms", "p99_frame_step_ms", "max_frame_step_ms", "frames", "lm_step_ms",
                                                            "lm_ctx_tokens", "lm_hbm_gbs", "lm_weight_gb_per_step")}
                 out[f"duplex_{fmt}"]["roofline_lm"] = rq
-    if rank == 0 and world == 1 and not args.no_cli_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_cli_leg:
         out["config"]["batch_cli"] = batch_cli_leg()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_encode(cfg, weights, chunk, ctx, 64, C)
         if not args.no_duplex:
             from realtime_codec_agent_amd.llm import LMConfig

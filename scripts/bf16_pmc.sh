@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 for pass in "sq GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES" "fetch FETCH_SIZE" "write WRITE_SIZE"; do
   set -- $pass; name=$1; shift
   rm -rf /tmp/bfpmc_$name
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/bfpmc_$name -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-duplex --no-trim-leg --no-cli-leg > /dev/null 2>&1
+  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/bfpmc_$name -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-duplex --no-trim-leg --no-cli-leg > /dev/null 2>&1
 done
 python3 - <<PY
 import csv, glob, collections

@@ -25,7 +25,7 @@ def main():
     # fall-back to gloo inside the rank processes for real (dist_utils.ControlPlane; RCA_REHEARSE_BACKEND=gloo skips the attempt)
     e1 = dict(env, RCA_BENCH_DEVICE="0", RCA_BENCH_BACKEND=os.environ.get("RCA_REHEARSE_BACKEND", "nccl"))
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--duplex-secs", "10"], env=e1,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--duplex-secs", "10"], env=e1,
                        capture_output=True, text=True, timeout=900)
     line = next((ln for ln in reversed(r.stdout.splitlines()) if ln.startswith("{")), None)
     assert r.returncode == 0 and line, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
