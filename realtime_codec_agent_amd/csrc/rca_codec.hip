@@ -181,6 +181,7 @@ __device__ float rca_buffer_load_f32(rca_rsrc_t rsrc, int voffset, int soffset, 
 __device__ rca_f32x2_t rca_buffer_load_f32x2(rca_rsrc_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");
 typedef float rca_f32x4_t __attribute__((ext_vector_type(4)));
 __device__ rca_f32x4_t rca_buffer_load_f32x4(rca_rsrc_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
+__device__ void rca_buffer_store_f32(float v, rca_rsrc_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.f32");
 __device__ __forceinline__ rca_rsrc_t rca_make_rsrc(const void* base, int num_records) {   // base must be wave-uniform
     const unsigned long a = (unsigned long)base;
     rca_rsrc_t r;
@@ -879,6 +880,254 @@ __global__ __launch_bounds__(64 * RCA_CONV_WPB, (((KS == 8 && CIC == 2) || (KS =
         o[0] = tl0; o[1] = tl1; o[2] = tl2; o[3] = tl3;
         o[4] = (long)hw | ((long)xcc << 32);
         o[5] = (long)KS | ((long)S << 8) | ((long)WM << 16) | ((long)wave << 24) | ((long)blockIdx.x << 32);
+    }
+#endif
+}
+
+// Fused first layer with conv_in on the matrix pipe (k4s2 layer, Cin = 32; RCA_FUSE_MFMA_IN=0 brings conv1d_mfma_kernel<4, 2, 2, 2, 4, 1>
+// back).  conv_in is a GEMM of its own: M = 32 channels, K = 7 taps + 1 pad, N = positions, so ONE v_mfma_f32_32x32x2_f32 chain of 4
+// yields all 32 input channels of 32 staged positions (the VALU path spends ~10 instructions per channel and position instead).  That
+// changes the staging order: the wave walks its 128 columns in NWN groups of 32 and, per group, runs the whole K = 128 reduction (16
+// channel pairs x 4 k pairs x 2 row tiles) from a rolling LDS window of position blocks, all 32 channels each:
+//   position e of the wave (e = 2 * slot + phase, slot s <-> column n0 - 1 + s) lives at ring[ch][e & 127]; group wn reads e in
+//   [64 wn + 1, 64 wn + 68] (tap kk of column 32 wn + j reads e = 2 (32 wn + j) + 1 + kk), i.e. blocks 2wn, 2wn+1 and 4 words of 2wn+2.
+//   During group wn the conv_in MFMAs of blocks 2wn+3 and 2wn+4 are interleaved into its MFMA stream; 2wn+3 replaces block 2wn-1 at
+//   once, 2wn+4 replaces block 2wn channel by channel as the group's reads leave those channels behind.
+// The 128 weight k pairs of the wave's 64 rows stay in registers for the whole wave (128 VGPRs, loaded once); the accumulators are
+// those of one 32-column group (32 registers), stored when the group is done.  Every output keeps its k order (bias, then channel-major,
+// tap-minor), so the results are those of conv1d_mfma_kernel bit for bit.
+template <int NWN, bool PRE>
+__global__ __launch_bounds__(64, 2) void conv_first_mfma_kernel(const float* __restrict__ wp, const float* __restrict__ bias,
+                                                               float* __restrict__ y, int Cout, int Lout, long Ncols, int post, float slope,
+                                                               FuseIn fin) {
+    constexpr int NW = NWN * 32;             // columns per wave
+    constexpr int E = (NW + 2) * 2;          // staged positions (two phases of NW + 2 slots)
+    constexpr int NBLK = 2 * NWN + 1;        // 32-position blocks that cover them
+    constexpr int RS = 136;                  // ring row stride (floats): positions 0..127, a zero word at 128, padding
+    constexpr int ZERO = 128;
+    constexpr int CIN = 32, KQ = CIN / 2;    // input channels; weight quads (4 k pairs = 2 channels) per 32-row tile
+    extern __shared__ __attribute__((aligned(16))) float ring[];   // [CIN][RS]
+#ifdef RCA_CONV_TIMELINE
+    long* const tl_buf = rca_prof_buf;
+#endif
+    RCA_TL_STAMP(tl0);
+    const int lane = threadIdx.x & 63;
+    const int half = lane >> 5, jl = lane & 31;
+    const int n_co = Cout / 64;
+    const long wg = blockIdx.x;
+    const int xcd = (int)(wg & 7);
+    const long seq = wg >> 3;
+    const int co_tile = __builtin_amdgcn_readfirstlane((int)(seq % n_co));
+    const long n0 = ((seq / n_co) * 8 + xcd) * NW;   // same walk as conv1d_mfma_kernel: the channel tiles of a column tile share an L2
+    const int co0 = co_tile * 64;
+    if (n0 >= Ncols) return;
+    const long n_base = n0 > 0 ? n0 - 1 : 0;
+    const int b_base = __builtin_amdgcn_readfirstlane((int)((unsigned)n_base / (unsigned)Lout));
+    const int t_base = (int)(n_base - (long)b_base * Lout);
+    const int lead = n0 > 0 ? 0 : 1;
+    const long left = Ncols - n_base;
+    const int ncol_left = left > NW + 2 ? NW + 2 : (int)left;
+    auto rel_bt = [&](int dn, int& bb, int& tt) {   // the host launches this kernel only for rows longer than NW + 2 columns
+        int dt = dn + t_base;
+        bb = dt >= Lout ? 1 : 0;
+        tt = bb ? dt - Lout : dt;
+    };
+
+    // ---- conv_in as MFMA.  A: lane = (channel jl, k slot half), k pair m holds taps 2m + half; B: lane = (position jl, same k slot);
+    // C starts at the bias (C/D row (r&3) + 8 (r>>2) + 4 half = channel).  The k pairs run in ascending tap order, so every output is
+    // conv_in_kernel's chain bias, fma(w0, x0), ..., fma(w6, x6), with taps outside the signal reading 0 (as in conv1d_mfma_kernel's
+    // fused staging).  The pad tap k = 7 has weight -0.0 and PCM +0: its product is -0, and acc + (-0) == acc for EVERY acc, signed
+    // zero included (+0 + -0 = +0, -0 + -0 = -0 in round-to-nearest), so it cannot change a value (a +0 weight could: -0 + +0 = +0).
+    const int ch_in = jl;
+    float a_in[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) a_in[m] = (2 * m + half < 7) ? fin.w_in[ch_in * 7 + 2 * m + half] : -0.0f;
+    f32x16 b_in;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) b_in[r] = fin.b_in[(r & 3) + 8 * (r >> 2) + 4 * half];
+    // PCM rows of the two batch rows the wave can touch, addressed from the lower one (as in conv1d_mfma_kernel)
+    long o0, o1;
+    if (fin.src.row_off) {
+        const long nrows = (Ncols + Lout - 1) / Lout;
+        o0 = fin.src.row_off[b_base];
+        o1 = fin.src.row_off[b_base + 1 < nrows ? b_base + 1 : b_base];
+    } else {
+        const int C = fin.src.C;
+        const int c0 = b_base % C, w0 = b_base / C;
+        const int c1 = c0 + 1 == C ? 0 : c0 + 1, w1 = c0 + 1 == C ? w0 + 1 : w0;
+        o0 = (long)c0 * fin.src.chan_stride + (long)w0 * fin.src.win_stride;
+        o1 = (long)c1 * fin.src.chan_stride + (long)w1 * fin.src.win_stride;
+    }
+    const long om = o0 < o1 ? o0 : o1;
+    const rca_rsrc_t rs_pcm = rca_make_rsrc(fin.src.base + om, 0x7FFFFFFF);
+    const unsigned prow0 = (unsigned)(o0 - om), prow1 = (unsigned)(o1 - om);
+    constexpr unsigned OOB = 0x80000000u;
+    // B operand of block bk: PCM taps 2m + half of position 32 bk + jl.  Positions of absent columns (before column 0, past the last
+    // column or the window) read only zeros; they are read back solely by the taps that cross a row edge, which the B reads below
+    // redirect to the zero word, so their values never reach an output (conv1d_mfma_kernel zeroes them; the outputs are the same).
+    auto pcm_load = [&](int bk, float (&pb)[4]) __attribute__((always_inline)) {
+        const int e = 32 * bk + jl;
+        const int dn = (e >> 1) - lead;
+        const bool ok = e < E && dn >= 0 && dn < ncol_left;
+        int bb, t;
+        rel_bt(ok ? dn : 0, bb, t);
+        const int i = 2 * t + (e & 1) - 3 + half;   // sample of tap `half`
+        const unsigned ro = bb ? prow1 : prow0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int j = i + 2 * m;
+            const unsigned off = (ok && 2 * m + half < 7 && j >= 0 && j < fin.src.T) ? (ro + (unsigned)j) * 4u : OOB;
+            pb[m] = rca_buffer_load_f32(rs_pcm, (int)off, 0, 0);
+        }
+    };
+    auto cin_mfma = [&](int m, const float (&pb)[4], f32x16& d) __attribute__((always_inline)) {
+        d = __builtin_amdgcn_mfma_f32_32x32x2f32(a_in[m], pb[m], m == 0 ? b_in : d, 0, 0, 0);
+    };
+    // rows r0..r1-1 of a finished block into the ring (the layer's pre-activation applied here, once per element)
+    const int w_lane = 4 * half * RS + jl;
+    auto cin_write = [&](int bk, f32x16& d, int r0, int r1) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = r0; r < r1; ++r) {
+            float v = d[r];
+            if (PRE) v = fmaxf(v, v * slope);   // the LeakyReLU of conv1d_mfma_kernel's staging
+            ring[w_lane + ((r & 3) + 8 * (r >> 2)) * RS + ((32 * bk) & 127)] = v;
+        }
+    };
+
+    // prologue: blocks 0..2 (what group 0 reads) and the zero word of every channel row.  Their PCM is requested ahead of the weight
+    // quads, so the conv_in MFMAs wait for it alone.
+    if (lane < CIN) ring[lane * RS + ZERO] = 0.0f;
+    float pa[4], pb[4];
+    float4 a[2][KQ];
+    {
+        float p2[4];
+        pcm_load(0, pa);
+        pcm_load(1, pb);
+        pcm_load(2, p2);
+        __builtin_amdgcn_sched_barrier(0);
+    // weights of the wave's 64 rows, A-fragment order (the packing of conv1d_mfma_kernel): a[wm][q] = k pairs 4q..4q+3
+        const rca_rsrc_t rs_w = rca_make_rsrc(reinterpret_cast<const float4*>(wp) + (long)co_tile * 2 * KQ * 64, 0x7FFFFFFF);
+#pragma unroll
+        for (int wm = 0; wm < 2; ++wm)
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) {
+                const rca_f32x4_t v = rca_buffer_load_f32x4(rs_w, lane * 16, (wm * KQ + q) * 1024, 0);
+                a[wm][q] = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+        f32x16 d0, d1;   // two result sets (the 128 weight registers are live from here on)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) { cin_mfma(m, pa, d0); cin_mfma(m, pb, d1); }
+        cin_write(0, d0, 0, 16);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) cin_mfma(m, p2, d0);
+        cin_write(1, d1, 0, 16);
+        cin_write(2, d0, 0, 16);
+    }
+    if (NBLK > 3) pcm_load(3, pa);
+    if (NBLK > 4) pcm_load(4, pb);
+    __builtin_amdgcn_wave_barrier();
+    RCA_TL_STAMP(tl1);
+#ifdef RCA_CONV_TIMELINE
+    long tl_load = 1 << 30, tl_mfma = 0, tl_write = 0;   // per group: SHORTEST group / sum of the groups / sum of the stores
+#endif
+
+    // stores through a descriptor over the wave's first output row: the row offset is scalar, a lane whose column does not exist gets
+    // an offset past num_records and its store is dropped (offsets stay below 2^31: host check on Cout * Lout)
+    const rca_rsrc_t rs_y = rca_make_rsrc(y + ((long)b_base * Cout + co0) * Lout, 0x7FFFFFFF);
+    __builtin_amdgcn_s_setprio(RCA_CONV_EPRIO);
+#pragma unroll
+    for (int wn = 0; wn < NWN; ++wn) {
+        RCA_TL_STAMP(ta);
+        const int j = 32 * wn + jl;   // column n0 + j
+        int bz, tz;
+        rel_bt(1 - lead + j, bz, tz);
+        // B-read addresses of this lane: k pair 2c holds taps (0, 1), 2c + 1 taps (2, 3) of channel c; tap kk reads e = 2j + 1 + kk.  A
+        // tap that crosses a row edge (tap 0 of t = 0, tap 3 of t = Lout - 1) reads the zero word instead (conv1d_mfma_kernel's zmask).
+        const int ad0 = (half == 0 && tz == 0) ? ZERO : ((2 * j + 1 + half) & 127);
+        const int ad1 = (half == 1 && tz == Lout - 1) ? ZERO : ((2 * j + 3 + half) & 127);
+        f32x16 acc[2];
+#pragma unroll
+        for (int wm = 0; wm < 2; ++wm)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 bq = *reinterpret_cast<const f32x4*>(bias + co0 + wm * 32 + 8 * q + 4 * half);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) acc[wm][4 * q + jj] = bq[jj];
+            }
+        const bool more = 2 * wn + 4 < NBLK;   // compile-time after unrolling
+        f32x16 d;
+        float bcur[4], bnxt[4];
+        auto b_read = [&](int c, float (&bv)[4]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int cl = 0; cl < 2; ++cl) {
+                bv[2 * cl] = ring[ad0 + (2 * c + cl) * RS];
+                bv[2 * cl + 1] = ring[ad1 + (2 * c + cl) * RS];
+            }
+        };
+        b_read(0, bcur);
+#pragma unroll
+        for (int c = 0; c < KQ; ++c) {
+            if (c + 1 < KQ) b_read(c + 1, bnxt);
+#pragma unroll
+            for (int kp = 0; kp < 4; ++kp) {
+#pragma unroll
+                for (int wm = 0; wm < 2; ++wm) {
+                    const float4 q4 = a[wm][c];
+                    const float av = kp == 0 ? q4.x : kp == 1 ? q4.y : kp == 2 ? q4.z : q4.w;
+                    acc[wm] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bcur[kp], acc[wm], 0, 0, 0);
+                }
+                // conv_in of the next blocks, one MFMA per k pair: block 2wn+3 in chunk 0, 2wn+4 in chunk 3
+                if (c == 0 && 2 * wn + 3 < NBLK) cin_mfma(kp, pa, d);
+                if (c == 3 && more) cin_mfma(kp, pb, d);
+            }
+            // block 2wn+3 replaces block 2wn-1 (not read by this group); block 2wn+4 replaces block 2wn, channels 8g..8g+7 once chunk
+            // 4g+3 has read them (the C/D rows 4g..4g+3 of a lane are channels 8g + (0..3) + 4 half)
+            if (c == 2 && 2 * wn + 3 < NBLK) cin_write(2 * wn + 3, d, 0, 16);
+            if (more && c >= 4 && (c & 3) == 3) cin_write(2 * wn + 4, d, 4 * (c >> 2) - 4, 4 * (c >> 2));
+            // the PCM of the next group's blocks, a dozen chunks ahead of its use, once this group's conv_in MFMAs have read the registers
+            if (c == 1 && 2 * wn + 5 < NBLK) pcm_load(2 * wn + 5, pa);
+            if (c == 4 && 2 * wn + 6 < NBLK) pcm_load(2 * wn + 6, pb);
+            if (c + 1 < KQ) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) bcur[i] = bnxt[i];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (more) cin_write(2 * wn + 4, d, 12, 16);
+        __builtin_amdgcn_wave_barrier();
+        RCA_TL_STAMP(tb);
+        // store the group (C/D layout: column jl, channel (r&3) + 8 (r>>2) + 4 half)
+        const int dn = 1 - lead + j;
+        int bb, t;
+        rel_bt(dn, bb, t);
+        const unsigned voff = dn < ncol_left ? ((unsigned)bb * (unsigned)(Cout * Lout) + (unsigned)t + (unsigned)(4 * half * Lout)) * 4u : OOB;
+        if (post) {   // the next layer is pre-activated: store LeakyReLU(y) (see conv1d_mfma_kernel)
+#pragma unroll
+            for (int wm = 0; wm < 2; ++wm)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[wm][r] = fmaxf(acc[wm][r], acc[wm][r] * slope);
+        }
+#pragma unroll
+        for (int wm = 0; wm < 2; ++wm)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) rca_buffer_store_f32(acc[wm][r], rs_y, (int)voff, (wm * 32 + (r & 3) + 8 * (r >> 2)) * Lout * 4, 0);
+        RCA_TL_STAMP(tc);
+        RCA_TL_MIN(tl_load, ta, tb); RCA_TL_ADD(tl_mfma, ta, tb); RCA_TL_ADD(tl_write, tb, tc);
+    }
+    if (RCA_CONV_EPRIO) __builtin_amdgcn_s_setprio(0);
+    RCA_TL_STAMP(tl2);
+#ifdef RCA_CONV_TIMELINE
+    if (tl_buf && lane == 0) {   // same record as conv1d_mfma_kernel (region 0, the k4s2 layer); "chunks" are the column groups here
+        const long tl3 = (long)wall_clock64();
+        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
+        const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);
+        long* o = tl_buf + ((long)blockIdx.x & 0xFFFF) * 8;
+        o[6] = tl_load | (tl_mfma << 32);
+        o[7] = tl_write | ((long)(2 * NWN) << 32);
+        o[0] = tl0; o[1] = tl1; o[2] = tl2; o[3] = tl3;
+        o[4] = (long)hw | ((long)xcc << 32);
+        o[5] = 4L | (2L << 8) | (2L << 16) | ((long)blockIdx.x << 32);
     }
 #endif
 }
@@ -2406,6 +2655,19 @@ static int launch_conv_mfma(const ConvLayer& L, const float* x, float* y, int B,
         // bit-identical.  RCA_FUSE_WIDE=0 brings the 64 x 64 tiles back (A/B).
         static const bool wide = []() { const char* e = getenv("RCA_FUSE_WIDE"); return !(e && e[0] == '0'); }();
         if constexpr (KS == 4 && S == 2) {
+            // conv_in on the matrix pipe (conv_first_mfma_kernel): same tiles, same results.  RCA_FUSE_MFMA_IN=0 (read per call) brings
+            // the VALU conv_in of conv1d_mfma_kernel back (A/B).
+            const char* mi = getenv("RCA_FUSE_MFMA_IN");
+            constexpr int NWN = 4;
+            if (!(mi && mi[0] == '0') && wide && waves_big >= BIG_MIN && Lout >= NWN * 32 + 3 && L.cin == 32 && L.cout % 64 == 0) {
+                const long col_tiles = (cdiv(Ncols, NWN * 32) + 7) / 8 * 8;
+                const dim3 grid((unsigned)(col_tiles * (L.cout / 64)));
+                constexpr int lds = 32 * 136 * 4;
+                if (act & 1) conv_first_mfma_kernel<NWN, true><<<grid, 64, lds, st>>>(L.wp, L.bp, y, L.cout, Lout, Ncols, act & 2, slope, *fuse);
+                else conv_first_mfma_kernel<NWN, false><<<grid, 64, lds, st>>>(L.wp, L.bp, y, L.cout, Lout, Ncols, act & 2, slope, *fuse);
+                RCA_LAUNCH_CHECK();
+                return RCA_OK;
+            }
             if (wide && waves_big >= BIG_MIN && Lout >= 131 && L.cin % 2 == 0) {
                 launch_conv_cfg<4, 2, 2, 2, 4, 1, 0>(L, L.wp, L.cin / 2, x, y, Lin, Lout, Ncols, slope, *fuse, notr, st, act);
                 RCA_LAUNCH_CHECK();

@@ -6,6 +6,9 @@
 Runs two bench-shaped encode passes (256 windows), lets the library dump (t_entry, t_loop, t_epilogue, t_exit, HW_ID)
 per wave at codec destruction and prints, per layer: prologue / chunk loop / epilogue time of a wave and the gap between
 one wave leaving a hardware wave slot and the next wave entering it.  wall_clock64 ticks are 10 ns.
+The fused first layer (k4s2) records the same fields from conv_first_mfma_kernel (RCA_FUSE_MFMA_IN=0: from conv1d_mfma_kernel):
+prologue = conv_in of the first three position blocks, loop = the NWN column groups with their stores, "chunks" = 2 x NWN, so a
+"per chunk" figure there is per column group (MFMA stream incl. the interleaved conv_in) and the store phase of a group.
 """
 import os
 import sys
