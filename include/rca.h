@@ -193,6 +193,19 @@ int rca_codec_codebook(rca_codec_t* h, float* out_host);
 int rca_codec_encode_tap(rca_codec_t* h, const float* pcm_host, int32_t B, int32_t T, int32_t layer,
                          float* out_host, int64_t out_numel);
 
+/* Tests only: run encode()'s bf16 blocked pipeline (mfma mode 1 / 3) through encoder layer `layer`
+ * and copy the bf16 planes it stored for the next layer: hi and, in mode 3, lo, as raw bf16 bits.
+ * RCA_ERR_ARG when encode() would not take the blocked pipeline for this mode / shape, or the
+ * layer is not materialised (layer 0 while conv_in is fused, or the last layer, which is f32).
+ * Same launches and instantiations as encode() for layers 0..layer; nothing after them runs.
+ * Layout as stored, channel-blocked: [B][C / 16][L][C % 16], numel = B * C * L of that layer.
+ * The stored values are the layer's f32 accumulator after LeakyReLU (max(v, slope * v), in f32:
+ * every layer this pipeline materialises feeds a pre-activated layer), then rounded to nearest
+ * even (mode 1: hi only; lo_host may be NULL and is not written) or split (mode 3: hi = rne(v),
+ * lo = rne(v - hi)).  tests/test_codec_bf16_gpu.py checks them against oracle/codec_bf16_ref.py. */
+int rca_codec_encode_tap_bf16(rca_codec_t* h, const float* pcm_host, int32_t B, int32_t T, int32_t layer,
+                              uint16_t* hi_host, uint16_t* lo_host, int64_t numel);
+
 /* Kernel-variant switch (parity tests compare variants): 0 = scalar-chain kernels,
  * 1 = MFMA/LDS kernels (default when available). */
 int rca_codec_set_variant(rca_codec_t* h, int32_t variant);

@@ -300,7 +300,7 @@ ABI_SYMBOLS = [
     "rca_codec_decode", "rca_codec_decode_dev",
     "rca_codec_encode_tail_dev", "rca_codec_decode_tail_dev", "rca_codec_encode_tail", "rca_codec_decode_tail", "rca_codec_set_stream_graphs", "rca_codec_receptive_field", "rca_codec_set_window_trim",
     "rca_codec_encoder_dev", "rca_codec_quantize_dev", "rca_codec_decoder_dev", "rca_codec_codebook_dev",
-    "rca_codec_codebook", "rca_codec_encode_tap", "rca_codec_set_variant", "rca_codec_sync",
+    "rca_codec_codebook", "rca_codec_encode_tap", "rca_codec_encode_tap_bf16", "rca_codec_set_variant", "rca_codec_sync",
     "rca_codec_profile", "rca_codec_profile_read",
     "rca_lm_create", "rca_lm_create_random", "rca_lm_destroy", "rca_lm_reset", "rca_lm_eval",
     "rca_lm_get_n_tokens", "rca_lm_set_n_tokens", "rca_lm_get_logits", "rca_lm_get_logits_row",

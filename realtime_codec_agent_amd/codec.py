@@ -30,6 +30,7 @@ class HipCodec:
         N.check(self._lib.rca_codec_create(C.byref(ccfg), tensors, len(weights), device, C.byref(self._h)), "rca_codec_create")
         del keep
         self.hop = cfg.hop
+        self.mfma_mode = 0
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -97,6 +98,7 @@ class HipCodec:
     def set_mfma_mode(self, mode: int) -> None:
         """Encoder conv arithmetic: 0 = f32 matrix instruction (bit-exact, default), 3 = bf16 hi + lo split, 1 = bf16 (opt-in, not bit-exact)."""
         N.check(self._lib.rca_codec_set_mfma_mode(self._h, int(mode)), "rca_codec_set_mfma_mode")
+        self.mfma_mode = int(mode)
 
     def set_stream_graphs(self, enable: bool) -> None:
         N.check(self._lib.rca_codec_set_stream_graphs(self._h, int(bool(enable))), "rca_codec_set_stream_graphs")
@@ -126,6 +128,23 @@ class HipCodec:
         N.check(self._lib.rca_codec_encode_tap(self._h, C.c_void_p(pcm.ctypes.data), B, T, layer, C.c_void_p(out.ctypes.data),
                                                C.c_int64(out.size)), "rca_codec_encode_tap")
         return out
+
+    def encode_tap_bf16(self, pcm: np.ndarray, layer: int) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """Tests only (rca_codec_encode_tap_bf16): the bf16 planes encode()'s blocked pipeline stores after encoder layer `layer`
+        in mfma mode 1 / 3, as raw bf16 bits [B, C, L] uint16: (hi, lo), lo None in mode 1."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        B, T = pcm.shape
+        L = self.num_frames(T) * self.hop
+        for i in range(layer):
+            L //= self.cfg.strides[i]
+        Cn = self.cfg.channels[layer] if 0 <= layer <= self.cfg.n_stages else 0
+        hi = np.empty((B, Cn // 16, L, 16), np.uint16)
+        lo = np.empty_like(hi) if self.mfma_mode == 3 else None
+        N.check(self._lib.rca_codec_encode_tap_bf16(self._h, C.c_void_p(pcm.ctypes.data), B, T, layer, C.c_void_p(hi.ctypes.data),
+                                                    C.c_void_p(lo.ctypes.data if lo is not None else None), C.c_int64(B * Cn * L)),
+                "rca_codec_encode_tap_bf16")
+        unblock = lambda a: np.ascontiguousarray(a.transpose(0, 1, 3, 2).reshape(B, Cn, L))   # [B][C/16][L][C%16] -> [B][C][L]
+        return unblock(hi), (unblock(lo) if lo is not None else None)
 
     # ---- device-pointer API (raw addresses; stream = hipStream_t as int, 0 = handle's own stream)
     def encode_dev(self, pcm_ptr: int, B: int, T: int, codes_ptr: int, stream: int = 0) -> None:

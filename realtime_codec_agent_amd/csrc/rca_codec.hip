@@ -2906,7 +2906,10 @@ static bool bf16_blk_ok(const rca_codec* h, int tap_layer) {
         if (!bf16_blk_layer_ok(h->enc[li], li + 1 == n)) return false;
     return true;
 }
-static int run_encoder_bf16(rca_codec* h, RowSrc src, int B, int Tp, size_t max_elems, hipStream_t st, float** ze_out, int tap_layer, float* tap_dev) {
+// bf16_tap >= 0 (rca_codec_encode_tap_bf16, tests only): the same launches up to and including layer bf16_tap, then stop and leave
+// that layer's stored planes (hi, lo) in bf16_planes[0..1] instead of running the rest of the stack.
+static int run_encoder_bf16(rca_codec* h, RowSrc src, int B, int Tp, size_t max_elems, hipStream_t st, float** ze_out, int tap_layer, float* tap_dev,
+                            int bf16_tap = -1, const conv_bf16raw** bf16_planes = nullptr) {
     const bool split = h->mfma_mode == 3;
     const float slope = h->cfg.leaky_slope;
     const size_t n = h->enc.size();
@@ -2931,6 +2934,14 @@ static int run_encoder_bf16(rca_codec* h, RowSrc src, int B, int Tp, size_t max_
     const double esz = split ? 4.0 : 2.0;
     int cur = 0, L = Tp;
     const bool fuse_in = h->enc[1].k == 4 && h->enc[1].s == 2 && h->enc[0].cout == 32 && !getenv("RCA_BF16_NO_FUSE_IN");
+    if (bf16_tap >= 0 && (bf16_tap + 1 >= (int)n || (bf16_tap == 0 && fuse_in)))
+        return fail(RCA_ERR_ARG, "bf16 tap: layer %d is not materialised (conv_in fused: %d, last layer: %d, f32)", bf16_tap, (int)fuse_in, (int)n - 1);
+    auto stop_at = [&](int li) {
+        if (li != bf16_tap) return false;
+        bf16_planes[0] = hi_of(cur);
+        bf16_planes[1] = lo_of(cur);
+        return true;
+    };
     if (!fuse_in) {
         const ConvLayer& L0 = h->enc[0];
         const long total = (long)B * L;
@@ -2939,6 +2950,7 @@ static int run_encoder_bf16(rca_codec* h, RowSrc src, int B, int Tp, size_t max_
         if (split) conv_in_blk_kernel<7, 1><<<dim3(cdiv(L, 256), B), 256, 0, st>>>(src, h->bf16_packs[0].w_in8, L0.b, hi_of(cur), lo_of(cur), B, L0.cout, L, act, slope);
         else conv_in_blk_kernel<7, 0><<<dim3(cdiv(L, 256), B), 256, 0, st>>>(src, h->bf16_packs[0].w_in8, L0.b, hi_of(cur), lo_of(cur), B, L0.cout, L, act, slope);
         RCA_LAUNCH_CHECK();
+        if (stop_at(0)) return RCA_OK;
     }
     for (size_t li = 1; li < n; ++li) {
         const ConvLayer& Ly = h->enc[li];
@@ -2968,6 +2980,7 @@ static int run_encoder_bf16(rca_codec* h, RowSrc src, int B, int Tp, size_t max_
         L = Lout;
         cur ^= 1;
         if (last && tap_layer == (int)li) RCA_HIP(hipMemcpyAsync(tap_dev, yf, (size_t)B * Ly.cout * L * 4, hipMemcpyDeviceToDevice, st));
+        if (stop_at((int)li)) return RCA_OK;
     }
     *ze_out = h->act[cur].as<float>();
     return RCA_OK;
@@ -2975,7 +2988,9 @@ static int run_encoder_bf16(rca_codec* h, RowSrc src, int B, int Tp, size_t max_
 
 // encoder stack: rows described by src -> ze [B][D][F] left in *ze_out (a workspace buffer).
 // tap_layer >= 0 copies that layer's output (device->device) into tap_dev.
-static int run_encoder(rca_codec* h, RowSrc src, int B, hipStream_t st, float** ze_out, int* F_out, int tap_layer, float* tap_dev) {
+// bf16_tap >= 0: see run_encoder_bf16; RCA_ERR_ARG when this call would not take the blocked bf16 pipeline.
+static int run_encoder(rca_codec* h, RowSrc src, int B, hipStream_t st, float** ze_out, int* F_out, int tap_layer, float* tap_dev,
+                       int bf16_tap = -1, const conv_bf16raw** bf16_planes = nullptr) {
     const rca_codec_config_t& c = h->cfg;
     const int F = (src.T + h->hop - 1) / h->hop;
     const int Tp = F * h->hop;
@@ -2992,8 +3007,9 @@ static int run_encoder(rca_codec* h, RowSrc src, int B, hipStream_t st, float** 
     if ((rc = h->act[1].ensure(max_elems * 4)) != RCA_OK) return rc;
     if (bf16_blk_ok(h, tap_layer) && (double)B * max_elems < 4.0e18 && Tp / h->enc[1].s >= 64) {   // opt-in bf16 modes: the blocked pipeline
         *F_out = F;
-        return run_encoder_bf16(h, src, B, Tp, max_elems, st, ze_out, tap_layer, tap_dev);
+        return run_encoder_bf16(h, src, B, Tp, max_elems, st, ze_out, tap_layer, tap_dev, bf16_tap, bf16_planes);
     }
+    if (bf16_tap >= 0) return fail(RCA_ERR_ARG, "bf16 tap: encode() does not take the blocked bf16 pipeline here (mfma mode %d, B=%d T=%d)", h->mfma_mode, B, src.T);
     int cur = 0;
     int L = Tp;
     size_t first = 1;
@@ -3220,6 +3236,33 @@ extern "C" int rca_codec_encode_tap(rca_codec_t* h, const float* pcm_host, int32
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "tap sync: %s", hipGetErrorString(e));
     }
     RCA_HIP(hipMemcpyAsync(out_host, h->io_b.p, (size_t)out_numel * 4, hipMemcpyDeviceToHost, h->stream));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    return RCA_OK;
+}
+
+extern "C" int rca_codec_encode_tap_bf16(rca_codec_t* h, const float* pcm_host, int32_t B, int32_t T, int32_t layer, uint16_t* hi_host,
+                                         uint16_t* lo_host, int64_t numel) {
+    if (!h || !pcm_host || !hi_host || B < 1 || T < 1) return fail(RCA_ERR_ARG, "bf16 tap: bad argument");
+    RCA_HIP(hipSetDevice(h->device));
+    const int n = h->cfg.n_stages;
+    if (layer < 0 || layer > n) return fail(RCA_ERR_ARG, "bf16 tap: layer %d out of range", layer);
+    {
+        long L = (long)((T + h->hop - 1) / h->hop) * h->hop;
+        for (int i = 0; i < layer; ++i) L /= h->cfg.strides[i];
+        const long want = (long)B * h->cfg.channels[layer] * L;
+        if (want != numel) return fail(RCA_ERR_ARG, "bf16 tap: numel %ld, expected %ld", (long)numel, want);
+    }
+    int rc;
+    if ((rc = h->io_a.ensure((size_t)B * T * 4)) != RCA_OK) return rc;
+    RCA_HIP(hipMemcpyAsync(h->io_a.p, pcm_host, (size_t)B * T * 4, hipMemcpyHostToDevice, h->stream));
+    RowSrc src{h->io_a.as<float>(), B, (long)T, 0, T};
+    (void)pick_stream(h, h->stream);
+    float* ze; int F;
+    const conv_bf16raw* planes[2] = {nullptr, nullptr};
+    if ((rc = run_encoder(h, src, B, h->stream, &ze, &F, -1, nullptr, layer, planes)) != RCA_OK) return rc;
+    // X[b][c / 16][t][c % 16], as stored
+    RCA_HIP(hipMemcpyAsync(hi_host, planes[0], (size_t)numel * 2, hipMemcpyDeviceToHost, h->stream));
+    if (h->mfma_mode == 3 && lo_host) RCA_HIP(hipMemcpyAsync(lo_host, planes[1], (size_t)numel * 2, hipMemcpyDeviceToHost, h->stream));
     RCA_HIP(hipStreamSynchronize(h->stream));
     return RCA_OK;
 }
