@@ -409,6 +409,9 @@ int rca_lm_set_graphs(rca_lm_t* h, int32_t enable);
  * :725-733) run as 128-token tiles on bf16 MFMA with hi/lo-split activations (default; logits within ~1e-3 of the
  * decode path); 0 routes them through the 8-token GEMV chunks, which are bit-identical to decode */
 int rca_lm_set_mfma_prefill(rca_lm_t* h, int32_t enable);
+/* Tests only: the route rca_lm_eval takes for an eval of more than LM_PREFILL_MIN tokens with the
+ * current settings: 0 = 8-token GEMV chunks, 1 = 32-token tiles, 2 = 128-token tiles. */
+int rca_lm_prefill_route(const rca_lm_t* h, int32_t* route);
 /* the format the projection matrices are kept and streamed in (0 bf16, 1 q8_0, 2 f16, 3 q4_k) and, optionally, the weight bytes one decode
  * step reads (llama.cpp prints the same two facts at load: file type and model size) */
 int rca_lm_weight_format(const rca_lm_t* h, int32_t* fmt, int64_t* bytes_per_step);

@@ -4116,6 +4116,14 @@ static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_
     return RCA_OK;
 }
 
+// The route of an eval of more than LM_PREFILL_MIN tokens (and of every rca_lm_eval_async piece) with the handle's current settings:
+// the one place that decides it -- lm_eval_impl branches on it and rca_lm_prefill_route reports it to the tests.
+enum { LM_ROUTE_GEMV = 0, LM_ROUTE_TILE32 = 1, LM_ROUTE_TILE128 = 2 };
+static int lm_prefill_route(const rca_lm* h) {
+    if (h->cfg.logits_all != 0 || !h->mfma_prefill || !lm_can_mfma_prefill(h)) return LM_ROUTE_GEMV;
+    return lm_can_gemm128(h) ? LM_ROUTE_TILE128 : LM_ROUTE_TILE32;
+}
+
 // an rca_lm_eval_async pass may still own the pinned staging block and the activations: wait for it before anything else runs
 static int lm_settle(rca_lm* h) {
     if (h->async_pending) {
@@ -4182,9 +4190,10 @@ static int lm_eval_impl(rca_lm_t* h, const int32_t* ids, int32_t n, bool wait_la
         if ((rc = lm_alloc((void**)&h->logits, (size_t)n * h->cfg.vocab_size * 4)) != RCA_OK) return rc;
     }
     float* logits_base = h->logits;
-    if (!all && (n > LM_PREFILL_MIN || as_prefill) && h->mfma_prefill && lm_can_mfma_prefill(h)) {
+    const int route = lm_prefill_route(h);
+    if ((n > LM_PREFILL_MIN || as_prefill) && route != LM_ROUTE_GEMV) {
         // long evals (session prefill, recompute_kv_cache): 32-token tiles on the bf16 MFMA path
-        const bool big = lm_can_gemm128(h);
+        const bool big = route == LM_ROUTE_TILE128;
         const int tile = big ? LM_MAXM : LM_TILE32;
         // A background tile (rca_lm_eval_async of one pass: kv_shadow.py feeds one per few frames) is ~230 launches; issued eagerly
         // they cost the calling frame ~2 ms of host time before its own replay is even launched (tile frames 9.5 ms against a median
@@ -5134,6 +5143,13 @@ extern "C" int rca_lm_weight_format(const rca_lm_t* h, int32_t* fmt, int64_t* by
         for (const LmLayer& L : h->layers) b += L.qkv.stream_bytes() + L.o.stream_bytes() + L.gu.stream_bytes() + L.down.stream_bytes() + (L.split_v ? L.vseg.stream_bytes() : 0);
         *bytes_per_step = b;
     }
+    return RCA_OK;
+}
+
+// tests only: which of the three prefill routes a long eval takes right now (lm_prefill_route, the predicate lm_eval_impl branches on)
+extern "C" int rca_lm_prefill_route(const rca_lm_t* h, int32_t* route) {
+    if (!h || !route) return fail(RCA_ERR_ARG, "null");
+    *route = lm_prefill_route(h);
     return RCA_OK;
 }
 

@@ -620,6 +620,13 @@ class LlamaForAlternatingCodeChannels:
         N.check(self._lib.rca_lm_set_mfma_prefill(self._h, 1 if enable else 0), "rca_lm_set_mfma_prefill")
         self._mfma_prefill = bool(enable)
 
+    def prefill_route(self) -> str:
+        """Tests only: the route an eval of more than 8 tokens takes with the current settings: "gemv" (the exact GEMV chunks),
+        "tile32" (32-token bf16 MFMA tiles) or "gemm128" (128-token tiles)."""
+        r = C.c_int32()
+        N.check(self._lib.rca_lm_prefill_route(self._h, C.byref(r)), "rca_lm_prefill_route")
+        return ("gemv", "tile32", "gemm128")[r.value]
+
     def set_attn_fuse(self, enable: bool) -> None:
         """Merge the attention splits inside the attention launch (default) or in a launch of its own."""
         N.check(self._lib.rca_lm_set_attn_fuse(self._h, 1 if enable else 0), "rca_lm_set_attn_fuse")
