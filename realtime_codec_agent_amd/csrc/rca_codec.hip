@@ -327,6 +327,12 @@ __device__ __forceinline__ void conv_split8(const float (&w)[8], uint4& hi, uint
 // FULLC = 1 (chosen by the launcher when Cin is a multiple of the chunk -- every layer of the encoder): no channel of any chunk lies
 // past Cin, so the per-channel choice between the input descriptor and the empty one (4 s_cselect + a compare per channel and
 // chunk: 40-60 scalar instructions of a ~150-instruction staging phase) is gone.  Same loads, same values.
+// Row geometry (plain convolution, not FUSE / TR): the two sides of a row are separate arguments.  `Lin` is only the LAYOUT of x -- channel
+// stride Lin, batch-row stride Cin * Lin, used for the descriptor base and the load offsets -- while `Lout` is the LOGICAL row: a
+// row has Lout columns, column t reads x[b][ci][t * S - padL + kk] from the pointer handed in, and taps left of column 0 / right of
+// column Lout - 1 are zero.  A launch over a window of every row (run_conv's `view`) therefore passes x advanced to the window's
+// first sample, the full Lin and the window's column count; y is stored compact, [B][Cout][Lout].  Nothing in the chunk loop depends
+// on which of the two it is.
 template <int KS, int S, int CIC, int WM, int WN, int FUSE, int TR, int BF = 0, int FULLC = 0>
 __global__ __launch_bounds__(64 * RCA_CONV_WPB, (((KS == 8 && CIC == 2) || (KS == 16 && CIC == 1)) && WM * WN < 8) ? 3 : RCA_CONV_OCC) void conv1d_mfma_kernel(const float* __restrict__ x, const float* __restrict__ wp,
                                                           const float* __restrict__ bias, float* __restrict__ y,
@@ -2790,12 +2796,29 @@ static bool mfma_conv_ok(const rca_codec* h, const ConvLayer& L, int B, int Lin,
     return (double)L.cin * Lin < 2.6e8 && (double)L.cout * Lin < 2.6e8 && (double)B * L.cin * Lin < 4.0e9 && (double)B * Lout < 2.0e9;
 }
 
+// true when run_conv can run this layer over a view of `view` columns per row: the f32 conv1d_mfma_kernel of the default variant,
+// nothing else.  A wave's window of at most 66 columns then spans 66 / view + 2 batch rows of x instead of two, all addressed with
+// 31-bit byte offsets from the first of them.
+static bool conv_view_ok(const rca_codec* h, const ConvLayer& L, int B, int Lin, int view) {
+    return h->variant == 1 && !h->lat_mode && h->mfma_mode == 0 && mfma_conv_ok(h, L, B, Lin, 0) &&
+           (66.0 / view + 2.0) * (double)L.cin * Lin < 5.2e8;
+}
+// Columns at the left of a view that a caller must ask for and skip: the view's left edge is not a signal edge, so the columns whose
+// taps reach across it are padded with zeros where the full launch reads samples.
+static int conv_view_halo(const ConvLayer& L) {
+    const int padL = (L.k - L.s + 1) / 2;   // input samples a column reaches to its left
+    return (padL + L.s - 1) / L.s;          // ... in output columns
+}
+
 // in_activated: x already holds LeakyReLU(x) (the producer applied this layer's pre-activation); want_post: store
 // LeakyReLU(y) if the kernel that runs can (then *post_done = true and the consumer must be told its input is activated)
+// view > 0 (see conv_view_ok): only the last `view` output columns of every row are computed and y is stored compact,
+// [B][Cout][view].  The view's right edge is the row's, so the zero padding there is the full launch's.
 static int run_conv(rca_codec* h, const ConvLayer& L, const float* x, float* y, int B, int Lin, int clamp_out, hipStream_t st,
-                    bool in_activated = false, bool want_post = false, bool* post_done = nullptr) {
+                    bool in_activated = false, bool want_post = false, bool* post_done = nullptr, int view = 0) {
     const float slope = h->cfg.leaky_slope;
     if (post_done) *post_done = false;
+    if (view > 0 && !conv_view_ok(h, L, B, Lin, view)) return fail(RCA_ERR_ARG, "internal: column view handed to a kernel without that mode");
     if (in_activated && !(h->variant == 1 && !h->lat_mode && mfma_conv_ok(h, L, B, Lin, clamp_out)))
         return fail(RCA_ERR_ARG, "internal: activated input handed to a kernel without that mode");
     if (h->lat_mode && try_conv_lds(h, L, x, (long)L.cin * Lin, Lin, y, B, Lin, clamp_out, st)) {
@@ -2816,6 +2839,30 @@ static int run_conv(rca_codec* h, const ConvLayer& L, const float* x, float* y, 
     const double cflops = 2.0 * L.cin * L.k * L.cout * (double)B * Lout;
     const double cbytes = 4.0 * ((double)B * L.cin * Lin + (double)B * L.cout * Lout + (double)L.cin * L.k * L.cout);
     // the MFMA kernel indexes the input with 32-bit element offsets
+    if (view > 0 && view < Lout) {
+        // the launch is profiled with what it executes: `view` columns per row and the input samples under them
+        const int Lv = view;
+        const double vin = std::min((double)Lin, (double)Lv * L.s + L.k - L.s);
+        ProfScope ps(h, st, 0, 2.0 * L.cin * L.k * L.cout * (double)B * Lv,
+                     4.0 * ((double)B * L.cin * vin + (double)B * L.cout * Lv + (double)L.cin * L.k * L.cout));
+        const float* xv = x + (long)(Lout - Lv) * L.s;
+        const int act = ((L.pre && !in_activated) ? 1 : 0) | (want_post ? 2 : 0);
+        if (post_done) *post_done = want_post;
+        if (L.k == 4 && L.s == 2) return launch_conv_mfma<4, 2, 4>(L, xv, y, B, Lin, Lv, slope, st, nullptr, act, 0);
+        if (L.k == 8 && L.s == 4) return launch_conv_mfma<8, 4, RCA_CIC_K8>(L, xv, y, B, Lin, Lv, slope, st, nullptr, act, 0);
+        if (L.k == 10 && L.s == 5) return launch_conv_mfma<10, 5, 4>(L, xv, y, B, Lin, Lv, slope, st, nullptr, act, 0);
+        if (L.k == 16 && L.s == 8) return launch_conv_mfma<16, 8, RCA_CIC_K16>(L, xv, y, B, Lin, Lv, slope, st, nullptr, act, 0);
+        // A view of a few columns per row is a small launch: at most one wave of 32 x 32 per SIMD (the headline's 256 x 6 columns:
+        // 384 waves on 1024 SIMDs), each a dependent chain of Cin * k / 2 MFMAs that nothing but its own depth keeps fed.
+        // 16 channels per chunk instead of RCA_CIC_K3 = 8 (same packed weights, same k order): 44 vs 52 us on the headline's
+        // launch; 32 per chunk measured 49 us.  (On the full-length launch 16 per chunk loses: profiles/r04/experiments/conv_k3_chunk16.txt.)
+        if ((long)cdiv((long)B * Lv, 32) * cdiv(L.cout, 32) <= 1024 && L.cin % 16 == 0) {
+            launch_conv_cfg<3, 1, 16, 1, 1, 0, 0>(L, L.wp, L.cin / 16, xv, y, Lin, Lv, (long)B * Lv, slope, FuseIn{}, TrInfo{}, st, act);
+            RCA_LAUNCH_CHECK();
+            return RCA_OK;
+        }
+        return launch_conv_mfma<3, 1, RCA_CIC_K3>(L, xv, y, B, Lin, Lv, slope, st, nullptr, act, 0);
+    }
     if (mfma_conv_ok(h, L, B, Lin, clamp_out)) {
         ProfScope ps(h, st, 0, cflops, cbytes);
         if (h->variant == 2 && try_conv_ws(L, x, y, B, Lin, Lout, slope, st, nullptr)) { RCA_LAUNCH_CHECK(); return RCA_OK; }
@@ -2989,12 +3036,19 @@ static int run_encoder_bf16(rca_codec* h, RowSrc src, int B, int Tp, size_t max_
 // encoder stack: rows described by src -> ze [B][D][F] left in *ze_out (a workspace buffer).
 // tap_layer >= 0 copies that layer's output (device->device) into tap_dev.
 // bf16_tap >= 0: see run_encoder_bf16; RCA_ERR_ARG when this call would not take the blocked bf16 pipeline.
+// keep: the number of trailing frames of every row the caller will read (<= 0 or >= F: all of them).  The LAST layer is evaluated
+// where it is read: with 0 < keep < F, and no layer tapped, it runs over the last keep + halo columns of every row only (run_conv's
+// view) and ze is [B][D][*Fz_out] with the kept frames at its end; every earlier layer still sees the whole window at every
+// position, so nothing is assumed about how far back the encoder looks (that is the window trim, which stays opt-in).  *Fz_out = F
+// otherwise.  Streaming tails, the scalar chain, variant 2 and the bf16 modes compute all frames.  RCA_HEAD_KEEP=0 (read per
+// call) brings the full-length last layer back (A/B, tests).
 static int run_encoder(rca_codec* h, RowSrc src, int B, hipStream_t st, float** ze_out, int* F_out, int tap_layer, float* tap_dev,
-                       int bf16_tap = -1, const conv_bf16raw** bf16_planes = nullptr) {
+                       int bf16_tap = -1, const conv_bf16raw** bf16_planes = nullptr, int keep = 0, int* Fz_out = nullptr) {
     const rca_codec_config_t& c = h->cfg;
     const int F = (src.T + h->hop - 1) / h->hop;
     const int Tp = F * h->hop;
     if (F < 1) return fail(RCA_ERR_ARG, "empty audio (T=%d)", src.T);
+    if (Fz_out) *Fz_out = F;
     size_t max_elems = 0;
     {
         long L = Tp;
@@ -3067,7 +3121,14 @@ static int run_encoder(rca_codec* h, RowSrc src, int B, hipStream_t st, float** 
         float* x = h->act[cur].as<float>();
         float* y = h->act[cur ^ 1].as<float>();
         bool done = false;
-        if ((rc = run_conv(h, Ly, x, y, B, L, 0, st, prev_post, handoff(li + 1, L / Ly.s), &done)) != RCA_OK) return rc;
+        int view = 0;
+        if (li + 1 == h->enc.size() && Fz_out && keep > 0 && tap_layer < 0 && !Ly.tr) {
+            const char* hk = getenv("RCA_HEAD_KEEP");
+            const int want = keep + conv_view_halo(Ly);
+            if (!(hk && hk[0] == '0') && want < L / Ly.s && conv_view_ok(h, Ly, B, L, want)) view = want;   // short windows take the whole row
+        }
+        if ((rc = run_conv(h, Ly, x, y, B, L, 0, st, prev_post, handoff(li + 1, L / Ly.s), &done, view)) != RCA_OK) return rc;
+        if (view) *Fz_out = view;
         prev_post = done;
         L /= Ly.s;
         cur ^= 1;
@@ -3167,11 +3228,12 @@ extern "C" int rca_codec_encode_tail_dev(rca_codec_t* h, const float* pcm, int32
     float* ze; int Ft, rc;
     // a handful of frames: the chains, not the FLOPs, set the time -> LDS-staged scalar-chain kernels (same bits)
     h->lat_mode = h->variant >= 1 && (long)B * (F - j) <= RCA_LAT_MAX_FRAMES;
-    rc = run_encoder(h, src, B, st, &ze, &Ft, -1, nullptr);
+    int Fz;
+    rc = run_encoder(h, src, B, st, &ze, &Ft, -1, nullptr, -1, nullptr, n_keep, &Fz);
     h->lat_mode = false;
     if (rc != RCA_OK) return rc;
     RowDst dst{codes, B, (long)n_keep, 0, n_keep};
-    return run_quantize(h, ze, 0, B, Ft, Ft - n_keep, n_keep, dst, st, nullptr);
+    return run_quantize(h, ze, 0, B, Fz, Fz - n_keep, n_keep, dst, st, nullptr);
 }
 
 extern "C" int rca_codec_receptive_field(const rca_codec_t* h, int32_t* enc_left_frames, int32_t* dec_left_frames) {
@@ -3293,11 +3355,11 @@ extern "C" int rca_codec_encode_chunk_range_dev(rca_codec_t* h, const float* aud
         const int jw = h->window_trim ? trimmable_frames(h, (Tfull + h->hop - 1) / h->hop, fpc) : 0;
         const int T = Tfull - jw * h->hop;
         RowSrc src{audio + (long)jw * h->hop, C, (long)N, 0, T};
-        float* ze; int F;
-        if ((rc = run_encoder(h, src, C, st, &ze, &F, -1, nullptr)) != RCA_OK) return rc;
+        float* ze; int F, Fz;
+        if ((rc = run_encoder(h, src, C, st, &ze, &F, -1, nullptr, -1, nullptr, fpc, &Fz)) != RCA_OK) return rc;
         if (F < fpc) return fail(RCA_ERR_STATE, "window of %d samples has %d frames < %d kept", T, F, fpc);
         RowDst dst{codes + (i - chunk_begin) * fpc, C, (long)codes_per_channel, 0, fpc};
-        if ((rc = run_quantize(h, ze, 0, C, F, F - fpc, fpc, dst, st, nullptr)) != RCA_OK) return rc;
+        if ((rc = run_quantize(h, ze, 0, C, Fz, Fz - fpc, fpc, dst, st, nullptr)) != RCA_OK) return rc;
     }
     // steady state: full windows [end - W, end), batch_windows rows (window x channel) per pass
     const int wins_per_pass = std::max(1, batch_windows / C);
@@ -3307,11 +3369,11 @@ extern "C" int rca_codec_encode_chunk_range_dev(rca_codec_t* h, const float* aud
         const int jw = h->window_trim ? trimmable_frames(h, (W + h->hop - 1) / h->hop, fpc) : 0;
         const long start0 = (i + 1) * (long)chunk - W + (long)jw * h->hop;
         RowSrc src{audio + start0, C, (long)N, (long)chunk, W - jw * h->hop};
-        float* ze; int F;
-        if ((rc = run_encoder(h, src, nw * C, st, &ze, &F, -1, nullptr)) != RCA_OK) return rc;
+        float* ze; int F, Fz;
+        if ((rc = run_encoder(h, src, nw * C, st, &ze, &F, -1, nullptr, -1, nullptr, fpc, &Fz)) != RCA_OK) return rc;
         if (F < fpc) return fail(RCA_ERR_STATE, "window has %d frames < %d kept", F, fpc);
         RowDst dst{codes + (i - chunk_begin) * fpc, C, (long)codes_per_channel, (long)fpc, fpc};
-        if ((rc = run_quantize(h, ze, 0, nw * C, F, F - fpc, fpc, dst, st, nullptr)) != RCA_OK) return rc;
+        if ((rc = run_quantize(h, ze, 0, nw * C, Fz, Fz - fpc, fpc, dst, st, nullptr)) != RCA_OK) return rc;
         i += nw;
     }
     return RCA_OK;
@@ -3338,11 +3400,11 @@ extern "C" int rca_codec_encode_rows_dev(rca_codec_t* h, const float* audio, con
     if (Ffull < n_keep) return fail(RCA_ERR_ARG, "encode_rows: a window of %d samples has %d frames < %d kept", T, Ffull, n_keep);
     const int jw = h->window_trim ? trimmable_frames(h, Ffull, n_keep) : 0;
     RowSrc src{audio + (long)jw * h->hop, B, 0, 0, T - jw * h->hop, reinterpret_cast<const long*>(src_off), (long)span};
-    float* ze; int F;
+    float* ze; int F, Fz;
     int rc;
-    if ((rc = run_encoder(h, src, B, st, &ze, &F, -1, nullptr)) != RCA_OK) return rc;
+    if ((rc = run_encoder(h, src, B, st, &ze, &F, -1, nullptr, -1, nullptr, n_keep, &Fz)) != RCA_OK) return rc;
     RowDst dst{codes, B, 0, 0, n_keep, reinterpret_cast<const long*>(dst_off)};
-    return run_quantize(h, ze, 0, B, F, F - n_keep, n_keep, dst, st, nullptr);
+    return run_quantize(h, ze, 0, B, Fz, Fz - n_keep, n_keep, dst, st, nullptr);
 }
 
 extern "C" int rca_codec_encoder_dev(rca_codec_t* h, const float* pcm, int32_t B, int32_t T, float* ze_out, void* stream) {
