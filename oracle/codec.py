@@ -145,6 +145,21 @@ class OracleCodec:
             return (B * F, cfg.codebook_dim)
         raise ValueError(layer)
 
+    def quantize_rows(self, ze_rows: np.ndarray) -> np.ndarray:
+        """quantizer.inference on rows [R][latent_dim] -> int64[R]: in_proj, then the first maximum of the score chain.
+        The bit-exact twin of rca_codec_quantize_dev."""
+        ze_rows = np.ascontiguousarray(ze_rows, dtype=np.float32)
+        assert ze_rows.ndim == 2 and ze_rows.shape[1] == self.cfg.latent_dim
+        R, J = ze_rows.shape[0], self.cfg.codebook_dim
+        z = np.empty((R, J), np.float32)
+        codes = np.empty((R,), np.int64)
+        w = self._wstruct
+        L = lib()
+        L.oracle_linear(_fp(ze_rows), C.c_long(R), C.c_int(self.cfg.latent_dim), w.q_in_w, w.q_in_b, C.c_int(J), _fp(z))
+        L.oracle_vq_argmax(_fp(z), C.c_long(R), _fp(self.cb), _fp(self.hc), C.c_int(self.cfg.codebook_size), C.c_int(J),
+                           codes.ctypes.data_as(C.POINTER(C.c_int64)))
+        return codes
+
     def decode(self, codes: np.ndarray) -> np.ndarray:
         codes = np.ascontiguousarray(codes, dtype=np.int64)
         assert codes.ndim == 2

@@ -1672,8 +1672,10 @@ __global__ __launch_bounds__(256) void codebook_norm_pack_kernel(const float* __
     }
 }
 
+// Once per frame and lane, after the code loop.  s + 0.0f turns -0.0 into +0.0 and changes no other value: the keys are
+// compared as bit patterns, where +0.0 would outrank the -0.0 that the float compare (and the oracle) call equal.
 __device__ __forceinline__ unsigned long long pack_key(float s, unsigned idx) {
-    unsigned u = __float_as_uint(s);
+    unsigned u = __float_as_uint(s + 0.0f);
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone float -> uint
     return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - idx);  // ties -> lower idx wins
 }
@@ -1799,7 +1801,9 @@ __global__ __launch_bounds__(256) void vq_mfma_kernel(const float* __restrict__ 
     }
 }
 
-// keys -> int64 codes with the output mapping of RowDst; also re-arms keys for the next call
+// keys -> int64 codes with the output mapping of RowDst; also re-arms keys for the next call.
+// An empty key (0: no score of the frame compared greater than -inf, i.e. every score NaN or -inf) gives code 0,
+// the oracle's answer, never the out-of-range 0xFFFFFFFF.
 struct RowDst {
     int64_t* base;
     int C;            // rows are (win, chan): chan = row_b % C, win = row_b / C
@@ -1816,7 +1820,7 @@ __global__ __launch_bounds__(256) void vq_finalize_kernel(unsigned long long* __
     const long b = i / dst.fc;
     const int j = (int)(i - b * dst.fc);
     dst.base[(dst.row_off ? dst.row_off[b] : (b % dst.C) * dst.chan_stride + (b / dst.C) * dst.win_stride) + j] =
-        (int64_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+        key == 0ull ? (int64_t)0 : (int64_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
 }
 
 // zq[b][j][f] = cb[codes[b][f]][j]

@@ -77,6 +77,10 @@ def test_decode_bit_exact(tag, hip_tiny, hip_full, tiny_oracle, full_oracle):
         want = oc.decode(codes)
         got = hip.decode(codes)
         assert np.array_equal(got, want), (F, B, np.abs(got - want).max())
+    last = oc.cfg.codebook_size - 1      # the two ends of the codebook: all first, all last, alternating
+    codes = np.stack([np.zeros(6, np.int64), np.full(6, last, np.int64), np.tile(np.array([0, last], np.int64), 3)])
+    got, want = hip.decode(codes), oc.decode(codes)
+    assert np.array_equal(got, want), np.abs(got - want).max()
     assert np.abs(rec).max() <= 1.0
 
 
