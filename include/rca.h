@@ -418,6 +418,28 @@ int rca_lm_weight_format(const rca_lm_t* h, int32_t* fmt, int64_t* bytes_per_ste
 /* decode steps merge the attention splits inside the attention launch (1, default: the workgroup that publishes its partial last
  * merges them; bit-identical to the separate merge launch) or in a launch of its own (0); tests compare the two */
 int rca_lm_set_attn_fuse(rca_lm_t* h, int32_t enable);
+/* activation format of the decode GEMVs over quantised matrices: 0 = f32 (default), 1 = q8_1 blocks + integer dot products
+ * (llama.cpp's GPU mat-vec class).  RCA_ERR_ARG for another value or when no projection matrix of the handle is q8_0 / Q4_K / Q6_K.
+ * Drops captured graphs when the value changes.  Per handle; rca_lm_create_shared copies the parent's value.
+ * q8_1: a row of K activations is cut into blocks of 32 consecutive values; per block d = amax / 127, inv = d != 0 ? 1 / d : 0 (IEEE
+ * division), q_j = roundf(x_j * inv) (ties away from zero) as int8, scale used d_x = (float)(fp16 rne of d); an all-zero block is
+ * q = 0, d = 0.  This is ggml's quantize_row_q8_1 restated from the published algorithm (ggml is not part of this tree: parity with
+ * llama.cpp's own bits is not pinned).  Per block a weight row contributes
+ *   q8_0: (d_w d_x) sum q_w q_x      Q6_K: d_x (s_w0 sum_first16 q_w q_x + s_w1 sum_second16 q_w q_x)
+ *   Q4_K: d_x ((d sc_b) sum q_w q_x - (dmin m_b) sum q_x)
+ * with exact integer sums (v_dot4c_i32_i8 over a lane's 8 values); scaling and the sums across chunks, lanes and waves are f32 in
+ * the order of the f32 path.  Matrices kept in bf16 / f16 and the MFMA prefill tiles keep f32 activations; the exact prefill
+ * route (rca_lm_set_mfma_prefill(0), evals of up to 8 tokens) is made of decode GEMV passes and follows the mode. */
+int rca_lm_set_act_format(rca_lm_t* h, int32_t fmt);
+int rca_lm_get_act_format(const rca_lm_t* h, int32_t* fmt);
+/* Tests only: ONE decode GEMV stage exactly as the step launches it (same instance, geometry and current activation format) on a
+ * host-supplied input.  kind 0 QKV (x = residual rows [M][hidden]; y = the q rows after RoPE [M][n_heads*64]; kv_host, if not NULL,
+ * receives the M new K rows then the M new V rows of `layer`'s cache as raw fp16), 1 O (x [M][AO]), 2 gate/up (y = silu(g)*u [M][ffn]),
+ * 3 down (x [M][ffn]), 4 head (layer ignored; y [M][V]).  For the residual-add stages (1, 3) the residual is zeroed first, so y is
+ * the product alone.  Positions are n_tokens .. n_tokens+M-1; n_tokens is left as it was.  M is 1 or 2.  The handle's activation
+ * buffers and the cache rows at those positions are overwritten. */
+int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const float* x_host, int32_t M, float* y_host, int64_t y_numel,
+                    uint16_t* kv_host);
 /* synchronise the handle's stream (timing) */
 int rca_lm_sync(rca_lm_t* h);
 int rca_codec_sync(rca_codec_t* h);

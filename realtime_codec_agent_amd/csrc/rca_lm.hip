@@ -313,7 +313,8 @@ __device__ __forceinline__ void wave_reduce_transposed(float (&val)[V]) {
 // the same 8 k (one 16-byte lane load feeds two rows with the x values the lane already holds), scales sc[k / 32][pair] =
 // (fp16, fp16) so a lane fetches the scales of a whole batch with one or two vector loads.  Arithmetic per lane and row:
 // p = fma chain of (float)q_j * x_j over its 8 elements, then d * p accumulated per chunk -- f32 activations throughout
-// (llama.cpp quantises the activations to q8_1 for this product; here only the weights are quantised).
+// (llama.cpp quantises the activations to q8_1 for this product; by default only the weights are quantised here, and the opt-in
+// ACT = 1 instances of lm_gemv_kernel do what llama.cpp does).
 // (float)(int8) of byte `b` of a dword.  The dword must have passed through q8_opaque() first:
 //   * if the optimiser can see that a loaded 16-byte value is only ever used byte by byte, it re-types the LOAD as sixteen byte
 //     values and unpacks them the moment it lands -- 4x the registers and nothing left in flight;
@@ -368,7 +369,16 @@ __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, lon
 // minimum waves per SIMD asked of the register allocator.  The q8_0 bodies otherwise spread over 200+ registers (one wave per
 // SIMD) although their live set is ~130: a streaming kernel wants the occupancy.
 constexpr int gemv_min_waves(int Q, int R, int NIT) { return (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K) ? 1 : (R * NIT >= 16 ? 2 : 4); }
-template <int M, int NIT, int R, int PRO, int EPI, int Q = 0>
+// ACT = 1 (rca_lm_set_act_format, packed formats only): the activations are quantised to q8_1 blocks -- 32 consecutive values, int8 +
+// one scale, ggml's quantize_row_q8_1 restated: d = amax / 127, inv = d != 0 ? 1 / d : 0 (IEEE division), q = roundf(x * inv), scale used
+// d_x = (float)(fp16 rne of d) -- and the products run on the signed byte dot (v_dot4c_i32_i8), llama.cpp's GPU mat-vec class:
+//   q8_0:  val = fma(d_w * d_x, (float)sum q_w q_x, val)            Q6_K: the same with the f32 scale of the group of 16 for d_w
+//   Q4_K:  val = fma(d1 * d_x, (float)sum q_w q_x, val); val = fma(-m1, d_x * (float)sum q_x, val)    (d1 = d * sc, m1 = dmin * m, exact)
+// per 8-value chunk of the lane; the integer sums are exact, everything after them is the f32 reduction of the f32 path.  The
+// quantiser runs INSIDE the GEMV (after the RMSNorm with PRO 1), once per workgroup, on the 8 * NIT * M values the lane holds anyway:
+// the four chunks of a block sit in four consecutive lanes of one `it`, so amax is two quad DPP exchanges.  For that a wave's chunk
+// range starts on a block boundary: cpw is rounded up to a multiple of 4 (K = 192: 8 / 8 / 8 / 0 chunks instead of 6 / 6 / 6 / 6).
+template <int M, int NIT, int R, int PRO, int EPI, int Q = 0, int ACT = 0>
 __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel(const LmDevState* __restrict__ stt, const bf16_t* __restrict__ W, GemvQ8 q8,
                                                       const float* __restrict__ x, int N, int K, float* __restrict__ y,
                                                       int batches_per_wg, int ldy, GemvPro pro, GemvRope rope) {
@@ -382,7 +392,9 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tid = threadIdx.x;
     const int nchunk = K >> 3;
-    const int cpw = (nchunk + 3) >> 2;                       // chunks per wave
+    constexpr bool QA = ACT == 1;
+    static_assert(!QA || Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K, "q8_1 activations go with the packed weight formats");
+    const int cpw = QA ? ((((nchunk + 3) >> 2) + 3) & ~3) : (nchunk + 3) >> 2;   // chunks per wave (q8_1: whole 32-blocks)
     const int c0 = wave * cpw;
     const int cn = max(0, min(cpw, nchunk - c0));            // this wave's chunk count (<= 64 * NIT)
     const int n_batches = (N + R - 1) / R;
@@ -558,8 +570,40 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
     }
     int pos0 = 0;
     if (EPI == 2) pos0 = stt->n_tokens;
+    // q8_1 activations: this lane's chunks as int8 (two dwords; Q4_K: elements 0 2 4 6 / 1 3 5 7, the order its nibbles unpack in),
+    // the block's fp16-rounded scale, and for Q4_K d_x * sum(q_x) of the chunk (the minimum term)
+    unsigned xq[QA ? M : 1][QA ? NIT : 1][2];
+    float xd[QA ? M : 1][QA ? NIT : 1];
     float sx[Q4 ? M : 1][Q4 ? NIT : 1];   // Q4_K: sum of this lane's x values per chunk (the minimum term: - (dmin * m) * sum(x))
-    if (Q4) {
+    if constexpr (QA) {
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                float amax = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(xr[m][it][j]));
+                amax = fmaxf(amax, dpp_mov<DPP_XOR1>(amax));   // c0 and K / 8 are multiples of 4: a quad of lanes is one block,
+                amax = fmaxf(amax, dpp_mov<DPP_XOR2>(amax));   // wholly inside the wave's range or wholly outside (x = 0 -> q = 0, d = 0)
+                const float d = amax / 127.0f;
+                const float inv = d != 0.0f ? 1.0f / d : 0.0f;
+                unsigned qb[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) qb[j] = (unsigned)(int)roundf(xr[m][it][j] * inv) & 0xffu;
+                if (Q4) {
+                    xq[m][it][0] = qb[0] | (qb[2] << 8) | (qb[4] << 16) | (qb[6] << 24);
+                    xq[m][it][1] = qb[1] | (qb[3] << 8) | (qb[5] << 16) | (qb[7] << 24);
+                } else {
+                    xq[m][it][0] = qb[0] | (qb[1] << 8) | (qb[2] << 16) | (qb[3] << 24);
+                    xq[m][it][1] = qb[4] | (qb[5] << 8) | (qb[6] << 16) | (qb[7] << 24);
+                }
+                xd[m][it] = (float)(f16_t)d;
+                if (Q4) {
+                    const int s = __builtin_amdgcn_sdot4((int)xq[m][it][1], 0x01010101, __builtin_amdgcn_sdot4((int)xq[m][it][0], 0x01010101, 0, false), false);
+                    sx[m][it] = xd[m][it] * (float)s;
+                }
+            }
+    } else if (Q4) {
 #pragma unroll
         for (int m = 0; m < M; ++m)
 #pragma unroll
@@ -589,6 +633,21 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
                 for (int i = 0; i < 4; ++i) {
                     const unsigned w = q8_opaque(aw[i]);
                     const unsigned lo = w & 0x0F0F0F0Fu, hi = (w >> 4) & 0x0F0F0F0Fu;   // bytes of lo = nibbles 0, 2, 4, 6; of hi = 1, 3, 5, 7
+                    if constexpr (QA) {   // bytes 0..15 are valid signed int8: the signed byte dot against the activation bytes in the same order
+                        const f16x2 d2 = __builtin_bit_cast(f16x2, dw[i]);
+                        const unsigned scm = (sw[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+                        const float d1 = (float)d2[0] * (float)(scm & 0xffu);
+                        const float m1 = (float)d2[1] * (float)(scm >> 8);
+#pragma unroll
+                        for (int m = 0; m < M; ++m) {
+                            const int p = __builtin_amdgcn_sdot4((int)hi, (int)xq[m][it][1], __builtin_amdgcn_sdot4((int)lo, (int)xq[m][it][0], 0, false), false);
+                            float acc = val[m * R + 4 * r + i];
+                            acc = __builtin_fmaf(d1 * xd[m][it], (float)p, acc);
+                            acc = __builtin_fmaf(-m1, sx[m][it], acc);
+                            val[m * R + 4 * r + i] = acc;
+                        }
+                        continue;
+                    }
                     float pq[M];
 #pragma unroll
                     for (int m = 0; m < M; ++m) pq[m] = 0.0f;
@@ -619,6 +678,19 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
             for (int it = 0; it < NIT; ++it) {
                 const u32x4 a = wq[r][it];
                 const unsigned wa[2] = {q8_opaque(a.x), q8_opaque(a.y)}, wb[2] = {q8_opaque(a.z), q8_opaque(a.w)};
+                if constexpr (QA) {
+                    const f16x2 d2 = __builtin_bit_cast(f16x2, wsc[it][r]);
+                    const float da = Q6 ? __uint_as_float(wsc[it][r]) : (float)d2[0], db = Q6 ? __uint_as_float(wsc2[it][r]) : (float)d2[1];
+#pragma unroll
+                    for (int m = 0; m < M; ++m) {
+                        const int ia = __builtin_amdgcn_sdot4((int)wa[1], (int)xq[m][it][1], __builtin_amdgcn_sdot4((int)wa[0], (int)xq[m][it][0], 0, false), false);
+                        const int ib = __builtin_amdgcn_sdot4((int)wb[1], (int)xq[m][it][1], __builtin_amdgcn_sdot4((int)wb[0], (int)xq[m][it][0], 0, false), false);
+                        val[m * R + 2 * r] = __builtin_fmaf(da * xd[m][it], (float)ia, val[m * R + 2 * r]);
+                        val[m * R + 2 * r + 1] = __builtin_fmaf(db * xd[m][it], (float)ib, val[m * R + 2 * r + 1]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);   // one pair at a time, as below
+                    continue;
+                }
                 float pa[M], pb[M];
 #pragma unroll
                 for (int m = 0; m < M; ++m) pa[m] = pb[m] = 0.0f;
@@ -1941,6 +2013,7 @@ struct rca_lm {
     bool graphs_enabled = true;
     bool mfma_prefill = true;   // evals longer than LM_PREFILL_MIN tokens use the bf16 MFMA tiles
     bool fuse_attn = true;      // decode steps merge the attention splits inside the attention launch (rca_lm_set_attn_fuse)
+    int act_format = 0;         // activations of the decode GEMVs over packed matrices: 0 f32, 1 q8_1 blocks + integer dots (rca_lm_set_act_format)
     // weight sharing (rca_lm_create_shared): a borrower points at the handle that owns the weights and the RoPE tables; an owner
     // destroyed while borrowers are alive keeps those allocations (and its struct) until the last borrower is gone
     rca_lm* weights_of = nullptr;
@@ -2613,6 +2686,7 @@ extern "C" int rca_lm_create_shared(rca_lm_t* parent, int32_t n_ctx, int32_t log
     // the twin evaluates with the kernels its parent would use (the shadow cache must hold the bits recompute_kv_cache would leave)
     h->fuse_attn = parent->fuse_attn;
     h->mfma_prefill = parent->mfma_prefill;
+    h->act_format = parent->act_format;
     owner->borrowers++;
     if ((rc = lm_common_init(h, nullptr, 0, owner)) != RCA_OK) { rca_lm_destroy(h); return rc; }
     *out = h;
@@ -2648,18 +2722,18 @@ static GemvGeom gemv_geom(int kind, int N, bool q8) {
     while (g.bpw > 1 && (N + g.R * g.bpw - 1) / (g.R * g.bpw) < 64) g.bpw >>= 1;
     return g;
 }
-template <int M, int NIT, int PRO, int EPI, int Q>
+template <int M, int NIT, int PRO, int EPI, int Q, int ACT>
 static void launch_gemv_r(const GemvGeom& g, rca_lm* h, const WMat& w, const float* x, float* y, int N, int K, int ldy, const GemvPro& pro,
                           const GemvRope& rope, hipStream_t st) {
     const int grid = cdiv(cdiv(N, g.R), g.bpw);
     const GemvQ8 qa{w.qs, w.sc, w.dd};
     switch (g.R) {
-        case 4: lm_gemv_kernel<M, NIT, 4, PRO, EPI, Q><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
-        case 8: lm_gemv_kernel<M, NIT, 8, PRO, EPI, Q><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
-        default: lm_gemv_kernel<M, NIT, 16, PRO, EPI, Q><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
+        case 4: lm_gemv_kernel<M, NIT, 4, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
+        case 8: lm_gemv_kernel<M, NIT, 8, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
+        default: lm_gemv_kernel<M, NIT, 16, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
     }
 }
-template <int PRO, int EPI, int Q>
+template <int PRO, int EPI, int Q, int ACT = 0>
 static void launch_gemv_q(GemvGeom g, rca_lm* h, int M, const WMat& w, const float* x, float* y, int N, int K, int ldy, const GemvPro& pro,
                           const GemvRope& rope, hipStream_t st) {
     const int nit = cdiv(cdiv(K >> 3, 4), 64);
@@ -2670,16 +2744,16 @@ static void launch_gemv_q(GemvGeom g, rca_lm* h, int M, const WMat& w, const flo
     if ((Q == WF_Q4K || Q == WF_Q6K) && g.R < 8) g.R = 8;   // a Q4_K batch is at least two quads (one per register half); Q6_K scale loads cover two pairs
     if (PRO == 0 && EPI == 3 && nit > 1) {
         if (nit == 2) {
-            if (M == 1) launch_gemv_r<1, 2, 0, 3, Q>(g, h, w, x, y, N, K, ldy, pro, rope, st);
-            else launch_gemv_r<2, 2, 0, 3, Q>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+            if (M == 1) launch_gemv_r<1, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+            else launch_gemv_r<2, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
         } else {
-            if (M == 1) launch_gemv_r<1, 4, 0, 3, Q>(g, h, w, x, y, N, K, ldy, pro, rope, st);
-            else launch_gemv_r<2, 4, 0, 3, Q>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+            if (M == 1) launch_gemv_r<1, 4, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+            else launch_gemv_r<2, 4, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
         }
         return;
     }
-    if (M == 1) launch_gemv_r<1, 1, PRO, EPI, Q>(g, h, w, x, y, N, K, ldy, pro, rope, st);
-    else launch_gemv_r<2, 1, PRO, EPI, Q>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+    if (M == 1) launch_gemv_r<1, 1, PRO, EPI, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+    else launch_gemv_r<2, 1, PRO, EPI, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
 }
 // M = 1 or 2 tokens.  Only the down projection (K = ffn) needs more than one chunk per lane and wave.  The matrix is streamed in the
 // format it is kept in.
@@ -2687,6 +2761,11 @@ template <int PRO, int EPI>
 static void launch_gemv(int kind, rca_lm* h, int M, const WMat& w, const float* x, float* y, int N, int K, int ldy, const GemvPro& pro,
                         const GemvRope& rope, hipStream_t st) {
     const GemvGeom g = gemv_geom(kind, N, w.fmt == WF_Q8 || w.fmt == WF_Q4K || w.fmt == WF_Q6K);
+    if (h->act_format == 1) {   // q8_1 activations on the integer dot (rca_lm_set_act_format); 16-bit matrices keep f32 activations
+        if (w.fmt == WF_Q6K) return launch_gemv_q<PRO, EPI, WF_Q6K, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+        if (w.fmt == WF_Q4K) return launch_gemv_q<PRO, EPI, WF_Q4K, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+        if (w.fmt == WF_Q8) return launch_gemv_q<PRO, EPI, WF_Q8, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+    }
     if (w.fmt == WF_Q6K) launch_gemv_q<PRO, EPI, WF_Q6K>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
     else if (w.fmt == WF_Q4K) launch_gemv_q<PRO, EPI, WF_Q4K>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
     else if (w.fmt == WF_Q8) launch_gemv_q<PRO, EPI, WF_Q8>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
@@ -5133,6 +5212,99 @@ extern "C" int rca_lm_set_attn_fuse(rca_lm_t* h, int32_t enable) {
     h->fuse_attn = enable != 0;
     return RCA_OK;
 }
+// Activation format of the decode GEMVs over packed (q8_0 / Q4_K / Q6_K) matrices: 0 = f32, 1 = q8_1 blocks + integer dot products
+// (lm_gemv_kernel<..., ACT = 1>).  The exact prefill route is made of the same launches and follows; the MFMA tiles do not.
+static bool lm_has_packed_matrix(const rca_lm* h) {
+    auto packed = [](const WMat& m) { return m.fmt == WF_Q8 || m.fmt == WF_Q4K || m.fmt == WF_Q6K; };
+    bool any = packed(h->head);
+    for (const LmLayer& L : h->layers) any = any || packed(L.qkv) || packed(L.o) || packed(L.gu) || packed(L.down) || (L.split_v && packed(L.vseg));
+    return any;
+}
+extern "C" int rca_lm_set_act_format(rca_lm_t* h, int32_t fmt) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    if (fmt != 0 && fmt != 1) return fail(RCA_ERR_ARG, "set_act_format: %d is neither 0 (f32) nor 1 (q8_1)", fmt);
+    if (fmt == 1 && !lm_has_packed_matrix(h))
+        return fail(RCA_ERR_ARG, "set_act_format: q8_1 activations need a q8_0 / Q4_K / Q6_K projection matrix, and this handle keeps all of its matrices in 16-bit floats");
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    if (h->act_format != fmt) {
+        RCA_HIP(hipSetDevice(h->device));
+        RCA_HIP(hipStreamSynchronize(h->stream));
+        lm_drop_graphs(h);   // the captured steps hold the other instances
+    }
+    h->act_format = fmt;
+    return RCA_OK;
+}
+extern "C" int rca_lm_get_act_format(const rca_lm_t* h, int32_t* fmt) {
+    if (!h || !fmt) return fail(RCA_ERR_ARG, "null");
+    *fmt = h->act_format;
+    return RCA_OK;
+}
+// tests only: one decode GEMV stage, launched by the very call lm_enqueue_pass makes for it, on a host-supplied input
+extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const float* x_host, int32_t M, float* y_host, int64_t y_numel,
+                               uint16_t* kv_host) {
+    if (!h || !x_host || !y_host) return fail(RCA_ERR_ARG, "null");
+    const rca_lm_config_t& c = h->cfg;
+    const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn, V = c.vocab_size;
+    if (kind < 0 || kind > 4) return fail(RCA_ERR_ARG, "gemv_tap: kind %d outside [0, 4]", kind);
+    if (M < 1 || M > LM_GEMV_M) return fail(RCA_ERR_ARG, "gemv_tap: M = %d, a decode pass has 1 or %d tokens", M, LM_GEMV_M);
+    if (kind != 4 && (layer < 0 || layer >= c.n_layers)) return fail(RCA_ERR_ARG, "gemv_tap: layer %d outside [0, %d)", layer, c.n_layers);
+    if (h->n_tokens + M > c.n_ctx) return fail(RCA_ERR_STATE, "gemv_tap: positions %d .. %d are outside the context of %d", h->n_tokens, h->n_tokens + M - 1, c.n_ctx);
+    const int in_w[5] = {H, AO, H, F, H}, out_w[5] = {AO, H, F, H, V};
+    if (y_numel != (int64_t)M * out_w[kind]) return fail(RCA_ERR_ARG, "gemv_tap: y_numel %ld, kind %d writes %d x %d values", (long)y_numel, kind, M, out_w[kind]);
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    RCA_HIP(hipStreamSynchronize(st));
+    const int32_t ids[LM_GEMV_M] = {};
+    int rc;
+    if ((rc = lm_push_state(h, ids, M, st)) != RCA_OK) return rc;
+    const GemvPro nopro{nullptr, nullptr, 0.0f, 0};
+    const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    float* xin = kind == 1 ? h->attn : (kind == 3 ? h->hbuf : h->x);
+    RCA_HIP(hipMemcpyAsync(xin, x_host, (size_t)M * in_w[kind] * 4, hipMemcpyHostToDevice, st));
+    const float* yd = nullptr;
+    int ldy = out_w[kind];
+    float* head_out = nullptr;
+    if (kind == 0) {
+        const LmLayer& L = h->layers[layer];
+        GemvRope rope{h->cos_t, h->sin_t, h->kc + (long)layer * h->kv_layer_stride, h->vc + (long)layer * h->kv_layer_stride, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
+        launch_gemv<1, 2>(GEMV_QKV, h, M, L.qkv, nullptr, h->qkv, L.qkv.N, H, QKV, GemvPro{h->x, L.attn_norm, c.rms_eps, 0}, rope, st);
+        if (L.split_v) {
+            rope.row_base = L.qkv.N;
+            launch_gemv<1, 2>(GEMV_QKV, h, M, L.vseg, nullptr, h->qkv, L.vseg.N, H, QKV, GemvPro{h->x, L.attn_norm, c.rms_eps, 0}, rope, st);
+        }
+        yd = h->qkv; ldy = QKV;
+    } else if (kind == 1) {
+        RCA_HIP(hipMemsetAsync(h->x, 0, (size_t)M * H * 4, st));
+        launch_gemv<0, 3>(GEMV_O, h, M, h->layers[layer].o, h->attn, h->x, H, AO, H, nopro, norope, st);
+        yd = h->x;
+    } else if (kind == 2) {
+        const LmLayer& L = h->layers[layer];
+        launch_gemv<1, 1>(GEMV_GU, h, M, L.gu, nullptr, h->hbuf, 2 * F, H, F, GemvPro{h->x, L.ffn_norm, c.rms_eps, 0}, norope, st);
+        yd = h->hbuf;
+    } else if (kind == 3) {
+        RCA_HIP(hipMemsetAsync(h->x, 0, (size_t)M * H * 4, st));
+        launch_gemv<0, 3>(GEMV_DOWN, h, M, h->layers[layer].down, h->hbuf, h->x, H, F, H, nopro, norope, st);
+        yd = h->x;
+    } else {
+        if ((rc = lm_alloc((void**)&head_out, (size_t)M * V * 4)) != RCA_OK) return rc;   // the handle's own logits buffer may hold one row only
+        launch_gemv<1, 0>(GEMV_HEAD, h, M, h->head, nullptr, head_out, V, H, V, GemvPro{h->x, h->final_norm, c.rms_eps, 0}, norope, st);
+        yd = head_out;
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy2DAsync(y_host, (size_t)out_w[kind] * 4, yd, (size_t)ldy * 4, (size_t)out_w[kind] * 4, M, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && kind == 0 && kv_host) {
+        const size_t n = (size_t)M * c.n_kv_heads * 64;
+        const long off = (long)layer * h->kv_layer_stride + (long)h->n_tokens * c.n_kv_heads * 64;
+        e = hipMemcpyAsync(kv_host, h->kc + off, n * 2, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(kv_host + n, h->vc + off, n * 2, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (head_out) (void)hipFree(head_out);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "gemv_tap: %s", hipGetErrorString(e));
+    return RCA_OK;
+}
+
 // the format the projection matrices are kept (and streamed) in: 0 bf16, 1 q8_0, 2 f16, 3 q4_k (4 = Q6_K, which only ever appears next to Q4_K
 // tensors); bytes = weight bytes one decode step reads
 extern "C" int rca_lm_weight_format(const rca_lm_t* h, int32_t* fmt, int64_t* bytes_per_step) {

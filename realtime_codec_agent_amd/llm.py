@@ -100,6 +100,7 @@ def bf16_bits_to_f32(b: np.ndarray) -> np.ndarray:
     return (b.astype(np.uint32) << 16).view(np.float32)
 
 
+ACTIVATION_FORMATS = ("f32", "q8_1")          # rca_lm_set_act_format's 0 / 1
 CODEC_PREFIX = "model.embed_codec_tokens."   # CodecLlamaCodecEmbedding's tensors (codec_llama.py:46-69)
 
 
@@ -192,13 +193,19 @@ class LlamaForAlternatingCodeChannels:
         init_std: float = 0.02,
         share_weights_with: Optional["LlamaForAlternatingCodeChannels"] = None,
         weight_format: Optional[str] = None,
+        activation_format: Optional[str] = None,
         **_ignored,
     ):
         """weight_format: the format every projection matrix and lm_head is KEPT in (one copy: the decode step streams it, the prefill
         tiles de-quantise it while staging).  None = as the checkpoint supplies it (bf16 / fp16 / Q8_0 tensors keep their format, f32 is
         rounded to bf16); "q8_0" = quantised at load like the Q8_0 file the reference deploys (prep_test_model.sh:29); "f16" = bf16
         values converted to fp16 (the F16 file of prep_test_model.sh:28, the reference's default model); "q4_k" = GGUF Q4_K blocks
-        (the bulk of the Q4_K_M file of prep_test_model.sh:31), quantised at load with this build's own min / max rule."""
+        (the bulk of the Q4_K_M file of prep_test_model.sh:31), quantised at load with this build's own min / max rule.
+        activation_format: what the decode GEMVs over quantised (q8_0 / Q4_K / Q6_K) matrices multiply the weights with.  None / "f32"
+        (default) = f32 activations; "q8_1" = activations quantised to 32-value int8 blocks inside the GEMV and integer dot products,
+        the arithmetic class of llama.cpp's GPU mat-vec (set_activation_format).  A twin inherits its parent's."""
+        if activation_format not in (None,) + ACTIVATION_FORMATS:
+            raise ValueError(f"activation_format {activation_format!r}: None / 'f32' or 'q8_1'")
         if weight_format not in (None, "bf16", "q8_0", "f16", "q4_k"):
             raise ValueError(f"weight_format {weight_format!r}: None / 'bf16' (as supplied), 'q8_0', 'f16' or 'q4_k'")
         self._lib = N.lib()
@@ -224,6 +231,8 @@ class LlamaForAlternatingCodeChannels:
             self._weights_parent = parent   # (the library also copes with the parent being closed first)
             self._finish_init(seed)
             self.weight_format = parent.weight_format
+            self.activation_format = self._query_activation_format()   # rca_lm_create_shared copied the parent's
+            self._init_activation_format(activation_format)
             return
         random_init = weights is None and (model_path is None or str(model_path).startswith("random:"))
         if weights is None and not random_init:
@@ -255,6 +264,46 @@ class LlamaForAlternatingCodeChannels:
                                               int(weights["codec.vocab_start"]), int(weights.get("codec.codebook_size", 0)) or None)
         self._finish_init(seed)
         self.weight_format = self._query_format()[0]
+        self.activation_format = "f32"
+        self._init_activation_format(activation_format)
+
+    def _init_activation_format(self, activation_format: Optional[str]) -> None:
+        if activation_format is None:
+            return
+        try:
+            self.set_activation_format(activation_format)
+        except Exception:
+            self.close()          # a refused mode must not leave the handle (and its weights) behind
+            raise
+
+    def _query_activation_format(self) -> str:
+        fmt = C.c_int32()
+        N.check(self._lib.rca_lm_get_act_format(self._h, C.byref(fmt)), "rca_lm_get_act_format")
+        return ACTIVATION_FORMATS[fmt.value]
+
+    def set_activation_format(self, activation_format: str) -> None:
+        """"f32" or "q8_1" (see the constructor).  Captured graphs are dropped on a change; the library refuses "q8_1" on a handle
+        whose matrices are all bf16 / f16 (RcaError).  The MFMA prefill tiles keep f32 activations in either mode."""
+        if activation_format not in ACTIVATION_FORMATS:
+            raise ValueError(f"activation_format {activation_format!r}: 'f32' or 'q8_1'")
+        N.check(self._lib.rca_lm_set_act_format(self._h, ACTIVATION_FORMATS.index(activation_format)), "rca_lm_set_act_format")
+        self.activation_format = activation_format
+
+    def gemv_tap(self, layer: int, kind: int, x: np.ndarray, want_kv: bool = False):
+        """Tests only (rca_lm_gemv_tap): one decode GEMV stage on the rows x [M, K]; kind 0 QKV, 1 O, 2 gate/up, 3 down, 4 head.
+        Returns y [M, N] float32, and with want_kv (kind 0) also the new K and V cache rows [M, n_kv_heads * 64] as float16."""
+        c = self.config
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        M = x.shape[0]
+        widths = {0: (c.hidden, c.n_heads * 64), 1: (c.n_heads * 64, c.hidden), 2: (c.hidden, c.ffn), 3: (c.ffn, c.hidden), 4: (c.hidden, c.vocab_size)}
+        if kind not in widths or x.ndim != 2 or x.shape[1] != widths[kind][0]:
+            raise ValueError(f"gemv_tap: kind {kind} takes rows of {widths.get(kind, ('?',))[0]} values, got {x.shape}")
+        y = np.empty((M, widths[kind][1]), np.float32)
+        kv = np.empty((2, M, c.n_kv_heads * 64), np.float16) if (want_kv and kind == 0) else None
+        N.check(self._lib.rca_lm_gemv_tap(self._h, int(layer), int(kind), x.ctypes.data_as(C.POINTER(C.c_float)), M,
+                                          y.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(y.size),
+                                          kv.ctypes.data_as(C.POINTER(C.c_uint16)) if kv is not None else None), "rca_lm_gemv_tap")
+        return (y, kv[0], kv[1]) if kv is not None else y
 
     def _query_format(self):
         fmt, nbytes = C.c_int32(), C.c_int64()
