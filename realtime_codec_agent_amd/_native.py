@@ -24,7 +24,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"
                "-Wno-unused-result", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
 MAX_STAGES = 8
-RCA_F32, RCA_BF16, RCA_Q8_0, RCA_F16, RCA_Q4_K, RCA_Q6_K = 0, 1, 2, 3, 4, 5
+RCA_F32, RCA_BF16, RCA_Q8_0, RCA_F16, RCA_Q4_K, RCA_Q6_K, RCA_Q5_K = 0, 1, 2, 3, 4, 5, 6
 
 
 class RcaError(RuntimeError):
@@ -79,6 +79,41 @@ class Q4KBlocks:
     def take_rows(self, index) -> "Q4KBlocks":
         r = self.raw[index]
         return Q4KBlocks(np.ascontiguousarray(r), (r.shape[0], self.shape[1]))
+
+
+class Q5KBlocks:
+    """A GGUF Q5_K tensor kept as its raw 176-byte super-blocks (fp16 d, fp16 dmin, 12 bytes of 6-bit scales / minima packed as in Q4_K,
+    32 bytes of high bits, 128 bytes of nibbles per 256 values): raw uint8 [rows, cols / 256 * 176], logical shape (rows, cols).
+    The bulk of a llama-quantize Q5_K_S / Q5_K_M file."""
+
+    def __init__(self, raw: np.ndarray, shape):
+        self.shape = tuple(int(x) for x in shape)
+        self.raw = raw.reshape(self.shape[0], self.shape[1] // 256 * 176)
+        self.dtype = np.dtype(np.uint8)
+
+    def dequantize(self) -> np.ndarray:
+        """llama.cpp's dequantize_row_q5_K: (d * sc) * q - (dmin * m) in f32, q = nibble | high bit << 4.  Weight 64 t + l takes the low
+        nibble of qs[32 t + l] and bit 2 t of qh[l], weight 64 t + 32 + l the high nibble and bit 2 t + 1."""
+        blk = self.raw.reshape(-1, 176)
+        d = blk[:, 0:2].copy().view(np.float16).astype(np.float32)
+        dmin = blk[:, 2:4].copy().view(np.float16).astype(np.float32)
+        s = blk[:, 4:16]
+        sc = np.empty((blk.shape[0], 8), np.uint8)
+        m = np.empty_like(sc)
+        sc[:, 0:4], m[:, 0:4] = s[:, 0:4] & 63, s[:, 4:8] & 63
+        sc[:, 4:8] = (s[:, 8:12] & 0xF) | ((s[:, 0:4] >> 6) << 4)
+        m[:, 4:8] = (s[:, 8:12] >> 4) | ((s[:, 4:8] >> 6) << 4)
+        qh = blk[:, 16:48].reshape(-1, 1, 1, 32)
+        qs = blk[:, 48:176].reshape(-1, 4, 32)
+        shift = np.arange(8, dtype=np.uint8).reshape(1, 4, 2, 1)                     # bit 2 t + (0 low nibble, 1 high nibble)
+        q = (np.stack([qs & 0xF, qs >> 4], axis=2) | (((qh >> shift) & 1) << 4)).astype(np.float32)
+        d1 = (d * sc.astype(np.float32)).astype(np.float32).reshape(-1, 4, 2, 1)
+        m1 = (dmin * m.astype(np.float32)).astype(np.float32).reshape(-1, 4, 2, 1)
+        return ((d1 * q).astype(np.float32) - m1).astype(np.float32).reshape(self.shape)
+
+    def take_rows(self, index) -> "Q5KBlocks":
+        r = self.raw[index]
+        return Q5KBlocks(np.ascontiguousarray(r), (r.shape[0], self.shape[1]))
 
 
 class Q6KBlocks:
@@ -347,11 +382,11 @@ def make_tensors(weights: Dict[str, np.ndarray]) -> Tuple[C.Array, list]:
     keep = []
     arr = (Tensor * len(weights))()
     for i, (name, a) in enumerate(weights.items()):
-        if isinstance(a, (Q8Blocks, Q4KBlocks, Q6KBlocks)):      # GGUF q8_0 / Q4_K / Q6_K blocks, handed over as they sit in the file
+        if isinstance(a, (Q8Blocks, Q4KBlocks, Q5KBlocks, Q6KBlocks)):      # GGUF q8_0 / Q4_K / Q5_K / Q6_K blocks, handed over as they sit in the file
             raw = np.ascontiguousarray(a.raw)
             nb = name.encode()
             keep += [raw, nb]
-            arr[i] = Tensor(nb, raw.ctypes.data, int(np.prod(a.shape)), RCA_Q8_0 if isinstance(a, Q8Blocks) else (RCA_Q4_K if isinstance(a, Q4KBlocks) else RCA_Q6_K))
+            arr[i] = Tensor(nb, raw.ctypes.data, int(np.prod(a.shape)), {Q8Blocks: RCA_Q8_0, Q4KBlocks: RCA_Q4_K, Q5KBlocks: RCA_Q5_K, Q6KBlocks: RCA_Q6_K}[type(a)])
             continue
         if a.dtype == np.uint16:
             dt = RCA_BF16

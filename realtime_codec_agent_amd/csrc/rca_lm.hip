@@ -352,6 +352,12 @@ struct GemvQ8 {          // the packed (quantised) forms: q8_0, and Q4_K (dd != 
 // slots (rows in the order the GEMV's epilogues pair them) in quads, qs[quad][k / 8] = one dword per slot holding the 8 nibbles of
 // 8 consecutive k (nibble j at bits 4 j): a 16-byte lane load feeds four rows with the x values the lane holds; 4.6 bits per weight
 // streamed.  Arithmetic per lane, slot and 8-k chunk: p = fma chain of q_j x_j (j ascending), then val += (d * sc) p - (dmin * m) sum(x).
+// Q5_K (GGUF block_q5_K: the bulk of a Q5_K_S / Q5_K_M file) is the Q4_K block with a fifth bit per value: q in 0..31, same scales,
+// minima and arithmetic.  Streamed as the Q4_K layout over the low nibbles plus ONE plane of high bits, qh[quad][k / 8]: a dword per
+// quad and 8-k chunk, the lane's 17th to 20th byte of the chunk.  Bit 8 (j / 2) + 2 slot + (j & 1) is the high bit of element j of
+// the quad's slot: shifted by 4 - 2 slot (even elements) or 3 - 2 slot (odd ones), the mask 0x10101010 leaves the four bits exactly
+// where the nibble bytes `lo` / `hi` of the Q4_K body want their bit 4 -- a shift and an and-or per four weights.
+__host__ __device__ __forceinline__ int q5k_hbit(int slot_in_quad, int j) { return 8 * (j >> 1) + 2 * slot_in_quad + (j & 1); }
 __host__ __device__ __forceinline__ long q4k_scm_index(long slot, long kblock, long nkb) { return ((slot >> 4) * nkb + kblock) * 16 + (slot & 15); }
 __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, long nkb) { return ((pair >> 3) * nkb + kblock) * 8 + (pair & 7); }
 // The format a projection matrix is kept in (ONE copy per matrix; the decode GEMV streams it, the prefill tiles de-quantise it while
@@ -363,12 +369,13 @@ __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, lon
 #define WF_Q8 1     // GGUF q8_0, pair-interleaved (GemvQ8)
 #define WF_F16 2    // fp16 [N][K] (the reference's default GGUF is F16, realtime_agent_resources.py:12)
 #define WF_Q4K 3    // GGUF Q4_K, quad-interleaved nibbles (GemvQ8 with dd)
+#define WF_Q5K 5    // GGUF Q5_K: the Q4_K layout (low nibbles, sc, dd) + one plane of high bits, q5k_hbit() above (5.6 bits per weight streamed)
 #define WF_Q6K 4    // GGUF Q6_K re-encoded losslessly: int8 values (the 6-bit value - 32) in the q8_0 pair layout + one f32 scale d * sc per
                     // row and group of 16 ((s_a, s_b) per pair, pairs in groups of 8: [ceil(N / 16)][K / 16][8][2] floats); 10 bits per
                     // weight streamed (the file holds 6.6); d * sc * q is exact in f32, so the values are llama.cpp's dequantize_row_q6_K's
 // minimum waves per SIMD asked of the register allocator.  The q8_0 bodies otherwise spread over 200+ registers (one wave per
 // SIMD) although their live set is ~130: a streaming kernel wants the occupancy.
-constexpr int gemv_min_waves(int Q, int R, int NIT) { return (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K) ? 1 : (R * NIT >= 16 ? 2 : 4); }
+constexpr int gemv_min_waves(int Q, int R, int NIT) { return (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K) ? 1 : (R * NIT >= 16 ? 2 : 4); }
 // ACT = 1 (rca_lm_set_act_format, packed formats only): the activations are quantised to q8_1 blocks -- 32 consecutive values, int8 +
 // one scale, ggml's quantize_row_q8_1 restated: d = amax / 127, inv = d != 0 ? 1 / d : 0 (IEEE division), q = roundf(x * inv), scale used
 // d_x = (float)(fp16 rne of d) -- and the products run on the signed byte dot (v_dot4c_i32_i8), llama.cpp's GPU mat-vec class:
@@ -393,7 +400,7 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
     const int tid = threadIdx.x;
     const int nchunk = K >> 3;
     constexpr bool QA = ACT == 1;
-    static_assert(!QA || Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K, "q8_1 activations go with the packed weight formats");
+    static_assert(!QA || Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K, "q8_1 activations go with the packed weight formats");
     const int cpw = QA ? ((((nchunk + 3) >> 2) + 3) & ~3) : (nchunk + 3) >> 2;   // chunks per wave (q8_1: whole 32-blocks)
     const int c0 = wave * cpw;
     const int cn = max(0, min(cpw, nchunk - c0));            // this wave's chunk count (<= 64 * NIT)
@@ -410,12 +417,14 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
         return b * R + r;
     };
     constexpr bool Q6 = Q == WF_Q6K;                 // the q8_0 body with another scale: f32 per group of 16 instead of fp16 per 32
-    constexpr bool Q8 = Q == WF_Q8 || Q6, Q4 = Q == WF_Q4K;
+    constexpr bool Q5 = Q == WF_Q5K;                 // the Q4_K body with a fifth bit per value; its plane of high bits arrives as W
+    constexpr bool Q8 = Q == WF_Q8 || Q6, Q4 = Q == WF_Q4K || Q5;
     constexpr int NL = Q8 ? R / 2 : (Q4 ? R / 4 : R);   // 16-byte weight loads per chunk: one per row, per slot pair (q8_0 / Q6_K) or per slot quad (Q4_K)
     constexpr int H0 = NL / 2;                // the batch's registers refill in two halves: loads [0, H0) and [H0, NL)
     u32x4 wq[NL][NIT];
     uint2 wscm[Q4 ? NIT : 1][Q4 ? NL : 1];    // Q4_K: (sc | m << 8) of a quad's four slots for this lane's 32-element sub-block
     u32x4 wdd[Q4 ? NIT : 1][Q4 ? NL : 1];     //       (d | dmin << 16) of the four slots for this lane's 256-element super-block
+    unsigned wqh[Q5 ? NL : 1][Q5 ? NIT : 1];  // Q5_K: the quad's dword of high bits for this lane's chunk
     unsigned wsc[Q8 ? NIT : 1][Q8 ? R / 2 : 1];   // q8_0: (fp16, fp16) scales of the batch's pairs for this lane's 32-element block
     unsigned wsc2[Q6 ? NIT : 1][Q6 ? R / 2 : 1];  // Q6_K: wsc / wsc2 = the f32 scales (bits) of the pair's first / second row for this lane's group of 16
     const int npairs = N >> 1;
@@ -434,6 +443,7 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
                 wdd[it][r] = *reinterpret_cast<const u32x4*>(q8.dd + q4k_scm_index(4 * quad, cc >> 5, K >> 8));
                 wscm[it][r] = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(q8.sc) + q4k_scm_index(4 * quad, cc >> 2, K >> 5));
                 wq[r][it] = __builtin_nontemporal_load(q8.qs + quad * nchunk + cc);
+                if constexpr (Q5) wqh[r][it] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(W) + quad * nchunk + cc);
             }
         } else if (Q8) {
             const long pp = min((long)b * (R / 2) + r, (long)npairs - 1);
@@ -632,8 +642,13 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const unsigned w = q8_opaque(aw[i]);
-                    const unsigned lo = w & 0x0F0F0F0Fu, hi = (w >> 4) & 0x0F0F0F0Fu;   // bytes of lo = nibbles 0, 2, 4, 6; of hi = 1, 3, 5, 7
-                    if constexpr (QA) {   // bytes 0..15 are valid signed int8: the signed byte dot against the activation bytes in the same order
+                    unsigned lo = w & 0x0F0F0F0Fu, hi = (w >> 4) & 0x0F0F0F0Fu;   // bytes of lo = nibbles 0, 2, 4, 6; of hi = 1, 3, 5, 7
+                    if constexpr (Q5) {   // bit 4 of every byte from the plane (q5k_hbit): slot i's even elements at bits 8 b + 2 i, odd at 8 b + 2 i + 1
+                        const unsigned hb = wqh[r][it];
+                        lo |= (i < 2 ? hb << (4 - 2 * i) : hb >> (2 * i - 4)) & 0x10101010u;
+                        hi |= (i < 2 ? hb << (3 - 2 * i) : hb >> (2 * i - 3)) & 0x10101010u;
+                    }
+                    if constexpr (QA) {   // bytes 0..15 (Q5_K: 0..31) are valid signed int8: the signed byte dot against the activation bytes in the same order
                         const f16x2 d2 = __builtin_bit_cast(f16x2, dw[i]);
                         const unsigned scm = (sw[i >> 1] >> (16 * (i & 1))) & 0xffffu;
                         const float d1 = (float)d2[0] * (float)(scm & 0xffu);
@@ -1793,9 +1808,34 @@ __global__ __launch_bounds__(256) void lm_q4k_unblock_kernel(const unsigned char
         if (e == 0) dd[blk] = (unsigned)bp[0] | ((unsigned)bp[1] << 8) | ((unsigned)bp[2] << 16) | ((unsigned)bp[3] << 24);
     }
 }
+// ---- Q5_K (176-byte block_q5_K = { fp16 d; fp16 dmin; scales[12]; qh[32]; qs[128] }).  Plain form: the Q4_K one with the 5-bit value in
+// the byte.  Weight 64 t + 32 high + l: low / high nibble of qs[32 t + l] and, as its bit 4, bit 2 t + high of qh[l].
+__global__ __launch_bounds__(256) void lm_q5k_unblock_kernel(const unsigned char* __restrict__ blocks, long nblocks, unsigned char* __restrict__ q,
+                                                             unsigned short* __restrict__ scm, unsigned* __restrict__ dd) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nblocks * 256; i += (long)gridDim.x * blockDim.x) {
+        const long blk = i >> 8;
+        const int e = (int)(i & 255);
+        const unsigned char* bp = blocks + blk * 176;
+        const int t = e >> 6, l = e & 31, high = (e >> 5) & 1;
+        const unsigned char byte = bp[48 + 32 * t + l];
+        const unsigned b4 = (bp[16 + l] >> (2 * t + high)) & 1u;
+        q[i] = (unsigned char)((high ? (byte >> 4) : (byte & 0xF)) | (b4 << 4));
+        if ((e & 31) == 0) {   // sub-block j = e / 32: get_scale_min_k4, as for Q4_K
+            const int j = e >> 5;
+            const unsigned char* sc = bp + 4;
+            unsigned scv, mv;
+            if (j < 4) { scv = sc[j] & 63; mv = sc[j + 4] & 63; }
+            else { scv = (sc[j + 4] & 0xF) | ((sc[j - 4] >> 6) << 4); mv = (sc[j + 4] >> 4) | ((sc[j] >> 6) << 4); }
+            scm[blk * 8 + j] = (unsigned short)(scv | (mv << 8));
+        }
+        if (e == 0) dd[blk] = (unsigned)bp[0] | ((unsigned)bp[1] << 8) | ((unsigned)bp[2] << 16) | ((unsigned)bp[3] << 24);
+    }
+}
 // This build's Q4_K quantiser (oracle/q4k_ref.py::quantize_q4_k, operation for operation): per 32 values offset o = -min(0, min w)
 // and step s = (max w + o) / 15; per 256 d = max s / 63, dmin = max o / 63 (fp16); sc = round(s / d), m = round(o / dmin);
 // q = clamp(round((w + dmin m) / (d sc)), 0, 15).  llama-quantize searches for better scales; the FORMAT and its de-quantisation are GGUF's.
+// QMAX = 31: the same rule with 31 steps, Q5_K (the plain form keeps the whole 5-bit value in its byte).
+template <int QMAX>
 __global__ __launch_bounds__(256) void lm_q4k_quantize_kernel(const bf16_t* __restrict__ w, int is_f16, long nblocks, unsigned char* __restrict__ q,
                                                               unsigned short* __restrict__ scm, unsigned* __restrict__ dd) {
     for (long blk = (long)blockIdx.x * blockDim.x + threadIdx.x; blk < nblocks; blk += (long)gridDim.x * blockDim.x) {
@@ -1808,7 +1848,7 @@ __global__ __launch_bounds__(256) void lm_q4k_quantize_kernel(const bf16_t* __re
                 mn = fminf(mn, v);
                 mx = fmaxf(mx, v);
             }
-            s[j] = (mx - mn) / 15.0f;
+            s[j] = (mx - mn) / (float)QMAX;
             o[j] = -mn;
             smax = fmaxf(smax, s[j]);
             omax = fmaxf(omax, o[j]);
@@ -1824,7 +1864,7 @@ __global__ __launch_bounds__(256) void lm_q4k_quantize_kernel(const bf16_t* __re
             for (int l = 0; l < 32; ++l) {
                 const float v = w16_to_f32(w[blk * 256 + j * 32 + l], is_f16);
                 float qq = d1 > 0.0f ? floorf((v + m1) / d1 + 0.5f) : 0.0f;
-                qq = fminf(fmaxf(qq, 0.0f), 15.0f);
+                qq = fminf(fmaxf(qq, 0.0f), (float)QMAX);
                 q[blk * 256 + j * 32 + l] = (unsigned char)qq;
             }
             scm[blk * 8 + j] = (unsigned short)((unsigned)sc | ((unsigned)mm << 8));
@@ -1848,14 +1888,17 @@ __host__ __device__ __forceinline__ long packed_slot_row(long slot, int qkv_pair
     const long pp = slot >> 1;
     return (pp >> 5) * 64 + (pp & 31) + 32 * (slot & 1);
 }
-// plain -> the quad-interleaved GEMV layout (GemvQ8 with dd)
+// plain -> the quad-interleaved GEMV layout (GemvQ8 with dd).  Q5 (Q5_K): the low nibbles as for Q4_K, bit 4 of every value into the
+// plane qh[quad][k / 8] (q5k_hbit).
+template <bool Q5>
 __global__ __launch_bounds__(256) void lm_q4k_pack_kernel(const unsigned char* __restrict__ q, const unsigned short* __restrict__ scm, const unsigned* __restrict__ dd,
-                                                          int N, int K, int qkv_pairs, u32x4* __restrict__ qs, unsigned short* __restrict__ oscm, unsigned* __restrict__ odd) {
+                                                          int N, int K, int qkv_pairs, u32x4* __restrict__ qs, unsigned short* __restrict__ oscm, unsigned* __restrict__ odd,
+                                                          unsigned* __restrict__ qh) {
     const long nchunk = K >> 3, nquad = (N + 3) >> 2, nkb = K >> 5, nk256 = K >> 8;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nquad * nchunk; i += (long)gridDim.x * blockDim.x) {
         const long quad = i / nchunk;
         const int c = (int)(i - quad * nchunk);
-        unsigned dw[4];
+        unsigned dw[4], hb = 0;
 #pragma unroll
         for (int sl = 0; sl < 4; ++sl) {
             const long slot = 4 * quad + sl, row = packed_slot_row(slot, qkv_pairs);
@@ -1865,12 +1908,17 @@ __global__ __launch_bounds__(256) void lm_q4k_pack_kernel(const unsigned char* _
                 const unsigned bytes[2] = {b8.x, b8.y};
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v |= ((bytes[j >> 2] >> (8 * (j & 3))) & 0xFu) << (4 * j);
+                if (Q5) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) hb |= ((bytes[j >> 2] >> (8 * (j & 3) + 4)) & 1u) << q5k_hbit(sl, j);
+                }
                 if ((c & 3) == 0) oscm[q4k_scm_index(slot, c >> 2, nkb)] = scm[row * nkb + (c >> 2)];
                 if ((c & 31) == 0) odd[q4k_scm_index(slot, c >> 5, nk256)] = dd[row * nk256 + (c >> 5)];
             }
             dw[sl] = v;
         }
         qs[i] = u32x4{dw[0], dw[1], dw[2], dw[3]};
+        if (Q5) qh[i] = hb;
     }
 }
 // ---- Q6_K.  Plain form on the device: q [N][K] int8 (the 6-bit value - 32), sc [N][K / 16] int8, d [N][K / 256] fp16.
@@ -1946,14 +1994,19 @@ struct WMat {
     bf16_t* w = nullptr;        // WF_BF16 / WF_F16: row-major 16-bit values
     u32x4* qs = nullptr;        // WF_Q8 / WF_Q4K (GemvQ8)
     unsigned* sc = nullptr;
-    unsigned* dd = nullptr;     // WF_Q4K
+    unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K
+    unsigned* qh = nullptr;     // WF_Q5K: the plane of high bits [N / 4][K / 8]
     void release() {
-        for (void* p : {(void*)w, (void*)qs, (void*)sc, (void*)dd})
+        for (void* p : {(void*)w, (void*)qs, (void*)sc, (void*)dd, (void*)qh})
             if (p) (void)hipFree(p);
-        w = nullptr; qs = nullptr; sc = nullptr; dd = nullptr;
+        w = nullptr; qs = nullptr; sc = nullptr; dd = nullptr; qh = nullptr;
     }
+    // the kernels' 16-bit weight pointer: the packed formats do not use it, and Q5_K hands its plane over in that argument (the
+    // argument list, and with it the 14 preloaded dwords, stays what it is for every format)
+    const bf16_t* wptr() const { return fmt == WF_Q5K ? reinterpret_cast<const bf16_t*>(qh) : w; }
     long stream_bytes() const {   // bytes one decode pass reads of it
         const long n = (long)N * K;
+        if (fmt == WF_Q5K) return n / 2 + n / 8 + n / 16 + n / 64;   // nibbles, plane, (sc, m), (d, dmin): 5.6 bits per weight
         return fmt == WF_Q8 ? n + n / 16 : (fmt == WF_Q4K ? n / 2 + n / 16 + n / 64 : (fmt == WF_Q6K ? n + n / 4 : 2 * n));
     }
 };
@@ -2124,7 +2177,7 @@ static int lm_check_cfg(const rca_lm_config_t* c) {
     if (c->ffn > LM_KSLICE * LM_MAXSPLIT) return fail(RCA_ERR_ARG, "ffn > %d unsupported", LM_KSLICE * LM_MAXSPLIT);
     if (c->ffn > LM_KSLICE && c->ffn % LM_KSLICE) return fail(RCA_ERR_ARG, "ffn above %d must be a multiple of it", LM_KSLICE);
     if (c->vocab_size < 2 || c->n_layers < 1 || c->n_ctx < 2) return fail(RCA_ERR_ARG, "bad sizes");
-    if (c->decode_weights < 0 || c->decode_weights > 3) return fail(RCA_ERR_ARG, "decode_weights %d (0 as supplied, 1 q8_0, 2 f16, 3 q4_k)", c->decode_weights);
+    if (c->decode_weights < 0 || c->decode_weights > 4) return fail(RCA_ERR_ARG, "decode_weights %d (0 as supplied, 1 q8_0, 2 f16, 3 q4_k, 4 q5_k)", c->decode_weights);
     return RCA_OK;
 }
 
@@ -2134,9 +2187,9 @@ struct RawMat {
     int fmt = WF_BF16;
     long rows = 0, cols = 0;
     bf16_t* w16 = nullptr;      // WF_BF16 / WF_F16
-    signed char* q = nullptr;   // WF_Q8: int8 [rows][cols]; WF_Q4K: one byte per 4-bit value
-    f16_t* d = nullptr;         // WF_Q8: fp16 [rows][cols / 32]; WF_Q4K: ushort (sc | m << 8) [rows][cols / 32]
-    unsigned* dd = nullptr;     // WF_Q4K: (d | dmin << 16) [rows][cols / 256]
+    signed char* q = nullptr;   // WF_Q8: int8 [rows][cols]; WF_Q4K / WF_Q5K: one byte per 4-bit / 5-bit value (the rest as WF_Q4K)
+    f16_t* d = nullptr;         // WF_Q8: fp16 [rows][cols / 32]; WF_Q4K / WF_Q5K: ushort (sc | m << 8) [rows][cols / 32]
+    unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K: (d | dmin << 16) [rows][cols / 256]
     void release() {
         for (void* p : {(void*)w16, (void*)q, (void*)d, (void*)dd})
             if (p) (void)hipFree(p);
@@ -2144,7 +2197,7 @@ struct RawMat {
     }
     // (array, bytes per row) of every component
     int parts(void** ptr, long* row_bytes) const {
-        if (fmt == WF_Q4K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; ptr[2] = dd; row_bytes[2] = cols / 256 * 4; return 3; }
+        if (fmt == WF_Q4K || fmt == WF_Q5K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; ptr[2] = dd; row_bytes[2] = cols / 256 * 4; return 3; }
         if (fmt == WF_Q6K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 16; ptr[2] = dd; row_bytes[2] = cols / 256 * 2; return 3; }   // d: int8 scales, dd: fp16 d
         if (fmt == WF_Q8) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; return 2; }
         ptr[0] = w16; row_bytes[0] = cols * 2;
@@ -2153,8 +2206,8 @@ struct RawMat {
     int alloc(int f, long r, long c) {
         fmt = f; rows = r; cols = c;
         int rc;
-        if (f == WF_Q4K) {
-            if (c % 256) return fail(RCA_ERR_ARG, "Q4_K needs rows of a multiple of 256 values (got %ld)", c);
+        if (f == WF_Q4K || f == WF_Q5K) {
+            if (c % 256) return fail(RCA_ERR_ARG, "%s needs rows of a multiple of 256 values (got %ld)", f == WF_Q5K ? "Q5_K" : "Q4_K", c);
             if ((rc = lm_alloc((void**)&q, (size_t)r * c)) != RCA_OK || (rc = lm_alloc((void**)&d, (size_t)r * (c / 32) * 2)) != RCA_OK ||
                 (rc = lm_alloc((void**)&dd, (size_t)r * (c / 256) * 4)) != RCA_OK) { release(); return rc; }
             return RCA_OK;
@@ -2204,6 +2257,20 @@ static int lm_upload_raw(rca_lm* h, const rca_tensor_t* ts, int nt, const std::s
         hipError_t e = hipMemcpy(raw, t->data, (size_t)nblk * 210, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             lm_q6k_unblock_kernel<<<4096, 256, 0, h->stream>>>(raw, nblk, out->q, (signed char*)out->d, (f16_t*)out->dd);
+            e = hipStreamSynchronize(h->stream);
+        }
+        (void)hipFree(raw);
+        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
+        return RCA_OK;
+    }
+    if (t->dtype == RCA_Q5_K) {
+        if ((rc = out->alloc(WF_Q5K, rows, cols)) != RCA_OK) return rc;
+        const long nblk = numel / 256;
+        unsigned char* raw = nullptr;
+        if ((rc = lm_alloc((void**)&raw, (size_t)nblk * 176)) != RCA_OK) { out->release(); return rc; }
+        hipError_t e = hipMemcpy(raw, t->data, (size_t)nblk * 176, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            lm_q5k_unblock_kernel<<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, (unsigned short*)out->d, out->dd);
             e = hipStreamSynchronize(h->stream);
         }
         (void)hipFree(raw);
@@ -2273,11 +2340,12 @@ static int lm_upload_embed(rca_lm* h, const rca_tensor_t* ts, int nt, const std:
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e));
         return RCA_OK;
     }
-    if (t->dtype == RCA_Q8_0 || t->dtype == RCA_Q4_K || t->dtype == RCA_Q6_K) {
+    if (t->dtype == RCA_Q8_0 || t->dtype == RCA_Q4_K || t->dtype == RCA_Q6_K || t->dtype == RCA_Q5_K) {
         RawMat raw;
         if ((rc = lm_upload_raw(h, ts, nt, name, rows, cols, &raw)) != RCA_OK) return rc;
         if (raw.fmt == WF_Q6K) lm_q6k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>(raw.q, (const signed char*)raw.d, (const f16_t*)raw.dd, (float*)h->embed, numel);
-        else if (raw.fmt == WF_Q4K) lm_q4k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, (const unsigned short*)raw.d, raw.dd, (float*)h->embed, numel);
+        else if (raw.fmt == WF_Q4K || raw.fmt == WF_Q5K)   // the plain byte holds the whole value, 4 or 5 bits
+            lm_q4k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, (const unsigned short*)raw.d, raw.dd, (float*)h->embed, numel);
         else lm_q8_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>(raw.q, raw.d, (float*)h->embed, numel);
         hipError_t e = hipStreamSynchronize(h->stream);
         raw.release();
@@ -2308,18 +2376,29 @@ static int lm_upload_f32(const rca_tensor_t* ts, int nt, const std::string& name
     return RCA_OK;
 }
 
-// rca_lm_config_t::decode_weights applied to one plain matrix: 1 = quantise to q8_0 the way llama-quantize does, 2 = fp16.
+// rca_lm_config_t::decode_weights applied to one plain matrix: 1 = quantise to q8_0 the way llama-quantize does, 2 = fp16,
+// 3 / 4 = this build's Q4_K / Q5_K quantiser.
 // A matrix that ARRIVED quantised stays what it is.
 static int lm_raw_convert(rca_lm* h, RawMat* m, int want) {
-    if (want == 0 || m->fmt == WF_Q8 || m->fmt == WF_Q4K || m->fmt == WF_Q6K) return RCA_OK;
+    if (want == 0 || m->fmt == WF_Q8 || m->fmt == WF_Q4K || m->fmt == WF_Q6K || m->fmt == WF_Q5K) return RCA_OK;
     int rc;
     if (want == 3) {
         RawMat qd;
         if ((rc = qd.alloc(WF_Q4K, m->rows, m->cols)) != RCA_OK) return rc;
-        lm_q4k_quantize_kernel<<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 256, (unsigned char*)qd.q, (unsigned short*)qd.d, qd.dd);
+        lm_q4k_quantize_kernel<15><<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 256, (unsigned char*)qd.q, (unsigned short*)qd.d, qd.dd);
         hipError_t e = hipStreamSynchronize(h->stream);
         m->release();
         if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "Q4_K quantise: %s", hipGetErrorString(e)); }
+        *m = qd;
+        return RCA_OK;
+    }
+    if (want == 4) {
+        RawMat qd;
+        if ((rc = qd.alloc(WF_Q5K, m->rows, m->cols)) != RCA_OK) return rc;
+        lm_q4k_quantize_kernel<31><<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 256, (unsigned char*)qd.q, (unsigned short*)qd.d, qd.dd);
+        hipError_t e = hipStreamSynchronize(h->stream);
+        m->release();
+        if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "Q5_K quantise: %s", hipGetErrorString(e)); }
         *m = qd;
         return RCA_OK;
     }
@@ -2384,21 +2463,27 @@ static int lm_raw_interleave(rca_lm* h, RawMat* a, RawMat* b, RawMat* out, const
 // plain -> the layout the decode GEMV streams.  Takes ownership of `raw` (released or moved into `out`).
 static int lm_finish_mat(rca_lm* h, RawMat* raw, int qkv_pairs, WMat* out, const char* what) {
     out->fmt = raw->fmt; out->N = (int)raw->rows; out->K = (int)raw->cols;
-    if (raw->fmt == WF_Q4K) {
+    if (raw->fmt == WF_Q4K || raw->fmt == WF_Q5K) {
         const int N = out->N, K = out->K;
-        if ((K % 256) || (N % 4) || (qkv_pairs && (N % 64))) { raw->release(); return fail(RCA_ERR_ARG, "Q4_K weights: %s is %d x %d (K must be a multiple of 256, N of 4)", what, N, K); }
+        const bool q5 = raw->fmt == WF_Q5K;
+        const char* fn = q5 ? "Q5_K" : "Q4_K";
+        if ((K % 256) || (N % 4) || (qkv_pairs && (N % 64))) { raw->release(); return fail(RCA_ERR_ARG, "%s weights: %s is %d x %d (K must be a multiple of 256, N of 4)", fn, what, N, K); }
         int rc;
         const long nquad = N / 4, nchunk = K / 8, g16 = (N + 15) / 16;
         const size_t scm_bytes = (size_t)g16 * (K / 32) * 16 * 2, dd_bytes = (size_t)g16 * (K / 256) * 16 * 4;
         if ((rc = lm_alloc((void**)&out->qs, (size_t)nquad * nchunk * 16)) != RCA_OK || (rc = lm_alloc((void**)&out->sc, scm_bytes)) != RCA_OK ||
-            (rc = lm_alloc((void**)&out->dd, dd_bytes)) != RCA_OK) { raw->release(); return rc; }
+            (rc = lm_alloc((void**)&out->dd, dd_bytes)) != RCA_OK || (q5 && (rc = lm_alloc((void**)&out->qh, (size_t)nquad * nchunk * 4)) != RCA_OK)) { raw->release(); return rc; }
         (void)hipMemsetAsync(out->sc, 0, scm_bytes, h->stream);
         (void)hipMemsetAsync(out->dd, 0, dd_bytes, h->stream);
-        lm_q4k_pack_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
-                                                        (unsigned short*)out->sc, out->dd);
+        if (q5)
+            lm_q4k_pack_kernel<true><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
+                                                                  (unsigned short*)out->sc, out->dd, out->qh);
+        else
+            lm_q4k_pack_kernel<false><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
+                                                                   (unsigned short*)out->sc, out->dd, nullptr);
         hipError_t e = hipStreamSynchronize(h->stream);
         raw->release();
-        if (e != hipSuccess) return fail(RCA_ERR_HIP, "Q4_K pack of %s: %s", what, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s pack of %s: %s", fn, what, hipGetErrorString(e));
         return RCA_OK;
     }
     if (raw->fmt == WF_Q6K) {
@@ -2728,9 +2813,14 @@ static void launch_gemv_r(const GemvGeom& g, rca_lm* h, const WMat& w, const flo
     const int grid = cdiv(cdiv(N, g.R), g.bpw);
     const GemvQ8 qa{w.qs, w.sc, w.dd};
     switch (g.R) {
-        case 4: lm_gemv_kernel<M, NIT, 4, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
-        case 8: lm_gemv_kernel<M, NIT, 8, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
-        default: lm_gemv_kernel<M, NIT, 16, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.w, qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
+        case 4: lm_gemv_kernel<M, NIT, 4, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
+        case 8: lm_gemv_kernel<M, NIT, 8, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
+        default:
+            // Q5_K at NIT = 4: launch_gemv_q never leaves R = 16 (four quads x four chunks = 16 loads, twice its limit), and the instance
+            // would not fit the register file (it spills): not built
+            if constexpr (!(Q == WF_Q5K && NIT == 4))
+                lm_gemv_kernel<M, NIT, 16, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope);
+            break;
     }
 }
 template <int PRO, int EPI, int Q, int ACT = 0>
@@ -2738,10 +2828,10 @@ static void launch_gemv_q(GemvGeom g, rca_lm* h, int M, const WMat& w, const flo
                           const GemvRope& rope, hipStream_t st) {
     const int nit = cdiv(cdiv(K >> 3, 4), 64);
     // 16-byte weight loads in flight per lane: at most 16 (registers); q8_0 needs one load per row PAIR
-    const int lpr = (Q == WF_Q8 || Q == WF_Q6K) ? 2 : (Q == WF_Q4K ? 4 : 1);
-    const int max_loads = Q == WF_Q4K ? 8 : 16;   // Q4_K also holds the factors of every quad in registers
+    const int lpr = (Q == WF_Q8 || Q == WF_Q6K) ? 2 : ((Q == WF_Q4K || Q == WF_Q5K) ? 4 : 1);
+    const int max_loads = (Q == WF_Q4K || Q == WF_Q5K) ? 8 : 16;   // Q4_K / Q5_K also hold the factors of every quad in registers
     while (g.R > 4 && (g.R / lpr) * (nit == 3 ? 4 : nit) > max_loads) g.R >>= 1;
-    if ((Q == WF_Q4K || Q == WF_Q6K) && g.R < 8) g.R = 8;   // a Q4_K batch is at least two quads (one per register half); Q6_K scale loads cover two pairs
+    if ((Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K) && g.R < 8) g.R = 8;   // a Q4_K batch is at least two quads (one per register half); Q6_K scale loads cover two pairs
     if (PRO == 0 && EPI == 3 && nit > 1) {
         if (nit == 2) {
             if (M == 1) launch_gemv_r<1, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
@@ -2760,14 +2850,16 @@ static void launch_gemv_q(GemvGeom g, rca_lm* h, int M, const WMat& w, const flo
 template <int PRO, int EPI>
 static void launch_gemv(int kind, rca_lm* h, int M, const WMat& w, const float* x, float* y, int N, int K, int ldy, const GemvPro& pro,
                         const GemvRope& rope, hipStream_t st) {
-    const GemvGeom g = gemv_geom(kind, N, w.fmt == WF_Q8 || w.fmt == WF_Q4K || w.fmt == WF_Q6K);
+    const GemvGeom g = gemv_geom(kind, N, w.fmt == WF_Q8 || w.fmt == WF_Q4K || w.fmt == WF_Q6K || w.fmt == WF_Q5K);
     if (h->act_format == 1) {   // q8_1 activations on the integer dot (rca_lm_set_act_format); 16-bit matrices keep f32 activations
         if (w.fmt == WF_Q6K) return launch_gemv_q<PRO, EPI, WF_Q6K, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
         if (w.fmt == WF_Q4K) return launch_gemv_q<PRO, EPI, WF_Q4K, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+        if (w.fmt == WF_Q5K) return launch_gemv_q<PRO, EPI, WF_Q5K, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
         if (w.fmt == WF_Q8) return launch_gemv_q<PRO, EPI, WF_Q8, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
     }
     if (w.fmt == WF_Q6K) launch_gemv_q<PRO, EPI, WF_Q6K>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
     else if (w.fmt == WF_Q4K) launch_gemv_q<PRO, EPI, WF_Q4K>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+    else if (w.fmt == WF_Q5K) launch_gemv_q<PRO, EPI, WF_Q5K>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
     else if (w.fmt == WF_Q8) launch_gemv_q<PRO, EPI, WF_Q8>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
     else if (w.fmt == WF_F16) launch_gemv_q<PRO, EPI, WF_F16>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
     else launch_gemv_q<PRO, EPI, WF_BF16>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
@@ -3750,9 +3842,11 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
     const float* gS6 = WF == WF_Q6K ? reinterpret_cast<const float*>(q8.sc) + 2 * q8_sc_index((n0 >> 1) + qp, (ks >> 4) + ((tid & 3) >> 1), K >> 4) : nullptr;   // next stage: + 2 groups of 16
     // Q4_K: a thread's stage is HALF a 16-byte unit = 8 k of two adjacent slots: quad tid / 8, chunk (tid / 2) % 4, slots 2 (tid % 2) + {0, 1}
     const int q4quad = tid >> 3, q4half = tid & 1, q4slot = 4 * ((n0 >> 2) + q4quad) + 2 * q4half;
-    const uint2* gQ4 = WF == WF_Q4K ? reinterpret_cast<const uint2*>(q8.qs + ((long)(n0 >> 2) + q4quad) * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3)) + q4half : nullptr;
-    const unsigned short* gS4 = WF == WF_Q4K ? reinterpret_cast<const unsigned short*>(q8.sc) + q4k_scm_index(q4slot, ks >> 5, q_nkb) : nullptr;   // next sub-block: + 16
-    const unsigned* gD4 = WF == WF_Q4K ? q8.dd + q4k_scm_index(q4slot, 0, K >> 8) : nullptr;                                                     // super-block k / 256: + 16 each
+    constexpr bool W4 = WF == WF_Q4K || WF == WF_Q5K;   // Q5_K: the Q4_K staging + the quad's dword of high bits (arrives as W)
+    const unsigned* gH5 = WF == WF_Q5K ? reinterpret_cast<const unsigned*>(W) + ((long)(n0 >> 2) + q4quad) * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3) : nullptr;
+    const uint2* gQ4 = W4 ? reinterpret_cast<const uint2*>(q8.qs + ((long)(n0 >> 2) + q4quad) * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3)) + q4half : nullptr;
+    const unsigned short* gS4 = W4 ? reinterpret_cast<const unsigned short*>(q8.sc) + q4k_scm_index(q4slot, ks >> 5, q_nkb) : nullptr;   // next sub-block: + 16
+    const unsigned* gD4 = W4 ? q8.dd + q4k_scm_index(q4slot, 0, K >> 8) : nullptr;                                                     // super-block k / 256: + 16 each
     int q4row[2];   // LDS rows of the two slots
 #pragma unroll
     for (int i = 0; i < 2; ++i) q4row[i] = (int)packed_slot_row(4 * q4quad + 2 * q4half + i, EPI == GEMM_EPI_ROPE);
@@ -3768,9 +3862,9 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
     uint2 rdd[DW];
     auto gload_w = [&](int slot, int s) {
         const int st = min(s, nstage - 1);
-        if (WF == WF_Q4K) {
+        if (W4) {
             const uint2 t = gQ4[(long)st * 8];                       // + 4 units of 16 bytes per stage
-            rw[slot][0] = make_uint4(t.x, t.y, 0u, 0u);
+            rw[slot][0] = make_uint4(t.x, t.y, WF == WF_Q5K ? gH5[(long)st * 4] : 0u, 0u);
             rs[slot] = *reinterpret_cast<const unsigned*>(gS4 + (long)st * 16);          // (sc | m << 8) of the two slots
             rdd[slot] = *reinterpret_cast<const uint2*>(gD4 + (long)(((ks >> 5) + st) >> 3) * 16);   // (d | dmin << 16) of the two slots
         } else if (WF == WF_Q6K) {
@@ -3810,14 +3904,18 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
                 *reinterpret_cast<uint4*>(&sm[buf][0][c ? soff1 : soff0]) = hi;
                 *reinterpret_cast<uint4*>(&sm[buf][3][c ? soff1 : soff0]) = lo;
             }
-        } else if (WF == WF_Q4K) {   // .x / .y = 8 nibbles of the first / second slot; the value is dequantize_row_q4_K's (d sc) q - (dmin m)
+        } else if (W4) {   // .x / .y = 8 nibbles of the first / second slot (.z: Q5_K's high bits); the value is dequantize_row_q4_K's (d sc) q - (dmin m)
             const unsigned qw[2] = {rw[ws][0].x, rw[ws][0].y}, ddw[2] = {rdd[ws].x, rdd[ws].y};
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const unsigned scm = (rs[ws] >> (16 * c)) & 0xffffu;
                 float wv[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) wv[j] = q4k_value(ddw[c], scm, (qw[c] >> (4 * j)) & 0xFu);
+                for (int j = 0; j < 8; ++j) {
+                    unsigned qv = (qw[c] >> (4 * j)) & 0xFu;
+                    if (WF == WF_Q5K) qv |= ((rw[ws][0].z >> q5k_hbit(2 * q4half + c, j)) & 1u) << 4;
+                    wv[j] = q4k_value(ddw[c], scm, qv);
+                }
                 uint4 hi, lo;
                 split_w8(wv, hi, lo);
                 *reinterpret_cast<uint4*>(&sm[buf][0][c ? q4soff1 : q4soff0]) = hi;
@@ -4135,6 +4233,7 @@ static void launch_gemm128(rca_lm* h, const WMat& w, dim3 grid, hipStream_t st, 
         (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
         (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_Q4K>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
         (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_Q6K>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
+        (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_Q5K>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
         attr_done = true;
     }
     const GemvQ8 qa{w.qs, w.sc, w.dd};
@@ -4142,6 +4241,8 @@ static void launch_gemm128(rca_lm* h, const WMat& w, dim3 grid, hipStream_t st, 
         lm_gemm128_kernel<EPI, WF_Q6K><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.w, qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
     else if (w.fmt == WF_Q4K)
         lm_gemm128_kernel<EPI, WF_Q4K><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.w, qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
+    else if (w.fmt == WF_Q5K)
+        lm_gemm128_kernel<EPI, WF_Q5K><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.wptr(), qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
     else if (w.fmt == WF_Q8)
         lm_gemm128_kernel<EPI, WF_Q8><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.w, qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
     else if (w.fmt == WF_F16)
@@ -5104,7 +5205,7 @@ extern "C" int rca_lm_mask_head_rows(rca_lm_t* h, int32_t row_begin, int32_t row
     const long n = (long)(row_end - row_begin) * h->cfg.hidden;
     if (n > 0 && h->head.fmt == WF_Q6K)   // Q6_K (what a Q4_K_M file keeps output.weight in): the row's f32 scales
         lm_q6k_zero_row_scales_kernel<<<256, 256, 0, h->stream>>>((float*)h->head.sc, h->cfg.hidden / 16, row_begin, row_end);
-    if (n > 0 && h->head.fmt == WF_Q4K)   // Q4_K: d = dmin = 0 makes every value of the row (0 * sc) * q - (0 * m) = 0
+    if (n > 0 && (h->head.fmt == WF_Q4K || h->head.fmt == WF_Q5K))   // Q4_K / Q5_K: d = dmin = 0 makes every value of the row (0 * sc) * q - (0 * m) = 0
         lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.dd, h->cfg.hidden / 256, row_begin, row_end);
     if (n > 0 && (h->head.fmt == WF_BF16 || h->head.fmt == WF_F16)) lm_zero_rows_kernel<<<2048, 256, 0, h->stream>>>(h->head.w + (long)row_begin * h->cfg.hidden, n);   // zero bits
     if (n > 0 && h->head.fmt == WF_Q8)   // the packed q8_0 head: a row is zero when its block scales are
@@ -5212,10 +5313,10 @@ extern "C" int rca_lm_set_attn_fuse(rca_lm_t* h, int32_t enable) {
     h->fuse_attn = enable != 0;
     return RCA_OK;
 }
-// Activation format of the decode GEMVs over packed (q8_0 / Q4_K / Q6_K) matrices: 0 = f32, 1 = q8_1 blocks + integer dot products
+// Activation format of the decode GEMVs over packed (q8_0 / Q4_K / Q5_K / Q6_K) matrices: 0 = f32, 1 = q8_1 blocks + integer dot products
 // (lm_gemv_kernel<..., ACT = 1>).  The exact prefill route is made of the same launches and follows; the MFMA tiles do not.
 static bool lm_has_packed_matrix(const rca_lm* h) {
-    auto packed = [](const WMat& m) { return m.fmt == WF_Q8 || m.fmt == WF_Q4K || m.fmt == WF_Q6K; };
+    auto packed = [](const WMat& m) { return m.fmt == WF_Q8 || m.fmt == WF_Q4K || m.fmt == WF_Q6K || m.fmt == WF_Q5K; };
     bool any = packed(h->head);
     for (const LmLayer& L : h->layers) any = any || packed(L.qkv) || packed(L.o) || packed(L.gu) || packed(L.down) || (L.split_v && packed(L.vseg));
     return any;
@@ -5224,7 +5325,7 @@ extern "C" int rca_lm_set_act_format(rca_lm_t* h, int32_t fmt) {
     if (!h) return fail(RCA_ERR_ARG, "null");
     if (fmt != 0 && fmt != 1) return fail(RCA_ERR_ARG, "set_act_format: %d is neither 0 (f32) nor 1 (q8_1)", fmt);
     if (fmt == 1 && !lm_has_packed_matrix(h))
-        return fail(RCA_ERR_ARG, "set_act_format: q8_1 activations need a q8_0 / Q4_K / Q6_K projection matrix, and this handle keeps all of its matrices in 16-bit floats");
+        return fail(RCA_ERR_ARG, "set_act_format: q8_1 activations need a q8_0 / Q4_K / Q6_K or Q5_K projection matrix, and this handle keeps all of its matrices in 16-bit floats");
     { const int src = lm_settle(h); if (src != RCA_OK) return src; }
     if (h->act_format != fmt) {
         RCA_HIP(hipSetDevice(h->device));
@@ -5305,8 +5406,8 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
     return RCA_OK;
 }
 
-// the format the projection matrices are kept (and streamed) in: 0 bf16, 1 q8_0, 2 f16, 3 q4_k (4 = Q6_K, which only ever appears next to Q4_K
-// tensors); bytes = weight bytes one decode step reads
+// the format the projection matrices are kept (and streamed) in: 0 bf16, 1 q8_0, 2 f16, 3 q4_k, 5 q5_k (4 = Q6_K, which only ever appears next
+// to Q4_K / Q5_K tensors); bytes = weight bytes one decode step reads
 extern "C" int rca_lm_weight_format(const rca_lm_t* h, int32_t* fmt, int64_t* bytes_per_step) {
     if (!h || !fmt) return fail(RCA_ERR_ARG, "null");
     *fmt = h->layers.empty() ? h->head.fmt : h->layers[0].gu.fmt;
