@@ -312,6 +312,22 @@ int rca_lm_eval_async(rca_lm_t* h, const int32_t* ids, int32_t n);
  * are kept per cache).  n_tokens is not exchanged: the caller sets it, as the reference does. */
 int rca_lm_copy_kv(rca_lm_t* dst, rca_lm_t* src, int32_t n_pos);
 int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b);
+/* llama.cpp's context shift (kv_cache_seq_rm(p0, p1) followed by kv_cache_seq_add(p1, -1, p0 - p1)), restated from its published
+ * behaviour (ggml is not in this tree: parity with its bits is not pinned).  Needs 0 <= p0 <= p1 <= n_tokens (RCA_ERR_ARG otherwise,
+ * nothing touched).  With delta = p1 - p0: in every layer the K and V rows of positions [p1, n_tokens) move to [p0, n_tokens - delta),
+ * V bit for bit, every K row rotated by -delta positions -- per head and d < 32, x1 = k[d], x2 = k[d + 32] widened to f32,
+ * c / s = the handle's RoPE table entries cos / sin(delta * inv_freq[d]): k'[d] = x1 c + x2 s, k'[d + 32] = x2 c - x1 s in f32,
+ * stored as fp16 (nearest even).  Angles add, under llama3 frequency scaling too, so the row becomes the key of its new position up
+ * to that one extra fp16 rounding -- but the K / V of layers above the first were computed while attending to the removed tokens:
+ * logits after the call are those of a SHIFTED cache, not of a recompute (opt-in, never on the default path).  n_tokens becomes
+ * n_tokens - delta; rows at and above it are stale, the last logits stay readable, as after rca_lm_set_n_tokens.  delta == 0 and
+ * p1 == n_tokens (pure truncation) launch nothing.  Runs on the handle's stream and returns after one synchronisation; captured step /
+ * frame / duplex graphs stay valid (the cache does not move and positions come from the device state).  The first call that moves
+ * rows allocates a staging buffer of 2 x 2 x n_layers x 256 cache rows, freed with the handle. */
+int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1);
+/* Tests only: raw fp16 rows [n_pos][n_kv_heads][64] of positions [pos0, pos0 + n_pos) (inside n_ctx) of one layer's K and V cache,
+ * after draining the handle's stream.  Either pointer may be NULL. */
+int rca_lm_kv_read(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, uint16_t* k_host, uint16_t* v_host);
 /* run the handle's stream at the device's lowest (1) / highest (0) stream priority: background prefill next to a live session */
 int rca_lm_set_low_priority(rca_lm_t* h, int32_t enable);
 /* read / write Llama.n_tokens: the agent rolls the KV cache back by writing it

@@ -2029,6 +2029,7 @@ struct rca_lm {
     std::vector<LmLayer> layers;
     float *cos_t = nullptr, *sin_t = nullptr;
     f16_t *kc = nullptr, *vc = nullptr;  // [L][n_ctx_pad][nkv][hd]
+    f16_t* kv_stage = nullptr;           // rca_lm_kv_remove: two slabs of [K, V][L][ATT_KEYS][nkv][hd], allocated by the first call that moves rows
     long kv_layer_stride = 0;
     int n_ctx_pad = 0, n_splits = 0;
     // activations
@@ -2140,11 +2141,11 @@ extern "C" int rca_lm_destroy(rca_lm_t* h) {
     lm_drop_graphs(h);
     duplex_destroy(h->duplex);
     h->duplex = nullptr;
-    for (void* p : {(void*)h->kc, (void*)h->vc, (void*)h->x, (void*)h->xn, (void*)h->qkv, (void*)h->attn, (void*)h->hbuf,
+    for (void* p : {(void*)h->kc, (void*)h->vc, (void*)h->kv_stage, (void*)h->x, (void*)h->xn, (void*)h->qkv, (void*)h->attn, (void*)h->hbuf,
                     (void*)h->att_part, (void*)h->logits, (void*)h->probs_dev, (void*)h->probe_ids_dev, (void*)h->att_arrive, (void*)h->xh, (void*)h->xl,
                     (void*)h->gpart, (void*)h->stt, (void*)h->samp, (void*)h->swork})
         if (p) (void)hipFree(p);
-    h->kc = h->vc = nullptr;
+    h->kc = h->vc = h->kv_stage = nullptr;
     h->x = h->xn = h->qkv = h->attn = h->hbuf = h->att_part = h->logits = h->probs_dev = h->gpart = nullptr;
     h->probe_ids_dev = nullptr; h->att_arrive = nullptr; h->xh = h->xl = nullptr; h->stt = nullptr; h->samp = nullptr; h->swork = nullptr;
     if (h->h_stt) { (void)hipHostFree(h->h_stt); h->h_stt = nullptr; }
@@ -4493,6 +4494,108 @@ extern "C" int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b) {
     a->async_pending = b->async_pending = false;
     std::swap(a->kc, b->kc);
     std::swap(a->vc, b->vc);
+    return RCA_OK;
+}
+
+// ---- context shift (rca_lm_kv_remove): cache positions [p1, n) of every layer move down to [p0, n - delta), delta = p1 - p0, and
+// their keys are rotated by -delta positions.  Source and destination rows overlap whenever delta < n - p1, so nothing moves in
+// place: the rows travel in slabs of at most ATT_KEYS positions, in ascending order, through two staging slabs.  Launch i rotates
+// source slab i into stage[i % 2] (unit kind A) and copies stage[(i - 1) % 2], which launch i - 1 filled, to destination slab
+// i - 1 (kind B).  Destination slab i - 1 ends at p0 + ATT_KEYS * i, below the start p1 + ATT_KEYS * i of source slab i for any
+// delta >= 1, and the two staging slabs are different buffers: inside one launch no byte is both read and written, whatever order
+// the workgroups run in; between launches the stream orders.
+// One unit = one thread = (layer, row of the slab, kv head, quarter q): elements q * 8 .. q * 8 + 7 and their RoPE partners
+// q * 8 + 32 .. q * 8 + 39 (the pairing the QKV epilogues store) of the K row and the same 2 x 16 bytes of the V row.
+__global__ __launch_bounds__(256) void lm_kv_shift_kernel(f16_t* kc, f16_t* vc, f16_t* __restrict__ stage_w, const f16_t* __restrict__ stage_r,
+                                                          const float* __restrict__ cos_d, const float* __restrict__ sin_d,   // rows `delta` of the RoPE tables
+                                                          long layer_stride, int n_layers, int nkv, int src_pos, int n_src, int dst_pos, int n_dst) {
+    const long stage_v = (long)n_layers * ATT_KEYS * nkv * 64;     // a staging slab holds its K rows first, its V rows stage_v elements later
+    const long ua = (long)n_layers * n_src * nkv * 4, ub = (long)n_layers * n_dst * nkv * 4;
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < ua + ub; u += (long)gridDim.x * 256) {
+        const bool rot = u < ua;
+        long t = rot ? u : u - ua;
+        const int npos = rot ? n_src : n_dst;
+        const int q = (int)(t & 3);
+        t >>= 2;
+        const int kvh = (int)(t % nkv);
+        t /= nkv;
+        const int r = (int)(t % npos), l = (int)(t / npos);
+        const long so = (((long)l * ATT_KEYS + r) * nkv + kvh) * 64 + q * 8;
+        const long co = (long)l * layer_stride + ((long)((rot ? src_pos : dst_pos) + r) * nkv + kvh) * 64 + q * 8;
+        if (rot) {
+            const f16x8 k1 = *reinterpret_cast<const f16x8*>(kc + co), k2 = *reinterpret_cast<const f16x8*>(kc + co + 32);
+            const u32x4 v1 = *reinterpret_cast<const u32x4*>(vc + co), v2 = *reinterpret_cast<const u32x4*>(vc + co + 32);
+            float c[8], s[8];
+            *reinterpret_cast<f32x4*>(c) = *reinterpret_cast<const f32x4*>(cos_d + q * 8);
+            *reinterpret_cast<f32x4*>(c + 4) = *reinterpret_cast<const f32x4*>(cos_d + q * 8 + 4);
+            *reinterpret_cast<f32x4*>(s) = *reinterpret_cast<const f32x4*>(sin_d + q * 8);
+            *reinterpret_cast<f32x4*>(s + 4) = *reinterpret_cast<const f32x4*>(sin_d + q * 8 + 4);
+            f16x8 o1, o2;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float x1 = (float)k1[j], x2 = (float)k2[j];
+                o1[j] = (f16_t)(x1 * c[j] + x2 * s[j]);       // the inverse of the epilogues' x1 c - x2 s, x2 c + x1 s; f32, then fp16 nearest-even
+                o2[j] = (f16_t)(x2 * c[j] - x1 * s[j]);
+            }
+            *reinterpret_cast<f16x8*>(stage_w + so) = o1;
+            *reinterpret_cast<f16x8*>(stage_w + so + 32) = o2;
+            *reinterpret_cast<u32x4*>(stage_w + stage_v + so) = v1;
+            *reinterpret_cast<u32x4*>(stage_w + stage_v + so + 32) = v2;
+        } else {
+            const u32x4 k1 = *reinterpret_cast<const u32x4*>(stage_r + so), k2 = *reinterpret_cast<const u32x4*>(stage_r + so + 32);
+            const u32x4 v1 = *reinterpret_cast<const u32x4*>(stage_r + stage_v + so), v2 = *reinterpret_cast<const u32x4*>(stage_r + stage_v + so + 32);
+            *reinterpret_cast<u32x4*>(kc + co) = k1;
+            *reinterpret_cast<u32x4*>(kc + co + 32) = k2;
+            *reinterpret_cast<u32x4*>(vc + co) = v1;
+            *reinterpret_cast<u32x4*>(vc + co + 32) = v2;
+        }
+    }
+}
+extern "C" int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    { const int rc = lm_settle(h); if (rc != RCA_OK) return rc; }
+    const int n = h->n_tokens;
+    if (p0 < 0 || p0 > p1 || p1 > n) return fail(RCA_ERR_ARG, "kv_remove: [%d, %d) is not a span of the %d cached positions", p0, p1, n);
+    const int delta = p1 - p0, tail = n - p1;
+    if (delta > 0 && tail > 0) {
+        const rca_lm_config_t& c = h->cfg;
+        RCA_HIP(hipSetDevice(h->device));
+        const long slab = 2L * c.n_layers * ATT_KEYS * c.n_kv_heads * 64;      // elements: K rows, then V rows
+        if (!h->kv_stage) {
+            const int rc = lm_alloc((void**)&h->kv_stage, (size_t)slab * 2 * sizeof(f16_t));
+            if (rc != RCA_OK) return rc;
+        }
+        const int nslab = (tail + ATT_KEYS - 1) / ATT_KEYS;
+        const float* cos_d = h->cos_t + (long)delta * 32;      // delta < n <= n_ctx: inside the tables (a borrower reads its owner's)
+        const float* sin_d = h->sin_t + (long)delta * 32;
+        for (int i = 0; i <= nslab; ++i) {
+            const int n_src = i < nslab ? std::min(ATT_KEYS, tail - ATT_KEYS * i) : 0;
+            const int n_dst = i > 0 ? std::min(ATT_KEYS, tail - ATT_KEYS * (i - 1)) : 0;
+            const long units = (long)c.n_layers * (n_src + n_dst) * c.n_kv_heads * 4;
+            const int blocks = (int)std::min<long>((units + 255) / 256, 2048);
+            lm_kv_shift_kernel<<<blocks, 256, 0, h->stream>>>(h->kc, h->vc, h->kv_stage + (long)(i & 1) * slab, h->kv_stage + (long)((i + 1) & 1) * slab,
+                                                              cos_d, sin_d, h->kv_layer_stride, c.n_layers, c.n_kv_heads,
+                                                              p1 + ATT_KEYS * i, n_src, p0 + ATT_KEYS * (i - 1), n_dst);
+            RCA_LAUNCH_CHECK();
+        }
+        RCA_HIP(hipStreamSynchronize(h->stream));
+    }
+    h->n_tokens = n - delta;
+    return RCA_OK;
+}
+// tests only: raw fp16 rows [n_pos][n_kv_heads][64] of one layer's K and / or V cache
+extern "C" int rca_lm_kv_read(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, uint16_t* k_host, uint16_t* v_host) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    const rca_lm_config_t& c = h->cfg;
+    if (layer < 0 || layer >= c.n_layers) return fail(RCA_ERR_ARG, "kv_read: layer %d outside [0, %d)", layer, c.n_layers);
+    if (pos0 < 0 || n_pos < 0 || pos0 > c.n_ctx - n_pos) return fail(RCA_ERR_ARG, "kv_read: positions [%d, %d + %d) outside the context of %d", pos0, pos0, n_pos, c.n_ctx);
+    RCA_HIP(hipSetDevice(h->device));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    h->async_pending = false;
+    const long off = (long)layer * h->kv_layer_stride + (long)pos0 * c.n_kv_heads * 64;
+    const size_t bytes = (size_t)n_pos * c.n_kv_heads * 64 * sizeof(f16_t);
+    if (k_host && bytes) RCA_HIP(hipMemcpy(k_host, h->kc + off, bytes, hipMemcpyDeviceToHost));
+    if (v_host && bytes) RCA_HIP(hipMemcpy(v_host, h->vc + off, bytes, hipMemcpyDeviceToHost));
     return RCA_OK;
 }
 extern "C" int rca_lm_set_low_priority(rca_lm_t* h, int32_t enable) {

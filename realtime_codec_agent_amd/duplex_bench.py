@@ -29,7 +29,10 @@ def session_resources_kwargs(seed: int = 0, n_ctx: int = 16384, weight_format=No
 
 
 def run_duplex_bench(dev=None, secs: float = 125.0, chunk_size_secs: float = 0.08, n_ctx: int = 16384, lm_steps_probe: int = 256,
-                     max_context_secs: float = 80.0, trim_by_secs: float = 20.0, weight_format=None, duplex_graph: bool = True) -> dict:
+                     max_context_secs: float = 80.0, trim_by_secs: float = 20.0, weight_format=None, duplex_graph: bool = True,
+                     kv_trim_mode: str = "recompute") -> dict:
+    """kv_trim_mode: RealtimeAgent's knob ("recompute", the default session bench.py measures, or "shift"; the result's "kv_shadow" is
+    False in shift mode: no twin exists)."""
     import torch
     from .llm import LMConfig
     from .realtime_agent_config import RealtimeAgentConfig
@@ -44,7 +47,7 @@ def run_duplex_bench(dev=None, secs: float = 125.0, chunk_size_secs: float = 0.0
     config = RealtimeAgentConfig(chunk_size_secs=chunk_size_secs, use_whisper=False, top_k=100, temperature=1.0, seed=42,
                                  max_context_secs=max_context_secs, trim_by_secs=trim_by_secs,
                                  force_trans_after_inactivity_secs=0.0, force_response_after_inactivity_secs=0.0)
-    agent = RealtimeAgent(resources=res, config=config)
+    agent = RealtimeAgent(resources=res, config=config, kv_trim_mode=kv_trim_mode)
     agent.use_duplex_graph = duplex_graph       # False: one replay per LM chunk between the separate codec calls (the round-2 path)
     load_s = time.perf_counter() - t0
     n = int(secs * 16000)

@@ -633,6 +633,24 @@ class LlamaForAlternatingCodeChannels:
         other._input_ids[:n] = tmp
         self._logits_valid = other._logits_valid = False
 
+    # ------------------------------------------------------------------ context shift (sliding-window trim without re-evaluation)
+    def kv_remove(self, p0: int, p1: int) -> None:
+        """llama.cpp's context shift (rca_lm_kv_remove): drop cache positions [p0, p1) and slide positions [p1, n_tokens) down by
+        p1 - p0, re-rotating their keys; n_tokens shrinks by p1 - p0 and the last logits stay readable.  Logits after a kv_remove
+        are those of a shifted cache, not those of a recompute: the surviving keys and values of every layer above the first were
+        computed while attending to the removed tokens, and each shift adds one fp16 rounding to the surviving keys."""
+        p0, p1, n = int(p0), int(p1), self.n_tokens
+        N.check(self._lib.rca_lm_kv_remove(self._h, p0, p1), "rca_lm_kv_remove")
+        self._input_ids[p0:n - (p1 - p0)] = self._input_ids[p1:n].copy()
+
+    def kv_read(self, layer: int, pos0: int, n_pos: int):
+        """Tests only (rca_lm_kv_read): the raw K and V cache rows [n_pos, n_kv_heads, 64] of one layer as float16."""
+        k = np.empty((int(n_pos), self.config.n_kv_heads, 64), np.float16)
+        v = np.empty_like(k)
+        N.check(self._lib.rca_lm_kv_read(self._h, int(layer), int(pos0), int(n_pos), k.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                         v.ctypes.data_as(C.POINTER(C.c_uint16))), "rca_lm_kv_read")
+        return k, v
+
     def mask_head_rows(self, row_begin: int, row_end: int) -> None:
         """Zero lm_head rows (random-init models: keep sampling on codec tokens like a trained model in audio mode)."""
         N.check(self._lib.rca_lm_mask_head_rows(self._h, int(row_begin), int(row_end)), "rca_lm_mask_head_rows")

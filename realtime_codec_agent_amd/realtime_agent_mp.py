@@ -64,7 +64,7 @@ def _snapshot(agent) -> RealtimeAgentMultiprocessingInfo:
         audio_history=agent.get_audio_history(), external_llm_messages=agent.get_external_llm_messages())
 
 
-def _worker_main(commands, results, epoch, config, self_play_mode, gpu_id, resources_factory, resources_kwargs):
+def _worker_main(commands, results, epoch, config, self_play_mode, gpu_id, resources_factory, resources_kwargs, kv_trim_mode="recompute"):
     """Worker process: build the session, then serve the command channel until told to stop."""
     try:
         if gpu_id is not None:
@@ -76,7 +76,7 @@ def _worker_main(commands, results, epoch, config, self_play_mode, gpu_id, resou
         else:
             from .realtime_agent_resources import RealtimeAgentResources
             resources = RealtimeAgentResources(**resources_kwargs)
-        agent = RealtimeAgent(resources=resources, config=config, self_play_mode=self_play_mode)
+        agent = RealtimeAgent(resources=resources, config=config, self_play_mode=self_play_mode, kv_trim_mode=kv_trim_mode)
     except BaseException:
         results.put((_FAILED, traceback.format_exc()))
         return
@@ -120,10 +120,10 @@ def _worker_main(commands, results, epoch, config, self_play_mode, gpu_id, resou
 class RealtimeAgentMultiprocessing:
     def __init__(self, wait_until_running: bool = True, config: RealtimeAgentConfig = None, self_play_mode: bool = False,
                  gpu_id: Optional[int] = None, idle_tol_secs: float = 1.0, resources_factory: Optional[Callable[..., Any]] = None,
-                 start_timeout_secs: float = 600.0, **resources_kwargs):
+                 start_timeout_secs: float = 600.0, kv_trim_mode: str = "recompute", **resources_kwargs):
         """Same arguments as the reference (:795-803); `idle_tol_secs` is accepted and unused (the worker blocks instead of polling).
         resources_factory: optional picklable callable building the resources object inside the worker (tests use fakes);
-        default RealtimeAgentResources(**resources_kwargs)."""
+        default RealtimeAgentResources(**resources_kwargs).  kv_trim_mode: RealtimeAgent's knob of the same name, for the worker's agent."""
         ctx = mp.get_context("spawn")           # a forked child of a process that has touched the GPU is not usable
         self._commands = ctx.Queue()
         self._results = ctx.Queue()
@@ -136,7 +136,7 @@ class RealtimeAgentMultiprocessing:
         self._pending: List[tuple] = []          # results read while waiting for a control reply
         self._process = ctx.Process(target=_worker_main, daemon=True,
                                     args=(self._commands, self._results, self._epoch, config, self_play_mode, gpu_id, resources_factory,
-                                          resources_kwargs))
+                                          resources_kwargs, kv_trim_mode))
         self._process.start()
         if wait_until_running:
             self.wait_until_running()
