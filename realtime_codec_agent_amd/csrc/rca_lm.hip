@@ -2133,6 +2133,25 @@ static rca_lm::GraphSet& lm_graph_set(rca_lm* h) {
     hit->last_use = ++h->gset_clock;
     return *hit;
 }
+// Capture what `enqueue` (a callable returning an rca status) puts on `st` into *exec, in thread-local mode so that other threads'
+// HIP calls do not break it.  The capture is ended whether or not `enqueue` failed; its failure is returned as it is.  *exec stays
+// null unless the graph was instantiated; the upload makes the device-side copy now, not inside the first frame that replays it
+// (pre-captured graphs: first trim frame, first frame of a bucket).  `tag` names the caller in the error text.
+template <class F>
+static int lm_capture(hipStream_t st, hipGraphExec_t* exec, const char* tag, F&& enqueue) {
+    hipGraph_t g = nullptr;
+    RCA_HIP(hipStreamSynchronize(st));
+    RCA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    hipError_t e = hipStreamEndCapture(st, &g);
+    if (rc != RCA_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s capture: %s", tag, hipGetErrorString(e));
+    e = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) { *exec = nullptr; return fail(RCA_ERR_HIP, "%s graph instantiate: %s", tag, hipGetErrorString(e)); }
+    (void)hipGraphUpload(*exec, st);
+    return RCA_OK;
+}
 
 extern "C" int rca_lm_destroy(rca_lm_t* h) {
     if (!h) return RCA_OK;
@@ -2780,6 +2799,21 @@ extern "C" int rca_lm_create_shared(rca_lm_t* parent, int32_t n_ctx, int32_t log
 }
 
 // ------------------------------------------------------------------------- forward pass (M tokens)
+// The one place that turns a matrix's runtime format into a template argument: f(std::integral_constant<int, WF_...>{}).  A new
+// format is added here (and to WF_FORMATS) and every launcher below sees it.
+static constexpr int WF_FORMATS[] = {WF_BF16, WF_Q8, WF_F16, WF_Q4K, WF_Q6K, WF_Q5K};
+constexpr bool wf_packed(int fmt) { return fmt == WF_Q8 || fmt == WF_Q4K || fmt == WF_Q6K || fmt == WF_Q5K; }
+template <class F>
+static void wf_dispatch(int fmt, F&& f) {
+    switch (fmt) {
+        case WF_Q6K: return f(std::integral_constant<int, WF_Q6K>{});
+        case WF_Q4K: return f(std::integral_constant<int, WF_Q4K>{});
+        case WF_Q5K: return f(std::integral_constant<int, WF_Q5K>{});
+        case WF_Q8: return f(std::integral_constant<int, WF_Q8>{});
+        case WF_F16: return f(std::integral_constant<int, WF_F16>{});
+        default: return f(std::integral_constant<int, WF_BF16>{});
+    }
+}
 // Launch geometry of the decode GEMVs: R rows per batch (weights of a whole batch are in flight per wave before any is
 // consumed) and batches per workgroup.  Defaults are sized for the 256 CUs (>= 2 workgroups each, all resident at once);
 // RCA_GEMV_<QKV|O|GU|DOWN|HEAD>="R,batches" overrides one for tuning runs (scripts/lm_gemv_sweep.sh).  Results do not
@@ -2851,19 +2885,13 @@ static void launch_gemv_q(GemvGeom g, rca_lm* h, int M, const WMat& w, const flo
 template <int PRO, int EPI>
 static void launch_gemv(int kind, rca_lm* h, int M, const WMat& w, const float* x, float* y, int N, int K, int ldy, const GemvPro& pro,
                         const GemvRope& rope, hipStream_t st) {
-    const GemvGeom g = gemv_geom(kind, N, w.fmt == WF_Q8 || w.fmt == WF_Q4K || w.fmt == WF_Q6K || w.fmt == WF_Q5K);
-    if (h->act_format == 1) {   // q8_1 activations on the integer dot (rca_lm_set_act_format); 16-bit matrices keep f32 activations
-        if (w.fmt == WF_Q6K) return launch_gemv_q<PRO, EPI, WF_Q6K, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-        if (w.fmt == WF_Q4K) return launch_gemv_q<PRO, EPI, WF_Q4K, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-        if (w.fmt == WF_Q5K) return launch_gemv_q<PRO, EPI, WF_Q5K, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-        if (w.fmt == WF_Q8) return launch_gemv_q<PRO, EPI, WF_Q8, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-    }
-    if (w.fmt == WF_Q6K) launch_gemv_q<PRO, EPI, WF_Q6K>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-    else if (w.fmt == WF_Q4K) launch_gemv_q<PRO, EPI, WF_Q4K>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-    else if (w.fmt == WF_Q5K) launch_gemv_q<PRO, EPI, WF_Q5K>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-    else if (w.fmt == WF_Q8) launch_gemv_q<PRO, EPI, WF_Q8>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-    else if (w.fmt == WF_F16) launch_gemv_q<PRO, EPI, WF_F16>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-    else launch_gemv_q<PRO, EPI, WF_BF16>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+    const GemvGeom g = gemv_geom(kind, N, wf_packed(w.fmt));
+    wf_dispatch(w.fmt, [&](auto wf) {
+        constexpr int Q = decltype(wf)::value;
+        if constexpr (wf_packed(Q))   // q8_1 activations on the integer dot (rca_lm_set_act_format); 16-bit matrices keep f32 activations
+            if (h->act_format == 1) return launch_gemv_q<PRO, EPI, Q, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+        launch_gemv_q<PRO, EPI, Q>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+    });
 }
 
 // Merge of the splits of one (token, head) row by ONE wave, lane <-> dim, in split order.  Latency code: every load it will ever
@@ -3731,40 +3759,57 @@ static void launch_attention_mfma(rca_lm* h, int M, int nsp_launch, const f16_t*
 // attention split blocks needed by a pass of m tokens on top of the current context
 static int lm_splits_needed(const rca_lm* h, int m) { return std::min(h->n_splits, (h->n_tokens + m + ATT_KEYS - 1) / ATT_KEYS); }
 
+// The five projections of a decode pass over M <= 2 tokens: each function owns the argument list of its launch, so whoever runs a
+// stage (lm_enqueue_pass, the head behind a prefill, rca_lm_gemv_tap for the tests) runs the same launch.
+static const GemvPro nopro{nullptr, nullptr, 0.0f, 0};
+static const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+static void lm_launch_qkv(rca_lm* h, int l, int M, hipStream_t st) {   // RMSNorm(x) -> [q; k; v] + RoPE -> qkv, KV cache of layer l
+    const rca_lm_config_t& c = h->cfg;
+    const LmLayer& L = h->layers[l];
+    const int QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim;
+    const GemvPro pro{h->x, L.attn_norm, c.rms_eps, 0};
+    GemvRope rope{h->cos_t, h->sin_t, h->kc + (long)l * h->kv_layer_stride, h->vc + (long)l * h->kv_layer_stride, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
+    launch_gemv<1, 2>(GEMV_QKV, h, M, L.qkv, nullptr, h->qkv, L.qkv.N, c.hidden, QKV, pro, rope, st);
+    if (L.split_v) {   // the V projection of this layer is kept in another format than Q / K (a Q4_K_M file): its own launch
+        rope.row_base = L.qkv.N;
+        launch_gemv<1, 2>(GEMV_QKV, h, M, L.vseg, nullptr, h->qkv, L.vseg.N, c.hidden, QKV, pro, rope, st);
+    }
+}
+static void lm_launch_o(rca_lm* h, int l, int M, hipStream_t st) {   // x += O attn
+    const int AO = h->cfg.n_heads * h->cfg.head_dim;
+    launch_gemv<0, 3>(GEMV_O, h, M, h->layers[l].o, h->attn, h->x, h->cfg.hidden, AO, h->cfg.hidden, nopro, norope, st);
+}
+static void lm_launch_gu(rca_lm* h, int l, int M, hipStream_t st) {   // RMSNorm(x) -> silu(gate) * up -> hbuf
+    const rca_lm_config_t& c = h->cfg;
+    const LmLayer& L = h->layers[l];
+    launch_gemv<1, 1>(GEMV_GU, h, M, L.gu, nullptr, h->hbuf, 2 * c.ffn, c.hidden, c.ffn, GemvPro{h->x, L.ffn_norm, c.rms_eps, 0}, norope, st);
+}
+static void lm_launch_down(rca_lm* h, int l, int M, hipStream_t st) {   // x += down hbuf
+    launch_gemv<0, 3>(GEMV_DOWN, h, M, h->layers[l].down, h->hbuf, h->x, h->cfg.hidden, h->cfg.ffn, h->cfg.hidden, nopro, norope, st);
+}
+// final RMSNorm + head over M rows of x -> out[M][vocab]; only_last (M = 1): the row is the pass's last token
+static void lm_launch_head(rca_lm* h, int M, hipStream_t st, float* out, bool only_last) {
+    const rca_lm_config_t& c = h->cfg;
+    launch_gemv<1, 0>(GEMV_HEAD, h, M, h->head, nullptr, out, c.vocab_size, c.hidden, c.vocab_size, GemvPro{h->x, h->final_norm, c.rms_eps, only_last ? 1 : 0}, norope, st);
+}
+
 // Enqueue one decode pass over the M <= 2 tokens whose ids / position are already in h->stt (device).
 // want_logits: 0 none, 1 last token only, 2 every token (logits_all).
 // Per layer: [norm+QKV+RoPE/KV-write] -> [split attention] -> [combine] -> [O proj + residual] -> [norm+gate/up+SwiGLU] -> [down + residual]
 // nsp_launch: attention split blocks to launch (>= ceil((n_tokens + M) / ATT_KEYS); later splits exit at once).
 static int lm_enqueue_pass(rca_lm* h, int M, int want_logits, hipStream_t st, int nsp_launch, bool skip_embed = false) {
     const rca_lm_config_t& c = h->cfg;
-    const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn;
     if (M < 1 || M > LM_GEMV_M) return fail(RCA_ERR_ARG, "decode pass of %d tokens", M);
-    const GemvPro nopro{nullptr, nullptr, 0.0f, 0};
-    GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
-    const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    float* x = h->x;
-    if (!skip_embed) lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, x, H, c.vocab_size);   // (inside a frame graph the previous step's sampler has gathered the rows)
+    if (!skip_embed) lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, h->x, c.hidden, c.vocab_size);   // (inside a frame graph the previous step's sampler has gathered the rows)
     for (int l = 0; l < c.n_layers; ++l) {
-        const LmLayer& L = h->layers[l];
-        f16_t* kc = h->kc + (long)l * h->kv_layer_stride;
-        f16_t* vc = h->vc + (long)l * h->kv_layer_stride;
-        rope.kc = kc; rope.vc = vc;
-        launch_gemv<1, 2>(GEMV_QKV, h, M, L.qkv, nullptr, h->qkv, L.qkv.N, H, QKV, GemvPro{x, L.attn_norm, c.rms_eps, 0}, rope, st);
-        if (L.split_v) {   // the V projection of this layer is kept in another format than Q / K (a Q4_K_M file): its own launch
-            rope.row_base = L.qkv.N;
-            launch_gemv<1, 2>(GEMV_QKV, h, M, L.vseg, nullptr, h->qkv, L.vseg.N, H, QKV, GemvPro{x, L.attn_norm, c.rms_eps, 0}, rope, st);
-            rope.row_base = 0;
-        }
-        launch_attention_mfma(h, M, nsp_launch, kc, vc, st);
-        launch_gemv<0, 3>(GEMV_O, h, M, L.o, h->attn, x, H, AO, H, nopro, norope, st);
-        launch_gemv<1, 1>(GEMV_GU, h, M, L.gu, nullptr, h->hbuf, 2 * F, H, F, GemvPro{x, L.ffn_norm, c.rms_eps, 0}, norope, st);
-        launch_gemv<0, 3>(GEMV_DOWN, h, M, L.down, h->hbuf, x, H, F, H, nopro, norope, st);
+        lm_launch_qkv(h, l, M, st);
+        launch_attention_mfma(h, M, nsp_launch, h->kc + (long)l * h->kv_layer_stride, h->vc + (long)l * h->kv_layer_stride, st);
+        lm_launch_o(h, l, M, st);
+        lm_launch_gu(h, l, M, st);
+        lm_launch_down(h, l, M, st);
     }
-    if (want_logits) {
-        const int only_last = want_logits == 1 ? 1 : 0;
-        launch_gemv<1, 0>(GEMV_HEAD, h, only_last ? 1 : M, h->head, nullptr, h->logits, c.vocab_size, H, c.vocab_size,
-                          GemvPro{x, h->final_norm, c.rms_eps, only_last}, norope, st);
-    }
+    if (want_logits == 1) lm_launch_head(h, 1, st, h->logits, true);
+    else if (want_logits) lm_launch_head(h, M, st, h->logits, false);
     RCA_LAUNCH_CHECK();
     return RCA_OK;
 }
@@ -4169,7 +4214,6 @@ static int lm_enqueue_prefill_tile(rca_lm* h, int M, hipStream_t st, int nsp_lau
     const rca_lm_config_t& c = h->cfg;
     const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn;
     GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
-    const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
     float* x = h->x;
     lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, x, H, c.vocab_size);
     for (int l = 0; l < c.n_layers; ++l) {
@@ -4230,32 +4274,24 @@ static void launch_gemm128(rca_lm* h, const WMat& w, dim3 grid, hipStream_t st, 
                            float* y, int ldy, bf16_t* oh, bf16_t* ol, GemvRope rope, int nseq) {
     static bool attr_done = false;
     if (!attr_done) {   // the four-tile variants need 80 KB of LDS
-        (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_Q8>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
-        (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
-        (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_Q4K>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
-        (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_Q6K>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
-        (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, WF_Q5K>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
+        for (int fmt : WF_FORMATS)
+            wf_dispatch(fmt, [](auto wf) {
+                if constexpr (decltype(wf)::value != WF_BF16)
+                    (void)hipFuncSetAttribute((const void*)lm_gemm128_kernel<EPI, decltype(wf)::value>, hipFuncAttributeMaxDynamicSharedMemorySize, G128_LDS_T(4));
+            });
         attr_done = true;
     }
     const GemvQ8 qa{w.qs, w.sc, w.dd};
-    if (w.fmt == WF_Q6K)
-        lm_gemm128_kernel<EPI, WF_Q6K><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.w, qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
-    else if (w.fmt == WF_Q4K)
-        lm_gemm128_kernel<EPI, WF_Q4K><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.w, qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
-    else if (w.fmt == WF_Q5K)
-        lm_gemm128_kernel<EPI, WF_Q5K><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.wptr(), qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
-    else if (w.fmt == WF_Q8)
-        lm_gemm128_kernel<EPI, WF_Q8><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.w, qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
-    else if (w.fmt == WF_F16)
-        lm_gemm128_kernel<EPI, WF_F16><<<grid, 256, G128_LDS_T(4), st>>>(h->stt, w.w, qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
-    else
-        lm_gemm128_kernel<EPI, WF_BF16><<<grid, 256, G128_LDS_T(3), st>>>(h->stt, w.w, qa, xh, xl, N, K, kslice, y, ldy, oh, ol, h->gpart, rope, nseq);
+    wf_dispatch(w.fmt, [&](auto wf) {   // bf16 fragments go to the MFMA as they are: three tiles per stage, not four
+        constexpr int WF = decltype(wf)::value;
+        lm_gemm128_kernel<EPI, WF><<<grid, 256, WF == WF_BF16 ? G128_LDS_T(3) : G128_LDS_T(4), st>>>(h->stt, w.wptr(), qa, xh, xl, N, K, kslice, y, ldy, oh, ol,
+                                                                                                 h->gpart, rope, nseq);
+    });
 }
 static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch) {
     const rca_lm_config_t& c = h->cfg;
     const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn;
     GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
-    const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
     const int so = g128_splits(H, AO), sg = g128_splits(2 * F, H), sd = g128_splits(H, F);
     const int tbz = cdiv(M, 128);   // token blocks of this pass
     // A projection whose token blocks alone put `seq_min` workgroups on the chip is run with every workgroup walking the k slices itself
@@ -4314,14 +4350,32 @@ static int lm_settle(rca_lm* h) {
     }
     return RCA_OK;
 }
-static int lm_push_state(rca_lm* h, const int32_t* ids, int m, hipStream_t st) {
+// The next pass as the device will read it, into the pinned staging block: KV position, m and the m ids.  The copy to the device is
+// the caller's (a captured graph's first node, or lm_push_state); the rng counter / out_token stay device-owned.
+static void lm_stage_state(rca_lm* h, const int32_t* ids, int m) {
     h->h_stt->n_tokens = h->n_tokens;
     h->h_stt->m = m;
     for (int i = 0; i < m; ++i) h->h_stt->ids[i] = ids[i];
-    // n_tokens, m and the m ids only; rng counter / out_token stay device-owned
-    RCA_HIP(hipMemcpyAsync(h->stt, h->h_stt, 8 + 4 * (size_t)std::max(m, 16), hipMemcpyHostToDevice, st));
+}
+static size_t lm_state_bytes(int m) { return 8 + 4 * (size_t)std::max(m, 16); }   // n_tokens, m and the m ids only
+static int lm_push_state(rca_lm* h, const int32_t* ids, int m, hipStream_t st) {
+    lm_stage_state(h, ids, m);
+    RCA_HIP(hipMemcpyAsync(h->stt, h->h_stt, lm_state_bytes(m), hipMemcpyHostToDevice, st));
     return RCA_OK;
 }
+
+// Context buckets of the captured decode graphs: bucket b launches min(n_splits, 4 << b) attention splits, the last bucket all of
+// them.  A call of m tokens takes the first bucket that covers the splits it needs (cap_bucket >= 0, rca_duplex_precapture: that one).
+struct LmBucket { int bucket, nsp_launch; };
+static LmBucket lm_bucket(const rca_lm* h, int m, int cap_bucket) {
+    const int need = lm_splits_needed(h, m);
+    int b = 0;
+    while (b + 1 < LM_GRAPH_BUCKETS && (4 << b) < need) ++b;
+    if (cap_bucket >= 0) b = cap_bucket;
+    return {b, b + 1 == LM_GRAPH_BUCKETS ? h->n_splits : std::min(h->n_splits, 4 << b)};
+}
+// the rule above can choose bucket b on this handle: the bucket before it does not launch every split yet
+static bool lm_bucket_reachable(const rca_lm* h, int b) { return b == 0 || (4 << (b - 1)) < h->n_splits; }
 
 extern "C" int rca_lm_reset(rca_lm_t* h) {
     if (!h) return fail(RCA_ERR_ARG, "null");
@@ -4378,7 +4432,7 @@ static int lm_eval_impl(rca_lm_t* h, const int32_t* ids, int32_t n, bool wait_la
         const int tile = big ? LM_MAXM : LM_TILE32;
         // A background tile (rca_lm_eval_async of one pass: kv_shadow.py feeds one per few frames) is ~230 launches; issued eagerly
         // they cost the calling frame ~2 ms of host time before its own replay is even launched (tile frames 9.5 ms against a median
-        // of 4.4).  The third pass of a size on this cache is captured and replayed from then on: one launch.  (First: eager --
+        // of 4.4).  The second pass of a size on this cache is captured and replayed from then on: one launch.  (First: eager --
         // the launchers' one-time attribute calls; the geometry of a pass depends on its token count only, the context is read
         // from the device state.)
         static const bool tile_graphs = !(getenv("RCA_LM_TILE_GRAPHS") && atoi(getenv("RCA_LM_TILE_GRAPHS")) == 0) &&
@@ -4394,28 +4448,16 @@ static int lm_eval_impl(rca_lm_t* h, const int32_t* ids, int32_t n, bool wait_la
                 gs.tile_m[slot] = n; gs.tile_seen[slot] = 0;
             }
             if (++gs.tile_seen[slot] >= 2) {
-                h->h_stt->n_tokens = h->n_tokens;
-                h->h_stt->m = n;
-                for (int i = 0; i < n; ++i) h->h_stt->ids[i] = ids[i];
+                lm_stage_state(h, ids, n);
                 if (!gs.tile_g[slot]) {
-                    hipGraph_t g = nullptr;
-                    RCA_HIP(hipStreamSynchronize(st));
-                    RCA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                    hipError_t e = hipMemcpyAsync(h->stt, h->h_stt, 8 + 4 * (size_t)std::max(n, 16), hipMemcpyHostToDevice, st);
-                    rc = e == hipSuccess ? lm_enqueue_prefill_tile128(h, n, st, 1) : fail(RCA_ERR_HIP, "tile capture memcpy: %s", hipGetErrorString(e));
-                    if (rc == RCA_OK) {
-                        const rca_lm_config_t& c = h->cfg;
-                        const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-                        launch_gemv<1, 0>(GEMV_HEAD, h, 1, h->head, nullptr, h->logits, c.vocab_size, c.hidden, c.vocab_size,
-                                          GemvPro{h->x, h->final_norm, c.rms_eps, 1}, norope, st);
-                    }
-                    hipError_t e2 = hipStreamEndCapture(st, &g);
-                    if (rc != RCA_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-                    if (e2 != hipSuccess) return fail(RCA_ERR_HIP, "tile capture: %s", hipGetErrorString(e2));
-                    e2 = hipGraphInstantiate(&gs.tile_g[slot], g, nullptr, nullptr, 0);
-                    (void)hipGraphDestroy(g);
-                    if (e2 != hipSuccess) { gs.tile_g[slot] = nullptr; return fail(RCA_ERR_HIP, "tile graph instantiate: %s", hipGetErrorString(e2)); }
-                    (void)hipGraphUpload(gs.tile_g[slot], st);
+                    rc = lm_capture(st, &gs.tile_g[slot], "tile", [&]() -> int {
+                        hipError_t e = hipMemcpyAsync(h->stt, h->h_stt, lm_state_bytes(n), hipMemcpyHostToDevice, st);
+                        if (e != hipSuccess) return fail(RCA_ERR_HIP, "tile capture memcpy: %s", hipGetErrorString(e));
+                        const int r = lm_enqueue_prefill_tile128(h, n, st, 1);
+                        if (r == RCA_OK) lm_launch_head(h, 1, st, h->logits, true);
+                        return r;
+                    });
+                    if (rc != RCA_OK) return rc;
                 }
                 RCA_HIP(hipGraphLaunch(gs.tile_g[slot], st));
                 h->n_tokens += n;
@@ -4431,10 +4473,7 @@ static int lm_eval_impl(rca_lm_t* h, const int32_t* ids, int32_t n, bool wait_la
             rc = big ? lm_enqueue_prefill_tile128(h, m, st, lm_splits_needed(h, m)) : lm_enqueue_prefill_tile(h, m, st, lm_splits_needed(h, m));
             if (rc != RCA_OK) return rc;
             if (last) {   // logits of the final token: final norm + head on the register GEMV path
-                const rca_lm_config_t& c = h->cfg;
-                const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-                launch_gemv<1, 0>(GEMV_HEAD, h, 1, h->head, nullptr, h->logits, c.vocab_size, c.hidden, c.vocab_size,
-                                  GemvPro{h->x, h->final_norm, c.rms_eps, 1}, norope, st);
+                lm_launch_head(h, 1, st, h->logits, true);
                 RCA_LAUNCH_CHECK();
             }
             h->n_tokens += m;
@@ -4743,28 +4782,19 @@ static int lm_step_impl(rca_lm_t* h, const int32_t* ids, int32_t n, const int32_
         return n_probe ? rca_lm_token_probs(h, probe_ids, n_probe, probs_out) : RCA_OK;
     }
     // stage inputs in pinned memory; the graph's first node copies them to the device
-    h->h_stt->n_tokens = h->n_tokens;
-    h->h_stt->m = n;
-    for (int i = 0; i < n; ++i) h->h_stt->ids[i] = ids[i];
-    if (n_probe) {
-        for (int i = 0; i < n_probe; ++i) h->h_probe[i] = probe_ids[i];
-    }
-    int bucket = 0;
-    const int need = lm_splits_needed(h, n);
-    while (bucket + 1 < LM_GRAPH_BUCKETS && (4 << bucket) < need) ++bucket;
-    if (cap_bucket >= 0) bucket = cap_bucket;
-    const int nsp_launch = bucket + 1 == LM_GRAPH_BUCKETS ? h->n_splits : std::min(h->n_splits, 4 << bucket);
+    lm_stage_state(h, ids, n);
+    for (int i = 0; i < n_probe; ++i) h->h_probe[i] = probe_ids[i];
+    const LmBucket bk = lm_bucket(h, n, cap_bucket);
     rca_lm::GraphSet& gs = lm_graph_set(h);
-    hipGraphExec_t& gexec = n_probe ? gs.gp[n][bucket] : gs.g[n][bucket];
-    if (n_probe && gexec && gs.gp_nprobe[n][bucket] != n_probe) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
+    hipGraphExec_t& gexec = n_probe ? gs.gp[n][bk.bucket] : gs.g[n][bk.bucket];
+    if (n_probe && gexec && gs.gp_nprobe[n][bk.bucket] != n_probe) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
     if (!gexec) {
-        hipGraph_t g = nullptr;
-        RCA_HIP(hipStreamSynchronize(st));
-        RCA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        hipError_t e = hipMemcpyAsync(h->stt, h->h_stt, LM_STATE_DECODE_BYTES, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_probe) e = hipMemcpyAsync(h->probe_ids_dev, h->h_probe, n_probe * 4, hipMemcpyHostToDevice, st);
-        rc = e == hipSuccess ? lm_enqueue_pass(h, n, 1, st, nsp_launch) : fail(RCA_ERR_HIP, "capture memcpy: %s", hipGetErrorString(e));
-        if (rc == RCA_OK) {
+        rc = lm_capture(st, &gexec, "step", [&]() -> int {
+            hipError_t e = hipMemcpyAsync(h->stt, h->h_stt, LM_STATE_DECODE_BYTES, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess && n_probe) e = hipMemcpyAsync(h->probe_ids_dev, h->h_probe, n_probe * 4, hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) return fail(RCA_ERR_HIP, "capture memcpy: %s", hipGetErrorString(e));
+            const int r = lm_enqueue_pass(h, n, 1, st, bk.nsp_launch);
+            if (r != RCA_OK) return r;
             lm_enqueue_sample(h, h->logits, st);
             if (n_probe) {   // rca_lm_token_probs' two launches, over the logits this step just wrote
                 lm_softmax_slices_kernel<<<PROBS_SLICES, 1024, 0, st>>>(h->logits, h->cfg.vocab_size, h->probs_dev + 64);
@@ -4772,16 +4802,10 @@ static int lm_step_impl(rca_lm_t* h, const int32_t* ids, int32_t n, const int32_
             }
             e = hipMemcpyAsync(&h->h_stt->out_token, &h->stt->out_token, 4, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess && n_probe) e = hipMemcpyAsync(h->h_probe + 64, h->probs_dev, n_probe * 4, hipMemcpyDeviceToHost, st);
-            if (e != hipSuccess) rc = fail(RCA_ERR_HIP, "capture d2h: %s", hipGetErrorString(e));
-        }
-        hipError_t e2 = hipStreamEndCapture(st, &g);
-        if (rc != RCA_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (e2 != hipSuccess) return fail(RCA_ERR_HIP, "end capture: %s", hipGetErrorString(e2));
-        e2 = hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e2 != hipSuccess) { gexec = nullptr; return fail(RCA_ERR_HIP, "graph instantiate: %s", hipGetErrorString(e2)); }
-        (void)hipGraphUpload(gexec, st);   // the device-side copy now, not inside the first frame that replays it (pre-captured graphs: first trim frame, first frame of a bucket)
-        if (n_probe) gs.gp_nprobe[n][bucket] = n_probe;
+            return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "capture d2h: %s", hipGetErrorString(e));
+        });
+        if (rc != RCA_OK) return rc;
+        if (n_probe) gs.gp_nprobe[n][bk.bucket] = n_probe;
     }
     if (cap_bucket >= 0) return RCA_OK;      // rca_duplex_precapture: the graph exists now, nothing is launched
     RCA_HIP(hipGraphLaunch(gexec, st));
@@ -4833,46 +4857,27 @@ static int lm_frame_core(rca_lm_t* h, const int32_t* first_pair, const int32_t* 
     RCA_HIP(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     int rc = RCA_OK;
-    h->h_stt->n_tokens = h->n_tokens;
-    h->h_stt->m = 2;
-    h->h_stt->ids[0] = first_pair[0];
-    h->h_stt->ids[1] = first_pair[1];
+    lm_stage_state(h, first_pair, 2);
     for (int i = 0; i < n_steps; ++i) h->h_stt->ids[LM_FRAME_USER0 + i] = user_ids[i];
-    int bucket = 0;
-    const int need = lm_splits_needed(h, 2 * n_steps);
-    while (bucket + 1 < LM_GRAPH_BUCKETS && (4 << bucket) < need) ++bucket;
-    if (cap_bucket >= 0) bucket = cap_bucket;
-    const int nsp_launch = bucket + 1 == LM_GRAPH_BUCKETS ? h->n_splits : std::min(h->n_splits, 4 << bucket);
-    hipGraphExec_t& gexec = lm_graph_set(h).fg[n_steps][bucket];
+    const LmBucket bk = lm_bucket(h, 2 * n_steps, cap_bucket);
+    hipGraphExec_t& gexec = lm_graph_set(h).fg[n_steps][bk.bucket];
     if (cap_bucket >= 0 && (gexec || !h->graphs_enabled)) return RCA_OK;
-    if (!gexec || !h->graphs_enabled) {
-        // graphs disabled (tests): the same launches, eagerly
-        const bool capture = h->graphs_enabled;
-        hipGraph_t g = nullptr;
-        RCA_HIP(hipStreamSynchronize(st));
-        if (capture) RCA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    auto enqueue = [&]() -> int {
         hipError_t e = hipMemcpyAsync(h->stt, h->h_stt, LM_STATE_DECODE_BYTES, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) rc = fail(RCA_ERR_HIP, "frame memcpy: %s", hipGetErrorString(e));
-        for (int i = 0; i < n_steps && rc == RCA_OK; ++i) {
-            rc = lm_enqueue_pass(h, 2, 1, st, nsp_launch, i > 0);
-            if (rc != RCA_OK) break;
+        if (e != hipSuccess) return fail(RCA_ERR_HIP, "frame memcpy: %s", hipGetErrorString(e));
+        for (int i = 0; i < n_steps; ++i) {
+            const int r = lm_enqueue_pass(h, 2, 1, st, bk.nsp_launch, i > 0);
+            if (r != RCA_OK) return r;
             lm_enqueue_sample(h, h->logits, st, i);
         }
-        if (rc == RCA_OK) {
-            e = hipMemcpyAsync(h->h_stt->frame_out, h->stt->frame_out, sizeof(int) * LM_FRAME_MAX, hipMemcpyDeviceToHost, st);
-            if (e != hipSuccess) rc = fail(RCA_ERR_HIP, "frame d2h: %s", hipGetErrorString(e));
-        }
-        if (capture) {
-            hipError_t e2 = hipStreamEndCapture(st, &g);
-            if (rc != RCA_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-            if (e2 != hipSuccess) return fail(RCA_ERR_HIP, "end capture: %s", hipGetErrorString(e2));
-            e2 = hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (e2 != hipSuccess) { gexec = nullptr; return fail(RCA_ERR_HIP, "graph instantiate: %s", hipGetErrorString(e2)); }
-            (void)hipGraphUpload(gexec, st);
-        } else if (rc != RCA_OK) {
-            return rc;
-        }
+        e = hipMemcpyAsync(h->h_stt->frame_out, h->stt->frame_out, sizeof(int) * LM_FRAME_MAX, hipMemcpyDeviceToHost, st);
+        return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "frame d2h: %s", hipGetErrorString(e));
+    };
+    if (!h->graphs_enabled) {   // tests: the same launches, eagerly
+        RCA_HIP(hipStreamSynchronize(st));
+        if ((rc = enqueue()) != RCA_OK) return rc;
+    } else if (!gexec && (rc = lm_capture(st, &gexec, "frame", enqueue)) != RCA_OK) {
+        return rc;
     }
     if (cap_bucket >= 0) return RCA_OK;      // rca_duplex_precapture: the graph exists now, nothing is launched
     if (h->graphs_enabled) RCA_HIP(hipGraphLaunch(gexec, st));
@@ -4988,6 +4993,13 @@ static int duplex_grow(T** p, size_t* cap, size_t n) {
     return rc;
 }
 
+// byte offsets of the variable parts of DuplexState::pin behind the DuplexPin header, each part on a 256-byte boundary
+struct DuplexPinLayout {
+    size_t pcm, codes, out, total;
+    DuplexPinLayout(int T, int F_ctx, int n_samples)
+        : pcm(sizeof(DuplexPin)), codes(pcm + (((size_t)T * 4 + 255) & ~(size_t)255)), out(codes + (((size_t)F_ctx * 8 + 255) & ~(size_t)255)),
+          total(out + (size_t)n_samples * 4) {}
+};
 // buffers, side stream and events of the duplex frame for a call shape (growing a buffer invalidates the graphs captured over it)
 static int duplex_reserve(rca_lm* h, int T, int F_ctx, int n, int n_samples) {
     int rc;
@@ -5002,8 +5014,7 @@ static int duplex_reserve(rca_lm* h, int T, int F_ctx, int n, int n_samples) {
     }
     DuplexState* d = h->duplex;
     const int F = F_ctx + n;
-    const size_t pin_pcm = sizeof(DuplexPin), pin_codes = pin_pcm + (((size_t)T * 4 + 255) & ~(size_t)255),
-                 pin_out = pin_codes + (((size_t)F_ctx * 8 + 255) & ~(size_t)255), pin_total = pin_out + (size_t)n_samples * 4;
+    const size_t pin_total = DuplexPinLayout(T, F_ctx, n_samples).total;
     if ((size_t)T > d->pcm_in_cap || (size_t)F > d->code_win_cap || (size_t)n_samples > d->pcm_out_cap || pin_total > d->pin_cap || !d->dev) {
         RCA_HIP(hipStreamSynchronize(st));
         duplex_drop_graphs(d);
@@ -5027,6 +5038,18 @@ extern "C" int rca_duplex_prepare(rca_lm_t* h, int32_t T, int32_t F_ctx, int32_t
     { const int src = lm_settle(h); if (src != RCA_OK) return src; }
     RCA_HIP(hipSetDevice(h->device));
     return duplex_reserve(h, T, F_ctx, n_steps, n_samples);
+}
+
+// An eager run (or the precapture's two tail calls) has sized the codec workspace of this call shape: record the shape as warmed under
+// the signature the workspace has now, and key the shape's graph by it.
+static int duplex_mark_warm(DuplexState* d, DuplexState::Entry* ent, const rca_duplex_frame_args_t* a, rca_codec_t* codec) {
+    uint64_t sig = 0;
+    const int rc = rca_codec_workspace_sig(codec, &sig);
+    if (rc != RCA_OK) return rc;
+    if (d->warm.size() >= 16) d->warm.clear();
+    d->warm.push_back(DuplexState::Warm{a->T, a->F_ctx, a->n_steps, a->n_samples, (const void*)codec, sig});
+    ent->key.codec_sig = sig;
+    return RCA_OK;
 }
 
 // cap_bucket < 0: run the frame.  cap_bucket >= 0 (rca_duplex_precapture): make sure the graph of this call shape exists for that
@@ -5057,29 +5080,21 @@ static int duplex_frame_core(rca_lm_t* h, rca_codec_t* codec, const rca_duplex_f
     if ((rc = duplex_reserve(h, a->T, a->F_ctx, n, a->n_samples)) != RCA_OK) return rc;
     DuplexState* d = h->duplex;
     const int F = a->F_ctx + n;
-    const size_t pin_pcm = sizeof(DuplexPin), pin_codes = pin_pcm + (((size_t)a->T * 4 + 255) & ~(size_t)255),
-                 pin_out = pin_codes + (((size_t)a->F_ctx * 8 + 255) & ~(size_t)255);
+    const DuplexPinLayout lay(a->T, a->F_ctx, a->n_samples);
     if (d->logits_at_capture != (const void*)h->logits) { duplex_drop_graphs(d); d->logits_at_capture = h->logits; }
     DuplexPin* pin = reinterpret_cast<DuplexPin*>(d->pin);
     // stage the inputs
-    h->h_stt->n_tokens = h->n_tokens;
-    h->h_stt->m = 2;
-    h->h_stt->ids[0] = a->first_pair[0];
-    h->h_stt->ids[1] = a->first_pair[1];
+    lm_stage_state(h, a->first_pair, 2);
     for (int i = 0; i < n; ++i) h->h_stt->ids[LM_FRAME_USER0 + i] = 0;
     pin->probe_id = a->probe_id >= 0 ? a->probe_id : 0;
     if (!cap_only) {
-        memcpy(d->pin + pin_pcm, a->pcm_window, (size_t)a->T * 4);
-        if (a->F_ctx) memcpy(d->pin + pin_codes, a->code_ctx, (size_t)a->F_ctx * 8);
+        memcpy(d->pin + lay.pcm, a->pcm_window, (size_t)a->T * 4);
+        if (a->F_ctx) memcpy(d->pin + lay.codes, a->code_ctx, (size_t)a->F_ctx * 8);
     }
-    int bucket = 0;
-    const int need = lm_splits_needed(h, 2 * n);
-    while (bucket + 1 < LM_GRAPH_BUCKETS && (4 << bucket) < need) ++bucket;
-    if (cap_only) bucket = cap_bucket;
-    const int nsp_launch = bucket + 1 == LM_GRAPH_BUCKETS ? h->n_splits : std::min(h->n_splits, 4 << bucket);
+    const LmBucket bk = lm_bucket(h, 2 * n, cap_bucket);
     uint64_t csig = 0;
     if ((rc = rca_codec_workspace_sig(codec, &csig)) != RCA_OK) return rc;
-    DuplexGraphKey key{a->T, a->F_ctx, n, a->n_samples, a->probe_id >= 0 ? 1 : 0, bucket, a->code_token_base, (const void*)h->kc, csig, (const void*)codec};
+    DuplexGraphKey key{a->T, a->F_ctx, n, a->n_samples, a->probe_id >= 0 ? 1 : 0, bk.bucket, a->code_token_base, (const void*)h->kc, csig, (const void*)codec};
     DuplexState::Entry* ent = nullptr;
     for (auto& e : d->graphs)
         if (e.key == key) ent = &e;
@@ -5093,8 +5108,8 @@ static int duplex_frame_core(rca_lm_t* h, rca_codec_t* codec, const rca_duplex_f
         warmed = warmed || (w.T == a->T && w.F_ctx == a->F_ctx && w.n_steps == n && w.n_samples == a->n_samples && w.codec == (const void*)codec && w.codec_sig == csig);
     auto enqueue = [&]() -> int {
         hipError_t e = hipMemcpyAsync(h->stt, h->h_stt, LM_STATE_DECODE_BYTES, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d->pcm_in, d->pin + pin_pcm, (size_t)a->T * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && a->F_ctx) e = hipMemcpyAsync(d->code_win, d->pin + pin_codes, (size_t)a->F_ctx * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d->pcm_in, d->pin + lay.pcm, (size_t)a->T * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && a->F_ctx) e = hipMemcpyAsync(d->code_win, d->pin + lay.codes, (size_t)a->F_ctx * 8, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(&d->dev->probe_id, &pin->probe_id, 4, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "duplex h2d: %s", hipGetErrorString(e));
         // Step 0 evaluates the PREVIOUS frame's pair: this chunk's codes are first needed by the sampler tail of step 0, which makes
@@ -5114,7 +5129,7 @@ static int duplex_frame_core(rca_lm_t* h, rca_codec_t* codec, const rca_duplex_f
             if (e != hipSuccess) return fail(RCA_ERR_HIP, "duplex join: %s", hipGetErrorString(e));
         }
         for (int i = 0; i < n; ++i) {
-            if ((r = lm_enqueue_pass(h, 2, 1, st, nsp_launch, i > 0)) != RCA_OK) return r;
+            if ((r = lm_enqueue_pass(h, 2, 1, st, bk.nsp_launch, i > 0)) != RCA_OK) return r;
             if (i == 0 && d->fork) {
                 e = hipStreamWaitEvent(st, d->ev_join, 0);
                 if (e != hipSuccess) return fail(RCA_ERR_HIP, "duplex join: %s", hipGetErrorString(e));
@@ -5130,7 +5145,7 @@ static int duplex_frame_core(rca_lm_t* h, rca_codec_t* codec, const rca_duplex_f
         RCA_LAUNCH_CHECK();
         e = hipMemcpyAsync(pin->frame_out, h->stt->frame_out, sizeof(int) * LM_FRAME_MAX, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(pin->user_codes, d->dev->user_codes, sizeof(long long) * LM_FRAME_MAX + 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d->pin + pin_out, d->pcm_out, (size_t)a->n_samples * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d->pin + lay.out, d->pcm_out, (size_t)a->n_samples * 4, hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "duplex d2h: %s", hipGetErrorString(e));
         return RCA_OK;
     };
@@ -5144,29 +5159,13 @@ static int duplex_frame_core(rca_lm_t* h, rca_codec_t* codec, const rca_duplex_f
         if ((rc = rca_codec_encode_tail_dev(codec, d->pcm_in, 1, a->T, n, (int64_t*)d->dev->user_codes, se)) != RCA_OK) return rc;
         if ((rc = rca_codec_decode_tail_dev(codec, (const int64_t*)d->code_win, 1, F, a->n_samples, d->pcm_out, se)) != RCA_OK) return rc;
         RCA_HIP(hipStreamSynchronize(se));
-        uint64_t csig2 = 0;
-        if ((rc = rca_codec_workspace_sig(codec, &csig2)) != RCA_OK) return rc;
-        if (d->warm.size() >= 16) d->warm.clear();
-        d->warm.push_back(DuplexState::Warm{a->T, a->F_ctx, n, a->n_samples, (const void*)codec, csig2});
-        ent->key.codec_sig = csig2;
+        if ((rc = duplex_mark_warm(d, ent, a, codec)) != RCA_OK) return rc;
         warmed = true;
     }
     const bool want_graph = h->graphs_enabled && warmed;
-    if (want_graph && !ent->exec) {
-        // the eager frame before this one sized every workspace buffer of this shape: nothing allocates under capture
-        hipGraph_t g = nullptr;
-        RCA_HIP(hipStreamSynchronize(st));
-        RCA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        rc = enqueue();
-        hipError_t e2 = hipStreamEndCapture(st, &g);
-        if (rc != RCA_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (e2 != hipSuccess) return fail(RCA_ERR_HIP, "duplex capture: %s", hipGetErrorString(e2));
-        e2 = hipGraphInstantiate(&ent->exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e2 != hipSuccess) { ent->exec = nullptr; return fail(RCA_ERR_HIP, "duplex graph instantiate: %s", hipGetErrorString(e2)); }
-        (void)hipGraphUpload(ent->exec, st);
-        // a workspace that moved under the eager run (first call of a shape) would have changed the signature: checked by the key
-    }
+    // the eager frame before this one sized every workspace buffer of this shape: nothing allocates under capture (a workspace that
+    // moved under the eager run, the first call of a shape, would have changed the signature: checked by the key)
+    if (want_graph && !ent->exec && (rc = lm_capture(st, &ent->exec, "duplex", enqueue)) != RCA_OK) return rc;
     if (cap_only) return RCA_OK;
     if (want_graph) {
         RCA_HIP(hipGraphLaunch(ent->exec, st));
@@ -5175,13 +5174,7 @@ static int duplex_frame_core(rca_lm_t* h, rca_codec_t* codec, const rca_duplex_f
     }
     RCA_HIP(hipStreamSynchronize(st));
     // the eager run may have (re)allocated codec workspace: graphs are keyed by the signature after it
-    if (!warmed) {
-        uint64_t csig2 = 0;
-        if ((rc = rca_codec_workspace_sig(codec, &csig2)) != RCA_OK) return rc;
-        if (d->warm.size() >= 16) d->warm.clear();
-        d->warm.push_back(DuplexState::Warm{a->T, a->F_ctx, n, a->n_samples, (const void*)codec, csig2});
-        ent->key.codec_sig = csig2;
-    }
+    if (!warmed && (rc = duplex_mark_warm(d, ent, a, codec)) != RCA_OK) return rc;
     int done = n;
     for (int i = 0; i < n; ++i) {
         out->tokens[i] = pin->frame_out[i];
@@ -5192,7 +5185,7 @@ static int duplex_frame_core(rca_lm_t* h, rca_codec_t* codec, const rca_duplex_f
     out->n_done = done;
     out->flags = pin->flags | (done < n ? 2 : 0);
     out->probe_prob = (a->probe_id >= 0 && done == n) ? pin->probe_prob : -1.0f;
-    if (out->flags == 0) memcpy(pcm_out_host, d->pin + pin_out, (size_t)a->n_samples * 4);
+    if (out->flags == 0) memcpy(pcm_out_host, d->pin + lay.out, (size_t)a->n_samples * 4);
     h->n_tokens += 2 * done;
     h->logits_rows = done < n ? 0 : 1;
     h->rng_host += (unsigned long long)done;
@@ -5224,7 +5217,7 @@ extern "C" int rca_duplex_precapture(rca_lm_t* h, rca_lm_t* twin, rca_codec_t* c
     for (int pass = 0; pass < (twin ? 2 : 1) && rc == RCA_OK; ++pass) {
         if (pass == 1) { std::swap(h->kc, twin->kc); std::swap(h->vc, twin->vc); }      // host pointers only: nothing runs under capture
         for (int b = 0; b < LM_GRAPH_BUCKETS && rc == RCA_OK; ++b) {
-            if (b > 0 && (4 << (b - 1)) >= h->n_splits) break;                       // the previous bucket already launches every split
+            if (!lm_bucket_reachable(h, b)) break;
             rc = duplex_frame_core(h, codec, a, nullptr, nullptr, b);
             if (rc == RCA_OK && n_probe > 0) rc = lm_step_capture_only(h, 1, n_probe, b);
             // the frames that cannot take the one-replay path (a trim, a text branch) replay the LM chunk or single steps
@@ -5419,7 +5412,7 @@ extern "C" int rca_lm_set_attn_fuse(rca_lm_t* h, int32_t enable) {
 // Activation format of the decode GEMVs over packed (q8_0 / Q4_K / Q5_K / Q6_K) matrices: 0 = f32, 1 = q8_1 blocks + integer dot products
 // (lm_gemv_kernel<..., ACT = 1>).  The exact prefill route is made of the same launches and follows; the MFMA tiles do not.
 static bool lm_has_packed_matrix(const rca_lm* h) {
-    auto packed = [](const WMat& m) { return m.fmt == WF_Q8 || m.fmt == WF_Q4K || m.fmt == WF_Q6K || m.fmt == WF_Q5K; };
+    auto packed = [](const WMat& m) { return wf_packed(m.fmt); };
     bool any = packed(h->head);
     for (const LmLayer& L : h->layers) any = any || packed(L.qkv) || packed(L.o) || packed(L.gu) || packed(L.down) || (L.split_v && packed(L.vseg));
     return any;
@@ -5462,37 +5455,28 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
     const int32_t ids[LM_GEMV_M] = {};
     int rc;
     if ((rc = lm_push_state(h, ids, M, st)) != RCA_OK) return rc;
-    const GemvPro nopro{nullptr, nullptr, 0.0f, 0};
-    const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
     float* xin = kind == 1 ? h->attn : (kind == 3 ? h->hbuf : h->x);
     RCA_HIP(hipMemcpyAsync(xin, x_host, (size_t)M * in_w[kind] * 4, hipMemcpyHostToDevice, st));
     const float* yd = nullptr;
     int ldy = out_w[kind];
     float* head_out = nullptr;
     if (kind == 0) {
-        const LmLayer& L = h->layers[layer];
-        GemvRope rope{h->cos_t, h->sin_t, h->kc + (long)layer * h->kv_layer_stride, h->vc + (long)layer * h->kv_layer_stride, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
-        launch_gemv<1, 2>(GEMV_QKV, h, M, L.qkv, nullptr, h->qkv, L.qkv.N, H, QKV, GemvPro{h->x, L.attn_norm, c.rms_eps, 0}, rope, st);
-        if (L.split_v) {
-            rope.row_base = L.qkv.N;
-            launch_gemv<1, 2>(GEMV_QKV, h, M, L.vseg, nullptr, h->qkv, L.vseg.N, H, QKV, GemvPro{h->x, L.attn_norm, c.rms_eps, 0}, rope, st);
-        }
+        lm_launch_qkv(h, layer, M, st);
         yd = h->qkv; ldy = QKV;
     } else if (kind == 1) {
         RCA_HIP(hipMemsetAsync(h->x, 0, (size_t)M * H * 4, st));
-        launch_gemv<0, 3>(GEMV_O, h, M, h->layers[layer].o, h->attn, h->x, H, AO, H, nopro, norope, st);
+        lm_launch_o(h, layer, M, st);
         yd = h->x;
     } else if (kind == 2) {
-        const LmLayer& L = h->layers[layer];
-        launch_gemv<1, 1>(GEMV_GU, h, M, L.gu, nullptr, h->hbuf, 2 * F, H, F, GemvPro{h->x, L.ffn_norm, c.rms_eps, 0}, norope, st);
+        lm_launch_gu(h, layer, M, st);
         yd = h->hbuf;
     } else if (kind == 3) {
         RCA_HIP(hipMemsetAsync(h->x, 0, (size_t)M * H * 4, st));
-        launch_gemv<0, 3>(GEMV_DOWN, h, M, h->layers[layer].down, h->hbuf, h->x, H, F, H, nopro, norope, st);
+        lm_launch_down(h, layer, M, st);
         yd = h->x;
     } else {
         if ((rc = lm_alloc((void**)&head_out, (size_t)M * V * 4)) != RCA_OK) return rc;   // the handle's own logits buffer may hold one row only
-        launch_gemv<1, 0>(GEMV_HEAD, h, M, h->head, nullptr, head_out, V, H, V, GemvPro{h->x, h->final_norm, c.rms_eps, 0}, norope, st);
+        lm_launch_head(h, M, st, head_out, false);
         yd = head_out;
     }
     hipError_t e = hipGetLastError();

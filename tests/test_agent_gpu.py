@@ -281,6 +281,37 @@ def test_duplex_frame_call_equals_the_separate_calls():
     twin.close()
 
 
+def test_duplex_precapture_changes_nothing():
+    """rca_duplex_precapture only makes graphs exist: a handle whose duplex-frame, frame, step and step-probe graphs were captured
+    ahead of time for every context bucket its n_ctx reaches samples the same tokens, stands at the same KV position and ends on
+    the same logits, bit for bit, as a handle over the same weights that captures each graph inside the call that first needs it.
+    (Here and not beside the LM tests: the codec handle the call takes needs a codebook of at least 128 entries, more than the tiny
+    LM's vocabulary holds.)"""
+    agent, res = make_agent(chunk=0.08)
+    llm, at = res.llm, res.audio_tokenizer
+    plain = llm.make_kv_shadow(low_priority=False)
+    base, floor = agent._code_token_base, agent.end_header_token_id
+    rng = np.random.default_rng(6)
+    prompt = [int(t) for t in rng.integers(base, base + at.codebook_size, size=40)]
+    users = [int(t) for t in rng.integers(base, base + at.codebook_size, size=6)]
+    runs = []
+    for m, precapture in ((llm, True), (plain, False)):
+        m.init_sampler_for_generate(top_k=100, top_p=1.0, min_p=0.0, temp=1.0, seed=11)
+        if precapture:
+            n0 = m.n_tokens
+            m.duplex_precapture(at.codec_model.hip, 32000, 96, 4, 1280 + 160, base, True, n_step_probe=2)
+            assert m.n_tokens == n0
+        m.reset()
+        m.eval(prompt[:-2])
+        toks = m.frame(prompt[-2:], users[:4], floor)      # (a frame cut short is compared all the same)
+        toks.append(m.step([toks[-1], users[4]]))
+        toks.append(m.step([toks[-1], users[5]]))
+        runs.append((toks, m.n_tokens, m._scores[-1].copy()))
+    assert runs[0][0] == runs[1][0] and len(runs[0][0]) >= 3 and runs[0][1] == runs[1][1] == 38 + 2 * len(runs[0][0])
+    assert np.array_equal(runs[0][2], runs[1][2])
+    plain.close()
+
+
 def test_full_size_duplex_session_equals_the_oracle_session():
     """BASELINE config [3] at full size against the oracle, not only inside bench.py: the default codec (131072 x 16 codebook, hop 320) and
     the Llama-3.2-1B-dims LM (V = 259 344, hash-generated weights, text rows of lm_head zeroed like a trained codec LM in audio mode) run

@@ -547,6 +547,42 @@ def test_frame_graph_equals_single_steps(graphs):
         llm.frame(ids[9:11], [llm._n_vocab], -1)
 
 
+def test_tile_graph_replay_equals_eager_tiles():
+    """rca_lm_eval_async pieces of one tile each are captured the second time a size is seen and replayed from then on (two sizes
+    are kept per cache, the less used one makes room for a third).  The cache and logits they leave equal, bit for bit, those of the
+    same pieces launched eagerly and those of one eval of the whole prompt: smallest shape on the 128-token route, 5 x 64 tokens
+    (eager, capture, three replays), then 40, 40 (a second size joins), 24, 24 (evicts it), 40 (evicts that), then a 2-token eval."""
+    import lm_shape_cases as sc
+    from realtime_codec_agent_amd.llm import LlamaForAlternatingCodeChannels
+    c = sc.BY_NAME["g4_k768"]
+    llm = LlamaForAlternatingCodeChannels(model_path=f"random:{c.name}", config=c.config(), n_ctx=c.n_ctx, random_seed=c.seed,
+                                          init_std=sc.INIT_STD, device=0, weight_format="q8_0")
+    assert llm.prefill_route() == "gemm128"
+    pieces = [64] * 5 + [40, 40, 24, 24, 40]
+    n = sum(pieces)
+    ids = c.ids().tolist()
+    got = {}
+    for mode in ("graphs", "eager", "whole"):
+        llm.reset()
+        llm.set_graphs(mode != "eager")
+        if mode == "whole":
+            llm.eval(ids[:n])
+        else:
+            off = 0
+            for p in pieces:
+                llm.eval_async(ids[off:off + p])
+                off += p
+            llm.sync()
+        assert llm.n_tokens == n
+        prefill = llm._scores[-1].copy()
+        llm.eval(ids[n:n + 2])
+        got[mode] = (prefill, llm._scores[-1].copy())
+    llm.set_graphs(True)
+    for other in ("eager", "whole"):
+        assert np.array_equal(got["graphs"][0], got[other][0]), other
+        assert np.array_equal(got["graphs"][1], got[other][1]), other
+
+
 def test_fused_attention_merge_equals_separate_merge_launch():
     """Decode steps merge the attention splits inside the attention launch: every workgroup publishes its partial with write-through
     stores and the one that arrives last merges them (sc1 hand-off).  Must equal the separate merge launch bit for bit: the 1B model,
