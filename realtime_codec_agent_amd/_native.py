@@ -24,7 +24,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"
                "-Wno-unused-result", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
 MAX_STAGES = 8
-RCA_F32, RCA_BF16, RCA_Q8_0, RCA_F16, RCA_Q4_K, RCA_Q6_K, RCA_Q5_K = 0, 1, 2, 3, 4, 5, 6
+RCA_F32, RCA_BF16, RCA_Q8_0, RCA_F16, RCA_Q4_K, RCA_Q6_K, RCA_Q5_K, RCA_Q4_0, RCA_Q4_1 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 
 class RcaError(RuntimeError):
@@ -114,6 +114,49 @@ class Q5KBlocks:
     def take_rows(self, index) -> "Q5KBlocks":
         r = self.raw[index]
         return Q5KBlocks(np.ascontiguousarray(r), (r.shape[0], self.shape[1]))
+
+
+class Q40Blocks:
+    """A GGUF Q4_0 tensor kept as its raw 18-byte blocks (fp16 d, 16 bytes of nibbles per 32 values; value j of a block in the low nibble
+    of byte j, value j + 16 in the high nibble): raw uint8 [rows, cols / 32 * 18], logical shape (rows, cols).  The bulk of a
+    llama-quantize Q4_0 file."""
+
+    BLOCK_BYTES = 18
+
+    def __init__(self, raw: np.ndarray, shape):
+        self.shape = tuple(int(x) for x in shape)
+        self.raw = raw.reshape(self.shape[0], self.shape[1] // 32 * self.BLOCK_BYTES)
+        self.dtype = np.dtype(np.uint8)
+
+    def _nibbles(self, qs: np.ndarray) -> np.ndarray:
+        return np.concatenate([qs & 0xF, qs >> 4], axis=1)
+
+    def dequantize(self) -> np.ndarray:
+        """llama.cpp's dequantize_row_q4_0: (q - 8) * d in f32 (exact)."""
+        blk = self.raw.reshape(-1, 18)
+        d = blk[:, 0:2].copy().view(np.float16).astype(np.float32)
+        q = self._nibbles(blk[:, 2:18]).astype(np.float32)
+        return ((q - np.float32(8.0)) * d).astype(np.float32).reshape(self.shape)
+
+    def take_rows(self, index):
+        r = self.raw[index]
+        return type(self)(np.ascontiguousarray(r), (r.shape[0], self.shape[1]))
+
+
+class Q41Blocks(Q40Blocks):
+    """A GGUF Q4_1 tensor kept as its raw 20-byte blocks (fp16 d, fp16 m, 16 bytes of nibbles per 32 values, nibble order as in Q4_0):
+    raw uint8 [rows, cols / 32 * 20], logical shape (rows, cols).  What llama-quantize Q4_0 gives some ffn_down tensors when an
+    importance matrix is supplied."""
+
+    BLOCK_BYTES = 20
+
+    def dequantize(self) -> np.ndarray:
+        """llama.cpp's dequantize_row_q4_1: q * d + m in f32 (one rounding on the sum)."""
+        blk = self.raw.reshape(-1, 20)
+        d = blk[:, 0:2].copy().view(np.float16).astype(np.float32)
+        m = blk[:, 2:4].copy().view(np.float16).astype(np.float32)
+        q = self._nibbles(blk[:, 4:20]).astype(np.float32)
+        return ((q * d).astype(np.float32) + m).astype(np.float32).reshape(self.shape)
 
 
 class Q6KBlocks:
@@ -382,11 +425,11 @@ def make_tensors(weights: Dict[str, np.ndarray]) -> Tuple[C.Array, list]:
     keep = []
     arr = (Tensor * len(weights))()
     for i, (name, a) in enumerate(weights.items()):
-        if isinstance(a, (Q8Blocks, Q4KBlocks, Q5KBlocks, Q6KBlocks)):      # GGUF q8_0 / Q4_K / Q5_K / Q6_K blocks, handed over as they sit in the file
+        if isinstance(a, (Q8Blocks, Q4KBlocks, Q5KBlocks, Q6KBlocks, Q40Blocks)):      # GGUF q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 blocks, handed over as they sit in the file
             raw = np.ascontiguousarray(a.raw)
             nb = name.encode()
             keep += [raw, nb]
-            arr[i] = Tensor(nb, raw.ctypes.data, int(np.prod(a.shape)), {Q8Blocks: RCA_Q8_0, Q4KBlocks: RCA_Q4_K, Q5KBlocks: RCA_Q5_K, Q6KBlocks: RCA_Q6_K}[type(a)])
+            arr[i] = Tensor(nb, raw.ctypes.data, int(np.prod(a.shape)), {Q8Blocks: RCA_Q8_0, Q4KBlocks: RCA_Q4_K, Q5KBlocks: RCA_Q5_K, Q6KBlocks: RCA_Q6_K, Q40Blocks: RCA_Q4_0, Q41Blocks: RCA_Q4_1}[type(a)])
             continue
         if a.dtype == np.uint16:
             dt = RCA_BF16

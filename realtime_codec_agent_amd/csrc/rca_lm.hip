@@ -358,6 +358,11 @@ struct GemvQ8 {          // the packed (quantised) forms: q8_0, and Q4_K (dd != 
 // the quad's slot: shifted by 4 - 2 slot (even elements) or 3 - 2 slot (odd ones), the mask 0x10101010 leaves the four bits exactly
 // where the nibble bytes `lo` / `hi` of the Q4_K body want their bit 4 -- a shift and an and-or per four weights.
 __host__ __device__ __forceinline__ int q5k_hbit(int slot_in_quad, int j) { return 8 * (j >> 1) + 2 * slot_in_quad + (j & 1); }
+// Q4_0 / Q4_1 (GGUF block_q4_0 / block_q4_1, the legacy 4-bit types): 4-bit values with one fp16 step per 32 (Q4_0: value = d (q - 8))
+// or a step and a minimum (Q4_1: value = d q + m).  Both are the Q4_K form s q - t with (s, t) = (d, 8 d) resp. (d, -m), formed once at
+// load (all exact in fp16).  Streamed as the Q4_K nibble layout plus ONE factor dword (fp16 s | fp16 t << 16) per slot and 32-value
+// block, in q8.sc, [ceil(N / 16)][K / 32][16] (q4k_scm_index over dwords): 5.0 bits per weight for both types, no (sc, m) / (d, dmin)
+// unpack and no d * sc / dmin * m products in the body.  Arithmetic as for Q4_K: val += s p - t sum(x).
 __host__ __device__ __forceinline__ long q4k_scm_index(long slot, long kblock, long nkb) { return ((slot >> 4) * nkb + kblock) * 16 + (slot & 15); }
 __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, long nkb) { return ((pair >> 3) * nkb + kblock) * 8 + (pair & 7); }
 // The format a projection matrix is kept in (ONE copy per matrix; the decode GEMV streams it, the prefill tiles de-quantise it while
@@ -370,12 +375,15 @@ __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, lon
 #define WF_F16 2    // fp16 [N][K] (the reference's default GGUF is F16, realtime_agent_resources.py:12)
 #define WF_Q4K 3    // GGUF Q4_K, quad-interleaved nibbles (GemvQ8 with dd)
 #define WF_Q5K 5    // GGUF Q5_K: the Q4_K layout (low nibbles, sc, dd) + one plane of high bits, q5k_hbit() above (5.6 bits per weight streamed)
+#define WF_Q40 6    // GGUF Q4_0: the Q4_K nibble layout + one (fp16 s | fp16 t << 16) dword per slot and 32 values, s = d, t = 8 d (5.0 bits per weight streamed)
+#define WF_Q41 7    // GGUF Q4_1: the same layout with t = -m.  The kernels know one form (template value WF_Q40); the id only tells the two apart in reports
 #define WF_Q6K 4    // GGUF Q6_K re-encoded losslessly: int8 values (the 6-bit value - 32) in the q8_0 pair layout + one f32 scale d * sc per
                     // row and group of 16 ((s_a, s_b) per pair, pairs in groups of 8: [ceil(N / 16)][K / 16][8][2] floats); 10 bits per
                     // weight streamed (the file holds 6.6); d * sc * q is exact in f32, so the values are llama.cpp's dequantize_row_q6_K's
+constexpr bool wf_packed(int fmt) { return fmt == WF_Q8 || fmt == WF_Q4K || fmt == WF_Q6K || fmt == WF_Q5K || fmt == WF_Q40 || fmt == WF_Q41; }
 // minimum waves per SIMD asked of the register allocator.  The q8_0 bodies otherwise spread over 200+ registers (one wave per
 // SIMD) although their live set is ~130: a streaming kernel wants the occupancy.
-constexpr int gemv_min_waves(int Q, int R, int NIT) { return (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K) ? 1 : (R * NIT >= 16 ? 2 : 4); }
+constexpr int gemv_min_waves(int Q, int R, int NIT) { return (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K && Q != WF_Q40) ? 1 : (R * NIT >= 16 ? 2 : 4); }
 // ACT = 1 (rca_lm_set_act_format, packed formats only): the activations are quantised to q8_1 blocks -- 32 consecutive values, int8 +
 // one scale, ggml's quantize_row_q8_1 restated: d = amax / 127, inv = d != 0 ? 1 / d : 0 (IEEE division), q = roundf(x * inv), scale used
 // d_x = (float)(fp16 rne of d) -- and the products run on the signed byte dot (v_dot4c_i32_i8), llama.cpp's GPU mat-vec class:
@@ -400,7 +408,7 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
     const int tid = threadIdx.x;
     const int nchunk = K >> 3;
     constexpr bool QA = ACT == 1;
-    static_assert(!QA || Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K, "q8_1 activations go with the packed weight formats");
+    static_assert(!QA || Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K || Q == WF_Q40, "q8_1 activations go with the packed weight formats");
     const int cpw = QA ? ((((nchunk + 3) >> 2) + 3) & ~3) : (nchunk + 3) >> 2;   // chunks per wave (q8_1: whole 32-blocks)
     const int c0 = wave * cpw;
     const int cn = max(0, min(cpw, nchunk - c0));            // this wave's chunk count (<= 64 * NIT)
@@ -418,12 +426,15 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
     };
     constexpr bool Q6 = Q == WF_Q6K;                 // the q8_0 body with another scale: f32 per group of 16 instead of fp16 per 32
     constexpr bool Q5 = Q == WF_Q5K;                 // the Q4_K body with a fifth bit per value; its plane of high bits arrives as W
-    constexpr bool Q8 = Q == WF_Q8 || Q6, Q4 = Q == WF_Q4K || Q5;
+    constexpr bool Q40 = Q == WF_Q40;                // Q4_0 / Q4_1: the Q4_K body with (s, t) read from one dword per slot and 32 values
+    constexpr bool Q8 = Q == WF_Q8 || Q6, Q4 = Q == WF_Q4K || Q5 || Q40;
     constexpr int NL = Q8 ? R / 2 : (Q4 ? R / 4 : R);   // 16-byte weight loads per chunk: one per row, per slot pair (q8_0 / Q6_K) or per slot quad (Q4_K)
     constexpr int H0 = NL / 2;                // the batch's registers refill in two halves: loads [0, H0) and [H0, NL)
     u32x4 wq[NL][NIT];
-    uint2 wscm[Q4 ? NIT : 1][Q4 ? NL : 1];    // Q4_K: (sc | m << 8) of a quad's four slots for this lane's 32-element sub-block
-    u32x4 wdd[Q4 ? NIT : 1][Q4 ? NL : 1];     //       (d | dmin << 16) of the four slots for this lane's 256-element super-block
+    constexpr bool Q4F = Q4 && !Q40;          // the two-level factors of the K-quants
+    uint2 wscm[Q4F ? NIT : 1][Q4F ? NL : 1];  // Q4_K: (sc | m << 8) of a quad's four slots for this lane's 32-element sub-block
+    u32x4 wdd[Q4 ? NIT : 1][Q4 ? NL : 1];     //       (d | dmin << 16) of the four slots for this lane's 256-element super-block;
+                                              //       Q4_0 / Q4_1: (s | t << 16) of the four slots for this lane's 32-element block
     unsigned wqh[Q5 ? NL : 1][Q5 ? NIT : 1];  // Q5_K: the quad's dword of high bits for this lane's chunk
     unsigned wsc[Q8 ? NIT : 1][Q8 ? R / 2 : 1];   // q8_0: (fp16, fp16) scales of the batch's pairs for this lane's 32-element block
     unsigned wsc2[Q6 ? NIT : 1][Q6 ? R / 2 : 1];  // Q6_K: wsc / wsc2 = the f32 scales (bits) of the pair's first / second row for this lane's group of 16
@@ -440,8 +451,12 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
             for (int it = 0; it < NIT; ++it) {
                 const int c = lane + 64 * it;
                 const int cc = cbase + (c < cn ? c : 0);
-                wdd[it][r] = *reinterpret_cast<const u32x4*>(q8.dd + q4k_scm_index(4 * quad, cc >> 5, K >> 8));
-                wscm[it][r] = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(q8.sc) + q4k_scm_index(4 * quad, cc >> 2, K >> 5));
+                if constexpr (Q40) {
+                    wdd[it][r] = *reinterpret_cast<const u32x4*>(q8.sc + q4k_scm_index(4 * quad, cc >> 2, K >> 5));
+                } else {
+                    wdd[it][r] = *reinterpret_cast<const u32x4*>(q8.dd + q4k_scm_index(4 * quad, cc >> 5, K >> 8));
+                    wscm[it][r] = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(q8.sc) + q4k_scm_index(4 * quad, cc >> 2, K >> 5));
+                }
                 wq[r][it] = __builtin_nontemporal_load(q8.qs + quad * nchunk + cc);
                 if constexpr (Q5) wqh[r][it] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(W) + quad * nchunk + cc);
             }
@@ -637,7 +652,8 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
             for (int it = 0; it < NIT; ++it) {
                 const u32x4 a = wq[r][it];
                 const u32x4 ddv = wdd[it][r];
-                const uint2 sm = wscm[it][r];
+                uint2 sm = make_uint2(0u, 0u);
+                if constexpr (Q4F) sm = wscm[it][r];
                 const unsigned aw[4] = {a.x, a.y, a.z, a.w}, dw[4] = {ddv.x, ddv.y, ddv.z, ddv.w}, sw[2] = {sm.x, sm.y};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -651,8 +667,8 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
                     if constexpr (QA) {   // bytes 0..15 (Q5_K: 0..31) are valid signed int8: the signed byte dot against the activation bytes in the same order
                         const f16x2 d2 = __builtin_bit_cast(f16x2, dw[i]);
                         const unsigned scm = (sw[i >> 1] >> (16 * (i & 1))) & 0xffffu;
-                        const float d1 = (float)d2[0] * (float)(scm & 0xffu);
-                        const float m1 = (float)d2[1] * (float)(scm >> 8);
+                        const float d1 = Q40 ? (float)d2[0] : (float)d2[0] * (float)(scm & 0xffu);   // Q4_0 / Q4_1: (s, t) as stored
+                        const float m1 = Q40 ? (float)d2[1] : (float)d2[1] * (float)(scm >> 8);
 #pragma unroll
                         for (int m = 0; m < M; ++m) {
                             const int p = __builtin_amdgcn_sdot4((int)hi, (int)xq[m][it][1], __builtin_amdgcn_sdot4((int)lo, (int)xq[m][it][0], 0, false), false);
@@ -676,8 +692,8 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
                     }
                     const f16x2 d2 = __builtin_bit_cast(f16x2, dw[i]);
                     const unsigned scm = (sw[i >> 1] >> (16 * (i & 1))) & 0xffffu;
-                    const float d1 = (float)d2[0] * (float)(scm & 0xffu);
-                    const float m1 = (float)d2[1] * (float)(scm >> 8);
+                    const float d1 = Q40 ? (float)d2[0] : (float)d2[0] * (float)(scm & 0xffu);   // Q4_0 / Q4_1: (s, t) as stored
+                    const float m1 = Q40 ? (float)d2[1] : (float)d2[1] * (float)(scm >> 8);
 #pragma unroll
                     for (int m = 0; m < M; ++m) {
                         float acc = val[m * R + 4 * r + i];
@@ -1831,6 +1847,71 @@ __global__ __launch_bounds__(256) void lm_q5k_unblock_kernel(const unsigned char
         if (e == 0) dd[blk] = (unsigned)bp[0] | ((unsigned)bp[1] << 8) | ((unsigned)bp[2] << 16) | ((unsigned)bp[3] << 24);
     }
 }
+// ---- Q4_0 / Q4_1 (18-byte block_q4_0 = { fp16 d; qs[16] }, 20-byte block_q4_1 = { fp16 d; fp16 m; qs[16] }; value j of a block is the low
+// nibble of qs[j], value j + 16 the high nibble).  Plain form on the device: q [N][K] one byte per 4-bit value, st [N][K / 32] uint
+// (fp16 s | fp16 t << 16) with value = s q - t: Q4_0 s = d, t = 8 d (exact in fp16 unless it overflows: *bad is set then and the load
+// fails), Q4_1 s = d, t = -m (the sign bit flipped).
+__device__ __forceinline__ unsigned q40_factors(unsigned short dbits, int* __restrict__ bad) {
+    const f16_t t = (f16_t)(8.0f * (float)__builtin_bit_cast(f16_t, dbits));
+    const unsigned short tb = __builtin_bit_cast(unsigned short, t);
+    if ((tb & 0x7c00u) == 0x7c00u) *bad = 1;   // inf or NaN
+    return (unsigned)dbits | ((unsigned)tb << 16);
+}
+template <bool Q41>
+__global__ __launch_bounds__(256) void lm_q40_unblock_kernel(const unsigned char* __restrict__ blocks, long nblocks, unsigned char* __restrict__ q,
+                                                             unsigned* __restrict__ st, int* __restrict__ bad) {
+    constexpr int BS = Q41 ? 20 : 18, Q0 = Q41 ? 4 : 2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nblocks * 32; i += (long)gridDim.x * blockDim.x) {
+        const long blk = i >> 5;
+        const int j = (int)(i & 31);
+        const unsigned char* bp = blocks + blk * BS;
+        const unsigned char byte = bp[Q0 + (j & 15)];
+        q[i] = j < 16 ? (byte & 0xF) : (byte >> 4);
+        if (j == 0) {
+            const unsigned short dbits = (unsigned short)bp[0] | ((unsigned short)bp[1] << 8);
+            if (Q41) st[blk] = (unsigned)dbits | (((unsigned)bp[2] | ((unsigned)bp[3] << 8)) ^ 0x8000u) << 16;
+            else st[blk] = q40_factors(dbits, bad);
+        }
+    }
+}
+// ggml's quantize_row_q4_0_ref / quantize_row_q4_1_ref restated from the published algorithm (ggml is not part of this tree: parity with
+// llama-quantize's own bits is not pinned).  Q4_0: max = the value of largest magnitude (the first on ties), d = max / -8,
+// id = d != 0 ? 1 / d : 0, q = min(15, (int)(x * id + 8.5f)).  Q4_1: d = (max - min) / 15, q = min(15, (int)((x - min) * id + 0.5f)).
+// Every operation is rounded to f32 on its own (the build runs with -ffp-contract=off); d and min are stored as fp16 (rne).
+template <bool Q41>
+__global__ __launch_bounds__(256) void lm_q40_quantize_kernel(const bf16_t* __restrict__ w, int is_f16, long nblocks, unsigned char* __restrict__ q,
+                                                              unsigned* __restrict__ st, int* __restrict__ bad) {
+    for (long blk = (long)blockIdx.x * blockDim.x + threadIdx.x; blk < nblocks; blk += (long)gridDim.x * blockDim.x) {
+        float v[32];
+        float amax = 0.0f, mx = 0.0f, lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            v[j] = w16_to_f32(w[blk * 32 + j], is_f16);
+            if (amax < fabsf(v[j])) { amax = fabsf(v[j]); mx = v[j]; }
+            lo = fminf(lo, v[j]);
+            hi = fmaxf(hi, v[j]);
+        }
+        const float d = Q41 ? (hi - lo) / 15.0f : mx / -8.0f;
+        const float id = d != 0.0f ? 1.0f / d : 0.0f;
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            const float y = Q41 ? (v[j] - lo) * id + 0.5f : v[j] * id + 8.5f;
+            q[blk * 32 + j] = (unsigned char)min(15, (int)y);
+        }
+        const unsigned short dbits = __builtin_bit_cast(unsigned short, (f16_t)d);
+        if (Q41) st[blk] = (unsigned)dbits | ((unsigned)(__builtin_bit_cast(unsigned short, (f16_t)lo) ^ 0x8000u) << 16);
+        else st[blk] = q40_factors(dbits, bad);
+    }
+}
+// s q - t in f32: d q and 8 d are exact and so is their difference, d (q - 8) (dequantize_row_q4_0's value); for Q4_1 the subtraction of
+// t = -m is dequantize_row_q4_1's one rounding on d q + m
+__device__ __forceinline__ float q40_value(unsigned st, unsigned q) {
+    const f16x2 f = __builtin_bit_cast(f16x2, st);
+    return (float)f[0] * (float)q - (float)f[1];
+}
+__global__ __launch_bounds__(256) void lm_q40_dequant_f32_kernel(const unsigned char* __restrict__ q, const unsigned* __restrict__ st, float* __restrict__ out, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = q40_value(st[i >> 5], q[i]);
+}
 // This build's Q4_K quantiser (oracle/q4k_ref.py::quantize_q4_k, operation for operation): per 32 values offset o = -min(0, min w)
 // and step s = (max w + o) / 15; per 256 d = max s / 63, dmin = max o / 63 (fp16); sc = round(s / d), m = round(o / dmin);
 // q = clamp(round((w + dmin m) / (d sc)), 0, 15).  llama-quantize searches for better scales; the FORMAT and its de-quantisation are GGUF's.
@@ -1888,9 +1969,10 @@ __host__ __device__ __forceinline__ long packed_slot_row(long slot, int qkv_pair
     const long pp = slot >> 1;
     return (pp >> 5) * 64 + (pp & 31) + 32 * (slot & 1);
 }
-// plain -> the quad-interleaved GEMV layout (GemvQ8 with dd).  Q5 (Q5_K): the low nibbles as for Q4_K, bit 4 of every value into the
-// plane qh[quad][k / 8] (q5k_hbit).
-template <bool Q5>
+// plain -> the quad-interleaved GEMV layout (GemvQ8 with dd).  WF_Q5K: the low nibbles as for Q4_K, bit 4 of every value into the
+// plane qh[quad][k / 8] (q5k_hbit).  WF_Q40 (Q4_0 / Q4_1): the nibbles as for Q4_K; `dd` is the plain factor array st [N][K / 32] and
+// `odd` its slot-grouped copy [ceil(N / 16)][K / 32][16] (scm / oscm unused).
+template <int WF>
 __global__ __launch_bounds__(256) void lm_q4k_pack_kernel(const unsigned char* __restrict__ q, const unsigned short* __restrict__ scm, const unsigned* __restrict__ dd,
                                                           int N, int K, int qkv_pairs, u32x4* __restrict__ qs, unsigned short* __restrict__ oscm, unsigned* __restrict__ odd,
                                                           unsigned* __restrict__ qh) {
@@ -1898,6 +1980,7 @@ __global__ __launch_bounds__(256) void lm_q4k_pack_kernel(const unsigned char* _
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nquad * nchunk; i += (long)gridDim.x * blockDim.x) {
         const long quad = i / nchunk;
         const int c = (int)(i - quad * nchunk);
+        constexpr bool Q5 = WF == WF_Q5K, Q40 = WF == WF_Q40;
         unsigned dw[4], hb = 0;
 #pragma unroll
         for (int sl = 0; sl < 4; ++sl) {
@@ -1912,8 +1995,12 @@ __global__ __launch_bounds__(256) void lm_q4k_pack_kernel(const unsigned char* _
 #pragma unroll
                     for (int j = 0; j < 8; ++j) hb |= ((bytes[j >> 2] >> (8 * (j & 3) + 4)) & 1u) << q5k_hbit(sl, j);
                 }
-                if ((c & 3) == 0) oscm[q4k_scm_index(slot, c >> 2, nkb)] = scm[row * nkb + (c >> 2)];
-                if ((c & 31) == 0) odd[q4k_scm_index(slot, c >> 5, nk256)] = dd[row * nk256 + (c >> 5)];
+                if (Q40) {
+                    if ((c & 3) == 0) odd[q4k_scm_index(slot, c >> 2, nkb)] = dd[row * nkb + (c >> 2)];
+                } else {
+                    if ((c & 3) == 0) oscm[q4k_scm_index(slot, c >> 2, nkb)] = scm[row * nkb + (c >> 2)];
+                    if ((c & 31) == 0) odd[q4k_scm_index(slot, c >> 5, nk256)] = dd[row * nk256 + (c >> 5)];
+                }
             }
             dw[sl] = v;
         }
@@ -1993,7 +2080,7 @@ struct WMat {
     int N = 0, K = 0;
     bf16_t* w = nullptr;        // WF_BF16 / WF_F16: row-major 16-bit values
     u32x4* qs = nullptr;        // WF_Q8 / WF_Q4K (GemvQ8)
-    unsigned* sc = nullptr;
+    unsigned* sc = nullptr;     // WF_Q40 / WF_Q41: the (s | t << 16) factor dwords
     unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K
     unsigned* qh = nullptr;     // WF_Q5K: the plane of high bits [N / 4][K / 8]
     void release() {
@@ -2007,6 +2094,7 @@ struct WMat {
     long stream_bytes() const {   // bytes one decode pass reads of it
         const long n = (long)N * K;
         if (fmt == WF_Q5K) return n / 2 + n / 8 + n / 16 + n / 64;   // nibbles, plane, (sc, m), (d, dmin): 5.6 bits per weight
+        if (fmt == WF_Q40 || fmt == WF_Q41) return n / 2 + n / 8;    // nibbles, (s, t): 5.0 bits per weight
         return fmt == WF_Q8 ? n + n / 16 : (fmt == WF_Q4K ? n / 2 + n / 16 + n / 64 : (fmt == WF_Q6K ? n + n / 4 : 2 * n));
     }
 };
@@ -2197,7 +2285,7 @@ static int lm_check_cfg(const rca_lm_config_t* c) {
     if (c->ffn > LM_KSLICE * LM_MAXSPLIT) return fail(RCA_ERR_ARG, "ffn > %d unsupported", LM_KSLICE * LM_MAXSPLIT);
     if (c->ffn > LM_KSLICE && c->ffn % LM_KSLICE) return fail(RCA_ERR_ARG, "ffn above %d must be a multiple of it", LM_KSLICE);
     if (c->vocab_size < 2 || c->n_layers < 1 || c->n_ctx < 2) return fail(RCA_ERR_ARG, "bad sizes");
-    if (c->decode_weights < 0 || c->decode_weights > 4) return fail(RCA_ERR_ARG, "decode_weights %d (0 as supplied, 1 q8_0, 2 f16, 3 q4_k, 4 q5_k)", c->decode_weights);
+    if (c->decode_weights < 0 || c->decode_weights > 6) return fail(RCA_ERR_ARG, "decode_weights %d (0 as supplied, 1 q8_0, 2 f16, 3 q4_k, 4 q5_k, 5 q4_0, 6 q4_1)", c->decode_weights);
     return RCA_OK;
 }
 
@@ -2209,7 +2297,7 @@ struct RawMat {
     bf16_t* w16 = nullptr;      // WF_BF16 / WF_F16
     signed char* q = nullptr;   // WF_Q8: int8 [rows][cols]; WF_Q4K / WF_Q5K: one byte per 4-bit / 5-bit value (the rest as WF_Q4K)
     f16_t* d = nullptr;         // WF_Q8: fp16 [rows][cols / 32]; WF_Q4K / WF_Q5K: ushort (sc | m << 8) [rows][cols / 32]
-    unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K: (d | dmin << 16) [rows][cols / 256]
+    unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K: (d | dmin << 16) [rows][cols / 256]; WF_Q40 / WF_Q41: (s | t << 16) [rows][cols / 32] (q as WF_Q4K, d unused)
     void release() {
         for (void* p : {(void*)w16, (void*)q, (void*)d, (void*)dd})
             if (p) (void)hipFree(p);
@@ -2218,6 +2306,7 @@ struct RawMat {
     // (array, bytes per row) of every component
     int parts(void** ptr, long* row_bytes) const {
         if (fmt == WF_Q4K || fmt == WF_Q5K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; ptr[2] = dd; row_bytes[2] = cols / 256 * 4; return 3; }
+        if (fmt == WF_Q40 || fmt == WF_Q41) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = dd; row_bytes[1] = cols / 32 * 4; return 2; }
         if (fmt == WF_Q6K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 16; ptr[2] = dd; row_bytes[2] = cols / 256 * 2; return 3; }   // d: int8 scales, dd: fp16 d
         if (fmt == WF_Q8) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; return 2; }
         ptr[0] = w16; row_bytes[0] = cols * 2;
@@ -2230,6 +2319,11 @@ struct RawMat {
             if (c % 256) return fail(RCA_ERR_ARG, "%s needs rows of a multiple of 256 values (got %ld)", f == WF_Q5K ? "Q5_K" : "Q4_K", c);
             if ((rc = lm_alloc((void**)&q, (size_t)r * c)) != RCA_OK || (rc = lm_alloc((void**)&d, (size_t)r * (c / 32) * 2)) != RCA_OK ||
                 (rc = lm_alloc((void**)&dd, (size_t)r * (c / 256) * 4)) != RCA_OK) { release(); return rc; }
+            return RCA_OK;
+        }
+        if (f == WF_Q40 || f == WF_Q41) {
+            if (c % 256) return fail(RCA_ERR_ARG, "%s needs rows of a multiple of 256 values (got %ld)", f == WF_Q41 ? "Q4_1" : "Q4_0", c);
+            if ((rc = lm_alloc((void**)&q, (size_t)r * c)) != RCA_OK || (rc = lm_alloc((void**)&dd, (size_t)r * (c / 32) * 4)) != RCA_OK) { release(); return rc; }
             return RCA_OK;
         }
         if (f == WF_Q6K) {
@@ -2297,6 +2391,28 @@ static int lm_upload_raw(rca_lm* h, const rca_tensor_t* ts, int nt, const std::s
         if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
         return RCA_OK;
     }
+    if (t->dtype == RCA_Q4_0 || t->dtype == RCA_Q4_1) {
+        const bool q41 = t->dtype == RCA_Q4_1;
+        if ((rc = out->alloc(q41 ? WF_Q41 : WF_Q40, rows, cols)) != RCA_OK) return rc;
+        const long nblk = numel / 32;
+        const size_t nbytes = (size_t)nblk * (q41 ? 20 : 18);
+        unsigned char* raw = nullptr;   // the blocks, then the flag "a block's 8 d overflows fp16"
+        if ((rc = lm_alloc((void**)&raw, nbytes + 8)) != RCA_OK) { out->release(); return rc; }
+        int* bad = reinterpret_cast<int*>(raw + ((nbytes + 3) & ~(size_t)3));
+        int bad_h = 0;
+        hipError_t e = hipMemcpy(raw, t->data, nbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 4, h->stream);
+        if (e == hipSuccess) {
+            if (q41) lm_q40_unblock_kernel<true><<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, out->dd, bad);
+            else lm_q40_unblock_kernel<false><<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, out->dd, bad);
+            e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        }
+        (void)hipFree(raw);
+        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
+        if (bad_h) { out->release(); return fail(RCA_ERR_ARG, "tensor '%s': a Q4_0 block's 8 d is not finite in fp16", name.c_str()); }
+        return RCA_OK;
+    }
     if (t->dtype == RCA_Q4_K) {
         if ((rc = out->alloc(WF_Q4K, rows, cols)) != RCA_OK) return rc;
         const long nblk = numel / 256;
@@ -2360,12 +2476,13 @@ static int lm_upload_embed(rca_lm* h, const rca_tensor_t* ts, int nt, const std:
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e));
         return RCA_OK;
     }
-    if (t->dtype == RCA_Q8_0 || t->dtype == RCA_Q4_K || t->dtype == RCA_Q6_K || t->dtype == RCA_Q5_K) {
+    if (t->dtype == RCA_Q8_0 || t->dtype == RCA_Q4_K || t->dtype == RCA_Q6_K || t->dtype == RCA_Q5_K || t->dtype == RCA_Q4_0 || t->dtype == RCA_Q4_1) {
         RawMat raw;
         if ((rc = lm_upload_raw(h, ts, nt, name, rows, cols, &raw)) != RCA_OK) return rc;
         if (raw.fmt == WF_Q6K) lm_q6k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>(raw.q, (const signed char*)raw.d, (const f16_t*)raw.dd, (float*)h->embed, numel);
         else if (raw.fmt == WF_Q4K || raw.fmt == WF_Q5K)   // the plain byte holds the whole value, 4 or 5 bits
             lm_q4k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, (const unsigned short*)raw.d, raw.dd, (float*)h->embed, numel);
+        else if (raw.fmt == WF_Q40 || raw.fmt == WF_Q41) lm_q40_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, raw.dd, (float*)h->embed, numel);
         else lm_q8_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>(raw.q, raw.d, (float*)h->embed, numel);
         hipError_t e = hipStreamSynchronize(h->stream);
         raw.release();
@@ -2397,11 +2514,31 @@ static int lm_upload_f32(const rca_tensor_t* ts, int nt, const std::string& name
 }
 
 // rca_lm_config_t::decode_weights applied to one plain matrix: 1 = quantise to q8_0 the way llama-quantize does, 2 = fp16,
-// 3 / 4 = this build's Q4_K / Q5_K quantiser.
+// 3 / 4 = this build's Q4_K / Q5_K quantiser, 5 / 6 = ggml's reference Q4_0 / Q4_1 rule.
 // A matrix that ARRIVED quantised stays what it is.
 static int lm_raw_convert(rca_lm* h, RawMat* m, int want) {
-    if (want == 0 || m->fmt == WF_Q8 || m->fmt == WF_Q4K || m->fmt == WF_Q6K || m->fmt == WF_Q5K) return RCA_OK;
+    if (want == 0 || wf_packed(m->fmt)) return RCA_OK;
     int rc;
+    if (want == 5 || want == 6) {
+        RawMat qd;
+        if ((rc = qd.alloc(want == 6 ? WF_Q41 : WF_Q40, m->rows, m->cols)) != RCA_OK) return rc;
+        int* bad = nullptr;
+        int bad_h = 0;
+        if ((rc = lm_alloc((void**)&bad, 4)) != RCA_OK) { qd.release(); return rc; }
+        hipError_t e = hipMemsetAsync(bad, 0, 4, h->stream);
+        if (e == hipSuccess) {
+            if (want == 6) lm_q40_quantize_kernel<true><<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 32, (unsigned char*)qd.q, qd.dd, bad);
+            else lm_q40_quantize_kernel<false><<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 32, (unsigned char*)qd.q, qd.dd, bad);
+            e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        }
+        (void)hipFree(bad);
+        m->release();
+        if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "%s quantise: %s", want == 6 ? "Q4_1" : "Q4_0", hipGetErrorString(e)); }
+        if (bad_h) { qd.release(); return fail(RCA_ERR_ARG, "Q4_0 quantise: a block's 8 d is not finite in fp16"); }
+        *m = qd;
+        return RCA_OK;
+    }
     if (want == 3) {
         RawMat qd;
         if ((rc = qd.alloc(WF_Q4K, m->rows, m->cols)) != RCA_OK) return rc;
@@ -2496,11 +2633,26 @@ static int lm_finish_mat(rca_lm* h, RawMat* raw, int qkv_pairs, WMat* out, const
         (void)hipMemsetAsync(out->sc, 0, scm_bytes, h->stream);
         (void)hipMemsetAsync(out->dd, 0, dd_bytes, h->stream);
         if (q5)
-            lm_q4k_pack_kernel<true><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
+            lm_q4k_pack_kernel<WF_Q5K><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
                                                                   (unsigned short*)out->sc, out->dd, out->qh);
         else
-            lm_q4k_pack_kernel<false><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
+            lm_q4k_pack_kernel<WF_Q4K><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
                                                                    (unsigned short*)out->sc, out->dd, nullptr);
+        hipError_t e = hipStreamSynchronize(h->stream);
+        raw->release();
+        if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s pack of %s: %s", fn, what, hipGetErrorString(e));
+        return RCA_OK;
+    }
+    if (raw->fmt == WF_Q40 || raw->fmt == WF_Q41) {
+        const int N = out->N, K = out->K;
+        const char* fn = raw->fmt == WF_Q41 ? "Q4_1" : "Q4_0";
+        if ((K % 256) || (N % 4) || (qkv_pairs && (N % 64))) { raw->release(); return fail(RCA_ERR_ARG, "%s weights: %s is %d x %d (K must be a multiple of 256, N of 4)", fn, what, N, K); }
+        int rc;
+        const long nquad = N / 4, nchunk = K / 8, g16 = (N + 15) / 16;
+        const size_t st_bytes = (size_t)g16 * (K / 32) * 16 * 4;   // groups of 16 slots, zero padded
+        if ((rc = lm_alloc((void**)&out->qs, (size_t)nquad * nchunk * 16)) != RCA_OK || (rc = lm_alloc((void**)&out->sc, st_bytes)) != RCA_OK) { raw->release(); return rc; }
+        (void)hipMemsetAsync(out->sc, 0, st_bytes, h->stream);
+        lm_q4k_pack_kernel<WF_Q40><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, nullptr, raw->dd, N, K, qkv_pairs, out->qs, nullptr, out->sc, nullptr);
         hipError_t e = hipStreamSynchronize(h->stream);
         raw->release();
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s pack of %s: %s", fn, what, hipGetErrorString(e));
@@ -2801,14 +2953,14 @@ extern "C" int rca_lm_create_shared(rca_lm_t* parent, int32_t n_ctx, int32_t log
 // ------------------------------------------------------------------------- forward pass (M tokens)
 // The one place that turns a matrix's runtime format into a template argument: f(std::integral_constant<int, WF_...>{}).  A new
 // format is added here (and to WF_FORMATS) and every launcher below sees it.
-static constexpr int WF_FORMATS[] = {WF_BF16, WF_Q8, WF_F16, WF_Q4K, WF_Q6K, WF_Q5K};
-constexpr bool wf_packed(int fmt) { return fmt == WF_Q8 || fmt == WF_Q4K || fmt == WF_Q6K || fmt == WF_Q5K; }
+static constexpr int WF_FORMATS[] = {WF_BF16, WF_Q8, WF_F16, WF_Q4K, WF_Q6K, WF_Q5K, WF_Q40};
 template <class F>
 static void wf_dispatch(int fmt, F&& f) {
     switch (fmt) {
         case WF_Q6K: return f(std::integral_constant<int, WF_Q6K>{});
         case WF_Q4K: return f(std::integral_constant<int, WF_Q4K>{});
         case WF_Q5K: return f(std::integral_constant<int, WF_Q5K>{});
+        case WF_Q40: case WF_Q41: return f(std::integral_constant<int, WF_Q40>{});   // one form on the device: the two differ only at load
         case WF_Q8: return f(std::integral_constant<int, WF_Q8>{});
         case WF_F16: return f(std::integral_constant<int, WF_F16>{});
         default: return f(std::integral_constant<int, WF_BF16>{});
@@ -2851,9 +3003,9 @@ static void launch_gemv_r(const GemvGeom& g, rca_lm* h, const WMat& w, const flo
         case 4: lm_gemv_kernel<M, NIT, 4, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
         case 8: lm_gemv_kernel<M, NIT, 8, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
         default:
-            // Q5_K at NIT = 4: launch_gemv_q never leaves R = 16 (four quads x four chunks = 16 loads, twice its limit), and the instance
-            // would not fit the register file (it spills): not built
-            if constexpr (!(Q == WF_Q5K && NIT == 4))
+            // Q5_K / Q4_0 at NIT = 4: launch_gemv_q never leaves R = 16 (four quads x four chunks = 16 loads, twice its limit), and the
+            // instance would not fit the register file (it spills): not built
+            if constexpr (!((Q == WF_Q5K || Q == WF_Q40) && NIT == 4))
                 lm_gemv_kernel<M, NIT, 16, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope);
             break;
     }
@@ -2863,10 +3015,10 @@ static void launch_gemv_q(GemvGeom g, rca_lm* h, int M, const WMat& w, const flo
                           const GemvRope& rope, hipStream_t st) {
     const int nit = cdiv(cdiv(K >> 3, 4), 64);
     // 16-byte weight loads in flight per lane: at most 16 (registers); q8_0 needs one load per row PAIR
-    const int lpr = (Q == WF_Q8 || Q == WF_Q6K) ? 2 : ((Q == WF_Q4K || Q == WF_Q5K) ? 4 : 1);
-    const int max_loads = (Q == WF_Q4K || Q == WF_Q5K) ? 8 : 16;   // Q4_K / Q5_K also hold the factors of every quad in registers
+    const int lpr = (Q == WF_Q8 || Q == WF_Q6K) ? 2 : ((Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40) ? 4 : 1);
+    const int max_loads = (Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40) ? 8 : 16;   // Q4_K / Q5_K / Q4_0 also hold the factors of every quad in registers
     while (g.R > 4 && (g.R / lpr) * (nit == 3 ? 4 : nit) > max_loads) g.R >>= 1;
-    if ((Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K) && g.R < 8) g.R = 8;   // a Q4_K batch is at least two quads (one per register half); Q6_K scale loads cover two pairs
+    if ((Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K || Q == WF_Q40) && g.R < 8) g.R = 8;   // a Q4_K batch is at least two quads (one per register half); Q6_K scale loads cover two pairs
     if (PRO == 0 && EPI == 3 && nit > 1) {
         if (nit == 2) {
             if (M == 1) launch_gemv_r<1, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
@@ -3888,11 +4040,13 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
     const float* gS6 = WF == WF_Q6K ? reinterpret_cast<const float*>(q8.sc) + 2 * q8_sc_index((n0 >> 1) + qp, (ks >> 4) + ((tid & 3) >> 1), K >> 4) : nullptr;   // next stage: + 2 groups of 16
     // Q4_K: a thread's stage is HALF a 16-byte unit = 8 k of two adjacent slots: quad tid / 8, chunk (tid / 2) % 4, slots 2 (tid % 2) + {0, 1}
     const int q4quad = tid >> 3, q4half = tid & 1, q4slot = 4 * ((n0 >> 2) + q4quad) + 2 * q4half;
-    constexpr bool W4 = WF == WF_Q4K || WF == WF_Q5K;   // Q5_K: the Q4_K staging + the quad's dword of high bits (arrives as W)
+    constexpr bool W40 = WF == WF_Q40;                  // Q4_0 / Q4_1: the Q4_K staging with the (s | t << 16) dword of each slot and stage
+    constexpr bool W4 = WF == WF_Q4K || WF == WF_Q5K || W40;   // Q5_K: the Q4_K staging + the quad's dword of high bits (arrives as W)
     const unsigned* gH5 = WF == WF_Q5K ? reinterpret_cast<const unsigned*>(W) + ((long)(n0 >> 2) + q4quad) * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3) : nullptr;
     const uint2* gQ4 = W4 ? reinterpret_cast<const uint2*>(q8.qs + ((long)(n0 >> 2) + q4quad) * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3)) + q4half : nullptr;
-    const unsigned short* gS4 = W4 ? reinterpret_cast<const unsigned short*>(q8.sc) + q4k_scm_index(q4slot, ks >> 5, q_nkb) : nullptr;   // next sub-block: + 16
-    const unsigned* gD4 = W4 ? q8.dd + q4k_scm_index(q4slot, 0, K >> 8) : nullptr;                                                     // super-block k / 256: + 16 each
+    const unsigned short* gS4 = (W4 && !W40) ? reinterpret_cast<const unsigned short*>(q8.sc) + q4k_scm_index(q4slot, ks >> 5, q_nkb) : nullptr;   // next sub-block: + 16
+    const unsigned* gF40 = W40 ? q8.sc + q4k_scm_index(q4slot, ks >> 5, q_nkb) : nullptr;                                                      // next block: + 16
+    const unsigned* gD4 = (W4 && !W40) ? q8.dd + q4k_scm_index(q4slot, 0, K >> 8) : nullptr;                                                     // super-block k / 256: + 16 each
     int q4row[2];   // LDS rows of the two slots
 #pragma unroll
     for (int i = 0; i < 2; ++i) q4row[i] = (int)packed_slot_row(4 * q4quad + 2 * q4half + i, EPI == GEMM_EPI_ROPE);
@@ -3911,8 +4065,12 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
         if (W4) {
             const uint2 t = gQ4[(long)st * 8];                       // + 4 units of 16 bytes per stage
             rw[slot][0] = make_uint4(t.x, t.y, WF == WF_Q5K ? gH5[(long)st * 4] : 0u, 0u);
-            rs[slot] = *reinterpret_cast<const unsigned*>(gS4 + (long)st * 16);          // (sc | m << 8) of the two slots
-            rdd[slot] = *reinterpret_cast<const uint2*>(gD4 + (long)(((ks >> 5) + st) >> 3) * 16);   // (d | dmin << 16) of the two slots
+            if constexpr (W40) {
+                rdd[slot] = *reinterpret_cast<const uint2*>(gF40 + (long)st * 16);       // (s | t << 16) of the two slots
+            } else {
+                rs[slot] = *reinterpret_cast<const unsigned*>(gS4 + (long)st * 16);          // (sc | m << 8) of the two slots
+                rdd[slot] = *reinterpret_cast<const uint2*>(gD4 + (long)(((ks >> 5) + st) >> 3) * 16);   // (d | dmin << 16) of the two slots
+            }
         } else if (WF == WF_Q6K) {
             const u32x4 t = gQ[st * 4];
             rw[slot][0] = make_uint4(t.x, t.y, t.z, t.w);
@@ -3954,13 +4112,13 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
             const unsigned qw[2] = {rw[ws][0].x, rw[ws][0].y}, ddw[2] = {rdd[ws].x, rdd[ws].y};
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const unsigned scm = (rs[ws] >> (16 * c)) & 0xffffu;
+                const unsigned scm = W40 ? 0u : (rs[ws] >> (16 * c)) & 0xffffu;
                 float wv[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     unsigned qv = (qw[c] >> (4 * j)) & 0xFu;
                     if (WF == WF_Q5K) qv |= ((rw[ws][0].z >> q5k_hbit(2 * q4half + c, j)) & 1u) << 4;
-                    wv[j] = q4k_value(ddw[c], scm, qv);
+                    wv[j] = W40 ? q40_value(ddw[c], qv) : q4k_value(ddw[c], scm, qv);   // Q4_0 / Q4_1: s q - t
                 }
                 uint4 hi, lo;
                 split_w8(wv, hi, lo);
@@ -5303,6 +5461,8 @@ extern "C" int rca_lm_mask_head_rows(rca_lm_t* h, int32_t row_begin, int32_t row
         lm_q6k_zero_row_scales_kernel<<<256, 256, 0, h->stream>>>((float*)h->head.sc, h->cfg.hidden / 16, row_begin, row_end);
     if (n > 0 && (h->head.fmt == WF_Q4K || h->head.fmt == WF_Q5K))   // Q4_K / Q5_K: d = dmin = 0 makes every value of the row (0 * sc) * q - (0 * m) = 0
         lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.dd, h->cfg.hidden / 256, row_begin, row_end);
+    if (n > 0 && (h->head.fmt == WF_Q40 || h->head.fmt == WF_Q41))   // Q4_0 / Q4_1: s = t = 0 makes every value of the row 0 * q - 0 = 0 (the same slot-grouped index, per 32 values)
+        lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.sc, h->cfg.hidden / 32, row_begin, row_end);
     if (n > 0 && (h->head.fmt == WF_BF16 || h->head.fmt == WF_F16)) lm_zero_rows_kernel<<<2048, 256, 0, h->stream>>>(h->head.w + (long)row_begin * h->cfg.hidden, n);   // zero bits
     if (n > 0 && h->head.fmt == WF_Q8)   // the packed q8_0 head: a row is zero when its block scales are
         lm_q8_zero_row_scales_kernel<<<256, 256, 0, h->stream>>>(h->head.sc, h->cfg.hidden / 32, row_begin, row_end);
@@ -5421,7 +5581,7 @@ extern "C" int rca_lm_set_act_format(rca_lm_t* h, int32_t fmt) {
     if (!h) return fail(RCA_ERR_ARG, "null");
     if (fmt != 0 && fmt != 1) return fail(RCA_ERR_ARG, "set_act_format: %d is neither 0 (f32) nor 1 (q8_1)", fmt);
     if (fmt == 1 && !lm_has_packed_matrix(h))
-        return fail(RCA_ERR_ARG, "set_act_format: q8_1 activations need a q8_0 / Q4_K / Q6_K or Q5_K projection matrix, and this handle keeps all of its matrices in 16-bit floats");
+        return fail(RCA_ERR_ARG, "set_act_format: q8_1 activations need a q8_0 / Q4_K / Q6_K, Q5_K or Q4_0 / Q4_1 projection matrix, and this handle keeps all of its matrices in 16-bit floats");
     { const int src = lm_settle(h); if (src != RCA_OK) return src; }
     if (h->act_format != fmt) {
         RCA_HIP(hipSetDevice(h->device));
@@ -5493,8 +5653,8 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
     return RCA_OK;
 }
 
-// the format the projection matrices are kept (and streamed) in: 0 bf16, 1 q8_0, 2 f16, 3 q4_k, 5 q5_k (4 = Q6_K, which only ever appears next
-// to Q4_K / Q5_K tensors); bytes = weight bytes one decode step reads
+// the format the projection matrices are kept (and streamed) in: 0 bf16, 1 q8_0, 2 f16, 3 q4_k, 5 q5_k, 6 q4_0, 7 q4_1 (4 = Q6_K, which only ever
+// appears next to Q4_K / Q5_K / Q4_0 tensors); bytes = weight bytes one decode step reads
 extern "C" int rca_lm_weight_format(const rca_lm_t* h, int32_t* fmt, int64_t* bytes_per_step) {
     if (!h || !fmt) return fail(RCA_ERR_ARG, "null");
     *fmt = h->layers.empty() ? h->head.fmt : h->layers[0].gu.fmt;

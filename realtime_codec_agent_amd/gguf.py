@@ -13,7 +13,9 @@ de-quantised exactly (f32 rows on the device: llama.cpp's get_rows does the same
 rejected with a clear error -- except the two a Q4_K_M file (prep_test_model.sh:31) is made of: Q4_K (144-byte super-blocks, kept packed,
 RCA_Q4_K) and Q6_K (210-byte super-blocks: output.weight and the attn_v / ffn_down tensors llama-quantize's use_more_bits() picks;
 RCA_Q6_K, re-encoded losslessly on the device as int8 values + one f32 scale per 16) -- and Q5_K (176-byte super-blocks, kept packed,
-RCA_Q5_K), which with Q6_K makes up a Q5_K_S / Q5_K_M file.  Q2_K / Q3_K and the legacy 4- / 5-bit types stay refused.
+RCA_Q5_K), which with Q6_K makes up a Q5_K_S / Q5_K_M file.  Of the legacy types, Q4_0 (18-byte blocks of 32 values, RCA_Q4_0: the
+bulk of a llama-quantize Q4_0 file) and Q4_1 (20-byte blocks, RCA_Q4_1: what such a file keeps some ffn_down tensors in) are kept packed
+too.  Q2_K / Q3_K and the legacy 5-bit types Q5_0 / Q5_1 stay refused.
 
 Two things convert_hf_to_gguf.py does to a Llama checkpoint are undone here:
   * q_proj / k_proj rows are permuted from the rotate-half layout to interleaved pairs (LlamaModel.permute);
@@ -30,7 +32,7 @@ from typing import Any, BinaryIO, Dict, Tuple
 import numpy as np
 
 GGUF_MAGIC = 0x46554747  # "GGUF"
-GGML_F32, GGML_F16, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_BF16 = 0, 1, 8, 12, 13, 14, 30
+GGML_F32, GGML_F16, GGML_Q4_0, GGML_Q4_1, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_BF16 = 0, 1, 2, 3, 8, 12, 13, 14, 30
 _TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 9: "Q8_1", 10: "Q2_K", 11: "Q3_K",
                12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 15: "Q8_K", 30: "BF16"}
 # metadata value types
@@ -92,6 +94,10 @@ def _dequant(raw: np.ndarray, ttype: int, numel: int) -> np.ndarray:
         d = blk[:, :2].copy().view(np.float16).astype(np.float32)          # [nb,1]
         q = blk[:, 2:].view(np.int8).astype(np.float32)                    # [nb,32]
         return (q * d).reshape(-1)
+    if ttype in (GGML_Q4_0, GGML_Q4_1):
+        from ._native import Q40Blocks, Q41Blocks
+        cls = Q41Blocks if ttype == GGML_Q4_1 else Q40Blocks
+        return cls(raw[: numel // 32 * cls.BLOCK_BYTES], (numel // 32, 32)).dequantize().reshape(-1)
     if ttype == GGML_Q4_K:
         from ._native import Q4KBlocks
         return Q4KBlocks(raw[: numel // 256 * 144], (numel // 256, 256)).dequantize().reshape(-1)
@@ -101,7 +107,7 @@ def _dequant(raw: np.ndarray, ttype: int, numel: int) -> np.ndarray:
     if ttype == GGML_Q6_K:
         from ._native import Q6KBlocks
         return Q6KBlocks(raw[: numel // 256 * 210], (numel // 256, 256)).dequantize().reshape(-1)
-    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K are)")
+    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K are)")
 
 
 def _nbytes(ttype: int, numel: int) -> int:
@@ -113,6 +119,10 @@ def _nbytes(ttype: int, numel: int) -> int:
         if numel % 32:
             raise GGUFError("Q8_0 tensor whose size is not a multiple of 32")
         return numel // 32 * 34
+    if ttype in (GGML_Q4_0, GGML_Q4_1):
+        if numel % 32:
+            raise GGUFError(f"{_TYPE_NAMES[ttype]} tensor whose size is not a multiple of 32")
+        return numel // 32 * (20 if ttype == GGML_Q4_1 else 18)
     if ttype == GGML_Q4_K:
         if numel % 256:
             raise GGUFError("Q4_K tensor whose size is not a multiple of 256")
@@ -125,8 +135,8 @@ def _nbytes(ttype: int, numel: int) -> int:
         if numel % 256:
             raise GGUFError("Q6_K tensor whose size is not a multiple of 256")
         return numel // 256 * 210
-    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K are: the types of the "
-                    "reference's F16 / Q8_0 / Q4_K_M files and of Q5_K_S / Q5_K_M ones)")
+    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K are: the types "
+                    "of the reference's F16 / Q8_0 / Q4_K_M files and of Q5_K_S / Q5_K_M and Q4_0 ones)")
 
 
 def read_gguf(path: str, keep_q8_0: bool = False) -> Tuple[Dict[str, Any], Dict[str, np.ndarray]]:
@@ -168,6 +178,10 @@ def read_gguf(path: str, keep_q8_0: bool = False) -> Tuple[Dict[str, Any], Dict[
             if keep_q8_0 and ttype == GGML_Q4_K and len(ne) == 2 and ne[0] % 256 == 0:
                 from ._native import Q4KBlocks
                 tensors[name] = Q4KBlocks(raw, tuple(reversed(ne)))
+                continue
+            if keep_q8_0 and ttype in (GGML_Q4_0, GGML_Q4_1) and len(ne) == 2 and ne[0] % 32 == 0:
+                from ._native import Q40Blocks, Q41Blocks
+                tensors[name] = (Q41Blocks if ttype == GGML_Q4_1 else Q40Blocks)(raw, tuple(reversed(ne)))
                 continue
             if keep_q8_0 and ttype == GGML_Q5_K and len(ne) == 2 and ne[0] % 256 == 0:
                 from ._native import Q5KBlocks
