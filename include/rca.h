@@ -340,6 +340,9 @@ int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1);
 /* Tests only: raw fp16 rows [n_pos][n_kv_heads][64] of positions [pos0, pos0 + n_pos) (inside n_ctx) of one layer's K and V cache,
  * after draining the handle's stream.  Either pointer may be NULL. */
 int rca_lm_kv_read(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, uint16_t* k_host, uint16_t* v_host);
+/* Tests only: the inverse of rca_lm_kv_read: the raw fp16 rows [n_pos][n_kv_heads][64] replace positions [pos0, pos0 + n_pos) (inside
+ * n_ctx) of one layer's K and V cache, after draining the handle's stream.  Either pointer may be NULL.  n_tokens is left as it was. */
+int rca_lm_kv_write(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, const uint16_t* k_host, const uint16_t* v_host);
 /* run the handle's stream at the device's lowest (1) / highest (0) stream priority: background prefill next to a live session */
 int rca_lm_set_low_priority(rca_lm_t* h, int32_t enable);
 /* read / write Llama.n_tokens: the agent rolls the KV cache back by writing it
@@ -476,6 +479,17 @@ int rca_lm_get_act_format(const rca_lm_t* h, int32_t* fmt);
  * buffers and the cache rows at those positions are overwritten. */
 int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const float* x_host, int32_t M, float* y_host, int64_t y_numel,
                     uint16_t* kv_host);
+/* Tests only: the attention of ONE layer exactly as a pass launches it (the same launcher picks the kernel, the grid and the merge), for
+ * M query tokens at positions n_tokens .. n_tokens+M-1 over whatever the layer's cache holds (rca_lm_kv_write).  q_host [M][n_heads*64]
+ * f32 are the query rows after RoPE.  route 0: the decode launch (M 1..2, follows rca_lm_set_attn_fuse); 1: the prefill launch with f32
+ * output (the 32-token-tile route's, M 1..1024); 2: the prefill launch with bf16 hi / lo output (the 128-token-tile route's; hi + lo is
+ * returned as f32), refused on a handle whose prefill route is not that one.  nsp_launch: 256-key splits the decode launch covers, 0 =
+ * the splits the positions need, else a value from there up to the handle's split count (the bucketed launches of the captured graphs).
+ * out_host [out_rows][n_heads*64], M <= out_rows <= 1024: the device rows are filled with NaN before the launch, so rows >= M come back
+ * NaN unless the kernel wrote them.  n_tokens is left as it was; the handle's activation buffers are overwritten.  A bad layer, route, M,
+ * nsp_launch or out_rows, or positions past n_ctx, are refused before anything is touched. */
+int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_t nsp_launch, const float* q_host, int32_t M, float* out_host,
+                    int32_t out_rows);
 /* synchronise the handle's stream (timing) */
 int rca_lm_sync(rca_lm_t* h);
 int rca_codec_sync(rca_codec_t* h);

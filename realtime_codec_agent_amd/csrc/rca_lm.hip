@@ -3640,7 +3640,13 @@ __global__ __launch_bounds__(64 * FLASH_WAVES * TEAMS, 3) void lm_attn_flash_ker
             const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 16 * sub), b = *reinterpret_cast<const f32x4*>(qp + 16 * sub + 4);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float q = (j < 4 ? a[j] : b[j - 4]) * qs;
+                float q = (j < 4 ? a[j] : b[j - 4]) * qs;
+                // the product as ONE f32 value for both uses below.  Left to itself the compiler folds the multiply into the conversion
+                // that feeds the subtraction (v_fma_mixlo_f16: the exact product rounded once) but not into the one that feeds the MFMA
+                // operand (v_cvt_pk_f16_f32 of the f32 product: rounded twice); where the two differ -- a product next to the middle
+                // of two fp16 values -- lo completed another hi than the one in use and the element was off by a whole fp16 ulp
+                // (tests/test_attn_gpu.py: one row in a few hundred with weights off by 1e-3)
+                asm("" : "+v"(q));
                 const _Float16 h16 = (_Float16)q;
                 qh[sub][j] = h16;
                 ql[sub][j] = (_Float16)(q - (float)h16);
@@ -4795,6 +4801,21 @@ extern "C" int rca_lm_kv_read(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t 
     if (v_host && bytes) RCA_HIP(hipMemcpy(v_host, h->vc + off, bytes, hipMemcpyDeviceToHost));
     return RCA_OK;
 }
+// tests only: the inverse of rca_lm_kv_read (n_tokens stays as it is)
+extern "C" int rca_lm_kv_write(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, const uint16_t* k_host, const uint16_t* v_host) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    const rca_lm_config_t& c = h->cfg;
+    if (layer < 0 || layer >= c.n_layers) return fail(RCA_ERR_ARG, "kv_write: layer %d outside [0, %d)", layer, c.n_layers);
+    if (pos0 < 0 || n_pos < 0 || pos0 > c.n_ctx - n_pos) return fail(RCA_ERR_ARG, "kv_write: positions [%d, %d + %d) outside the context of %d", pos0, pos0, n_pos, c.n_ctx);
+    RCA_HIP(hipSetDevice(h->device));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    h->async_pending = false;
+    const long off = (long)layer * h->kv_layer_stride + (long)pos0 * c.n_kv_heads * 64;
+    const size_t bytes = (size_t)n_pos * c.n_kv_heads * 64 * sizeof(f16_t);
+    if (k_host && bytes) RCA_HIP(hipMemcpy(h->kc + off, k_host, bytes, hipMemcpyHostToDevice));
+    if (v_host && bytes) RCA_HIP(hipMemcpy(h->vc + off, v_host, bytes, hipMemcpyHostToDevice));
+    return RCA_OK;
+}
 extern "C" int rca_lm_set_low_priority(rca_lm_t* h, int32_t enable) {
     if (!h) return fail(RCA_ERR_ARG, "null");
     RCA_HIP(hipSetDevice(h->device));
@@ -5650,6 +5671,67 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (head_out) (void)hipFree(head_out);
     if (e != hipSuccess) return fail(RCA_ERR_HIP, "gemv_tap: %s", hipGetErrorString(e));
+    return RCA_OK;
+}
+// tests only: the attention of one layer alone, launched by the very call the passes make for it (launch_attention_mfma), for M host-supplied
+// post-RoPE query rows at positions n_tokens .. n_tokens + M - 1 over whatever the cache holds (rca_lm_kv_write)
+extern "C" int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_t nsp_launch, const float* q_host, int32_t M, float* out_host,
+                               int32_t out_rows) {
+    if (!h || !q_host || !out_host) return fail(RCA_ERR_ARG, "null");
+    const rca_lm_config_t& c = h->cfg;
+    const int QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim;
+    if (layer < 0 || layer >= c.n_layers) return fail(RCA_ERR_ARG, "attn_tap: layer %d outside [0, %d)", layer, c.n_layers);
+    if (route < 0 || route > 2) return fail(RCA_ERR_ARG, "attn_tap: route %d outside [0, 2]", route);
+    const int m_max = route == 0 ? LM_GEMV_M : LM_MAXM;
+    if (M < 1 || M > m_max) return fail(RCA_ERR_ARG, "attn_tap: M = %d, route %d takes 1 .. %d query tokens", M, route, m_max);
+    if (route == 2 && lm_prefill_route(h) != LM_ROUTE_TILE128)
+        return fail(RCA_ERR_ARG, "attn_tap: route 2 is the attention of the gemm128 prefill route, which this handle does not take");
+    if (h->n_tokens + M > c.n_ctx) return fail(RCA_ERR_STATE, "attn_tap: positions %d .. %d are outside the context of %d", h->n_tokens, h->n_tokens + M - 1, c.n_ctx);
+    if (out_rows < M || out_rows > LM_MAXM) return fail(RCA_ERR_ARG, "attn_tap: out_rows %d outside [M = %d, %d]", out_rows, M, LM_MAXM);
+    const int need = lm_splits_needed(h, M);
+    if (nsp_launch == 0) nsp_launch = need;
+    if (nsp_launch < need || nsp_launch > h->n_splits)
+        return fail(RCA_ERR_ARG, "attn_tap: nsp_launch %d outside [%d needed, %d splits]", nsp_launch, need, h->n_splits);
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    RCA_HIP(hipStreamSynchronize(st));
+    const std::vector<int32_t> ids((size_t)M, 0);
+    int rc;
+    if ((rc = lm_push_state(h, ids.data(), M, st)) != RCA_OK) return rc;
+    RCA_HIP(hipMemcpy2DAsync(h->qkv, (size_t)QKV * 4, q_host, (size_t)AO * 4, (size_t)AO * 4, M, hipMemcpyHostToDevice, st));
+    // NaN sentinel (all bits set, as f32 and as bf16) in the rows a caller may look at: rows >= M must come back untouched
+    const size_t n_out = (size_t)out_rows * AO;
+    if (route == 2) {
+        RCA_HIP(hipMemsetAsync(h->xh, 0xFF, n_out * 2, st));
+        RCA_HIP(hipMemsetAsync(h->xl, 0xFF, n_out * 2, st));
+    } else {
+        RCA_HIP(hipMemsetAsync(h->attn, 0xFF, n_out * 4, st));
+    }
+    const f16_t* kc = h->kc + (long)layer * h->kv_layer_stride;
+    const f16_t* vc = h->vc + (long)layer * h->kv_layer_stride;
+    if (route == 0) launch_attention_mfma(h, M, nsp_launch, kc, vc, st);
+    else if (route == 1) launch_attention_mfma(h, M, nsp_launch, kc, vc, st, nullptr, nullptr, true);
+    else launch_attention_mfma(h, M, nsp_launch, kc, vc, st, h->xh, h->xl, true);
+    hipError_t e = hipGetLastError();
+    std::vector<uint16_t> hb;
+    if (route == 2) {
+        hb.resize(2 * n_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), h->xh, n_out * 2, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(hb.data() + n_out, h->xl, n_out * 2, hipMemcpyDeviceToHost, st);
+        // later passes read the split buffers in blocks of 128 rows: leave no NaN behind in them
+        if (e == hipSuccess) e = hipMemsetAsync(h->xh, 0, n_out * 2, st);
+        if (e == hipSuccess) e = hipMemsetAsync(h->xl, 0, n_out * 2, st);
+    } else {
+        if (e == hipSuccess) e = hipMemcpyAsync(out_host, h->attn, n_out * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemsetAsync(h->attn, 0, n_out * 4, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "attn_tap: %s", hipGetErrorString(e));
+    if (route == 2) {
+        auto widen = [](uint16_t b) { const uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; };
+        for (size_t i = 0; i < n_out; ++i) out_host[i] = widen(hb[i]) + widen(hb[n_out + i]);
+    }
     return RCA_OK;
 }
 

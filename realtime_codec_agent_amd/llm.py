@@ -653,6 +653,34 @@ class LlamaForAlternatingCodeChannels:
                                          v.ctypes.data_as(C.POINTER(C.c_uint16))), "rca_lm_kv_read")
         return k, v
 
+    def kv_write(self, layer: int, pos0: int, k: Optional[np.ndarray] = None, v: Optional[np.ndarray] = None) -> None:
+        """Tests only (rca_lm_kv_write): replace the raw K and / or V cache rows [n_pos, n_kv_heads, 64] (float16) of one layer from
+        position pos0 on.  n_tokens is left as it was."""
+        for a in (k, v):
+            if a is not None and (a.dtype != np.float16 or a.ndim != 3 or a.shape[1:] != (self.config.n_kv_heads, 64)):
+                raise ValueError(f"kv_write: rows are float16 [n_pos, {self.config.n_kv_heads}, 64], got {a.dtype} {a.shape}")
+        if k is not None and v is not None and k.shape != v.shape:
+            raise ValueError(f"kv_write: K rows {k.shape} and V rows {v.shape} differ")
+        rows = [np.ascontiguousarray(a).view(np.uint16) if a is not None else None for a in (k, v)]
+        n_pos = next((a.shape[0] for a in (k, v) if a is not None), 0)
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint16)) if a is not None else None
+        N.check(self._lib.rca_lm_kv_write(self._h, int(layer), int(pos0), int(n_pos), ptr(rows[0]), ptr(rows[1])), "rca_lm_kv_write")
+
+    def attn_tap(self, layer: int, route: int, q: np.ndarray, nsp_launch: int = 0, out_rows: Optional[int] = None) -> np.ndarray:
+        """Tests only (rca_lm_attn_tap): the attention of one layer alone for the post-RoPE query rows q [M, n_heads * 64] at positions
+        n_tokens .. n_tokens + M - 1, over whatever the cache holds.  route 0: the decode launch, 1: the prefill launch with f32 output,
+        2: the prefill launch with bf16 hi / lo output (returned as hi + lo).  nsp_launch 0: the splits the positions need.  Returns
+        [out_rows, n_heads * 64] float32; rows >= M hold the NaN the device rows were filled with before the launch."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.config.n_heads * 64:
+            raise ValueError(f"attn_tap: q rows have {self.config.n_heads * 64} values, got {q.shape}")
+        M = q.shape[0]
+        out_rows = M if out_rows is None else int(out_rows)
+        out = np.empty((max(out_rows, 0), q.shape[1]), np.float32)
+        N.check(self._lib.rca_lm_attn_tap(self._h, int(layer), int(route), int(nsp_launch), q.ctypes.data_as(C.POINTER(C.c_float)), M,
+                                          out.ctypes.data_as(C.POINTER(C.c_float)), out_rows), "rca_lm_attn_tap")
+        return out
+
     def mask_head_rows(self, row_begin: int, row_end: int) -> None:
         """Zero lm_head rows (random-init models: keep sampling on codec tokens like a trained model in audio mode)."""
         N.check(self._lib.rca_lm_mask_head_rows(self._h, int(row_begin), int(row_end)), "rca_lm_mask_head_rows")

@@ -63,3 +63,24 @@ def long_1b_oracle_points(weight_format=None):
     for s in steps:
         pts.append(ref.eval(s, last_only=True)[-1].numpy())
     return pts
+
+
+# ---------------------------------------------------------------- narrow models (1 and 2 kv heads) followed to 16.5 k tokens
+# The wide model has 8 kv heads: 32 launched splits are the last grid its decode steps merge inside the attention launch.  With
+# 1 or 2 kv heads the 64-split bucket (8 300 tokens) and the 80 splits of n_ctx = 20480 (16 500 tokens) are merged in the launch
+# too -- the second block of pre-fetched splits and the second 64-split chunk of the merge, through the real bucket rule.
+# NARROW_STD makes the oracle's logits span what the wide model's do (max|logit| ~4.5: 0.125 * sqrt(128) * ~3 sigma over 512 ids),
+# so the file's absolute tolerances apply unscaled; the test asserts the range on the oracle.
+NARROW_SEED, NARROW_STD = 9, 0.125
+NARROW_N_CTX = WIDE_N_CTX
+NARROW_CHECKPOINTS = (8300, 16500)
+NARROW_TOKENS = NARROW_CHECKPOINTS[-1] + 4
+
+
+def narrow_config(n_kv_heads):
+    from realtime_codec_agent_amd.llm import LMConfig
+    return LMConfig(vocab_size=512, hidden=128, n_layers=2, n_heads=4, n_kv_heads=n_kv_heads, head_dim=64, ffn=256)
+
+
+def narrow_ids():
+    return np.random.default_rng(78).integers(0, 512, NARROW_TOKENS).astype(np.int64)

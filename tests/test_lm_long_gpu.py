@@ -115,6 +115,77 @@ def test_wide_model_matches_oracle_from_1k_to_16k_tokens():
         llm.close()
 
 
+@pytest.mark.parametrize("n_kv_heads", [1, 2])
+def test_narrow_model_matches_oracle_at_8k_and_16k_tokens(n_kv_heads):
+    """The narrow twin of the wide test: hidden 128, 4 q heads over 1 and over 2 kv heads, 2 layers, V = 512, n_ctx = 20480, followed
+    against the oracle to 8 300 and 16 500 tokens.  With so few kv heads the real bucket rule keeps the merge of the attention splits
+    INSIDE the attention launch at 64 launched splits (8 300) and at 80 of 80 (16 500) -- grids that take the separate combine launch
+    in the wide test -- so the later blocks of pre-fetched splits and the second 64-split chunk of the in-launch merge meet the oracle
+    here.  At each checkpoint: the prefill's last-token logits (exact and bf16-MFMA prefill handles), an eager 2-token eval, and the
+    graph-replayed 2-token step with the merge inside and outside the launch, bit-identical to each other.  Tolerances are the
+    file's TOL, unscaled: the case's init_std makes the oracle's logits span the wide model's range, asserted below.  Teeth: the
+    oracle with one 256-key split, or the partial last split, masked out moves by more than 10 tolerances."""
+    from realtime_codec_agent_amd.llm import LlamaForAlternatingCodeChannels
+    cfg = lc.narrow_config(n_kv_heads)
+    ids = lc.narrow_ids().tolist()
+    llms = {}
+    for mfma in (False, True):
+        llm = LlamaForAlternatingCodeChannels(model_path="random:narrow", config=cfg, n_ctx=lc.NARROW_N_CTX, random_seed=lc.NARROW_SEED,
+                                              init_std=lc.NARROW_STD, device=0)
+        llm.set_mfma_prefill(mfma)
+        llms[mfma] = llm
+    ref = lm_ref.LMRef(cfg, lm_ref.random_weights(cfg, lc.NARROW_SEED, lc.NARROW_STD), kv_dtype=torch.float16)
+    params = dict(top_k=50, top_p=1.0, min_p=0.0, temp=1.0)
+    pos = 0
+    for c in lc.NARROW_CHECKPOINTS:
+        rows = []
+
+        def check(tag, want, got=None):
+            assert 4.5 / 2 < np.abs(want).max() < 4.5 * 2, (c, tag, np.abs(want).max())     # the wide model's logit range: TOL applies as it is
+            for mfma, llm in llms.items():
+                d = _maxdiff(llm._scores[-1] if got is None else got[mfma], want)
+                rows.append(f"{tag} {'mfma ' if mfma else 'exact'} {d:.2e}")
+                assert d < TOL[mfma], (n_kv_heads, c, tag, mfma, d)
+
+        want = ref.eval(ids[pos:c], last_only=True, chunk=1024)[-1].numpy()
+        for llm in llms.values():
+            llm.eval(ids[pos:c])
+            assert llm.n_tokens == c
+        check("prefill", want)
+        want = ref.eval(ids[c:c + 2])[-1].numpy()
+        for a, b in ((4096, 4352), (c // 256 * 256, c)):
+            ref.set_n_tokens(c)
+            lost = ref.eval(ids[c:c + 2], drop_keys=(a, b))[-1].numpy()
+            assert _maxdiff(lost, want) > 10 * TOL[True], (a, b)
+        ref.set_n_tokens(c)
+        ref.eval(ids[c:c + 2])
+        for llm in llms.values():
+            llm.set_graphs(False)
+            llm.eval(ids[c:c + 2])
+        check("eager", want)
+        for llm in llms.values():
+            llm.set_graphs(True)
+        got = {}
+        for mfma, llm in llms.items():
+            outs = []
+            for fuse in (True, False):
+                llm.set_attn_fuse(fuse)
+                llm.n_tokens = c
+                llm.init_sampler_for_generate(seed=c, **params)
+                tok = llm.step(ids[c:c + 2])
+                assert llm.n_tokens == c + 2
+                assert tok == lm_ref.sample(llm._scores[-1], params["top_k"], 1.0, 0.0, 1.0, c, 0)
+                outs.append(llm._scores[-1].copy())
+            llm.set_attn_fuse(True)
+            assert np.array_equal(outs[0], outs[1]), (n_kv_heads, c, mfma, "the step's logits depend on where the splits are merged")
+            got[mfma] = outs[0]
+        check("graph step", want, got)
+        pos = c + 2
+        print(f"narrow {4}/{n_kv_heads} heads, context {c:6d}: max|dlogit| " + "; ".join(rows))
+    for llm in llms.values():
+        llm.close()
+
+
 _ORACLE_CACHE = {}
 
 
