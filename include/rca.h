@@ -146,6 +146,37 @@ int rca_codec_encode_chunk_range_dev(rca_codec_t* h, const float* audio_dev, int
 int rca_codec_encode_rows_dev(rca_codec_t* h, const float* audio_dev, const int64_t* src_off_dev, int32_t B, int32_t T, int32_t n_keep,
                               int64_t* codes_dev, const int64_t* dst_off_dev, int64_t span, void* stream);
 
+/* Device ingest for the batch CLI: PCM as the file holds it (int16 or f32, interleaved or planar, at the file's rate) -> the f32
+ * rows at the codec rate that rca_codec_encode_rows_dev reads.  One launch converts, de-interleaves, downmixes and resamples.
+ * Row r takes n_in frames; frame k is the mean of the n_mix elements src[src_off + k * src_stride + c], c < n_mix (int16: v * 2^-15,
+ * exact; f32 as it is; the sum in ascending c in f32, then one IEEE division by n_mix; n_mix == 1 takes the element unchanged).
+ * With t = n * down + (n_taps - 1) / 2 the row's n_out = ceil(n_in * up / down) outputs are
+ *     y[n] = sum over k in [0, n_in) with 0 <= t - k * up < n_taps of taps[t - k * up] * m[k]      (zero beyond both ends)
+ * -- scipy.signal.resample_poly's definition -- stored at dst_dev[dst_off + n].  The sum is an f32 fma chain over k descending from
+ * floor(t / up), ceil(n_taps / up) terms (taps past the table and frames past the row enter as zeros): the bits depend on
+ * (n, up, down, taps, the row's frames) only, never on where the row lies, on the grid or on the other rows of the call.
+ * up == down == 1 is the pure conversion / de-interleave / downmix: exact, the taps are not consulted.
+ * Every row of a call shares (src_fmt, up, down, taps).  rows_host is the host copy of rows_dev: the grid and every check come from
+ * it, nothing is read back.  RCA_ERR_ARG before anything is enqueued for: an even n_taps, up / down / n_mix / src_stride < 1,
+ * n_mix > src_stride (a planar row has one channel), a row reaching outside [0, src_span) elements of src_dev or
+ * [0, dst_span) of dst_dev, and a ratio whose phase table and input tile do not fit the kernel's LDS budget (64 KiB; every ratio
+ * from 8000 / 11025 / 12000 / 22050 / 24000 / 32000 / 44100 / 48000 Hz to 16000 Hz fits) -- rca_codec_ingest_supported asks that
+ * last question alone.  The phase table of a (up, down, taps) is uploaded on its first call (a blocking copy: not inside a stream
+ * capture) and kept on the handle; later calls only enqueue on `stream`. */
+#define RCA_PCM_F32 0
+#define RCA_PCM_S16 1
+typedef struct {
+    int64_t src_off;    /* element offset (in elements of the source format) of channel 0 of the row's first frame */
+    int64_t n_in;       /* frames; 0 writes nothing */
+    int64_t dst_off;    /* element offset of the row's first output sample in dst_dev */
+    int32_t src_stride; /* elements between consecutive frames: the interleaved channel count, 1 for planar rows */
+    int32_t n_mix;      /* channels averaged into the row */
+} rca_ingest_row_t;
+int rca_codec_ingest_rows_dev(rca_codec_t* h, const void* src_dev, int64_t src_span, int32_t src_fmt, const rca_ingest_row_t* rows_dev,
+                              const rca_ingest_row_t* rows_host, int32_t n_rows, int32_t up, int32_t down, const float* taps_host,
+                              int32_t n_taps, float* dst_dev, int64_t dst_span, void* stream);
+int rca_codec_ingest_supported(const rca_codec_t* h, int32_t up, int32_t down, int32_t n_taps);
+
 /* Streaming tail of the encoder.  AudioTokenizer.tokenize_audio re-encodes the whole rolling
  * window for every chunk and keeps only the last int(secs*framerate) codes (audio_tokenizer.py:72-74,98-101).
  * This returns exactly those codes -- bit-identical to the last n_keep columns of rca_codec_encode_dev(pcm, B, T) --

@@ -190,6 +190,11 @@ class Q6KBlocks:
         return Q6KBlocks(np.ascontiguousarray(r), (r.shape[0], self.shape[1]))
 
 
+RCA_PCM_F32, RCA_PCM_S16 = 0, 1
+# rca_ingest_row_t as a numpy record: a row table is one array of these, handed over as its host copy and its device twin
+INGEST_ROW = np.dtype([("src_off", "<i8"), ("n_in", "<i8"), ("dst_off", "<i8"), ("src_stride", "<i4"), ("n_mix", "<i4")])
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64), ("dtype", C.c_int32)]
 
@@ -375,6 +380,7 @@ ABI_SYMBOLS = [
     "rca_last_error", "rca_device_count", "rca_device_sync", "rca_version",
     "rca_codec_create", "rca_codec_destroy", "rca_codec_hop", "rca_codec_num_frames",
     "rca_codec_encode", "rca_codec_encode_dev", "rca_codec_encode_windows_dev", "rca_codec_encode_chunk_range_dev", "rca_codec_encode_rows_dev",
+    "rca_codec_ingest_rows_dev", "rca_codec_ingest_supported",
     "rca_codec_decode", "rca_codec_decode_dev",
     "rca_codec_encode_tail_dev", "rca_codec_decode_tail_dev", "rca_codec_encode_tail", "rca_codec_decode_tail", "rca_codec_set_stream_graphs", "rca_codec_receptive_field", "rca_codec_set_window_trim",
     "rca_codec_encoder_dev", "rca_codec_quantize_dev", "rca_codec_decoder_dev", "rca_codec_codebook_dev",

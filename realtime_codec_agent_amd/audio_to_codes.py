@@ -23,6 +23,11 @@ of thousands of 10-60 s utterances, so a 256-window pass must not stop at a file
 rca_codec_encode_rows_dev in full passes.  Three stages overlap: reader threads (disk -> float32), the main thread
 (pack, H2D from pinned memory, enqueue), a writer thread (D2H'd codes -> .npy).  The output tree is byte-identical to the
 one-file-at-a-time path (tests compare the two).
+
+--device_ingest (opt-in): the reader threads hand over the PCM as the file holds it (int16 or float32, interleaved or planar, at the
+file's rate) and one kernel (rca_codec_ingest_rows_dev) converts, de-interleaves, downmixes and resamples it on the GPU into the rows
+the passes read.  Files at the codec rate give the same bytes as without the flag; resampled files may differ in a few ids near
+ties (the downmix comes before the filter and the f32 sums run in another order than scipy's: DESIGN.md).
 """
 from __future__ import annotations
 
@@ -39,6 +44,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._native import INGEST_ROW, RCA_PCM_F32, RCA_PCM_S16
 from .dist_utils import ControlPlane, env_rank_world, shard_by_duration
 
 AUDIO_EXTS = (".wav", ".npy")
@@ -100,6 +106,69 @@ def read_audio(path: str) -> Tuple[int, np.ndarray]:
     return sr, np.ascontiguousarray(a.reshape(-1, ch).T)
 
 
+def read_audio_raw(path: str) -> Tuple[int, np.ndarray, str]:
+    """read_audio's twin for --device_ingest: -> (sample_rate, samples, layout) with nothing converted on the reader thread.
+    layout "interleaved": samples [N, C] (a PCM16 .wav: the '<i2' view of readframes(), no copy; a float .wav: '<f4');
+    layout "planar": float32 [C, N] (.npy, decoded compressed files)."""
+    if path.lower().endswith(COMPRESSED_EXTS) or path.endswith(".npy"):
+        sr, a = read_audio(path)
+        return sr, np.ascontiguousarray(a), "planar"
+    with wave.open(path, "rb") as w:
+        sr, ch, sw, n = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
+        raw = w.readframes(n)
+    if sw not in (2, 4):
+        raise ValueError(f"{path}: unsupported sample width {sw}")
+    return sr, np.frombuffer(raw, dtype="<i2" if sw == 2 else "<f4").reshape(-1, ch), "interleaved"
+
+
+class RawAudio:
+    """One file as read_audio_raw left it, plus what the device ingest will make of it: `n_rows` rows (one per channel, or one for
+    all channels when `mix`) of `out_len` samples at the codec rate."""
+    __slots__ = ("sr", "data", "layout", "mix", "up", "down", "out_len")
+
+    def __init__(self, sr: int, data: np.ndarray, layout: str, mix: bool, codec_sr: int):
+        from .audio_tokenizer import ingest_out_len, ingest_taps
+        if layout not in ("interleaved", "planar") or data.ndim != 2 or not data.flags.c_contiguous:
+            raise ValueError("RawAudio: a C-contiguous [N, C] (interleaved) or [C, N] (planar) array is needed")
+        if data.dtype not in (np.dtype("<i2"), np.dtype("<f4")):
+            raise ValueError(f"RawAudio: int16 or float32 samples, not {data.dtype}")
+        if layout == "planar" and mix and data.shape[0] > 1:
+            raise ValueError("RawAudio: the channels of a planar array are not adjacent: average them before")
+        self.sr, self.data, self.layout, self.mix = int(sr), data, layout, bool(mix)
+        self.up, self.down, _ = ingest_taps(self.sr, int(codec_sr))
+        self.out_len = ingest_out_len(self.frames, self.up, self.down)
+
+    @property
+    def channels(self) -> int:
+        return self.data.shape[1 if self.layout == "interleaved" else 0]
+
+    @property
+    def frames(self) -> int:
+        return self.data.shape[0 if self.layout == "interleaved" else 1]
+
+    @property
+    def n_rows(self) -> int:
+        return 1 if self.mix else self.channels
+
+    def rows(self, elem0: int, dst_offs: Sequence[int]) -> List[tuple]:
+        """rca_ingest_row_t records (src_off, n_in, dst_off, src_stride, n_mix) of this file's rows, its samples lying at element
+        offset elem0 of the source buffer."""
+        ch, n = self.channels, self.frames
+        if self.layout == "planar":
+            return [(elem0 + c * n, n, int(d), 1, 1) for c, d in enumerate(dst_offs)]
+        if self.mix:
+            return [(elem0, n, int(dst_offs[0]), ch, ch)]
+        return [(elem0 + c, n, int(d), ch, 1) for c, d in enumerate(dst_offs)]
+
+
+def _n_rows(a) -> int:
+    return a.n_rows if isinstance(a, RawAudio) else a.shape[0]
+
+
+def _n_out(a) -> int:
+    return a.out_len if isinstance(a, RawAudio) else a.shape[-1]
+
+
 def probe_duration(path: str) -> float:
     if path.lower().endswith(COMPRESSED_EXTS):
         sr, a = read_audio(path)
@@ -141,9 +210,22 @@ class HipWindowEncoder:
 
     RING = 3      # super-batches in flight: one being packed, one on the GPU, one being written
 
-    def _slot(self, k: int, n_samples: int, n_codes: int, n_windows: int):
+    supports_device_ingest = True
+
+    def ingest_supported(self, up: int, down: int, n_taps: int) -> bool:
+        return self.model.hip.ingest_supported(up, down, n_taps)
+
+    def _grow(self, sl: dict, name: str, n: int, dtype, pinned: bool):
+        cur = sl.get(name)
+        if cur is None or cur.numel() < n:
+            cap = max(int(n * 1.25), 1)
+            sl[name] = self.torch.empty(cap, dtype=dtype).pin_memory() if pinned else self.torch.empty(cap, dtype=dtype, device=self.device)
+        return sl[name]
+
+    def _slot(self, k: int, n_samples: int, n_codes: int, n_windows: int, n_staged: Optional[int] = None):
         """Ring slot k: pinned staging + device buffers, grown on demand and reused (a pinned allocation of a few hundred MB costs
-        tens of milliseconds: once per slot, not once per super-batch)."""
+        tens of milliseconds: once per slot, not once per super-batch).  n_staged: samples of f32 staging (device ingest stages the
+        files' own bytes instead and asks for none)."""
         torch = self.torch
         if not hasattr(self, "_ring"):
             self._ring = [dict() for _ in range(self.RING)]
@@ -154,12 +236,8 @@ class HipWindowEncoder:
             sl["free"].wait()                                   # ... and the writer is done with its host codes
         sl["free"] = threading.Event()
         def grow(name, n, dtype, pinned):
-            cur = sl.get(name)
-            if cur is None or cur.numel() < n:
-                cap = max(int(n * 1.25), 1)
-                sl[name] = torch.empty(cap, dtype=dtype).pin_memory() if pinned else torch.empty(cap, dtype=dtype, device=self.device)
-            return sl[name]
-        return (grow("stage", n_samples, torch.float32, True), grow("dev_audio", n_samples, torch.float32, False),
+            return self._grow(sl, name, n, dtype, pinned)
+        return (grow("stage", n_samples if n_staged is None else n_staged, torch.float32, True), grow("dev_audio", n_samples, torch.float32, False),
                 grow("host_codes", n_codes, torch.int64, True), grow("dev_codes", n_codes, torch.int64, False),
                 grow("tab_host", 2 * n_windows, torch.int64, True), grow("tab_dev", 2 * n_windows, torch.int64, False), sl)
 
@@ -168,12 +246,19 @@ class HipWindowEncoder:
         channel count).  -> (pinned host int64 codes [total], [(a, b)] slice of every (file, channel) row, wait()) -- wait()
         blocks until the codes have landed in the host buffer.  Everything up to the D2H copy is enqueued asynchronously, so the
         caller can prepare the next super-batch while this one runs.  Staging and device buffers come from a ring of RING slots
-        (the returned host buffer stays valid until RING - 1 further calls have been made)."""
+        (the returned host buffer stays valid until RING - 1 further calls have been made).
+        Device ingest: any item may be a RawAudio (the file's own samples, at its own rate).  The window table, the row offsets and
+        the code slices are then the ones the resampled audio would get, the files' bytes are staged and uploaded as they are, and
+        one rca_codec_ingest_rows_dev per (sample format, rate) writes the f32 rows the passes read; the passes are unchanged."""
         torch, hip = self.torch, self.model.hip
         t_in = time.perf_counter()
         W = max(chunk, ctx)
         fpc = hip.frames_per_chunk(chunk)
-        lengths = [a.shape[-1] for a in audios for _ in range(a.shape[0])]      # one entry per (file, channel) row
+        raw = any(isinstance(a, RawAudio) for a in audios)
+        if raw:      # items prepared on the host (a ratio the kernel refuses) enter as f32 planar 1 : 1 rows
+            audios = [a if isinstance(a, RawAudio) else RawAudio(self.cfg.sample_rate, np.ascontiguousarray(a, dtype=np.float32), "planar", False,
+                                                                 self.cfg.sample_rate) for a in audios]
+        lengths = [_n_out(a) for a in audios for _ in range(_n_rows(a))]       # one entry per (file, channel) row
         # one pinned staging buffer, rows back to back (file-major, channel-minor), each start aligned to 4 samples
         row_len = [((n + 3) // 4) * 4 for n in lengths]
         src_base = np.concatenate([[0], np.cumsum(row_len)[:-1]]).astype(np.int64)
@@ -184,17 +269,35 @@ class HipWindowEncoder:
         slices = [(int(b), int(b + n)) for b, n in zip(dst_base, n_codes)]
         T, src, dst = window_table(lengths, chunk, W, fpc, src_base, dst_base)
         self._calls = getattr(self, "_calls", 0) + 1
-        stage, dev_audio, host_codes, dev_codes, tab_host, tab_dev, sl = self._slot(self._calls % self.RING, total, total_codes, len(T))
+        stage, dev_audio, host_codes, dev_codes, tab_host, tab_dev, sl = self._slot(self._calls % self.RING, total, total_codes, len(T),
+                                                                                    0 if raw else None)
         t_slot = time.perf_counter()
-        sv = stage.numpy()
-        r = 0
-        for a in audios:
-            for c in range(a.shape[0]):
-                sv[src_base[r]:src_base[r] + a.shape[-1]] = a[c]
-                r += 1
+        if raw:
+            # the files' bytes back to back (each start aligned to 16 bytes) in a pinned byte buffer, and one table of ingest rows
+            # ordered by (sample format, rate): every group is one launch
+            raw_off = np.concatenate([[0], np.cumsum([(a.data.nbytes + 15) // 16 * 16 for a in audios])]).astype(np.int64)
+            raw_bytes = int(raw_off[-1])
+            raw_stage, raw_dev = self._grow(sl, "raw_stage", raw_bytes, torch.uint8, True), self._grow(sl, "raw_dev", raw_bytes, torch.uint8, False)
+            bv = raw_stage.numpy()
+            groups, r = {}, 0
+            for a, off in zip(audios, raw_off):
+                bv[off:off + a.data.nbytes] = a.data.reshape(-1).view(np.uint8)
+                groups.setdefault((a.data.dtype.itemsize, a.sr), []).extend(a.rows(int(off) // a.data.dtype.itemsize, src_base[r:r + a.n_rows]))
+                r += a.n_rows
+            rows_np = np.array([rec for key in sorted(groups) for rec in groups[key]], dtype=INGEST_ROW)
+            rows_host = self._grow(sl, "rows_host", rows_np.nbytes, torch.uint8, True)
+            rows_dev = self._grow(sl, "rows_dev", rows_np.nbytes, torch.uint8, False)
+            rows_host.numpy()[:rows_np.nbytes] = rows_np.view(np.uint8)
+        else:
+            sv = stage.numpy()
+            r = 0
+            for a in audios:
+                for c in range(a.shape[0]):
+                    sv[src_base[r]:src_base[r] + a.shape[-1]] = a[c]
+                    r += 1
         st_ = getattr(self, "stage_times", None)
         if st_ is None:
-            st_ = self.stage_times = dict(slot_wait_s=0.0, pack_s=0.0, enqueue_s=0.0, gpu_ms=0.0, super_batches=0, passes=0)
+            st_ = self.stage_times = dict(slot_wait_s=0.0, pack_s=0.0, enqueue_s=0.0, gpu_ms=0.0, ingest_gpu_ms=0.0, super_batches=0, passes=0)
         if len(T) == 0:
             sl["free"].set()
             return host_codes.numpy()[:0], slices, (lambda: None)
@@ -204,7 +307,16 @@ class HipWindowEncoder:
         with torch.cuda.device(self.device):
             st = torch.cuda.current_stream(self.device)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            dev_audio[:total].copy_(stage[:total], non_blocking=True)
+            ei = None
+            if raw:
+                raw_dev[:raw_bytes].copy_(raw_stage[:raw_bytes], non_blocking=True)
+                rows_dev[:rows_np.nbytes].copy_(rows_host[:rows_np.nbytes], non_blocking=True)
+                ei = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ei[0].record(st)
+                self._ingest_groups(groups, rows_np, rows_dev.data_ptr(), raw_dev.data_ptr(), raw_bytes, dev_audio.data_ptr(), total, st.cuda_stream)
+                ei[1].record(st)
+            else:
+                dev_audio[:total].copy_(stage[:total], non_blocking=True)
             tab_dev[:2 * len(T)].copy_(tab_host[:2 * len(T)], non_blocking=True)
             e0.record(st)
             src_ptr, dst_ptr = tab_dev.data_ptr(), tab_dev.data_ptr() + 8 * len(T)
@@ -229,21 +341,52 @@ class HipWindowEncoder:
         t_out = time.perf_counter()
         st_["slot_wait_s"] += t_slot - t_in; st_["pack_s"] += t_pack - t_slot; st_["enqueue_s"] += t_out - t_pack; st_["super_batches"] += 1
 
-        def wait(_e0=e0, _e1=e1):
+        def wait(_e0=e0, _e1=e1, _ei=ei):
             ev.synchronize()
             st_["gpu_ms"] += _e0.elapsed_time(_e1)
+            if _ei is not None:
+                st_["ingest_gpu_ms"] += _ei[0].elapsed_time(_ei[1])
         wait.release = sl["free"].set                           # the consumer calls it once it no longer reads `hc`
         return hc, slices, wait
 
-    def encode(self, audio: np.ndarray, chunk: int, ctx: int, batch_windows: int) -> np.ndarray:
+    def _ingest_groups(self, groups: dict, rows_np: np.ndarray, rows_dev_ptr: int, src_ptr: int, src_bytes: int, dst_ptr: int, dst_span: int,
+                       stream: int) -> None:
+        """One rca_codec_ingest_rows_dev per (sample size, rate) group of `rows_np`, which holds the groups in sorted key order."""
+        from .audio_tokenizer import ingest_taps
+        i = 0
+        for itemsize, sr in sorted(groups):
+            n = len(groups[(itemsize, sr)])
+            up, down, taps = ingest_taps(sr, self.cfg.sample_rate)
+            self.model.hip.ingest_rows_dev(src_ptr, src_bytes // itemsize, RCA_PCM_S16 if itemsize == 2 else RCA_PCM_F32,
+                                           rows_dev_ptr + INGEST_ROW.itemsize * i, rows_np[i:i + n], up, down, taps, dst_ptr, dst_span, stream)
+            i += n
+
+    def ingest(self, raw: RawAudio):
+        """-> device float32 [n_rows, out_len]: the rows rca_codec_ingest_rows_dev makes of one file."""
+        torch = self.torch
+        host = torch.empty(max(raw.data.nbytes, 1), dtype=torch.uint8)
+        host.numpy()[:raw.data.nbytes] = raw.data.reshape(-1).view(np.uint8)
+        out = torch.empty((raw.n_rows, raw.out_len), dtype=torch.float32, device=self.device)
+        if out.numel() == 0:
+            return out
+        rows_np = np.array(raw.rows(0, [r * raw.out_len for r in range(raw.n_rows)]), dtype=INGEST_ROW)
+        with torch.cuda.device(self.device):
+            src = host.to(self.device)
+            rows_dev = torch.from_numpy(rows_np.view(np.uint8)).to(self.device)
+            self._ingest_groups({(raw.data.dtype.itemsize, raw.sr): rows_np}, rows_np, rows_dev.data_ptr(), src.data_ptr(), raw.data.nbytes,
+                                out.data_ptr(), out.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+        return out
+
+    def encode(self, audio, chunk: int, ctx: int, batch_windows: int) -> np.ndarray:
+        """audio: float32 [C, N] at the codec rate, or a RawAudio (device ingest: its rows are made on the GPU first)."""
         torch = self.torch
         hip = self.model.hip
-        C, N = audio.shape
+        C, N = _n_rows(audio), _n_out(audio)
         n_chunks = N // chunk
         fpc = hip.frames_per_chunk(chunk)
         if n_chunks == 0:
             return np.zeros((C, 0), np.int64)
-        dev = torch.from_numpy(np.ascontiguousarray(audio)).to(self.device)
+        dev = self.ingest(audio) if isinstance(audio, RawAudio) else torch.from_numpy(np.ascontiguousarray(audio)).to(self.device)
         out = torch.empty((C, n_chunks * fpc), dtype=torch.int64, device=self.device)
         hip.encode_windows_dev(dev.data_ptr(), C, N, chunk, ctx, batch_windows, out.data_ptr(), n_chunks * fpc,
                                torch.cuda.current_stream(self.device).cuda_stream)
@@ -284,15 +427,16 @@ def encode_files(files: Sequence[str], encoder, args, rank: int = 0) -> Tuple[fl
     ctx = int(args.context_secs * sr)
     out_root = _out_root(args, cfg, rank)
     total_secs, total_codes = 0.0, 0
+    ingest = getattr(args, "device_ingest", False)
     for path in files:
-        audio = _prepare(path, sr, args.stereo)
+        audio = _prepare_raw(path, sr, args.stereo, encoder) if ingest else _prepare(path, sr, args.stereo)
         codes = encoder.encode(audio, chunk, ctx, args.batch_size)
         rel = os.path.splitext(os.path.relpath(path, args.audio_path))[0]
         for c in range(codes.shape[0]):
             dst = os.path.join(out_root, f"{rel}_c{c}.npy")
             os.makedirs(os.path.dirname(dst), exist_ok=True)
             np.save(dst, codes[c][None, :])  # (num_codebooks, T)
-        total_secs += audio.shape[-1] / sr
+        total_secs += _n_out(audio) / sr
         total_codes += int(codes.size)
     return total_secs, total_codes
 
@@ -307,9 +451,33 @@ def _prepare(path: str, sr: int, stereo: bool) -> np.ndarray:
     return np.ascontiguousarray(audio, dtype=np.float32)
 
 
-def _super_batches(files: Sequence[str], sr: int, stereo: bool, budget_samples: int, readers: int) -> Iterator[List[Tuple[str, np.ndarray]]]:
+_refused_rates: set = set()
+_refused_lock = threading.Lock()
+
+
+def _prepare_raw(path: str, sr: int, stereo: bool, encoder):
+    """_prepare for --device_ingest: the file's samples untouched, as a RawAudio.  A rate whose filter the kernel refuses (its tap
+    table does not fit) is prepared on the host as without the flag and enters as float32 rows at the codec rate."""
+    from .audio_tokenizer import ingest_taps
+    fsr, data, layout = read_audio_raw(path)
+    up, down, taps = ingest_taps(fsr, sr)
+    if not encoder.ingest_supported(up, down, taps.size):
+        with _refused_lock:
+            new = fsr not in _refused_rates
+            _refused_rates.add(fsr)
+        if new:
+            print(f"audio_to_codes: device ingest does not take {fsr} Hz -> {sr} Hz ({up}/{down}, {taps.size} taps): such files are "
+                  "resampled on the host", file=sys.stderr)
+        return _prepare(path, sr, stereo)
+    if layout == "planar" and not stereo and data.shape[0] > 1:
+        data = data.mean(axis=0, keepdims=True)       # planes are not adjacent in memory: this one downmix stays on the host
+    return RawAudio(fsr, data, layout, not stereo, sr)
+
+
+def _super_batches(files: Sequence[str], sr: int, stereo: bool, budget_samples: int, readers: int, encoder=None) -> Iterator[List[Tuple[str, np.ndarray]]]:
     """Reader stage: files are decoded by a small thread pool (disk and int16 -> float32 conversion release the GIL) a bounded
-    distance ahead of the consumer and handed over in groups of about budget_samples samples (all channels counted)."""
+    distance ahead of the consumer and handed over in groups of about budget_samples samples (all channels counted).  With an
+    `encoder` (device ingest) the readers only read: the items are RawAudio and count by the samples their rows will hold."""
     with ThreadPoolExecutor(max_workers=readers) as pool:
         pending: "queue.Queue" = queue.Queue()
         it = iter(files)
@@ -321,7 +489,7 @@ def _super_batches(files: Sequence[str], sr: int, stereo: bool, budget_samples: 
                 p = next(it, None)
                 if p is None:
                     return
-                pending.put((p, pool.submit(_prepare, p, sr, stereo)))
+                pending.put((p, pool.submit(_prepare_raw, p, sr, stereo, encoder) if encoder is not None else pool.submit(_prepare, p, sr, stereo)))
                 inflight += 1
         submit_more()
         group, size, n_groups = [], 0, 0
@@ -333,11 +501,12 @@ def _super_batches(files: Sequence[str], sr: int, stereo: bool, budget_samples: 
             # ramp-up: the first super-batches are small (1/8, 1/2 of the budget), so the GPU has work a few milliseconds after the
             # start instead of after a whole budget has been read and packed; from the third on nothing is exposed any more
             budget = budget_samples >> 3 if n_groups == 0 else budget_samples >> 1 if n_groups == 1 else budget_samples
-            if group and size + audio.size > budget:
+            n_samples = audio.out_len * audio.n_rows if isinstance(audio, RawAudio) else audio.size
+            if group and size + n_samples > budget:
                 yield group
                 group, size, n_groups = [], 0, n_groups + 1
             group.append((p, audio))
-            size += audio.size
+            size += n_samples
         if group:
             yield group
 
@@ -386,7 +555,8 @@ def encode_files_pipelined(files: Sequence[str], encoder, args, rank: int = 0) -
     wt.start()
     t_start = time.perf_counter()
     try:
-        gen = _super_batches(files, sr, args.stereo, getattr(args, "super_batch_samples", DEFAULT_SUPER_BATCH), getattr(args, "reader_threads", 4))
+        gen = _super_batches(files, sr, args.stereo, getattr(args, "super_batch_samples", DEFAULT_SUPER_BATCH), getattr(args, "reader_threads", 4),
+                             encoder if getattr(args, "device_ingest", False) else None)
         while True:
             t0 = time.perf_counter()
             group = next(gen, None)
@@ -400,12 +570,12 @@ def encode_files_pipelined(files: Sequence[str], encoder, args, rank: int = 0) -
             host_codes, slices, wait = encoder.encode_many(audios, chunk, ctx, args.batch_size)
             t2 = time.perf_counter()
             times["encode_many_s"] += t2 - t1
-            names = [(os.path.splitext(os.path.relpath(p, args.audio_path))[0], c) for p, a in group for c in range(a.shape[0])]
+            names = [(os.path.splitext(os.path.relpath(p, args.audio_path))[0], c) for p, a in group for c in range(_n_rows(a))]
             if len(names) != len(slices):
                 raise RuntimeError(f"encode_many returned {len(slices)} code rows for {len(names)} (file, channel) rows")
             done.put((names, wait, host_codes, slices))
             times["queue_wait_s"] += time.perf_counter() - t2
-            totals[0] += sum(a.shape[-1] for a in audios) / sr
+            totals[0] += sum(_n_out(a) for a in audios) / sr
             totals[1] += int(sum(b - a for a, b in slices))
     finally:
         done.put(None)
@@ -447,6 +617,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--receptive_field_trim", action="store_true",
                     help="encode only what each chunk's kept frames can see instead of the whole context window: identical "
                          "codes for this build's conv codec, ~8x faster (rca_codec_set_window_trim)")
+    ap.add_argument("--device_ingest", action="store_true",
+                    help="upload the PCM as the files hold it (int16 / float32, at their own rate) and convert, downmix and resample it "
+                         "on the GPU (rca_codec_ingest_rows_dev); same codes for files at the codec rate, resampled files may differ "
+                         "in a few ids near ties")
     return ap
 
 
@@ -461,6 +635,9 @@ def main(argv=None, encoder=None, backend: Optional[str] = None) -> dict:
         encoder = HipWindowEncoder(args.codec_model, local)
         encoder.model.hip.set_window_trim(args.receptive_field_trim)
         backend = backend or os.environ.get("RCA_DIST_BACKEND", "nccl")
+    if args.device_ingest and not getattr(encoder, "supports_device_ingest", False):
+        raise ValueError(f"--device_ingest: {type(encoder).__name__} has no device ingest (an encoder with supports_device_ingest, "
+                         "ingest_supported() and RawAudio items in encode / encode_many is needed)")
     cp = ControlPlane(prefer=backend or "gloo", device_index=local)     # falls back to gloo by itself when RCCL cannot come up
     files = list_audio_files(args.audio_path, args.audio_filter)
     shards = shard_by_duration([probe_duration(f) for f in files], world)

@@ -24,6 +24,7 @@ How the codec is driven:
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Any, List, Optional, Tuple, Union
 
@@ -46,6 +47,28 @@ def _resample(audio: np.ndarray, orig_sr: int, target_sr: int) -> np.ndarray:
     from scipy.signal import resample_poly
     g = math.gcd(int(orig_sr), int(target_sr))
     return resample_poly(audio, int(target_sr) // g, int(orig_sr) // g, axis=-1).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def ingest_taps(orig_sr: int, target_sr: int) -> Tuple[int, int, np.ndarray]:
+    """-> (up, down, taps): the filter _resample applies through resample_poly, restated for the batch CLI's device ingest
+    (rca_codec_ingest_rows_dev): half = 10 * max(up, down), firwin(2 * half + 1, 1 / max(up, down), kaiser 5.0) in float32, times up.
+    Equal rates give (1, 1, [1.0]): a pure conversion.  The array is shared between callers and read-only."""
+    g = math.gcd(int(orig_sr), int(target_sr))
+    up, down = int(target_sr) // g, int(orig_sr) // g
+    if up == down:
+        taps = np.ones(1, np.float32)
+    else:
+        from scipy.signal import firwin
+        m = max(up, down)
+        taps = firwin(20 * m + 1, 1.0 / m, window=("kaiser", 5.0)).astype(np.float32) * np.float32(up)
+    taps.setflags(write=False)
+    return up, down, taps
+
+
+def ingest_out_len(n_in: int, up: int, down: int) -> int:
+    """Samples resample_poly returns for n_in: ceil(n_in * up / down)."""
+    return -(-int(n_in) * int(up) // int(down))
 
 
 class PcmWindow:

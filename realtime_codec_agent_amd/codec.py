@@ -192,6 +192,26 @@ class HipCodec:
         N.check(self._lib.rca_codec_encode_rows_dev(self._h, C.c_void_p(audio_ptr), C.c_void_p(src_off_ptr), B, T, n_keep, C.c_void_p(codes_ptr),
                                                     C.c_void_p(dst_off_ptr), C.c_int64(span), C.c_void_p(stream)), "rca_codec_encode_rows_dev")
 
+    def ingest_supported(self, up: int, down: int, n_taps: int) -> bool:
+        """Whether rca_codec_ingest_rows_dev takes this ratio (its phase table and input tile fit the kernel's LDS budget)."""
+        return self._lib.rca_codec_ingest_supported(self._h, int(up), int(down), int(n_taps)) == 0
+
+    def ingest_rows_dev(self, src_ptr: int, src_span: int, src_fmt: int, rows_dev_ptr: int, rows_host: np.ndarray, up: int, down: int,
+                        taps: Optional[np.ndarray], dst_ptr: int, dst_span: int, stream: int = 0) -> None:
+        """PCM as the file holds it -> f32 rows at the codec rate (rca_codec_ingest_rows_dev).  rows_host: a contiguous array of
+        _native.INGEST_ROW records, the host copy of the table at rows_dev_ptr; taps: float32, odd length (None for 1 : 1)."""
+        if rows_host.dtype != N.INGEST_ROW or not rows_host.flags.c_contiguous:
+            raise ValueError("rows_host must be a contiguous array of _native.INGEST_ROW records")
+        if taps is None:
+            taps_ptr, n_taps = None, 1
+        else:
+            taps = np.ascontiguousarray(taps, dtype=np.float32)
+            taps_ptr, n_taps = taps.ctypes.data, taps.size
+        N.check(self._lib.rca_codec_ingest_rows_dev(self._h, C.c_void_p(src_ptr), C.c_int64(src_span), int(src_fmt), C.c_void_p(rows_dev_ptr),
+                                                    C.c_void_p(rows_host.ctypes.data), int(rows_host.size), int(up), int(down),
+                                                    C.c_void_p(taps_ptr), int(n_taps), C.c_void_p(dst_ptr), C.c_int64(dst_span),
+                                                    C.c_void_p(stream)), "rca_codec_ingest_rows_dev")
+
     def encoder_dev(self, pcm_ptr: int, B: int, T: int, ze_ptr: int, stream: int = 0) -> None:
         N.check(self._lib.rca_codec_encoder_dev(self._h, C.c_void_p(pcm_ptr), B, T, C.c_void_p(ze_ptr), C.c_void_p(stream)), "rca_codec_encoder_dev")
 

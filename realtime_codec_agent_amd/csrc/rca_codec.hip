@@ -2296,6 +2296,8 @@ struct rca_codec {
     struct StreamGraph { hipGraphExec_t exec = nullptr; int seen = 0; unsigned long long sig = 0; };
     std::map<std::array<int, 5>, StreamGraph> sgraphs;
     bool stream_graphs = true;
+    // device ingest (rca_codec_ingest_rows_dev): phase tables by (up, down, n_taps, hash of the taps), uploaded on first use
+    std::map<std::array<long, 4>, float*> ingest_tabs;
     int* err_flag = nullptr;
     hipStream_t last_stream = nullptr;
     bool last_stream_valid = false;
@@ -2457,6 +2459,8 @@ extern "C" int rca_codec_destroy(rca_codec_t* h) {
     for (auto& kv : h->sgraphs)
         if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     if (h->pin) (void)hipHostFree(h->pin);
+    for (auto& kv : h->ingest_tabs)
+        if (kv.second) (void)hipFree(kv.second);
     h->act[0].release(); h->act[1].release(); h->zbuf.release(); h->keys.release(); h->io_a.release(); h->io_b.release(); h->tail.release();
     for (auto* v : {&h->prof, &h->prof_pool})
         for (auto& p : *v) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -3409,6 +3413,151 @@ extern "C" int rca_codec_encode_rows_dev(rca_codec_t* h, const float* audio, con
     if ((rc = run_encoder(h, src, B, st, &ze, &F, -1, nullptr, -1, nullptr, n_keep, &Fz)) != RCA_OK) return rc;
     RowDst dst{codes, B, 0, 0, n_keep, reinterpret_cast<const long*>(dst_off)};
     return run_quantize(h, ze, 0, B, Fz, Fz - n_keep, n_keep, dst, st, nullptr);
+}
+
+// ------------------------------------------------------------------------------------ device ingest
+// PCM as the file holds it -> f32 rows at the codec rate (include/rca.h has the definition).  Polyphase form: with t = n * down + half,
+// kh = t / up and p = t % up, output n is  sum_j taps[p + j * up] * m[kh - j],  j < jmax = ceil(n_taps / up).  The taps sit in LDS by
+// phase, ph[p * pitch + j] = taps[p + j * up] (zero past the table), so an output reads one contiguous run of jmax taps and one
+// contiguous run of jmax staged frames.  pitch = jmax | 1: lanes of a wave step their phase by down % up, and with an odd pitch
+// phases that differ mod 64 start in different banks (up a multiple of 64 -- 640, 320 -- with an odd step: all 64 lanes apart; the
+// small tables of 2 / 1, 1 / 2, 1 / 3 ... are read at a handful of addresses, which broadcast).
+// A block of 256 threads takes RCA_INGEST_SPAN consecutive outputs of one row, tile by tile: per tile the frames its outputs see are
+// converted and downmixed once into LDS (zeros beyond the row's ends), then one thread per output runs the fma chain.  Which block or
+// tile an output falls into changes nothing it adds up: the chain is j = 0 .. jmax - 1 for every output.
+#define RCA_INGEST_TILE 256
+#define RCA_INGEST_SPAN (8 * RCA_INGEST_TILE)
+#define RCA_INGEST_LDS_BUDGET (64 * 1024)
+
+__device__ __forceinline__ float ingest_cvt(float v) { return v; }
+__device__ __forceinline__ float ingest_cvt(int16_t v) { return (float)v * 0x1p-15f; }
+
+template <typename S>
+__device__ __forceinline__ float ingest_frame(const S* __restrict__ src, long off, int n_mix) {
+    float a = ingest_cvt(src[off]);
+    if (n_mix > 1) {
+        for (int c = 1; c < n_mix; ++c) a += ingest_cvt(src[off + c]);
+        a = a / (float)n_mix;
+    }
+    return a;
+}
+
+template <typename S>
+__global__ __launch_bounds__(RCA_INGEST_TILE) void ingest_rows_kernel(const S* __restrict__ src, const rca_ingest_row_t* __restrict__ rows,
+                                                                      int up, int down, int half, int jmax, int pitch,
+                                                                      const float* __restrict__ ph_tab, float* __restrict__ dst) {
+    extern __shared__ float ingest_lds[];
+    float* ph = ingest_lds;
+    float* xs = ingest_lds + (long)up * pitch;
+    const rca_ingest_row_t r = rows[blockIdx.y];
+    const long n_out = (r.n_in * up + down - 1) / down;
+    long n0 = (long)blockIdx.x * RCA_INGEST_SPAN;
+    if (n0 >= n_out) return;
+    const long n_end = n0 + RCA_INGEST_SPAN < n_out ? n0 + RCA_INGEST_SPAN : n_out;
+    const int tid = threadIdx.x;
+    if (up == 1 && down == 1) {                                      // conversion / de-interleave / downmix only
+        for (long n = n0 + tid; n < n_end; n += RCA_INGEST_TILE) dst[r.dst_off + n] = ingest_frame(src, r.src_off + n * r.src_stride, r.n_mix);
+        return;
+    }
+    for (int i = tid; i < up * pitch; i += RCA_INGEST_TILE) ph[i] = ph_tab[i];
+    for (; n0 < n_end; n0 += RCA_INGEST_TILE) {
+        const int cnt = (int)(n_end - n0 < RCA_INGEST_TILE ? n_end - n0 : RCA_INGEST_TILE);
+        const long k_first = (n0 * down + half) / up - (jmax - 1);
+        const long k_last = ((n0 + cnt - 1) * down + half) / up;
+        const int span = (int)(k_last - k_first + 1);               // <= (TILE - 1) * down / up + jmax + 1: the host sized xs for it
+        __syncthreads();                                             // the previous tile's reads of xs are done (first tile: nothing yet)
+        for (int i = tid; i < span; i += RCA_INGEST_TILE) {
+            const long k = k_first + i;
+            xs[i] = (k >= 0 && k < r.n_in) ? ingest_frame(src, r.src_off + k * r.src_stride, r.n_mix) : 0.0f;
+        }
+        __syncthreads();
+        if (tid < cnt) {
+            const long t = (n0 + tid) * down + half;
+            const long kh = t / up;
+            const float* pr = ph + (t - kh * up) * pitch;
+            const float* xr = xs + (kh - k_first);
+            float acc = 0.0f;
+            for (int j = 0; j < jmax; ++j) acc = __builtin_fmaf(pr[j], xr[-j], acc);
+            dst[r.dst_off + n0 + tid] = acc;
+        }
+    }
+}
+
+// LDS floats of a ratio: the phase table and the widest input tile; 0 when the arguments are unusable
+static long ingest_lds_floats(int up, int down, int n_taps, int* jmax_out, int* pitch_out) {
+    if (up < 1 || down < 1 || n_taps < 1 || (n_taps & 1) == 0) return 0;
+    const int jmax = (n_taps + up - 1) / up, pitch = jmax | 1;
+    if (jmax_out) *jmax_out = jmax;
+    if (pitch_out) *pitch_out = pitch;
+    if (up == 1 && down == 1) return 1;
+    return (long)up * pitch + ((long)(RCA_INGEST_TILE - 1) * down) / up + jmax + 2;
+}
+
+extern "C" int rca_codec_ingest_supported(const rca_codec_t* h, int32_t up, int32_t down, int32_t n_taps) {
+    if (!h) return fail(RCA_ERR_ARG, "ingest: null handle");
+    const long fl = ingest_lds_floats(up, down, n_taps, nullptr, nullptr);
+    if (fl == 0) return fail(RCA_ERR_ARG, "ingest: up=%d down=%d n_taps=%d (both ratios >= 1 and an odd tap count are needed)", up, down, n_taps);
+    if (fl * 4 > RCA_INGEST_LDS_BUDGET)
+        return fail(RCA_ERR_ARG, "ingest: %d/%d with %d taps needs %ld bytes of LDS, the kernel's budget is %d", up, down, n_taps, fl * 4, RCA_INGEST_LDS_BUDGET);
+    return RCA_OK;
+}
+
+extern "C" int rca_codec_ingest_rows_dev(rca_codec_t* h, const void* src, int64_t src_span, int32_t src_fmt, const rca_ingest_row_t* rows_dev,
+                                         const rca_ingest_row_t* rows_host, int32_t n_rows, int32_t up, int32_t down, const float* taps,
+                                         int32_t n_taps, float* dst, int64_t dst_span, void* stream) {
+    if (!h || !src || !rows_dev || !rows_host || !dst || n_rows < 0 || (src_fmt != RCA_PCM_F32 && src_fmt != RCA_PCM_S16))
+        return fail(RCA_ERR_ARG, "ingest_rows: bad argument");
+    int rc, jmax = 1, pitch = 1;
+    if ((rc = rca_codec_ingest_supported(h, up, down, n_taps)) != RCA_OK) return rc;
+    const long lds_floats = ingest_lds_floats(up, down, n_taps, &jmax, &pitch);
+    const bool pass = up == 1 && down == 1;
+    if (!pass && !taps) return fail(RCA_ERR_ARG, "ingest_rows: no taps");
+    long max_out = 0;
+    for (int r = 0; r < n_rows; ++r) {
+        const rca_ingest_row_t& w = rows_host[r];
+        if (w.n_in < 0 || w.src_stride < 1 || w.n_mix < 1 || w.n_mix > w.src_stride || w.n_in > (INT64_MAX >> 1) / up)
+            return fail(RCA_ERR_ARG, "ingest_rows: row %d: n_in=%ld src_stride=%d n_mix=%d", r, (long)w.n_in, w.src_stride, w.n_mix);
+        if (w.n_in == 0) continue;
+        const long n_out = (w.n_in * up + down - 1) / down;
+        if (w.src_off < 0 || w.src_off + (w.n_in - 1) * w.src_stride + w.n_mix > src_span)
+            return fail(RCA_ERR_ARG, "ingest_rows: row %d reads outside the source (offset %ld, %ld frames of stride %d, span %ld)", r,
+                        (long)w.src_off, (long)w.n_in, w.src_stride, (long)src_span);
+        if (w.dst_off < 0 || w.dst_off + n_out > dst_span)
+            return fail(RCA_ERR_ARG, "ingest_rows: row %d writes [%ld, %ld) outside the destination of %ld", r, (long)w.dst_off,
+                        (long)(w.dst_off + n_out), (long)dst_span);
+        max_out = std::max(max_out, n_out);
+    }
+    RCA_HIP(hipSetDevice(h->device));
+    float* tab = nullptr;
+    if (!pass) {
+        unsigned long hash = 1469598103934665603ul;                 // FNV-1a over the taps' bits: another filter of the same size is another table
+        for (int i = 0; i < n_taps; ++i) { unsigned int b; memcpy(&b, taps + i, 4); hash = (hash ^ b) * 1099511628211ul; }
+        const std::array<long, 4> key{up, down, n_taps, (long)hash};
+        auto it = h->ingest_tabs.find(key);
+        if (it == h->ingest_tabs.end()) {
+            std::vector<float> ph((size_t)up * pitch, 0.0f);
+            for (int i = 0; i < n_taps; ++i) ph[(size_t)(i % up) * pitch + i / up] = taps[i];
+            RCA_HIP(hipMalloc((void**)&tab, ph.size() * sizeof(float)));
+            hipError_t e = hipMemcpy(tab, ph.data(), ph.size() * sizeof(float), hipMemcpyHostToDevice);
+            if (e != hipSuccess) { (void)hipFree(tab); return fail(RCA_ERR_HIP, "ingest_rows: table upload -> %s", hipGetErrorString(e)); }
+            h->ingest_tabs[key] = tab;
+        } else {
+            tab = it->second;
+        }
+    }
+    if (max_out == 0) return RCA_OK;
+    hipStream_t st = pick_stream(h, stream);
+    const size_t lds = pass ? 0 : (size_t)lds_floats * sizeof(float);
+    const int half = (n_taps - 1) / 2;
+    for (int r0 = 0; r0 < n_rows; r0 += 65535) {                    // grid.y holds at most 65535 rows
+        const dim3 grid(cdiv(max_out, RCA_INGEST_SPAN), (unsigned)std::min(65535, n_rows - r0));
+        if (src_fmt == RCA_PCM_S16)
+            ingest_rows_kernel<int16_t><<<grid, RCA_INGEST_TILE, lds, st>>>((const int16_t*)src, rows_dev + r0, up, down, half, jmax, pitch, tab, dst);
+        else
+            ingest_rows_kernel<float><<<grid, RCA_INGEST_TILE, lds, st>>>((const float*)src, rows_dev + r0, up, down, half, jmax, pitch, tab, dst);
+        RCA_LAUNCH_CHECK();
+    }
+    return RCA_OK;
 }
 
 extern "C" int rca_codec_encoder_dev(rca_codec_t* h, const float* pcm, int32_t B, int32_t T, float* ze_out, void* stream) {
