@@ -191,6 +191,49 @@ int rca_codec_encode_tail_dev(rca_codec_t* h, const float* pcm_dev, int32_t B, i
  * audio_tokenizer.py:113,141-145).  codes [B,F] int64 (row stride F) -> pcm [B,n_samples] f32. */
 int rca_codec_decode_tail_dev(rca_codec_t* h, const int64_t* codes_dev, int32_t B, int32_t F, int32_t n_samples,
                               float* pcm_dev, void* stream);
+/* The decode mirror of rca_codec_encode_rows_dev: B rows of F codes taken ANYWHERE in one device buffer -- row b is the F codes at
+ * codes_dev + src_off_dev[b] (elements; rows may overlap, as consecutive windows of one stream do) and the last n_samples of its decode
+ * go to pcm_dev + dst_off_dev[b].  Each row is bit-identical to row b of rca_codec_decode_tail_dev on the same codes, the receptive-field
+ * trim included (the decoder runs over frames j = max(0, f0 - dec_left_frames) onwards, f0 the first frame a kept sample belongs to).
+ * Replaces one AudioTokenizer.detokenize_audio call per 0.1 s chunk and per file (audio_tokenizer.py:106-149 as driven by the loop of
+ * run_stream_codes.py:60-68): a pass holds the windows of many chunks of many streams.  code_span / pcm_span = largest offset + F /
+ * + n_samples.  Destination rows must not overlap: that is the caller's contract, nothing checks it.
+ * RCA_ERR_ARG before anything is enqueued for B < 1, F < 1, n_samples < 1, n_samples > F * hop, a null pointer or a span that holds no
+ * row.  The offset tables live on the device, so a row outside its span is caught by the kernels: it is not read / not written and
+ * raises the handle's decode error flag, as a code outside [0, codebook_size) does (rca_codec_decode_error). */
+int rca_codec_decode_rows_dev(rca_codec_t* h, const int64_t* codes_dev, const int64_t* src_off_dev, int32_t B, int32_t F, int32_t n_samples,
+                              float* pcm_dev, const int64_t* dst_off_dev, int64_t code_span, int64_t pcm_span, void* stream);
+/* The error flag the decode kernels raise on the device (code out of range, row outside its span): synchronises `stream`, returns
+ * the flag in *raised and clears it.  The host-buffer decode calls read it themselves; the _dev calls leave it to the caller. */
+int rca_codec_decode_error(rca_codec_t* h, void* stream, int32_t* raised);
+
+/* smooth_join (utils/audio_utils.py:22-30) for many streams in ONE launch: the loop of run_stream_codes.py:60-68 joins every
+ * decoded chunk to the audio so far, `audio = smooth_join(audio, chunk, L, fade_in, fade_out)`, on the host.  Here seg_dev holds
+ * decoded segments (each the preroll + chunk that detokenize_audio returned), segment s being the n samples at seg_off that land at
+ * out_off in out_dev.  The descriptors of one stream are consecutive; flags bit 0 marks the head of a stream (nothing to blend
+ * into), bit 1 its tail (no successor).  Inside a stream out_off[s + 1] == out_off[s] + n[s] - n_fade: the last n_fade samples of
+ * segment s meet the first n_fade of segment s + 1, and there the output is
+ *     prev * fade_out[k] + cur * fade_in[k],   fade_out[k] = fade_in[n_fade - 1 - k]
+ * evaluated as numpy does: two f32 products, each rounded, then one f32 sum (never a fused multiply-add).  Every other sample is a
+ * copy; every output sample is written by exactly one thread; n_fade == 0 is pure concatenation.  fade_in_dev: n_fade floats on the
+ * device (create_crossfade_ramps, utils/audio_utils.py:14-19).  segs_host is the host copy of segs_dev: every check comes from it,
+ * nothing is read back.  RCA_ERR_ARG before anything is enqueued for: a first segment that is no head, a head inside an open stream,
+ * a last segment that is no tail, a broken out_off chain, a segment with a predecessor or with a successor shorter than n_fade, one
+ * with both shorter than 2 * n_fade, a negative length, and anything reaching outside [0, seg_span) / [0, out_span).  The outputs of
+ * different streams must not overlap (the caller's contract). */
+#define RCA_JOIN_HEAD 1
+#define RCA_JOIN_TAIL 2
+typedef struct {
+    int64_t seg_off;   /* element offset of the segment's first sample in seg_dev */
+    int64_t n;         /* samples, preroll included */
+    int64_t out_off;   /* element offset in out_dev of the segment's first sample */
+    int32_t flags;     /* RCA_JOIN_HEAD | RCA_JOIN_TAIL */
+    int32_t reserved;  /* 0 */
+} rca_join_seg_t;
+int rca_codec_crossfade_join_dev(rca_codec_t* h, const float* seg_dev, int64_t seg_span, const rca_join_seg_t* segs_dev,
+                                 const rca_join_seg_t* segs_host, int32_t n_segs, const float* fade_in_dev, int32_t n_fade, float* out_dev,
+                                 int64_t out_span, void* stream);
+
 /* The same two calls with host buffers, as the streaming tokenizer makes them once per frame: H2D of the window,
  * the tail kernels, D2H of the result, one synchronisation.  Shapes repeat frame after frame, so from the second
  * call of a shape on the whole sequence replays as one hipGraph over pinned staging buffers

@@ -193,6 +193,9 @@ class Q6KBlocks:
 RCA_PCM_F32, RCA_PCM_S16 = 0, 1
 # rca_ingest_row_t as a numpy record: a row table is one array of these, handed over as its host copy and its device twin
 INGEST_ROW = np.dtype([("src_off", "<i8"), ("n_in", "<i8"), ("dst_off", "<i8"), ("src_stride", "<i4"), ("n_mix", "<i4")])
+# rca_join_seg_t likewise (rca_codec_crossfade_join_dev): one decoded segment of one stream
+JOIN_SEG = np.dtype([("seg_off", "<i8"), ("n", "<i8"), ("out_off", "<i8"), ("flags", "<i4"), ("reserved", "<i4")])
+RCA_JOIN_HEAD, RCA_JOIN_TAIL = 1, 2
 
 
 class Tensor(C.Structure):
@@ -381,6 +384,7 @@ ABI_SYMBOLS = [
     "rca_codec_create", "rca_codec_destroy", "rca_codec_hop", "rca_codec_num_frames",
     "rca_codec_encode", "rca_codec_encode_dev", "rca_codec_encode_windows_dev", "rca_codec_encode_chunk_range_dev", "rca_codec_encode_rows_dev",
     "rca_codec_ingest_rows_dev", "rca_codec_ingest_supported",
+    "rca_codec_decode_rows_dev", "rca_codec_decode_error", "rca_codec_crossfade_join_dev",
     "rca_codec_decode", "rca_codec_decode_dev",
     "rca_codec_encode_tail_dev", "rca_codec_decode_tail_dev", "rca_codec_encode_tail", "rca_codec_decode_tail", "rca_codec_set_stream_graphs", "rca_codec_receptive_field", "rca_codec_set_window_trim",
     "rca_codec_encoder_dev", "rca_codec_quantize_dev", "rca_codec_decoder_dev", "rca_codec_codebook_dev",

@@ -201,6 +201,57 @@ class AudioTokenizer:
         preroll_left = max(0, preroll_samples - n_samples + pcm.shape[-1])
         return (self.sampling_rate, pcm[0, 0] if self.num_channels == 1 else pcm[0]), end_hanging, preroll_left
 
+    def chunked_detokenize_audio(self, audio_codes_str: str, chunk_size_secs: float, fade_secs: float = 0.02) -> Tuple[int, np.ndarray]:
+        """The mirror of chunked_tokenize_audio: the string rendered chunk by chunk as the streaming loop renders it
+        (run_stream_codes.py:60-68) --
+
+            for every chunk of int(chunk_size_secs * framerate * num_channels) characters:
+                (_, out), _, _ = self.detokenize_audio(chunk, preroll_samples=L)
+                audio = smooth_join(audio, out, L, fade_in, fade_out)
+
+        -- started from the current detokenize_context and leaving the context the loop leaves.  -> (sampling_rate, [N] or [C, N]).
+        A model that offers run_stream_plan executes the whole loop on the device as one plan (stream_decode.py), bit-identical;
+        that path is taken only when the string, the chunk, the context limit and the present context are whole frames and every
+        kept piece is long enough for its crossfades, otherwise the loop itself runs."""
+        from .utils.audio_utils import create_crossfade_ramps, smooth_join
+        C = self.num_channels
+        L, fade_in, fade_out = create_crossfade_ramps(self.sampling_rate, fade_secs)
+        step = int(chunk_size_secs * self.framerate * C)
+        if step < 1:
+            raise ValueError(f"chunk_size_secs={chunk_size_secs} holds no code at {self.framerate} Hz")
+        audio = self._stream_plan_decode(audio_codes_str, step, L, fade_in)
+        if audio is None:
+            audio = np.zeros((C, 0), dtype=np.float32)
+            for start in range(0, len(audio_codes_str), step):
+                (_, out), _, _ = self.detokenize_audio(audio_codes_str[start:start + step], preroll_samples=L)
+                audio = smooth_join(audio, out.reshape(C, -1), L, fade_in, fade_out)
+        return self.sampling_rate, (audio[0] if C == 1 else audio)
+
+    def _stream_plan_decode(self, chars: str, step: int, L: int, fade_in: np.ndarray) -> Optional[np.ndarray]:
+        """chunked_detokenize_audio's loop as one device plan; None when the loop has to run instead."""
+        from .stream_decode import chunk_samples, plan_batch
+        model, C, text = self.codec_model, self.num_channels, self._codes.text
+        if not (self.streaming_tail and hasattr(model, "run_stream_plan")) or not chars:
+            return None
+        if len(chars) % C or step % C or self.context_frames % C or len(text) % C or chunk_samples(step, self.framerate, C, self.sampling_rate, 0) < L:
+            return None
+        have, n_new, k, ctx = len(text) // C, len(chars) // C, step // C, self.context_frames // C
+        try:
+            plan = plan_batch([n_new] * C, [have] * C, k, ctx, L, model.hop, self.framerate, self.sampling_rate, channels=C,
+                              dec_left=model.cfg.receptive_field()[1])
+        except ValueError:                       # a piece shorter than its crossfades: numpy's chained join is the definition there
+            return None
+        whole = text + chars
+        ids = np.stack([chars_to_codes(whole[c::C], self.num_codebooks, self.codebook_size, unicode_offset=self.unicode_offset)[0] for c in range(C)])
+        with torch.cuda.device(model.device):
+            dev = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)).to(model.device)
+            out = model.run_stream_plan(dev, plan, fade_in)
+            model.hip.check_decode_error(int(torch.cuda.current_stream(model.device).cuda_stream))
+            audio = out.cpu().numpy().reshape(C, -1)
+        last = n_new - (-(-n_new // k) - 1) * k              # codes of the last chunk; its window is what CodeWindow.push leaves
+        self._codes.text = whole[-min(have + n_new, max(last, ctx)) * C:]
+        return audio
+
     # ------------------------------------------------------------------ one-replay duplex frame (rca_duplex_frame)
     def duplex_plan(self, audio: AudioArg, preroll_samples: int = 0) -> Optional[dict]:
         """What tokenize_audio(audio) followed by detokenize_audio(<as many codes>, preroll_samples) would hand to the codec, WITHOUT

@@ -212,6 +212,32 @@ class HipCodec:
                                                     C.c_void_p(taps_ptr), int(n_taps), C.c_void_p(dst_ptr), C.c_int64(dst_span),
                                                     C.c_void_p(stream)), "rca_codec_ingest_rows_dev")
 
+    def decode_rows_dev(self, codes_ptr: int, src_off_ptr: int, B: int, F: int, n_samples: int, pcm_ptr: int, dst_off_ptr: int, code_span: int,
+                        pcm_span: int, stream: int = 0) -> None:
+        """B rows of F codes at codes + src_off[b]; the last n_samples of row b's decode land at pcm + dst_off[b] (each row bit-identical
+        to decode_tail_dev of that row).  Destination rows must not overlap."""
+        N.check(self._lib.rca_codec_decode_rows_dev(self._h, C.c_void_p(codes_ptr), C.c_void_p(src_off_ptr), B, F, n_samples, C.c_void_p(pcm_ptr),
+                                                    C.c_void_p(dst_off_ptr), C.c_int64(code_span), C.c_int64(pcm_span), C.c_void_p(stream)),
+                "rca_codec_decode_rows_dev")
+
+    def check_decode_error(self, stream: int = 0) -> None:
+        """Synchronise `stream` and raise if a decode kernel flagged a code outside the codebook or a row outside its span."""
+        flag = C.c_int32()
+        N.check(self._lib.rca_codec_decode_error(self._h, C.c_void_p(stream), C.byref(flag)), "rca_codec_decode_error")
+        if flag.value:
+            raise N.RcaError(f"decode: code out of range [0, {self.cfg.codebook_size}) or row outside its span")
+
+    def crossfade_join_dev(self, seg_ptr: int, seg_span: int, segs_dev_ptr: int, segs_host: np.ndarray, fade_in_ptr: int, n_fade: int, out_ptr: int,
+                           out_span: int, stream: int = 0) -> None:
+        """smooth_join of many streams in one launch (rca_codec_crossfade_join_dev).  segs_host: a contiguous array of _native.JOIN_SEG
+        records, the host copy of the table at segs_dev_ptr; fade_in_ptr: n_fade float32 on the device (0 when n_fade == 0)."""
+        if segs_host.dtype != N.JOIN_SEG or not segs_host.flags.c_contiguous:
+            raise ValueError("segs_host must be a contiguous array of _native.JOIN_SEG records")
+        N.check(self._lib.rca_codec_crossfade_join_dev(self._h, C.c_void_p(seg_ptr), C.c_int64(seg_span), C.c_void_p(segs_dev_ptr),
+                                                       C.c_void_p(segs_host.ctypes.data), int(segs_host.size), C.c_void_p(fade_in_ptr or None),
+                                                       int(n_fade), C.c_void_p(out_ptr), C.c_int64(out_span), C.c_void_p(stream)),
+                "rca_codec_crossfade_join_dev")
+
     def encoder_dev(self, pcm_ptr: int, B: int, T: int, ze_ptr: int, stream: int = 0) -> None:
         N.check(self._lib.rca_codec_encoder_dev(self._h, C.c_void_p(pcm_ptr), B, T, C.c_void_p(ze_ptr), C.c_void_p(stream)), "rca_codec_encoder_dev")
 
@@ -387,6 +413,63 @@ class MagiCodecHIP:
         pcm = torch.empty((B, 1, n), dtype=torch.float32, device=codes.device)
         self.hip.decode_tail_dev(codes.data_ptr(), B, F, n, pcm.data_ptr(), _stream_of(codes))
         return pcm
+
+    def run_stream_plan(self, codes_dev, plan, fade_in: np.ndarray, batch: int = 256, times: Optional[dict] = None):
+        """Execute a stream_decode.BatchPlan on the device: codes_dev is the flat int64 code buffer the plan was laid over (a torch
+        tensor on this device).  Every row group goes through rca_codec_decode_rows_dev in passes of `batch` rows, then ONE
+        rca_codec_crossfade_join_dev writes the joined streams.  -> flat f32 device tensor [plan.out_span]; everything is enqueued
+        on the current stream, nothing is synchronised (HipCodec.check_decode_error does both)."""
+        torch = _torch()
+        dev = codes_dev.device
+        n_rows, S = len(plan.F), len(plan.segs)
+        out = torch.empty(max(plan.out_span, 1), dtype=torch.float32, device=dev)
+        if n_rows == 0:
+            return out[:0]
+        st = _stream_of(codes_dev)
+        tab = torch.from_numpy(np.concatenate([plan.src, plan.dst]).astype(np.int64)).pin_memory().to(dev, non_blocking=True)
+        segs_host = np.ascontiguousarray(plan.segs)
+        segs_dev = torch.from_numpy(segs_host.view(np.uint8).copy()).pin_memory().to(dev, non_blocking=True)
+        fade_dev = torch.from_numpy(np.ascontiguousarray(fade_in, dtype=np.float32)).to(dev) if plan.n_fade else None
+        pieces = torch.empty(plan.seg_span, dtype=torch.float32, device=dev)
+        src_ptr, dst_ptr = tab.data_ptr(), tab.data_ptr() + 8 * n_rows
+        for F, n, a, b in plan.groups:
+            for k in range(a, b, batch):
+                self.hip.decode_rows_dev(codes_dev.data_ptr(), src_ptr + 8 * k, min(batch, b - k), F, n, pieces.data_ptr(), dst_ptr + 8 * k,
+                                         plan.code_span, plan.seg_span, st)
+                if times is not None:
+                    times["passes"] = times.get("passes", 0) + 1
+        self.hip.crossfade_join_dev(pieces.data_ptr(), plan.seg_span, segs_dev.data_ptr(), segs_host, fade_dev.data_ptr() if plan.n_fade else 0,
+                                    plan.n_fade, out.data_ptr(), plan.out_span, st)
+        # the tables and the pieces are read by work still in flight: the caching allocator hands their memory out again only to
+        # later work on the same stream, which runs after it
+        return out[:plan.out_span]
+
+    def stream_decode_np(self, codes: np.ndarray, chunk_frames: int, context_frames: int, preroll: int, fade_in: Optional[np.ndarray] = None,
+                         have: int = 0, clip: bool = True, batch: int = 256) -> np.ndarray:
+        """R independent streams rendered as the per-chunk loop renders them (detokenize_audio(chunk, preroll_samples=preroll) +
+        smooth_join per chunk of chunk_frames codes, context_frames of rolling code context), the whole plan on the device.
+        codes [R, have + N] int64: `have` codes of earlier context, then the N codes to render.  fade_in: the `preroll` ramp values
+        (default: create_crossfade_ramps' equal-power ramp).  -> f32 [R, N_out], bit-identical to the loop."""
+        from .stream_decode import plan_batch
+        torch = _torch()
+        codes = np.ascontiguousarray(codes, dtype=np.int64)
+        if codes.ndim != 2 or codes.shape[1] < have:
+            raise ValueError("codes must be [R, have + N]")
+        R, N_ = codes.shape[0], codes.shape[1] - have
+        if fade_in is None:
+            fade_in = np.sin(0.5 * np.pi * np.linspace(0, 1, preroll, endpoint=False, dtype=np.float32))
+        if len(fade_in) != preroll:
+            raise ValueError(f"fade_in holds {len(fade_in)} values for a preroll of {preroll}")
+        dec_left = self.hip.receptive_field()[1] if clip else None
+        plan = plan_batch([N_] * R, [have] * R, chunk_frames, context_frames, preroll, self.hop, self.cfg.framerate, self.cfg.sample_rate,
+                          dec_left=dec_left)
+        if plan.out_span == 0:
+            return np.zeros((R, 0), np.float32)
+        with torch.cuda.device(self.device):
+            codes_dev = torch.from_numpy(codes.reshape(-1)).to(self.device)
+            out = self.run_stream_plan(codes_dev, plan, fade_in, batch)
+            self.hip.check_decode_error(_stream_of(codes_dev))
+            return out.cpu().numpy().reshape(R, -1)
 
     def decode_codes(self, codes):
         """embedding(codes, projected codebook) -> decoder in one C-ABI call: [B,F] int64 -> [B,1,T] f32."""

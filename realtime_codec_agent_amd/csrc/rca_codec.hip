@@ -1838,6 +1838,65 @@ __global__ __launch_bounds__(256) void embed_codes_kernel(const int64_t* __restr
     zq[idx] = cb[c * J + j];
 }
 
+// zq[b][j][f] = cb[codes[src_off[b] + f0 + f]][j]: embed_codes_kernel for rows that start anywhere in one buffer (rca_codec_decode_rows_dev).
+// A row that does not lie inside [0, span) reads nothing and raises the error flag, like a code outside the codebook.
+__global__ __launch_bounds__(256) void embed_rows_kernel(const int64_t* __restrict__ codes, const long* __restrict__ src_off, int f0, int Frow,
+                                                         long span, const float* __restrict__ cb, float* __restrict__ zq, int B, int F, int J,
+                                                         int N, int* __restrict__ err) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)B * J * F) return;
+    const int f = (int)(idx % F);
+    const long r = idx / F;
+    const int j = (int)(r % J);
+    const int b = (int)(r / J);
+    const long o = src_off[b];
+    int64_t c = -1;
+    if (o >= 0 && o <= span - Frow) c = codes[o + f0 + f];
+    if (c < 0 || c >= N) { atomicExch(err, 1); c = 0; }
+    zq[idx] = cb[c * J + j];
+}
+
+// dst[dst_off[b] + i] = src[b][T - n + i], i < n: the kept tail of every decoded row, stored at the row's own destination.
+// A destination outside [0, span) is not written and raises the error flag.
+__global__ __launch_bounds__(256) void scatter_tail_kernel(const float* __restrict__ src, long T, int n, float* __restrict__ dst,
+                                                           const long* __restrict__ dst_off, long span, int B, int* __restrict__ err) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)B * n) return;
+    const long b = idx / n;
+    const int i = (int)(idx - b * n);
+    const long o = dst_off[b];
+    if (o < 0 || o > span - n) { if (i == 0) atomicExch(err, 1); return; }
+    dst[o + i] = src[b * T + (T - n) + i];
+}
+
+// smooth_join of many streams (rca_codec_crossfade_join_dev).  Block (s, t) takes samples [t * RCA_JOIN_TILE, ...) of segment s; sample i
+// of a segment lands at out_off + i.  The first n_fade samples of a segment with a predecessor are the blend with the predecessor's last
+// n_fade; the last n_fade of a segment with a successor are left to the successor's threads: every output sample has one writer.
+#define RCA_JOIN_TILE 1024
+__global__ __launch_bounds__(256) void crossfade_join_kernel(const float* __restrict__ seg, const rca_join_seg_t* __restrict__ segs, int n_fade,
+                                                             const float* __restrict__ fade_in, float* __restrict__ out) {
+    const rca_join_seg_t d = segs[blockIdx.x];
+    const long i0 = (long)blockIdx.y * RCA_JOIN_TILE;
+    if (i0 >= d.n) return;
+    const long i1 = i0 + RCA_JOIN_TILE < d.n ? i0 + RCA_JOIN_TILE : d.n;
+    const bool head = d.flags & RCA_JOIN_HEAD, tail = d.flags & RCA_JOIN_TAIL;
+    const long keep_end = tail ? d.n : d.n - n_fade;
+    long prev_tail = 0;                                            // element offset of the predecessor's last n_fade samples
+    if (!head) { const rca_join_seg_t p = segs[blockIdx.x - 1]; prev_tail = p.seg_off + p.n - n_fade; }
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) {
+        if (i >= keep_end) break;
+        const float cur = seg[d.seg_off + i];
+        float v = cur;
+        if (!head && i < n_fade) {
+            // numpy's prev * fade_out + cur * fade_in: two rounded products, then one rounded sum (never an fma)
+            const float a = __fmul_rn(seg[prev_tail + i], fade_in[n_fade - 1 - i]);
+            const float c = __fmul_rn(cur, fade_in[i]);
+            v = __fadd_rn(a, c);
+        }
+        out[d.out_off + i] = v;
+    }
+}
+
 // [B][F][J] -> [B][J][F]
 __global__ __launch_bounds__(256) void transpose_fj_kernel(const float* __restrict__ in, float* __restrict__ out, int B,
                                                            int F, int J) {
@@ -3649,6 +3708,89 @@ extern "C" int rca_codec_decode_tail_dev(rca_codec_t* h, const int64_t* codes, i
     if (rc != RCA_OK) return rc;
     RCA_HIP(hipMemcpy2DAsync(pcm, (size_t)n_samples * 4, h->tail.as<float>() + (Tt - n_samples), (size_t)Tt * 4, (size_t)n_samples * 4, B,
                              hipMemcpyDeviceToDevice, st));
+    return RCA_OK;
+}
+
+// B rows of F codes taken anywhere in one device buffer; the last n_samples of row b's decode go to pcm + dst_off[b].  The launches
+// are those of rca_codec_decode_tail_dev for a [B, F] block -- same receptive-field trim, same conv instances -- between a gather-embed
+// that reads its row start from the offset table and one scatter of the kept tails (why a scatter and no store epilogue).
+extern "C" int rca_codec_decode_rows_dev(rca_codec_t* h, const int64_t* codes, const int64_t* src_off, int32_t B, int32_t F, int32_t n_samples,
+                                         float* pcm, const int64_t* dst_off, int64_t code_span, int64_t pcm_span, void* stream) {
+    if (!h || !codes || !src_off || !pcm || !dst_off || B < 1 || F < 1 || n_samples < 1)
+        return fail(RCA_ERR_ARG, "decode_rows: bad argument (B=%d F=%d n=%d)", B, F, n_samples);
+    if ((long)n_samples > (long)F * h->hop) return fail(RCA_ERR_ARG, "decode_rows: %d samples wanted, %d codes give %ld", n_samples, F, (long)F * h->hop);
+    if (code_span < F || pcm_span < n_samples)
+        return fail(RCA_ERR_ARG, "decode_rows: spans (%ld codes, %ld samples) hold no row of %d codes / %d samples", (long)code_span, (long)pcm_span, F, n_samples);
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, stream);
+    static_assert(sizeof(long) == sizeof(int64_t), "offset tables are 64-bit");
+    const int f0 = (int)(((long)F * h->hop - n_samples) / h->hop);
+    const int j = std::max(0, f0 - h->dec_left_frames);
+    const int Ft = F - j;
+    int rc;
+    if ((rc = decoder_workspace(h, B, Ft)) != RCA_OK) return rc;
+    const long Tt = (long)Ft * h->hop;
+    if ((rc = h->tail.ensure((size_t)B * Tt * 4)) != RCA_OK) return rc;
+    const int J = h->cfg.codebook_dim;
+    float* zq = h->act[0].as<float>();
+    embed_rows_kernel<<<cdiv((long)B * J * Ft, 256), 256, 0, st>>>(codes, reinterpret_cast<const long*>(src_off), j, F, (long)code_span, h->cb, zq, B, Ft,
+                                                                   J, h->cfg.codebook_size, h->err_flag);
+    RCA_LAUNCH_CHECK();
+    h->lat_mode = h->variant >= 1 && (long)B * Ft <= RCA_LAT_MAX_FRAMES;
+    rc = run_decoder(h, zq, B, Ft, h->tail.as<float>(), st);
+    h->lat_mode = false;
+    if (rc != RCA_OK) return rc;
+    scatter_tail_kernel<<<cdiv((long)B * n_samples, 256), 256, 0, st>>>(h->tail.as<float>(), Tt, n_samples, pcm, reinterpret_cast<const long*>(dst_off),
+                                                                        (long)pcm_span, B, h->err_flag);
+    RCA_LAUNCH_CHECK();
+    return RCA_OK;
+}
+
+// Reads and clears the error flag that a decode kernel raises (a code outside the codebook, a row outside its span); synchronises.
+extern "C" int rca_codec_decode_error(rca_codec_t* h, void* stream, int32_t* raised) {
+    if (!h || !raised) return fail(RCA_ERR_ARG, "null");
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, stream);
+    int err = 0;
+    RCA_HIP(hipMemcpyAsync(&err, h->err_flag, 4, hipMemcpyDeviceToHost, st));
+    RCA_HIP(hipStreamSynchronize(st));
+    if (err) RCA_HIP(hipMemsetAsync(h->err_flag, 0, 4, st));
+    *raised = err;
+    return RCA_OK;
+}
+
+extern "C" int rca_codec_crossfade_join_dev(rca_codec_t* h, const float* seg, int64_t seg_span, const rca_join_seg_t* segs_dev,
+                                            const rca_join_seg_t* segs_host, int32_t n_segs, const float* fade_in_dev, int32_t n_fade, float* out,
+                                            int64_t out_span, void* stream) {
+    if (!h || !seg || !segs_dev || !segs_host || !out || n_segs < 1 || n_fade < 0 || (n_fade > 0 && !fade_in_dev) || seg_span < 0 || out_span < 0)
+        return fail(RCA_ERR_ARG, "crossfade_join: bad argument (n_segs=%d n_fade=%d)", n_segs, n_fade);
+    long max_n = 0;
+    for (int s = 0; s < n_segs; ++s) {
+        const rca_join_seg_t& d = segs_host[s];
+        const bool head = d.flags & RCA_JOIN_HEAD, tail = d.flags & RCA_JOIN_TAIL;
+        if (d.flags & ~(RCA_JOIN_HEAD | RCA_JOIN_TAIL)) return fail(RCA_ERR_ARG, "crossfade_join: segment %d: flags 0x%x", s, d.flags);
+        if (d.n < 0) return fail(RCA_ERR_ARG, "crossfade_join: segment %d holds %ld samples", s, (long)d.n);
+        const bool prev_open = s > 0 && !(segs_host[s - 1].flags & RCA_JOIN_TAIL);
+        if (head == prev_open) return fail(RCA_ERR_ARG, "crossfade_join: segment %d %s", s, head ? "starts a stream inside another" : "has no predecessor");
+        if (s + 1 == n_segs && !tail) return fail(RCA_ERR_ARG, "crossfade_join: the last segment has no successor and is not marked as a tail");
+        const long need = (head ? 0 : (long)n_fade) + (tail ? 0 : (long)n_fade);
+        if (d.n < need) return fail(RCA_ERR_ARG, "crossfade_join: segment %d holds %ld samples, its blends need %ld", s, (long)d.n, need);
+        if (d.seg_off < 0 || d.seg_off > seg_span - d.n)
+            return fail(RCA_ERR_ARG, "crossfade_join: segment %d reads [%ld, +%ld) outside the %ld samples given", s, (long)d.seg_off, (long)d.n, (long)seg_span);
+        if (d.out_off < 0 || d.out_off > out_span - d.n)
+            return fail(RCA_ERR_ARG, "crossfade_join: segment %d writes [%ld, +%ld) outside the output of %ld", s, (long)d.out_off, (long)d.n, (long)out_span);
+        if (!head && d.out_off != segs_host[s - 1].out_off + segs_host[s - 1].n - n_fade)
+            return fail(RCA_ERR_ARG, "crossfade_join: segment %d lands at %ld, its predecessor ends %d before %ld", s, (long)d.out_off, n_fade,
+                        (long)(segs_host[s - 1].out_off + segs_host[s - 1].n));
+        max_n = std::max(max_n, (long)d.n);
+    }
+    if (max_n == 0) return RCA_OK;
+    const long tiles = cdiv(max_n, RCA_JOIN_TILE);
+    if (tiles > 65535) return fail(RCA_ERR_ARG, "crossfade_join: a segment of %ld samples (at most %ld)", max_n, 65535l * RCA_JOIN_TILE);
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, stream);
+    crossfade_join_kernel<<<dim3((unsigned)n_segs, (unsigned)tiles), 256, 0, st>>>(seg, segs_dev, n_fade, fade_in_dev, out);
+    RCA_LAUNCH_CHECK();
     return RCA_OK;
 }
 
