@@ -564,6 +564,37 @@ int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const float* x_hos
  * nsp_launch or out_rows, or positions past n_ctx, are refused before anything is touched. */
 int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_t nsp_launch, const float* q_host, int32_t M, float* out_host,
                     int32_t out_rows);
+/* One scored position (rca_lm_score): what llama-perplexity and its --kl-divergence mode reduce a row of logits to, reduced on the
+ * device so that the logits never leave it.  With P = softmax(logits) of the scored handle and P_base of the base handle:
+ * lse = log sum_j exp(logit_j), max_logit / argmax = the largest logit and its LOWEST index, logprob = logit[target] - lse,
+ * base_logprob = the same under the base, kl = KL(P_base || P) = sum_j p_base,j (b_j - a_j) - lse_base + lse.
+ * A -inf logit has probability 0; a 0 * inf term of the KL sum counts as 0; a -inf in P where the base has mass gives kl = +inf.
+ * flags: bit 0 = the row holds a NaN (logprob, lse, max_logit and kl are NaN), bit 1 = the base row holds one (base_logprob and kl
+ * are NaN), bit 2 = kl is +inf.  target -1 ("not scored"): logprob and base_logprob are NaN.  Without a base: kl and base_logprob are
+ * NaN and base_argmax is -1. */
+typedef struct rca_score_row {
+    float logprob, lse, max_logit, kl, base_logprob;
+    int32_t argmax, base_argmax, flags;
+} rca_score_row_t;
+/* llama-perplexity (and --kl-divergence against `base`): llama_decode of a chunk with logits for every position, then
+ * log_softmax / the KL sums per row on the host (llama.cpp tools/perplexity; the reference deploys through llama.cpp,
+ * realtime_agent_resources.py:19-33, and scores with Llama.eval + log-softmax of _scores, llamacpp_utils.py:30-37).  Appends the n ids at
+ * n_tokens exactly as a long rca_lm_eval_async does -- on the 128-token-tile route the same launches, so the KV cache holds the same
+ * bits -- advances n_tokens and leaves the LAST position's logits where rca_lm_eval leaves them (sample / get_logits follow as after
+ * an eval).  Every 128-token block gets its logits from the head on the same tiles into a scratch block and one row reduction;
+ * rows_host[i] scores position i against targets[i] (-1 = skip; targets == NULL: ids shifted by one, the last -1).  Handles whose long
+ * evals do not take the 128-token tiles (shape, or rca_lm_set_mfma_prefill(0)) are scored on the exact 2-token decode passes: slower,
+ * same results within the routes' rounding.  logits_all is ignored.  base (may be NULL; any weight format, may be a
+ * rca_lm_create_shared twin): advanced over the same ids in lock-step on its own stream, ordered by events; it must be another
+ * handle on the same device with the same vocabulary, the same n_tokens and room for n more (both handles run the decode passes
+ * unless both take the tiles).  One download of n rows and one synchronisation per call; the base handle is left pending like after
+ * rca_lm_eval_async.  Refused, with nothing changed: context overflow (RCA_ERR_STATE), an id or target outside the vocabulary, a
+ * mismatched base (RCA_ERR_ARG).  The scratch (128 x V floats per handle) is allocated by the first call; captured graphs stay valid. */
+int rca_lm_score(rca_lm_t* h, rca_lm_t* base, const int32_t* ids, int32_t n, const int32_t* targets, rca_score_row_t* rows_host);
+/* Tests only: the row reduction of rca_lm_score alone on M rows of host-supplied logits [M][V] (V = the handle's vocabulary;
+ * base_logits_host may be NULL), targets [M] in [-1, V).  The handle's state is untouched. */
+int rca_lm_score_rows_tap(rca_lm_t* h, const float* logits_host, const float* base_logits_host, const int32_t* targets, int32_t M,
+                          rca_score_row_t* rows_host);
 /* synchronise the handle's stream (timing) */
 int rca_lm_sync(rca_lm_t* h);
 int rca_codec_sync(rca_codec_t* h);

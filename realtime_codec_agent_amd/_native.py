@@ -257,6 +257,17 @@ class SamplerParamsC(C.Structure):
     ]
 
 
+class ScoreRowC(C.Structure):
+    """rca_score_row_t: one scored position of rca_lm_score (SCORE_ROW_DTYPE is the same record as a numpy dtype)."""
+    _fields_ = [("logprob", C.c_float), ("lse", C.c_float), ("max_logit", C.c_float), ("kl", C.c_float), ("base_logprob", C.c_float),
+                ("argmax", C.c_int32), ("base_argmax", C.c_int32), ("flags", C.c_int32)]
+
+
+SCORE_ROW_DTYPE = np.dtype([("logprob", np.float32), ("lse", np.float32), ("max_logit", np.float32), ("kl", np.float32),
+                            ("base_logprob", np.float32), ("argmax", np.int32), ("base_argmax", np.int32), ("flags", np.int32)])
+assert SCORE_ROW_DTYPE.itemsize == C.sizeof(ScoreRowC)
+
+
 class DuplexFrameArgsC(C.Structure):
     _fields_ = [
         ("pcm_window", C.c_void_p),
@@ -397,7 +408,7 @@ ABI_SYMBOLS = [
     "rca_lm_persist_codec_embeddings", "rca_lm_create_shared", "rca_lm_eval_async", "rca_lm_copy_kv", "rca_lm_swap_kv",
     "rca_lm_set_low_priority", "rca_lm_frame", "rca_lm_weight_format", "rca_lm_set_attn_fuse", "rca_lm_prefill_route",
     "rca_lm_set_act_format", "rca_lm_get_act_format", "rca_lm_gemv_tap", "rca_lm_kv_remove", "rca_lm_kv_read",
-    "rca_lm_kv_write", "rca_lm_attn_tap",
+    "rca_lm_kv_write", "rca_lm_attn_tap", "rca_lm_score", "rca_lm_score_rows_tap",
     "rca_duplex_frame", "rca_codec_workspace_sig", "rca_codec_stream_handoff", "rca_codec_codebook_size", "rca_codec_set_mfma_mode", "rca_lm_step_probe", "rca_duplex_prepare", "rca_duplex_precapture",
 ]
 

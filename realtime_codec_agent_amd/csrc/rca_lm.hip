@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <type_traits>
 #include <cmath>
+#include <climits>
 
 #include "rca_common.h"
 
@@ -894,6 +895,7 @@ __global__ __launch_bounds__(256) void lm_split_bf16_kernel(const LmDevState* __
 #define GEMM_EPI_RESID 0
 #define GEMM_EPI_ROPE 1
 #define GEMM_EPI_SWIGLU 2
+#define GEMM_EPI_LOGITS 3   // lm_gemm128_kernel only: the head of rca_lm_score, plain f32 stores into one token block's [128][V] scratch
 template <int EPI>
 __global__ __launch_bounds__(256) void lm_gemm_mfma_kernel(const LmDevState* __restrict__ stt, const bf16_t* __restrict__ W,
                                                            const bf16_t* __restrict__ xh, const bf16_t* __restrict__ xl, int N, int K,
@@ -2162,6 +2164,14 @@ struct rca_lm {
     int borrowers = 0;
     bool zombie = false;
     struct DuplexState* duplex = nullptr;   // rca_duplex_frame: buffers + graphs of the one-replay frame
+    // rca_lm_score: allocated by the first call that needs them, freed with the handle
+    float* sc_blk = nullptr;                 // the logits of one 128-token block [128][V]
+    rca_score_row_t* sc_rows = nullptr;      // device rows of a call + its targets behind them
+    int* sc_tgt = nullptr;
+    long sc_rows_cap = 0;
+    char* sc_pin = nullptr;                  // pinned: the (n_tokens, m, ids) block of EVERY pass of a call, so no pass waits for the one before
+    size_t sc_pin_cap = 0;
+    hipEvent_t sc_ready = nullptr, sc_free = nullptr;   // base: block logits written; scored handle: block logits consumed
 };
 struct DuplexState;
 static void duplex_destroy(DuplexState* d);
@@ -2257,6 +2267,12 @@ extern "C" int rca_lm_destroy(rca_lm_t* h) {
     h->probe_ids_dev = nullptr; h->att_arrive = nullptr; h->xh = h->xl = nullptr; h->stt = nullptr; h->samp = nullptr; h->swork = nullptr;
     if (h->h_stt) { (void)hipHostFree(h->h_stt); h->h_stt = nullptr; }
     if (h->h_probe) { (void)hipHostFree(h->h_probe); h->h_probe = nullptr; }
+    for (void* p : {(void*)h->sc_blk, (void*)h->sc_rows, (void*)h->sc_tgt})
+        if (p) (void)hipFree(p);
+    h->sc_blk = nullptr; h->sc_rows = nullptr; h->sc_tgt = nullptr;
+    if (h->sc_pin) { (void)hipHostFree(h->sc_pin); h->sc_pin = nullptr; }
+    if (h->sc_ready) { (void)hipEventDestroy(h->sc_ready); h->sc_ready = nullptr; }
+    if (h->sc_free) { (void)hipEventDestroy(h->sc_free); h->sc_free = nullptr; }
     if (h->stream) { (void)hipStreamDestroy(h->stream); h->stream = nullptr; }
     if (h->weights_of) {            // borrower: the weights belong to someone else
         rca_lm* owner = h->weights_of;
@@ -4032,24 +4048,33 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
     const int nstage = nseq * spf;
     // staging role: two 16-byte chunks per tile and thread: rows c >> 2, k offset (c & 3) * 8
     const int srow0 = tid >> 2, skc = (tid & 3) * 8;
-    const bf16_t* gW = W + (long)(n0 + srow0) * K + ks + skc;
+    // GEMM_EPI_LOGITS: N (the vocabulary) is no multiple of 128, so the last row tile clamps every weight address to the last valid
+    // row / pair / quad (the packed formats are loaded with N % 2 == 0 resp. N % 4 == 0) -- no read passes the end of the matrix or of
+    // its scale arrays; the rows staged twice that way are masked at the store (n >= N).  The other epilogues see what they always saw.
+    constexpr bool RAGGED = EPI == GEMM_EPI_LOGITS;
+    const int wrow0 = RAGGED ? min(n0 + srow0, N - 1) : n0 + srow0;
+    const bf16_t* gW = W + (long)wrow0 * K + ks + skc;
     const bf16_t* gH = xh + (long)(tb + srow0) * K + ks + skc;
     const bf16_t* gL = xl + (long)(tb + srow0) * K + ks + skc;
     const long rstep = 64L * K;     // second chunk: row + 64
+    const long wstep = RAGGED ? (long)(min(n0 + srow0 + 64, N - 1) - wrow0) * K : rstep;
     const int soff0 = srow0 * G128_PITCH + skc, soff1 = soff0 + 64 * G128_PITCH;
     // q8_0: a thread's stage is ONE 16-byte unit of the packed layout = 8 k of the two rows of pair (n0 / 2 + tid / 4); the pair's
     // rows are (2p, 2p + 1), or (d, d + 32) of one head in the fused QKV matrix (the only matrix that runs the RoPE epilogue)
     const int qp = tid >> 2;
     const long q_nkb = K >> 5;
-    const u32x4* gQ = (WF == WF_Q8 || WF == WF_Q6K) ? q8.qs + ((long)(n0 >> 1) + qp) * (K >> 3) + (ks >> 3) + (tid & 3) : nullptr;
-    const unsigned* gS = WF == WF_Q8 ? q8.sc + q8_sc_index((n0 >> 1) + qp, ks >> 5, q_nkb) : nullptr;   // next k block: + 8
-    const float* gS6 = WF == WF_Q6K ? reinterpret_cast<const float*>(q8.sc) + 2 * q8_sc_index((n0 >> 1) + qp, (ks >> 4) + ((tid & 3) >> 1), K >> 4) : nullptr;   // next stage: + 2 groups of 16
+    const int gpair = RAGGED ? min((n0 >> 1) + qp, (N >> 1) - 1) : (n0 >> 1) + qp;
+    const u32x4* gQ = (WF == WF_Q8 || WF == WF_Q6K) ? q8.qs + (long)gpair * (K >> 3) + (ks >> 3) + (tid & 3) : nullptr;
+    const unsigned* gS = WF == WF_Q8 ? q8.sc + q8_sc_index(gpair, ks >> 5, q_nkb) : nullptr;   // next k block: + 8
+    const float* gS6 = WF == WF_Q6K ? reinterpret_cast<const float*>(q8.sc) + 2 * q8_sc_index(gpair, (ks >> 4) + ((tid & 3) >> 1), K >> 4) : nullptr;   // next stage: + 2 groups of 16
     // Q4_K: a thread's stage is HALF a 16-byte unit = 8 k of two adjacent slots: quad tid / 8, chunk (tid / 2) % 4, slots 2 (tid % 2) + {0, 1}
-    const int q4quad = tid >> 3, q4half = tid & 1, q4slot = 4 * ((n0 >> 2) + q4quad) + 2 * q4half;
+    const int q4quad = tid >> 3, q4half = tid & 1;
+    const int gquad = RAGGED ? min((n0 >> 2) + q4quad, (N >> 2) - 1) : (n0 >> 2) + q4quad;
+    const int q4slot = 4 * gquad + 2 * q4half;
     constexpr bool W40 = WF == WF_Q40;                  // Q4_0 / Q4_1: the Q4_K staging with the (s | t << 16) dword of each slot and stage
     constexpr bool W4 = WF == WF_Q4K || WF == WF_Q5K || W40;   // Q5_K: the Q4_K staging + the quad's dword of high bits (arrives as W)
-    const unsigned* gH5 = WF == WF_Q5K ? reinterpret_cast<const unsigned*>(W) + ((long)(n0 >> 2) + q4quad) * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3) : nullptr;
-    const uint2* gQ4 = W4 ? reinterpret_cast<const uint2*>(q8.qs + ((long)(n0 >> 2) + q4quad) * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3)) + q4half : nullptr;
+    const unsigned* gH5 = WF == WF_Q5K ? reinterpret_cast<const unsigned*>(W) + (long)gquad * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3) : nullptr;
+    const uint2* gQ4 = W4 ? reinterpret_cast<const uint2*>(q8.qs + (long)gquad * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3)) + q4half : nullptr;
     const unsigned short* gS4 = (W4 && !W40) ? reinterpret_cast<const unsigned short*>(q8.sc) + q4k_scm_index(q4slot, ks >> 5, q_nkb) : nullptr;   // next sub-block: + 16
     const unsigned* gF40 = W40 ? q8.sc + q4k_scm_index(q4slot, ks >> 5, q_nkb) : nullptr;                                                      // next block: + 16
     const unsigned* gD4 = (W4 && !W40) ? q8.dd + q4k_scm_index(q4slot, 0, K >> 8) : nullptr;                                                     // super-block k / 256: + 16 each
@@ -4087,7 +4112,7 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
             rs[slot] = gS[(long)st * 8];
         } else {
             const int k = st << 5;
-            rw[slot][0] = *reinterpret_cast<const uint4*>(gW + k); rw[slot][1] = *reinterpret_cast<const uint4*>(gW + rstep + k);
+            rw[slot][0] = *reinterpret_cast<const uint4*>(gW + k); rw[slot][1] = *reinterpret_cast<const uint4*>(gW + wstep + k);
         }
     };
     auto gload_x = [&](int slot, int s) {
@@ -4221,6 +4246,24 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int tok = tb + wc * 64 + j * 32 + (lane & 31);
+        if (EPI == GEMM_EPI_LOGITS) {   // y = the block's scratch [128][ldy], rope.row_base = first token of the block inside the pass
+            if (rope.row_base + tok >= Mv) continue;
+            float* yr = y + (long)tok * ldy;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {   // registers 4 q .. 4 q + 3 are four consecutive rows
+                    const int n = n0 + wr * 64 + i * 32 + 8 * q + 4 * half;
+                    if (n + 3 < N && (ldy & 3) == 0) {
+                        *reinterpret_cast<float4*>(yr + n) = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (n + e < N) yr[n + e] = acc[i][j][4 * q + e];
+                    }
+                }
+            continue;
+        }
         if (tok >= Mv) continue;
         if (nsplit > 1) {   // partial sums of this k slice, token-contiguous [split][n][LM_MAXM]: lanes are tokens -> 128-byte runs
             float* p = part + ((long)blockIdx.y * N + n0 + wr * 64) * LM_MAXM + tok;
@@ -5759,5 +5802,300 @@ extern "C" int rca_lm_prefill_route(const rca_lm_t* h, int32_t* route) {
 extern "C" int rca_lm_set_mfma_prefill(rca_lm_t* h, int32_t enable) {
     if (!h) return fail(RCA_ERR_ARG, "null");
     h->mfma_prefill = enable != 0;
+    return RCA_OK;
+}
+
+// ------------------------------------------------------------------------------------ scoring (rca_lm_score)
+// One workgroup per token row, ONE pass over the row's V logits (and over the same row of the base's block) with an online softmax:
+// a thread keeps (m, s, t, arg) = running maximum, sum of exp(x - m), [base only] sum of exp(b - m_b) (b - a), index of the maximum.
+// It takes 16-byte chunks tid, tid + 256, ...; per chunk the maximum is raised first (s and t scaled by exp(m_old - m_new), once per
+// chunk), then the four terms are added in index order.  The <= 3 values in front of the first aligned chunk (V need not be a multiple
+// of 4, so a row need not start on 16 bytes) go to thread 0 before its chunks, the <= 3 behind the last one to thread 255 after its
+// chunks.  The 256 states are merged by a 6-step xor butterfly inside each wave (offsets 32 .. 1), then wave 1, 2, 3 are merged into
+// wave 0 in that order: merge((m1, s1), (m2, s2)) = (M, s1 exp(m1 - M) + s2 exp(m2 - M)) with M = max, exp(0) taken as exactly 1.
+// The longest chain of f32 additions is 4 ceil(chunks / 256) + 3 + 6 + 3 (tests/score_ref.py derives the error bound from it).
+// Ties of the maximum go to the lowest index: strict > inside a thread (ascending indices), (value, lower index) between threads.
+// -inf logits contribute exactly 0 (never exp(-inf - -inf)); NaN never wins a maximum, is flagged and turns the row's outputs NaN.
+struct ScoreAcc { float m, s, t; int arg; };
+__device__ __forceinline__ float score_scale(float from, float to) { return from == to ? 1.0f : expf(from - to); }
+__device__ __forceinline__ void score_merge(ScoreAcc& a, const ScoreAcc& b) {
+    const float M = fmaxf(a.m, b.m);
+    const float fa = score_scale(a.m, M), fb = score_scale(b.m, M);
+    if (b.m > a.m || (b.m == a.m && b.arg < a.arg)) a.arg = b.arg;
+    a.s = a.s * fa + b.s * fb;
+    a.t = a.t * fa + b.t * fb;
+    a.m = M;
+}
+__device__ __forceinline__ void score_raise(ScoreAcc& A, const float* v, int idx0, int cnt) {
+    float nm = A.m;
+    for (int j = 0; j < cnt; ++j)
+        if (v[j] > nm) { nm = v[j]; A.arg = idx0 + j; }
+    if (nm != A.m) {
+        const float f = expf(A.m - nm);
+        A.s = A.s * f;
+        A.t = A.t * f;
+        A.m = nm;
+    }
+}
+template <bool BASE>
+__device__ __forceinline__ void score_take(ScoreAcc& A, ScoreAcc& B, int& fl, const float* a, const float* b, int idx0, int cnt) {
+    score_raise(A, a, idx0, cnt);
+    if (BASE) score_raise(B, b, idx0, cnt);
+    for (int j = 0; j < cnt; ++j) {
+        if (a[j] != a[j]) fl |= 1;
+        A.s = A.s + (a[j] == -INFINITY ? 0.0f : expf(a[j] - A.m));
+        if (BASE) {
+            if (b[j] != b[j]) fl |= 2;
+            const float e = b[j] == -INFINITY ? 0.0f : expf(b[j] - B.m);
+            B.s = B.s + e;
+            if (b[j] > -INFINITY) {   // p_base = 0: the term counts as 0 whatever a is
+                if (a[j] == -INFINITY) fl |= 4;   // P gives no mass where the base does: kl = +inf
+                else B.t = B.t + e * (b[j] - a[j]);
+            }
+        }
+    }
+}
+__device__ __forceinline__ void score_wave_merge(ScoreAcc& A) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        ScoreAcc o;
+        o.m = __shfl_xor(A.m, off); o.s = __shfl_xor(A.s, off); o.t = __shfl_xor(A.t, off); o.arg = __shfl_xor(A.arg, off);
+        score_merge(A, o);
+    }
+}
+#define SCORE_THREADS 256
+template <bool BASE>
+__global__ __launch_bounds__(SCORE_THREADS) void lm_score_rows_kernel(const float* __restrict__ logits, const float* __restrict__ base, int V,
+                                                                      const int* __restrict__ targets, rca_score_row_t* __restrict__ out) {
+    __shared__ ScoreAcc smA[SCORE_THREADS / 64], smB[SCORE_THREADS / 64];
+    __shared__ int smf[SCORE_THREADS / 64];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* pa = logits + (long)row * V;
+    const float* pb = BASE ? base + (long)row * V : nullptr;
+    const int pre = min(V, (4 - (int)(((long)row * V) & 3)) & 3);   // values in front of the row's first 16-byte boundary
+    const int nb4 = (V - pre) >> 2, tail0 = pre + 4 * nb4;
+    ScoreAcc A{-INFINITY, 0.0f, 0.0f, INT_MAX}, B{-INFINITY, 0.0f, 0.0f, INT_MAX};
+    int fl = 0;
+    float a[4], b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (tid == 0 && pre > 0) {
+        for (int j = 0; j < pre; ++j) { a[j] = pa[j]; if (BASE) b[j] = pb[j]; }
+        score_take<BASE>(A, B, fl, a, b, 0, pre);
+    }
+    for (int c = tid; c < nb4; c += SCORE_THREADS) {
+        const float4 va = *reinterpret_cast<const float4*>(pa + pre + 4 * c);
+        a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w;
+        if (BASE) {
+            const float4 vb = *reinterpret_cast<const float4*>(pb + pre + 4 * c);
+            b[0] = vb.x; b[1] = vb.y; b[2] = vb.z; b[3] = vb.w;
+        }
+        score_take<BASE>(A, B, fl, a, b, pre + 4 * c, 4);
+    }
+    if (tid == SCORE_THREADS - 1 && tail0 < V) {
+        for (int j = 0; j < V - tail0; ++j) { a[j] = pa[tail0 + j]; if (BASE) b[j] = pb[tail0 + j]; }
+        score_take<BASE>(A, B, fl, a, b, tail0, V - tail0);
+    }
+    score_wave_merge(A);
+    if (BASE) score_wave_merge(B);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) fl |= __shfl_xor(fl, off);
+    if ((tid & 63) == 0) { smA[tid >> 6] = A; smB[tid >> 6] = B; smf[tid >> 6] = fl; }
+    __syncthreads();
+    if (tid != 0) return;
+    for (int w = 1; w < SCORE_THREADS / 64; ++w) {
+        score_merge(A, smA[w]);
+        if (BASE) score_merge(B, smB[w]);
+        fl |= smf[w];
+    }
+    const float nanv = __uint_as_float(0x7fc00000u);
+    const int tgt = targets[row];
+    rca_score_row_t r;
+    r.flags = fl;
+    r.argmax = A.arg == INT_MAX ? 0 : A.arg;
+    r.max_logit = A.m;
+    r.lse = A.m + logf(A.s);
+    r.logprob = tgt >= 0 ? pa[tgt] - r.lse : nanv;
+    r.kl = nanv; r.base_logprob = nanv; r.base_argmax = -1;
+    if (BASE) {
+        const float lse_b = B.m + logf(B.s);
+        r.base_argmax = B.arg == INT_MAX ? 0 : B.arg;
+        r.base_logprob = tgt >= 0 ? pb[tgt] - lse_b : nanv;
+        r.kl = (fl & 4) ? INFINITY : (B.t / B.s - lse_b) + r.lse;
+        if (fl & 2) r.base_logprob = nanv;
+        if (fl & 3) r.kl = nanv;
+    }
+    if (fl & 1) { r.lse = nanv; r.max_logit = nanv; r.logprob = nanv; }
+    out[row] = r;
+}
+static void lm_launch_score_rows(const float* blk, const float* base_blk, int V, const int* tgt, rca_score_row_t* rows, int M, hipStream_t st) {
+    if (base_blk) lm_score_rows_kernel<true><<<M, SCORE_THREADS, 0, st>>>(blk, base_blk, V, tgt, rows);
+    else lm_score_rows_kernel<false><<<M, SCORE_THREADS, 0, st>>>(blk, nullptr, V, tgt, rows);
+}
+
+// the route rca_lm_score takes: the 128-token tiles wherever a long eval of the handle could take them (logits_all is ignored: the
+// logits never leave the device), else the exact decode passes
+static int lm_score_route(const rca_lm* h) { return h->mfma_prefill && lm_can_gemm128(h) ? LM_ROUTE_TILE128 : LM_ROUTE_GEMV; }
+static size_t lm_score_pin_bytes(int n, int step) {   // every pass's state block, 16-byte aligned
+    size_t b = 0;
+    for (int off = 0; off < n; off += step) b += (lm_state_bytes(std::min(step, n - off)) + 15) / 16 * 16;
+    return b;
+}
+static int lm_score_reserve(rca_lm* h, long n_rows, size_t pin_bytes) {
+    int rc;
+    if (!h->sc_blk && (rc = lm_alloc((void**)&h->sc_blk, (size_t)128 * h->cfg.vocab_size * 4)) != RCA_OK) return rc;
+    if (!h->sc_ready) RCA_HIP(hipEventCreateWithFlags(&h->sc_ready, hipEventDisableTiming));
+    if (!h->sc_free) RCA_HIP(hipEventCreateWithFlags(&h->sc_free, hipEventDisableTiming));
+    if (n_rows > h->sc_rows_cap) {
+        for (void* p : {(void*)h->sc_rows, (void*)h->sc_tgt})
+            if (p) (void)hipFree(p);
+        h->sc_rows = nullptr; h->sc_tgt = nullptr; h->sc_rows_cap = 0;
+        if ((rc = lm_alloc((void**)&h->sc_rows, (size_t)n_rows * sizeof(rca_score_row_t))) != RCA_OK) return rc;
+        if ((rc = lm_alloc((void**)&h->sc_tgt, (size_t)n_rows * 4)) != RCA_OK) return rc;
+        h->sc_rows_cap = n_rows;
+    }
+    if (pin_bytes > h->sc_pin_cap) {
+        if (h->sc_pin) { (void)hipHostFree(h->sc_pin); h->sc_pin = nullptr; h->sc_pin_cap = 0; }
+        RCA_HIP(hipHostMalloc((void**)&h->sc_pin, pin_bytes, hipHostMallocDefault));
+        h->sc_pin_cap = pin_bytes;
+    }
+    return RCA_OK;
+}
+// the next pass of a scoring call as the device will read it, from this pass's OWN pinned block (lm_push_state reuses one)
+static int lm_score_push(rca_lm* x, size_t* pin_off, const int32_t* ids, int m, hipStream_t st) {
+    int* p = reinterpret_cast<int*>(x->sc_pin + *pin_off);
+    const size_t nb = lm_state_bytes(m);
+    memset(p, 0, nb);
+    p[0] = x->n_tokens;
+    p[1] = m;
+    memcpy(p + 2, ids, (size_t)m * 4);
+    *pin_off += (nb + 15) / 16 * 16;
+    RCA_HIP(hipMemcpyAsync(x->stt, p, nb, hipMemcpyHostToDevice, st));
+    return RCA_OK;
+}
+// final RMSNorm + head of tokens [tb, tb + 128) of the pass in x->x on the 128-row tiles -> x->sc_blk.  The caller has written the
+// hi / lo split of the normalised rows to x->xh / x->xl.  Every workgroup walks all of K itself (one slice: no partial sums).
+static void lm_launch_head128(rca_lm* x, int tb, hipStream_t st) {
+    const rca_lm_config_t& c = x->cfg;
+    GemvRope rp = norope;
+    rp.row_base = tb;
+    launch_gemm128<GEMM_EPI_LOGITS>(x, x->head, dim3(cdiv(c.vocab_size, 128), 1, 1), st, x->xh + (long)tb * c.hidden, x->xl + (long)tb * c.hidden,
+                                    c.vocab_size, c.hidden, c.hidden, x->sc_blk, c.vocab_size, nullptr, nullptr, rp, 1);
+}
+
+extern "C" int rca_lm_score(rca_lm_t* h, rca_lm_t* base, const int32_t* ids, int32_t n, const int32_t* targets, rca_score_row_t* rows_host) {
+    if (!h || n < 0 || (n > 0 && (!ids || !rows_host))) return fail(RCA_ERR_ARG, "score: bad argument");
+    if (n == 0) return RCA_OK;
+    const rca_lm_config_t& c = h->cfg;
+    const int V = c.vocab_size;
+    if (h->n_tokens + n > c.n_ctx) return fail(RCA_ERR_STATE, "score: context overflow: %d + %d > n_ctx %d", h->n_tokens, n, c.n_ctx);
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= V) return fail(RCA_ERR_ARG, "score: token id %d at index %d is outside the vocabulary [0, %d)", ids[i], i, V);
+    if (targets)
+        for (int i = 0; i < n; ++i)
+            if (targets[i] < -1 || targets[i] >= V) return fail(RCA_ERR_ARG, "score: target %d at index %d is neither -1 nor inside the vocabulary [0, %d)", targets[i], i, V);
+    if (base) {
+        if (base == h) return fail(RCA_ERR_ARG, "score: the base is the scored handle itself");
+        if (base->device != h->device) return fail(RCA_ERR_ARG, "score: the base sits on device %d, the scored handle on %d", base->device, h->device);
+        if (base->cfg.vocab_size != V) return fail(RCA_ERR_ARG, "score: the base has a vocabulary of %d, the scored handle one of %d", base->cfg.vocab_size, V);
+        if (base->n_tokens != h->n_tokens) return fail(RCA_ERR_ARG, "score: the base is at n_tokens %d, the scored handle at %d", base->n_tokens, h->n_tokens);
+        if (base->n_tokens + n > base->cfg.n_ctx) return fail(RCA_ERR_STATE, "score: context overflow of the base: %d + %d > n_ctx %d", base->n_tokens, n, base->cfg.n_ctx);
+    }
+    int rc;
+    if ((rc = lm_settle(h)) != RCA_OK) return rc;
+    if (base && (rc = lm_settle(base)) != RCA_OK) return rc;
+    RCA_HIP(hipSetDevice(h->device));
+    const bool tiles = lm_score_route(h) == LM_ROUTE_TILE128 && (!base || lm_score_route(base) == LM_ROUTE_TILE128);
+    const int step = tiles ? LM_MAXM : LM_GEMV_M;
+    const size_t pin_states = lm_score_pin_bytes(n, step);
+    if ((rc = lm_score_reserve(h, n, pin_states + (size_t)n * 4)) != RCA_OK) return rc;
+    if (base && (rc = lm_score_reserve(base, 0, pin_states)) != RCA_OK) return rc;
+    hipStream_t st = h->stream, sb = base ? base->stream : nullptr;
+    int* tgt_pin = reinterpret_cast<int*>(h->sc_pin + pin_states);
+    for (int i = 0; i < n; ++i) tgt_pin[i] = targets ? targets[i] : (i + 1 < n ? ids[i + 1] : -1);
+    RCA_HIP(hipMemcpyAsync(h->sc_tgt, tgt_pin, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    rca_lm* xs[2] = {h, base};
+    hipStream_t ss[2] = {st, sb};
+    size_t pin_off[2] = {0, 0};
+    const int nx = base ? 2 : 1;
+    bool base_blk_used = false;   // the scored handle's stream has read the base's block: the base waits before it overwrites it
+    // one block of logits: both handles write theirs (the base on its own stream), the scored handle's stream waits for the base's
+    // event, reduces the rows and records that the base's block is free again
+    auto score_block = [&](int row0, int mb) -> int {
+        if (base) {
+            RCA_HIP(hipEventRecord(base->sc_ready, sb));
+            RCA_HIP(hipStreamWaitEvent(st, base->sc_ready, 0));
+        }
+        lm_launch_score_rows(h->sc_blk, base ? base->sc_blk : nullptr, V, h->sc_tgt + row0, h->sc_rows + row0, mb, st);
+        if (base) {
+            RCA_HIP(hipEventRecord(h->sc_free, st));
+            base_blk_used = true;
+        }
+        return RCA_OK;
+    };
+    for (int off = 0; off < n; off += step) {
+        const int m = std::min(step, n - off);
+        const bool last = off + m >= n;
+        for (int k = 0; k < nx; ++k) {
+            rca_lm* x = xs[k];
+            if ((rc = lm_score_push(x, &pin_off[k], ids + off, m, ss[k])) != RCA_OK) return rc;
+            if (tiles) {
+                if ((rc = lm_enqueue_prefill_tile128(x, m, ss[k], lm_splits_needed(x, m))) != RCA_OK) return rc;
+                if (last) lm_launch_head(x, 1, ss[k], x->logits, true);   // the last position's logits, as rca_lm_eval computes them
+                lm_add_rmsnorm_kernel<<<m, 64, 0, ss[k]>>>(x->stt, x->x, nullptr, nullptr, 0, 0, x->final_norm, x->xn, x->cfg.hidden, x->cfg.rms_eps, x->xh, x->xl);
+            } else {
+                if ((rc = lm_enqueue_pass(x, m, 0, ss[k], lm_splits_needed(x, m))) != RCA_OK) return rc;
+                if (last) lm_launch_head(x, 1, ss[k], x->logits, true);
+            }
+        }
+        for (int tb = 0; tb < m; tb += 128) {
+            const int mb = std::min(128, m - tb);
+            if (base && base_blk_used) RCA_HIP(hipStreamWaitEvent(sb, h->sc_free, 0));
+            for (int k = 0; k < nx; ++k) {
+                if (tiles) lm_launch_head128(xs[k], tb, ss[k]);
+                else lm_launch_head(xs[k], mb, ss[k], xs[k]->sc_blk, false);
+            }
+            if ((rc = score_block(off + tb, mb)) != RCA_OK) return rc;
+        }
+        RCA_LAUNCH_CHECK();
+        for (int k = 0; k < nx; ++k) xs[k]->n_tokens += m;
+    }
+    for (int k = 0; k < nx; ++k) xs[k]->logits_rows = 1;
+    if (base) base->async_pending = true;   // its stream may still run; everything the scored rows need has been waited for through the events
+    RCA_HIP(hipMemcpyAsync(rows_host, h->sc_rows, (size_t)n * sizeof(rca_score_row_t), hipMemcpyDeviceToHost, st));
+    RCA_HIP(hipStreamSynchronize(st));
+    return RCA_OK;
+}
+
+extern "C" int rca_lm_score_rows_tap(rca_lm_t* h, const float* logits_host, const float* base_logits_host, const int32_t* targets, int32_t M,
+                                     rca_score_row_t* rows_host) {
+    if (!h || !logits_host || !targets || !rows_host) return fail(RCA_ERR_ARG, "null");
+    const int V = h->cfg.vocab_size;
+    if (M < 1 || M > 4096) return fail(RCA_ERR_ARG, "score_rows_tap: M = %d outside [1, 4096]", M);
+    for (int i = 0; i < M; ++i)
+        if (targets[i] < -1 || targets[i] >= V) return fail(RCA_ERR_ARG, "score_rows_tap: target %d at index %d is neither -1 nor inside the vocabulary [0, %d)", targets[i], i, V);
+    int rc;
+    if ((rc = lm_settle(h)) != RCA_OK) return rc;
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const size_t nb = (size_t)M * V * 4;
+    float *la = nullptr, *lb = nullptr;
+    int* tg = nullptr;
+    rca_score_row_t* rows = nullptr;
+    hipError_t e = hipSuccess;
+    if ((rc = lm_alloc((void**)&la, nb)) == RCA_OK && (!base_logits_host || (rc = lm_alloc((void**)&lb, nb)) == RCA_OK) &&
+        (rc = lm_alloc((void**)&tg, (size_t)M * 4)) == RCA_OK && (rc = lm_alloc((void**)&rows, (size_t)M * sizeof(rca_score_row_t))) == RCA_OK) {
+        e = hipMemcpyAsync(la, logits_host, nb, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && lb) e = hipMemcpyAsync(lb, base_logits_host, nb, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(tg, targets, (size_t)M * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            lm_launch_score_rows(la, lb, V, tg, rows, M, st);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(rows_host, rows, (size_t)M * sizeof(rca_score_row_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    for (void* p : {(void*)la, (void*)lb, (void*)tg, (void*)rows})
+        if (p) (void)hipFree(p);
+    if (rc != RCA_OK) return rc;
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "score_rows_tap: %s", hipGetErrorString(e));
     return RCA_OK;
 }

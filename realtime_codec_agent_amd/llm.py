@@ -406,8 +406,66 @@ class LlamaForAlternatingCodeChannels:
         shifted = logits - mx
         return shifted - np.log(np.sum(np.exp(shifted), axis=axis, keepdims=True))
 
-    def get_logprobs(self, ctx_input_ids, input_ids):
-        """llamacpp_utils.py:30-37: log p(input_ids[i] | ctx, input_ids[:i]) on a logits_all handle."""
+    def score(self, tokens: Sequence[int], targets: Optional[Sequence[int]] = None,
+              base: Optional["LlamaForAlternatingCodeChannels"] = None) -> "ScoreResult":
+        """Append `tokens` at n_tokens like a long eval and reduce every position's logits ON THE DEVICE (rca_lm_score): what
+        llama-perplexity and its --kl-divergence mode compute.  targets[i] is the token scored at position i (-1 = not scored: its
+        logprob is NaN); None = the next token of `tokens`, the last position unscored.  base: a second handle (any weight format, or
+        a twin of this one) at the same n_tokens, advanced over the same tokens; the result then carries KL(P_base || P), the base's
+        logprob and its top-1 token per position.  The last position's logits are left as after eval()."""
+        tokens = list(tokens)
+        n = len(tokens)
+        rows = np.zeros(n, N.SCORE_ROW_DTYPE)
+        if n == 0:
+            return ScoreResult(rows, base is not None)
+        if targets is not None and len(targets) != n:
+            raise ValueError(f"score: {len(targets)} targets for {n} tokens")
+        n0 = self.n_tokens
+        arr = (C.c_int32 * n)(*tokens)
+        tg = (C.c_int32 * n)(*[int(t) for t in targets]) if targets is not None else None
+        N.check(self._lib.rca_lm_score(self._h, base._h if base is not None else None, arr, n, tg,
+                                       rows.ctypes.data_as(C.POINTER(N.ScoreRowC))), "rca_lm_score")
+        for llm in (self, base):
+            if llm is not None:
+                llm._input_ids[n0:n0 + n] = tokens
+                llm._logits_valid = False
+        return ScoreResult(rows, base is not None)
+
+    def score_rows_tap(self, logits: np.ndarray, targets: Sequence[int], base_logits: Optional[np.ndarray] = None) -> "ScoreResult":
+        """Tests only (rca_lm_score_rows_tap): the row reduction of score() alone on host-supplied logits [M, n_vocab]."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        if logits.ndim != 2 or logits.shape[1] != self._n_vocab:
+            raise ValueError(f"score_rows_tap: rows have {self._n_vocab} logits, got {logits.shape}")
+        M = logits.shape[0]
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        if base_logits is not None:
+            base_logits = np.ascontiguousarray(base_logits, dtype=np.float32)
+            if base_logits.shape != logits.shape:
+                raise ValueError(f"score_rows_tap: base rows {base_logits.shape} against {logits.shape}")
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        if tg.shape != (M,):
+            raise ValueError(f"score_rows_tap: {tg.shape} targets for {M} rows")
+        rows = np.zeros(M, N.SCORE_ROW_DTYPE)
+        N.check(self._lib.rca_lm_score_rows_tap(self._h, fp(logits), fp(base_logits) if base_logits is not None else None,
+                                                tg.ctypes.data_as(C.POINTER(C.c_int32)), M, rows.ctypes.data_as(C.POINTER(N.ScoreRowC))),
+                "rca_lm_score_rows_tap")
+        return ScoreResult(rows, base_logits is not None)
+
+    def get_logprobs(self, ctx_input_ids, input_ids, route: str = "decode"):
+        """llamacpp_utils.py:30-37: log p(input_ids[i] | ctx, input_ids[:i]) on a logits_all handle.
+        route="prefill" (opt-in: the prefill tiles round differently from the decode passes) evaluates the context with eval() and
+        the scored tokens with score(): no logits_all handle needed, no logits on the host."""
+        if route not in ("decode", "prefill"):
+            raise ValueError(f"get_logprobs: route {route!r} is neither 'decode' nor 'prefill'")
+        if route == "prefill":
+            ctx_input_ids, input_ids = list(ctx_input_ids), list(input_ids)
+            if not ctx_input_ids:
+                raise ValueError("get_logprobs: the context holds no token to predict input_ids[0] from")
+            if not input_ids:
+                return np.zeros(0, np.float32)
+            self.reset()
+            self.eval(ctx_input_ids[:-1])
+            return self.score(ctx_input_ids[-1:] + input_ids[:-1], targets=input_ids).logprob
         if not self._logits_all:
             raise N.RcaError("get_logprobs needs a handle created with logits_all=True")
         self.reset()
@@ -735,6 +793,23 @@ class LlamaForAlternatingCodeChannels:
 
     def set_graphs(self, enable: bool) -> None:
         N.check(self._lib.rca_lm_set_graphs(self._h, 1 if enable else 0), "rca_lm_set_graphs")
+
+
+class ScoreResult:
+    """What score() returns: one numpy array per field of rca_score_row_t, one entry per position.  logprob / lse / max_logit /
+    argmax of the scored handle; with a base also kl = KL(P_base || P), base_logprob and base_argmax (None without one).
+    flags: bit 0 a NaN in the row, bit 1 a NaN in the base's row, bit 2 kl = +inf."""
+
+    def __init__(self, rows: np.ndarray, has_base: bool):
+        self.rows = rows
+        self.logprob, self.lse, self.max_logit = rows["logprob"].copy(), rows["lse"].copy(), rows["max_logit"].copy()
+        self.argmax, self.flags = rows["argmax"].copy(), rows["flags"].copy()
+        self.kl = rows["kl"].copy() if has_base else None
+        self.base_logprob = rows["base_logprob"].copy() if has_base else None
+        self.base_argmax = rows["base_argmax"].copy() if has_base else None
+
+    def __len__(self) -> int:
+        return len(self.rows)
 
 
 class _LogitBiasProcessorList(list):
