@@ -437,6 +437,31 @@ int rca_lm_sample(rca_lm_t* h, int32_t* token);
 /* next(generate(tokens, reset=False)) (llamacpp_utils.py:145-161; realtime_agent_v2.py:355):
  * eval + sample with no host round trip in between; hipGraph-replayed for n<=2 */
 int rca_lm_step(rca_lm_t* h, const int32_t* ids, int32_t n, int32_t* token);
+/* Group step: several sessions over ONE set of weights advance together, every weight matrix streamed once for all of them.  The
+ * reference's self-play runs two agents on one card by loading the GGUF twice and stepping each model on its own
+ * (inference_client_self_play.py:148-159: two weight streams per frame); llama.cpp knows the capability as parallel sequences
+ * (n_seq_max, llama-server -np: several sequences in one llama_decode).
+ * rca_lm_group_create: a group over 2 to 4 existing handles.  RCA_ERR_ARG, with a message naming the member, when two members are
+ *   the same handle, a member is on another device than member 0, does not share member 0's weights (the parent and its
+ *   rca_lm_create_shared twins do), has another activation format (rca_lm_set_act_format), or is a logits_all handle.  Every weight format
+ *   and both activation formats of the single step have their four-row GEMV instances.  The group holds no state of its members beyond pointers: the members live
+ *   on, and the group is destroyed BEFORE any of them.
+ * rca_lm_group_step: ids [n_members][n], tokens [n_members].  Member s evaluates ids[s * n .. s * n + n) at ITS n_tokens and samples
+ *   with ITS sampler; n_members * n is 2 or 4 (2 x 1, 2 x 2 -- the duplex pair step of two sessions -- or 4 x 1).  Afterwards every
+ *   member is in exactly the state rca_lm_step(member, its ids, n, &tokens[s]) would have left, bit for bit: n_tokens += n, its KV
+ *   rows written, its last logits where rca_lm_get_logits / rca_lm_token_probs / rca_lm_sample / rca_lm_logits_dev find them, its
+ *   draw counter, penalty window and sampled token advanced.  Single-handle calls and group steps may be interleaved freely.
+ *   Pending rca_lm_eval_async work of a member is waited for first.  Refused before anything is enqueued, with NO member changed:
+ *   another row count (RCA_ERR_ARG), an id outside the vocabulary (RCA_ERR_ARG), a member without a sampler, a member switched to
+ *   logits_all or to another activation format since the group was made, and a context overflow of ANY member (all RCA_ERR_STATE).
+ *   The pass runs on member 0's stream, in member 0's activation workspace, and ends with one synchronisation and one download of
+ *   the tokens; with graphs enabled on every member it is one replay, captured per (n, largest context bucket among the members)
+ *   and re-captured when a member's captured state changes (rca_lm_swap_kv, a sampler of another kind, rca_lm_set_act_format, ...);
+ *   rca_lm_set_graphs(member, 0) on any member makes it eager. */
+typedef struct rca_lm_group rca_lm_group_t;
+int rca_lm_group_create(rca_lm_t* const* members, int32_t n_members, rca_lm_group_t** out);
+int rca_lm_group_destroy(rca_lm_group_t* g);
+int rca_lm_group_step(rca_lm_group_t* g, const int32_t* ids, int32_t n, int32_t* tokens);
 /* One whole frame of process_audio_input_ids (realtime_agent_v2.py:332-372) as ONE hipGraph: n_steps (<= 8) S=2 steps, the
  * agent token sampled by step i fed back on the device together with user_ids[i] as step i+1's input pair; first_pair is the
  * pair step 0 evaluates (the last two ids of the sequence).  out_tokens[i] = token sampled by step i.  *n_done = number of steps

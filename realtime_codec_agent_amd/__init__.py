@@ -13,6 +13,7 @@ _LAZY = {
     "RealtimeAgentV2": ".realtime_agent_v2",
     "RealtimeAgentMultiprocessing": ".realtime_agent_v2",
     "LlamaForAlternatingCodeChannels": ".llm",
+    "LlamaGroup": ".llm",
     "MagiCodecHIP": ".codec",
     "HipCodec": ".codec",
     "CodecConfig": ".codec_model",

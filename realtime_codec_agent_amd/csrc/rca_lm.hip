@@ -384,7 +384,11 @@ __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, lon
 constexpr bool wf_packed(int fmt) { return fmt == WF_Q8 || fmt == WF_Q4K || fmt == WF_Q6K || fmt == WF_Q5K || fmt == WF_Q40 || fmt == WF_Q41; }
 // minimum waves per SIMD asked of the register allocator.  The q8_0 bodies otherwise spread over 200+ registers (one wave per
 // SIMD) although their live set is ~130: a streaming kernel wants the occupancy.
-constexpr int gemv_min_waves(int Q, int R, int NIT) { return (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K && Q != WF_Q40) ? 1 : (R * NIT >= 16 ? 2 : 4); }
+constexpr int gemv_min_waves(int Q, int R, int NIT, int M = 2) {
+    if (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K && Q != WF_Q40) return 1;
+    if (M == 4 && NIT == 4) return 1;   // four rows x four chunks: 128 x values per lane beside the batch (group steps, wide FFN)
+    return R * NIT >= 16 ? 2 : 4;
+}
 // ACT = 1 (rca_lm_set_act_format, packed formats only): the activations are quantised to q8_1 blocks -- 32 consecutive values, int8 +
 // one scale, ggml's quantize_row_q8_1 restated: d = amax / 127, inv = d != 0 ? 1 / d : 0 (IEEE division), q = roundf(x * inv), scale used
 // d_x = (float)(fp16 rne of d) -- and the products run on the signed byte dot (v_dot4c_i32_i8), llama.cpp's GPU mat-vec class:
@@ -394,12 +398,29 @@ constexpr int gemv_min_waves(int Q, int R, int NIT) { return (Q != WF_Q8 && Q !=
 // quantiser runs INSIDE the GEMV (after the RMSNorm with PRO 1), once per workgroup, on the 8 * NIT * M values the lane holds anyway:
 // the four chunks of a block sit in four consecutive lanes of one `it`, so amax is two quad DPP exchanges.  For that a wave's chunk
 // range starts on a block boundary: cpw is rounded up to a multiple of 4 (K = 192: 8 / 8 / 8 / 0 chunks instead of 6 / 6 / 6 / 6).
-template <int M, int NIT, int R, int PRO, int EPI, int Q = 0, int ACT = 0>
-__global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel(const LmDevState* __restrict__ stt, const bf16_t* __restrict__ W, GemvQ8 q8,
-                                                      const float* __restrict__ x, int N, int K, float* __restrict__ y,
-                                                      int batches_per_wg, int ldy, GemvPro pro, GemvRope rope) {
-    // (argument order: the weight pointers of either form, x, N, K -- what the first loads need -- are the 14 dwords the dispatcher
-    //  preloads into SGPRs)
+// GRP = 1 (rca_lm_group_step): the M rows of the pass belong to DIFFERENT sessions that share the weights.  Whatever the body reads
+// from the step state of "the" handle -- the KV position and cache of a row (EPI 2), which row of x is a session's last token and
+// where its logits go (PRO 1 + EPI 0, the head) -- comes per row from a small device table instead; `stt` is not read.  The
+// arithmetic of a row is untouched, so a row comes out with the bits its own session's pass would have given it.  The body is shared
+// and always inlined: the GRP = 0 kernels below are, instruction for instruction, what they were before the table existed.
+struct LmGroupRow {
+    LmDevState* stt;         // the row's session: n_tokens = KV position of ITS first token of the pass
+    f16_t* kc; f16_t* vc;    // that session's KV cache (layer 0) and its layer stride in elements
+    float* dst;              // head rows: the session's logits buffer
+    long kv_stride;
+    int j;                   // index of the row inside its session's tokens of the pass
+    int xrow;                // row of the activation buffer the slot reads (QKV: the slot itself; head: the session's last token)
+    int n_ctx;
+    int pad;
+};
+struct GemvGroup {
+    const LmGroupRow* rows; int layer;
+};
+template <int M, int NIT, int R, int PRO, int EPI, int Q, int ACT, int GRP>
+__device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt, const bf16_t* __restrict__ W, const GemvQ8& q8,
+                                             const float* __restrict__ x, int N, int K, float* __restrict__ y,
+                                             int batches_per_wg, int ldy, const GemvPro& pro, const GemvRope& rope, const GemvGroup& grp) {
+    static_assert(!GRP || (PRO == 1 && (EPI == 0 || EPI == 2)), "only the QKV projection and the head read per-session state");
     constexpr int V = R * M;
     static_assert(V % 4 == 0 && R % 2 == 0, "R * M must be a multiple of 4");
     __shared__ float kred[2][4][V];
@@ -532,7 +553,7 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
     float nw[PRO == 1 ? NIT : 1][8];
     {
         int mbase = 0;
-        if (PRO == 1 && pro.only_last) mbase = stt->m - 1;
+        if (!GRP && PRO == 1 && pro.only_last) mbase = stt->m - 1;
         const float* xsrc = PRO == 1 ? pro.xin : x;
 #pragma unroll
         for (int m = 0; m < M; ++m)
@@ -540,7 +561,7 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
             for (int it = 0; it < NIT; ++it) {
                 const int c = lane + 64 * it;
                 if (c < cn) {
-                    const float* p = xsrc + (long)(mbase + m) * K + (long)(c0 + c) * 8;
+                    const float* p = xsrc + (long)(GRP ? grp.rows[m].xrow : mbase + m) * K + (long)(c0 + c) * 8;
                     const float4 a = *reinterpret_cast<const float4*>(p);
                     const float4 b = *reinterpret_cast<const float4*>(p + 4);
                     xr[m][it][0] = a.x; xr[m][it][1] = a.y; xr[m][it][2] = a.z; xr[m][it][3] = a.w;
@@ -595,7 +616,21 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
         }
     }
     int pos0 = 0;
-    if (EPI == 2) pos0 = stt->n_tokens;
+    if (!GRP && EPI == 2) pos0 = stt->n_tokens;
+    // grouped QKV: the epilogue thread of (row m, pair s) takes position, cache and context bound of row m's session
+    int g_pos = 0, g_nctx = 0;
+    f16_t *g_kc = nullptr, *g_vc = nullptr;
+    float* g_dst = nullptr;
+    if constexpr (GRP != 0) {
+        if (EPI == 2 && tid < V / 2) {
+            const LmGroupRow rw = grp.rows[tid / (R / 2)];
+            g_pos = rw.stt->n_tokens + rw.j;
+            g_nctx = rw.n_ctx;
+            g_kc = rw.kc + (long)grp.layer * rw.kv_stride;
+            g_vc = rw.vc + (long)grp.layer * rw.kv_stride;
+        }
+        if (EPI == 0 && tid < V) g_dst = grp.rows[tid / R].dst;
+    }
     // q8_1 activations: this lane's chunks as int8 (two dwords; Q4_K: elements 0 2 4 6 / 1 3 5 7, the order its nibbles unpack in),
     // the block's fp16-rounded scale, and for Q4_K d_x * sum(q_x) of the chunk (the minimum term)
     unsigned xq[QA ? M : 1][QA ? NIT : 1][2];
@@ -789,7 +824,7 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
         if (EPI == 2 && tid < V / 2) {
             const int m = tid / (R / 2), s = tid % (R / 2);
             const int d = (b * (R / 2) + s) & 31;
-            const long pos = min(pos0 + m, rope.n_ctx - 1);
+            const long pos = GRP ? min(g_pos, g_nctx - 1) : min(pos0 + m, rope.n_ctx - 1);
             cs = rope.cos_t[pos * 32 + d];
             sn = rope.sin_t[pos * 32 + d];
         }
@@ -826,7 +861,8 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
         if (EPI == 0 || EPI == 3) {
             if (tid < V) {
                 const int m = tid / R, row = row_of(b, tid % R);
-                if (row < N) y[(long)m * ldy + row] = EPI == 3 ? yv + total(tid) : total(tid);
+                if (GRP) { if (row < N) g_dst[row] = total(tid); }
+                else if (row < N) y[(long)m * ldy + row] = EPI == 3 ? yv + total(tid) : total(tid);
             }
         } else if (EPI == 1) {
             if (tid < V / 2) {
@@ -842,8 +878,10 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
                 const int m = tid / (R / 2), s = tid % (R / 2);
                 const int rl = row_of(b, 2 * s);             // row inside this matrix
                 const int r0 = rl + rope.row_base;           // row inside [q; k; v]
-                const int pos = pos0 + m;
-                if (rl + 32 < N && pos < rope.n_ctx) {
+                const int pos = GRP ? g_pos : pos0 + m;
+                f16_t* const kcache = GRP ? g_kc : rope.kc;
+                f16_t* const vcache = GRP ? g_vc : rope.vc;
+                if (rl + 32 < N && pos < (GRP ? g_nctx : rope.n_ctx)) {
                     const float x1 = total(m * R + 2 * s), x2 = total(m * R + 2 * s + 1);
                     const int head = r0 >> 6, d = r0 & 63;   // d < 32
                     if (head < rope.nh + rope.nkv) {
@@ -853,12 +891,12 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
                             y[(long)m * ldy + r0] = o1;
                             y[(long)m * ldy + r0 + 32] = o2;
                         } else {
-                            f16_t* kp = rope.kc + ((long)pos * rope.nkv + (head - rope.nh)) * 64;
+                            f16_t* kp = kcache + ((long)pos * rope.nkv + (head - rope.nh)) * 64;
                             kp[d] = (f16_t)o1;
                             kp[d + 32] = (f16_t)o2;
                         }
                     } else {
-                        f16_t* vp = rope.vc + ((long)pos * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
+                        f16_t* vp = vcache + ((long)pos * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
                         vp[d] = (f16_t)x1;
                         vp[d + 32] = (f16_t)x2;
                     }
@@ -868,6 +906,21 @@ __global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT)) void lm_gemv_kernel
     };
     for (int b = b_beg; b + 1 < b_end; ++b) run_batch(b, std::true_type{});
     run_batch(b_end - 1, std::false_type{});
+}
+template <int M, int NIT, int R, int PRO, int EPI, int Q = 0, int ACT = 0>
+__global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT, M)) void lm_gemv_kernel(const LmDevState* __restrict__ stt, const bf16_t* __restrict__ W, GemvQ8 q8,
+                                                      const float* __restrict__ x, int N, int K, float* __restrict__ y,
+                                                      int batches_per_wg, int ldy, GemvPro pro, GemvRope rope) {
+    // (argument order: the weight pointers of either form, x, N, K -- what the first loads need -- are the 14 dwords the dispatcher
+    //  preloads into SGPRs)
+    lm_gemv_body<M, NIT, R, PRO, EPI, Q, ACT, 0>(stt, W, q8, x, N, K, y, batches_per_wg, ldy, pro, rope, GemvGroup{nullptr, 0});
+}
+// the grouped QKV projection and head: the same first 14 dwords, the row table behind everything else
+template <int M, int NIT, int R, int PRO, int EPI, int Q = 0, int ACT = 0>
+__global__ __launch_bounds__(256, gemv_min_waves(Q, R, NIT, M)) void lm_gemv_group_kernel(const LmDevState* __restrict__ stt, const bf16_t* __restrict__ W, GemvQ8 q8,
+                                                      const float* __restrict__ x, int N, int K, float* __restrict__ y,
+                                                      int batches_per_wg, int ldy, GemvPro pro, GemvRope rope, GemvGroup grp) {
+    lm_gemv_body<M, NIT, R, PRO, EPI, Q, ACT, 1>(stt, W, q8, x, N, K, y, batches_per_wg, ldy, pro, rope, grp);
 }
 
 
@@ -2155,6 +2208,8 @@ struct rca_lm {
     bool async_pending = false;   // an rca_lm_eval_async pass may still be running on the stream
     unsigned long long rng_host = 0;   // host mirror of the device's draw counter (restored when a frame graph is cut short)
     bool graphs_enabled = true;
+    unsigned long long graph_epoch = 0;   // bumped by whatever invalidates graphs captured over this handle (lm_drop_graphs, rca_lm_swap_kv): a group
+                                          // (rca_lm_group_step) holds graphs over SEVERAL handles and compares before it replays one
     bool mfma_prefill = true;   // evals longer than LM_PREFILL_MIN tokens use the bf16 MFMA tiles
     bool fuse_attn = true;      // decode steps merge the attention splits inside the attention launch (rca_lm_set_attn_fuse)
     int act_format = 0;         // activations of the decode GEMVs over packed matrices: 0 f32, 1 q8_1 blocks + integer dots (rca_lm_set_act_format)
@@ -2215,6 +2270,7 @@ static void lm_drop_graph_set(rca_lm::GraphSet& gs) {
     gs.kc = nullptr;
 }
 static void lm_drop_graphs(rca_lm* h) {
+    h->graph_epoch++;
     for (auto& gs : h->gset) lm_drop_graph_set(gs);
     duplex_drop_graphs(h->duplex);
 }
@@ -3010,55 +3066,91 @@ static GemvGeom gemv_geom(int kind, int N, bool q8) {
     while (g.bpw > 1 && (N + g.R * g.bpw - 1) / (g.R * g.bpw) < 64) g.bpw >>= 1;
     return g;
 }
-template <int M, int NIT, int PRO, int EPI, int Q, int ACT>
+// M = 4 (the group step's rows) costs registers per weight row in flight: 4 R sums and 32 NIT x values per lane.  gemv_group_r lowers R
+// until R * NIT <= 16 (the 4-bit forms and Q6_K keep their minimum of 8), and the packed instances with four chunks per lane (the down
+// projection of a wide FFN: 128 x values) ask the allocator for one wave per SIMD instead of two (gemv_min_waves).  With that every
+// format has its M = 4 instances and none of them uses scratch: profiles/r13/gemv_m4_registers.txt.
+constexpr bool gemv_built(int M, int NIT, int R, int Q) {
+    // Q5_K / Q4_0 at NIT = 4: launch_gemv_q never leaves R = 16 (four quads x four chunks = 16 loads, twice its limit), and the
+    // instance would not fit the register file (it spills): not built
+    if ((Q == WF_Q5K || Q == WF_Q40) && NIT == 4 && R == 16) return false;
+    if (M == 4) {   // what gemv_group_r never asks for is not built
+        const bool min8 = Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40 || Q == WF_Q6K;
+        if (min8 ? (R == 4 || (R == 16 && NIT > 1)) : R * NIT > 16) return false;
+    }
+    return true;
+}
+template <int M, int NIT, int PRO, int EPI, int Q, int ACT, int GRP = 0>
 static void launch_gemv_r(const GemvGeom& g, rca_lm* h, const WMat& w, const float* x, float* y, int N, int K, int ldy, const GemvPro& pro,
-                          const GemvRope& rope, hipStream_t st) {
+                          const GemvRope& rope, hipStream_t st, const GemvGroup& grp = GemvGroup{nullptr, 0}) {
     const int grid = cdiv(cdiv(N, g.R), g.bpw);
     const GemvQ8 qa{w.qs, w.sc, w.dd};
+    auto go = [&](auto rr) {
+        constexpr int R = decltype(rr)::value;
+        if constexpr (gemv_built(M, NIT, R, Q)) {
+            if constexpr (GRP != 0) lm_gemv_group_kernel<M, NIT, R, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(nullptr, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope, grp);
+            else lm_gemv_kernel<M, NIT, R, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope);
+        }
+    };
     switch (g.R) {
-        case 4: lm_gemv_kernel<M, NIT, 4, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
-        case 8: lm_gemv_kernel<M, NIT, 8, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope); break;
-        default:
-            // Q5_K / Q4_0 at NIT = 4: launch_gemv_q never leaves R = 16 (four quads x four chunks = 16 loads, twice its limit), and the
-            // instance would not fit the register file (it spills): not built
-            if constexpr (!((Q == WF_Q5K || Q == WF_Q40) && NIT == 4))
-                lm_gemv_kernel<M, NIT, 16, PRO, EPI, Q, ACT><<<grid, 256, 0, st>>>(h->stt, w.wptr(), qa, x, N, K, y, g.bpw, ldy, pro, rope);
-            break;
+        case 4: go(std::integral_constant<int, 4>{}); break;
+        case 8: go(std::integral_constant<int, 8>{}); break;
+        default: go(std::integral_constant<int, 16>{}); break;
     }
 }
-template <int PRO, int EPI, int Q, int ACT = 0>
+// rows per batch of an M = 4 launch: the geometry of the M <= 2 launch, halved until R * NIT <= 16 (the packed 4-bit forms keep two
+// quads).  Results do not depend on R.
+static int gemv_group_r(int R, int nit_t, bool four_bit) {
+    while (R > (four_bit ? 8 : 4) && R * nit_t > 16) R >>= 1;
+    return R;
+}
+// M = 1, 2 or (group steps) 4 rows; GRP: the rows' sessions come from `grp` (QKV and head only, M = 2 or 4)
+template <int PRO, int EPI, int Q, int ACT = 0, int GRP = 0>
 static void launch_gemv_q(GemvGeom g, rca_lm* h, int M, const WMat& w, const float* x, float* y, int N, int K, int ldy, const GemvPro& pro,
-                          const GemvRope& rope, hipStream_t st) {
+                          const GemvRope& rope, hipStream_t st, const GemvGroup& grp = GemvGroup{nullptr, 0}) {
     const int nit = cdiv(cdiv(K >> 3, 4), 64);
     // 16-byte weight loads in flight per lane: at most 16 (registers); q8_0 needs one load per row PAIR
-    const int lpr = (Q == WF_Q8 || Q == WF_Q6K) ? 2 : ((Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40) ? 4 : 1);
-    const int max_loads = (Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40) ? 8 : 16;   // Q4_K / Q5_K / Q4_0 also hold the factors of every quad in registers
+    constexpr bool four_bit = Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40;
+    const int lpr = (Q == WF_Q8 || Q == WF_Q6K) ? 2 : (four_bit ? 4 : 1);
+    const int max_loads = four_bit ? 8 : 16;   // Q4_K / Q5_K / Q4_0 also hold the factors of every quad in registers
     while (g.R > 4 && (g.R / lpr) * (nit == 3 ? 4 : nit) > max_loads) g.R >>= 1;
-    if ((Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K || Q == WF_Q40) && g.R < 8) g.R = 8;   // a Q4_K batch is at least two quads (one per register half); Q6_K scale loads cover two pairs
+    if ((four_bit || Q == WF_Q6K) && g.R < 8) g.R = 8;   // a Q4_K batch is at least two quads (one per register half); Q6_K scale loads cover two pairs
+    if (M == 4) g.R = gemv_group_r(g.R, nit == 3 ? 4 : nit, four_bit || Q == WF_Q6K);
     if (PRO == 0 && EPI == 3 && nit > 1) {
-        if (nit == 2) {
-            if (M == 1) launch_gemv_r<1, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
-            else launch_gemv_r<2, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
-        } else {
-            if (M == 1) launch_gemv_r<1, 4, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
-            else launch_gemv_r<2, 4, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+        if constexpr (GRP == 0) {
+            if (nit == 2) {
+                if (M == 1) launch_gemv_r<1, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+                else if (M == 2) launch_gemv_r<2, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+                else launch_gemv_r<4, 2, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+            } else {
+                if (M == 1) launch_gemv_r<1, 4, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+                else if (M == 2) launch_gemv_r<2, 4, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+                else launch_gemv_r<4, 4, 0, 3, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+            }
         }
         return;
     }
-    if (M == 1) launch_gemv_r<1, 1, PRO, EPI, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
-    else launch_gemv_r<2, 1, PRO, EPI, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+    if constexpr (GRP != 0) {
+        if (M == 2) launch_gemv_r<2, 1, PRO, EPI, Q, ACT, 1>(g, h, w, x, y, N, K, ldy, pro, rope, st, grp);
+        else launch_gemv_r<4, 1, PRO, EPI, Q, ACT, 1>(g, h, w, x, y, N, K, ldy, pro, rope, st, grp);
+    } else {
+        if (M == 1) launch_gemv_r<1, 1, PRO, EPI, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+        else if (M == 2) launch_gemv_r<2, 1, PRO, EPI, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+        else if constexpr (!(PRO == 1 && (EPI == 0 || EPI == 2)))   // four rows of ONE session do not exist: QKV and head at M = 4 are grouped launches
+            launch_gemv_r<4, 1, PRO, EPI, Q, ACT>(g, h, w, x, y, N, K, ldy, pro, rope, st);
+    }
 }
-// M = 1 or 2 tokens.  Only the down projection (K = ffn) needs more than one chunk per lane and wave.  The matrix is streamed in the
-// format it is kept in.
-template <int PRO, int EPI>
+// M = 1 or 2 tokens of one session, or the 2 / 4 rows of a group step.  Only the down projection (K = ffn) needs more than one chunk per
+// lane and wave.  The matrix is streamed in the format it is kept in.
+template <int PRO, int EPI, int GRP = 0>
 static void launch_gemv(int kind, rca_lm* h, int M, const WMat& w, const float* x, float* y, int N, int K, int ldy, const GemvPro& pro,
-                        const GemvRope& rope, hipStream_t st) {
+                        const GemvRope& rope, hipStream_t st, const GemvGroup& grp = GemvGroup{nullptr, 0}) {
     const GemvGeom g = gemv_geom(kind, N, wf_packed(w.fmt));
     wf_dispatch(w.fmt, [&](auto wf) {
         constexpr int Q = decltype(wf)::value;
         if constexpr (wf_packed(Q))   // q8_1 activations on the integer dot (rca_lm_set_act_format); 16-bit matrices keep f32 activations
-            if (h->act_format == 1) return launch_gemv_q<PRO, EPI, Q, 1>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
-        launch_gemv_q<PRO, EPI, Q>(g, h, M, w, x, y, N, K, ldy, pro, rope, st);
+            if (h->act_format == 1) return launch_gemv_q<PRO, EPI, Q, 1, GRP>(g, h, M, w, x, y, N, K, ldy, pro, rope, st, grp);
+        launch_gemv_q<PRO, EPI, Q, 0, GRP>(g, h, M, w, x, y, N, K, ldy, pro, rope, st, grp);
     });
 }
 
@@ -3898,7 +3990,9 @@ static void launch_attention_flash(rca_lm* h, int M, const f16_t* kc, const f16_
 }
 
 // split attention on MFMA + merge of the splits, for the M tokens of the current pass
-static void launch_attention_mfma(rca_lm* h, int M, int nsp_launch, const f16_t* kc, const f16_t* vc, hipStream_t st,
+// qkv / attn: the M query rows and where their outputs go -- the handle's own buffers for its own passes, the rows of ONE member inside the
+// shared buffers of a group step (the flash route, prefill only, reads the handle's)
+static void launch_attention_mfma(rca_lm* h, int M, int nsp_launch, const f16_t* kc, const f16_t* vc, const float* qkv, float* attn, hipStream_t st,
                                   bf16_t* hi = nullptr, bf16_t* lo = nullptr, bool prefill = false) {
     const rca_lm_config_t& c = h->cfg;
     static const bool flash = !(getenv("RCA_LM_FLASH") && atoi(getenv("RCA_LM_FLASH")) == 0);   // 0: A/B runs against the split kernel
@@ -3921,9 +4015,9 @@ static void launch_attention_mfma(rca_lm* h, int M, int nsp_launch, const f16_t*
     const bool fuse = h->fuse_attn && !hi && agm.z == 1 && c.n_kv_heads * nsp_launch <= 256 && M * G <= 8 && nsp_launch <= ATT_TAG_MAXSP && c.n_kv_heads <= ATT_EPOCH_INTS;
     int* arrive = fuse ? h->att_arrive : nullptr;
 #define RCA_ATTN_LAUNCH(GG)                                                                                                                        \
-    lm_attn_mfma_kernel<GG><<<agm, 512, ATTM_LDS, st>>>(h->stt, h->qkv, kc, vc, c.n_heads, c.n_kv_heads, h->n_splits, scale, c.n_ctx, h->att_part, \
-                                                        arrive, h->attn);                                                                          \
-    if (!fuse) lm_attn_mfma_combine_kernel<GG><<<M * c.n_heads, 64, 0, st>>>(h->stt, h->att_part, h->attn, c.n_heads, c.n_kv_heads, h->n_splits, nsp_launch, hi, lo);
+    lm_attn_mfma_kernel<GG><<<agm, 512, ATTM_LDS, st>>>(h->stt, qkv, kc, vc, c.n_heads, c.n_kv_heads, h->n_splits, scale, c.n_ctx, h->att_part, \
+                                                        arrive, attn);                                                                             \
+    if (!fuse) lm_attn_mfma_combine_kernel<GG><<<M * c.n_heads, 64, 0, st>>>(h->stt, h->att_part, attn, c.n_heads, c.n_kv_heads, h->n_splits, nsp_launch, hi, lo);
     if (G == 4) { RCA_ATTN_LAUNCH(4) }
     else if (G == 2) { RCA_ATTN_LAUNCH(2) }
     else { RCA_ATTN_LAUNCH(1) }
@@ -3977,7 +4071,7 @@ static int lm_enqueue_pass(rca_lm* h, int M, int want_logits, hipStream_t st, in
     if (!skip_embed) lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, h->x, c.hidden, c.vocab_size);   // (inside a frame graph the previous step's sampler has gathered the rows)
     for (int l = 0; l < c.n_layers; ++l) {
         lm_launch_qkv(h, l, M, st);
-        launch_attention_mfma(h, M, nsp_launch, h->kc + (long)l * h->kv_layer_stride, h->vc + (long)l * h->kv_layer_stride, st);
+        launch_attention_mfma(h, M, nsp_launch, h->kc + (long)l * h->kv_layer_stride, h->vc + (long)l * h->kv_layer_stride, h->qkv, h->attn, st);
         lm_launch_o(h, l, M, st);
         lm_launch_gu(h, l, M, st);
         lm_launch_down(h, l, M, st);
@@ -4431,7 +4525,7 @@ static int lm_enqueue_prefill_tile(rca_lm* h, int M, hipStream_t st, int nsp_lau
         lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.attn_norm, h->xn, H, c.rms_eps);
         lm_split_bf16_kernel<<<dim3(cdiv(H, 256), M), 256, 0, st>>>(h->stt, h->xn, h->xh, h->xl, H);
         lm_gemm_mfma_kernel<GEMM_EPI_ROPE><<<QKV / 32, 256, 0, st>>>(h->stt, L.qkv.w, h->xh, h->xl, QKV, H, h->qkv, QKV, nullptr, nullptr, rope);
-        launch_attention_mfma(h, M, nsp_launch, kc, vc, st, nullptr, nullptr, true);
+        launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, nullptr, nullptr, true);
         lm_split_bf16_kernel<<<dim3(cdiv(AO, 256), M), 256, 0, st>>>(h->stt, h->attn, h->xh, h->xl, AO);
         lm_gemm_mfma_kernel<GEMM_EPI_RESID><<<H / 32, 256, 0, st>>>(h->stt, L.o.w, h->xh, h->xl, H, AO, x, H, nullptr, nullptr, norope);
         lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.ffn_norm, h->xn, H, c.rms_eps);
@@ -4523,7 +4617,7 @@ static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_
             if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE><<<dim3(Ns / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fq.ep_nsplit, fq.ep_grp, Ns, h->qkv, QKV, nullptr, nullptr, rope);
         }
         rope.row_base = 0;
-        launch_attention_mfma(h, M, nsp_launch, kc, vc, st, h->xh, h->xl, true);
+        launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, h->xh, h->xl, true);
         launch_gemm128<GEMM_EPI_RESID>(h, L.o, dim3(H / 128, fo.grid_y, tbz), st, h->xh, h->xl, H, AO, AO / so, x, H, nullptr, nullptr, norope, fo.nseq);
         if (fo.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fo.ep_nsplit, fo.ep_grp, H, x, H, nullptr, nullptr, norope);
         lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.ffn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
@@ -4740,6 +4834,8 @@ extern "C" int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b) {
     a->async_pending = b->async_pending = false;
     std::swap(a->kc, b->kc);
     std::swap(a->vc, b->vc);
+    a->graph_epoch++;   // the handles' own graph sets are keyed by the cache; a group's graphs over either handle are not
+    b->graph_epoch++;
     return RCA_OK;
 }
 
@@ -5056,6 +5152,211 @@ extern "C" int rca_lm_step(rca_lm_t* h, const int32_t* ids, int32_t n, int32_t* 
 extern "C" int rca_lm_step_probe(rca_lm_t* h, const int32_t* ids, int32_t n, const int32_t* probe_ids, int32_t n_probe, int32_t* token, float* probs_out) {
     if (n_probe < 1) return fail(RCA_ERR_ARG, "step_probe: 1..8 probe ids");
     return lm_step_impl(h, ids, n, probe_ids, n_probe, token, probs_out);
+}
+
+// ------------------------------------------------------------------------------------ group step (rca_lm_group_step)
+// Several sessions over ONE set of weights (rca_lm_create_shared twins) advance by n tokens each in one pass: every projection is one
+// GEMV launch over the n_members * n rows, so a matrix is streamed once whatever the number of sessions (the reference's self-play
+// loads the GGUF twice and streams it twice, inference_client_self_play.py:148-159).  Per-session work -- attention over the
+// session's own cache, its sampler chain -- stays one launch (chain) per member.  The rows live in the FIRST member's activation
+// buffers (x, qkv, attn, hbuf hold nothing between calls) and the pass runs on its stream, as one linear launch sequence.
+#define LM_GROUP_MAX 4
+struct LmGroupStage { int n_tokens[LM_GROUP_MAX]; int ids[LM_GROUP_MAX][LM_GEMV_M]; };
+struct LmGroupPin { LmGroupStage in; int tokens[LM_GROUP_MAX]; };
+struct rca_lm_group {
+    int n_members = 0;
+    rca_lm* m[LM_GROUP_MAX] = {};
+    // row tables [n - 1][0 .. 3] = the QKV rows (member s, token j) -> row s * n + j, [n - 1][4 .. 7] = the head rows, one per member
+    LmGroupRow* rows = nullptr;        // device, [LM_GEMV_M][2 * LM_GROUP_MAX]
+    bool rows_valid = false;
+    unsigned long long epoch[LM_GROUP_MAX] = {};   // the members' graph epochs the tables and graphs below were made under
+    LmGroupStage* stage = nullptr;     // device copy of pin->in
+    int* tokens = nullptr;             // device: the members' sampled tokens, gathered for one download
+    LmGroupPin* pin = nullptr;         // pinned
+    hipGraphExec_t g[LM_GEMV_M][LM_GRAPH_BUCKETS] = {};   // (n, largest context bucket among the members)
+};
+// the members' step states for this pass: what lm_push_state uploads for one handle, from one staging block
+__global__ void lm_group_stage_kernel(const LmGroupStage* __restrict__ in, const LmGroupRow* __restrict__ head_rows, int n_members, int n) {
+    const int s = threadIdx.x;
+    if (s >= n_members) return;
+    LmDevState* stt = head_rows[s].stt;
+    stt->n_tokens = in->n_tokens[s];
+    stt->m = n;
+    for (int j = 0; j < n; ++j) stt->ids[j] = in->ids[s][j];
+}
+__global__ __launch_bounds__(256) void lm_embed_group_kernel(const LmGroupRow* __restrict__ rows, const void* __restrict__ table, int f32tab,
+                                                             float* __restrict__ x, int H, int V) {
+    const int m = blockIdx.x;
+    int id = rows[m].stt->ids[rows[m].j];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    if (f32tab) {
+        const float* row = reinterpret_cast<const float*>(table) + (long)id * H;
+        for (int h = threadIdx.x; h < H; h += 256) x[(long)m * H + h] = row[h];
+    } else {
+        const bf16_t* row = reinterpret_cast<const bf16_t*>(table) + (long)id * H;
+        for (int h = threadIdx.x; h < H; h += 256) x[(long)m * H + h] = __uint_as_float((unsigned)row[h] << 16);
+    }
+}
+__global__ void lm_group_tokens_kernel(const LmGroupRow* __restrict__ head_rows, int n_members, int* __restrict__ out) {
+    if ((int)threadIdx.x < n_members) out[threadIdx.x] = head_rows[threadIdx.x].stt->out_token;
+}
+static void lm_group_drop_graphs(rca_lm_group* g) {
+    for (auto& per_n : g->g)
+        for (hipGraphExec_t& e : per_n)
+            if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+}
+static const rca_lm* lm_weight_owner(const rca_lm* h) { return h->weights_of ? h->weights_of : h; }
+extern "C" int rca_lm_group_create(rca_lm_t* const* members, int32_t n_members, rca_lm_group_t** out) {
+    if (!members || !out) return fail(RCA_ERR_ARG, "group_create: null argument");
+    if (n_members < 2 || n_members > LM_GROUP_MAX) return fail(RCA_ERR_ARG, "group_create: %d members, a group has 2 to %d", n_members, LM_GROUP_MAX);
+    for (int s = 0; s < n_members; ++s) {
+        const rca_lm* h = members[s];
+        if (!h) return fail(RCA_ERR_ARG, "group_create: member %d is null", s);
+        for (int t = 0; t < s; ++t)
+            if (members[t] == h) return fail(RCA_ERR_ARG, "group_create: member %d is the same handle as member %d", s, t);
+        if (h->device != members[0]->device) return fail(RCA_ERR_ARG, "group_create: member %d is on device %d, member 0 on device %d", s, h->device, members[0]->device);
+        if (lm_weight_owner(h) != lm_weight_owner(members[0]))
+            return fail(RCA_ERR_ARG, "group_create: member %d does not share member 0's weights (rca_lm_create_shared makes handles that do)", s);
+        if (h->act_format != members[0]->act_format)
+            return fail(RCA_ERR_ARG, "group_create: member %d has activation format %d, member 0 has %d", s, h->act_format, members[0]->act_format);
+        if (h->cfg.logits_all) return fail(RCA_ERR_ARG, "group_create: member %d is a logits_all handle (a group step keeps the last position's logits only)", s);
+    }
+    RCA_HIP(hipSetDevice(members[0]->device));
+    rca_lm_group* g = new rca_lm_group();
+    g->n_members = n_members;
+    for (int s = 0; s < n_members; ++s) g->m[s] = members[s];
+    int rc = lm_alloc((void**)&g->rows, sizeof(LmGroupRow) * LM_GEMV_M * 2 * LM_GROUP_MAX);
+    if (rc == RCA_OK) rc = lm_alloc((void**)&g->stage, sizeof(LmGroupStage));
+    if (rc == RCA_OK) rc = lm_alloc((void**)&g->tokens, sizeof(int) * LM_GROUP_MAX);
+    if (rc == RCA_OK && hipHostMalloc((void**)&g->pin, sizeof(LmGroupPin), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "group_create: pinned staging");
+    if (rc != RCA_OK) { rca_lm_group_destroy(g); return rc; }
+    memset(g->pin, 0, sizeof(LmGroupPin));
+    *out = g;
+    return RCA_OK;
+}
+extern "C" int rca_lm_group_destroy(rca_lm_group_t* g) {
+    if (!g) return RCA_OK;
+    lm_group_drop_graphs(g);
+    for (void* p : {(void*)g->rows, (void*)g->stage, (void*)g->tokens})
+        if (p) (void)hipFree(p);
+    if (g->pin) (void)hipHostFree(g->pin);
+    delete g;
+    return RCA_OK;
+}
+// tables + graphs follow the members: a swapped cache, a moved logits buffer or another sampler chain shows as a new epoch
+static int lm_group_refresh(rca_lm_group* g) {
+    bool same = g->rows_valid;
+    for (int s = 0; s < g->n_members; ++s) same = same && g->epoch[s] == g->m[s]->graph_epoch;
+    if (same) return RCA_OK;
+    lm_group_drop_graphs(g);
+    LmGroupRow tab[LM_GEMV_M][2 * LM_GROUP_MAX];
+    memset(tab, 0, sizeof(tab));
+    for (int n = 1; n <= LM_GEMV_M; ++n)
+        for (int s = 0; s < g->n_members; ++s) {
+            rca_lm* h = g->m[s];
+            LmGroupRow r{h->stt, h->kc, h->vc, h->logits, h->kv_layer_stride, 0, 0, h->cfg.n_ctx, 0};
+            r.j = n - 1; r.xrow = s * n + n - 1;
+            tab[n - 1][LM_GROUP_MAX + s] = r;
+            for (int j = 0; j < n && s * n + j < LM_GROUP_MAX; ++j) {
+                r.j = j; r.xrow = s * n + j;
+                tab[n - 1][s * n + j] = r;
+            }
+        }
+    RCA_HIP(hipMemcpy(g->rows, tab, sizeof(tab), hipMemcpyHostToDevice));
+    for (int s = 0; s < g->n_members; ++s) g->epoch[s] = g->m[s]->graph_epoch;
+    g->rows_valid = true;
+    return RCA_OK;
+}
+// upload of the staged states -> embedding -> the layers -> head -> every member's sampler -> download of the tokens, all on `st`
+static int lm_group_enqueue(rca_lm_group* g, int n, int nsp_launch, hipStream_t st) {
+    rca_lm* ws = g->m[0];
+    const rca_lm_config_t& c = ws->cfg;
+    const int NM = g->n_members, MT = NM * n;
+    const int QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim;
+    const LmGroupRow* qrows = g->rows + (size_t)(n - 1) * 2 * LM_GROUP_MAX;
+    const LmGroupRow* hrows = qrows + LM_GROUP_MAX;
+    hipError_t e = hipMemcpyAsync(g->stage, &g->pin->in, sizeof(LmGroupStage), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "group step upload: %s", hipGetErrorString(e));
+    lm_group_stage_kernel<<<1, 64, 0, st>>>(g->stage, hrows, NM, n);
+    lm_embed_group_kernel<<<MT, 256, 0, st>>>(qrows, ws->embed, ws->embed_f32, ws->x, c.hidden, c.vocab_size);
+    for (int l = 0; l < c.n_layers; ++l) {
+        const LmLayer& L = ws->layers[l];
+        const GemvPro pro{ws->x, L.attn_norm, c.rms_eps, 0};
+        GemvRope rope{ws->cos_t, ws->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, 0};   // cache, position and context bound: per row, from the table
+        const GemvGroup grp{qrows, l};
+        launch_gemv<1, 2, 1>(GEMV_QKV, ws, MT, L.qkv, nullptr, ws->qkv, L.qkv.N, c.hidden, QKV, pro, rope, st, grp);
+        if (L.split_v) {
+            rope.row_base = L.qkv.N;
+            launch_gemv<1, 2, 1>(GEMV_QKV, ws, MT, L.vseg, nullptr, ws->qkv, L.vseg.N, c.hidden, QKV, pro, rope, st, grp);
+        }
+        for (int s = 0; s < NM; ++s) {
+            rca_lm* h = g->m[s];
+            launch_attention_mfma(h, n, std::min(nsp_launch, h->n_splits), h->kc + (long)l * h->kv_layer_stride, h->vc + (long)l * h->kv_layer_stride,
+                                  ws->qkv + (long)s * n * QKV, ws->attn + (long)s * n * AO, st);
+        }
+        lm_launch_o(ws, l, MT, st);
+        lm_launch_gu(ws, l, MT, st);
+        lm_launch_down(ws, l, MT, st);
+    }
+    // final RMSNorm + head over the last row of every member, each row's logits straight into its member's buffer
+    launch_gemv<1, 0, 1>(GEMV_HEAD, ws, NM, ws->head, nullptr, nullptr, c.vocab_size, c.hidden, c.vocab_size, GemvPro{ws->x, ws->final_norm, c.rms_eps, 1}, norope, st,
+                         GemvGroup{hrows, 0});
+    for (int s = 0; s < NM; ++s) lm_enqueue_sample(g->m[s], g->m[s]->logits, st);
+    lm_group_tokens_kernel<<<1, 64, 0, st>>>(hrows, NM, g->tokens);
+    RCA_LAUNCH_CHECK();
+    e = hipMemcpyAsync(g->pin->tokens, g->tokens, sizeof(int) * LM_GROUP_MAX, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "group step download: %s", hipGetErrorString(e));
+}
+extern "C" int rca_lm_group_step(rca_lm_group_t* g, const int32_t* ids, int32_t n, int32_t* tokens) {
+    if (!g || !ids || !tokens) return fail(RCA_ERR_ARG, "group_step: null argument");
+    const int NM = g->n_members;
+    if (n < 1 || n > LM_GEMV_M || (NM * n != 2 && NM * n != 4))
+        return fail(RCA_ERR_ARG, "group_step: %d members x %d tokens = %d rows, a group pass has 2 or 4 (2 x 1, 2 x 2 or 4 x 1)", NM, n, NM * n);
+    int rc;
+    for (int s = 0; s < NM; ++s)
+        if ((rc = lm_settle(g->m[s])) != RCA_OK) return rc;
+    // every refusal before anything is staged or enqueued: no member changes
+    for (int s = 0; s < NM; ++s) {
+        const rca_lm* h = g->m[s];
+        if (!h->sampler_set) return fail(RCA_ERR_STATE, "group_step: member %d has no sampler (rca_lm_sampler_init)", s);
+        if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "group_step: member %d was switched to logits_all after the group was made", s);
+        if (h->act_format != g->m[0]->act_format) return fail(RCA_ERR_STATE, "group_step: member %d has activation format %d, member 0 has %d", s, h->act_format, g->m[0]->act_format);
+        if (h->n_tokens + n > h->cfg.n_ctx) return fail(RCA_ERR_STATE, "group_step: context overflow of member %d: %d + %d > n_ctx %d", s, h->n_tokens, n, h->cfg.n_ctx);
+        for (int j = 0; j < n; ++j)
+            if (ids[s * n + j] < 0 || ids[s * n + j] >= h->cfg.vocab_size)
+                return fail(RCA_ERR_ARG, "group_step: token id %d of member %d at index %d is outside the vocabulary [0, %d)", ids[s * n + j], s, j, h->cfg.vocab_size);
+    }
+    RCA_HIP(hipSetDevice(g->m[0]->device));
+    hipStream_t st = g->m[0]->stream;
+    if ((rc = lm_group_refresh(g)) != RCA_OK) return rc;
+    bool graphs = true;
+    int bucket = 0, nsp = 1;
+    for (int s = 0; s < NM; ++s) {
+        const rca_lm* h = g->m[s];
+        graphs = graphs && h->graphs_enabled;
+        g->pin->in.n_tokens[s] = h->n_tokens;
+        for (int j = 0; j < n; ++j) g->pin->in.ids[s][j] = ids[s * n + j];
+        bucket = std::max(bucket, lm_bucket(h, n, -1).bucket);
+        nsp = std::max(nsp, lm_splits_needed(h, n));
+    }
+    if (graphs) {
+        // the split count of the largest bucket among the members (each member's launch is capped at its own cache below)
+        const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? INT_MAX : 4 << bucket;
+        hipGraphExec_t& gexec = g->g[n - 1][bucket];
+        if (!gexec && (rc = lm_capture(st, &gexec, "group step", [&]() -> int { return lm_group_enqueue(g, n, nsp_bucket, st); })) != RCA_OK) return rc;
+        RCA_HIP(hipGraphLaunch(gexec, st));
+    } else if ((rc = lm_group_enqueue(g, n, nsp, st)) != RCA_OK) {
+        return rc;
+    }
+    RCA_HIP(hipStreamSynchronize(st));
+    for (int s = 0; s < NM; ++s) {
+        rca_lm* h = g->m[s];
+        h->n_tokens += n;
+        h->logits_rows = 1;
+        h->rng_host += 1;
+        tokens[s] = g->pin->tokens[s];
+    }
+    return RCA_OK;
 }
 
 // One frame of the duplex loop as ONE graph (process_audio_input_ids, realtime_agent_v2.py:332-372, while every sampled token is an
@@ -5753,9 +6054,9 @@ extern "C" int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_
     }
     const f16_t* kc = h->kc + (long)layer * h->kv_layer_stride;
     const f16_t* vc = h->vc + (long)layer * h->kv_layer_stride;
-    if (route == 0) launch_attention_mfma(h, M, nsp_launch, kc, vc, st);
-    else if (route == 1) launch_attention_mfma(h, M, nsp_launch, kc, vc, st, nullptr, nullptr, true);
-    else launch_attention_mfma(h, M, nsp_launch, kc, vc, st, h->xh, h->xl, true);
+    if (route == 0) launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st);
+    else if (route == 1) launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, nullptr, nullptr, true);
+    else launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, h->xh, h->xl, true);
     hipError_t e = hipGetLastError();
     std::vector<uint16_t> hb;
     if (route == 2) {

@@ -795,6 +795,52 @@ class LlamaForAlternatingCodeChannels:
         N.check(self._lib.rca_lm_set_graphs(self._h, 1 if enable else 0), "rca_lm_set_graphs")
 
 
+class LlamaGroup:
+    """2 to 4 sessions over ONE set of weights (a handle and its share_weights_with= twins) stepped together: every weight matrix is
+    streamed once per step for all of them (rca_lm_group_step; llama.cpp's parallel sequences).  The reference's self-play loads the
+    model once per agent and steps each on its own (inference_client_self_play.py:148-159).  Every member ends a group step in the
+    state its own step() would have left, bit for bit, so step() / eval() / sample() on a member and group steps mix freely.
+    Close the group before its members."""
+
+    def __init__(self, members: Sequence["LlamaForAlternatingCodeChannels"], lib=None):
+        self.members = list(members)
+        self._lib = lib if lib is not None else N.lib()
+        self._g = C.c_void_p()
+        handles = (C.c_void_p * len(self.members))(*[m._h for m in self.members])
+        N.check(self._lib.rca_lm_group_create(handles, len(self.members), C.byref(self._g)), "rca_lm_group_create")
+
+    def step(self, tokens_per_member: Sequence[Sequence[int]]) -> List[int]:
+        """Member s evaluates tokens_per_member[s] (all of one length n, len(members) * n = 2 or 4) at its own n_tokens and samples with
+        its own sampler; returns the sampled token of every member.  A refusal (context overflow of any member, an id outside the
+        vocabulary, a member without a sampler) raises and leaves every member as it was."""
+        rows = [list(t) for t in tokens_per_member]
+        if len(rows) != len(self.members):
+            raise ValueError(f"{len(rows)} token lists for {len(self.members)} members")
+        n = len(rows[0])
+        if any(len(r) != n for r in rows):
+            raise ValueError("every member evaluates the same number of tokens in a group step")
+        starts = [m.n_tokens for m in self.members]
+        flat = [t for r in rows for t in r]
+        arr = (C.c_int32 * max(len(flat), 1))(*flat)
+        out = (C.c_int32 * len(self.members))()
+        N.check(self._lib.rca_lm_group_step(self._g, arr, n, out), "rca_lm_group_step")
+        for m, n0, r in zip(self.members, starts, rows):
+            m._input_ids[n0:n0 + n] = r
+            m._logits_valid = False
+        return [int(t) for t in out]
+
+    def close(self) -> None:
+        if getattr(self, "_g", None) is not None and self._g:
+            self._lib.rca_lm_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ScoreResult:
     """What score() returns: one numpy array per field of rca_score_row_t, one entry per position.  logprob / lse / max_logit /
     argmax of the scored handle; with a base also kl = KL(P_base || P), base_logprob and base_argmax (None without one).
