@@ -462,6 +462,37 @@ typedef struct rca_lm_group rca_lm_group_t;
 int rca_lm_group_create(rca_lm_t* const* members, int32_t n_members, rca_lm_group_t** out);
 int rca_lm_group_destroy(rca_lm_group_t* g);
 int rca_lm_group_step(rca_lm_group_t* g, const int32_t* ids, int32_t n, int32_t* tokens);
+/* Batch step: 2 to 64 sessions over ONE set of weights advance together as one token block of the 128-token MFMA tiles (llama.cpp:
+ * -np N with N above 4).  Where the group step runs the decode GEMVs over 2 or 4 rows, the batch step runs every projection as one
+ * tile GEMM over all n_members * n rows, the decode attention of every member in one launch (+ one merge) per layer, the head as
+ * one tile GEMM over one row per member and the top-k sampler chain (top_k 1..256) once for all members.
+ * rca_lm_batch_create: a batch over 2 to 64 existing handles.  RCA_ERR_ARG, with a message naming the member, for the refusals of
+ *   rca_lm_group_create (a null or duplicate member, another device, other weights, a logits_all member) and for a member whose
+ *   long evals do not take the 128-token tiles (rca_lm_prefill_route != 2): such models stay with the group step.  Members MAY
+ *   differ in activation format: the tiles always run f32 activations split into bf16 hi + lo, exactly as rca_lm_eval_async and
+ *   rca_lm_score do, so rca_lm_set_act_format does not apply to a batch step.  The batch holds pointers to its members only and is
+ *   destroyed BEFORE any of them.
+ * rca_lm_batch_step: ids [n_members][n], tokens [n_members]; n is 1 or 2 and n_members * n <= 128.  Member s evaluates
+ *   ids[s * n .. s * n + n) at ITS n_tokens and samples with ITS sampler.  Afterwards every member has n_tokens += n, its K / V rows
+ *   written in its own cache, its last row's logits where rca_lm_get_logits / rca_lm_token_probs / rca_lm_sample /
+ *   rca_lm_logits_dev find them, its draw counter and penalty window advanced and its sampled token in tokens[s].
+ *   Contract (NOT the group step's bit-for-bit promise against rca_lm_step: the tiles round differently from the GEMVs):
+ *     - the arithmetic class is that of a decode step on a tile-built cache: tile GEMMs + the split decode attention;
+ *     - a K / V row is, bit for bit, the row rca_lm_eval_async writes for the same token at the same position over the same
+ *       earlier rows;
+ *     - a member's logits and K / V rows do not depend on its slot, on the other members, or on graphs being on or off;
+ *     - the token is the one rca_lm_sample would draw from the member's logits at its draw counter.
+ *   Pending rca_lm_eval_async work of a member is waited for first.  Refused before anything is staged, with NO member changed: n
+ *   outside 1..2, more than 128 rows, an id outside the vocabulary (RCA_ERR_ARG); a member without a sampler, a member switched to
+ *   logits_all or off the tile route since the batch was made, a context overflow of ANY member (RCA_ERR_STATE).  Messages name
+ *   the member.  The pass runs on member 0's stream, in member 0's activation workspace: one upload, one synchronisation, one
+ *   download.  With graphs enabled on every member it is one replay, captured per (n, largest context bucket among the members) as
+ *   one linear launch sequence and re-captured when a member's captured state changes; rca_lm_set_graphs(member, 0) on any member
+ *   makes it eager.  Single-handle calls, group steps and batch steps may be interleaved freely on the same handles. */
+typedef struct rca_lm_batch rca_lm_batch_t;
+int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, rca_lm_batch_t** out);
+int rca_lm_batch_destroy(rca_lm_batch_t* b);
+int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t n, int32_t* tokens);
 /* One whole frame of process_audio_input_ids (realtime_agent_v2.py:332-372) as ONE hipGraph: n_steps (<= 8) S=2 steps, the
  * agent token sampled by step i fed back on the device together with user_ids[i] as step i+1's input pair; first_pair is the
  * pair step 0 evaluates (the last two ids of the sequence).  out_tokens[i] = token sampled by step i.  *n_done = number of steps

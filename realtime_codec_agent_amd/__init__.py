@@ -14,6 +14,7 @@ _LAZY = {
     "RealtimeAgentMultiprocessing": ".realtime_agent_v2",
     "LlamaForAlternatingCodeChannels": ".llm",
     "LlamaGroup": ".llm",
+    "LlamaBatch": ".llm",
     "MagiCodecHIP": ".codec",
     "HipCodec": ".codec",
     "CodecConfig": ".codec_model",

@@ -949,6 +949,8 @@ __global__ __launch_bounds__(256) void lm_split_bf16_kernel(const LmDevState* __
 #define GEMM_EPI_ROPE 1
 #define GEMM_EPI_SWIGLU 2
 #define GEMM_EPI_LOGITS 3   // lm_gemm128_kernel only: the head of rca_lm_score, plain f32 stores into one token block's [128][V] scratch
+#define GEMM_EPI_ROPE_ROWS 4   // lm_gemm128_kernel (+ its k-split epilogue) only: GEMM_EPI_ROPE whose token rows belong to DIFFERENT sessions
+                               // (rca_lm_batch_step): position, K / V cache and context bound of a row come from an LmGroupRow table
 template <int EPI>
 __global__ __launch_bounds__(256) void lm_gemm_mfma_kernel(const LmDevState* __restrict__ stt, const bf16_t* __restrict__ W,
                                                            const bf16_t* __restrict__ xh, const bf16_t* __restrict__ xl, int N, int K,
@@ -1172,8 +1174,11 @@ __device__ __forceinline__ float samp_penalise(float v, int count, float repeat,
 // accepted j draws ago, thread 64 + b bias entry b.  The first holder of a token owns it: bias entries in order (as the logits
 // processor adds them, llamacpp_utils.py:8-24), then the penalty; the original goes to the override list, the adjusted value into
 // the row.
-__global__ __launch_bounds__(128) void samp_prepare_kernel(float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
-                                                           const LmDevState* __restrict__ stt, SampWork* __restrict__ w) {
+// (The bodies of the four kernels of the serial chain are device functions, always inlined: the kernels of one handle pass their
+// arguments through, the table kernels of rca_lm_batch_step -- one member per grid y -- read them from the member's table entry.
+// A member's draw is the same instructions on the same operands either way.)
+__device__ __forceinline__ void samp_prepare_body(float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
+                                                  const LmDevState* __restrict__ stt, SampWork* __restrict__ w) {
     __shared__ int tok[72];
     const int tid = threadIdx.x;
     const unsigned long long cnt = stt->rng_counter;
@@ -1226,8 +1231,13 @@ __device__ __forceinline__ int samp_k(const SamplerDev* sp, int V) {
     return k > V ? V : k;
 }
 
-__global__ __launch_bounds__(256) void samp_hist_kernel(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
-                                                        SampWork* __restrict__ w) {
+__global__ __launch_bounds__(128) void samp_prepare_kernel(float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
+                                                           const LmDevState* __restrict__ stt, SampWork* __restrict__ w) {
+    samp_prepare_body(logits, V, sp, stt, w);
+}
+
+__device__ __forceinline__ void samp_hist_body(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
+                                               SampWork* __restrict__ w) {
     __shared__ unsigned hl[SAMP_BINS];
     for (int b = threadIdx.x; b < SAMP_BINS; b += 256) hl[b] = 0;
     __syncthreads();
@@ -1240,8 +1250,13 @@ __global__ __launch_bounds__(256) void samp_hist_kernel(const float* __restrict_
         if (hl[b]) atomicAdd(&w->hist[b], hl[b]);
 }
 
-__global__ __launch_bounds__(256) void samp_gather_kernel(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
-                                                          SampWork* __restrict__ w) {
+__global__ __launch_bounds__(256) void samp_hist_kernel(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
+                                                        SampWork* __restrict__ w) {
+    samp_hist_body(logits, V, sp, w);
+}
+
+__device__ __forceinline__ void samp_gather_body(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
+                                                 SampWork* __restrict__ w) {
     __shared__ unsigned wtot[4];
     __shared__ unsigned thr_bin;
     const int k = samp_k(sp, V);
@@ -1291,6 +1306,11 @@ __global__ __launch_bounds__(256) void samp_gather_kernel(const float* __restric
     }
 }
 
+__global__ __launch_bounds__(256) void samp_gather_kernel(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
+                                                          SampWork* __restrict__ w) {
+    samp_gather_body(logits, V, sp, w);
+}
+
 // Inside a frame graph samp_final_kernel's tail also does what a one-thread "next pair" launch and the next step's embedding launch
 // did: record the token, advance the position, make [token, user id of this frame] the next pair and gather their embedding rows
 // into x (two launches less per step of a frame).  (One launch for the WHOLE sampler -- histogram, last-arriver gather + selection --
@@ -1303,8 +1323,8 @@ struct SampTail {
     float* x;
     int H;
 };
-__global__ __launch_bounds__(1024) void samp_final_kernel(float* logits, int V, const SamplerDev* __restrict__ sp,
-                                                          LmDevState* __restrict__ stt, SampWork* __restrict__ w, SampTail tail) {
+__device__ __forceinline__ void samp_final_body(float* logits, int V, const SamplerDev* __restrict__ sp,
+                                                LmDevState* __restrict__ stt, SampWork* __restrict__ w, const SampTail& tail) {
     __shared__ unsigned long long s_draw;
     __shared__ unsigned hist[256];
     __shared__ unsigned long long sel_prefix;
@@ -1467,6 +1487,10 @@ __global__ __launch_bounds__(1024) void samp_final_kernel(float* logits, int V, 
                                     : __uint_as_float((unsigned)reinterpret_cast<const bf16_t*>(tail.table)[(long)id * tail.H + hh] << 16);
         }
     }
+}
+__global__ __launch_bounds__(1024) void samp_final_kernel(float* logits, int V, const SamplerDev* __restrict__ sp,
+                                                          LmDevState* __restrict__ stt, SampWork* __restrict__ w, SampTail tail) {
+    samp_final_body(logits, V, sp, stt, w, tail);
 }
 
 // ---- top_k <= 0: llama.cpp's "whole vocabulary" (its top-k sampler is then a no-op; llamacpp_utils.py:39-77 passes top_k straight
@@ -3243,13 +3267,43 @@ __device__ long* rca_attn_tl = nullptr;
 #endif
 
 #define ATTM_LDS (8 * 32 * 64 * 4 + 2 * 8 * 32 * 4)   // wo (aliases the K / V images) + wm + wl
-template <int G>
+// TAB = true (rca_lm_batch_step): the decode attention of EVERY member of a batch in one launch, grid (kv head, 256-key split, member).
+// A member's n <= 2 query tokens are one query block; its state, cache, partials and its rows of the shared qkv buffer come from
+// tab[member] (the pointer arguments are unused).  The grid covers the largest split count among the members: a split past a
+// member's cache leaves at once (its att_part has no slot for it), one past its context takes the empty-split path below.  Partials
+// always go through att_part and a separate merge launch: the in-launch merge and its polling loop are compiled out of this instance.
+// The TAB = false instances are the kernel as it was before the table existed.
+struct LmBatchMember {
+    LmDevState* stt;          // the member's step state: n_tokens = its KV position, m = its tokens of the pass
+    const f16_t* kc; const f16_t* vc;   // its cache (layer 0)
+    long kv_stride;           // layer stride in elements
+    float* part;              // its att_part
+    float* logits;            // its logits buffer (the head's row copy)
+    SamplerDev* samp;         // its sampler + work area (the table chain)
+    SampWork* swork;
+    int row0;                 // its first row in the batch's qkv / hi / lo buffers
+    int n_splits, n_ctx;
+    int serial;               // 1: its sampler is the serial top-k chain, run by the table kernels
+};
+template <int G, bool TAB = false>
 // (argument order: what the first loads need -- the cache pointers, the head counts, n_ctx -- sits inside the 14 dwords the
 //  dispatcher preloads into SGPRs; `part` / `arrive` / `attn_out` are only needed at the end)
 __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __restrict__ stt, const float* __restrict__ qkv,
                                                            const f16_t* __restrict__ kc, const f16_t* __restrict__ vc,
                                                            int nh, int nkv, int n_splits, float scale, int n_ctx,
-                                                           float* __restrict__ part, int* __restrict__ arrive, float* __restrict__ attn_out) {
+                                                           float* __restrict__ part, int* __restrict__ arrive, float* __restrict__ attn_out,
+                                                           const LmBatchMember* __restrict__ tab = nullptr, int tab_layer = 0) {
+    if constexpr (TAB) {
+        const LmBatchMember e = tab[blockIdx.z];
+        if ((int)blockIdx.y >= e.n_splits) return;
+        stt = e.stt;
+        qkv += (long)e.row0 * (nh + 2 * nkv) * 64;
+        kc = e.kc + (long)tab_layer * e.kv_stride;
+        vc = e.vc + (long)tab_layer * e.kv_stride;
+        n_splits = e.n_splits;
+        n_ctx = e.n_ctx;
+        part = e.part;
+    }
     // arrive != nullptr (decode steps: one query block, at most one workgroup per CU, at most 8 live query rows): the merge of the
     // splits happens HERE, by data-tagged granules (MI355X_MICROARCH.md, price list rows handoff-1to1 / allgather: "granule = one
     // naturally aligned 8-byte {data, tag} written by ONE sc1 store", polled with sc1 loads; R2: a granule needs no ordering).  Every
@@ -3263,7 +3317,7 @@ __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __r
     // Round 3 did this with drained sc1 stores + an arrival ticket + a re-read by the last arriver: 4.2 us from the last partial's
     // stores to the merged row at 6.6 k context (profiles/r04/attn_decode_timeline.txt); the granules take the drain, the two
     // barriers and the ticket round trip out of the chain.
-    const bool fused = arrive != nullptr;
+    const bool fused = !TAB && arrive != nullptr;
 #ifdef RCA_ATTN_TIMELINE
     long* const atl = (rca_attn_tl && fused) ? rca_attn_tl + ((long)(blockIdx.y * gridDim.x + blockIdx.x) & 1023) * 16 : nullptr;
 #endif
@@ -3368,7 +3422,7 @@ __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __r
     // (the waves' K / V images, 8 KB each, alias wo: they are dead before wo is written)
     float (*wm)[32] = reinterpret_cast<float (*)[32]>(attm_lds + 8 * 32 * HD);
     float (*wl)[32] = wm + 8;
-    const int g = blockIdx.x, sp = blockIdx.y, qb = blockIdx.z;
+    const int g = blockIdx.x, sp = blockIdx.y, qb = TAB ? 0 : blockIdx.z;
     const int lane = threadIdx.x & 63;
     const int half = lane >> 5, col = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -3631,6 +3685,24 @@ __global__ __launch_bounds__(64) void lm_attn_mfma_combine_kernel(const LmDevSta
     } else {
         attn[(long)m * nh * 64 + head * 64 + d] = ov;
     }
+}
+// the merge behind lm_attn_mfma_kernel<G, true>, grid (token of the member * head, member): the arithmetic and the bf16 hi / lo output of
+// the kernel above, over the splits the member has, into the member's rows of the planes the O projection's tile GEMM reads
+template <int G>
+__global__ __launch_bounds__(64) void lm_attn_mfma_batch_combine_kernel(const LmBatchMember* __restrict__ tab, int nh, int nkv, int nsp_launch,
+                                                                        bf16_t* __restrict__ hi, bf16_t* __restrict__ lo) {
+    const LmBatchMember e = tab[blockIdx.y];
+    const int m = blockIdx.x / nh, head = blockIdx.x % nh;
+    const int g = head / G, hq = head % G;
+    const int r = m * G + hq;   // one query block per member
+    const int d = threadIdx.x;
+    const float* base = e.part + ((long)g * e.n_splits) * 32 * 66 + r * 66;
+    const float ov = attn_merge_row<false>(base, min(nsp_launch, e.n_splits), d);
+    if (m >= e.stt->m) return;
+    const long o = (long)(e.row0 + m) * nh * 64 + head * 64 + d;
+    const bf16_t hb = f32_to_bf16_rne(ov);
+    hi[o] = hb;
+    lo[o] = f32_to_bf16_rne(ov - __uint_as_float((unsigned)hb << 16));
 }
 
 // ------------------------------------------------------------------ prefill attention, flash shape
@@ -4031,6 +4103,7 @@ static int lm_splits_needed(const rca_lm* h, int m) { return std::min(h->n_split
 // stage (lm_enqueue_pass, the head behind a prefill, rca_lm_gemv_tap for the tests) runs the same launch.
 static const GemvPro nopro{nullptr, nullptr, 0.0f, 0};
 static const GemvRope norope{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+static const GemvGroup nogroup{nullptr, 0};
 static void lm_launch_qkv(rca_lm* h, int l, int M, hipStream_t st) {   // RMSNorm(x) -> [q; k; v] + RoPE -> qkv, KV cache of layer l
     const rca_lm_config_t& c = h->cfg;
     const LmLayer& L = h->layers[l];
@@ -4120,7 +4193,9 @@ template <int EPI, int WF>
 __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __restrict__ stt, const bf16_t* __restrict__ W, GemvQ8 q8,
                                                             const bf16_t* __restrict__ xh, const bf16_t* __restrict__ xl, int N, int K,
                                                             int kslice, float* __restrict__ y, int ldy, bf16_t* __restrict__ oh,
-                                                            bf16_t* __restrict__ ol, float* __restrict__ part, GemvRope rope, int nseq) {
+                                                            bf16_t* __restrict__ ol, float* __restrict__ part, GemvRope rope, int nseq,
+                                                            GemvGroup grp) {
+    constexpr bool ROPE = EPI == GEMM_EPI_ROPE || EPI == GEMM_EPI_ROPE_ROWS;   // the weight rows of the fused QKV matrix: pairs (d, d + 32) of one head
     // nseq > 1: this workgroup walks nseq consecutive k slices itself.  Each slice is summed into a fresh accumulator and that is
     // added to a running total -- exactly the additions, in exactly the order, of "every slice its own workgroup, then
     // lm_gemm128_epilogue_kernel adds the partial sums starting from 0" -- so the result does not depend on which of the two forms a
@@ -4174,10 +4249,10 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
     const unsigned* gD4 = (W4 && !W40) ? q8.dd + q4k_scm_index(q4slot, 0, K >> 8) : nullptr;                                                     // super-block k / 256: + 16 each
     int q4row[2];   // LDS rows of the two slots
 #pragma unroll
-    for (int i = 0; i < 2; ++i) q4row[i] = (int)packed_slot_row(4 * q4quad + 2 * q4half + i, EPI == GEMM_EPI_ROPE);
+    for (int i = 0; i < 2; ++i) q4row[i] = (int)packed_slot_row(4 * q4quad + 2 * q4half + i, ROPE);
     const int q4soff0 = q4row[0] * G128_PITCH + ((tid >> 1) & 3) * 8, q4soff1 = q4row[1] * G128_PITCH + ((tid >> 1) & 3) * 8;
-    const int qra = EPI == GEMM_EPI_ROPE ? (qp >> 5) * 64 + (qp & 31) : 2 * qp;
-    const int qsoff0 = qra * G128_PITCH + skc, qsoff1 = qsoff0 + (EPI == GEMM_EPI_ROPE ? 32 : 1) * G128_PITCH;
+    const int qra = ROPE ? (qp >> 5) * 64 + (qp & 31) : 2 * qp;
+    const int qsoff0 = qra * G128_PITCH + skc, qsoff1 = qsoff0 + (ROPE ? 32 : 1) * G128_PITCH;
     // Software pipeline.  A workgroup's stage needs 8 KB of weights straight from HBM (~2 us away) and 16 KB of
     // activations from L2 (~0.7 us): weight chunks are requested DW stages ahead, activation chunks DX stages ahead,
     // both held in registers until their LDS buffer is free.
@@ -4373,9 +4448,15 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
                     const int n = n0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                     y[(long)tok * ldy + n] = y[(long)tok * ldy + n] + acc[i][j][r];
                 }
-        } else if (EPI == GEMM_EPI_ROPE) {
+        } else if (ROPE) {
             // the wave's 64 rows are one head: rows d (tile 0) and d + 32 (tile 1) sit in the same register slot
-            const int pos = stt->n_tokens + tok;
+            if (EPI == GEMM_EPI_ROPE_ROWS) {   // this token row's session: its position, its cache (the arithmetic below is shared)
+                const LmGroupRow gr = grp.rows[tok];
+                rope.kc = gr.kc + (long)grp.layer * gr.kv_stride;
+                rope.vc = gr.vc + (long)grp.layer * gr.kv_stride;
+                rope.n_ctx = gr.n_ctx;
+            }
+            const int pos = EPI == GEMM_EPI_ROPE_ROWS ? grp.rows[tok].stt->n_tokens + grp.rows[tok].j : stt->n_tokens + tok;
             if (pos >= rope.n_ctx) continue;
             const int head = (n0 + wr * 64 + rope.row_base) >> 6;
 #pragma unroll
@@ -4423,7 +4504,7 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
 template <int EPI>
 __global__ __launch_bounds__(256) void lm_gemm128_epilogue_kernel(const LmDevState* __restrict__ stt, const float* __restrict__ part, int nsplit, int grp, int N,
                                                                   float* __restrict__ y, int ldy, bf16_t* __restrict__ oh, bf16_t* __restrict__ ol,
-                                                                  GemvRope rope) {
+                                                                  GemvRope rope, GemvGroup rt) {
     __shared__ float tile[64][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // ty 0..7
     const int n0 = blockIdx.x * 64, t0 = blockIdx.y * 32;
@@ -4463,8 +4544,14 @@ __global__ __launch_bounds__(256) void lm_gemm128_epilogue_kernel(const LmDevSta
             float* yr = y + (long)tok * ldy + n0;
             yr[tx] = yr[tx] + tile[tx][tl];
             yr[tx + 32] = yr[tx + 32] + tile[tx + 32][tl];
-        } else if (EPI == GEMM_EPI_ROPE) {
-            const int pos = stt->n_tokens + tok;
+        } else if (EPI == GEMM_EPI_ROPE || EPI == GEMM_EPI_ROPE_ROWS) {
+            if (EPI == GEMM_EPI_ROPE_ROWS) {   // this token row's session: its position, its cache (the arithmetic below is shared)
+                const LmGroupRow gr = rt.rows[tok];
+                rope.kc = gr.kc + (long)rt.layer * gr.kv_stride;
+                rope.vc = gr.vc + (long)rt.layer * gr.kv_stride;
+                rope.n_ctx = gr.n_ctx;
+            }
+            const int pos = EPI == GEMM_EPI_ROPE_ROWS ? rt.rows[tok].stt->n_tokens + rt.rows[tok].j : stt->n_tokens + tok;
             if (pos >= rope.n_ctx) continue;
             const int head = (n0 + rope.row_base) >> 6, d = tx;
             const float x1 = tile[d][tl], x2 = tile[d + 32][tl];
@@ -4561,6 +4648,10 @@ static G128Form g128_form(int N, int ns, int tbz, int seq_min) {
     if (grp > 1 && seq_min > 0 && (N / 128) * tbz * ng >= seq_min) return {ng, grp, ng, 1};     // workgroups walk a group, group sums stored
     return {ns, 1, ns, grp};                                                                     // every slice stored
 }
+static int g128_seq_min() {   // one value per process: every pass of a token block takes the same form
+    static const int v = getenv("RCA_LM_SEQ_MIN_WGS") ? atoi(getenv("RCA_LM_SEQ_MIN_WGS")) : 512;
+    return v;
+}
 static bool lm_can_gemm128(const rca_lm* h) {
     const rca_lm_config_t& c = h->cfg;
     const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn;
@@ -4572,7 +4663,8 @@ static bool lm_can_gemm128(const rca_lm* h) {
 // one 128-row GEMM launch in the format the matrix is kept in
 template <int EPI>
 static void launch_gemm128(rca_lm* h, const WMat& w, dim3 grid, hipStream_t st, const bf16_t* xh, const bf16_t* xl, int N, int K, int kslice,
-                           float* y, int ldy, bf16_t* oh, bf16_t* ol, GemvRope rope, int nseq) {
+                           float* y, int ldy, bf16_t* oh, bf16_t* ol, GemvRope rope, int nseq, const LmDevState* stt = nullptr,
+                           const GemvGroup& grp = nogroup) {   // stt: the pass's own device state (a batch step's), else the handle's
     static bool attr_done = false;
     if (!attr_done) {   // the four-tile variants need 80 KB of LDS
         for (int fmt : WF_FORMATS)
@@ -4585,8 +4677,8 @@ static void launch_gemm128(rca_lm* h, const WMat& w, dim3 grid, hipStream_t st, 
     const GemvQ8 qa{w.qs, w.sc, w.dd};
     wf_dispatch(w.fmt, [&](auto wf) {   // bf16 fragments go to the MFMA as they are: three tiles per stage, not four
         constexpr int WF = decltype(wf)::value;
-        lm_gemm128_kernel<EPI, WF><<<grid, 256, WF == WF_BF16 ? G128_LDS_T(3) : G128_LDS_T(4), st>>>(h->stt, w.wptr(), qa, xh, xl, N, K, kslice, y, ldy, oh, ol,
-                                                                                                 h->gpart, rope, nseq);
+        lm_gemm128_kernel<EPI, WF><<<grid, 256, WF == WF_BF16 ? G128_LDS_T(3) : G128_LDS_T(4), st>>>(stt ? stt : h->stt, w.wptr(), qa, xh, xl, N, K, kslice, y, ldy, oh, ol,
+                                                                                                 h->gpart, rope, nseq, grp);
     });
 }
 static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch) {
@@ -4598,7 +4690,7 @@ static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_
     // A projection whose token blocks alone put `seq_min` workgroups on the chip is run with every workgroup walking the k slices itself
     // (same sums in the same order, no partial sums through HBM, no epilogue launch); RCA_LM_SEQ_MIN_WGS overrides the threshold
     // (0 = never) for A/B runs.
-    static const int seq_min = getenv("RCA_LM_SEQ_MIN_WGS") ? atoi(getenv("RCA_LM_SEQ_MIN_WGS")) : 512;
+    const int seq_min = g128_seq_min();
     const G128Form fo = g128_form(H, so, tbz, seq_min), fg = g128_form(2 * F, sg, tbz, seq_min), fd = g128_form(H, sd, tbz, seq_min);
     float* x = h->x;
     lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, x, H, c.vocab_size);
@@ -4614,21 +4706,21 @@ static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_
             const G128Form fq = g128_form(Ns, ss, tbz, seq_min);
             rope.row_base = seg ? L.qkv.N : 0;
             launch_gemm128<GEMM_EPI_ROPE>(h, w, dim3(Ns / 128, fq.grid_y, tbz), st, h->xh, h->xl, Ns, H, H / ss, h->qkv, QKV, nullptr, nullptr, rope, fq.nseq);
-            if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE><<<dim3(Ns / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fq.ep_nsplit, fq.ep_grp, Ns, h->qkv, QKV, nullptr, nullptr, rope);
+            if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE><<<dim3(Ns / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fq.ep_nsplit, fq.ep_grp, Ns, h->qkv, QKV, nullptr, nullptr, rope, nogroup);
         }
         rope.row_base = 0;
         launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, h->xh, h->xl, true);
         launch_gemm128<GEMM_EPI_RESID>(h, L.o, dim3(H / 128, fo.grid_y, tbz), st, h->xh, h->xl, H, AO, AO / so, x, H, nullptr, nullptr, norope, fo.nseq);
-        if (fo.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fo.ep_nsplit, fo.ep_grp, H, x, H, nullptr, nullptr, norope);
+        if (fo.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fo.ep_nsplit, fo.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
         lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.ffn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
         // SwiGLU epilogue writes the hi/lo split of h straight into the (ffn-wide) split buffers of the down projection:
         // it reads xh/xl [M][H] and writes [M][F] -- distinct regions are needed, so h goes to the second half of hbuf
         bf16_t* hh = reinterpret_cast<bf16_t*>(h->hbuf);
         bf16_t* hl = hh + (long)LM_MAXM * F;
         launch_gemm128<GEMM_EPI_SWIGLU>(h, L.gu, dim3(2 * F / 128, fg.grid_y, tbz), st, h->xh, h->xl, 2 * F, H, H / sg, nullptr, F, hh, hl, norope, fg.nseq);
-        if (fg.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_SWIGLU><<<dim3(2 * F / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fg.ep_nsplit, fg.ep_grp, 2 * F, nullptr, 0, hh, hl, norope);
+        if (fg.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_SWIGLU><<<dim3(2 * F / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fg.ep_nsplit, fg.ep_grp, 2 * F, nullptr, 0, hh, hl, norope, nogroup);
         launch_gemm128<GEMM_EPI_RESID>(h, L.down, dim3(H / 128, fd.grid_y, tbz), st, hh, hl, H, F, F / sd, x, H, nullptr, nullptr, norope, fd.nseq);
-        if (fd.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fd.ep_nsplit, fd.ep_grp, H, x, H, nullptr, nullptr, norope);
+        if (fd.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fd.ep_nsplit, fd.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
     }
     RCA_LAUNCH_CHECK();
     return RCA_OK;
@@ -5355,6 +5447,298 @@ extern "C" int rca_lm_group_step(rca_lm_group_t* g, const int32_t* ids, int32_t 
         h->logits_rows = 1;
         h->rng_host += 1;
         tokens[s] = g->pin->tokens[s];
+    }
+    return RCA_OK;
+}
+
+// ------------------------------------------------------------------------------------ batch step (rca_lm_batch_step)
+// 2 to 64 sessions over ONE set of weights advance by n = 1 or 2 tokens each as ONE token block of the 128-token MFMA tiles: the
+// n_members * n rows are a small GEMM, not a GEMV, so a matrix is staged (and de-quantised) once for all of them and the cost of a
+// step grows slowly with the members.  The pass is lm_enqueue_prefill_tile128's for the row-wise stages -- embedding gather, RMSNorm +
+// hi / lo split, O, gate / up + SwiGLU, down, with the same k-split forms (functions of the matrix only) -- driven by a batch-owned
+// LmDevState whose m is the row count.  What is per session comes from tables: the QKV epilogue (GEMM_EPI_ROPE_ROWS) takes a row's
+// position and cache from an LmGroupRow, the decode attention (split kernel + separate combine, never the in-launch merge) and the
+// serial sampler chain take a member per grid z / y from an LmBatchMember.  The head is one tile GEMM over the members' last rows
+// into a batch-owned block, then a row copy into every member's own logits buffer.  Arithmetic class: tile GEMMs (f32 activations
+// as bf16 hi + lo) and decode attention, i.e. what a decode step on a tile-built cache sees -- not the GEMV steps' bits, so no
+// bit-for-bit promise against rca_lm_step; a row's result does not depend on its slot or its companions.
+#define LM_BATCH_MAX 64
+#define LM_BATCH_ROWS 128   // one token block
+struct LmBatchStage { int n_tokens[LM_BATCH_MAX]; int ids[LM_BATCH_ROWS]; };
+struct LmBatchPin { LmBatchStage in; int tokens[LM_BATCH_MAX]; };
+struct rca_lm_batch {
+    int n_members = 0;
+    rca_lm* m[LM_BATCH_MAX] = {};
+    LmGroupRow* rows = nullptr;       // device, [LM_GEMV_M][LM_BATCH_ROWS]: (member s, token j) -> row s * n + j
+    LmBatchMember* tab = nullptr;     // device, [LM_GEMV_M][LM_BATCH_MAX]
+    bool tabs_valid = false;
+    unsigned long long epoch[LM_BATCH_MAX] = {};   // the members' graph epochs the tables and graphs below were made under
+    bool any_serial = false, any_patch = false;    // the table sampler chain has members / some of them patch their logits
+    LmDevState* stt = nullptr;        // device: the pass over all rows (m = n_members * n, the rows' ids)
+    LmDevState* stt_head = nullptr;   // device: the head's pass (m = n_members)
+    float* head_blk = nullptr;        // device, [n_members][V]: the head GEMM's block
+    LmBatchStage* stage = nullptr;    // device copy of pin->in
+    int* tokens = nullptr;            // device: the members' sampled tokens, gathered for one download
+    LmBatchPin* pin = nullptr;        // pinned
+    hipGraphExec_t g[LM_GEMV_M][LM_GRAPH_BUCKETS] = {};   // (n, largest context bucket among the members)
+};
+// the pass's state and the members' step states, from one staging block
+__global__ void lm_batch_stage_kernel(const LmBatchStage* __restrict__ in, const LmBatchMember* __restrict__ tab, LmDevState* __restrict__ bstt,
+                                      LmDevState* __restrict__ hstt, int n_members, int n) {
+    const int t = threadIdx.x;
+    if (t == 0) { bstt->n_tokens = 0; bstt->m = n_members * n; hstt->n_tokens = 0; hstt->m = n_members; }
+    if (t < n_members * n) bstt->ids[t] = in->ids[t];
+    if (t < n_members) {
+        LmDevState* stt = tab[t].stt;
+        stt->n_tokens = in->n_tokens[t];
+        stt->m = n;
+        for (int j = 0; j < n; ++j) stt->ids[j] = in->ids[t * n + j];
+    }
+}
+// n = 2: the members' last rows of x, packed for the head's RMSNorm
+__global__ __launch_bounds__(256) void lm_batch_last_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int n, int H) {
+    const float* src = x + ((long)blockIdx.x * n + n - 1) * H;
+    for (int h = threadIdx.x; h < H; h += 256) out[(long)blockIdx.x * H + h] = src[h];
+}
+// the head block's rows -> the members' own logits buffers
+__global__ __launch_bounds__(256) void lm_batch_logits_rows_kernel(const LmBatchMember* __restrict__ tab, const float* __restrict__ blk, int V) {
+    float* dst = tab[blockIdx.y].logits;
+    const float* src = blk + (long)blockIdx.y * V;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) dst[i] = src[i];
+}
+// the serial sampler chain with the member in grid y: the bodies of samp_prepare / hist / gather / final_kernel on the member's own
+// {logits, SamplerDev, LmDevState, SampWork}.  Members on a whole-vocabulary sampler are skipped here (their own launches follow).
+__global__ __launch_bounds__(128) void samp_prepare_batch_kernel(const LmBatchMember* __restrict__ tab, int V) {
+    const LmBatchMember e = tab[blockIdx.y];
+    if (!e.serial || !e.samp->patch) return;
+    samp_prepare_body(e.logits, V, e.samp, e.stt, e.swork);
+}
+__global__ __launch_bounds__(256) void samp_hist_batch_kernel(const LmBatchMember* __restrict__ tab, int V) {
+    const LmBatchMember e = tab[blockIdx.y];
+    if (!e.serial) return;
+    samp_hist_body(e.logits, V, e.samp, e.swork);
+}
+__global__ __launch_bounds__(256) void samp_gather_batch_kernel(const LmBatchMember* __restrict__ tab, int V) {
+    const LmBatchMember e = tab[blockIdx.y];
+    if (!e.serial) return;
+    samp_gather_body(e.logits, V, e.samp, e.swork);
+}
+__global__ __launch_bounds__(1024) void samp_final_batch_kernel(const LmBatchMember* __restrict__ tab, int V) {
+    const LmBatchMember e = tab[blockIdx.y];
+    if (!e.serial) return;
+    samp_final_body(e.logits, V, e.samp, e.stt, e.swork, SampTail{-1, nullptr, 0, nullptr, 0});
+}
+__global__ void lm_batch_tokens_kernel(const LmBatchMember* __restrict__ tab, int n_members, int* __restrict__ out) {
+    if ((int)threadIdx.x < n_members) out[threadIdx.x] = tab[threadIdx.x].stt->out_token;
+}
+static void lm_batch_drop_graphs(rca_lm_batch* b) {
+    for (auto& per_n : b->g)
+        for (hipGraphExec_t& e : per_n)
+            if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+}
+extern "C" int rca_lm_batch_destroy(rca_lm_batch_t* b);
+extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, rca_lm_batch_t** out) {
+    if (!members || !out) return fail(RCA_ERR_ARG, "batch_create: null argument");
+    if (n_members < 2 || n_members > LM_BATCH_MAX) return fail(RCA_ERR_ARG, "batch_create: %d members, a batch has 2 to %d", n_members, LM_BATCH_MAX);
+    for (int s = 0; s < n_members; ++s) {
+        const rca_lm* h = members[s];
+        if (!h) return fail(RCA_ERR_ARG, "batch_create: member %d is null", s);
+        for (int t = 0; t < s; ++t)
+            if (members[t] == h) return fail(RCA_ERR_ARG, "batch_create: member %d is the same handle as member %d", s, t);
+        if (h->device != members[0]->device) return fail(RCA_ERR_ARG, "batch_create: member %d is on device %d, member 0 on device %d", s, h->device, members[0]->device);
+        if (lm_weight_owner(h) != lm_weight_owner(members[0]))
+            return fail(RCA_ERR_ARG, "batch_create: member %d does not share member 0's weights (rca_lm_create_shared makes handles that do)", s);
+        if (h->cfg.logits_all) return fail(RCA_ERR_ARG, "batch_create: member %d is a logits_all handle (a batch step keeps the last position's logits only)", s);
+        if (lm_prefill_route(h) != LM_ROUTE_TILE128)
+            return fail(RCA_ERR_ARG, "batch_create: member %d does not take the 128-token tiles (rca_lm_prefill_route %d, a batch step needs 2); such models stay with rca_lm_group_step",
+                        s, lm_prefill_route(h));
+    }
+    RCA_HIP(hipSetDevice(members[0]->device));
+    rca_lm_batch* b = new rca_lm_batch();
+    b->n_members = n_members;
+    for (int s = 0; s < n_members; ++s) b->m[s] = members[s];
+    int rc = lm_alloc((void**)&b->rows, sizeof(LmGroupRow) * LM_GEMV_M * LM_BATCH_ROWS);
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->tab, sizeof(LmBatchMember) * LM_GEMV_M * LM_BATCH_MAX);
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->stt, sizeof(LmDevState));
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->stt_head, sizeof(LmDevState));
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->head_blk, (size_t)n_members * members[0]->cfg.vocab_size * 4);
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->stage, sizeof(LmBatchStage));
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->tokens, sizeof(int) * LM_BATCH_MAX);
+    if (rc == RCA_OK && hipHostMalloc((void**)&b->pin, sizeof(LmBatchPin), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
+    if (rc == RCA_OK && (hipMemset(b->stt, 0, sizeof(LmDevState)) != hipSuccess || hipMemset(b->stt_head, 0, sizeof(LmDevState)) != hipSuccess))
+        rc = fail(RCA_ERR_HIP, "batch_create: clearing the pass states");
+    if (rc != RCA_OK) { rca_lm_batch_destroy(b); return rc; }
+    memset(b->pin, 0, sizeof(LmBatchPin));
+    *out = b;
+    return RCA_OK;
+}
+extern "C" int rca_lm_batch_destroy(rca_lm_batch_t* b) {
+    if (!b) return RCA_OK;
+    lm_batch_drop_graphs(b);
+    for (void* p : {(void*)b->rows, (void*)b->tab, (void*)b->stt, (void*)b->stt_head, (void*)b->head_blk, (void*)b->stage, (void*)b->tokens})
+        if (p) (void)hipFree(p);
+    if (b->pin) (void)hipHostFree(b->pin);
+    delete b;
+    return RCA_OK;
+}
+// tables + graphs follow the members: a swapped cache, a moved logits buffer or another sampler chain shows as a new epoch
+static int lm_batch_refresh(rca_lm_batch* b) {
+    bool same = b->tabs_valid;
+    for (int s = 0; s < b->n_members; ++s) same = same && b->epoch[s] == b->m[s]->graph_epoch;
+    if (same) return RCA_OK;
+    lm_batch_drop_graphs(b);
+    std::vector<LmGroupRow> rows((size_t)LM_GEMV_M * LM_BATCH_ROWS);
+    std::vector<LmBatchMember> tab((size_t)LM_GEMV_M * LM_BATCH_MAX);
+    memset(rows.data(), 0, rows.size() * sizeof(LmGroupRow));
+    memset(tab.data(), 0, tab.size() * sizeof(LmBatchMember));
+    b->any_serial = b->any_patch = false;
+    for (int n = 1; n <= LM_GEMV_M; ++n)
+        for (int s = 0; s < b->n_members; ++s) {
+            rca_lm* h = b->m[s];
+            if (s * n + n > LM_BATCH_ROWS) break;   // (more rows than a token block: refused by the step before anything reads the table)
+            const bool serial = h->sampler_set && !h->samp_full;
+            tab[(size_t)(n - 1) * LM_BATCH_MAX + s] = LmBatchMember{h->stt, h->kc, h->vc, h->kv_layer_stride, h->att_part, h->logits, h->samp, h->swork,
+                                                                     s * n, h->n_splits, h->cfg.n_ctx, serial ? 1 : 0};
+            b->any_serial = b->any_serial || serial;
+            b->any_patch = b->any_patch || (serial && h->samp_patch);
+            for (int j = 0; j < n; ++j) {
+                LmGroupRow r{h->stt, h->kc, h->vc, h->logits, h->kv_layer_stride, j, s * n + j, h->cfg.n_ctx, 0};
+                rows[(size_t)(n - 1) * LM_BATCH_ROWS + s * n + j] = r;
+            }
+        }
+    RCA_HIP(hipMemcpy(b->rows, rows.data(), rows.size() * sizeof(LmGroupRow), hipMemcpyHostToDevice));
+    RCA_HIP(hipMemcpy(b->tab, tab.data(), tab.size() * sizeof(LmBatchMember), hipMemcpyHostToDevice));
+    for (int s = 0; s < b->n_members; ++s) b->epoch[s] = b->m[s]->graph_epoch;
+    b->tabs_valid = true;
+    return RCA_OK;
+}
+// upload of the staged states -> embedding -> the layers -> head -> samplers -> download of the tokens, all on `st`, one linear sequence
+static int lm_batch_enqueue(rca_lm_batch* b, int n, int nsp_launch, hipStream_t st) {
+    rca_lm* ws = b->m[0];
+    const rca_lm_config_t& c = ws->cfg;
+    const int NM = b->n_members, MT = NM * n;
+    const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn, V = c.vocab_size;
+    const int G = c.n_heads / c.n_kv_heads;
+    const LmGroupRow* qrows = b->rows + (size_t)(n - 1) * LM_BATCH_ROWS;
+    const LmBatchMember* tab = b->tab + (size_t)(n - 1) * LM_BATCH_MAX;
+    const LmDevState* bs = b->stt;
+    static bool attr_done = false;
+    if (!attr_done) {
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        attr_done = true;
+    }
+    hipError_t e = hipMemcpyAsync(b->stage, &b->pin->in, sizeof(LmBatchStage), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch step upload: %s", hipGetErrorString(e));
+    lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->stage, tab, b->stt, b->stt_head, NM, n);
+    // the k-split forms of one token block: what an rca_lm_eval_async pass of up to 128 tokens uses, so a row's sums are that pass's
+    const int seq_min = g128_seq_min();
+    const int so = g128_splits(H, AO), sg = g128_splits(2 * F, H), sd = g128_splits(H, F);
+    const G128Form fo = g128_form(H, so, 1, seq_min), fg = g128_form(2 * F, sg, 1, seq_min), fd = g128_form(H, sd, 1, seq_min);
+    GemvRope rope{ws->cos_t, ws->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, 0};   // cache, position and context bound: per row, from the table
+    const float scale = 1.0f / sqrtf((float)c.head_dim);
+    const dim3 agm(c.n_kv_heads, nsp_launch, NM);
+    float* x = ws->x;
+    lm_embed_kernel<<<MT, 256, 0, st>>>(bs, ws->embed, ws->embed_f32, x, H, V);
+    for (int l = 0; l < c.n_layers; ++l) {
+        const LmLayer& L = ws->layers[l];
+        const GemvGroup grp{qrows, l};
+        lm_add_rmsnorm_kernel<<<MT, 64, 0, st>>>(bs, x, nullptr, nullptr, 0, 0, L.attn_norm, ws->xn, H, c.rms_eps, ws->xh, ws->xl);
+        for (int seg = 0; seg < (L.split_v ? 2 : 1); ++seg) {
+            const WMat& w = seg ? L.vseg : L.qkv;
+            const int Ns = w.N, ss = g128_splits(Ns, H);
+            const G128Form fq = g128_form(Ns, ss, 1, seq_min);
+            rope.row_base = seg ? L.qkv.N : 0;
+            launch_gemm128<GEMM_EPI_ROPE_ROWS>(ws, w, dim3(Ns / 128, fq.grid_y, 1), st, ws->xh, ws->xl, Ns, H, H / ss, ws->qkv, QKV, nullptr, nullptr, rope, fq.nseq, bs, grp);
+            if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE_ROWS><<<dim3(Ns / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fq.ep_nsplit, fq.ep_grp, Ns, ws->qkv, QKV, nullptr, nullptr, rope, grp);
+        }
+#define RCA_BATCH_ATTN(GG)                                                                                                            \
+        lm_attn_mfma_kernel<GG, true><<<agm, 512, ATTM_LDS, st>>>(nullptr, ws->qkv, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, scale, 0, nullptr, \
+                                                                  nullptr, nullptr, tab, l);                                                      \
+        lm_attn_mfma_batch_combine_kernel<GG><<<dim3(n * c.n_heads, NM), 64, 0, st>>>(tab, c.n_heads, c.n_kv_heads, nsp_launch, ws->xh, ws->xl);
+        if (G == 4) { RCA_BATCH_ATTN(4) }
+        else if (G == 2) { RCA_BATCH_ATTN(2) }
+        else { RCA_BATCH_ATTN(1) }
+#undef RCA_BATCH_ATTN
+        launch_gemm128<GEMM_EPI_RESID>(ws, L.o, dim3(H / 128, fo.grid_y, 1), st, ws->xh, ws->xl, H, AO, AO / so, x, H, nullptr, nullptr, norope, fo.nseq, bs);
+        if (fo.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fo.ep_nsplit, fo.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
+        lm_add_rmsnorm_kernel<<<MT, 64, 0, st>>>(bs, x, nullptr, nullptr, 0, 0, L.ffn_norm, ws->xn, H, c.rms_eps, ws->xh, ws->xl);
+        bf16_t* hh = reinterpret_cast<bf16_t*>(ws->hbuf);   // the SwiGLU epilogue's hi / lo planes, as in lm_enqueue_prefill_tile128
+        bf16_t* hl = hh + (long)LM_MAXM * F;
+        launch_gemm128<GEMM_EPI_SWIGLU>(ws, L.gu, dim3(2 * F / 128, fg.grid_y, 1), st, ws->xh, ws->xl, 2 * F, H, H / sg, nullptr, F, hh, hl, norope, fg.nseq, bs);
+        if (fg.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_SWIGLU><<<dim3(2 * F / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fg.ep_nsplit, fg.ep_grp, 2 * F, nullptr, 0, hh, hl, norope, nogroup);
+        launch_gemm128<GEMM_EPI_RESID>(ws, L.down, dim3(H / 128, fd.grid_y, 1), st, hh, hl, H, F, F / sd, x, H, nullptr, nullptr, norope, fd.nseq, bs);
+        if (fd.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fd.ep_nsplit, fd.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
+    }
+    // final RMSNorm + head over the last row of every member (one row per member: rows 0 .. NM - 1 of the hi / lo planes), every
+    // workgroup walking all of K like rca_lm_score's head; the ragged last row tile of the vocabulary is the logits epilogue's
+    if (n > 1) lm_batch_last_rows_kernel<<<NM, 256, 0, st>>>(x, ws->xn, n, H);
+    lm_add_rmsnorm_kernel<<<NM, 64, 0, st>>>(b->stt_head, n > 1 ? ws->xn : x, nullptr, nullptr, 0, 0, ws->final_norm, ws->xn, H, c.rms_eps, ws->xh, ws->xl);
+    launch_gemm128<GEMM_EPI_LOGITS>(ws, ws->head, dim3(cdiv(V, 128), 1, 1), st, ws->xh, ws->xl, V, H, H, b->head_blk, V, nullptr, nullptr, norope, 1, b->stt_head);
+    lm_batch_logits_rows_kernel<<<dim3(std::min((int)cdiv(V, 256), 64), NM), 256, 0, st>>>(tab, b->head_blk, V);
+    if (b->any_serial) {
+        if (b->any_patch) samp_prepare_batch_kernel<<<dim3(1, NM), 128, 0, st>>>(tab, V);
+        samp_hist_batch_kernel<<<dim3(128, NM), 256, 0, st>>>(tab, V);
+        samp_gather_batch_kernel<<<dim3(128, NM), 256, 0, st>>>(tab, V);
+        samp_final_batch_kernel<<<dim3(1, NM), 1024, 0, st>>>(tab, V);
+    }
+    for (int s = 0; s < NM; ++s)
+        if (b->m[s]->samp_full) lm_enqueue_sample(b->m[s], b->m[s]->logits, st);
+    lm_batch_tokens_kernel<<<1, LM_BATCH_MAX, 0, st>>>(tab, NM, b->tokens);
+    RCA_LAUNCH_CHECK();
+    e = hipMemcpyAsync(b->pin->tokens, b->tokens, sizeof(int) * LM_BATCH_MAX, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch step download: %s", hipGetErrorString(e));
+}
+extern "C" int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t n, int32_t* tokens) {
+    if (!b || !ids || !tokens) return fail(RCA_ERR_ARG, "batch_step: null argument");
+    const int NM = b->n_members;
+    if (n < 1 || n > LM_GEMV_M) return fail(RCA_ERR_ARG, "batch_step: %d tokens per member (1..%d)", n, LM_GEMV_M);
+    if (NM * n > LM_BATCH_ROWS) return fail(RCA_ERR_ARG, "batch_step: %d members x %d tokens = %d rows, a batch pass is one token block of %d", NM, n, NM * n, LM_BATCH_ROWS);
+    int rc;
+    for (int s = 0; s < NM; ++s)
+        if ((rc = lm_settle(b->m[s])) != RCA_OK) return rc;
+    // every refusal before anything is staged or enqueued: no member changes
+    for (int s = 0; s < NM; ++s) {
+        const rca_lm* h = b->m[s];
+        if (!h->sampler_set) return fail(RCA_ERR_STATE, "batch_step: member %d has no sampler (rca_lm_sampler_init)", s);
+        if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "batch_step: member %d was switched to logits_all after the batch was made", s);
+        if (lm_prefill_route(h) != LM_ROUTE_TILE128) return fail(RCA_ERR_STATE, "batch_step: member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", s, lm_prefill_route(h));
+        if (h->n_tokens + n > h->cfg.n_ctx) return fail(RCA_ERR_STATE, "batch_step: context overflow of member %d: %d + %d > n_ctx %d", s, h->n_tokens, n, h->cfg.n_ctx);
+        for (int j = 0; j < n; ++j)
+            if (ids[s * n + j] < 0 || ids[s * n + j] >= h->cfg.vocab_size)
+                return fail(RCA_ERR_ARG, "batch_step: token id %d of member %d at index %d is outside the vocabulary [0, %d)", ids[s * n + j], s, j, h->cfg.vocab_size);
+    }
+    RCA_HIP(hipSetDevice(b->m[0]->device));
+    hipStream_t st = b->m[0]->stream;
+    if ((rc = lm_batch_refresh(b)) != RCA_OK) return rc;
+    bool graphs = true;
+    int bucket = 0, nsp = 1, nsp_max = 1;
+    for (int s = 0; s < NM; ++s) {
+        const rca_lm* h = b->m[s];
+        graphs = graphs && h->graphs_enabled;
+        b->pin->in.n_tokens[s] = h->n_tokens;
+        for (int j = 0; j < n; ++j) b->pin->in.ids[s * n + j] = ids[s * n + j];
+        bucket = std::max(bucket, lm_bucket(h, n, -1).bucket);
+        nsp = std::max(nsp, lm_splits_needed(h, n));
+        nsp_max = std::max(nsp_max, h->n_splits);
+    }
+    if (graphs) {
+        // the split count of the largest bucket among the members (a split past a member's cache leaves at once)
+        const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? nsp_max : std::min(nsp_max, 4 << bucket);
+        hipGraphExec_t& gexec = b->g[n - 1][bucket];
+        if (!gexec && (rc = lm_capture(st, &gexec, "batch step", [&]() -> int { return lm_batch_enqueue(b, n, nsp_bucket, st); })) != RCA_OK) return rc;
+        RCA_HIP(hipGraphLaunch(gexec, st));
+    } else if ((rc = lm_batch_enqueue(b, n, nsp, st)) != RCA_OK) {
+        return rc;
+    }
+    RCA_HIP(hipStreamSynchronize(st));
+    for (int s = 0; s < NM; ++s) {
+        rca_lm* h = b->m[s];
+        h->n_tokens += n;
+        h->logits_rows = 1;
+        h->rng_host += 1;
+        tokens[s] = b->pin->tokens[s];
     }
     return RCA_OK;
 }

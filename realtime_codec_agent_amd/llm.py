@@ -841,6 +841,53 @@ class LlamaGroup:
             pass
 
 
+class LlamaBatch:
+    """2 to 64 sessions over ONE set of weights (a handle and its share_weights_with= twins) stepped together as one token block of the
+    128-token MFMA tiles (rca_lm_batch_step; llama.cpp's -np N above 4): every projection is one tile GEMM over all members' rows,
+    attention one launch per layer, the head one tile GEMM, the top-k sampler one chain.  Needs a model whose long evals take the
+    128-token tiles; smaller models stay with LlamaGroup.  Unlike a group step a batch step is NOT bit-identical to step(): it is in
+    the arithmetic class of a decode on a tile-built cache, and a member's result does not depend on its slot or companions.
+    step() / eval() / sample() on a member, group steps and batch steps mix freely.  Close the batch before its members."""
+
+    def __init__(self, members: Sequence["LlamaForAlternatingCodeChannels"], lib=None):
+        self.members = list(members)
+        self._lib = lib if lib is not None else N.lib()
+        self._b = C.c_void_p()
+        handles = (C.c_void_p * len(self.members))(*[m._h for m in self.members])
+        N.check(self._lib.rca_lm_batch_create(handles, len(self.members), C.byref(self._b)), "rca_lm_batch_create")
+
+    def step(self, tokens_per_member: Sequence[Sequence[int]]) -> List[int]:
+        """Member s evaluates tokens_per_member[s] (all of one length n = 1 or 2, len(members) * n <= 128) at its own n_tokens and
+        samples with its own sampler; returns the sampled token of every member.  A refusal (context overflow of any member, an id
+        outside the vocabulary, a member without a sampler) raises and leaves every member as it was."""
+        rows = [list(t) for t in tokens_per_member]
+        if len(rows) != len(self.members):
+            raise ValueError(f"{len(rows)} token lists for {len(self.members)} members")
+        n = len(rows[0])
+        if any(len(r) != n for r in rows):
+            raise ValueError("every member evaluates the same number of tokens in a batch step")
+        starts = [m.n_tokens for m in self.members]
+        flat = [t for r in rows for t in r]
+        arr = (C.c_int32 * max(len(flat), 1))(*flat)
+        out = (C.c_int32 * len(self.members))()
+        N.check(self._lib.rca_lm_batch_step(self._b, arr, n, out), "rca_lm_batch_step")
+        for m, n0, r in zip(self.members, starts, rows):
+            m._input_ids[n0:n0 + n] = r
+            m._logits_valid = False
+        return [int(t) for t in out]
+
+    def close(self) -> None:
+        if getattr(self, "_b", None) is not None and self._b:
+            self._lib.rca_lm_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ScoreResult:
     """What score() returns: one numpy array per field of rca_score_row_t, one entry per position.  logprob / lse / max_logit /
     argmax of the scored handle; with a base also kl = KL(P_base || P), base_logprob and base_argmax (None without one).
