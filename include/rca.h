@@ -493,6 +493,31 @@ typedef struct rca_lm_batch rca_lm_batch_t;
 int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, rca_lm_batch_t** out);
 int rca_lm_batch_destroy(rca_lm_batch_t* b);
 int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t n, int32_t* tokens);
+/* Batch frame: rca_lm_frame (below) for every member of a batch in ONE call -- the unit of work of N duplex sessions on a card.
+ * first_pairs [n_members][2], user_ids [n_members][n_steps], probe_ids [n_members] or NULL (-1: no probe for that member),
+ * out_tokens [n_members][n_steps], n_done [n_members], probe_probs [n_members] or NULL.  n_steps is 1..8, n_members * 2 <= 128.
+ *   Step i of member s evaluates its current pair -- first_pairs[s] for i = 0, then [token it sampled at step i - 1,
+ *   user_ids[s][i - 1]] -- at ITS position through the batch pass of rca_lm_batch_step and samples with ITS sampler; the feedback
+ *   happens on the device.  The whole frame is one linear launch sequence on member 0's stream: one upload, one synchronisation,
+ *   one download.  With graphs enabled on every member it is one replay, captured per (n_steps, largest context bucket among the
+ *   members at the frame's END, probes on / off) and re-captured under the rule of the batch step's graphs; with graphs off on any
+ *   member it is eager.  Every step is a batch step's launches with a batch step's arguments, so member s ends the frame, bit for
+ *   bit, as n_done[s] rca_lm_batch_step calls of n = 2 with the tokens fed back by the caller would have left it.
+ *   Every member runs all n_steps steps; what stands is settled per member, with rca_lm_frame's semantics:
+ *     - n_done[s] = n_steps, or j + 1 for the first step j whose token is <= audio_id_floor; out_tokens[s][i] = -1 for i >= n_done[s];
+ *     - the member ends with n_tokens += 2 * n_done[s] and its draw counter at + n_done[s], on the host mirror and on the device
+ *       (one small launch over the cut members); the cache slots and penalty-window entries of the discarded steps are stale and get
+ *       overwritten, exactly as after a cut rca_lm_frame;
+ *     - a member with n_done[s] < n_steps has NO logits: get_logits / sample / token_probs fail with "no logits" until its next
+ *       eval or step; a complete member has its last step's logits in its own buffer.
+ *   With probe_ids, probe_probs[s] = softmax(last logits of member s)[probe_ids[s]], computed inside the same replay with
+ *   rca_lm_token_probs' arithmetic; -1 where the member was cut or its probe id is -1.
+ *   Refused before anything is staged, with NO member changed: what rca_lm_batch_step refuses, n_steps outside 1..8, an id of a first
+ *   pair, a user id or a probe id outside the vocabulary, probe_probs NULL while probe_ids is not (RCA_ERR_ARG); a context overflow
+ *   of ANY member counted with 2 * n_steps (RCA_ERR_STATE).  Messages name the member.  Single-handle calls, group steps, batch
+ *   steps and batch frames may be interleaved freely on the same handles. */
+int rca_lm_batch_frame(rca_lm_batch_t* b, const int32_t* first_pairs, const int32_t* user_ids, int32_t n_steps, int32_t audio_id_floor,
+                       const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done, float* probe_probs);
 /* One whole frame of process_audio_input_ids (realtime_agent_v2.py:332-372) as ONE hipGraph: n_steps (<= 8) S=2 steps, the
  * agent token sampled by step i fed back on the device together with user_ids[i] as step i+1's input pair; first_pair is the
  * pair step 0 evaluates (the last two ids of the sequence).  out_tokens[i] = token sampled by step i.  *n_done = number of steps

@@ -411,7 +411,7 @@ ABI_SYMBOLS = [
     "rca_lm_kv_write", "rca_lm_attn_tap", "rca_lm_score", "rca_lm_score_rows_tap",
     "rca_duplex_frame", "rca_codec_workspace_sig", "rca_codec_stream_handoff", "rca_codec_codebook_size", "rca_codec_set_mfma_mode", "rca_lm_step_probe", "rca_duplex_prepare", "rca_duplex_precapture",
     "rca_lm_group_create", "rca_lm_group_destroy", "rca_lm_group_step",
-    "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step",
+    "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
 ]
 
 

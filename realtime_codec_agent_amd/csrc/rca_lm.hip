@@ -1748,7 +1748,8 @@ __global__ __launch_bounds__(1024) void samp_big_pick_kernel(const float* __rest
 // softmax(logits)[ids] in two launches (the agent asks for P(<|end_audio|>) once per frame, realtime_agent_v2.py:448-452):
 // 64 workgroups reduce a slice each to (max, sum of exp relative to it); one wave merges the slices in slice order.
 #define PROBS_SLICES 64
-__global__ __launch_bounds__(1024) void lm_softmax_slices_kernel(const float* __restrict__ logits, int V, float* __restrict__ part) {
+// (bodies: shared with the table forms of rca_lm_batch_frame, which take the member's logits from grid y)
+__device__ __forceinline__ void lm_softmax_slices_body(const float* __restrict__ logits, int V, float* __restrict__ part) {
     __shared__ float red[16];
     __shared__ float smax;
     const int per = (V + PROBS_SLICES - 1) / PROBS_SLICES;
@@ -1774,8 +1775,11 @@ __global__ __launch_bounds__(1024) void lm_softmax_slices_kernel(const float* __
         part[2 * blockIdx.x + 1] = t;
     }
 }
-__global__ __launch_bounds__(64) void lm_token_probs_kernel(const float* __restrict__ logits, int V, const float* __restrict__ part,
-                                                            const int* __restrict__ ids, int n, float* __restrict__ probs) {
+__global__ __launch_bounds__(1024) void lm_softmax_slices_kernel(const float* __restrict__ logits, int V, float* __restrict__ part) {
+    lm_softmax_slices_body(logits, V, part);
+}
+__device__ __forceinline__ void lm_token_probs_body(const float* __restrict__ logits, int V, const float* __restrict__ part,
+                                                    const int* __restrict__ ids, int n, float* __restrict__ probs) {
     const float pm = part[2 * threadIdx.x], ps = part[2 * threadIdx.x + 1];   // PROBS_SLICES == 64 lanes
     const float mx = wave_max(pm);
     const float contrib = (pm == -INFINITY) ? 0.0f : ps * __expf(pm - mx);
@@ -1785,6 +1789,10 @@ __global__ __launch_bounds__(64) void lm_token_probs_kernel(const float* __restr
         const int id = ids[threadIdx.x];
         probs[threadIdx.x] = (id >= 0 && id < V) ? __expf(logits[id] - mx) / tot : 0.0f;
     }
+}
+__global__ __launch_bounds__(64) void lm_token_probs_kernel(const float* __restrict__ logits, int V, const float* __restrict__ part,
+                                                            const int* __restrict__ ids, int n, float* __restrict__ probs) {
+    lm_token_probs_body(logits, V, part, ids, n, probs);
 }
 
 // ------------------------------------------------------------------------- random init (bench)
@@ -5465,7 +5473,10 @@ extern "C" int rca_lm_group_step(rca_lm_group_t* g, const int32_t* ids, int32_t 
 #define LM_BATCH_MAX 64
 #define LM_BATCH_ROWS 128   // one token block
 struct LmBatchStage { int n_tokens[LM_BATCH_MAX]; int ids[LM_BATCH_ROWS]; };
-struct LmBatchPin { LmBatchStage in; int tokens[LM_BATCH_MAX]; };
+// rca_lm_batch_frame: the step's block (the first pairs in ids), then the user's token of every step and the probe id of every member
+struct LmBatchFrameStage : LmBatchStage { int user[LM_BATCH_MAX * LM_FRAME_MAX]; int probe[LM_BATCH_MAX]; };
+struct LmBatchFrameOut { int tokens[LM_BATCH_MAX * LM_FRAME_MAX]; float probs[LM_BATCH_MAX]; };
+struct LmBatchPin { LmBatchFrameStage in; int tokens[LM_BATCH_MAX]; LmBatchFrameOut frame; };
 struct rca_lm_batch {
     int n_members = 0;
     rca_lm* m[LM_BATCH_MAX] = {};
@@ -5477,10 +5488,14 @@ struct rca_lm_batch {
     LmDevState* stt = nullptr;        // device: the pass over all rows (m = n_members * n, the rows' ids)
     LmDevState* stt_head = nullptr;   // device: the head's pass (m = n_members)
     float* head_blk = nullptr;        // device, [n_members][V]: the head GEMM's block
-    LmBatchStage* stage = nullptr;    // device copy of pin->in
+    LmBatchFrameStage* stage = nullptr;   // device copy of pin->in (a step uploads its LmBatchStage head only)
     int* tokens = nullptr;            // device: the members' sampled tokens, gathered for one download
     LmBatchPin* pin = nullptr;        // pinned
     hipGraphExec_t g[LM_GEMV_M][LM_GRAPH_BUCKETS] = {};   // (n, largest context bucket among the members)
+    // rca_lm_batch_frame
+    LmBatchFrameOut* frame_out = nullptr;   // device: every step's tokens and the probes, gathered for one download
+    float* probe_part = nullptr;            // device, [n_members][PROBS_SLICES (max, sum) pairs]
+    hipGraphExec_t fg[LM_FRAME_MAX][LM_GRAPH_BUCKETS][2] = {};   // (n_steps - 1, largest context bucket at the frame's end, probes)
 };
 // the pass's state and the members' step states, from one staging block
 __global__ void lm_batch_stage_kernel(const LmBatchStage* __restrict__ in, const LmBatchMember* __restrict__ tab, LmDevState* __restrict__ bstt,
@@ -5531,10 +5546,45 @@ __global__ __launch_bounds__(1024) void samp_final_batch_kernel(const LmBatchMem
 __global__ void lm_batch_tokens_kernel(const LmBatchMember* __restrict__ tab, int n_members, int* __restrict__ out) {
     if ((int)threadIdx.x < n_members) out[threadIdx.x] = tab[threadIdx.x].stt->out_token;
 }
+// rca_lm_batch_frame, behind the samplers of step `step`: what the SampTail feedback does for one handle, for all members at once.
+// Records the token, advances the member's position past the pair just evaluated and makes [token, user's token of this step] the
+// next pair -- in the member's own step state (attention, RoPE rows and its sampler read it) and in the pass's id list (the
+// embedding gather reads that one).
+__global__ void lm_batch_feedback_kernel(const LmBatchFrameStage* __restrict__ in, const LmBatchMember* __restrict__ tab, LmDevState* __restrict__ bstt,
+                                         LmBatchFrameOut* __restrict__ out, int n_members, int step) {
+    const int t = threadIdx.x;
+    if (t >= n_members) return;
+    LmDevState* stt = tab[t].stt;
+    const int tok = stt->out_token, user = in->user[t * LM_FRAME_MAX + step];
+    out->tokens[t * LM_FRAME_MAX + step] = tok;
+    stt->n_tokens += 2;
+    stt->ids[0] = tok;
+    stt->ids[1] = user;
+    bstt->ids[2 * t] = tok;
+    bstt->ids[2 * t + 1] = user;
+}
+// softmax(member's logits)[its probe id]: lm_softmax_slices_kernel / lm_token_probs_kernel with the member in grid y
+__global__ __launch_bounds__(1024) void lm_softmax_slices_batch_kernel(const LmBatchMember* __restrict__ tab, int V, float* __restrict__ part) {
+    lm_softmax_slices_body(tab[blockIdx.y].logits, V, part + (long)blockIdx.y * 2 * PROBS_SLICES);
+}
+__global__ __launch_bounds__(64) void lm_token_probs_batch_kernel(const LmBatchMember* __restrict__ tab, int V, const float* __restrict__ part,
+                                                                  const int* __restrict__ ids, float* __restrict__ probs) {
+    const int s = blockIdx.y;
+    lm_token_probs_body(tab[s].logits, V, part + (long)s * 2 * PROBS_SLICES, ids + s, 1, probs + s);
+}
+// a frame drew n_steps times for every member: the counters of the members it cut go back to where their accepted draws end
+struct LmBatchCuts { int n; int member[LM_BATCH_MAX]; unsigned long long counter[LM_BATCH_MAX]; };
+__global__ void lm_batch_counters_kernel(const LmBatchMember* __restrict__ tab, LmBatchCuts cuts) {
+    if ((int)threadIdx.x < cuts.n) tab[cuts.member[threadIdx.x]].stt->rng_counter = cuts.counter[threadIdx.x];
+}
 static void lm_batch_drop_graphs(rca_lm_batch* b) {
     for (auto& per_n : b->g)
         for (hipGraphExec_t& e : per_n)
             if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+    for (auto& per_n : b->fg)
+        for (auto& per_b : per_n)
+            for (hipGraphExec_t& e : per_b)
+                if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
 }
 extern "C" int rca_lm_batch_destroy(rca_lm_batch_t* b);
 extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, rca_lm_batch_t** out) {
@@ -5562,7 +5612,9 @@ extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, 
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->stt, sizeof(LmDevState));
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->stt_head, sizeof(LmDevState));
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->head_blk, (size_t)n_members * members[0]->cfg.vocab_size * 4);
-    if (rc == RCA_OK) rc = lm_alloc((void**)&b->stage, sizeof(LmBatchStage));
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->stage, sizeof(LmBatchFrameStage));
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->frame_out, sizeof(LmBatchFrameOut));
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->probe_part, sizeof(float) * 2 * PROBS_SLICES * n_members);
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->tokens, sizeof(int) * LM_BATCH_MAX);
     if (rc == RCA_OK && hipHostMalloc((void**)&b->pin, sizeof(LmBatchPin), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
     if (rc == RCA_OK && (hipMemset(b->stt, 0, sizeof(LmDevState)) != hipSuccess || hipMemset(b->stt_head, 0, sizeof(LmDevState)) != hipSuccess))
@@ -5575,7 +5627,8 @@ extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, 
 extern "C" int rca_lm_batch_destroy(rca_lm_batch_t* b) {
     if (!b) return RCA_OK;
     lm_batch_drop_graphs(b);
-    for (void* p : {(void*)b->rows, (void*)b->tab, (void*)b->stt, (void*)b->stt_head, (void*)b->head_blk, (void*)b->stage, (void*)b->tokens})
+    for (void* p : {(void*)b->rows, (void*)b->tab, (void*)b->stt, (void*)b->stt_head, (void*)b->head_blk, (void*)b->stage, (void*)b->tokens, (void*)b->frame_out,
+                    (void*)b->probe_part})
         if (p) (void)hipFree(p);
     if (b->pin) (void)hipHostFree(b->pin);
     delete b;
@@ -5612,8 +5665,9 @@ static int lm_batch_refresh(rca_lm_batch* b) {
     b->tabs_valid = true;
     return RCA_OK;
 }
-// upload of the staged states -> embedding -> the layers -> head -> samplers -> download of the tokens, all on `st`, one linear sequence
-static int lm_batch_enqueue(rca_lm_batch* b, int n, int nsp_launch, hipStream_t st) {
+// embedding -> the layers -> head -> samplers over the device states as they stand (staged by lm_batch_stage_kernel, or left by
+// lm_batch_feedback_kernel): the part a step and every step of a frame share
+static void lm_batch_enqueue_pass(rca_lm_batch* b, int n, int nsp_launch, hipStream_t st) {
     rca_lm* ws = b->m[0];
     const rca_lm_config_t& c = ws->cfg;
     const int NM = b->n_members, MT = NM * n;
@@ -5629,9 +5683,6 @@ static int lm_batch_enqueue(rca_lm_batch* b, int n, int nsp_launch, hipStream_t 
         (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
         attr_done = true;
     }
-    hipError_t e = hipMemcpyAsync(b->stage, &b->pin->in, sizeof(LmBatchStage), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch step upload: %s", hipGetErrorString(e));
-    lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->stage, tab, b->stt, b->stt_head, NM, n);
     // the k-split forms of one token block: what an rca_lm_eval_async pass of up to 128 tokens uses, so a row's sums are that pass's
     const int seq_min = g128_seq_min();
     const int so = g128_splits(H, AO), sg = g128_splits(2 * F, H), sd = g128_splits(H, F);
@@ -5685,10 +5736,26 @@ static int lm_batch_enqueue(rca_lm_batch* b, int n, int nsp_launch, hipStream_t 
     }
     for (int s = 0; s < NM; ++s)
         if (b->m[s]->samp_full) lm_enqueue_sample(b->m[s], b->m[s]->logits, st);
+}
+// upload of the staged states -> the pass -> download of the tokens, all on `st`, one linear sequence
+static int lm_batch_enqueue(rca_lm_batch* b, int n, int nsp_launch, hipStream_t st) {
+    const LmBatchMember* tab = b->tab + (size_t)(n - 1) * LM_BATCH_MAX;
+    const int NM = b->n_members;
+    hipError_t e = hipMemcpyAsync(b->stage, static_cast<const LmBatchStage*>(&b->pin->in), sizeof(LmBatchStage), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch step upload: %s", hipGetErrorString(e));
+    lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->stage, tab, b->stt, b->stt_head, NM, n);
+    lm_batch_enqueue_pass(b, n, nsp_launch, st);
     lm_batch_tokens_kernel<<<1, LM_BATCH_MAX, 0, st>>>(tab, NM, b->tokens);
     RCA_LAUNCH_CHECK();
     e = hipMemcpyAsync(b->pin->tokens, b->tokens, sizeof(int) * LM_BATCH_MAX, hipMemcpyDeviceToHost, st);
     return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch step download: %s", hipGetErrorString(e));
+}
+// what a step and a frame refuse alike about member s (`who` starts the message), before anything is staged
+static int lm_batch_member_ok(const rca_lm* h, int s, const char* who) {
+    if (!h->sampler_set) return fail(RCA_ERR_STATE, "%s: member %d has no sampler (rca_lm_sampler_init)", who, s);
+    if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "%s: member %d was switched to logits_all after the batch was made", who, s);
+    if (lm_prefill_route(h) != LM_ROUTE_TILE128) return fail(RCA_ERR_STATE, "%s: member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", who, s, lm_prefill_route(h));
+    return RCA_OK;
 }
 extern "C" int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t n, int32_t* tokens) {
     if (!b || !ids || !tokens) return fail(RCA_ERR_ARG, "batch_step: null argument");
@@ -5701,9 +5768,7 @@ extern "C" int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t 
     // every refusal before anything is staged or enqueued: no member changes
     for (int s = 0; s < NM; ++s) {
         const rca_lm* h = b->m[s];
-        if (!h->sampler_set) return fail(RCA_ERR_STATE, "batch_step: member %d has no sampler (rca_lm_sampler_init)", s);
-        if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "batch_step: member %d was switched to logits_all after the batch was made", s);
-        if (lm_prefill_route(h) != LM_ROUTE_TILE128) return fail(RCA_ERR_STATE, "batch_step: member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", s, lm_prefill_route(h));
+        if ((rc = lm_batch_member_ok(h, s, "batch_step")) != RCA_OK) return rc;
         if (h->n_tokens + n > h->cfg.n_ctx) return fail(RCA_ERR_STATE, "batch_step: context overflow of member %d: %d + %d > n_ctx %d", s, h->n_tokens, n, h->cfg.n_ctx);
         for (int j = 0; j < n; ++j)
             if (ids[s * n + j] < 0 || ids[s * n + j] >= h->cfg.vocab_size)
@@ -5739,6 +5804,113 @@ extern "C" int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t 
         h->logits_rows = 1;
         h->rng_host += 1;
         tokens[s] = b->pin->tokens[s];
+    }
+    return RCA_OK;
+}
+
+// ------------------------------------------------------------------------------------ batch frame (rca_lm_batch_frame)
+// rca_lm_frame for every member of a batch in one launch sequence: n_steps times the batch pass over pairs (lm_batch_enqueue_pass, the
+// launches of a 2-token batch step) with lm_batch_feedback_kernel between them, then the probes.  Every member runs every step -- a
+// row cannot leave a captured graph -- and the host settles afterwards which steps of a member stand, as lm_frame_core does for one.
+static int lm_batch_frame_enqueue(rca_lm_batch* b, int n_steps, int nsp_launch, bool probes, hipStream_t st) {
+    const LmBatchMember* tab = b->tab + (size_t)(2 - 1) * LM_BATCH_MAX;
+    const int NM = b->n_members, V = b->m[0]->cfg.vocab_size;
+    hipError_t e = hipMemcpyAsync(b->stage, &b->pin->in, sizeof(LmBatchFrameStage), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch frame upload: %s", hipGetErrorString(e));
+    lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->stage, tab, b->stt, b->stt_head, NM, 2);
+    for (int i = 0; i < n_steps; ++i) {
+        lm_batch_enqueue_pass(b, 2, nsp_launch, st);
+        lm_batch_feedback_kernel<<<1, LM_BATCH_MAX, 0, st>>>(b->stage, tab, b->stt, b->frame_out, NM, i);
+    }
+    if (probes) {
+        lm_softmax_slices_batch_kernel<<<dim3(PROBS_SLICES, NM), 1024, 0, st>>>(tab, V, b->probe_part);
+        lm_token_probs_batch_kernel<<<dim3(1, NM), 64, 0, st>>>(tab, V, b->probe_part, b->stage->probe, b->frame_out->probs);
+    }
+    RCA_LAUNCH_CHECK();
+    e = hipMemcpyAsync(&b->pin->frame, b->frame_out, sizeof(LmBatchFrameOut), hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch frame download: %s", hipGetErrorString(e));
+}
+extern "C" int rca_lm_batch_frame(rca_lm_batch_t* b, const int32_t* first_pairs, const int32_t* user_ids, int32_t n_steps, int32_t audio_id_floor,
+                                  const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done, float* probe_probs) {
+    if (!b || !first_pairs || !user_ids || !out_tokens || !n_done) return fail(RCA_ERR_ARG, "batch_frame: null argument");
+    if (probe_ids && !probe_probs) return fail(RCA_ERR_ARG, "batch_frame: probe_ids without probe_probs");
+    const int NM = b->n_members;
+    if (n_steps < 1 || n_steps > LM_FRAME_MAX) return fail(RCA_ERR_ARG, "batch_frame: %d steps (1..%d)", n_steps, LM_FRAME_MAX);
+    if (NM * 2 > LM_BATCH_ROWS) return fail(RCA_ERR_ARG, "batch_frame: %d members x 2 tokens = %d rows, a batch pass is one token block of %d", NM, NM * 2, LM_BATCH_ROWS);
+    int rc;
+    for (int s = 0; s < NM; ++s)
+        if ((rc = lm_settle(b->m[s])) != RCA_OK) return rc;
+    // every refusal before anything is staged or enqueued: no member changes
+    for (int s = 0; s < NM; ++s) {
+        const rca_lm* h = b->m[s];
+        const int V = h->cfg.vocab_size;
+        if ((rc = lm_batch_member_ok(h, s, "batch_frame")) != RCA_OK) return rc;
+        if (h->n_tokens + 2 * n_steps > h->cfg.n_ctx)
+            return fail(RCA_ERR_STATE, "batch_frame: context overflow of member %d: %d + %d > n_ctx %d", s, h->n_tokens, 2 * n_steps, h->cfg.n_ctx);
+        for (int j = 0; j < 2; ++j)
+            if (first_pairs[s * 2 + j] < 0 || first_pairs[s * 2 + j] >= V)
+                return fail(RCA_ERR_ARG, "batch_frame: token id %d of member %d at index %d of its first pair is outside the vocabulary [0, %d)", first_pairs[s * 2 + j], s, j, V);
+        for (int i = 0; i < n_steps; ++i)
+            if (user_ids[s * n_steps + i] < 0 || user_ids[s * n_steps + i] >= V)
+                return fail(RCA_ERR_ARG, "batch_frame: user token id %d of member %d at step %d is outside the vocabulary [0, %d)", user_ids[s * n_steps + i], s, i, V);
+        if (probe_ids && (probe_ids[s] < -1 || probe_ids[s] >= V))
+            return fail(RCA_ERR_ARG, "batch_frame: probe id %d of member %d is outside the vocabulary [0, %d) (-1: no probe)", probe_ids[s], s, V);
+    }
+    RCA_HIP(hipSetDevice(b->m[0]->device));
+    hipStream_t st = b->m[0]->stream;
+    if ((rc = lm_batch_refresh(b)) != RCA_OK) return rc;
+    const bool probes = probe_ids != nullptr;
+    bool graphs = true;
+    int bucket = 0, nsp = 1, nsp_max = 1;
+    LmBatchFrameStage& in = b->pin->in;
+    for (int s = 0; s < NM; ++s) {
+        const rca_lm* h = b->m[s];
+        graphs = graphs && h->graphs_enabled;
+        in.n_tokens[s] = h->n_tokens;
+        for (int j = 0; j < 2; ++j) in.ids[s * 2 + j] = first_pairs[s * 2 + j];
+        for (int i = 0; i < LM_FRAME_MAX; ++i) in.user[s * LM_FRAME_MAX + i] = i < n_steps ? user_ids[s * n_steps + i] : 0;
+        in.probe[s] = probes ? probe_ids[s] : -1;
+        // the bucket and the splits of the frame's END (as lm_frame_core): a frame that crosses a bucket or a 256-key split inside
+        // itself has the splits its last step needs; its earlier steps leave the extra ones at once
+        bucket = std::max(bucket, lm_bucket(h, 2 * n_steps, -1).bucket);
+        nsp = std::max(nsp, lm_splits_needed(h, 2 * n_steps));
+        nsp_max = std::max(nsp_max, h->n_splits);
+    }
+    if (graphs) {
+        const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? nsp_max : std::min(nsp_max, 4 << bucket);
+        hipGraphExec_t& gexec = b->fg[n_steps - 1][bucket][probes ? 1 : 0];
+        if (!gexec && (rc = lm_capture(st, &gexec, "batch frame", [&]() -> int { return lm_batch_frame_enqueue(b, n_steps, nsp_bucket, probes, st); })) != RCA_OK) return rc;
+        RCA_HIP(hipGraphLaunch(gexec, st));
+    } else if ((rc = lm_batch_frame_enqueue(b, n_steps, nsp, probes, st)) != RCA_OK) {
+        return rc;
+    }
+    RCA_HIP(hipStreamSynchronize(st));
+    const LmBatchFrameOut& out = b->pin->frame;
+    LmBatchCuts cuts;
+    cuts.n = 0;
+    for (int s = 0; s < NM; ++s) {
+        rca_lm* h = b->m[s];
+        int done = n_steps;
+        for (int i = 0; i < n_steps; ++i) {
+            out_tokens[s * n_steps + i] = out.tokens[s * LM_FRAME_MAX + i];
+            if (out_tokens[s * n_steps + i] <= audio_id_floor) { done = i + 1; break; }
+        }
+        for (int i = done; i < n_steps; ++i) out_tokens[s * n_steps + i] = -1;
+        n_done[s] = done;
+        h->n_tokens += 2 * done;
+        // a member cut short holds the logits of a LATER step (evaluated on a wrong-guess pair): nothing may read them
+        h->logits_rows = done < n_steps ? 0 : 1;
+        h->rng_host += (unsigned long long)done;
+        if (done < n_steps) {
+            cuts.member[cuts.n] = s;
+            cuts.counter[cuts.n++] = h->rng_host;
+        }
+        if (probes) probe_probs[s] = done < n_steps || probe_ids[s] < 0 ? -1.0f : out.probs[s];
+    }
+    if (cuts.n) {   // the device drew n_steps times for these: their counters go where the step-by-step loop would be, in one launch
+        lm_batch_counters_kernel<<<1, LM_BATCH_MAX, 0, st>>>(b->tab + (size_t)(2 - 1) * LM_BATCH_MAX, cuts);
+        RCA_LAUNCH_CHECK();
+        RCA_HIP(hipStreamSynchronize(st));
     }
     return RCA_OK;
 }

@@ -876,6 +876,51 @@ class LlamaBatch:
             m._logits_valid = False
         return [int(t) for t in out]
 
+    def frame(self, first_pairs: Sequence[Sequence[int]], user_ids: Sequence[Sequence[int]], audio_id_floor: int,
+              probe_ids: Optional[Sequence[int]] = None):
+        """frame() of every member in ONE call (rca_lm_batch_frame; one graph replay when every member has graphs on): member s runs
+        len(user_ids[s]) S=2 steps from first_pairs[s] with its sampled token fed back on the device.  Returns (tokens, probe_probs):
+        tokens[s] is the list of member s's sampled tokens, shorter than user_ids[s] when a step sampled a token <= audio_id_floor
+        (the cutting token is its last element; the member's n_tokens and draw counter are then what that many batch steps leave and
+        it has no logits until its next eval or step).  probe_probs is None without probe_ids, else a float32 array with
+        softmax(member s's last logits)[probe_ids[s]], NaN where the member was cut or its probe id is -1.  A refusal raises and
+        leaves every member as it was."""
+        pairs = [[int(t) for t in p] for p in first_pairs]
+        users = [[int(t) for t in u] for u in user_ids]
+        nm = len(self.members)
+        if len(pairs) != nm or len(users) != nm:
+            raise ValueError(f"{len(pairs)} first pairs and {len(users)} user id lists for {nm} members")
+        if any(len(p) != 2 for p in pairs):
+            raise ValueError("frame() starts from the last [agent, user] pair of every member")
+        n = len(users[0])
+        if any(len(u) != n for u in users):
+            raise ValueError("every member runs the same number of steps in a batch frame")
+        probes = None
+        if probe_ids is not None:
+            probes = [int(p) for p in probe_ids]
+            if len(probes) != nm:
+                raise ValueError(f"{len(probes)} probe ids for {nm} members")
+        starts = [m.n_tokens for m in self.members]
+        fp = (C.c_int32 * (2 * nm))(*[t for p in pairs for t in p])
+        us = (C.c_int32 * max(nm * n, 1))(*[t for u in users for t in u])
+        out = (C.c_int32 * max(nm * n, 1))()
+        done = (C.c_int32 * nm)()
+        pid = (C.c_int32 * nm)(*probes) if probes is not None else None
+        pp = (C.c_float * nm)() if probes is not None else None
+        N.check(self._lib.rca_lm_batch_frame(self._b, fp, us, n, int(audio_id_floor), pid, out, done, pp), "rca_lm_batch_frame")
+        tokens = []
+        for s, (m, n0) in enumerate(zip(self.members, starts)):
+            toks = [int(t) for t in out[s * n:s * n + done[s]]]
+            evaluated = pairs[s] + [t for pair in zip(toks[:-1], users[s]) for t in pair]
+            m._input_ids[n0:n0 + len(evaluated)] = evaluated
+            m._logits_valid = False
+            tokens.append(toks)
+        if probes is None:
+            return tokens, None
+        probs = np.array(pp[:], dtype=np.float32)
+        probs[probs < 0.0] = np.nan
+        return tokens, probs
+
     def close(self) -> None:
         if getattr(self, "_b", None) is not None and self._b:
             self._lib.rca_lm_batch_destroy(self._b)
