@@ -518,6 +518,33 @@ int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t n, int32_t*
  *   steps and batch frames may be interleaved freely on the same handles. */
 int rca_lm_batch_frame(rca_lm_batch_t* b, const int32_t* first_pairs, const int32_t* user_ids, int32_t n_steps, int32_t audio_id_floor,
                        const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done, float* probe_probs);
+/* Selection frame: rca_lm_batch_frame over a SUBSET of the members -- a session sits a tick out while its codec windows fill, on a
+ * forced transcription or response, when a trim falls between two steps, after it left audio mode, or when its chunk has not arrived.
+ * sel [n_sel]: distinct member indices of the batch in any order, n_sel in 1..n_members.  Every per-member array is indexed by k, the
+ * position in sel, NOT by member: first_pairs [n_sel][2], user_ids [n_sel][n_steps], probe_ids [n_sel] or NULL, out_tokens
+ * [n_sel][n_steps], n_done [n_sel], probe_probs [n_sel] or NULL.  Per selected member the semantics are rca_lm_batch_frame's: cut,
+ * roll-back, probes, "no logits" after a cut.
+ *   Contract, bit for bit: a selected member ends as rca_lm_batch_frame on a batch created over ONLY the selected members would leave
+ *   it (a member does not depend on slot or companions).  An unselected member is not touched at all: no byte of its K / V cache (rows
+ *   at and past its n_tokens included), not its n_tokens, logits buffer or logits_rows, not its draw counter, penalty window or device
+ *   state; pending rca_lm_eval_async work of an unselected member is not waited for.  An unselected member with a full cache or
+ *   without a sampler is no reason to refuse.  (The pass runs on member 0's stream in member 0's activation workspace, selected or not.)
+ *   Refused before anything is staged, with NO member changed, in a message that names k and the member: n_sel outside 1..n_members,
+ *   an index outside the batch, an index selected twice (RCA_ERR_ARG), and everything rca_lm_batch_frame refuses, checked on the
+ *   selected members only.
+ *   The selected members are compacted into slots 0 .. n_sel - 1 of device tables composed on the host for this call and uploaded with
+ *   the frame's block inside the replay; the launches cover the selection's geometry class -- n_sel rounded up to 8, 16, 32 or 64
+ *   slots -- and every kernel leaves at once for a slot past the live count, which travels in the uploaded block.  A graph therefore
+ *   holds no member's pointer: it is captured per (class, n_steps, largest context bucket among the SELECTED members at the frame's
+ *   end, probes on / off, a logit-patching sampler among the selected) and serves every selection of its class, also after a member's
+ *   rca_lm_swap_kv.  It is re-captured when a member's own graphs are dropped (a sampler of another kind, rca_lm_set_act_format, ...).
+ *   A selection that holds a member on a whole-vocabulary sampler (top_k 0 or above 256: its own launches with its own pointers), or a
+ *   member with graphs off, runs the same launches eagerly: same results. */
+int rca_lm_batch_frame_sel(rca_lm_batch_t* b, const int32_t* sel, int32_t n_sel, const int32_t* first_pairs, const int32_t* user_ids,
+                           int32_t n_steps, int32_t audio_id_floor, const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done,
+                           float* probe_probs);
+/* graph captures made by this batch so far (batch steps, batch frames and selection frames) */
+int rca_lm_batch_captures(const rca_lm_batch_t* b, int64_t* n);
 /* One whole frame of process_audio_input_ids (realtime_agent_v2.py:332-372) as ONE hipGraph: n_steps (<= 8) S=2 steps, the
  * agent token sampled by step i fed back on the device together with user_ids[i] as step i+1's input pair; first_pair is the
  * pair step 0 evaluates (the last two ids of the sequence).  out_tokens[i] = token sampled by step i.  *n_done = number of steps
@@ -559,6 +586,42 @@ typedef struct rca_duplex_frame_out {
 } rca_duplex_frame_out_t;
 int rca_duplex_frame(rca_lm_t* lm, rca_codec_t* codec, const rca_duplex_frame_args_t* args, rca_duplex_frame_out_t* out,
                      float* pcm_out_host);
+/* Duplex batch frame: rca_duplex_frame for every selected member of a batch in ONE call -- encode tails -> ids -> the selection frame
+ * (rca_lm_batch_frame_sel) -> codes -> decode tails -> probes for N sessions.  All members of one call share one call shape, the
+ * steady-state shape AudioTokenizer.duplex_plan produces.  One upload, ONE linear launch sequence on member 0's stream (no side-stream
+ * fork: at these sizes the encode tails are a fraction of a batch pass, and a captured graph without parallel branches is the plainer
+ * shape), one download, one synchronisation.  The user's ids of the frame's block are written on the device by the table form of the
+ * codes -> ids kernel; the sampled tokens go behind each row's context codes through the table form of the ids -> codes kernel, which
+ * raises a flag per member.  The codec tails run over the row count of the selection's geometry class (8, 16, 32 or 64): the rows past
+ * the selection hold code 0 and stale finite PCM and their results are not read, which keeps one codec shape per class.
+ * Per member k, bit for bit what rca_duplex_frame gives one handle: user_codes = the encode tail of that window alone (B = 1); tokens,
+ * n_done, the member's state and probe_prob = rca_lm_batch_frame_sel with code_token_base + code as user ids (so the batch's
+ * arithmetic class: a session inside a batch samples other tokens than the same session alone); flags bit 0 when a sampled token is no
+ * codec token (its code is 0 for the decode), bit 1 when the member was cut; the PCM row pcm_out_host + k * n_samples = the decode tail of
+ * (code_ctx[k] + the new codes) alone, copied only when flags[k] == 0 -- otherwise the row is untouched and the caller decodes on its own path.
+ * The first call of a (class, shape) runs eagerly and sizes the codec workspace; later calls replay a graph keyed by class, shape, base,
+ * probes on / off, context bucket, rca_codec_workspace_sig and the codec (a selection with a whole-vocabulary sampler or graphs off
+ * stays eager).  Refused before anything is staged, with NO member changed: what rca_lm_batch_frame_sel refuses, a bad shape, n_steps
+ * codes not inside the window, n_samples > (F_ctx + n_steps) * hop, a base that puts codes outside the vocabulary, a context code outside
+ * the codebook.  Buffers, pinned staging and graphs belong to the batch: rca_lm_batch_destroy frees them. */
+typedef struct rca_duplex_batch_args {
+    const int32_t* sel;         /* members taking part this tick */
+    int32_t n_sel;
+    const float* pcm_windows;   /* host [n_sel][T] */
+    const int64_t* code_ctx;    /* host [n_sel][F_ctx], NULL when F_ctx = 0 */
+    const int32_t* first_pairs; /* [n_sel][2] */
+    const int32_t* probe_ids;   /* [n_sel] (-1: none) or NULL */
+    int32_t T, F_ctx, n_steps, n_samples, code_token_base, audio_id_floor;
+} rca_duplex_batch_args_t;
+typedef struct rca_duplex_batch_out {   /* caller-allocated arrays, indexed by k */
+    int64_t* user_codes;        /* [n_sel][8] */
+    int32_t* tokens;            /* [n_sel][8], -1 from n_done on */
+    int32_t* n_done;            /* [n_sel] */
+    int32_t* flags;             /* [n_sel], rca_duplex_frame's bits */
+    float* probe_prob;          /* [n_sel], -1 as rca_duplex_frame */
+} rca_duplex_batch_out_t;
+int rca_duplex_batch_frame(rca_lm_batch_t* b, rca_codec_t* codec, const rca_duplex_batch_args_t* a, rca_duplex_batch_out_t* out,
+                           float* pcm_out_host /* [n_sel][n_samples] */);
 /* Optional: make rca_duplex_frame's one-time allocations for a call shape (pinned staging, device buffers, side stream) ahead of the
  * first frame -- a session calls it at reset() (realtime_agent_v2.py:127-161) so that no frame pays for a pinned allocation. */
 int rca_duplex_prepare(rca_lm_t* lm, int32_t T, int32_t F_ctx, int32_t n_steps, int32_t n_samples);

@@ -12,6 +12,7 @@ _LAZY = {
     "RealtimeAgent": ".realtime_agent_v2",
     "RealtimeAgentV2": ".realtime_agent_v2",
     "RealtimeAgentMultiprocessing": ".realtime_agent_v2",
+    "RealtimeAgentBatch": ".realtime_agent_batch",
     "LlamaForAlternatingCodeChannels": ".llm",
     "LlamaGroup": ".llm",
     "LlamaBatch": ".llm",

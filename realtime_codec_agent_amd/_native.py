@@ -293,6 +293,33 @@ class DuplexFrameOutC(C.Structure):
     ]
 
 
+class DuplexBatchArgsC(C.Structure):
+    _fields_ = [
+        ("sel", C.c_void_p),
+        ("n_sel", C.c_int32),
+        ("pcm_windows", C.c_void_p),
+        ("code_ctx", C.c_void_p),
+        ("first_pairs", C.c_void_p),
+        ("probe_ids", C.c_void_p),
+        ("T", C.c_int32),
+        ("F_ctx", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_samples", C.c_int32),
+        ("code_token_base", C.c_int32),
+        ("audio_id_floor", C.c_int32),
+    ]
+
+
+class DuplexBatchOutC(C.Structure):
+    _fields_ = [
+        ("user_codes", C.c_void_p),
+        ("tokens", C.c_void_p),
+        ("n_done", C.c_void_p),
+        ("flags", C.c_void_p),
+        ("probe_prob", C.c_void_p),
+    ]
+
+
 def sources() -> List[str]:
     return [os.path.join(CSRC_DIR, s) for s in HIP_SOURCES if os.path.exists(os.path.join(CSRC_DIR, s))]
 
@@ -412,6 +439,7 @@ ABI_SYMBOLS = [
     "rca_duplex_frame", "rca_codec_workspace_sig", "rca_codec_stream_handoff", "rca_codec_codebook_size", "rca_codec_set_mfma_mode", "rca_lm_step_probe", "rca_duplex_prepare", "rca_duplex_precapture",
     "rca_lm_group_create", "rca_lm_group_destroy", "rca_lm_group_step",
     "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
+    "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame",
 ]
 
 

@@ -2242,6 +2242,8 @@ struct rca_lm {
     bool graphs_enabled = true;
     unsigned long long graph_epoch = 0;   // bumped by whatever invalidates graphs captured over this handle (lm_drop_graphs, rca_lm_swap_kv): a group
                                           // (rca_lm_group_step) holds graphs over SEVERAL handles and compares before it replays one
+    unsigned long long drop_epoch = 0;    // bumped by lm_drop_graphs alone: a selection frame's graphs (rca_lm_batch_frame_sel) hold no cache pointer and
+                                          // outlive rca_lm_swap_kv, but not a moved buffer or another sampler chain
     bool mfma_prefill = true;   // evals longer than LM_PREFILL_MIN tokens use the bf16 MFMA tiles
     bool fuse_attn = true;      // decode steps merge the attention splits inside the attention launch (rca_lm_set_attn_fuse)
     int act_format = 0;         // activations of the decode GEMVs over packed matrices: 0 f32, 1 q8_1 blocks + integer dots (rca_lm_set_act_format)
@@ -2303,6 +2305,7 @@ static void lm_drop_graph_set(rca_lm::GraphSet& gs) {
 }
 static void lm_drop_graphs(rca_lm* h) {
     h->graph_epoch++;
+    h->drop_epoch++;
     for (auto& gs : h->gset) lm_drop_graph_set(gs);
     duplex_drop_graphs(h->duplex);
 }
@@ -3303,7 +3306,7 @@ __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __r
                                                            const LmBatchMember* __restrict__ tab = nullptr, int tab_layer = 0) {
     if constexpr (TAB) {
         const LmBatchMember e = tab[blockIdx.z];
-        if ((int)blockIdx.y >= e.n_splits) return;
+        if ((int)blockIdx.y >= e.n_splits) return;   // (also a slot past a selection's live count: an all-zero entry has no splits)
         stt = e.stt;
         qkv += (long)e.row0 * (nh + 2 * nkv) * 64;
         kc = e.kc + (long)tab_layer * e.kv_stride;
@@ -3700,6 +3703,7 @@ template <int G>
 __global__ __launch_bounds__(64) void lm_attn_mfma_batch_combine_kernel(const LmBatchMember* __restrict__ tab, int nh, int nkv, int nsp_launch,
                                                                         bf16_t* __restrict__ hi, bf16_t* __restrict__ lo) {
     const LmBatchMember e = tab[blockIdx.y];
+    if (!e.stt) return;   // a slot past the live count of a selection frame (rca_lm_batch_frame_sel): its table entry is all zero
     const int m = blockIdx.x / nh, head = blockIdx.x % nh;
     const int g = head / G, hq = head % G;
     const int r = m * G + hq;   // one query block per member
@@ -5477,6 +5481,12 @@ struct LmBatchStage { int n_tokens[LM_BATCH_MAX]; int ids[LM_BATCH_ROWS]; };
 struct LmBatchFrameStage : LmBatchStage { int user[LM_BATCH_MAX * LM_FRAME_MAX]; int probe[LM_BATCH_MAX]; };
 struct LmBatchFrameOut { int tokens[LM_BATCH_MAX * LM_FRAME_MAX]; float probs[LM_BATCH_MAX]; };
 struct LmBatchPin { LmBatchFrameStage in; int tokens[LM_BATCH_MAX]; LmBatchFrameOut frame; };
+// rca_lm_batch_frame_sel: the frame's block over the SELECTED members in slots 0 .. n_live - 1, and the two tables of exactly those
+// slots, composed on the host for every call and uploaded as one block inside the replay: a graph over them holds no member's pointer
+#define LM_BATCH_CLASSES 4   // launch geometries: 8, 16, 32 or 64 slots
+struct LmBatchSelStage { LmBatchFrameStage in; int n_live; int pad; LmBatchMember tab[LM_BATCH_MAX]; LmGroupRow rows[LM_BATCH_ROWS]; };
+// what a pass reads about its members: the batch's own tables, or a selection's
+struct LmBatchView { const LmGroupRow* rows; const LmBatchMember* tab; int NM; bool any_serial, any_patch; rca_lm* const* hm; int n_hm; };
 struct rca_lm_batch {
     int n_members = 0;
     rca_lm* m[LM_BATCH_MAX] = {};
@@ -5496,7 +5506,27 @@ struct rca_lm_batch {
     LmBatchFrameOut* frame_out = nullptr;   // device: every step's tokens and the probes, gathered for one download
     float* probe_part = nullptr;            // device, [n_members][PROBS_SLICES (max, sum) pairs]
     hipGraphExec_t fg[LM_FRAME_MAX][LM_GRAPH_BUCKETS][2] = {};   // (n_steps - 1, largest context bucket at the frame's end, probes)
+    // rca_lm_batch_frame_sel
+    LmBatchSelStage* sel_stage = nullptr;   // device copy of sel_pin
+    LmBatchSelStage* sel_pin = nullptr;     // pinned
+    int nsp_all = 1;                        // the largest split count among ALL members: a selection graph's attention grid
+    unsigned long long sel_epoch = 0;       // sum of the members' drop_epoch the graphs below were captured under
+    hipGraphExec_t sg[LM_BATCH_CLASSES][LM_FRAME_MAX][LM_GRAPH_BUCKETS][2][2] = {};   // (class, n_steps - 1, bucket, probes, a patching sampler among them)
+    long long n_captures = 0;               // rca_lm_batch_captures
+    struct LmBatchDuplex* dx = nullptr;     // rca_duplex_batch_frame: buffers, pinned staging and graphs (made by its first call)
 };
+// the pass's state and the selected members' step states from a selection's block; the live count comes from the block, not the launch
+__global__ void lm_batch_sel_stage_kernel(const LmBatchSelStage* __restrict__ in, LmDevState* __restrict__ bstt, LmDevState* __restrict__ hstt) {
+    const int t = threadIdx.x, nl = in->n_live;
+    if (t == 0) { bstt->n_tokens = 0; bstt->m = nl * 2; hstt->n_tokens = 0; hstt->m = nl; }
+    if (t < nl * 2) bstt->ids[t] = in->in.ids[t];
+    if (t < nl) {
+        LmDevState* stt = in->tab[t].stt;
+        stt->n_tokens = in->in.n_tokens[t];
+        stt->m = 2;
+        for (int j = 0; j < 2; ++j) stt->ids[j] = in->in.ids[t * 2 + j];
+    }
+}
 // the pass's state and the members' step states, from one staging block
 __global__ void lm_batch_stage_kernel(const LmBatchStage* __restrict__ in, const LmBatchMember* __restrict__ tab, LmDevState* __restrict__ bstt,
                                       LmDevState* __restrict__ hstt, int n_members, int n) {
@@ -5518,11 +5548,13 @@ __global__ __launch_bounds__(256) void lm_batch_last_rows_kernel(const float* __
 // the head block's rows -> the members' own logits buffers
 __global__ __launch_bounds__(256) void lm_batch_logits_rows_kernel(const LmBatchMember* __restrict__ tab, const float* __restrict__ blk, int V) {
     float* dst = tab[blockIdx.y].logits;
+    if (!dst) return;   // a slot past a selection's live count
     const float* src = blk + (long)blockIdx.y * V;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) dst[i] = src[i];
 }
 // the serial sampler chain with the member in grid y: the bodies of samp_prepare / hist / gather / final_kernel on the member's own
-// {logits, SamplerDev, LmDevState, SampWork}.  Members on a whole-vocabulary sampler are skipped here (their own launches follow).
+// {logits, SamplerDev, LmDevState, SampWork}.  Members on a whole-vocabulary sampler are skipped here (their own launches follow),
+// and so is a slot past a selection's live count: its all-zero entry is not serial.
 __global__ __launch_bounds__(128) void samp_prepare_batch_kernel(const LmBatchMember* __restrict__ tab, int V) {
     const LmBatchMember e = tab[blockIdx.y];
     if (!e.serial || !e.samp->patch) return;
@@ -5544,7 +5576,7 @@ __global__ __launch_bounds__(1024) void samp_final_batch_kernel(const LmBatchMem
     samp_final_body(e.logits, V, e.samp, e.stt, e.swork, SampTail{-1, nullptr, 0, nullptr, 0});
 }
 __global__ void lm_batch_tokens_kernel(const LmBatchMember* __restrict__ tab, int n_members, int* __restrict__ out) {
-    if ((int)threadIdx.x < n_members) out[threadIdx.x] = tab[threadIdx.x].stt->out_token;
+    if ((int)threadIdx.x < n_members && tab[threadIdx.x].stt) out[threadIdx.x] = tab[threadIdx.x].stt->out_token;
 }
 // rca_lm_batch_frame, behind the samplers of step `step`: what the SampTail feedback does for one handle, for all members at once.
 // Records the token, advances the member's position past the pair just evaluated and makes [token, user's token of this step] the
@@ -5555,6 +5587,7 @@ __global__ void lm_batch_feedback_kernel(const LmBatchFrameStage* __restrict__ i
     const int t = threadIdx.x;
     if (t >= n_members) return;
     LmDevState* stt = tab[t].stt;
+    if (!stt) return;   // a slot past a selection's live count
     const int tok = stt->out_token, user = in->user[t * LM_FRAME_MAX + step];
     out->tokens[t * LM_FRAME_MAX + step] = tok;
     stt->n_tokens += 2;
@@ -5565,11 +5598,13 @@ __global__ void lm_batch_feedback_kernel(const LmBatchFrameStage* __restrict__ i
 }
 // softmax(member's logits)[its probe id]: lm_softmax_slices_kernel / lm_token_probs_kernel with the member in grid y
 __global__ __launch_bounds__(1024) void lm_softmax_slices_batch_kernel(const LmBatchMember* __restrict__ tab, int V, float* __restrict__ part) {
+    if (!tab[blockIdx.y].logits) return;   // a slot past a selection's live count
     lm_softmax_slices_body(tab[blockIdx.y].logits, V, part + (long)blockIdx.y * 2 * PROBS_SLICES);
 }
 __global__ __launch_bounds__(64) void lm_token_probs_batch_kernel(const LmBatchMember* __restrict__ tab, int V, const float* __restrict__ part,
                                                                   const int* __restrict__ ids, float* __restrict__ probs) {
     const int s = blockIdx.y;
+    if (!tab[s].logits) return;
     lm_token_probs_body(tab[s].logits, V, part + (long)s * 2 * PROBS_SLICES, ids + s, 1, probs + s);
 }
 // a frame drew n_steps times for every member: the counters of the members it cut go back to where their accepted draws end
@@ -5586,6 +5621,15 @@ static void lm_batch_drop_graphs(rca_lm_batch* b) {
             for (hipGraphExec_t& e : per_b)
                 if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
 }
+static void lm_batch_drop_sel_graphs(rca_lm_batch* b) {
+    hipGraphExec_t* e = &b->sg[0][0][0][0][0];
+    for (size_t i = 0; i < sizeof(b->sg) / sizeof(hipGraphExec_t); ++i)
+        if (e[i]) { (void)hipGraphExecDestroy(e[i]); e[i] = nullptr; }
+}
+// the launch geometry of n slots: 8, 16, 32 or 64
+static int lm_batch_class(int n) { return n <= 8 ? 0 : n <= 16 ? 1 : n <= 32 ? 2 : 3; }
+static void lm_batch_duplex_destroy(struct LmBatchDuplex* d);
+static void lm_batch_duplex_drop_graphs(struct LmBatchDuplex* d);
 extern "C" int rca_lm_batch_destroy(rca_lm_batch_t* b);
 extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, rca_lm_batch_t** out) {
     if (!members || !out) return fail(RCA_ERR_ARG, "batch_create: null argument");
@@ -5611,26 +5655,34 @@ extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, 
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->tab, sizeof(LmBatchMember) * LM_GEMV_M * LM_BATCH_MAX);
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->stt, sizeof(LmDevState));
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->stt_head, sizeof(LmDevState));
-    if (rc == RCA_OK) rc = lm_alloc((void**)&b->head_blk, (size_t)n_members * members[0]->cfg.vocab_size * 4);
+    const int n_slots = 8 << lm_batch_class(n_members);   // a selection frame launches at its class's slot count
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->head_blk, (size_t)n_slots * members[0]->cfg.vocab_size * 4);
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->stage, sizeof(LmBatchFrameStage));
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->frame_out, sizeof(LmBatchFrameOut));
-    if (rc == RCA_OK) rc = lm_alloc((void**)&b->probe_part, sizeof(float) * 2 * PROBS_SLICES * n_members);
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->probe_part, sizeof(float) * 2 * PROBS_SLICES * n_slots);
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->sel_stage, sizeof(LmBatchSelStage));
+    if (rc == RCA_OK && hipHostMalloc((void**)&b->sel_pin, sizeof(LmBatchSelStage), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->tokens, sizeof(int) * LM_BATCH_MAX);
     if (rc == RCA_OK && hipHostMalloc((void**)&b->pin, sizeof(LmBatchPin), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
     if (rc == RCA_OK && (hipMemset(b->stt, 0, sizeof(LmDevState)) != hipSuccess || hipMemset(b->stt_head, 0, sizeof(LmDevState)) != hipSuccess))
         rc = fail(RCA_ERR_HIP, "batch_create: clearing the pass states");
     if (rc != RCA_OK) { rca_lm_batch_destroy(b); return rc; }
     memset(b->pin, 0, sizeof(LmBatchPin));
+    memset(b->sel_pin, 0, sizeof(LmBatchSelStage));
+    for (int s = 0; s < n_members; ++s) b->nsp_all = std::max(b->nsp_all, members[s]->n_splits);
     *out = b;
     return RCA_OK;
 }
 extern "C" int rca_lm_batch_destroy(rca_lm_batch_t* b) {
     if (!b) return RCA_OK;
     lm_batch_drop_graphs(b);
+    lm_batch_drop_sel_graphs(b);
+    lm_batch_duplex_destroy(b->dx);
     for (void* p : {(void*)b->rows, (void*)b->tab, (void*)b->stt, (void*)b->stt_head, (void*)b->head_blk, (void*)b->stage, (void*)b->tokens, (void*)b->frame_out,
-                    (void*)b->probe_part})
+                    (void*)b->probe_part, (void*)b->sel_stage})
         if (p) (void)hipFree(p);
     if (b->pin) (void)hipHostFree(b->pin);
+    if (b->sel_pin) (void)hipHostFree(b->sel_pin);
     delete b;
     return RCA_OK;
 }
@@ -5667,14 +5719,14 @@ static int lm_batch_refresh(rca_lm_batch* b) {
 }
 // embedding -> the layers -> head -> samplers over the device states as they stand (staged by lm_batch_stage_kernel, or left by
 // lm_batch_feedback_kernel): the part a step and every step of a frame share
-static void lm_batch_enqueue_pass(rca_lm_batch* b, int n, int nsp_launch, hipStream_t st) {
+static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n, int nsp_launch, hipStream_t st) {
     rca_lm* ws = b->m[0];
     const rca_lm_config_t& c = ws->cfg;
-    const int NM = b->n_members, MT = NM * n;
+    const int NM = vw.NM, MT = NM * n;
     const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn, V = c.vocab_size;
     const int G = c.n_heads / c.n_kv_heads;
-    const LmGroupRow* qrows = b->rows + (size_t)(n - 1) * LM_BATCH_ROWS;
-    const LmBatchMember* tab = b->tab + (size_t)(n - 1) * LM_BATCH_MAX;
+    const LmGroupRow* qrows = vw.rows;
+    const LmBatchMember* tab = vw.tab;
     const LmDevState* bs = b->stt;
     static bool attr_done = false;
     if (!attr_done) {
@@ -5728,14 +5780,18 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, int n, int nsp_launch, hipStr
     lm_add_rmsnorm_kernel<<<NM, 64, 0, st>>>(b->stt_head, n > 1 ? ws->xn : x, nullptr, nullptr, 0, 0, ws->final_norm, ws->xn, H, c.rms_eps, ws->xh, ws->xl);
     launch_gemm128<GEMM_EPI_LOGITS>(ws, ws->head, dim3(cdiv(V, 128), 1, 1), st, ws->xh, ws->xl, V, H, H, b->head_blk, V, nullptr, nullptr, norope, 1, b->stt_head);
     lm_batch_logits_rows_kernel<<<dim3(std::min((int)cdiv(V, 256), 64), NM), 256, 0, st>>>(tab, b->head_blk, V);
-    if (b->any_serial) {
-        if (b->any_patch) samp_prepare_batch_kernel<<<dim3(1, NM), 128, 0, st>>>(tab, V);
+    if (vw.any_serial) {
+        if (vw.any_patch) samp_prepare_batch_kernel<<<dim3(1, NM), 128, 0, st>>>(tab, V);
         samp_hist_batch_kernel<<<dim3(128, NM), 256, 0, st>>>(tab, V);
         samp_gather_batch_kernel<<<dim3(128, NM), 256, 0, st>>>(tab, V);
         samp_final_batch_kernel<<<dim3(1, NM), 1024, 0, st>>>(tab, V);
     }
-    for (int s = 0; s < NM; ++s)
-        if (b->m[s]->samp_full) lm_enqueue_sample(b->m[s], b->m[s]->logits, st);
+    for (int s = 0; s < vw.n_hm; ++s)
+        if (vw.hm[s]->samp_full) lm_enqueue_sample(vw.hm[s], vw.hm[s]->logits, st);
+}
+// the batch's own tables for n tokens per member, every member in its slot
+static LmBatchView lm_batch_view(rca_lm_batch* b, int n) {
+    return LmBatchView{b->rows + (size_t)(n - 1) * LM_BATCH_ROWS, b->tab + (size_t)(n - 1) * LM_BATCH_MAX, b->n_members, b->any_serial, b->any_patch, b->m, b->n_members};
 }
 // upload of the staged states -> the pass -> download of the tokens, all on `st`, one linear sequence
 static int lm_batch_enqueue(rca_lm_batch* b, int n, int nsp_launch, hipStream_t st) {
@@ -5744,7 +5800,7 @@ static int lm_batch_enqueue(rca_lm_batch* b, int n, int nsp_launch, hipStream_t 
     hipError_t e = hipMemcpyAsync(b->stage, static_cast<const LmBatchStage*>(&b->pin->in), sizeof(LmBatchStage), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch step upload: %s", hipGetErrorString(e));
     lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->stage, tab, b->stt, b->stt_head, NM, n);
-    lm_batch_enqueue_pass(b, n, nsp_launch, st);
+    lm_batch_enqueue_pass(b, lm_batch_view(b, n), n, nsp_launch, st);
     lm_batch_tokens_kernel<<<1, LM_BATCH_MAX, 0, st>>>(tab, NM, b->tokens);
     RCA_LAUNCH_CHECK();
     e = hipMemcpyAsync(b->pin->tokens, b->tokens, sizeof(int) * LM_BATCH_MAX, hipMemcpyDeviceToHost, st);
@@ -5792,7 +5848,10 @@ extern "C" int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t 
         // the split count of the largest bucket among the members (a split past a member's cache leaves at once)
         const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? nsp_max : std::min(nsp_max, 4 << bucket);
         hipGraphExec_t& gexec = b->g[n - 1][bucket];
-        if (!gexec && (rc = lm_capture(st, &gexec, "batch step", [&]() -> int { return lm_batch_enqueue(b, n, nsp_bucket, st); })) != RCA_OK) return rc;
+        if (!gexec) {
+            if ((rc = lm_capture(st, &gexec, "batch step", [&]() -> int { return lm_batch_enqueue(b, n, nsp_bucket, st); })) != RCA_OK) return rc;
+            b->n_captures++;
+        }
         RCA_HIP(hipGraphLaunch(gexec, st));
     } else if ((rc = lm_batch_enqueue(b, n, nsp, st)) != RCA_OK) {
         return rc;
@@ -5819,7 +5878,7 @@ static int lm_batch_frame_enqueue(rca_lm_batch* b, int n_steps, int nsp_launch, 
     if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch frame upload: %s", hipGetErrorString(e));
     lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->stage, tab, b->stt, b->stt_head, NM, 2);
     for (int i = 0; i < n_steps; ++i) {
-        lm_batch_enqueue_pass(b, 2, nsp_launch, st);
+        lm_batch_enqueue_pass(b, lm_batch_view(b, 2), 2, nsp_launch, st);
         lm_batch_feedback_kernel<<<1, LM_BATCH_MAX, 0, st>>>(b->stage, tab, b->stt, b->frame_out, NM, i);
     }
     if (probes) {
@@ -5879,7 +5938,10 @@ extern "C" int rca_lm_batch_frame(rca_lm_batch_t* b, const int32_t* first_pairs,
     if (graphs) {
         const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? nsp_max : std::min(nsp_max, 4 << bucket);
         hipGraphExec_t& gexec = b->fg[n_steps - 1][bucket][probes ? 1 : 0];
-        if (!gexec && (rc = lm_capture(st, &gexec, "batch frame", [&]() -> int { return lm_batch_frame_enqueue(b, n_steps, nsp_bucket, probes, st); })) != RCA_OK) return rc;
+        if (!gexec) {
+            if ((rc = lm_capture(st, &gexec, "batch frame", [&]() -> int { return lm_batch_frame_enqueue(b, n_steps, nsp_bucket, probes, st); })) != RCA_OK) return rc;
+            b->n_captures++;
+        }
         RCA_HIP(hipGraphLaunch(gexec, st));
     } else if ((rc = lm_batch_frame_enqueue(b, n_steps, nsp, probes, st)) != RCA_OK) {
         return rc;
@@ -5912,6 +5974,388 @@ extern "C" int rca_lm_batch_frame(rca_lm_batch_t* b, const int32_t* first_pairs,
         RCA_LAUNCH_CHECK();
         RCA_HIP(hipStreamSynchronize(st));
     }
+    return RCA_OK;
+}
+
+// ------------------------------------------------------------------------------------ selection frame (rca_lm_batch_frame_sel)
+// rca_lm_batch_frame over a SUBSET of the members: sessions sit ticks out (windows still filling, a forced branch, a trim between two
+// steps, a chunk that has not arrived).  The selected members are compacted into slots 0 .. n_sel - 1 of tables composed on the host
+// for THIS call (LmBatchSelStage) and uploaded with the frame's block inside the replay; the launches cover the selection's geometry
+// class (8, 16, 32 or 64 slots).  The live count travels in the block: the row-wise kernels leave on the pass state's m, the table
+// kernels on the all-zero entry of a slot past it.  So a graph holds no member's pointer -- only member 0's workspace and weights --
+// and is keyed by (class, n_steps, bucket, probes, patching samplers): it serves every selection of its class and outlives a member's
+// rca_lm_swap_kv.  An unselected member is not read on the device and not written anywhere.
+// (grows a device buffer of rca_duplex_frame / rca_duplex_batch_frame; the old contents are not kept)
+template <class T>
+static int duplex_grow(T** p, size_t* cap, size_t n) {
+    if (n <= *cap) return RCA_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    int rc = lm_alloc((void**)p, n * sizeof(T));
+    if (rc == RCA_OK) *cap = n;
+    return rc;
+}
+// What rca_duplex_batch_frame adds around the selection frame's passes: buffers, pinned staging and graphs, owned by the batch.
+struct LmBatchDuplexDev { long long user_codes[LM_BATCH_MAX * LM_FRAME_MAX]; int flags[LM_BATCH_MAX]; };   // [slot][step of the call]; one download
+struct LmBatchDuplexKey {
+    int cls, T, F_ctx, n_steps, n_samples, probes, bucket, base, patch;
+    unsigned long long codec_sig;
+    const void* codec;
+    bool operator==(const LmBatchDuplexKey& o) const {
+        return cls == o.cls && T == o.T && F_ctx == o.F_ctx && n_steps == o.n_steps && n_samples == o.n_samples && probes == o.probes && bucket == o.bucket &&
+               base == o.base && patch == o.patch && codec_sig == o.codec_sig && codec == o.codec;
+    }
+};
+struct LmBatchDuplex {
+    float* pcm_in = nullptr; size_t pcm_in_cap = 0;           // device [slots][T]
+    long long* code_win = nullptr; size_t code_win_cap = 0;   // device [slots][F_ctx + n]
+    float* pcm_out = nullptr; size_t pcm_out_cap = 0;         // device [slots][n_samples]
+    LmBatchDuplexDev* dev = nullptr;
+    char* pin = nullptr; size_t pin_cap = 0;                  // pinned: [LmBatchDuplexDev | pcm windows | code contexts | pcm out]
+    struct Entry { LmBatchDuplexKey key; hipGraphExec_t exec = nullptr; };
+    std::vector<Entry> graphs;
+    struct Warm { int cls, T, F_ctx, n_steps, n_samples; const void* codec; unsigned long long codec_sig; };
+    std::vector<Warm> warm;   // (class, shape)s whose codec workspace an eager call has sized: a capture must not allocate
+};
+// one call's geometry, handed to the enqueue
+struct LmBatchDuplexCall {
+    rca_codec_t* codec;
+    int slots, T, F_ctx, n_samples, base, n_codes;
+    size_t pin_pcm, pin_codes, pin_out;   // byte offsets in LmBatchDuplex::pin
+};
+// codes -> ids, table form over [slot][step]: the user's ids of the frame's block, where lm_batch_feedback_kernel reads them, written by
+// the device instead of the upload; clears the slots' flags
+__global__ void duplex_batch_codes_to_ids_kernel(const long long* __restrict__ codes, int n, int base, LmBatchSelStage* __restrict__ stage,
+                                                 int* __restrict__ flags) {
+    const int k = blockIdx.x, i = threadIdx.x;
+    if (k >= stage->n_live) return;
+    if (i == 0) flags[k] = 0;
+    if (i < n) stage->in.user[k * LM_FRAME_MAX + i] = base + (int)codes[(long)k * n + i];
+}
+// ids -> codes, table form: every live slot's sampled tokens of the frame go behind its row's context codes; a token that is no codec
+// token becomes code 0 and raises the slot's flag bit 0
+__global__ void duplex_batch_tokens_to_codes_kernel(const LmBatchFrameOut* __restrict__ out, const LmBatchSelStage* __restrict__ stage, int n, int base,
+                                                    int n_codes, long long* __restrict__ code_win, int F, int* __restrict__ flags) {
+    const int k = blockIdx.x, i = threadIdx.x;
+    if (k >= stage->n_live || i >= n) return;
+    const int c = out->tokens[k * LM_FRAME_MAX + i] - base;
+    const bool ok = c >= 0 && c < n_codes;
+    code_win[(long)k * F + (F - n) + i] = ok ? c : 0;
+    if (!ok) atomicOr(&flags[k], 1);
+}
+static void lm_batch_duplex_drop_graphs(LmBatchDuplex* d) {
+    if (!d) return;
+    for (auto& e : d->graphs)
+        if (e.exec) (void)hipGraphExecDestroy(e.exec);
+    d->graphs.clear();
+}
+static void lm_batch_duplex_destroy(LmBatchDuplex* d) {
+    if (!d) return;
+    lm_batch_duplex_drop_graphs(d);
+    for (void* p : {(void*)d->pcm_in, (void*)d->code_win, (void*)d->pcm_out, (void*)d->dev})
+        if (p) (void)hipFree(p);
+    if (d->pin) (void)hipHostFree(d->pin);
+    delete d;
+}
+
+// upload -> stage -> [encode tails -> codes to ids] -> n_steps x (pass, feedback) -> [ids to codes -> decode tails] -> probes -> download,
+// one linear sequence on `st`; the bracketed parts with a duplex call only
+static int lm_batch_sel_enqueue(rca_lm_batch* b, const LmBatchView& vw, int n_steps, int nsp_launch, bool probes, hipStream_t st,
+                                const LmBatchDuplexCall* dc = nullptr) {
+    const int V = b->m[0]->cfg.vocab_size;
+    LmBatchDuplex* d = b->dx;
+    hipError_t e = hipMemcpyAsync(b->sel_stage, b->sel_pin, sizeof(LmBatchSelStage), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pcm_in, d->pin + dc->pin_pcm, (size_t)dc->slots * dc->T * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->code_win, d->pin + dc->pin_codes, (size_t)dc->slots * (dc->F_ctx + n_steps) * 8, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch frame_sel upload: %s", hipGetErrorString(e));
+    lm_batch_sel_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->sel_stage, b->stt, b->stt_head);
+    if (dc) {
+        const int r = rca_codec_encode_tail_dev(dc->codec, d->pcm_in, dc->slots, dc->T, n_steps, (int64_t*)d->dev->user_codes, st);
+        if (r != RCA_OK) return r;
+        duplex_batch_codes_to_ids_kernel<<<dc->slots, 64, 0, st>>>(d->dev->user_codes, n_steps, dc->base, b->sel_stage, d->dev->flags);
+    }
+    for (int i = 0; i < n_steps; ++i) {
+        lm_batch_enqueue_pass(b, vw, 2, nsp_launch, st);
+        lm_batch_feedback_kernel<<<1, LM_BATCH_MAX, 0, st>>>(&b->sel_stage->in, vw.tab, b->stt, b->frame_out, vw.NM, i);
+    }
+    if (dc) {
+        const int F = dc->F_ctx + n_steps;
+        duplex_batch_tokens_to_codes_kernel<<<dc->slots, 64, 0, st>>>(b->frame_out, b->sel_stage, n_steps, dc->base, dc->n_codes, d->code_win, F, d->dev->flags);
+        const int r = rca_codec_decode_tail_dev(dc->codec, (const int64_t*)d->code_win, dc->slots, F, dc->n_samples, d->pcm_out, st);
+        if (r != RCA_OK) return r;
+    }
+    if (probes) {
+        lm_softmax_slices_batch_kernel<<<dim3(PROBS_SLICES, vw.NM), 1024, 0, st>>>(vw.tab, V, b->probe_part);
+        lm_token_probs_batch_kernel<<<dim3(1, vw.NM), 64, 0, st>>>(vw.tab, V, b->probe_part, b->sel_stage->in.probe, b->frame_out->probs);
+    }
+    RCA_LAUNCH_CHECK();
+    e = hipMemcpyAsync(&b->pin->frame, b->frame_out, sizeof(LmBatchFrameOut), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pin, d->dev, sizeof(LmBatchDuplexDev), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pin + dc->pin_out, d->pcm_out, (size_t)dc->slots * dc->n_samples * 4, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch frame_sel download: %s", hipGetErrorString(e));
+}
+// The refusals of a selection frame, before anything is staged: no member changes.  hm[k] receives the handle of sel[k].  user_ids is
+// null when the device produces them (rca_duplex_batch_frame).
+static int lm_batch_sel_check(rca_lm_batch* b, const char* who, const int32_t* sel, int n_sel, const int32_t* first_pairs, const int32_t* user_ids, int n_steps,
+                              const int32_t* probe_ids, rca_lm** hm) {
+    const int NM = b->n_members;
+    if (n_sel < 1 || n_sel > NM) return fail(RCA_ERR_ARG, "%s: %d selected members, the batch has %d (1..%d)", who, n_sel, NM, NM);
+    if (n_steps < 1 || n_steps > LM_FRAME_MAX) return fail(RCA_ERR_ARG, "%s: %d steps (1..%d)", who, n_steps, LM_FRAME_MAX);
+    int first_k[LM_BATCH_MAX];
+    for (int s = 0; s < NM; ++s) first_k[s] = -1;
+    for (int k = 0; k < n_sel; ++k) {
+        const int s = sel[k];
+        if (s < 0 || s >= NM) return fail(RCA_ERR_ARG, "%s: sel[%d] = member %d is outside the batch's members [0, %d)", who, k, s, NM);
+        if (first_k[s] >= 0) return fail(RCA_ERR_ARG, "%s: sel[%d] = member %d is selected twice (also sel[%d])", who, k, s, first_k[s]);
+        first_k[s] = k;
+        hm[k] = b->m[s];
+    }
+    int rc;
+    for (int k = 0; k < n_sel; ++k)
+        if ((rc = lm_settle(hm[k])) != RCA_OK) return rc;
+    for (int k = 0; k < n_sel; ++k) {
+        const rca_lm* h = hm[k];
+        const int s = sel[k], V = h->cfg.vocab_size;
+        if (!h->sampler_set) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has no sampler (rca_lm_sampler_init)", who, k, s);
+        if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d was switched to logits_all after the batch was made", who, k, s);
+        if (lm_prefill_route(h) != LM_ROUTE_TILE128)
+            return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", who, k, s, lm_prefill_route(h));
+        if (h->n_tokens + 2 * n_steps > h->cfg.n_ctx)
+            return fail(RCA_ERR_STATE, "%s: context overflow of sel[%d] = member %d: %d + %d > n_ctx %d", who, k, s, h->n_tokens, 2 * n_steps, h->cfg.n_ctx);
+        for (int j = 0; j < 2; ++j)
+            if (first_pairs[k * 2 + j] < 0 || first_pairs[k * 2 + j] >= V)
+                return fail(RCA_ERR_ARG, "%s: token id %d of sel[%d] = member %d at index %d of its first pair is outside the vocabulary [0, %d)", who,
+                            first_pairs[k * 2 + j], k, s, j, V);
+        for (int i = 0; user_ids && i < n_steps; ++i)
+            if (user_ids[k * n_steps + i] < 0 || user_ids[k * n_steps + i] >= V)
+                return fail(RCA_ERR_ARG, "%s: user token id %d of sel[%d] = member %d at step %d is outside the vocabulary [0, %d)", who,
+                            user_ids[k * n_steps + i], k, s, i, V);
+        if (probe_ids && (probe_ids[k] < -1 || probe_ids[k] >= V))
+            return fail(RCA_ERR_ARG, "%s: probe id %d of sel[%d] = member %d is outside the vocabulary [0, %d) (-1: no probe)", who, probe_ids[k], k, s, V);
+    }
+    return RCA_OK;
+}
+// the call's block in pinned memory -- tables of the selected members in slots 0 .. n_sel - 1, all-zero entries behind them -- and what
+// the launches need to know about the selection
+struct LmBatchSelPlan { LmBatchView vw; bool graphs, any_patch; int cls, bucket, nsp, nsp_bucket; };
+static LmBatchSelPlan lm_batch_sel_stage(rca_lm_batch* b, rca_lm* const* hm, int n_sel, const int32_t* first_pairs, const int32_t* user_ids, int n_steps,
+                                         const int32_t* probe_ids) {
+    // the graphs hold member 0's workspace and the sampler launches of the chain: they go when a member dropped its own graphs
+    unsigned long long epoch = 0;
+    for (int s = 0; s < b->n_members; ++s) epoch += b->m[s]->drop_epoch;
+    if (epoch != b->sel_epoch) {
+        lm_batch_drop_sel_graphs(b);
+        lm_batch_duplex_drop_graphs(b->dx);
+        b->sel_epoch = epoch;
+    }
+    LmBatchSelPlan p{};
+    p.cls = lm_batch_class(n_sel);
+    p.graphs = true;
+    p.nsp = 1;
+    bool any_serial = false;
+    LmBatchSelStage& in = *b->sel_pin;
+    memset(&in, 0, sizeof(in));   // slots past the selection: all-zero entries, the table kernels leave on them
+    in.n_live = n_sel;
+    for (int k = 0; k < n_sel; ++k) {
+        rca_lm* h = hm[k];
+        const bool serial = !h->samp_full;
+        p.graphs = p.graphs && h->graphs_enabled && serial;   // a whole-vocabulary sampler has launches of its own with its own pointers: eager
+        any_serial = any_serial || serial;
+        p.any_patch = p.any_patch || (serial && h->samp_patch);
+        in.tab[k] = LmBatchMember{h->stt, h->kc, h->vc, h->kv_layer_stride, h->att_part, h->logits, h->samp, h->swork, k * 2, h->n_splits, h->cfg.n_ctx, serial ? 1 : 0};
+        for (int j = 0; j < 2; ++j) {
+            in.rows[k * 2 + j] = LmGroupRow{h->stt, h->kc, h->vc, h->logits, h->kv_layer_stride, j, k * 2 + j, h->cfg.n_ctx, 0};
+            in.in.ids[k * 2 + j] = first_pairs[k * 2 + j];
+        }
+        in.in.n_tokens[k] = h->n_tokens;
+        for (int i = 0; user_ids && i < n_steps; ++i) in.in.user[k * LM_FRAME_MAX + i] = user_ids[k * n_steps + i];
+        in.in.probe[k] = probe_ids ? probe_ids[k] : -1;
+        // the bucket and the splits of the frame's END, as rca_lm_batch_frame
+        p.bucket = std::max(p.bucket, lm_bucket(h, 2 * n_steps, -1).bucket);
+        p.nsp = std::max(p.nsp, lm_splits_needed(h, 2 * n_steps));
+    }
+    for (int k = n_sel; k < LM_BATCH_MAX; ++k) in.in.probe[k] = -1;
+    // a graph's split count is the bucket's over ALL members of the batch, so that the grid does not depend on who is selected (a
+    // split past a member's cache leaves at once)
+    p.nsp_bucket = p.bucket + 1 == LM_GRAPH_BUCKETS ? b->nsp_all : std::min(b->nsp_all, 4 << p.bucket);
+    p.vw = LmBatchView{b->sel_stage->rows, b->sel_stage->tab, 8 << p.cls, any_serial, p.any_patch, hm, n_sel};
+    return p;
+}
+// after the synchronisation: which steps of every selected member stand (rca_lm_batch_frame's settlement, indexed by k)
+static int lm_batch_sel_settle(rca_lm_batch* b, rca_lm* const* hm, int n_sel, int n_steps, int audio_id_floor, const int32_t* probe_ids, int32_t* out_tokens,
+                               int out_stride, int32_t* n_done, float* probe_probs, hipStream_t st) {
+    const LmBatchFrameOut& out = b->pin->frame;
+    LmBatchCuts cuts;
+    cuts.n = 0;
+    for (int k = 0; k < n_sel; ++k) {
+        rca_lm* h = hm[k];
+        int done = n_steps;
+        for (int i = 0; i < n_steps; ++i) {
+            out_tokens[k * out_stride + i] = out.tokens[k * LM_FRAME_MAX + i];
+            if (out_tokens[k * out_stride + i] <= audio_id_floor) { done = i + 1; break; }
+        }
+        for (int i = done; i < out_stride; ++i) out_tokens[k * out_stride + i] = -1;
+        n_done[k] = done;
+        h->n_tokens += 2 * done;
+        h->logits_rows = done < n_steps ? 0 : 1;
+        h->rng_host += (unsigned long long)done;
+        if (done < n_steps) {
+            cuts.member[cuts.n] = k;   // the slot: the device tables still hold this call's selection
+            cuts.counter[cuts.n++] = h->rng_host;
+        }
+        if (probe_probs) probe_probs[k] = done < n_steps || !probe_ids || probe_ids[k] < 0 ? -1.0f : out.probs[k];
+    }
+    if (cuts.n) {
+        lm_batch_counters_kernel<<<1, LM_BATCH_MAX, 0, st>>>(b->sel_stage->tab, cuts);
+        RCA_LAUNCH_CHECK();
+        RCA_HIP(hipStreamSynchronize(st));
+    }
+    return RCA_OK;
+}
+extern "C" int rca_lm_batch_frame_sel(rca_lm_batch_t* b, const int32_t* sel, int32_t n_sel, const int32_t* first_pairs, const int32_t* user_ids, int32_t n_steps,
+                                      int32_t audio_id_floor, const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done, float* probe_probs) {
+    if (!b || !sel || !first_pairs || !user_ids || !out_tokens || !n_done) return fail(RCA_ERR_ARG, "batch_frame_sel: null argument");
+    if (probe_ids && !probe_probs) return fail(RCA_ERR_ARG, "batch_frame_sel: probe_ids without probe_probs");
+    rca_lm* hm[LM_BATCH_MAX];
+    int rc;
+    if ((rc = lm_batch_sel_check(b, "batch_frame_sel", sel, n_sel, first_pairs, user_ids, n_steps, probe_ids, hm)) != RCA_OK) return rc;
+    RCA_HIP(hipSetDevice(b->m[0]->device));
+    hipStream_t st = b->m[0]->stream;
+    const bool probes = probe_ids != nullptr;
+    const LmBatchSelPlan p = lm_batch_sel_stage(b, hm, n_sel, first_pairs, user_ids, n_steps, probe_ids);
+    if (p.graphs) {
+        hipGraphExec_t& gexec = b->sg[p.cls][n_steps - 1][p.bucket][probes ? 1 : 0][p.any_patch ? 1 : 0];
+        if (!gexec) {
+            if ((rc = lm_capture(st, &gexec, "batch frame_sel", [&]() -> int { return lm_batch_sel_enqueue(b, p.vw, n_steps, p.nsp_bucket, probes, st); })) != RCA_OK) return rc;
+            b->n_captures++;
+        }
+        RCA_HIP(hipGraphLaunch(gexec, st));
+    } else if ((rc = lm_batch_sel_enqueue(b, p.vw, n_steps, p.nsp, probes, st)) != RCA_OK) {
+        return rc;
+    }
+    RCA_HIP(hipStreamSynchronize(st));
+    return lm_batch_sel_settle(b, hm, n_sel, n_steps, audio_id_floor, probe_ids, out_tokens, n_steps, n_done, probes ? probe_probs : nullptr, st);
+}
+
+// ------------------------------------------------------------------------------------ duplex batch frame (rca_duplex_batch_frame)
+// rca_duplex_frame for every selected member of a batch in one call: upload -> encode tails over the class's rows -> codes to ids (into
+// the frame block's user table, on the device) -> the selection frame -> ids to codes behind every row's context -> decode tails ->
+// probes -> download, one linear sequence on member 0's stream with no side branch.  The host owns every rolling window and passes them
+// whole, as for one session.  Rows past the selection hold code 0 and whatever finite PCM the block held: the codec runs over them
+// (one codec shape per class) and nothing reads their results.
+static int lm_batch_duplex_reserve(rca_lm_batch* b, int slots, int T, int F, int n_samples, size_t pin_total, hipStream_t st) {
+    if (!b->dx) b->dx = new LmBatchDuplex();
+    LmBatchDuplex* d = b->dx;
+    const size_t np = (size_t)slots * T, nc = (size_t)slots * F, no = (size_t)slots * n_samples;
+    if (np <= d->pcm_in_cap && nc <= d->code_win_cap && no <= d->pcm_out_cap && pin_total <= d->pin_cap && d->dev) return RCA_OK;
+    RCA_HIP(hipStreamSynchronize(st));
+    lm_batch_duplex_drop_graphs(d);   // a buffer is about to move
+    int rc;
+    if (np > d->pcm_in_cap) {
+        if ((rc = duplex_grow(&d->pcm_in, &d->pcm_in_cap, np)) != RCA_OK) return rc;
+        RCA_HIP(hipMemset(d->pcm_in, 0, np * 4));
+    }
+    if (nc > d->code_win_cap) {
+        if ((rc = duplex_grow(&d->code_win, &d->code_win_cap, nc)) != RCA_OK) return rc;
+        RCA_HIP(hipMemset(d->code_win, 0, nc * 8));
+    }
+    if (no > d->pcm_out_cap && (rc = duplex_grow(&d->pcm_out, &d->pcm_out_cap, no)) != RCA_OK) return rc;
+    if (!d->dev) {
+        if ((rc = lm_alloc((void**)&d->dev, sizeof(LmBatchDuplexDev))) != RCA_OK) return rc;
+        RCA_HIP(hipMemset(d->dev, 0, sizeof(LmBatchDuplexDev)));
+    }
+    if (pin_total > d->pin_cap) {
+        if (d->pin) (void)hipHostFree(d->pin);
+        d->pin = nullptr; d->pin_cap = 0;
+        RCA_HIP(hipHostMalloc((void**)&d->pin, pin_total, hipHostMallocDefault));
+        d->pin_cap = pin_total;
+        memset(d->pin, 0, pin_total);
+    }
+    return RCA_OK;
+}
+extern "C" int rca_duplex_batch_frame(rca_lm_batch_t* b, rca_codec_t* codec, const rca_duplex_batch_args_t* a, rca_duplex_batch_out_t* out, float* pcm_out_host) {
+    if (!b || !codec || !a || !out || !pcm_out_host || !a->sel || !a->pcm_windows || !a->first_pairs || (a->F_ctx > 0 && !a->code_ctx) || !out->user_codes ||
+        !out->tokens || !out->n_done || !out->flags || !out->probe_prob)
+        return fail(RCA_ERR_ARG, "duplex_batch_frame: null argument");
+    const int n = a->n_steps, n_sel = a->n_sel;
+    if (a->T < 1 || a->F_ctx < 0 || a->n_samples < 1) return fail(RCA_ERR_ARG, "duplex_batch_frame: bad shape (T=%d F_ctx=%d n_samples=%d)", a->T, a->F_ctx, a->n_samples);
+    rca_lm* hm[LM_BATCH_MAX];
+    int rc;
+    if ((rc = lm_batch_sel_check(b, "duplex_batch_frame", a->sel, n_sel, a->first_pairs, nullptr, n, a->probe_ids, hm)) != RCA_OK) return rc;
+    int32_t n_codes = 0, hop = 0;
+    if ((rc = rca_codec_codebook_size(codec, &n_codes)) != RCA_OK || (rc = rca_codec_hop(codec, &hop)) != RCA_OK) return rc;
+    const int V = b->m[0]->cfg.vocab_size, F = a->F_ctx + n;
+    if (a->code_token_base < 0 || (long)a->code_token_base + n_codes > V)
+        return fail(RCA_ERR_ARG, "duplex_batch_frame: codes [%d, %d + %d) fall outside the vocabulary", a->code_token_base, a->code_token_base, n_codes);
+    if (((long)a->T + hop - 1) / hop < n) return fail(RCA_ERR_ARG, "duplex_batch_frame: %d codes wanted, a window of %d samples holds %ld", n, a->T, ((long)a->T + hop - 1) / hop);
+    if ((long)a->n_samples > (long)F * hop) return fail(RCA_ERR_ARG, "duplex_batch_frame: %d samples wanted, %d codes give %ld", a->n_samples, F, (long)F * hop);
+    for (int k = 0; k < n_sel; ++k)
+        for (int i = 0; i < a->F_ctx; ++i) {
+            const long long c = a->code_ctx[(long)k * a->F_ctx + i];
+            if (c < 0 || c >= n_codes) return fail(RCA_ERR_ARG, "duplex_batch_frame: code %lld of sel[%d] = member %d at index %d of its context is out of range [0, %d)", c, k, a->sel[k], i, n_codes);
+        }
+    RCA_HIP(hipSetDevice(b->m[0]->device));
+    hipStream_t st = b->m[0]->stream;
+    const bool probes = a->probe_ids != nullptr;
+    const LmBatchSelPlan p = lm_batch_sel_stage(b, hm, n_sel, a->first_pairs, nullptr, n, a->probe_ids);
+    const int slots = 8 << p.cls;
+    auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    LmBatchDuplexCall dc{codec, slots, a->T, a->F_ctx, a->n_samples, a->code_token_base, n_codes, 0, 0, 0};
+    dc.pin_pcm = up256(sizeof(LmBatchDuplexDev));
+    dc.pin_codes = dc.pin_pcm + up256((size_t)slots * a->T * 4);
+    dc.pin_out = dc.pin_codes + up256((size_t)slots * F * 8);
+    const size_t pin_total = dc.pin_out + (size_t)slots * a->n_samples * 4;
+    if ((rc = lm_batch_duplex_reserve(b, slots, a->T, F, a->n_samples, pin_total, st)) != RCA_OK) return rc;
+    LmBatchDuplex* d = b->dx;
+    // The code rows past the selection are cleared for every call (at most 64 x F codes): whatever an earlier call of another shape or
+    // another codec left at this place of the block must not reach the decoder as a code.  The PCM rows past the selection keep what
+    // they hold -- zeros, or bytes of an earlier call's windows, codes or output, all finite floats -- and nothing reads their results.
+    memset(d->pin + dc.pin_codes + (size_t)n_sel * F * 8, 0, (size_t)(slots - n_sel) * F * 8);
+    // stage the windows: row k of the class's block is sel[k]'s (the new codes' places of a context row are written by the device)
+    memcpy(d->pin + dc.pin_pcm, a->pcm_windows, (size_t)n_sel * a->T * 4);
+    for (int k = 0; k < n_sel && a->F_ctx; ++k) memcpy(d->pin + dc.pin_codes + (size_t)k * F * 8, a->code_ctx + (long)k * a->F_ctx, (size_t)a->F_ctx * 8);
+    uint64_t csig = 0;
+    if ((rc = rca_codec_workspace_sig(codec, &csig)) != RCA_OK) return rc;
+    bool warmed = false;
+    for (auto& w : d->warm)
+        warmed = warmed || (w.cls == p.cls && w.T == a->T && w.F_ctx == a->F_ctx && w.n_steps == n && w.n_samples == a->n_samples && w.codec == (const void*)codec && w.codec_sig == csig);
+    // the codec's ordering moves to this stream (nothing of it is in flight elsewhere once this returns)
+    if ((rc = rca_codec_stream_handoff(codec, st)) != RCA_OK) return rc;
+    if (p.graphs && warmed) {
+        const LmBatchDuplexKey key{p.cls, a->T, a->F_ctx, n, a->n_samples, probes ? 1 : 0, p.bucket, a->code_token_base, p.any_patch ? 1 : 0, csig, (const void*)codec};
+        LmBatchDuplex::Entry* ent = nullptr;
+        for (auto& e : d->graphs)
+            if (e.key == key) ent = &e;
+        if (!ent) {
+            if (d->graphs.size() >= 32) lm_batch_duplex_drop_graphs(d);   // stale shapes: start over (the stream is idle between calls)
+            d->graphs.push_back(LmBatchDuplex::Entry{key, nullptr});
+            ent = &d->graphs.back();
+        }
+        if (!ent->exec) {
+            if ((rc = lm_capture(st, &ent->exec, "duplex batch", [&]() -> int { return lm_batch_sel_enqueue(b, p.vw, n, p.nsp_bucket, probes, st, &dc); })) != RCA_OK) return rc;
+            b->n_captures++;
+        }
+        RCA_HIP(hipGraphLaunch(ent->exec, st));
+    } else if ((rc = lm_batch_sel_enqueue(b, p.vw, n, p.nsp, probes, st, &dc)) != RCA_OK) {
+        return rc;
+    }
+    RCA_HIP(hipStreamSynchronize(st));
+    if (!warmed) {   // the eager run sized the codec workspace of this (class, shape): graphs are keyed by the signature after it
+        if ((rc = rca_codec_workspace_sig(codec, &csig)) != RCA_OK) return rc;
+        if (d->warm.size() >= 32) d->warm.clear();
+        d->warm.push_back(LmBatchDuplex::Warm{p.cls, a->T, a->F_ctx, n, a->n_samples, (const void*)codec, csig});
+    }
+    if ((rc = lm_batch_sel_settle(b, hm, n_sel, n, a->audio_id_floor, a->probe_ids, out->tokens, LM_FRAME_MAX, out->n_done, out->probe_prob, st)) != RCA_OK) return rc;
+    const LmBatchDuplexDev* got = reinterpret_cast<const LmBatchDuplexDev*>(d->pin);
+    for (int k = 0; k < n_sel; ++k) {
+        for (int i = 0; i < LM_FRAME_MAX; ++i) out->user_codes[k * LM_FRAME_MAX + i] = i < n ? got->user_codes[k * n + i] : 0;
+        out->flags[k] = got->flags[k] | (out->n_done[k] < n ? 2 : 0);
+        if (out->flags[k] == 0) memcpy(pcm_out_host + (size_t)k * a->n_samples, d->pin + dc.pin_out + (size_t)k * a->n_samples * 4, (size_t)a->n_samples * 4);
+    }
+    return RCA_OK;
+}
+extern "C" int rca_lm_batch_captures(const rca_lm_batch_t* b, int64_t* n) {
+    if (!b || !n) return fail(RCA_ERR_ARG, "batch_captures: null argument");
+    *n = b->n_captures;
     return RCA_OK;
 }
 
@@ -6062,14 +6506,6 @@ static void duplex_destroy(DuplexState* d) {
     if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
     if (d->ev_join) (void)hipEventDestroy(d->ev_join);
     delete d;
-}
-template <class T>
-static int duplex_grow(T** p, size_t* cap, size_t n) {
-    if (n <= *cap) return RCA_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    int rc = lm_alloc((void**)p, n * sizeof(T));
-    if (rc == RCA_OK) *cap = n;
-    return rc;
 }
 
 // byte offsets of the variable parts of DuplexState::pin behind the DuplexPin header, each part on a 256-byte boundary

@@ -847,7 +847,10 @@ class LlamaBatch:
     attention one launch per layer, the head one tile GEMM, the top-k sampler one chain.  Needs a model whose long evals take the
     128-token tiles; smaller models stay with LlamaGroup.  Unlike a group step a batch step is NOT bit-identical to step(): it is in
     the arithmetic class of a decode on a tile-built cache, and a member's result does not depend on its slot or companions.
-    step() / eval() / sample() on a member, group steps and batch steps mix freely.  Close the batch before its members."""
+    step() / eval() / sample() on a member, group steps and batch steps mix freely.  Close the batch before its members.
+    Sessions that sit a tick out stay members and are left out of the call: frame(members=[...]) and duplex_frame(codec, members, ...)
+    run over a selection and touch no other member; selections of one size class (up to 8, 16, 32, 64) share their graphs, which hold
+    no member's pointers and outlive a member's swap_kv (captures() counts them)."""
 
     def __init__(self, members: Sequence["LlamaForAlternatingCodeChannels"], lib=None):
         self.members = list(members)
@@ -877,17 +880,26 @@ class LlamaBatch:
         return [int(t) for t in out]
 
     def frame(self, first_pairs: Sequence[Sequence[int]], user_ids: Sequence[Sequence[int]], audio_id_floor: int,
-              probe_ids: Optional[Sequence[int]] = None):
+              probe_ids: Optional[Sequence[int]] = None, members: Optional[Sequence[int]] = None):
         """frame() of every member in ONE call (rca_lm_batch_frame; one graph replay when every member has graphs on): member s runs
         len(user_ids[s]) S=2 steps from first_pairs[s] with its sampled token fed back on the device.  Returns (tokens, probe_probs):
         tokens[s] is the list of member s's sampled tokens, shorter than user_ids[s] when a step sampled a token <= audio_id_floor
         (the cutting token is its last element; the member's n_tokens and draw counter are then what that many batch steps leave and
         it has no logits until its next eval or step).  probe_probs is None without probe_ids, else a float32 array with
         softmax(member s's last logits)[probe_ids[s]], NaN where the member was cut or its probe id is -1.  A refusal raises and
-        leaves every member as it was."""
+        leaves every member as it was.
+        members: a list of distinct member indices (any order) that take part (rca_lm_batch_frame_sel); every argument and result
+        is then indexed by the position in that list.  A selected member ends as frame() of a batch over only the selected members
+        would leave it, bit for bit; the others are not touched.  None: every member, the call as it always was."""
         pairs = [[int(t) for t in p] for p in first_pairs]
         users = [[int(t) for t in u] for u in user_ids]
-        nm = len(self.members)
+        sel = None if members is None else [int(s) for s in members]
+        if sel is not None and any(s < 0 or s >= len(self.members) for s in sel):
+            raise N.RcaError(f"members {sel}: an index outside the batch's {len(self.members)} members")
+        taking = self.members if sel is None else [self.members[s] for s in sel]
+        nm = len(taking)
+        if nm == 0:
+            raise N.RcaError("an empty selection (1 to len(members) members take part)")
         if len(pairs) != nm or len(users) != nm:
             raise ValueError(f"{len(pairs)} first pairs and {len(users)} user id lists for {nm} members")
         if any(len(p) != 2 for p in pairs):
@@ -900,16 +912,20 @@ class LlamaBatch:
             probes = [int(p) for p in probe_ids]
             if len(probes) != nm:
                 raise ValueError(f"{len(probes)} probe ids for {nm} members")
-        starts = [m.n_tokens for m in self.members]
+        starts = [m.n_tokens for m in taking]
         fp = (C.c_int32 * (2 * nm))(*[t for p in pairs for t in p])
         us = (C.c_int32 * max(nm * n, 1))(*[t for u in users for t in u])
         out = (C.c_int32 * max(nm * n, 1))()
         done = (C.c_int32 * nm)()
         pid = (C.c_int32 * nm)(*probes) if probes is not None else None
         pp = (C.c_float * nm)() if probes is not None else None
-        N.check(self._lib.rca_lm_batch_frame(self._b, fp, us, n, int(audio_id_floor), pid, out, done, pp), "rca_lm_batch_frame")
+        if sel is None:
+            N.check(self._lib.rca_lm_batch_frame(self._b, fp, us, n, int(audio_id_floor), pid, out, done, pp), "rca_lm_batch_frame")
+        else:
+            sl = (C.c_int32 * nm)(*sel)
+            N.check(self._lib.rca_lm_batch_frame_sel(self._b, sl, nm, fp, us, n, int(audio_id_floor), pid, out, done, pp), "rca_lm_batch_frame_sel")
         tokens = []
-        for s, (m, n0) in enumerate(zip(self.members, starts)):
+        for s, (m, n0) in enumerate(zip(taking, starts)):
             toks = [int(t) for t in out[s * n:s * n + done[s]]]
             evaluated = pairs[s] + [t for pair in zip(toks[:-1], users[s]) for t in pair]
             m._input_ids[n0:n0 + len(evaluated)] = evaluated
@@ -920,6 +936,63 @@ class LlamaBatch:
         probs = np.array(pp[:], dtype=np.float32)
         probs[probs < 0.0] = np.nan
         return tokens, probs
+
+    def duplex_frame(self, codec_handle, members: Sequence[int], pcm_windows, code_ctxs, n_steps: int, n_samples: int, code_token_base: int,
+                     audio_id_floor: int, probe_ids: Optional[Sequence[int]], first_pairs: Sequence[Sequence[int]]) -> List[dict]:
+        """duplex_frame() of every member of `members` in ONE call (rca_duplex_batch_frame): encode tails -> ids -> the selection frame
+        -> codes -> decode tails -> P(probe), one replay from the second call of a shape on.  pcm_windows [len(members)][T] and
+        code_ctxs [len(members)][F_ctx] are the members' rolling windows in one call shape; probe_ids one id per member (-1: none) or
+        None.  Returns, per member, the dict LlamaForAlternatingCodeChannels.duplex_frame returns: user_codes, tokens (shorter when a
+        step left audio mode), pcm or None when the decode of this call must not be used, probe_prob or None, plus "flags" (the C
+        call's bits: 1 a sampled token is no codec token, 2 cut).  Only the selected
+        members' _input_ids are touched.  A refusal raises and leaves every member as it was."""
+        sel = [int(s) for s in members]
+        if not sel or any(s < 0 or s >= len(self.members) for s in sel):
+            raise N.RcaError(f"members {sel}: 1 to {len(self.members)} indices inside the batch's members")
+        nm, n = len(sel), int(n_steps)
+        taking = [self.members[s] for s in sel]
+        pairs = [[int(t) for t in p] for p in first_pairs]
+        if len(pairs) != nm or any(len(p) != 2 for p in pairs):
+            raise ValueError("duplex_frame() starts from the last [agent, user] pair of every selected member")
+        pcm_in = np.ascontiguousarray(pcm_windows, dtype=np.float32).reshape(nm, -1)
+        ctx = np.ascontiguousarray(code_ctxs, dtype=np.int64)
+        ctx = ctx.reshape(nm, ctx.size // nm)          # (an empty context, F_ctx = 0, is a call shape too)
+        probes = None if probe_ids is None else [int(p) for p in probe_ids]
+        if probes is not None and len(probes) != nm:
+            raise ValueError(f"{len(probes)} probe ids for {nm} members")
+        starts = [m.n_tokens for m in taking]
+        sl = (C.c_int32 * nm)(*sel)
+        fp = (C.c_int32 * (2 * nm))(*[t for p in pairs for t in p])
+        pid = (C.c_int32 * nm)(*probes) if probes is not None else None
+        a = N.DuplexBatchArgsC(sel=C.addressof(sl), n_sel=nm, pcm_windows=pcm_in.ctypes.data, code_ctx=ctx.ctypes.data if ctx.size else None,
+                               first_pairs=C.addressof(fp), probe_ids=C.addressof(pid) if pid is not None else None, T=pcm_in.shape[1],
+                               F_ctx=ctx.shape[1], n_steps=n, n_samples=int(n_samples), code_token_base=int(code_token_base),
+                               audio_id_floor=int(audio_id_floor))
+        codes = np.zeros((nm, 8), np.int64)
+        toks = np.zeros((nm, 8), np.int32)
+        done, flags, prob = np.zeros(nm, np.int32), np.zeros(nm, np.int32), np.zeros(nm, np.float32)
+        out = N.DuplexBatchOutC(user_codes=codes.ctypes.data, tokens=toks.ctypes.data, n_done=done.ctypes.data, flags=flags.ctypes.data,
+                                probe_prob=prob.ctypes.data)
+        pcm = np.empty((nm, int(n_samples)), dtype=np.float32)
+        N.check(self._lib.rca_duplex_batch_frame(self._b, codec_handle._h, C.byref(a), C.byref(out), C.c_void_p(pcm.ctypes.data)), "rca_duplex_batch_frame")
+        res = []
+        for k, (m, n0) in enumerate(zip(taking, starts)):
+            uc = [int(c) for c in codes[k, :n]]
+            tk = [int(t) for t in toks[k, :done[k]]]
+            user_ids = [int(code_token_base) + c for c in uc]
+            evaluated = pairs[k] + [t for pair in zip(tk[:-1], user_ids) for t in pair]
+            m._input_ids[n0:n0 + len(evaluated)] = evaluated
+            m._logits_valid = False
+            res.append({"user_codes": uc, "tokens": tk, "pcm": pcm[k] if flags[k] == 0 else None,
+                        "probe_prob": float(prob[k]) if prob[k] >= 0.0 else None, "flags": int(flags[k])})
+        return res
+
+    def captures(self) -> int:
+        """graph captures this batch has made so far (rca_lm_batch_captures): selections of one geometry class (up to 8, 16, 32, 64
+        members) share one capture per (steps, context bucket, probes), also after a member's swap_kv"""
+        n = C.c_int64()
+        N.check(self._lib.rca_lm_batch_captures(self._b, C.byref(n)), "rca_lm_batch_captures")
+        return int(n.value)
 
     def close(self) -> None:
         if getattr(self, "_b", None) is not None and self._b:

@@ -1,0 +1,135 @@
+"""RealtimeAgentBatch -- N RealtimeAgents over one set of LM weights, one tick at a time.
+
+A server that keeps many duplex sessions on a card gives every session its own RealtimeAgent (own sequence, codec windows, sampler,
+statistics) over weight-sharing LM handles (RealtimeAgentResources.clone_for_self_play) and ONE codec handle, and calls
+process_audio(chunks) once per tick.  The sessions whose frame can run as one replay (RealtimeAgent._replay_plan: both codec windows
+full, audio mode, nothing forced, no trim between two steps) are grouped by call shape, and every group of at least `min_batch` takes ONE
+LlamaBatch.duplex_frame (rca_duplex_batch_frame); every other session with a chunk runs its own process_audio unchanged.
+
+A batch frame is in the tile arithmetic class (LlamaBatch): a session inside the batch samples other tokens than the same session
+alone -- equally valid ones; with use_duplex_batch_graph=False the ready group runs the same LM arithmetic through the separate calls
+(tokenize_audio, one LlamaBatch.frame(members=...), detokenize_output_chunk), so the two can be compared, as use_duplex_graph does for
+one session.  Not thread-safe: one caller per tick."""
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+
+class RealtimeAgentBatch:
+    def __init__(self, agents: Sequence, min_batch: int = 4, use_duplex_batch_graph: bool = True):
+        self.agents = list(agents)
+        self.min_batch = max(1, int(min_batch))     # where one batch call starts to win over as many single frames: 4, the smallest size measured (profiles/r16)
+        self.use_duplex_batch_graph = bool(use_duplex_batch_graph)
+        self.fused_ticks = 0       # ticks in which at least one group took the batch call
+        self.fused_frames = 0      # agent frames that went through it
+        self._batch = None
+        if len(self.agents) < 2:
+            raise ValueError("a RealtimeAgentBatch drives at least two agents")
+        llms = [a.resources.llm for a in self.agents]
+        if len({id(m) for m in llms}) != len(llms):
+            raise ValueError("every agent needs an LM handle of its own (RealtimeAgentResources.clone_for_self_play)")
+        first = self.agents[0]
+        for i, a in enumerate(self.agents[1:], 1):
+            for what in ("_code_token_base", "end_header_token_id", "end_audio_token_id"):
+                if getattr(a, what) != getattr(first, what):
+                    raise ValueError(f"agent {i} has another {what.lstrip('_')} than agent 0 ({getattr(a, what)} / {getattr(first, what)})")
+            if self._codec(a) is not self._codec(first):
+                raise ValueError(f"agent {i} uses another codec handle than agent 0")
+        if all(hasattr(m, "duplex_frame") and hasattr(m, "_h") for m in llms) and self._codec(first) is not None:
+            from . import _native as N
+            from .llm import LlamaBatch
+            try:
+                self._batch = LlamaBatch(llms)
+            except N.RcaError as e:       # other weights, another device, a model off the tile route
+                raise ValueError(f"the agents' LMs cannot form one batch: {e}") from e
+
+    @staticmethod
+    def _codec(agent):
+        return getattr(agent.resources.audio_tokenizer.codec_model, "hip", None)
+
+    # ------------------------------------------------------------------ who runs how
+    def _partition(self, plans: Sequence[Optional[dict]]) -> Tuple[List[List[int]], List[int]]:
+        """plans[i]: agent i's plan, or None (no chunk, or not ready).  Returns (groups, rest): the ready agents grouped by call shape,
+        groups of at least min_batch only, each in agent order; and the other ready agents, which run on their own."""
+        by_shape = {}
+        for i, p in enumerate(plans):
+            if p is not None:
+                shape = (len(p["window"]) if np.ndim(p["window"]) == 1 else np.shape(p["window"])[-1], len(p["code_ctx"]), p["n_codes"], p["n_samples"])
+                by_shape.setdefault(shape, []).append(i)
+        groups = [g for g in by_shape.values() if len(g) >= self.min_batch]
+        rest = sorted(i for g in by_shape.values() if len(g) < self.min_batch for i in g)
+        return groups, rest
+
+    def process_audio(self, chunks: Sequence[Optional[np.ndarray]]) -> list:
+        """One chunk or None per agent in, one RealtimeAgent.process_audio result or None per agent out."""
+        if len(chunks) != len(self.agents):
+            raise ValueError(f"{len(chunks)} chunks for {len(self.agents)} agents")
+        outs = [None] * len(self.agents)
+        live = [i for i, c in enumerate(chunks) if c is not None]
+        for i in live:
+            self.agents[i]._settle_shadow()
+        plans = [None] * len(self.agents)
+        if self._batch is not None:
+            for i in live:
+                plans[i] = self.agents[i]._replay_plan(chunks[i])
+        groups, _ = self._partition(plans)
+        fused = {i for g in groups for i in g}
+        for g in groups:
+            self._run_group(g, chunks, plans, outs)
+        for i in live:
+            if i not in fused:
+                outs[i] = self.agents[i].process_audio(chunks[i])     # settles and advances its own shadow cache
+        for i in sorted(fused):
+            self.agents[i]._advance_shadow()
+        if groups:
+            self.fused_ticks += 1
+            self.fused_frames += len(fused)
+        return outs
+
+    def _run_group(self, sel: List[int], chunks, plans, outs) -> None:
+        A = self.agents
+        first, p0 = A[sel[0]], plans[sel[0]]
+        pairs = [A[i].input_ids[-2:] for i in sel]
+        probes = [first.end_audio_token_id] * len(sel)
+        if self.use_duplex_batch_graph:
+            res = self._batch.duplex_frame(self._codec(first), sel, np.stack([np.reshape(plans[i]["window"], -1) for i in sel]),
+                                           np.stack([plans[i]["code_ctx"] for i in sel]), p0["n_codes"], p0["n_samples"], first._code_token_base,
+                                           first.end_header_token_id, probes, pairs)
+            for k, i in enumerate(sel):
+                a = A[i]
+                with a.profilers.total_profiler:
+                    out = a._replay_commit(chunks[i], plans[i], lambda r=res[k]: r)
+                outs[i] = out if a.self_play_mode else out[0]
+            return
+        # the unfused path: the separate codec calls around ONE selection frame
+        user_ids = []
+        for i in sel:
+            a, r = A[i], A[i].resources
+            with a.profilers.audio_tokenize_profiler:
+                s = r.audio_tokenizer.tokenize_audio(chunks[i])
+            with a.profilers.tokenize_profiler:
+                user_ids.append(r.tokenizer.encode(s, add_special_tokens=False))
+        toks, probs = self._batch.frame(pairs, user_ids, first.end_header_token_id, probe_ids=probes, members=sel)
+        for k, i in enumerate(sel):
+            a = A[i]
+            with a.profilers.total_profiler:
+                with a.profilers.lm_profiler:
+                    a.frame_graph_active = True
+                    out_ids = a.process_audio_input_ids(user_ids[k], pre=toks[k])
+                out_chunk = a.detokenize_output_chunk(out_ids)
+                a.audio_history_ch2.append(chunks[i])
+                a.measure_event_prob(None if np.isnan(probs[k]) else float(probs[k]))
+                a.update_inactivity_timers()
+            outs[i] = (out_chunk, out_ids) if a.self_play_mode else out_chunk
+
+    def close(self) -> None:
+        """the batch first, then the agents' LM handles (shadow twins included)"""
+        if self._batch is not None:
+            self._batch.close()
+            self._batch = None
+        for a in self.agents:
+            sh = getattr(a, "_kv_shadow", None)
+            if sh is not None and hasattr(sh.twin, "close"):
+                sh.twin.close()
+            if hasattr(a.resources.llm, "close"):
+                a.resources.llm.close()
