@@ -689,6 +689,35 @@ int rca_lm_set_attn_fuse(rca_lm_t* h, int32_t enable);
  * route (rca_lm_set_mfma_prefill(0), evals of up to 8 tokens) is made of decode GEMV passes and follows the mode. */
 int rca_lm_set_act_format(rca_lm_t* h, int32_t fmt);
 int rca_lm_get_act_format(const rca_lm_t* h, int32_t* fmt);
+/* Format of the handle's KV cache: 0 = fp16 (default; bit for bit the cache of earlier versions), 1 = q8_0 (llama.cpp's
+ * --cache-type-k q8_0 --cache-type-v q8_0).  RCA_ERR_ARG for another value, RCA_ERR_STATE unless n_tokens == 0 (nothing is touched).
+ * When the value changes the cache is re-allocated, zeroed, and every captured graph is dropped.  Per handle; rca_lm_create_shared
+ * copies the parent's value, so shadow and aux twins follow.  rca_lm_config_t is not extended.
+ * FORMAT.  Per layer, position and kv head the 64 values of K and of V are two ggml q8_0 blocks (32 int8 + one fp16 scale each),
+ * kept in separate planes per tensor: q[n_layers][n_ctx_pad][n_kv_heads][64] int8 and d[n_layers][n_ctx_pad][n_kv_heads][2] fp16 --
+ * a head row is 64 contiguous, 64-byte-aligned bytes.  A cached position takes n_layers * n_kv_heads * 2 * 68 bytes instead of
+ * n_layers * n_kv_heads * 2 * 128 (rca_lm_kv_bytes_per_position).
+ * RULE.  The quantiser's input is the fp16 row the default cache would hold: cache row == Q8(fp16 row of the default path).  It is the
+ * q8_1 rule of rca_lm_set_act_format: per block d = amax / 127 (IEEE f32 division), inv = d != 0 ? 1 / d : 0, q_j = roundf(x_j * inv)
+ * (ties away from zero) as int8, stored scale d16 = fp16 rne of d; an all-zero block is q = 0, d16 = 0, and a block whose d rounds to
+ * fp16 zero de-quantises to zeros, and a block whose amax is 65504 de-quantises its extreme element to infinity (d16 rounds up to 516;
+ * 516 * 127 is beyond fp16) -- the rule, not an error.  Attention multiplies fp16_rne((float)d16 * q_j), formed while a row is
+ * staged into the LDS images of the attention kernels; everything behind the images (MFMA, softmax, merge, combine) is the code of
+ * the fp16 cache.  The QKV epilogues store their fp16 rows into a per-handle ring of 1024 positions (row = position & 1023, one ring
+ * for all layers, about 2 MB at 8 kv heads) and one small launch per layer quantises the rows of the pass before attention runs.
+ * Every eval / step / frame / score / duplex / group / batch call works on a q8_0 handle.  rca_lm_copy_kv / rca_lm_swap_kv between
+ * handles of different formats, and groups or batches whose members differ in format, are refused.  rca_lm_kv_remove on a q8_0 handle
+ * is refused (RCA_ERR_STATE, n_tokens unchanged): re-rotating quantised keys would quantise them a second time.
+ * Tests-only calls on a q8_0 handle: rca_lm_kv_write quantises the given fp16 rows with the kernel the passes use; rca_lm_kv_read and
+ * rca_lm_gemv_tap's kv_host return the de-quantised fp16 rows, exactly the values attention stages; rca_lm_kv_read_q8 the raw blocks. */
+int rca_lm_set_kv_format(rca_lm_t* h, int32_t fmt);
+int rca_lm_get_kv_format(const rca_lm_t* h, int32_t* fmt);
+/* bytes one cached position takes in the handle's KV format (all layers, K and V); ring_positions (may be NULL): positions of the
+ * fp16 staging ring of a q8_0 cache, 0 for an fp16 cache */
+int rca_lm_kv_bytes_per_position(const rca_lm_t* h, int64_t* bytes, int32_t* ring_positions);
+/* Tests only, q8_0 handles (RCA_ERR_STATE otherwise): the raw blocks of positions [pos0, pos0 + n_pos) of one layer: int8 values
+ * [n_pos][n_kv_heads][64] and fp16 scales [n_pos][n_kv_heads][2] of K and of V.  Any pointer may be NULL. */
+int rca_lm_kv_read_q8(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, int8_t* k_q, uint16_t* k_d, int8_t* v_q, uint16_t* v_d);
 /* Tests only: ONE decode GEMV stage exactly as the step launches it (same instance, geometry and current activation format) on a
  * host-supplied input.  kind 0 QKV (x = residual rows [M][hidden]; y = the q rows after RoPE [M][n_heads*64]; kv_host, if not NULL,
  * receives the M new K rows then the M new V rows of `layer`'s cache as raw fp16), 1 O (x [M][AO]), 2 gate/up (y = silu(g)*u [M][ffn]),

@@ -33,6 +33,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 #define LM_MAXM 1024       // tokens per prefill pass (activation buffers): up to 8 token blocks of 128 share one launch per GEMM
+#define LM_KV_RING LM_MAXM // q8_0 KV cache: positions of the fp16 staging ring the QKV epilogues store into (the largest pass)
 #define LM_STATE_DECODE_BYTES (8 + 4 * 16)   // n_tokens, m and the ids a decode step / frame graph needs (LmDevState prefix)
 #define LM_TILE32 32       // token tile of the small-model prefill kernels (lm_gemm_mfma_kernel)
 #define LM_GEMV_M 2        // tokens per decode pass (GEMV kernels); evals longer than LM_PREFILL_MIN go through the MFMA prefill path
@@ -276,6 +277,8 @@ struct GemvRope {
     const float* cos_t; const float* sin_t; f16_t* kc; f16_t* vc; int nh, nkv, n_ctx;
     int row_base;   // first row of this matrix inside the fused [q; k; v] layout (a multiple of 64): a Q4_K_M file keeps some attn_v tensors
                     // in another format than attn_q / attn_k, and such a layer's V projection is a matrix of its own
+    int pos_mask = -1;   // a row of position p is stored at row p & pos_mask of kc / vc: all ones over the fp16 cache itself, ring size - 1
+                         // over the staging ring of a q8_0 cache (rca_lm_set_kv_format), whose rows lm_kv_quant_kernel quantises
 };
 __device__ __forceinline__ void lane_swap32(float& a, float& b) {   // a = [a.lo, b.lo], b = [a.hi, b.hi]
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
@@ -405,13 +408,13 @@ constexpr int gemv_min_waves(int Q, int R, int NIT, int M = 2) {
 // and always inlined: the GRP = 0 kernels below are, instruction for instruction, what they were before the table existed.
 struct LmGroupRow {
     LmDevState* stt;         // the row's session: n_tokens = KV position of ITS first token of the pass
-    f16_t* kc; f16_t* vc;    // that session's KV cache (layer 0) and its layer stride in elements
+    f16_t* kc; f16_t* vc;    // that session's KV cache (layer 0) and its layer stride in elements (q8_0 cache: its fp16 ring, stride 0)
     float* dst;              // head rows: the session's logits buffer
     long kv_stride;
     int j;                   // index of the row inside its session's tokens of the pass
     int xrow;                // row of the activation buffer the slot reads (QKV: the slot itself; head: the session's last token)
     int n_ctx;
-    int pad;
+    int pos_mask;            // GemvRope::pos_mask of that session
 };
 struct GemvGroup {
     const LmGroupRow* rows; int layer;
@@ -618,7 +621,7 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
     int pos0 = 0;
     if (!GRP && EPI == 2) pos0 = stt->n_tokens;
     // grouped QKV: the epilogue thread of (row m, pair s) takes position, cache and context bound of row m's session
-    int g_pos = 0, g_nctx = 0;
+    int g_pos = 0, g_nctx = 0, g_mask = -1;
     f16_t *g_kc = nullptr, *g_vc = nullptr;
     float* g_dst = nullptr;
     if constexpr (GRP != 0) {
@@ -626,6 +629,7 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
             const LmGroupRow rw = grp.rows[tid / (R / 2)];
             g_pos = rw.stt->n_tokens + rw.j;
             g_nctx = rw.n_ctx;
+            g_mask = rw.pos_mask;
             g_kc = rw.kc + (long)grp.layer * rw.kv_stride;
             g_vc = rw.vc + (long)grp.layer * rw.kv_stride;
         }
@@ -881,6 +885,7 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
                 const int pos = GRP ? g_pos : pos0 + m;
                 f16_t* const kcache = GRP ? g_kc : rope.kc;
                 f16_t* const vcache = GRP ? g_vc : rope.vc;
+                const int prow = pos & (GRP ? g_mask : rope.pos_mask);
                 if (rl + 32 < N && pos < (GRP ? g_nctx : rope.n_ctx)) {
                     const float x1 = total(m * R + 2 * s), x2 = total(m * R + 2 * s + 1);
                     const int head = r0 >> 6, d = r0 & 63;   // d < 32
@@ -891,12 +896,12 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
                             y[(long)m * ldy + r0] = o1;
                             y[(long)m * ldy + r0 + 32] = o2;
                         } else {
-                            f16_t* kp = kcache + ((long)pos * rope.nkv + (head - rope.nh)) * 64;
+                            f16_t* kp = kcache + ((long)prow * rope.nkv + (head - rope.nh)) * 64;
                             kp[d] = (f16_t)o1;
                             kp[d + 32] = (f16_t)o2;
                         }
                     } else {
-                        f16_t* vp = vcache + ((long)pos * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
+                        f16_t* vp = vcache + ((long)prow * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
                         vp[d] = (f16_t)x1;
                         vp[d + 32] = (f16_t)x2;
                     }
@@ -1033,12 +1038,12 @@ __global__ __launch_bounds__(256) void lm_gemm_mfma_kernel(const LmDevState* __r
                     y[(long)tok * ldy + n1] = o1;
                     y[(long)tok * ldy + n1 + 32] = o2;
                 } else {
-                    f16_t* kp = rope.kc + ((long)pos * rope.nkv + (head - rope.nh)) * 64;
+                    f16_t* kp = rope.kc + ((long)(pos & rope.pos_mask) * rope.nkv + (head - rope.nh)) * 64;
                     kp[d] = (f16_t)o1;
                     kp[d + 32] = (f16_t)o2;
                 }
             } else {
-                f16_t* vp = rope.vc + ((long)pos * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
+                f16_t* vp = rope.vc + ((long)(pos & rope.pos_mask) * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
                 vp[d] = (f16_t)x1;
                 vp[d + 32] = (f16_t)x2;
             }
@@ -2203,7 +2208,11 @@ struct rca_lm {
     float* final_norm = nullptr;
     std::vector<LmLayer> layers;
     float *cos_t = nullptr, *sin_t = nullptr;
-    f16_t *kc = nullptr, *vc = nullptr;  // [L][n_ctx_pad][nkv][hd]
+    f16_t *kc = nullptr, *vc = nullptr;  // [L][n_ctx_pad][nkv][hd]; kv_format 1: ONE allocation each of the int8 plane [L][n_ctx_pad][nkv][64] and,
+                                         // behind it, the fp16 scales [L][n_ctx_pad][nkv][2] -- so whatever exchanges or keys caches by these two
+                                         // pointers (rca_lm_swap_kv, the graph sets, rca_duplex_precapture) holds for either format
+    int kv_format = 0;                   // 0 fp16, 1 q8_0 (rca_lm_set_kv_format)
+    f16_t *ring_k = nullptr, *ring_v = nullptr;   // q8_0: [LM_KV_RING][nkv][64] fp16 rows of the current pass and layer, what the QKV epilogues store
     f16_t* kv_stage = nullptr;           // rca_lm_kv_remove: two slabs of [K, V][L][ATT_KEYS][nkv][hd], allocated by the first call that moves rows
     long kv_layer_stride = 0;
     int n_ctx_pad = 0, n_splits = 0;
@@ -2262,6 +2271,54 @@ struct rca_lm {
     size_t sc_pin_cap = 0;
     hipEvent_t sc_ready = nullptr, sc_free = nullptr;   // base: block logits written; scored handle: block logits consumed
 };
+// ---- the two KV formats behind one pair of pointers (kv_layer_stride: elements of a layer = bytes of a layer's int8 plane)
+static bool lm_kv_q8(const rca_lm* h) { return h->kv_format == 1; }
+static size_t lm_kv_plane_bytes(const rca_lm* h) {
+    const size_t n = (size_t)h->cfg.n_layers * h->kv_layer_stride;
+    return lm_kv_q8(h) ? n + n / 32 * sizeof(f16_t) : n * sizeof(f16_t);
+}
+static long lm_kv_sc_off(const rca_lm* h) { return (long)h->cfg.n_layers * h->kv_layer_stride; }   // q8_0: bytes from kc / vc to the scales
+template <class T>
+static T* lm_kv_layer(const rca_lm* h, T* base, int l) {   // layer l of kc / vc as the attention kernels take it
+    return lm_kv_q8(h) ? reinterpret_cast<T*>((char*)base + (long)l * h->kv_layer_stride) : base + (long)l * h->kv_layer_stride;
+}
+static const f16_t* lm_kv_scales(const rca_lm* h, const f16_t* base, int l) {   // q8_0: the scales of layer l
+    return reinterpret_cast<const f16_t*>((const char*)base + lm_kv_sc_off(h)) + (long)l * (h->kv_layer_stride >> 5);
+}
+static int lm_kv_bytes_per_pos(const rca_lm* h) {
+    const int per_row = lm_kv_q8(h) ? 64 + 2 * (int)sizeof(f16_t) : 64 * (int)sizeof(f16_t);
+    return 2 * h->cfg.n_layers * h->cfg.n_kv_heads * per_row;
+}
+// where the QKV epilogues of layer l store their fp16 rows: the cache itself, or the ring
+static void lm_rope_target(const rca_lm* h, int l, GemvRope& rope) {
+    if (lm_kv_q8(h)) { rope.kc = h->ring_k; rope.vc = h->ring_v; rope.pos_mask = LM_KV_RING - 1; }
+    else { rope.kc = h->kc + (long)l * h->kv_layer_stride; rope.vc = h->vc + (long)l * h->kv_layer_stride; rope.pos_mask = -1; }
+}
+static LmGroupRow lm_group_row(const rca_lm* h, int j, int xrow) {
+    if (lm_kv_q8(h)) return LmGroupRow{h->stt, h->ring_k, h->ring_v, h->logits, 0, j, xrow, h->cfg.n_ctx, LM_KV_RING - 1};
+    return LmGroupRow{h->stt, h->kc, h->vc, h->logits, h->kv_layer_stride, j, xrow, h->cfg.n_ctx, -1};
+}
+static int lm_alloc(void** p, size_t bytes);
+// (re)allocate the cache in the handle's format, zeroed
+static int lm_kv_alloc(rca_lm* h) {
+    int rc;
+    for (f16_t** p : {&h->kc, &h->vc, &h->ring_k, &h->ring_v})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    const size_t kvb = lm_kv_plane_bytes(h);
+    if (lm_kv_q8(h) && (kvb >> 35) != 0) return fail(RCA_ERR_ARG, "q8_0 KV cache: %zu bytes per tensor (the scale offset is passed in 16-byte units as an int)", kvb);
+    if ((rc = lm_alloc((void**)&h->kc, kvb)) != RCA_OK) return rc;
+    if ((rc = lm_alloc((void**)&h->vc, kvb)) != RCA_OK) return rc;
+    RCA_HIP(hipMemsetAsync(h->kc, 0, kvb, h->stream));
+    RCA_HIP(hipMemsetAsync(h->vc, 0, kvb, h->stream));
+    if (lm_kv_q8(h)) {
+        const size_t rb = (size_t)LM_KV_RING * h->cfg.n_kv_heads * 64 * sizeof(f16_t);
+        if ((rc = lm_alloc((void**)&h->ring_k, rb)) != RCA_OK) return rc;
+        if ((rc = lm_alloc((void**)&h->ring_v, rb)) != RCA_OK) return rc;
+        RCA_HIP(hipMemsetAsync(h->ring_k, 0, rb, h->stream));
+        RCA_HIP(hipMemsetAsync(h->ring_v, 0, rb, h->stream));
+    }
+    return RCA_OK;
+}
 struct DuplexState;
 static void duplex_destroy(DuplexState* d);
 static void duplex_drop_graphs(DuplexState* d);
@@ -2349,11 +2406,11 @@ extern "C" int rca_lm_destroy(rca_lm_t* h) {
     lm_drop_graphs(h);
     duplex_destroy(h->duplex);
     h->duplex = nullptr;
-    for (void* p : {(void*)h->kc, (void*)h->vc, (void*)h->kv_stage, (void*)h->x, (void*)h->xn, (void*)h->qkv, (void*)h->attn, (void*)h->hbuf,
+    for (void* p : {(void*)h->kc, (void*)h->vc, (void*)h->ring_k, (void*)h->ring_v, (void*)h->kv_stage, (void*)h->x, (void*)h->xn, (void*)h->qkv, (void*)h->attn, (void*)h->hbuf,
                     (void*)h->att_part, (void*)h->logits, (void*)h->probs_dev, (void*)h->probe_ids_dev, (void*)h->att_arrive, (void*)h->xh, (void*)h->xl,
                     (void*)h->gpart, (void*)h->stt, (void*)h->samp, (void*)h->swork})
         if (p) (void)hipFree(p);
-    h->kc = h->vc = h->kv_stage = nullptr;
+    h->kc = h->vc = h->kv_stage = h->ring_k = h->ring_v = nullptr;
     h->x = h->xn = h->qkv = h->attn = h->hbuf = h->att_part = h->logits = h->probs_dev = h->gpart = nullptr;
     h->probe_ids_dev = nullptr; h->att_arrive = nullptr; h->xh = h->xl = nullptr; h->stt = nullptr; h->samp = nullptr; h->swork = nullptr;
     if (h->h_stt) { (void)hipHostFree(h->h_stt); h->h_stt = nullptr; }
@@ -2843,11 +2900,7 @@ static int lm_common_init(rca_lm* h, const rca_tensor_t* ts, int nt, const rca_l
     }
     // KV cache
     h->kv_layer_stride = (long)h->n_ctx_pad * c.n_kv_heads * c.head_dim;
-    const size_t kvb = (size_t)c.n_layers * h->kv_layer_stride * 2;
-    if ((rc = lm_alloc((void**)&h->kc, kvb)) != RCA_OK) return rc;
-    if ((rc = lm_alloc((void**)&h->vc, kvb)) != RCA_OK) return rc;
-    RCA_HIP(hipMemsetAsync(h->kc, 0, kvb, h->stream));
-    RCA_HIP(hipMemsetAsync(h->vc, 0, kvb, h->stream));
+    if ((rc = lm_kv_alloc(h)) != RCA_OK) return rc;
     // activations
     const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim;
     if ((rc = lm_alloc((void**)&h->x, (size_t)LM_MAXM * H * 4)) != RCA_OK) return rc;
@@ -3051,6 +3104,7 @@ extern "C" int rca_lm_create_shared(rca_lm_t* parent, int32_t n_ctx, int32_t log
     h->fuse_attn = parent->fuse_attn;
     h->mfma_prefill = parent->mfma_prefill;
     h->act_format = parent->act_format;
+    h->kv_format = parent->kv_format;   // (lm_common_init below allocates the cache in it)
     owner->borrowers++;
     if ((rc = lm_common_init(h, nullptr, 0, owner)) != RCA_OK) { rca_lm_destroy(h); return rc; }
     *out = h;
@@ -3295,8 +3349,88 @@ struct LmBatchMember {
     int row0;                 // its first row in the batch's qkv / hi / lo buffers
     int n_splits, n_ctx;
     int serial;               // 1: its sampler is the serial top-k chain, run by the table kernels
+    // q8_0 cache (every member of a batch has the same format): kc / vc are the int8 planes, kv_stride their layer stride in bytes; the
+    // fp16 scales [L][n_ctx_pad][nkv][2] start sc_off bytes behind kc / vc; ring_k / ring_v: the member's staging ring (LmGroupRow::kc)
+    long sc_off;
+    const f16_t* ring_k; const f16_t* ring_v;
+    int ring_mask, pad;
 };
-template <int G, bool TAB = false>
+// ------------------------------------------------------------------ q8_0 KV cache (rca_lm_set_kv_format)
+// A cached head row (64 values of K or of V) is two ggml q8_0 blocks: 32 int8 + one fp16 scale each, kept in two planes per tensor,
+// q[L][n_ctx_pad][nkv][64] int8 and d[L][n_ctx_pad][nkv][2] fp16, so a head row is 64 contiguous, 64-byte-aligned bytes.
+// Contract: cache row == Q8(the fp16 row the default cache would hold).  The QKV epilogues are untouched but for where they store:
+// under q8_0 their fp16 rows go to a per-handle ring of LM_KV_RING positions (row pos & (LM_KV_RING - 1); one ring for all layers,
+// a layer's rows are quantised before the next layer's projection runs), and lm_kv_quant_kernel, one small launch per layer between
+// the projection and attention, turns the rows of the pass into blocks with the rule of the q8_1 activations:
+//   d = amax / 127;  inv = d != 0 ? 1 / d : 0;  q_j = roundf(x_j * inv);  stored scale d16 = fp16_rne(d)
+// Attention multiplies fp16_rne((float)d16 * q_j), formed while a row is staged into the LDS images (kvq8_deq16): behind the images
+// nothing differs from the fp16 cache.
+static_assert((LM_KV_RING & (LM_KV_RING - 1)) == 0, "ring positions are masked");
+// 16 int8 of one block and the block's scale -> the 16 fp16 values as two 16-byte chunks ((float)d16 * q is exact in f32: 11 x 7 bits)
+__device__ __forceinline__ void kvq8_deq16(const u32x4 q, const f16_t d16, u32x4& c0, u32x4& c1) {
+    const float d = (float)d16;
+    f16x8 a, b;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float v = (float)(int)(signed char)(q[w] >> (8 * e)) * d;
+            if (w < 2) a[4 * w + e] = (_Float16)v;
+            else b[4 * (w - 2) + e] = (_Float16)v;
+        }
+    c0 = __builtin_bit_cast(u32x4, a);
+    c1 = __builtin_bit_cast(u32x4, b);
+}
+// grid (blocks of 8 units, token of the pass, member): a unit is one q8_0 block = 32 lanes, lane <-> value; units of a position are
+// ordered (tensor, kv head, block).  stt != nullptr: position and token count of the pass come from the device state (graph-safe);
+// else from pos0_arg / m_arg (rca_lm_kv_write).  which: bit 0 K, bit 1 V.  TAB: everything per member from tab[blockIdx.z].
+template <bool TAB>
+__global__ __launch_bounds__(256) void lm_kv_quant_kernel(const LmDevState* __restrict__ stt, const f16_t* __restrict__ ring_k, const f16_t* __restrict__ ring_v,
+                                                          int ring_mask, signed char* __restrict__ kq, signed char* __restrict__ vq,
+                                                          f16_t* __restrict__ kd, f16_t* __restrict__ vd, int nkv, int n_ctx, int pos0_arg, int m_arg,
+                                                          int which, const LmBatchMember* __restrict__ tab, int tab_layer) {
+    if constexpr (TAB) {
+        const LmBatchMember e = tab[blockIdx.z];
+        if (!e.stt) return;   // a slot past the live count of a selection frame
+        stt = e.stt;
+        ring_k = e.ring_k; ring_v = e.ring_v; ring_mask = e.ring_mask;
+        kq = reinterpret_cast<signed char*>(const_cast<f16_t*>(e.kc)) + (long)tab_layer * e.kv_stride;
+        vq = reinterpret_cast<signed char*>(const_cast<f16_t*>(e.vc)) + (long)tab_layer * e.kv_stride;
+        kd = reinterpret_cast<f16_t*>(reinterpret_cast<char*>(const_cast<f16_t*>(e.kc)) + e.sc_off) + (long)tab_layer * (e.kv_stride >> 5);
+        vd = reinterpret_cast<f16_t*>(reinterpret_cast<char*>(const_cast<f16_t*>(e.vc)) + e.sc_off) + (long)tab_layer * (e.kv_stride >> 5);
+        n_ctx = e.n_ctx;
+    }
+    const int M = stt ? stt->m : m_arg;
+    const int tok = blockIdx.y;
+    if (tok >= M) return;
+    const int pos = (stt ? stt->n_tokens : pos0_arg) + tok;
+    if (pos >= n_ctx) return;
+    const int unit = blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (unit >= 4 * nkv) return;
+    const int tensor = unit / (2 * nkv), hb = unit - tensor * 2 * nkv;   // hb = kv head * 2 + block
+    if (!((which >> tensor) & 1)) return;
+    const int j = threadIdx.x & 31;
+    const float x = (float)(tensor ? ring_v : ring_k)[((long)(pos & ring_mask) * nkv) * 64 + hb * 32 + j];
+    float amax = fabsf(x);
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 32));
+    const float d = amax / 127.0f;
+    const float inv = d != 0.0f ? 1.0f / d : 0.0f;
+    (tensor ? vq : kq)[((long)pos * nkv) * 64 + hb * 32 + j] = (signed char)(int)roundf(x * inv);
+    if (j == 0) (tensor ? vd : kd)[((long)pos * nkv) * 2 + hb] = (f16_t)d;
+}
+// rca_lm_kv_read / rca_lm_gemv_tap on a q8_0 cache: n16 pieces of 16 values, de-quantised by the code attention stages rows with
+__global__ __launch_bounds__(256) void lm_kv_dequant_kernel(const signed char* __restrict__ q, const f16_t* __restrict__ d, f16_t* __restrict__ out, long n16) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n16) return;
+    u32x4 c0, c1;
+    kvq8_deq16(*reinterpret_cast<const u32x4*>(q + 16 * i), d[i >> 1], c0, c1);
+    *reinterpret_cast<u32x4*>(out + 16 * i) = c0;
+    *reinterpret_cast<u32x4*>(out + 16 * i + 8) = c1;
+}
+// KVQ = 1: the cache is q8_0 -- kc / vc are the int8 planes of the layer, kd / vd its scales; only the global loads and the image writes
+// differ (a lane takes 16 int8 of a row and their block's scale: 16 rows per instruction, two chunks per lane and load)
+template <int G, bool TAB = false, int KVQ = 0>
 // (argument order: what the first loads need -- the cache pointers, the head counts, n_ctx -- sits inside the 14 dwords the
 //  dispatcher preloads into SGPRs; `part` / `arrive` / `attn_out` are only needed at the end)
 __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __restrict__ stt, const float* __restrict__ qkv,
@@ -3304,13 +3438,28 @@ __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __r
                                                            int nh, int nkv, int n_splits, float scale, int n_ctx,
                                                            float* __restrict__ part, int* __restrict__ arrive, float* __restrict__ attn_out,
                                                            const LmBatchMember* __restrict__ tab = nullptr, int tab_layer = 0) {
+    // q8_0 scales of the layer.  The argument list is the fp16 kernel's (its instances are what they were): without a table, tab_layer
+    // carries the distance from the layer's int8 plane to its scales in units of 16 bytes -- the same for K and V, whose allocations
+    // have one layout
+    const f16_t *kd = nullptr, *vd = nullptr;
+    if constexpr (KVQ && !TAB) {
+        kd = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(kc) + (long)tab_layer * 16);
+        vd = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(vc) + (long)tab_layer * 16);
+    }
     if constexpr (TAB) {
         const LmBatchMember e = tab[blockIdx.z];
         if ((int)blockIdx.y >= e.n_splits) return;   // (also a slot past a selection's live count: an all-zero entry has no splits)
         stt = e.stt;
         qkv += (long)e.row0 * (nh + 2 * nkv) * 64;
-        kc = e.kc + (long)tab_layer * e.kv_stride;
-        vc = e.vc + (long)tab_layer * e.kv_stride;
+        if constexpr (KVQ) {
+            kd = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(e.kc) + e.sc_off) + (long)tab_layer * (e.kv_stride >> 5);
+            vd = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(e.vc) + e.sc_off) + (long)tab_layer * (e.kv_stride >> 5);
+            kc = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(e.kc) + (long)tab_layer * e.kv_stride);
+            vc = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(e.vc) + (long)tab_layer * e.kv_stride);
+        } else {
+            kc = e.kc + (long)tab_layer * e.kv_stride;
+            vc = e.vc + (long)tab_layer * e.kv_stride;
+        }
         n_splits = e.n_splits;
         n_ctx = e.n_ctx;
         part = e.part;
@@ -3448,17 +3597,27 @@ __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __r
     // swizzles).  Loading the A layout directly (lane <-> key: 16 bytes of each of 32 rows per instruction) made the CU's address
     // path the bottleneck of the whole launch: round-4 timeline, 1 k context, 32 workgroups: wave 0 had its keys 2.4 us after entry
     // and wave 7 1.55 us later (profiles/r04/attn_decode_timeline.txt).  K first, then q, then V: S^T starts while V is in flight.
-    u32x4 kf[4], vf[4];
+    u32x4 kf[KVQ ? 2 : 4], vf[KVQ ? 2 : 4];
+    f16_t ksc[2], vsc[2];   // q8_0: the scales of the two loads' blocks
     f32x4 qf[4][2];
     char* const kbytes = reinterpret_cast<char*>(attm_lds) + wave * 8192;   // K image [key][128 bytes], chunk c of key k at c ^ ((k >> 1) & 7)
     char* const vbytes = kbytes + 4096;                                     // V image, chunk c of key k at c ^ (k1 k2 k0)
-    const int ld_key = lane >> 3, ld_chunk = lane & 7;
+    const int ld_key = KVQ ? lane >> 2 : lane >> 3, ld_chunk = KVQ ? 2 * (lane & 3) : lane & 7;   // q8_0: the first of the lane's two chunks
     {
-        long roff[4];
+        long roff[4];   // (q8_0: two loads, their offsets set below)
 #pragma unroll
         for (int i = 0; i < 4; ++i) roff[i] = ((long)min(kwb + 8 * i + ld_key, n_ctx - 1) * nkv + g) * HD + 8 * ld_chunk;
+        if constexpr (KVQ) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) kf[i] = *reinterpret_cast<const u32x4*>(kc + roff[i]);
+            for (int i = 0; i < 2; ++i) {   // load i: keys 16 i .. 16 i + 15; byte offset == element offset, a block is 4 chunks
+                roff[i] = ((long)min(kwb + 16 * i + ld_key, n_ctx - 1) * nkv + g) * HD + 8 * ld_chunk;
+                kf[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(kc) + roff[i]);
+                ksc[i] = kd[roff[i] >> 5];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) kf[i] = *reinterpret_cast<const u32x4*>(kc + roff[i]);
+        }
         // a decode step (fused merge) has at most two tokens: the lanes of the 24 dead query rows load nothing (their scores are
         // masked whatever q they hold) -- the q loads were as many bytes through the CU's address path as K and V together
         const float* qp = qkv + (long)min(t0 + tl, LM_MAXM - 1) * ld + (g * G + hq) * HD + 8 * half;
@@ -3471,13 +3630,28 @@ __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __r
                 qf[sub][1] = *reinterpret_cast<const f32x4*>(qp + 16 * sub + 4);
             }
         }
+        if constexpr (KVQ) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) vf[i] = *reinterpret_cast<const u32x4*>(vc + roff[i]);
+            for (int i = 0; i < 2; ++i) {
+                vf[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(vc) + roff[i]);
+                vsc[i] = vd[roff[i] >> 5];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) vf[i] = *reinterpret_cast<const u32x4*>(vc + roff[i]);
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
     auto pin_loads = [&]() {
+        if constexpr (KVQ) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) asm volatile("" ::"v"(kf[c]), "v"(vf[c]), "v"(qf[c][0]), "v"(qf[c][1]));
+            for (int c = 0; c < 2; ++c) asm volatile("" ::"v"(kf[c]), "v"(vf[c]), "v"(ksc[c]), "v"(vsc[c]));
+#pragma unroll
+            for (int c = 0; c < 4; ++c) asm volatile("" ::"v"(qf[c][0]), "v"(qf[c][1]));
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) asm volatile("" ::"v"(kf[c]), "v"(vf[c]), "v"(qf[c][0]), "v"(qf[c][1]));
+        }
     };
     const int M = stt->m;
     if (t0 >= M) { pin_loads(); return; }
@@ -3496,10 +3670,21 @@ __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __r
         return;
     }
     // ---- K image of this wave (written and read by this wave only: LDS operations of a wave complete in order)
+    if constexpr (KVQ) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = 8 * i + ld_key;
-        *reinterpret_cast<u32x4*>(kbytes + k * 128 + ((ld_chunk ^ ((k >> 1) & 7)) << 4)) = kf[i];
+        for (int i = 0; i < 2; ++i) {
+            const int k = 16 * i + ld_key;
+            u32x4 c0, c1;
+            kvq8_deq16(kf[i], ksc[i], c0, c1);
+            *reinterpret_cast<u32x4*>(kbytes + k * 128 + ((ld_chunk ^ ((k >> 1) & 7)) << 4)) = c0;
+            *reinterpret_cast<u32x4*>(kbytes + k * 128 + (((ld_chunk + 1) ^ ((k >> 1) & 7)) << 4)) = c1;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = 8 * i + ld_key;
+            *reinterpret_cast<u32x4*>(kbytes + k * 128 + ((ld_chunk ^ ((k >> 1) & 7)) << 4)) = kf[i];
+        }
     }
     ATL_STAMP(13);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -3525,10 +3710,22 @@ __global__ __launch_bounds__(512) void lm_attn_mfma_kernel(const LmDevState* __r
         sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfr, ql, sacc, 0, 0, 0);
     }
     // ---- V image (its loads were issued behind K and q)
+    if constexpr (KVQ) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = 8 * i + ld_key;
-        *reinterpret_cast<u32x4*>(vbytes + k * 128 + ((ld_chunk ^ ((((k >> 1) & 1) << 2) | (((k >> 2) & 1) << 1) | (k & 1))) << 4)) = vf[i];
+        for (int i = 0; i < 2; ++i) {
+            const int k = 16 * i + ld_key;
+            const int sw = (((k >> 1) & 1) << 2) | (((k >> 2) & 1) << 1) | (k & 1);
+            u32x4 c0, c1;
+            kvq8_deq16(vf[i], vsc[i], c0, c1);
+            *reinterpret_cast<u32x4*>(vbytes + k * 128 + ((ld_chunk ^ sw) << 4)) = c0;
+            *reinterpret_cast<u32x4*>(vbytes + k * 128 + (((ld_chunk + 1) ^ sw) << 4)) = c1;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = 8 * i + ld_key;
+            *reinterpret_cast<u32x4*>(vbytes + k * 128 + ((ld_chunk ^ ((((k >> 1) & 1) << 2) | (((k >> 2) & 1) << 1) | (k & 1))) << 4)) = vf[i];
+        }
     }
     ATL_STAMP(1);   // V of this wave is in registers (its image requested)
     ATL_STAMP_W7(9);
@@ -3746,11 +3943,13 @@ __global__ __launch_bounds__(64) void lm_attn_mfma_batch_combine_kernel(const Lm
 // LDS, so every CU gets exactly one and the dispatcher cannot pile five tiles on one CU and three on another (measured with one tile
 // per workgroup: 414 .. 730 key blocks per CU, the last CU done at 135 us against a median of 101); the four tiles of workgroup j
 // are j, 2 n - 1 - j, 2 n + j and 4 n - 1 - j of the head's 4 n tiles, whose causal lengths add up to the same total for every j.
-template <int G, int TEAMS>
+// KVQ = 1: q8_0 cache (see lm_attn_mfma_kernel): the block in flight is 2 x 16 int8 per lane and tensor plus the blocks' scales
+template <int G, int TEAMS, int KVQ = 0>
 __global__ __launch_bounds__(64 * FLASH_WAVES * TEAMS, 3) void lm_attn_flash_kernel(const LmDevState* __restrict__ stt, const float* __restrict__ qkv,
                                                                         const f16_t* __restrict__ kc, const f16_t* __restrict__ vc,
                                                                         float* __restrict__ attn_out, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo,
-                                                                        int nh, int nkv, float scale, int n_ctx) {
+                                                                        int nh, int nkv, float scale, int n_ctx,
+                                                                        const f16_t* __restrict__ kd = nullptr, const f16_t* __restrict__ vd = nullptr) {
     constexpr int HD = 64;
     constexpr int TPB = 32 / G;   // tokens per tile
     constexpr int NWAVES = FLASH_WAVES * TEAMS;
@@ -3797,28 +3996,54 @@ __global__ __launch_bounds__(64 * FLASH_WAVES * TEAMS, 3) void lm_attn_flash_ker
     // each of 32 rows per instruction -- touched 32 lines for 1 KB and made the kernel wait on the L1: 4100 of 4900 cycles per block.)
     // Images: chunk c of key k sits at chunk c ^ sw(k); K: sw = (k >> 1) & 7, so the 16 lanes of a ds_read_b128 group (lane <-> key) tile
     // the 64 banks; V: sw = k1 k2 k0 (bits of k), so the 4 rows x 64 bytes of a transposed read do.  A store group is 8 lanes = one row.
-    u32x4 kf[4], vf[4];
-    const int ld_key = lane >> 3, ld_chunk = lane & 7;
+    u32x4 kf[KVQ ? 2 : 4], vf[KVQ ? 2 : 4];
+    f16_t ksc[2], vsc[2];
+    const int ld_key = KVQ ? lane >> 2 : lane >> 3, ld_chunk = KVQ ? 2 * (lane & 3) : lane & 7;   // q8_0: 16 rows per load, the first of the lane's two chunks
     auto load_block = [&](int kb) {
+        if constexpr (KVQ) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const long off = ((long)min(32 * max(kb, 0) + 8 * i + ld_key, kmax - 1) * nkv + g) * HD + 8 * ld_chunk;   // keys past kmax: a written row, p = 0
-            kf[i] = *reinterpret_cast<const u32x4*>(kc + off);
-            vf[i] = *reinterpret_cast<const u32x4*>(vc + off);
+            for (int i = 0; i < 2; ++i) {   // byte offset == element offset; a scale covers 32 of them
+                const long off = ((long)min(32 * max(kb, 0) + 16 * i + ld_key, kmax - 1) * nkv + g) * HD + 8 * ld_chunk;
+                kf[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(kc) + off);
+                vf[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(vc) + off);
+                ksc[i] = kd[off >> 5];
+                vsc[i] = vd[off >> 5];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const long off = ((long)min(32 * max(kb, 0) + 8 * i + ld_key, kmax - 1) * nkv + g) * HD + 8 * ld_chunk;   // keys past kmax: a written row, p = 0
+                kf[i] = *reinterpret_cast<const u32x4*>(kc + off);
+                vf[i] = *reinterpret_cast<const u32x4*>(vc + off);
+            }
         }
     };
-    int kw_off[4], vw_off[4];
+    int kw_off[4], vw_off[4];   // q8_0: [2 i + j] = chunk ld_chunk + j of load i
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int k = 8 * i + ld_key;
-        kw_off[i] = k * 128 + ((ld_chunk ^ ((k >> 1) & 7)) << 4);
-        vw_off[i] = k * 128 + ((ld_chunk ^ ((((k >> 1) & 1) << 2) | (((k >> 2) & 1) << 1) | (k & 1))) << 4);
+        const int k = KVQ ? 16 * (i >> 1) + ld_key : 8 * i + ld_key;
+        const int ch = KVQ ? ld_chunk + (i & 1) : ld_chunk;
+        kw_off[i] = k * 128 + ((ch ^ ((k >> 1) & 7)) << 4);
+        vw_off[i] = k * 128 + ((ch ^ ((((k >> 1) & 1) << 2) | (((k >> 2) & 1) << 1) | (k & 1))) << 4);
     }
     auto stage_block = [&]() {   // the registers' block becomes the current images
+        if constexpr (KVQ) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<u32x4*>(kbytes + kw_off[i]) = kf[i];
-            *reinterpret_cast<u32x4*>(vbytes + vw_off[i]) = vf[i];
+            for (int i = 0; i < 2; ++i) {
+                u32x4 c0, c1;
+                kvq8_deq16(kf[i], ksc[i], c0, c1);
+                *reinterpret_cast<u32x4*>(kbytes + kw_off[2 * i]) = c0;
+                *reinterpret_cast<u32x4*>(kbytes + kw_off[2 * i + 1]) = c1;
+                kvq8_deq16(vf[i], vsc[i], c0, c1);
+                *reinterpret_cast<u32x4*>(vbytes + vw_off[2 * i]) = c0;
+                *reinterpret_cast<u32x4*>(vbytes + vw_off[2 * i + 1]) = c1;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                *reinterpret_cast<u32x4*>(kbytes + kw_off[i]) = kf[i];
+                *reinterpret_cast<u32x4*>(vbytes + vw_off[i]) = vf[i];
+            }
         }
     };
     load_block(min(wave, nblk - 1));
@@ -4054,11 +4279,20 @@ __global__ __launch_bounds__(64 * FLASH_WAVES * TEAMS, 3) void lm_attn_flash_ker
     }
 }
 template <int G>
-static void launch_attention_flash_g(rca_lm* h, int M, const f16_t* kc, const f16_t* vc, hipStream_t st, bf16_t* hi, bf16_t* lo) {
+static void launch_attention_flash_g(rca_lm* h, int M, const f16_t* kc, const f16_t* vc, hipStream_t st, bf16_t* hi, bf16_t* lo, const f16_t* kd, const f16_t* vd) {
     const rca_lm_config_t& c = h->cfg;
     const float scale = 1.0f / sqrtf((float)c.head_dim);
     const int ntiles = cdiv(M * G, 32);
     // teams per workgroup: 4 (one workgroup per CU) once that still gives every CU of the device a workgroup, else 2, else 1
+    if (kd) {   // q8_0 cache: the same three shapes
+        if (c.n_kv_heads * cdiv(ntiles, 4) >= h->n_cus)
+            lm_attn_flash_kernel<G, 4, 1><<<dim3(c.n_kv_heads, cdiv(ntiles, 4)), 64 * FLASH_WAVES * 4, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx, kd, vd);
+        else if (c.n_kv_heads * cdiv(ntiles, 2) >= h->n_cus)
+            lm_attn_flash_kernel<G, 2, 1><<<dim3(c.n_kv_heads, cdiv(ntiles, 2)), 64 * FLASH_WAVES * 2, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx, kd, vd);
+        else
+            lm_attn_flash_kernel<G, 1, 1><<<dim3(c.n_kv_heads, ntiles), 64 * FLASH_WAVES, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx, kd, vd);
+        return;
+    }
     if (c.n_kv_heads * cdiv(ntiles, 4) >= h->n_cus)
         lm_attn_flash_kernel<G, 4><<<dim3(c.n_kv_heads, cdiv(ntiles, 4)), 64 * FLASH_WAVES * 4, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx);
     else if (c.n_kv_heads * cdiv(ntiles, 2) >= h->n_cus)
@@ -4066,13 +4300,27 @@ static void launch_attention_flash_g(rca_lm* h, int M, const f16_t* kc, const f1
     else
         lm_attn_flash_kernel<G, 1><<<dim3(c.n_kv_heads, ntiles), 64 * FLASH_WAVES, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx);
 }
-static void launch_attention_flash(rca_lm* h, int M, const f16_t* kc, const f16_t* vc, hipStream_t st, bf16_t* hi, bf16_t* lo) {
+static void launch_attention_flash(rca_lm* h, int M, const f16_t* kc, const f16_t* vc, hipStream_t st, bf16_t* hi, bf16_t* lo, const f16_t* kd, const f16_t* vd) {
     const int G = h->cfg.n_heads / h->cfg.n_kv_heads;
-    if (G == 4) launch_attention_flash_g<4>(h, M, kc, vc, st, hi, lo);
-    else if (G == 2) launch_attention_flash_g<2>(h, M, kc, vc, st, hi, lo);
-    else launch_attention_flash_g<1>(h, M, kc, vc, st, hi, lo);
+    if (G == 4) launch_attention_flash_g<4>(h, M, kc, vc, st, hi, lo, kd, vd);
+    else if (G == 2) launch_attention_flash_g<2>(h, M, kc, vc, st, hi, lo, kd, vd);
+    else launch_attention_flash_g<1>(h, M, kc, vc, st, hi, lo, kd, vd);
+}
+// the q8_0 quantiser of layer l over the rows the pass has just stored into the ring (nothing to do for an fp16 cache).  m_max: the
+// most tokens the pass can have (the grid); the live count and the position are read on the device
+static void lm_launch_kv_quant(rca_lm* h, int l, int m_max, hipStream_t st) {
+    if (!lm_kv_q8(h)) return;
+    const rca_lm_config_t& c = h->cfg;
+    lm_kv_quant_kernel<false><<<dim3(cdiv(4 * c.n_kv_heads, 8), m_max), 256, 0, st>>>(
+        h->stt, h->ring_k, h->ring_v, LM_KV_RING - 1, reinterpret_cast<signed char*>(lm_kv_layer(h, h->kc, l)), reinterpret_cast<signed char*>(lm_kv_layer(h, h->vc, l)),
+        const_cast<f16_t*>(lm_kv_scales(h, h->kc, l)), const_cast<f16_t*>(lm_kv_scales(h, h->vc, l)), c.n_kv_heads, c.n_ctx, 0, 0, 3, nullptr, 0);
 }
 
+// a member's entry of a batch table (either cache format)
+static LmBatchMember lm_batch_member(const rca_lm* h, int row0, bool serial) {
+    return LmBatchMember{h->stt, h->kc, h->vc, h->kv_layer_stride, h->att_part, h->logits, h->samp, h->swork, row0, h->n_splits, h->cfg.n_ctx, serial ? 1 : 0,
+                         lm_kv_q8(h) ? lm_kv_sc_off(h) : 0, h->ring_k, h->ring_v, LM_KV_RING - 1, 0};
+}
 // split attention on MFMA + merge of the splits, for the M tokens of the current pass
 // qkv / attn: the M query rows and where their outputs go -- the handle's own buffers for its own passes, the rows of ONE member inside the
 // shared buffers of a group step (the flash route, prefill only, reads the handle's)
@@ -4080,18 +4328,28 @@ static void launch_attention_mfma(rca_lm* h, int M, int nsp_launch, const f16_t*
                                   bf16_t* hi = nullptr, bf16_t* lo = nullptr, bool prefill = false) {
     const rca_lm_config_t& c = h->cfg;
     static const bool flash = !(getenv("RCA_LM_FLASH") && atoi(getenv("RCA_LM_FLASH")) == 0);   // 0: A/B runs against the split kernel
+    // q8_0 cache: kc / vc are a layer of the int8 planes (lm_kv_layer); its scales sit at the same element offset / 32 of the scale plane
+    const f16_t *kd = nullptr, *vd = nullptr;
+    if (lm_kv_q8(h)) {
+        kd = lm_kv_scales(h, h->kc, 0) + (((const char*)kc - (const char*)h->kc) >> 5);
+        vd = lm_kv_scales(h, h->vc, 0) + (((const char*)vc - (const char*)h->vc) >> 5);
+    }
     if (prefill && flash) {   // every pass of the prefill-tile path, whatever its size: pieces of one long eval must use ONE arithmetic
-        launch_attention_flash(h, M, kc, vc, st, hi, lo);
+        launch_attention_flash(h, M, kc, vc, st, hi, lo, kd, vd);
         return;
     }
     const int G = c.n_heads / c.n_kv_heads;
     const float scale = 1.0f / sqrtf((float)c.head_dim);
+    const int sc_units = kd ? (int)(((const char*)kd - (const char*)kc) >> 4) : 0;   // (lm_kv_alloc keeps a plane below 2^35 bytes)
     dim3 agm(c.n_kv_heads, nsp_launch, cdiv(M * G, 32));
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
         (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
         (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
         attr_done = true;
     }
     // decode steps: the merge of the splits is fused into the attention launch while the grid is at most one workgroup per CU (the
@@ -4099,7 +4357,9 @@ static void launch_attention_mfma(rca_lm* h, int M, int nsp_launch, const f16_t*
     const bool fuse = h->fuse_attn && !hi && agm.z == 1 && c.n_kv_heads * nsp_launch <= 256 && M * G <= 8 && nsp_launch <= ATT_TAG_MAXSP && c.n_kv_heads <= ATT_EPOCH_INTS;
     int* arrive = fuse ? h->att_arrive : nullptr;
 #define RCA_ATTN_LAUNCH(GG)                                                                                                                        \
-    lm_attn_mfma_kernel<GG><<<agm, 512, ATTM_LDS, st>>>(h->stt, qkv, kc, vc, c.n_heads, c.n_kv_heads, h->n_splits, scale, c.n_ctx, h->att_part, \
+    if (kd) lm_attn_mfma_kernel<GG, false, 1><<<agm, 512, ATTM_LDS, st>>>(h->stt, qkv, kc, vc, c.n_heads, c.n_kv_heads, h->n_splits, scale, c.n_ctx,  \
+                                                                          h->att_part, arrive, attn, nullptr, sc_units);                           \
+    else lm_attn_mfma_kernel<GG><<<agm, 512, ATTM_LDS, st>>>(h->stt, qkv, kc, vc, c.n_heads, c.n_kv_heads, h->n_splits, scale, c.n_ctx, h->att_part, \
                                                         arrive, attn);                                                                             \
     if (!fuse) lm_attn_mfma_combine_kernel<GG><<<M * c.n_heads, 64, 0, st>>>(h->stt, h->att_part, attn, c.n_heads, c.n_kv_heads, h->n_splits, nsp_launch, hi, lo);
     if (G == 4) { RCA_ATTN_LAUNCH(4) }
@@ -4121,12 +4381,14 @@ static void lm_launch_qkv(rca_lm* h, int l, int M, hipStream_t st) {   // RMSNor
     const LmLayer& L = h->layers[l];
     const int QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim;
     const GemvPro pro{h->x, L.attn_norm, c.rms_eps, 0};
-    GemvRope rope{h->cos_t, h->sin_t, h->kc + (long)l * h->kv_layer_stride, h->vc + (long)l * h->kv_layer_stride, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
+    GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
+    lm_rope_target(h, l, rope);
     launch_gemv<1, 2>(GEMV_QKV, h, M, L.qkv, nullptr, h->qkv, L.qkv.N, c.hidden, QKV, pro, rope, st);
     if (L.split_v) {   // the V projection of this layer is kept in another format than Q / K (a Q4_K_M file): its own launch
         rope.row_base = L.qkv.N;
         launch_gemv<1, 2>(GEMV_QKV, h, M, L.vseg, nullptr, h->qkv, L.vseg.N, c.hidden, QKV, pro, rope, st);
     }
+    lm_launch_kv_quant(h, l, M, st);
 }
 static void lm_launch_o(rca_lm* h, int l, int M, hipStream_t st) {   // x += O attn
     const int AO = h->cfg.n_heads * h->cfg.head_dim;
@@ -4156,7 +4418,7 @@ static int lm_enqueue_pass(rca_lm* h, int M, int want_logits, hipStream_t st, in
     if (!skip_embed) lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, h->x, c.hidden, c.vocab_size);   // (inside a frame graph the previous step's sampler has gathered the rows)
     for (int l = 0; l < c.n_layers; ++l) {
         lm_launch_qkv(h, l, M, st);
-        launch_attention_mfma(h, M, nsp_launch, h->kc + (long)l * h->kv_layer_stride, h->vc + (long)l * h->kv_layer_stride, h->qkv, h->attn, st);
+        launch_attention_mfma(h, M, nsp_launch, lm_kv_layer(h, h->kc, l), lm_kv_layer(h, h->vc, l), h->qkv, h->attn, st);
         lm_launch_o(h, l, M, st);
         lm_launch_gu(h, l, M, st);
         lm_launch_down(h, l, M, st);
@@ -4467,6 +4729,7 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
                 rope.kc = gr.kc + (long)grp.layer * gr.kv_stride;
                 rope.vc = gr.vc + (long)grp.layer * gr.kv_stride;
                 rope.n_ctx = gr.n_ctx;
+                rope.pos_mask = gr.pos_mask;
             }
             const int pos = EPI == GEMM_EPI_ROPE_ROWS ? grp.rows[tok].stt->n_tokens + grp.rows[tok].j : stt->n_tokens + tok;
             if (pos >= rope.n_ctx) continue;
@@ -4483,12 +4746,12 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
                         y[(long)tok * ldy + head * 64 + d] = o1;
                         y[(long)tok * ldy + head * 64 + d + 32] = o2;
                     } else {
-                        f16_t* kp = rope.kc + ((long)pos * rope.nkv + (head - rope.nh)) * 64;
+                        f16_t* kp = rope.kc + ((long)(pos & rope.pos_mask) * rope.nkv + (head - rope.nh)) * 64;
                         kp[d] = (f16_t)o1;
                         kp[d + 32] = (f16_t)o2;
                     }
                 } else {
-                    f16_t* vp = rope.vc + ((long)pos * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
+                    f16_t* vp = rope.vc + ((long)(pos & rope.pos_mask) * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
                     vp[d] = (f16_t)x1;
                     vp[d + 32] = (f16_t)x2;
                 }
@@ -4562,6 +4825,7 @@ __global__ __launch_bounds__(256) void lm_gemm128_epilogue_kernel(const LmDevSta
                 rope.kc = gr.kc + (long)rt.layer * gr.kv_stride;
                 rope.vc = gr.vc + (long)rt.layer * gr.kv_stride;
                 rope.n_ctx = gr.n_ctx;
+                rope.pos_mask = gr.pos_mask;
             }
             const int pos = EPI == GEMM_EPI_ROPE_ROWS ? rt.rows[tok].stt->n_tokens + rt.rows[tok].j : stt->n_tokens + tok;
             if (pos >= rope.n_ctx) continue;
@@ -4575,12 +4839,12 @@ __global__ __launch_bounds__(256) void lm_gemm128_epilogue_kernel(const LmDevSta
                     y[(long)tok * ldy + head * 64 + d] = o1;
                     y[(long)tok * ldy + head * 64 + d + 32] = o2;
                 } else {
-                    f16_t* kp = rope.kc + ((long)pos * rope.nkv + (head - rope.nh)) * 64;
+                    f16_t* kp = rope.kc + ((long)(pos & rope.pos_mask) * rope.nkv + (head - rope.nh)) * 64;
                     kp[d] = (f16_t)o1;
                     kp[d + 32] = (f16_t)o2;
                 }
             } else {
-                f16_t* vp = rope.vc + ((long)pos * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
+                f16_t* vp = rope.vc + ((long)(pos & rope.pos_mask) * rope.nkv + (head - rope.nh - rope.nkv)) * 64;
                 vp[d] = (f16_t)x1;
                 vp[d + 32] = (f16_t)x2;
             }
@@ -4618,12 +4882,13 @@ static int lm_enqueue_prefill_tile(rca_lm* h, int M, hipStream_t st, int nsp_lau
     lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, x, H, c.vocab_size);
     for (int l = 0; l < c.n_layers; ++l) {
         const LmLayer& L = h->layers[l];
-        f16_t* kc = h->kc + (long)l * h->kv_layer_stride;
-        f16_t* vc = h->vc + (long)l * h->kv_layer_stride;
-        rope.kc = kc; rope.vc = vc;
+        f16_t* kc = lm_kv_layer(h, h->kc, l);
+        f16_t* vc = lm_kv_layer(h, h->vc, l);
+        lm_rope_target(h, l, rope);
         lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.attn_norm, h->xn, H, c.rms_eps);
         lm_split_bf16_kernel<<<dim3(cdiv(H, 256), M), 256, 0, st>>>(h->stt, h->xn, h->xh, h->xl, H);
         lm_gemm_mfma_kernel<GEMM_EPI_ROPE><<<QKV / 32, 256, 0, st>>>(h->stt, L.qkv.w, h->xh, h->xl, QKV, H, h->qkv, QKV, nullptr, nullptr, rope);
+        lm_launch_kv_quant(h, l, M, st);
         launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, nullptr, nullptr, true);
         lm_split_bf16_kernel<<<dim3(cdiv(AO, 256), M), 256, 0, st>>>(h->stt, h->attn, h->xh, h->xl, AO);
         lm_gemm_mfma_kernel<GEMM_EPI_RESID><<<H / 32, 256, 0, st>>>(h->stt, L.o.w, h->xh, h->xl, H, AO, x, H, nullptr, nullptr, norope);
@@ -4708,9 +4973,9 @@ static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_
     lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, x, H, c.vocab_size);
     for (int l = 0; l < c.n_layers; ++l) {
         const LmLayer& L = h->layers[l];
-        f16_t* kc = h->kc + (long)l * h->kv_layer_stride;
-        f16_t* vc = h->vc + (long)l * h->kv_layer_stride;
-        rope.kc = kc; rope.vc = vc;
+        f16_t* kc = lm_kv_layer(h, h->kc, l);
+        f16_t* vc = lm_kv_layer(h, h->vc, l);
+        lm_rope_target(h, l, rope);
         lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.attn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
         for (int seg = 0; seg < (L.split_v ? 2 : 1); ++seg) {   // [q; k; v] as one matrix, or [q; k] and v when their formats differ
             const WMat& w = seg ? L.vseg : L.qkv;
@@ -4721,6 +4986,7 @@ static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_
             if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE><<<dim3(Ns / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fq.ep_nsplit, fq.ep_grp, Ns, h->qkv, QKV, nullptr, nullptr, rope, nogroup);
         }
         rope.row_base = 0;
+        lm_launch_kv_quant(h, l, M, st);
         launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, h->xh, h->xl, true);
         launch_gemm128<GEMM_EPI_RESID>(h, L.o, dim3(H / 128, fo.grid_y, tbz), st, h->xh, h->xl, H, AO, AO / so, x, H, nullptr, nullptr, norope, fo.nseq);
         if (fo.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fo.ep_nsplit, fo.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
@@ -4916,15 +5182,21 @@ static int lm_same_cache_shape(const rca_lm* a, const rca_lm* b) {
 extern "C" int rca_lm_copy_kv(rca_lm_t* dst, rca_lm_t* src, int32_t n_pos) {
     if (!dst || !src || dst == src) return fail(RCA_ERR_ARG, "copy_kv: two different handles needed");
     if (!lm_same_cache_shape(dst, src)) return fail(RCA_ERR_ARG, "copy_kv: the two KV caches differ in shape");
+    if (dst->kv_format != src->kv_format) return fail(RCA_ERR_ARG, "copy_kv: the two KV caches differ in format (%d and %d, rca_lm_set_kv_format)", dst->kv_format, src->kv_format);
     if (n_pos < 0 || n_pos > src->cfg.n_ctx) return fail(RCA_ERR_ARG, "copy_kv: %d positions outside [0, %d]", n_pos, src->cfg.n_ctx);
     RCA_HIP(hipSetDevice(dst->device));
     RCA_HIP(hipStreamSynchronize(src->stream));   // everything src has evaluated so far is in its cache
     src->async_pending = false;
     if (dst->async_pending) { RCA_HIP(hipStreamSynchronize(dst->stream)); dst->async_pending = false; }
-    const size_t bytes = (size_t)n_pos * src->cfg.n_kv_heads * src->cfg.head_dim * sizeof(f16_t);
+    const size_t rows = (size_t)n_pos * src->cfg.n_kv_heads;   // head rows per layer: 128 bytes of fp16, or 64 int8 + two fp16 scales
+    const size_t bytes = rows * (lm_kv_q8(src) ? 64 : 64 * sizeof(f16_t));
     for (int l = 0; l < src->cfg.n_layers && bytes; ++l) {
-        RCA_HIP(hipMemcpyAsync(dst->kc + (long)l * dst->kv_layer_stride, src->kc + (long)l * src->kv_layer_stride, bytes, hipMemcpyDeviceToDevice, dst->stream));
-        RCA_HIP(hipMemcpyAsync(dst->vc + (long)l * dst->kv_layer_stride, src->vc + (long)l * src->kv_layer_stride, bytes, hipMemcpyDeviceToDevice, dst->stream));
+        RCA_HIP(hipMemcpyAsync(lm_kv_layer(dst, dst->kc, l), lm_kv_layer(src, src->kc, l), bytes, hipMemcpyDeviceToDevice, dst->stream));
+        RCA_HIP(hipMemcpyAsync(lm_kv_layer(dst, dst->vc, l), lm_kv_layer(src, src->vc, l), bytes, hipMemcpyDeviceToDevice, dst->stream));
+        if (lm_kv_q8(src)) {   // the scale planes, same position range
+            RCA_HIP(hipMemcpyAsync(const_cast<f16_t*>(lm_kv_scales(dst, dst->kc, l)), lm_kv_scales(src, src->kc, l), rows * 2 * sizeof(f16_t), hipMemcpyDeviceToDevice, dst->stream));
+            RCA_HIP(hipMemcpyAsync(const_cast<f16_t*>(lm_kv_scales(dst, dst->vc, l)), lm_kv_scales(src, src->vc, l), rows * 2 * sizeof(f16_t), hipMemcpyDeviceToDevice, dst->stream));
+        }
     }
     dst->async_pending = true;
     return RCA_OK;
@@ -4932,6 +5204,7 @@ extern "C" int rca_lm_copy_kv(rca_lm_t* dst, rca_lm_t* src, int32_t n_pos) {
 extern "C" int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b) {
     if (!a || !b || a == b) return fail(RCA_ERR_ARG, "swap_kv: two different handles needed");
     if (!lm_same_cache_shape(a, b)) return fail(RCA_ERR_ARG, "swap_kv: the two KV caches differ in shape");
+    if (a->kv_format != b->kv_format) return fail(RCA_ERR_ARG, "swap_kv: the two KV caches differ in format (%d and %d, rca_lm_set_kv_format)", a->kv_format, b->kv_format);
     RCA_HIP(hipSetDevice(a->device));
     RCA_HIP(hipStreamSynchronize(a->stream));
     RCA_HIP(hipStreamSynchronize(b->stream));
@@ -4999,6 +5272,9 @@ __global__ __launch_bounds__(256) void lm_kv_shift_kernel(f16_t* kc, f16_t* vc, 
 }
 extern "C" int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1) {
     if (!h) return fail(RCA_ERR_ARG, "null");
+    if (lm_kv_q8(h))
+        return fail(RCA_ERR_STATE, "kv_remove: this handle keeps a q8_0 KV cache (rca_lm_set_kv_format); re-rotating quantised keys would quantise them a second time, "
+                                   "which this version does not do -- use an fp16 cache for the context shift");
     { const int rc = lm_settle(h); if (rc != RCA_OK) return rc; }
     const int n = h->n_tokens;
     if (p0 < 0 || p0 > p1 || p1 > n) return fail(RCA_ERR_ARG, "kv_remove: [%d, %d) is not a span of the %d cached positions", p0, p1, n);
@@ -5029,7 +5305,22 @@ extern "C" int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1) {
     h->n_tokens = n - delta;
     return RCA_OK;
 }
-// tests only: raw fp16 rows [n_pos][n_kv_heads][64] of one layer's K and / or V cache
+// q8_0 cache: rows [pos0, pos0 + n_pos) of layer `layer` of one tensor (base = kc or vc), de-quantised into dst_host through a scratch buffer
+static int lm_kv_read_deq(rca_lm* h, const f16_t* base, int layer, int pos0, int n_pos, uint16_t* dst_host) {
+    const long n = (long)n_pos * h->cfg.n_kv_heads * 64, off = (long)pos0 * h->cfg.n_kv_heads * 64;
+    f16_t* tmp = nullptr;
+    int rc = lm_alloc((void**)&tmp, (size_t)n * sizeof(f16_t));
+    if (rc != RCA_OK) return rc;
+    lm_kv_dequant_kernel<<<cdiv(n / 16, 256), 256, 0, h->stream>>>(reinterpret_cast<const signed char*>(lm_kv_layer(h, base, layer)) + off,
+                                                                   lm_kv_scales(h, base, layer) + (off >> 5), tmp, n / 16);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(dst_host, tmp, (size_t)n * sizeof(f16_t), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(tmp);
+    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "kv_read (q8_0): %s", hipGetErrorString(e));
+}
+// tests only: fp16 rows [n_pos][n_kv_heads][64] of one layer's K and / or V cache -- the raw rows of an fp16 cache, the de-quantised
+// rows of a q8_0 cache (exactly the values attention stages)
 extern "C" int rca_lm_kv_read(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, uint16_t* k_host, uint16_t* v_host) {
     if (!h) return fail(RCA_ERR_ARG, "null");
     const rca_lm_config_t& c = h->cfg;
@@ -5040,11 +5331,36 @@ extern "C" int rca_lm_kv_read(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t 
     h->async_pending = false;
     const long off = (long)layer * h->kv_layer_stride + (long)pos0 * c.n_kv_heads * 64;
     const size_t bytes = (size_t)n_pos * c.n_kv_heads * 64 * sizeof(f16_t);
+    if (lm_kv_q8(h)) {
+        int rc = RCA_OK;
+        if (k_host && bytes) rc = lm_kv_read_deq(h, h->kc, layer, pos0, n_pos, k_host);
+        if (rc == RCA_OK && v_host && bytes) rc = lm_kv_read_deq(h, h->vc, layer, pos0, n_pos, v_host);
+        return rc;
+    }
     if (k_host && bytes) RCA_HIP(hipMemcpy(k_host, h->kc + off, bytes, hipMemcpyDeviceToHost));
     if (v_host && bytes) RCA_HIP(hipMemcpy(v_host, h->vc + off, bytes, hipMemcpyDeviceToHost));
     return RCA_OK;
 }
-// tests only: the inverse of rca_lm_kv_read (n_tokens stays as it is)
+// tests only: the raw blocks of a q8_0 cache: int8 values [n_pos][n_kv_heads][64] and fp16 scales [n_pos][n_kv_heads][2] of K and / or V
+extern "C" int rca_lm_kv_read_q8(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, int8_t* k_q, uint16_t* k_d, int8_t* v_q, uint16_t* v_d) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    const rca_lm_config_t& c = h->cfg;
+    if (!lm_kv_q8(h)) return fail(RCA_ERR_STATE, "kv_read_q8: this handle keeps an fp16 KV cache (rca_lm_set_kv_format)");
+    if (layer < 0 || layer >= c.n_layers) return fail(RCA_ERR_ARG, "kv_read_q8: layer %d outside [0, %d)", layer, c.n_layers);
+    if (pos0 < 0 || n_pos < 0 || pos0 > c.n_ctx - n_pos) return fail(RCA_ERR_ARG, "kv_read_q8: positions [%d, %d + %d) outside the context of %d", pos0, pos0, n_pos, c.n_ctx);
+    RCA_HIP(hipSetDevice(h->device));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    h->async_pending = false;
+    const long off = (long)pos0 * c.n_kv_heads * 64;
+    const size_t n = (size_t)n_pos * c.n_kv_heads * 64;
+    if (!n) return RCA_OK;
+    if (k_q) RCA_HIP(hipMemcpy(k_q, (const char*)lm_kv_layer(h, h->kc, layer) + off, n, hipMemcpyDeviceToHost));
+    if (v_q) RCA_HIP(hipMemcpy(v_q, (const char*)lm_kv_layer(h, h->vc, layer) + off, n, hipMemcpyDeviceToHost));
+    if (k_d) RCA_HIP(hipMemcpy(k_d, lm_kv_scales(h, h->kc, layer) + (off >> 5), n / 32 * sizeof(f16_t), hipMemcpyDeviceToHost));
+    if (v_d) RCA_HIP(hipMemcpy(v_d, lm_kv_scales(h, h->vc, layer) + (off >> 5), n / 32 * sizeof(f16_t), hipMemcpyDeviceToHost));
+    return RCA_OK;
+}
+// tests only: the inverse of rca_lm_kv_read (n_tokens stays as it is); a q8_0 cache quantises the rows with the kernel its passes use
 extern "C" int rca_lm_kv_write(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, const uint16_t* k_host, const uint16_t* v_host) {
     if (!h) return fail(RCA_ERR_ARG, "null");
     const rca_lm_config_t& c = h->cfg;
@@ -5055,6 +5371,23 @@ extern "C" int rca_lm_kv_write(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t
     h->async_pending = false;
     const long off = (long)layer * h->kv_layer_stride + (long)pos0 * c.n_kv_heads * 64;
     const size_t bytes = (size_t)n_pos * c.n_kv_heads * 64 * sizeof(f16_t);
+    if (lm_kv_q8(h)) {   // through the ring, at most LM_KV_RING positions at a time, at the slots a pass would use
+        const size_t prow = (size_t)c.n_kv_heads * 64;   // elements per position
+        for (int p = 0; p < n_pos && bytes;) {
+            const int slot = (pos0 + p) & (LM_KV_RING - 1);
+            const int cnt = std::min(n_pos - p, LM_KV_RING - slot);   // up to the ring's end
+            if (k_host) RCA_HIP(hipMemcpy(h->ring_k + slot * prow, k_host + p * prow, cnt * prow * sizeof(f16_t), hipMemcpyHostToDevice));
+            if (v_host) RCA_HIP(hipMemcpy(h->ring_v + slot * prow, v_host + p * prow, cnt * prow * sizeof(f16_t), hipMemcpyHostToDevice));
+            lm_kv_quant_kernel<false><<<dim3(cdiv(4 * c.n_kv_heads, 8), cnt), 256, 0, h->stream>>>(
+                nullptr, h->ring_k, h->ring_v, LM_KV_RING - 1, reinterpret_cast<signed char*>(lm_kv_layer(h, h->kc, layer)), reinterpret_cast<signed char*>(lm_kv_layer(h, h->vc, layer)),
+                const_cast<f16_t*>(lm_kv_scales(h, h->kc, layer)), const_cast<f16_t*>(lm_kv_scales(h, h->vc, layer)), c.n_kv_heads, c.n_ctx, pos0 + p, cnt,
+                (k_host ? 1 : 0) | (v_host ? 2 : 0), nullptr, 0);
+            RCA_LAUNCH_CHECK();
+            RCA_HIP(hipStreamSynchronize(h->stream));
+            p += cnt;
+        }
+        return RCA_OK;
+    }
     if (k_host && bytes) RCA_HIP(hipMemcpy(h->kc + off, k_host, bytes, hipMemcpyHostToDevice));
     if (v_host && bytes) RCA_HIP(hipMemcpy(h->vc + off, v_host, bytes, hipMemcpyHostToDevice));
     return RCA_OK;
@@ -5323,6 +5656,8 @@ extern "C" int rca_lm_group_create(rca_lm_t* const* members, int32_t n_members, 
             return fail(RCA_ERR_ARG, "group_create: member %d does not share member 0's weights (rca_lm_create_shared makes handles that do)", s);
         if (h->act_format != members[0]->act_format)
             return fail(RCA_ERR_ARG, "group_create: member %d has activation format %d, member 0 has %d", s, h->act_format, members[0]->act_format);
+        if (h->kv_format != members[0]->kv_format)
+            return fail(RCA_ERR_ARG, "group_create: member %d has KV format %d, member 0 has %d", s, h->kv_format, members[0]->kv_format);
         if (h->cfg.logits_all) return fail(RCA_ERR_ARG, "group_create: member %d is a logits_all handle (a group step keeps the last position's logits only)", s);
     }
     RCA_HIP(hipSetDevice(members[0]->device));
@@ -5358,7 +5693,7 @@ static int lm_group_refresh(rca_lm_group* g) {
     for (int n = 1; n <= LM_GEMV_M; ++n)
         for (int s = 0; s < g->n_members; ++s) {
             rca_lm* h = g->m[s];
-            LmGroupRow r{h->stt, h->kc, h->vc, h->logits, h->kv_layer_stride, 0, 0, h->cfg.n_ctx, 0};
+            LmGroupRow r = lm_group_row(h, 0, 0);
             r.j = n - 1; r.xrow = s * n + n - 1;
             tab[n - 1][LM_GROUP_MAX + s] = r;
             for (int j = 0; j < n && s * n + j < LM_GROUP_MAX; ++j) {
@@ -5395,7 +5730,8 @@ static int lm_group_enqueue(rca_lm_group* g, int n, int nsp_launch, hipStream_t 
         }
         for (int s = 0; s < NM; ++s) {
             rca_lm* h = g->m[s];
-            launch_attention_mfma(h, n, std::min(nsp_launch, h->n_splits), h->kc + (long)l * h->kv_layer_stride, h->vc + (long)l * h->kv_layer_stride,
+            lm_launch_kv_quant(h, l, n, st);   // (q8_0 caches: the member's rows of the pass, as its own launches do)
+            launch_attention_mfma(h, n, std::min(nsp_launch, h->n_splits), lm_kv_layer(h, h->kc, l), lm_kv_layer(h, h->vc, l),
                                   ws->qkv + (long)s * n * QKV, ws->attn + (long)s * n * AO, st);
         }
         lm_launch_o(ws, l, MT, st);
@@ -5424,6 +5760,7 @@ extern "C" int rca_lm_group_step(rca_lm_group_t* g, const int32_t* ids, int32_t 
         const rca_lm* h = g->m[s];
         if (!h->sampler_set) return fail(RCA_ERR_STATE, "group_step: member %d has no sampler (rca_lm_sampler_init)", s);
         if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "group_step: member %d was switched to logits_all after the group was made", s);
+        if (h->kv_format != g->m[0]->kv_format) return fail(RCA_ERR_STATE, "group_step: member %d has KV format %d, member 0 has %d", s, h->kv_format, g->m[0]->kv_format);
         if (h->act_format != g->m[0]->act_format) return fail(RCA_ERR_STATE, "group_step: member %d has activation format %d, member 0 has %d", s, h->act_format, g->m[0]->act_format);
         if (h->n_tokens + n > h->cfg.n_ctx) return fail(RCA_ERR_STATE, "group_step: context overflow of member %d: %d + %d > n_ctx %d", s, h->n_tokens, n, h->cfg.n_ctx);
         for (int j = 0; j < n; ++j)
@@ -5642,6 +5979,8 @@ extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, 
         if (h->device != members[0]->device) return fail(RCA_ERR_ARG, "batch_create: member %d is on device %d, member 0 on device %d", s, h->device, members[0]->device);
         if (lm_weight_owner(h) != lm_weight_owner(members[0]))
             return fail(RCA_ERR_ARG, "batch_create: member %d does not share member 0's weights (rca_lm_create_shared makes handles that do)", s);
+        if (h->kv_format != members[0]->kv_format)
+            return fail(RCA_ERR_ARG, "batch_create: member %d has KV format %d, member 0 has %d", s, h->kv_format, members[0]->kv_format);
         if (h->cfg.logits_all) return fail(RCA_ERR_ARG, "batch_create: member %d is a logits_all handle (a batch step keeps the last position's logits only)", s);
         if (lm_prefill_route(h) != LM_ROUTE_TILE128)
             return fail(RCA_ERR_ARG, "batch_create: member %d does not take the 128-token tiles (rca_lm_prefill_route %d, a batch step needs 2); such models stay with rca_lm_group_step",
@@ -5692,6 +6031,9 @@ static int lm_batch_refresh(rca_lm_batch* b) {
     for (int s = 0; s < b->n_members; ++s) same = same && b->epoch[s] == b->m[s]->graph_epoch;
     if (same) return RCA_OK;
     lm_batch_drop_graphs(b);
+    for (int s = 1; s < b->n_members; ++s)
+        if (b->m[s]->kv_format != b->m[0]->kv_format)
+            return fail(RCA_ERR_STATE, "batch: member %d has KV format %d, member 0 has %d", s, b->m[s]->kv_format, b->m[0]->kv_format);
     std::vector<LmGroupRow> rows((size_t)LM_GEMV_M * LM_BATCH_ROWS);
     std::vector<LmBatchMember> tab((size_t)LM_GEMV_M * LM_BATCH_MAX);
     memset(rows.data(), 0, rows.size() * sizeof(LmGroupRow));
@@ -5702,12 +6044,11 @@ static int lm_batch_refresh(rca_lm_batch* b) {
             rca_lm* h = b->m[s];
             if (s * n + n > LM_BATCH_ROWS) break;   // (more rows than a token block: refused by the step before anything reads the table)
             const bool serial = h->sampler_set && !h->samp_full;
-            tab[(size_t)(n - 1) * LM_BATCH_MAX + s] = LmBatchMember{h->stt, h->kc, h->vc, h->kv_layer_stride, h->att_part, h->logits, h->samp, h->swork,
-                                                                     s * n, h->n_splits, h->cfg.n_ctx, serial ? 1 : 0};
+            tab[(size_t)(n - 1) * LM_BATCH_MAX + s] = lm_batch_member(h, s * n, serial);
             b->any_serial = b->any_serial || serial;
             b->any_patch = b->any_patch || (serial && h->samp_patch);
             for (int j = 0; j < n; ++j) {
-                LmGroupRow r{h->stt, h->kc, h->vc, h->logits, h->kv_layer_stride, j, s * n + j, h->cfg.n_ctx, 0};
+                LmGroupRow r = lm_group_row(h, j, s * n + j);
                 rows[(size_t)(n - 1) * LM_BATCH_ROWS + s * n + j] = r;
             }
         }
@@ -5733,6 +6074,9 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
         (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
         (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
         (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
         attr_done = true;
     }
     // the k-split forms of one token block: what an rca_lm_eval_async pass of up to 128 tokens uses, so a row's sums are that pass's
@@ -5756,8 +6100,13 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
             launch_gemm128<GEMM_EPI_ROPE_ROWS>(ws, w, dim3(Ns / 128, fq.grid_y, 1), st, ws->xh, ws->xl, Ns, H, H / ss, ws->qkv, QKV, nullptr, nullptr, rope, fq.nseq, bs, grp);
             if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE_ROWS><<<dim3(Ns / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fq.ep_nsplit, fq.ep_grp, Ns, ws->qkv, QKV, nullptr, nullptr, rope, grp);
         }
+        const bool q8kv = lm_kv_q8(ws);   // every member's format (rca_lm_batch_create, lm_batch_member_ok)
+        if (q8kv)   // every member's new rows, ring -> int8 planes, in one launch
+            lm_kv_quant_kernel<true><<<dim3(cdiv(4 * c.n_kv_heads, 8), n, NM), 256, 0, st>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, c.n_kv_heads, 0, 0, 0, 3, tab, l);
 #define RCA_BATCH_ATTN(GG)                                                                                                            \
-        lm_attn_mfma_kernel<GG, true><<<agm, 512, ATTM_LDS, st>>>(nullptr, ws->qkv, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, scale, 0, nullptr, \
+        if (q8kv) lm_attn_mfma_kernel<GG, true, 1><<<agm, 512, ATTM_LDS, st>>>(nullptr, ws->qkv, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, scale, 0, nullptr, \
+                                                                               nullptr, nullptr, tab, l);                                         \
+        else lm_attn_mfma_kernel<GG, true><<<agm, 512, ATTM_LDS, st>>>(nullptr, ws->qkv, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, scale, 0, nullptr, \
                                                                   nullptr, nullptr, tab, l);                                                      \
         lm_attn_mfma_batch_combine_kernel<GG><<<dim3(n * c.n_heads, NM), 64, 0, st>>>(tab, c.n_heads, c.n_kv_heads, nsp_launch, ws->xh, ws->xl);
         if (G == 4) { RCA_BATCH_ATTN(4) }
@@ -6117,6 +6466,7 @@ static int lm_batch_sel_check(rca_lm_batch* b, const char* who, const int32_t* s
         const int s = sel[k], V = h->cfg.vocab_size;
         if (!h->sampler_set) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has no sampler (rca_lm_sampler_init)", who, k, s);
         if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d was switched to logits_all after the batch was made", who, k, s);
+        if (h->kv_format != b->m[0]->kv_format) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has KV format %d, member 0 has %d", who, k, s, h->kv_format, b->m[0]->kv_format);
         if (lm_prefill_route(h) != LM_ROUTE_TILE128)
             return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", who, k, s, lm_prefill_route(h));
         if (h->n_tokens + 2 * n_steps > h->cfg.n_ctx)
@@ -6161,9 +6511,9 @@ static LmBatchSelPlan lm_batch_sel_stage(rca_lm_batch* b, rca_lm* const* hm, int
         p.graphs = p.graphs && h->graphs_enabled && serial;   // a whole-vocabulary sampler has launches of its own with its own pointers: eager
         any_serial = any_serial || serial;
         p.any_patch = p.any_patch || (serial && h->samp_patch);
-        in.tab[k] = LmBatchMember{h->stt, h->kc, h->vc, h->kv_layer_stride, h->att_part, h->logits, h->samp, h->swork, k * 2, h->n_splits, h->cfg.n_ctx, serial ? 1 : 0};
+        in.tab[k] = lm_batch_member(h, k * 2, serial);
         for (int j = 0; j < 2; ++j) {
-            in.rows[k * 2 + j] = LmGroupRow{h->stt, h->kc, h->vc, h->logits, h->kv_layer_stride, j, k * 2 + j, h->cfg.n_ctx, 0};
+            in.rows[k * 2 + j] = lm_group_row(h, j, k * 2 + j);
             in.in.ids[k * 2 + j] = first_pairs[k * 2 + j];
         }
         in.in.n_tokens[k] = h->n_tokens;
@@ -6953,6 +7303,38 @@ extern "C" int rca_lm_get_act_format(const rca_lm_t* h, int32_t* fmt) {
     *fmt = h->act_format;
     return RCA_OK;
 }
+// Format of the KV cache: 0 = fp16 (default), 1 = q8_0 blocks (the comment above lm_kv_quant_kernel).  Only an empty handle (n_tokens == 0)
+// can change it: the cache is re-allocated (zeroed) in the new format and every captured graph goes.
+extern "C" int rca_lm_set_kv_format(rca_lm_t* h, int32_t fmt) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    if (fmt != 0 && fmt != 1) return fail(RCA_ERR_ARG, "set_kv_format: %d is neither 0 (f16) nor 1 (q8_0)", fmt);
+    if (h->cfg.head_dim != 64) return fail(RCA_ERR_ARG, "set_kv_format: head_dim %d (the cache kernels take 64)", h->cfg.head_dim);
+    if (h->n_tokens != 0) return fail(RCA_ERR_STATE, "set_kv_format: the cache holds %d positions; the format changes on an empty handle only (rca_lm_reset)", h->n_tokens);
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    if (h->kv_format == fmt) return RCA_OK;
+    RCA_HIP(hipSetDevice(h->device));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    lm_drop_graphs(h);   // the captured passes hold the old cache and the other kernel instances
+    const int old = h->kv_format;
+    h->kv_format = fmt;
+    const int rc = lm_kv_alloc(h);
+    if (rc != RCA_OK) { h->kv_format = old; (void)lm_kv_alloc(h); return rc; }
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    return RCA_OK;
+}
+extern "C" int rca_lm_get_kv_format(const rca_lm_t* h, int32_t* fmt) {
+    if (!h || !fmt) return fail(RCA_ERR_ARG, "null");
+    *fmt = h->kv_format;
+    return RCA_OK;
+}
+// bytes one cached position takes in the handle's format (all layers, K and V); ring_positions (may be null): positions of the fp16
+// staging ring of a q8_0 cache, 0 for an fp16 cache
+extern "C" int rca_lm_kv_bytes_per_position(const rca_lm_t* h, int64_t* bytes, int32_t* ring_positions) {
+    if (!h || !bytes) return fail(RCA_ERR_ARG, "null");
+    *bytes = lm_kv_bytes_per_pos(h);
+    if (ring_positions) *ring_positions = lm_kv_q8(h) ? LM_KV_RING : 0;
+    return RCA_OK;
+}
 // tests only: one decode GEMV stage, launched by the very call lm_enqueue_pass makes for it, on a host-supplied input
 extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const float* x_host, int32_t M, float* y_host, int64_t y_numel,
                                uint16_t* kv_host) {
@@ -6998,7 +7380,12 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy2DAsync(y_host, (size_t)out_w[kind] * 4, yd, (size_t)ldy * 4, (size_t)out_w[kind] * 4, M, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && kind == 0 && kv_host) {
+    if (e == hipSuccess && kind == 0 && kv_host && lm_kv_q8(h)) {   // the de-quantised rows, as rca_lm_kv_read gives them
+        const size_t n = (size_t)M * c.n_kv_heads * 64;
+        rc = lm_kv_read_deq(h, h->kc, layer, h->n_tokens, M, kv_host);
+        if (rc == RCA_OK) rc = lm_kv_read_deq(h, h->vc, layer, h->n_tokens, M, kv_host + n);
+        if (rc != RCA_OK) { if (head_out) (void)hipFree(head_out); return rc; }
+    } else if (e == hipSuccess && kind == 0 && kv_host) {
         const size_t n = (size_t)M * c.n_kv_heads * 64;
         const long off = (long)layer * h->kv_layer_stride + (long)h->n_tokens * c.n_kv_heads * 64;
         e = hipMemcpyAsync(kv_host, h->kc + off, n * 2, hipMemcpyDeviceToHost, st);
@@ -7044,8 +7431,8 @@ extern "C" int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_
     } else {
         RCA_HIP(hipMemsetAsync(h->attn, 0xFF, n_out * 4, st));
     }
-    const f16_t* kc = h->kc + (long)layer * h->kv_layer_stride;
-    const f16_t* vc = h->vc + (long)layer * h->kv_layer_stride;
+    const f16_t* kc = lm_kv_layer(h, h->kc, layer);
+    const f16_t* vc = lm_kv_layer(h, h->vc, layer);
     if (route == 0) launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st);
     else if (route == 1) launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, nullptr, nullptr, true);
     else launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, h->xh, h->xl, true);

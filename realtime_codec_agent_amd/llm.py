@@ -101,6 +101,7 @@ def bf16_bits_to_f32(b: np.ndarray) -> np.ndarray:
 
 
 ACTIVATION_FORMATS = ("f32", "q8_1")          # rca_lm_set_act_format's 0 / 1
+KV_FORMATS = ("f16", "q8_0")                  # rca_lm_set_kv_format's 0 / 1
 CODEC_PREFIX = "model.embed_codec_tokens."   # CodecLlamaCodecEmbedding's tensors (codec_llama.py:46-69)
 
 
@@ -194,6 +195,7 @@ class LlamaForAlternatingCodeChannels:
         share_weights_with: Optional["LlamaForAlternatingCodeChannels"] = None,
         weight_format: Optional[str] = None,
         activation_format: Optional[str] = None,
+        kv_format: Optional[str] = None,
         **_ignored,
     ):
         """weight_format: the format every projection matrix and lm_head is KEPT in (one copy: the decode step streams it, the prefill
@@ -206,7 +208,11 @@ class LlamaForAlternatingCodeChannels:
         importance-matrix search of llama-quantize is not part of it).
         activation_format: what the decode GEMVs over quantised (q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1) matrices multiply the weights with.  None / "f32"
         (default) = f32 activations; "q8_1" = activations quantised to 32-value int8 blocks inside the GEMV and integer dot products,
-        the arithmetic class of llama.cpp's GPU mat-vec (set_activation_format).  A twin inherits its parent's."""
+        the arithmetic class of llama.cpp's GPU mat-vec (set_activation_format).  A twin inherits its parent's.
+        kv_format: what the KV cache holds.  None / "f16" (default) = fp16 rows; "q8_0" = ggml q8_0 blocks, 68 bytes per head row instead
+        of 128 (llama-cpp-python's type_k = type_v = GGML_TYPE_Q8_0 next to flash_attn=True; set_kv_format).  A twin inherits its parent's."""
+        if kv_format not in (None,) + KV_FORMATS:
+            raise ValueError(f"kv_format {kv_format!r}: None / 'f16' or 'q8_0'")
         if activation_format not in (None,) + ACTIVATION_FORMATS:
             raise ValueError(f"activation_format {activation_format!r}: None / 'f32' or 'q8_1'")
         if weight_format not in (None, "bf16", "q8_0", "f16", "q4_k", "q5_k", "q4_0", "q4_1"):
@@ -236,6 +242,8 @@ class LlamaForAlternatingCodeChannels:
             self.weight_format = parent.weight_format
             self.activation_format = self._query_activation_format()   # rca_lm_create_shared copied the parent's
             self._init_activation_format(activation_format)
+            self.kv_format = self._query_kv_format()                   # and the parent's KV format
+            self._init_kv_format(kv_format)
             return
         random_init = weights is None and (model_path is None or str(model_path).startswith("random:"))
         if weights is None and not random_init:
@@ -269,6 +277,53 @@ class LlamaForAlternatingCodeChannels:
         self.weight_format = self._query_format()[0]
         self.activation_format = "f32"
         self._init_activation_format(activation_format)
+        self.kv_format = "f16"
+        self._init_kv_format(kv_format)
+
+    def _init_kv_format(self, kv_format: Optional[str]) -> None:
+        if kv_format is None:
+            return
+        try:
+            self.set_kv_format(kv_format)
+        except Exception:
+            self.close()
+            raise
+
+    def _query_kv_format(self) -> str:
+        fmt = C.c_int32()
+        N.check(self._lib.rca_lm_get_kv_format(self._h, C.byref(fmt)), "rca_lm_get_kv_format")
+        return KV_FORMATS[fmt.value]
+
+    def set_kv_format(self, kv_format: str) -> None:
+        """"f16" or "q8_0" (see the constructor).  Only an empty handle (n_tokens == 0) can change: the cache is re-allocated and captured
+        graphs are dropped.  kv_remove (the context-shift trim) is refused on a "q8_0" handle."""
+        if kv_format not in KV_FORMATS:
+            raise ValueError(f"kv_format {kv_format!r}: 'f16' or 'q8_0'")
+        N.check(self._lib.rca_lm_set_kv_format(self._h, KV_FORMATS.index(kv_format)), "rca_lm_set_kv_format")
+        self.kv_format = kv_format
+
+    def kv_bytes_per_position(self) -> int:
+        """Bytes one cached position takes (all layers, K and V) in the handle's KV format."""
+        b = C.c_int64()
+        N.check(self._lib.rca_lm_kv_bytes_per_position(self._h, C.byref(b), None), "rca_lm_kv_bytes_per_position")
+        return int(b.value)
+
+    def kv_ring_positions(self) -> int:
+        """Positions of the fp16 staging ring of a "q8_0" cache (0 for "f16"): tests pick passes that wrap it."""
+        b, r = C.c_int64(), C.c_int32()
+        N.check(self._lib.rca_lm_kv_bytes_per_position(self._h, C.byref(b), C.byref(r)), "rca_lm_kv_bytes_per_position")
+        return int(r.value)
+
+    def kv_read_q8(self, layer: int, pos0: int, n_pos: int):
+        """Tests only (rca_lm_kv_read_q8): the raw blocks of a "q8_0" cache: (k_q, k_d, v_q, v_d), int8 [n_pos, n_kv_heads, 64] and
+        float16 scales [n_pos, n_kv_heads, 2]."""
+        nkv = self.config.n_kv_heads
+        kq, vq = (np.empty((n_pos, nkv, 64), np.int8) for _ in range(2))
+        kd, vd = (np.empty((n_pos, nkv, 2), np.float16) for _ in range(2))
+        N.check(self._lib.rca_lm_kv_read_q8(self._h, int(layer), int(pos0), int(n_pos), kq.ctypes.data_as(C.POINTER(C.c_int8)),
+                                            kd.ctypes.data_as(C.POINTER(C.c_uint16)), vq.ctypes.data_as(C.POINTER(C.c_int8)),
+                                            vd.ctypes.data_as(C.POINTER(C.c_uint16))), "rca_lm_kv_read_q8")
+        return kq, kd, vq, vd
 
     def _init_activation_format(self, activation_format: Optional[str]) -> None:
         if activation_format is None:

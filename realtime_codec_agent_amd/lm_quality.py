@@ -3,7 +3,7 @@ llama-perplexity and its --kl-divergence mode report, computed with LlamaForAlte
 device; rca_lm_score).
 
     python -m realtime_codec_agent_amd.lm_quality --model M [--base B] --ids PATH [--window 2048] [--burn_in N] [--weight_format F]
-                                                  [--activation_format A] [--base_weight_format F] [--json]
+                                                  [--activation_format A] [--base_weight_format F] [--kv_format K] [--base_kv_format K] [--json]
 
 PATH is a .npy of int32 token ids or a directory of them (one stream per file).  Every stream is cut into consecutive windows of
 `window` tokens; each window is scored on a reset context and its first `burn_in` positions (default: half the window, as
@@ -138,6 +138,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--weight_format", default=None)
     ap.add_argument("--activation_format", default=None)
     ap.add_argument("--base_weight_format", default=None)
+    ap.add_argument("--kv_format", default=None, help="KV cache of the scored model: f16 (default) or q8_0")
+    ap.add_argument("--base_kv_format", default=None, help="KV cache of the reference model; given alone it makes --model its own reference")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--json", action="store_true", help="print the report as one JSON object")
     a = ap.parse_args(argv)
@@ -145,10 +147,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     streams = load_streams(a.ids)
     burn_in = a.window // 2 if a.burn_in is None else a.burn_in
     llm = LlamaForAlternatingCodeChannels(model_path=a.model, n_ctx=a.window, device=a.device, weight_format=a.weight_format,
-                                          activation_format=a.activation_format)
+                                          activation_format=a.activation_format, kv_format=a.kv_format)
     base = None
-    if a.base is not None or a.base_weight_format is not None:
-        base = LlamaForAlternatingCodeChannels(model_path=a.base or a.model, n_ctx=a.window, device=a.device, weight_format=a.base_weight_format)
+    if a.base is not None or a.base_weight_format is not None or a.base_kv_format is not None:
+        base = LlamaForAlternatingCodeChannels(model_path=a.base or a.model, n_ctx=a.window, device=a.device,
+                                               weight_format=a.base_weight_format if (a.base is not None or a.base_weight_format is not None) else a.weight_format,
+                                               kv_format=a.base_kv_format)
     try:
         rep = score_streams(llm, streams, a.window, burn_in, base)
     finally:
@@ -156,7 +160,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if base is not None:
             base.close()
     rep.update(model=a.model, base=(a.base or a.model) if base is not None else None, weight_format=llm.weight_format,
-               activation_format=llm.activation_format, base_weight_format=base.weight_format if base is not None else None)
+               activation_format=llm.activation_format, base_weight_format=base.weight_format if base is not None else None,
+               kv_format=llm.kv_format, base_kv_format=base.kv_format if base is not None else None)
     print(json.dumps(rep) if a.json else format_report(rep))
     return 0
 

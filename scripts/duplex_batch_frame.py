@@ -2,7 +2,7 @@
 frame (rca_lm_batch_frame_sel), N decode tails, N probes -- and (c) N rca_duplex_frame calls, for N in 4, 8, 16, 32, 64.  1B dims,
 random-init weights (head rows outside the codec range zeroed), the default codec, one parent handle and its weight-sharing twins in ONE
 batch of 64, every member at CONTEXT tokens, 4 steps per tick, the steady-state call shape (T 32000, F_ctx 96, 1440 samples), graphs on.
-usage: duplex_batch_frame.py CONTEXT TICKS      (RCA_LM_FORMAT=q8_0|q4_k|... as scripts/lm_profile.py)
+usage: duplex_batch_frame.py CONTEXT TICKS      (RCA_LM_FORMAT=q8_0|q4_k|... as scripts/lm_profile.py; RCA_LM_KV=q8_0: q8_0 KV caches)
 The three legs alternate inside one process (a, b, c, a, ... REPEATS times each); every timed leg is TICKS ticks behind WARMUP untimed
 ticks of the same leg, and every tick starts from the same context (n_tokens is put back).  Printed per N: the median over the repeats
 with the spread per leg, a / c and a / b.  Then: the session count from which (a) is faster than (c); the host time of stacking N PCM
@@ -20,6 +20,8 @@ ticks = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 REPEATS, WARMUP, N_STEPS, NB = 3, 2, 4, 64
 T, F_CTX, N_SAMPLES = 32000, 96, 1440
 SHAPES = (4, 8, 16, 32, 64)
+if os.environ.get("RCA_DUPLEX_SHAPES"):   # e.g. "64": a subset, for a short run
+    SHAPES = tuple(int(v) for v in os.environ["RCA_DUPLEX_SHAPES"].split(","))
 cfg = LMConfig.llama_3_2_1b()
 fmt = os.environ.get("RCA_LM_FORMAT")
 at = AudioTokenizer(codec_model="MagiCodec-50Hz-Base", device=None)
@@ -27,7 +29,10 @@ hip = at.codec_model.hip
 tok = CodecTokenizer(codebook_size=at.codebook_size, unicode_offset=at.unicode_offset)
 base, ncb = tok.codec_vocab_start, at.codebook_size
 n_ctx = (ctx + 64 + 255) // 256 * 256
-parent = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=n_ctx, device=0, weight_format=fmt)
+kvf = os.environ.get("RCA_LM_KV") or None    # "q8_0": quantised KV cache; the twins inherit it
+parent = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=n_ctx, device=0, weight_format=fmt, **({"kv_format": kvf} if kvf else {}))
+if kvf:
+    print(f"kv_format {parent.kv_format}: {parent.kv_bytes_per_position()} bytes per cached position")
 parent.mask_head_rows(0, base)
 parent.mask_head_rows(len(tok), parent.n_vocab())
 members = [parent] + [LlamaForAlternatingCodeChannels(n_ctx=n_ctx, share_weights_with=parent, device=0) for _ in range(NB - 1)]

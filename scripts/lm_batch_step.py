@@ -2,7 +2,7 @@
 (b) ceil(B / 4) rca_lm_group_step calls of 4 x 1 (n = 2: ceil(B / 2) calls of 2 x 2) and (c) B rca_lm_step calls, for B x n in
 8x1, 16x1, 32x1, 64x1, 8x2, 32x2, 64x2.  1B dims, random-init weights, one parent handle and its weight-sharing twins, every member
 at CONTEXT tokens (the parent's prefill, copied into the twins' caches), graph replay.
-usage: lm_batch_step.py CONTEXT STEPS        (RCA_LM_FORMAT=q8_0|q4_k|... as scripts/lm_profile.py)
+usage: lm_batch_step.py CONTEXT STEPS        (RCA_LM_FORMAT=q8_0|q4_k|... as scripts/lm_profile.py; RCA_LM_KV=q8_0: q8_0 KV caches)
 The three legs alternate inside one process (batch, group, single, batch, ... REPEATS times each), every timed leg is STEPS rounds
 behind WARMUP untimed rounds of the same leg, and every round starts from the same context (n_tokens is put back).  Printed per shape:
 the median over the repeats with the spread (min .. max) per leg, and the ratios of the medians."""
@@ -15,10 +15,16 @@ ctx = int(sys.argv[1]) if len(sys.argv) > 1 else 2200
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 REPEATS, WARMUP = 5, 5
 SHAPES = ((8, 1), (16, 1), (32, 1), (64, 1), (8, 2), (32, 2), (64, 2))
+if os.environ.get("RCA_BATCH_SHAPES"):   # e.g. "16x1,64x1,64x2": a subset, for a short run
+    SHAPES = tuple(tuple(int(v) for v in t.split("x")) for t in os.environ["RCA_BATCH_SHAPES"].split(","))
+BATCH_ONLY = os.environ.get("RCA_BATCH_ONLY") == "1"   # time the batch leg alone (the group / single legs do not depend on what is compared)
 cfg = LMConfig.llama_3_2_1b()
 fmt = os.environ.get("RCA_LM_FORMAT")
 n_ctx = (ctx + 64 + 255) // 256 * 256
-parent = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=n_ctx, device=0, weight_format=fmt)
+kvf = os.environ.get("RCA_LM_KV") or None    # "q8_0": quantised KV cache; the twins inherit it
+parent = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=n_ctx, device=0, weight_format=fmt, **({"kv_format": kvf} if kvf else {}))
+if kvf:
+    print(f"kv_format {parent.kv_format}: {parent.kv_bytes_per_position()} bytes per cached position")
 members = [parent] + [LlamaForAlternatingCodeChannels(n_ctx=n_ctx, share_weights_with=parent, device=0) for _ in range(63)]
 rng = np.random.default_rng(0)
 ids = rng.integers(128266, 259338, ctx + 80).tolist()
@@ -72,8 +78,8 @@ for nm, n in SHAPES:
     tb, tg, ts = [], [], []
     for _ in range(REPEATS):
         tb.append(timed(leg_batch, bat, ms, rows))
-        tg.append(timed(leg_group, grps, ms, rows))
-        ts.append(timed(leg_single, ms, rows))
+        tg.append(timed(leg_group, grps, ms, rows) if not BATCH_ONLY else float("nan"))
+        ts.append(timed(leg_single, ms, rows) if not BATCH_ONLY else float("nan"))
     bat.close()
     for g, _ in grps:
         g.close()

@@ -10,7 +10,11 @@ eager = len(sys.argv) > 3 and sys.argv[3] == "eager"
 cfg = LMConfig.llama_3_2_1b()
 fmt = os.environ.get("RCA_LM_FORMAT")   # "q8_0": decode from packed q8_0 weights
 act = os.environ.get("RCA_LM_ACT") or None   # "q8_1": q8_1 activations + integer dots in the decode GEMVs over packed weights
-llm = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=16384, device=0, weight_format=fmt, activation_format=act)
+kvf = os.environ.get("RCA_LM_KV") or None    # "q8_0": quantised KV cache (68 instead of 128 bytes per head row)
+llm = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=16384, device=0, weight_format=fmt, activation_format=act,
+                                      **({"kv_format": kvf} if kvf else {}))
+if kvf:
+    print(f"kv_format {llm.kv_format}: {llm.kv_bytes_per_position()} bytes per cached position")
 llm.init_sampler_for_generate(top_k=100, top_p=1.0, min_p=0.0, temp=1.0, seed=42)
 rng = np.random.default_rng(0)
 ids = rng.integers(128266, 259338, ctx + 2).tolist()
