@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "rca_common.h"
+#include "rca_conv_balance.h"
 
 namespace rca {
 thread_local char g_err[512] = {0};
@@ -333,11 +334,13 @@ __device__ __forceinline__ void conv_split8(const float (&w)[8], uint4& hi, uint
 // column Lout - 1 are zero.  A launch over a window of every row (run_conv's `view`) therefore passes x advanced to the window's
 // first sample, the full Lin and the window's column count; y is stored compact, [B][Cout][Lout].  Nothing in the chunk loop depends
 // on which of the two it is.
-template <int KS, int S, int CIC, int WM, int WN, int FUSE, int TR, int BF = 0, int FULLC = 0>
-__global__ __launch_bounds__(64 * RCA_CONV_WPB, (((KS == 8 && CIC == 2) || (KS == 16 && CIC == 1)) && WM * WN < 8) ? 3 : RCA_CONV_OCC) void conv1d_mfma_kernel(const float* __restrict__ x, const float* __restrict__ wp,
-                                                          const float* __restrict__ bias, float* __restrict__ y,
-                                                          int Cin, int Lin, int Cout, int Lout, long Ncols, int nchunks,
-                                                          int pre, float slope, FuseIn fin, TrInfo tr) {
+// The kernel body is a function of the workgroup index `wg` and of the first column `n_off` of its grid region, so that one launch can
+// hold two regions of different wave tiles (conv1d_mfma_mixed_kernel below); conv1d_mfma_kernel is the region (blockIdx.x, 0).
+template <int KS, int S, int CIC, int WM, int WN, int FUSE, int TR, int BF, int FULLC>
+__device__ __forceinline__ void conv1d_mfma_body(const float* __restrict__ x, const float* __restrict__ wp,
+                                                 const float* __restrict__ bias, float* __restrict__ y,
+                                                 int Cin, int Lin, int Cout, int Lout, long Ncols, int nchunks,
+                                                 int pre, float slope, FuseIn fin, TrInfo tr, const long wg, const long n_off) {
     constexpr int MT = WM * 32;            // channels per wave (and per workgroup)
     constexpr int NW = WN * 32;            // columns per wave
     constexpr int U = ConvLds<S>::stride(NW);
@@ -367,14 +370,13 @@ __global__ __launch_bounds__(64 * RCA_CONV_WPB, (((KS == 8 && CIC == 2) || (KS =
     // input span is fetched from HBM once and re-read from that XCD's L2 (speed only; any placement is correct).
     const int n_co_real = (Cout + MT - 1) / MT;
     const int n_co = TR ? n_co_real * tr.s : n_co_real;   // TR: (phase, channel tile) pairs
-    const long wg = blockIdx.x;
     const int xcd = (int)(wg & 7);
     const long seq = wg >> 3;
     const int co_tile_x = __builtin_amdgcn_readfirstlane((int)(seq % n_co));   // uniform, but the 64-bit division runs on the VALU: pin it to an SGPR
     const int phase = TR ? co_tile_x / n_co_real : 0;
     const int co_tile = TR ? co_tile_x % n_co_real : co_tile_x;
     const long col_tile = (seq / n_co) * 8 + xcd;
-    const long n0 = (col_tile * RCA_CONV_WPB + wave) * NW;   // first column of this wave
+    const long n0 = n_off + (col_tile * RCA_CONV_WPB + wave) * NW;   // first column of this wave
     const int co0 = co_tile * MT;
     if (n0 >= Ncols) return;  // whole wave out of range (no barriers: safe)
     // column -> (batch row, position): every column this wave touches is n_base + dn with 0 <= dn <= NW + 2, and the
@@ -885,9 +887,36 @@ __global__ __launch_bounds__(64 * RCA_CONV_WPB, (((KS == 8 && CIC == 2) || (KS =
         o[7] = tl_write | ((long)nchunks << 32);
         o[0] = tl0; o[1] = tl1; o[2] = tl2; o[3] = tl3;
         o[4] = (long)hw | ((long)xcc << 32);
-        o[5] = (long)KS | ((long)S << 8) | ((long)WM << 16) | ((long)wave << 24) | ((long)blockIdx.x << 32);
+        o[5] = (long)KS | ((long)S << 8) | ((long)(WM | (WN << 4)) << 16) | ((long)wave << 24) | ((long)blockIdx.x << 32);   // WM, WN: the region of a mixed grid
     }
 #endif
+}
+
+template <int KS, int S, int CIC, int WM, int WN, int FUSE, int TR, int BF = 0, int FULLC = 0>
+__global__ __launch_bounds__(64 * RCA_CONV_WPB, (((KS == 8 && CIC == 2) || (KS == 16 && CIC == 1)) && WM * WN < 8) ? 3 : RCA_CONV_OCC) void conv1d_mfma_kernel(const float* __restrict__ x, const float* __restrict__ wp,
+                                                          const float* __restrict__ bias, float* __restrict__ y,
+                                                          int Cin, int Lin, int Cout, int Lout, long Ncols, int nchunks,
+                                                          int pre, float slope, FuseIn fin, TrInfo tr) {
+    conv1d_mfma_body<KS, S, CIC, WM, WN, FUSE, TR, BF, FULLC>(x, wp, bias, y, Cin, Lin, Cout, Lout, Ncols, nchunks, pre, slope, fin, tr, blockIdx.x, 0);
+}
+
+// Mixed-tile grid (plain f32 convolution only): workgroups [0, n_bulk_wg) run the bulk wave tile (WM x WN) over the column tiles
+// [0, n_bulk_wg / channel tiles), exactly as conv1d_mfma_kernel would; the workgroups behind them run the fine tile (WM2 x WN2) over the
+// columns from `fine_col0` (a multiple of 64) on.  The host sizes the bulk to whole rounds of resident waves (rca_conv_balance.h) and
+// the hardware dispatches workgroups in index order, so the fine waves fill the slots that free up while the last bulk round drains
+// and the SIMDs go quiet together instead of a few of them running one more full-size wave each.  Both regions keep the XCD walk and
+// the padding of their column tiles to 8; the waves stay independent (no barrier, flag or wait between them); the one branch is
+// uniform and taken before any accumulator is live.  Results are those of either single-shape grid, bit for bit: a wave tile
+// changes which wave computes an output, not its fma chain.
+template <int KS, int S, int CIC, int WM, int WN, int WM2, int WN2, int FULLC>
+__global__ __launch_bounds__(64 * RCA_CONV_WPB, (((KS == 8 && CIC == 2) || (KS == 16 && CIC == 1)) && WM * WN < 8) ? 3 : RCA_CONV_OCC) void conv1d_mfma_mixed_kernel(const float* __restrict__ x, const float* __restrict__ wp,
+                                                          const float* __restrict__ bias, float* __restrict__ y,
+                                                          int Cin, int Lin, int Cout, int Lout, long Ncols, int nchunks,
+                                                          int pre, float slope, unsigned n_bulk_wg, long fine_col0) {
+    const FuseIn fin{};
+    const TrInfo tr{};
+    if (blockIdx.x < n_bulk_wg) conv1d_mfma_body<KS, S, CIC, WM, WN, 0, 0, 0, FULLC>(x, wp, bias, y, Cin, Lin, Cout, Lout, Ncols, nchunks, pre, slope, fin, tr, blockIdx.x, 0);
+    else conv1d_mfma_body<KS, S, CIC, WM2, WN2, 0, 0, 0, FULLC>(x, wp, bias, y, Cin, Lin, Cout, Lout, Ncols, nchunks, pre, slope, fin, tr, blockIdx.x - n_bulk_wg, fine_col0);
 }
 
 // Fused first layer with conv_in on the matrix pipe (k4s2 layer, Cin = 32; RCA_FUSE_MFMA_IN=0 brings conv1d_mfma_kernel<4, 2, 2, 2, 4, 1>
@@ -2665,6 +2694,49 @@ extern "C" int rca_codec_sync(rca_codec_t* h) {
     return RCA_OK;
 }
 
+// Mixed-tile launch of a plain f32 convolution with whole chunks (the strided encoder layers): the whole rounds of resident waves keep
+// the wave tile WM x WN, the columns behind them run on finer tiles at the end of the same grid (plan and model: rca_conv_balance.h).
+// false: nothing launched -- the plan is the single-shape grid (under one round, no remainder, no modelled gain) or RCA_CONV_BALANCE=0
+// (read per call: the parent grid, for A/B runs and as the tests' reference).  RCA_CONV_BALANCE_PLAN=<bulk column tiles>:<32x64|32x32>
+// (read per call, tests only) puts the seam anywhere, on any device.
+template <int KS, int S, int CIC, int WM, int WN>
+static bool launch_conv_balanced(const ConvLayer& L, const float* wp, int nchunks, const float* x, float* y, int Lin, int Lc, long Ncols,
+                                 float slope, hipStream_t st, int act, int lds) {
+    constexpr int NT = RCA_CONV_WPB * WN * 32, MT = WM * 32;
+    const char* on = getenv("RCA_CONV_BALANCE");
+    if (on && on[0] == '0') return false;
+    const long total = cdiv(Ncols, NT);
+    const int n_co = (int)cdiv(L.cout, MT);
+    ConvBalancePlan p;
+    if (!conv_balance_parse(getenv("RCA_CONV_BALANCE_PLAN"), total, WM, WN, &p)) {
+        // resident waves per SIMD of the bulk instantiation and the SIMD count, asked once per device (a device has 4 SIMDs per CU)
+        static int simds_of[64], occ_of[64];
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+        if (!simds_of[dev]) {
+            int cus = 0, blocks = 0;
+            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return false;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, conv1d_mfma_kernel<KS, S, CIC, WM, WN, 0, 0, 0, 1>, 64 * RCA_CONV_WPB, lds) != hipSuccess || blocks < 4)
+                return false;
+            occ_of[dev] = blocks * RCA_CONV_WPB / 4;
+            simds_of[dev] = 4 * cus;
+        }
+        p = conv_balance_plan(total, n_co, simds_of[dev], occ_of[dev], WM, WN);
+    }
+    if (!p.fine_wn) return false;
+    const long fine_col0 = p.bulk_col_tiles * NT;   // a multiple of 8 * 64 columns
+    const long n_bulk_wg = p.bulk_col_tiles * n_co;
+    const long fine_tiles = (cdiv(Ncols - fine_col0, RCA_CONV_WPB * p.fine_wn * 32) + 7) / 8 * 8;
+    const long n_wg = n_bulk_wg + fine_tiles * cdiv(L.cout, p.fine_wm * 32);
+    if (n_wg >= (1L << 31)) return false;
+    const dim3 grid((unsigned)n_wg);
+    if (WM * WN == 4 && p.fine_wn == 2)
+        conv1d_mfma_mixed_kernel<KS, S, CIC, WM, WN, 1, (WM * WN == 4 ? 2 : 1), 1><<<grid, 64 * RCA_CONV_WPB, lds, st>>>(x, wp, L.bp, y, L.cin, Lin, L.cout, Lc, Ncols, nchunks, act, slope, (unsigned)n_bulk_wg, fine_col0);
+    else
+        conv1d_mfma_mixed_kernel<KS, S, CIC, WM, WN, 1, 1, 1><<<grid, 64 * RCA_CONV_WPB, lds, st>>>(x, wp, L.bp, y, L.cin, Lin, L.cout, Lc, Ncols, nchunks, act, slope, (unsigned)n_bulk_wg, fine_col0);
+    return true;
+}
+
 template <int KS, int S, int CIC, int WM, int WN, int FUSE, int TR, int BF = 0>
 static void launch_conv_cfg(const ConvLayer& L, const float* wp, int nchunks, const float* x, float* y, int Lin, int Lc, long Ncols,
                             float slope, const FuseIn& fin, const TrInfo& tr, hipStream_t st, int act) {
@@ -2676,6 +2748,10 @@ static void launch_conv_cfg(const ConvLayer& L, const float* wp, int nchunks, co
     dim3 grid((unsigned)(col_tiles * cdiv(L.cout, MT) * (TR ? tr.s : 1)));
     if constexpr (!FUSE && !TR && BF == 0) {
         if (L.cin % CIC == 0 && nchunks * CIC == L.cin) {   // whole chunks only: the kernel without the per-channel descriptor selects
+            // the strided layers at 32 x 64 and 64 x 64 wave tiles: whole rounds on this tile, the rest on finer tiles (mixed grid)
+            if constexpr (KS >= 8 && WN == 2 && WM <= 2) {
+                if (launch_conv_balanced<KS, S, CIC, WM, WN>(L, wp, nchunks, x, y, Lin, Lc, Ncols, slope, st, act, lds)) return;
+            }
             conv1d_mfma_kernel<KS, S, CIC, WM, WN, 0, 0, 0, 1><<<grid, 64 * RCA_CONV_WPB, lds, st>>>(x, wp, L.bp, y, L.cin, Lin, L.cout, Lc, Ncols, nchunks, act, slope, fin, tr);
             return;
         }
@@ -2713,12 +2789,31 @@ static int launch_conv_mfma(const ConvLayer& L, const float* x, float* y, int B,
     // 32x32 992 us / 3.3 GB -- every column tile streams the layer's 8.4 MB of weights through a 4 MB L2, so narrow
     // column tiles multiply the fetches: 32 x 64 in the middle range, 32 x 32 only for small launches.  64x64 stays ahead
     // at 3360 workgroups (k10s5: 1137 vs 1169 us).
+    // Those figures hold for single-shape grids, last round included (RCA_CONV_BALANCE=0 still launches them).  With the mixed grid
+    // (launch_conv_balanced: whole rounds on the class's tile, the remaining columns on finer tiles) the 64 x 64 class no longer pays
+    // a part-filled round of full-size waves, and it wins from 1.5 rounds of its 2048 slots up.  Kernel trace, us per launch,
+    // mixed-grid 64 x 64 bulk / mixed-grid 32 x 64 bulk / single-shape 32 x 64 / single-shape 64 x 64:
+    //   k16s8, 256 windows (3200 waves of 64 x 64): 868 / 889-900 / 901-909 / -- (1081 vs 991 when the comparison above was made)
+    //   k10s5,  64 windows (3200):                  282 / 301 / 302 / 322
+    //   k10s5, 128 windows (6400):                  530 / 538 / 539 / 558
+    //   k8s4,   64 windows (8000, plan = single shape for both): 64 x 64 287, 32 x 64 313
+    // so the strided layers that have the mixed grid (k >= 8, whole chunks) take 64 x 64 tiles from BIG_BAL_MIN waves up.  Forced
+    // seams on the k16s8 layer at 256 windows (RCA_CONV_BALANCE_PLAN, bulk column tiles : fine tile): 64 x 64 bulk 128:32x32 887,
+    // 192:32x32 881, 256:32x32 868 (the plan), 320:32x32 1012, 256:32x64 904; 32 x 64 bulk 192:32x32 876, 288 888, 384 (the plan) 889-900.
     const long waves_big = (long)cdiv(Ncols, 64) * cdiv(L.cout, 64);
 #ifdef RCA_CONV_FORCE_MID   // timing experiment: 32 x 64 wave tiles (3 waves per SIMD) also for the largest launches
-    constexpr long BIG_MIN = 1L << 40, MID_MIN = 2048;
+    constexpr long BIG_MIN = 1L << 40, MID_MIN = 2048, BIG_BAL_MIN = 1L << 40;
 #else
     constexpr long BIG_MIN = 8192, MID_MIN = 2048;
+#ifdef RCA_CONV_BIG_BAL_MIN   // timing experiment: 8192 keeps the parent's classes under the mixed grid (A/B of the bulk tile)
+    constexpr long BIG_BAL_MIN = RCA_CONV_BIG_BAL_MIN;
+#else
+    constexpr long BIG_BAL_MIN = 3072;
 #endif
+#endif
+    const char* bal = getenv("RCA_CONV_BALANCE");
+    const bool balanced = KS >= 8 && !fuse && !(bal && bal[0] == '0') && L.cin % CIC == 0 && L.nchunks * CIC == L.cin;
+    const long big_min = balanced && BIG_BAL_MIN < BIG_MIN ? BIG_BAL_MIN : BIG_MIN;
     const FuseIn none{};
     const TrInfo notr{};
     if (fuse) {
@@ -2752,7 +2847,7 @@ static int launch_conv_mfma(const ConvLayer& L, const float* x, float* y, int B,
     } else {
         // (64 x 128 tiles on the k8s4 layer, <8, 4, 2, 2, 4>: 252 VGPRs, no spills, 1048 vs 1041 us -- its prologue is 7 % of a wave's
         //  life, not 30 %: not kept)
-        if (waves_big >= BIG_MIN) launch_conv_cfg<KS, S, CIC, 2, 2, 0, 0>(L, L.wp, L.nchunks, x, y, Lin, Lout, Ncols, slope, none, notr, st, act);
+        if (waves_big >= big_min) launch_conv_cfg<KS, S, CIC, 2, 2, 0, 0>(L, L.wp, L.nchunks, x, y, Lin, Lout, Ncols, slope, none, notr, st, act);
         else if (waves_big >= MID_MIN) launch_conv_cfg<KS, S, CIC, 1, 2, 0, 0>(L, L.wp, L.nchunks, x, y, Lin, Lout, Ncols, slope, none, notr, st, act);
         // the stride-1 k = 3 layers have a short reduction per column tile: 64 x 32 wave tiles (half the staging per MFMA of 32 x 32)
         // measured 213 vs 222 us on conv_out of the 256-window step; weights (0.8 MB) stay in L2, so no extra fetches

@@ -1,6 +1,7 @@
 """Per-wave timeline of conv1d_mfma_kernel.  Needs a library built with -DRCA_CONV_TIMELINE:
     export RCA_EXTRA_HIPCC_FLAGS=-DRCA_CONV_TIMELINE RCA_LIB_PATH=/tmp/rca_convtl.so; python -c "from realtime_codec_agent_amd import _native; _native.build()"
     RCA_CONV_TIMELINE_OUT=/tmp/tl.bin python scripts/conv_timeline.py && RCA_CONV_TIMELINE_OUT=/tmp/tl.bin python scripts/conv_timeline.py analyse
+`python scripts/conv_timeline.py tail` prints how each launch ends (SIMDs that still hold a wave over the last part of its span).
 (RCA_LIB_PATH keeps the diagnostic build away from the in-tree library: _native.build refuses extra flags without it).
 
 Runs two bench-shaped encode passes (256 windows), lets the library dump (t_entry, t_loop, t_epilogue, t_exit, HW_ID)
@@ -75,10 +76,46 @@ def analyse(path):
               f"  distinct slots {len(set(sl.tolist()))}")
 
 
+def tail(path):
+    """How a launch ends: waves alive and SIMDs that hold a wave at fractions of the launch span, the duration of the waves that start
+    late, and the point from which fewer than half of the SIMDs are busy (the part-filled last round of a single-shape grid; the
+    regions of a mixed grid show as two wave tiles)."""
+    raw = open(path, "rb").read()
+    a = np.frombuffer(raw[4:], np.int64).reshape(-1, 8)
+    a = a[a[:, 0] != 0]
+    ks = a[:, 5] & 0xFF
+    for k in sorted(set(ks.tolist())):
+        sub = a[ks == k]
+        T0, T3, HW = sub[:, 0], sub[:, 3], sub[:, 4]
+        wm, wn = (sub[:, 5] >> 16) & 0xF, (sub[:, 5] >> 20) & 0xF
+        simd = ((HW >> 4) & 3) | (((HW >> 8) & 0xFF) << 8) | ((HW >> 32) << 20)
+        t_lo, t_hi = T0.min(), T3.max()
+        dur = (T3 - T0) * 0.01
+        tiles = sorted(set(zip((32 * wm).tolist(), (32 * wn).tolist())))
+        print(f"k{k}: waves {len(sub)} span {(t_hi - t_lo) * 0.01:.1f} us, simds {len(set(simd.tolist()))}, wave tiles {tiles}, wave duration median {np.median(dur):.1f} us")
+        cells = []
+        for f in (0.5, 0.7, 0.8, 0.85, 0.9, 0.92, 0.94, 0.96, 0.98, 0.99):
+            t = t_lo + int(f * (t_hi - t_lo))
+            alive = (T0 <= t) & (T3 > t)
+            cells.append(f"{f:.2f}:{int(alive.sum())}w/{len(set(simd[alive].tolist()))}s")
+        print("   waves alive / simds holding a wave at fraction of span: " + "  ".join(cells))
+        for f in (0.0, 0.5, 0.7, 0.8, 0.85, 0.9):
+            m = T0 >= t_lo + int(f * (t_hi - t_lo))
+            if m.sum():
+                print(f"   waves starting after {f:.2f} of span: n={int(m.sum())} median duration {np.median(dur[m]):.1f} us (p10 {np.percentile(dur[m], 10):.1f}, p90 {np.percentile(dur[m], 90):.1f})")
+        ts = np.linspace(t_lo, t_hi, 400)
+        busy = np.array([len(set(simd[(T0 <= t) & (T3 > t)].tolist())) for t in ts])
+        late = [i for i in np.where(busy < 0.5 * len(set(simd.tolist())))[0] if i > 200]
+        if late:
+            print(f"   busy simds fall below half at {(ts[late[0]] - t_lo) * 0.01:.1f} us ({100 * (1 - (ts[late[0]] - t_lo) / (t_hi - t_lo)):.1f} % of the span is tail)")
+
+
 if __name__ == "__main__":
     path = os.environ.get("RCA_CONV_TIMELINE_OUT")
     assert path, "set RCA_CONV_TIMELINE_OUT=<file>"
     if len(sys.argv) > 1 and sys.argv[1] == "analyse":
         analyse(path)
+    elif len(sys.argv) > 1 and sys.argv[1] == "tail":
+        tail(path)
     else:
         run(path)
