@@ -543,7 +543,31 @@ int rca_lm_batch_frame(rca_lm_batch_t* b, const int32_t* first_pairs, const int3
 int rca_lm_batch_frame_sel(rca_lm_batch_t* b, const int32_t* sel, int32_t n_sel, const int32_t* first_pairs, const int32_t* user_ids,
                            int32_t n_steps, int32_t audio_id_floor, const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done,
                            float* probe_probs);
-/* graph captures made by this batch so far (batch steps, batch frames and selection frames) */
+/* Selection step: rca_lm_step_probe for a SUBSET of the members in one pass -- the agents' speculative <|end_audio|> step for the
+ * sessions of a tick that owe it, or a server's step of the sessions that are in a text branch.  sel [n_sel] as for the selection
+ * frame; every per-member array is indexed by k, the position in sel: ids [n_sel][n] with n 1 or 2, probe_ids [n_sel][n_probe] with
+ * n_probe 0..8 (NULL exactly when n_probe is 0), tokens [n_sel], probs [n_sel][n_probe] (may be NULL when n_probe is 0).  Member
+ * sel[k] evaluates ids[k * n .. k * n + n) at ITS n_tokens, samples with ITS sampler (draw counter + 1, the token joins its penalty
+ * window) and probs[k][i] = softmax(logits of the evaluated position)[probe_ids[k][i]].
+ *   Contract, bit for bit: a selected member ends as rca_lm_batch_step(n) on a batch created over ONLY the selected members would
+ *   leave it -- token, logits, K / V rows, n_tokens, draw counter, penalty window -- and its probabilities are the bytes
+ *   rca_lm_token_probs returns on it right after that step.  An unselected member is in no table of the call: nothing reads or writes
+ *   it, it is neither settled nor checked, and its full cache or missing sampler refuses nothing.  The caller that only wanted the
+ *   probabilities rolls back with rca_lm_set_n_tokens(n_tokens - n): the next evaluation overwrites the speculative rows.
+ *   Refused before anything is staged, with NO member changed, in a message that names k and the member: a null argument, n outside
+ *   1..2, n_probe outside 0..8, probe_ids or probs NULL while n_probe > 0, n_sel outside 1..n_members, an index outside the batch or
+ *   selected twice, a token or probe id outside the vocabulary (RCA_ERR_ARG); a selected member without a sampler, switched to
+ *   logits_all, off the 128-token tile route, in another KV format than member 0, or with n_tokens + n > n_ctx (RCA_ERR_STATE).
+ *   The launches are the selection frame's machinery with n tokens per member: tables of slots 0 .. n_sel - 1, the ids and the probe
+ *   ids uploaded as one block inside the replay, the class's launch geometry, one linear sequence on member 0's stream, tokens and
+ *   probabilities gathered for one download.  A graph is captured per (class, n, largest context bucket among the SELECTED members
+ *   after the step, probes present or not, a logit-patching sampler among the selected); n_probe and the ids come from the block, so
+ *   one graph serves every selection of its class, also after a member's rca_lm_swap_kv, and is dropped with the selection frame's
+ *   graphs.  A selection that holds a member on a whole-vocabulary sampler, or a member with graphs off, runs the same launches
+ *   eagerly: same results. */
+int rca_lm_batch_step_sel(rca_lm_batch_t* b, const int32_t* sel, int32_t n_sel, const int32_t* ids, int32_t n, const int32_t* probe_ids,
+                          int32_t n_probe, int32_t* tokens, float* probs);
+/* graph captures made by this batch so far (batch steps, batch frames, selection frames and selection steps) */
 int rca_lm_batch_captures(const rca_lm_batch_t* b, int64_t* n);
 /* One whole frame of process_audio_input_ids (realtime_agent_v2.py:332-372) as ONE hipGraph: n_steps (<= 8) S=2 steps, the
  * agent token sampled by step i fed back on the device together with user_ids[i] as step i+1's input pair; first_pair is the

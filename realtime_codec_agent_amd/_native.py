@@ -320,6 +320,11 @@ class DuplexBatchOutC(C.Structure):
     ]
 
 
+# int rca_lm_batch_step_sel(b, sel, n_sel, ids, n, probe_ids, n_probe, tokens, probs), argument for argument as in include/rca.h
+_I32P = C.POINTER(C.c_int32)
+BATCH_STEP_SEL_ARGTYPES = [C.c_void_p, _I32P, C.c_int32, _I32P, C.c_int32, _I32P, C.c_int32, _I32P, C.POINTER(C.c_float)]
+
+
 def sources() -> List[str]:
     return [os.path.join(CSRC_DIR, s) for s in HIP_SOURCES if os.path.exists(os.path.join(CSRC_DIR, s))]
 
@@ -440,7 +445,7 @@ ABI_SYMBOLS = [
     "rca_duplex_frame", "rca_codec_workspace_sig", "rca_codec_stream_handoff", "rca_codec_codebook_size", "rca_codec_set_mfma_mode", "rca_lm_step_probe", "rca_duplex_prepare", "rca_duplex_precapture",
     "rca_lm_group_create", "rca_lm_group_destroy", "rca_lm_group_step",
     "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
-    "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame",
+    "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame", "rca_lm_batch_step_sel",
 ]
 
 
@@ -464,6 +469,8 @@ def lib():
         raise RcaError(f"cannot load {LIB_PATH}: {e}") from e
     _lib.rca_last_error.restype = C.c_char_p
     _lib.rca_version.restype = C.c_char_p
+    _lib.rca_lm_batch_step_sel.argtypes = BATCH_STEP_SEL_ARGTYPES
+    _lib.rca_lm_batch_step_sel.restype = C.c_int
     return _lib
 
 

@@ -5822,6 +5822,11 @@ struct LmBatchPin { LmBatchFrameStage in; int tokens[LM_BATCH_MAX]; LmBatchFrame
 // slots, composed on the host for every call and uploaded as one block inside the replay: a graph over them holds no member's pointer
 #define LM_BATCH_CLASSES 4   // launch geometries: 8, 16, 32 or 64 slots
 struct LmBatchSelStage { LmBatchFrameStage in; int n_live; int pad; LmBatchMember tab[LM_BATCH_MAX]; LmGroupRow rows[LM_BATCH_ROWS]; };
+// rca_lm_batch_step_sel: the selection's block with the step's probe ids behind it (a frame uploads the LmBatchSelStage head only), and
+// what the step gathers for its one download
+#define LM_STEP_PROBES 8
+struct LmBatchStepSelStage : LmBatchSelStage { int n_probe; int pad2; int probe_ids[LM_BATCH_MAX * LM_STEP_PROBES]; };   // probe_ids[k * n_probe + i]
+struct LmBatchStepSelOut { int tokens[LM_BATCH_MAX]; float probs[LM_BATCH_MAX * LM_STEP_PROBES]; };                    // probs[k * n_probe + i]
 // what a pass reads about its members: the batch's own tables, or a selection's
 struct LmBatchView { const LmGroupRow* rows; const LmBatchMember* tab; int NM; bool any_serial, any_patch; rca_lm* const* hm; int n_hm; };
 struct rca_lm_batch {
@@ -5844,25 +5849,36 @@ struct rca_lm_batch {
     float* probe_part = nullptr;            // device, [n_members][PROBS_SLICES (max, sum) pairs]
     hipGraphExec_t fg[LM_FRAME_MAX][LM_GRAPH_BUCKETS][2] = {};   // (n_steps - 1, largest context bucket at the frame's end, probes)
     // rca_lm_batch_frame_sel
-    LmBatchSelStage* sel_stage = nullptr;   // device copy of sel_pin
-    LmBatchSelStage* sel_pin = nullptr;     // pinned
+    LmBatchStepSelStage* sel_stage = nullptr;   // device copy of sel_pin
+    LmBatchStepSelStage* sel_pin = nullptr;     // pinned
     int nsp_all = 1;                        // the largest split count among ALL members: a selection graph's attention grid
     unsigned long long sel_epoch = 0;       // sum of the members' drop_epoch the graphs below were captured under
     hipGraphExec_t sg[LM_BATCH_CLASSES][LM_FRAME_MAX][LM_GRAPH_BUCKETS][2][2] = {};   // (class, n_steps - 1, bucket, probes, a patching sampler among them)
     long long n_captures = 0;               // rca_lm_batch_captures
     struct LmBatchDuplex* dx = nullptr;     // rca_duplex_batch_frame: buffers, pinned staging and graphs (made by its first call)
+    // rca_lm_batch_step_sel
+    LmBatchStepSelOut* step_out = nullptr;      // device: the selected members' tokens and probabilities, gathered for one download
+    LmBatchStepSelOut* step_out_pin = nullptr;  // pinned
+    hipGraphExec_t ssg[LM_BATCH_CLASSES][LM_GEMV_M][LM_GRAPH_BUCKETS][2][2] = {};   // (class, n - 1, bucket, probes, a patching sampler among them)
 };
 // the pass's state and the selected members' step states from a selection's block; the live count comes from the block, not the launch
-__global__ void lm_batch_sel_stage_kernel(const LmBatchSelStage* __restrict__ in, LmDevState* __restrict__ bstt, LmDevState* __restrict__ hstt) {
+__device__ __forceinline__ void lm_batch_sel_stage_body(const LmBatchSelStage* __restrict__ in, LmDevState* __restrict__ bstt, LmDevState* __restrict__ hstt, int n) {
     const int t = threadIdx.x, nl = in->n_live;
-    if (t == 0) { bstt->n_tokens = 0; bstt->m = nl * 2; hstt->n_tokens = 0; hstt->m = nl; }
-    if (t < nl * 2) bstt->ids[t] = in->in.ids[t];
+    if (t == 0) { bstt->n_tokens = 0; bstt->m = nl * n; hstt->n_tokens = 0; hstt->m = nl; }
+    if (t < nl * n) bstt->ids[t] = in->in.ids[t];
     if (t < nl) {
         LmDevState* stt = in->tab[t].stt;
         stt->n_tokens = in->in.n_tokens[t];
-        stt->m = 2;
-        for (int j = 0; j < 2; ++j) stt->ids[j] = in->in.ids[t * 2 + j];
+        stt->m = n;
+        for (int j = 0; j < n; ++j) stt->ids[j] = in->in.ids[t * n + j];
     }
+}
+__global__ void lm_batch_sel_stage_kernel(const LmBatchSelStage* __restrict__ in, LmDevState* __restrict__ bstt, LmDevState* __restrict__ hstt) {
+    lm_batch_sel_stage_body(in, bstt, hstt, 2);
+}
+// the same for a selection step of n tokens per member (rca_lm_batch_step_sel)
+__global__ void lm_batch_sel_stage_n_kernel(const LmBatchSelStage* __restrict__ in, LmDevState* __restrict__ bstt, LmDevState* __restrict__ hstt, int n) {
+    lm_batch_sel_stage_body(in, bstt, hstt, n);
 }
 // the pass's state and the members' step states, from one staging block
 __global__ void lm_batch_stage_kernel(const LmBatchStage* __restrict__ in, const LmBatchMember* __restrict__ tab, LmDevState* __restrict__ bstt,
@@ -5944,6 +5960,13 @@ __global__ __launch_bounds__(64) void lm_token_probs_batch_kernel(const LmBatchM
     if (!tab[s].logits) return;
     lm_token_probs_body(tab[s].logits, V, part + (long)s * 2 * PROBS_SLICES, ids + s, 1, probs + s);
 }
+// rca_lm_batch_step_sel: softmax(slot's logits)[its n_probe ids]; the count and the ids come from the uploaded block, not the launch
+__global__ __launch_bounds__(64) void lm_token_probs_sel_kernel(const LmBatchMember* __restrict__ tab, int V, const float* __restrict__ part,
+                                                                const LmBatchStepSelStage* __restrict__ in, float* __restrict__ probs) {
+    const int s = blockIdx.y, np = in->n_probe;
+    if (!tab[s].logits) return;   // a slot past the selection's live count
+    lm_token_probs_body(tab[s].logits, V, part + (long)s * 2 * PROBS_SLICES, in->probe_ids + s * np, np, probs + s * np);
+}
 // a frame drew n_steps times for every member: the counters of the members it cut go back to where their accepted draws end
 struct LmBatchCuts { int n; int member[LM_BATCH_MAX]; unsigned long long counter[LM_BATCH_MAX]; };
 __global__ void lm_batch_counters_kernel(const LmBatchMember* __restrict__ tab, LmBatchCuts cuts) {
@@ -5961,6 +5984,9 @@ static void lm_batch_drop_graphs(rca_lm_batch* b) {
 static void lm_batch_drop_sel_graphs(rca_lm_batch* b) {
     hipGraphExec_t* e = &b->sg[0][0][0][0][0];
     for (size_t i = 0; i < sizeof(b->sg) / sizeof(hipGraphExec_t); ++i)
+        if (e[i]) { (void)hipGraphExecDestroy(e[i]); e[i] = nullptr; }
+    e = &b->ssg[0][0][0][0][0];   // rca_lm_batch_step_sel's
+    for (size_t i = 0; i < sizeof(b->ssg) / sizeof(hipGraphExec_t); ++i)
         if (e[i]) { (void)hipGraphExecDestroy(e[i]); e[i] = nullptr; }
 }
 // the launch geometry of n slots: 8, 16, 32 or 64
@@ -5999,15 +6025,17 @@ extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, 
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->stage, sizeof(LmBatchFrameStage));
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->frame_out, sizeof(LmBatchFrameOut));
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->probe_part, sizeof(float) * 2 * PROBS_SLICES * n_slots);
-    if (rc == RCA_OK) rc = lm_alloc((void**)&b->sel_stage, sizeof(LmBatchSelStage));
-    if (rc == RCA_OK && hipHostMalloc((void**)&b->sel_pin, sizeof(LmBatchSelStage), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->sel_stage, sizeof(LmBatchStepSelStage));
+    if (rc == RCA_OK && hipHostMalloc((void**)&b->sel_pin, sizeof(LmBatchStepSelStage), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
+    if (rc == RCA_OK) rc = lm_alloc((void**)&b->step_out, sizeof(LmBatchStepSelOut));
+    if (rc == RCA_OK && hipHostMalloc((void**)&b->step_out_pin, sizeof(LmBatchStepSelOut), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->tokens, sizeof(int) * LM_BATCH_MAX);
     if (rc == RCA_OK && hipHostMalloc((void**)&b->pin, sizeof(LmBatchPin), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
     if (rc == RCA_OK && (hipMemset(b->stt, 0, sizeof(LmDevState)) != hipSuccess || hipMemset(b->stt_head, 0, sizeof(LmDevState)) != hipSuccess))
         rc = fail(RCA_ERR_HIP, "batch_create: clearing the pass states");
     if (rc != RCA_OK) { rca_lm_batch_destroy(b); return rc; }
     memset(b->pin, 0, sizeof(LmBatchPin));
-    memset(b->sel_pin, 0, sizeof(LmBatchSelStage));
+    memset(b->sel_pin, 0, sizeof(LmBatchStepSelStage));
     for (int s = 0; s < n_members; ++s) b->nsp_all = std::max(b->nsp_all, members[s]->n_splits);
     *out = b;
     return RCA_OK;
@@ -6018,10 +6046,11 @@ extern "C" int rca_lm_batch_destroy(rca_lm_batch_t* b) {
     lm_batch_drop_sel_graphs(b);
     lm_batch_duplex_destroy(b->dx);
     for (void* p : {(void*)b->rows, (void*)b->tab, (void*)b->stt, (void*)b->stt_head, (void*)b->head_blk, (void*)b->stage, (void*)b->tokens, (void*)b->frame_out,
-                    (void*)b->probe_part, (void*)b->sel_stage})
+                    (void*)b->probe_part, (void*)b->sel_stage, (void*)b->step_out})
         if (p) (void)hipFree(p);
     if (b->pin) (void)hipHostFree(b->pin);
     if (b->sel_pin) (void)hipHostFree(b->sel_pin);
+    if (b->step_out_pin) (void)hipHostFree(b->step_out_pin);
     delete b;
     return RCA_OK;
 }
@@ -6442,13 +6471,10 @@ static int lm_batch_sel_enqueue(rca_lm_batch* b, const LmBatchView& vw, int n_st
     if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pin + dc->pin_out, d->pcm_out, (size_t)dc->slots * dc->n_samples * 4, hipMemcpyDeviceToHost, st);
     return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch frame_sel download: %s", hipGetErrorString(e));
 }
-// The refusals of a selection frame, before anything is staged: no member changes.  hm[k] receives the handle of sel[k].  user_ids is
-// null when the device produces them (rca_duplex_batch_frame).
-static int lm_batch_sel_check(rca_lm_batch* b, const char* who, const int32_t* sel, int n_sel, const int32_t* first_pairs, const int32_t* user_ids, int n_steps,
-                              const int32_t* probe_ids, rca_lm** hm) {
+// The parts of a selection's refusals that its frame and its step (rca_lm_batch_step_sel) share.  Members: every index in range and
+// selected once, hm[k] receives the handle of sel[k], and the selected members are settled.
+static int lm_batch_sel_members(rca_lm_batch* b, const char* who, const int32_t* sel, int n_sel, rca_lm** hm) {
     const int NM = b->n_members;
-    if (n_sel < 1 || n_sel > NM) return fail(RCA_ERR_ARG, "%s: %d selected members, the batch has %d (1..%d)", who, n_sel, NM, NM);
-    if (n_steps < 1 || n_steps > LM_FRAME_MAX) return fail(RCA_ERR_ARG, "%s: %d steps (1..%d)", who, n_steps, LM_FRAME_MAX);
     int first_k[LM_BATCH_MAX];
     for (int s = 0; s < NM; ++s) first_k[s] = -1;
     for (int k = 0; k < n_sel; ++k) {
@@ -6461,14 +6487,40 @@ static int lm_batch_sel_check(rca_lm_batch* b, const char* who, const int32_t* s
     int rc;
     for (int k = 0; k < n_sel; ++k)
         if ((rc = lm_settle(hm[k])) != RCA_OK) return rc;
+    return RCA_OK;
+}
+// what makes sel[k] = member s unfit for a selection's pass
+static int lm_batch_sel_member_ok(const rca_lm_batch* b, const char* who, const rca_lm* h, int k, int s) {
+    if (!h->sampler_set) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has no sampler (rca_lm_sampler_init)", who, k, s);
+    if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d was switched to logits_all after the batch was made", who, k, s);
+    if (h->kv_format != b->m[0]->kv_format) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has KV format %d, member 0 has %d", who, k, s, h->kv_format, b->m[0]->kv_format);
+    if (lm_prefill_route(h) != LM_ROUTE_TILE128)
+        return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", who, k, s, lm_prefill_route(h));
+    return RCA_OK;
+}
+// the selection graphs hold member 0's workspace and the sampler launches of the chain: they go when a member dropped its own graphs
+static void lm_batch_sel_epoch(rca_lm_batch* b) {
+    unsigned long long epoch = 0;
+    for (int s = 0; s < b->n_members; ++s) epoch += b->m[s]->drop_epoch;
+    if (epoch != b->sel_epoch) {
+        lm_batch_drop_sel_graphs(b);
+        lm_batch_duplex_drop_graphs(b->dx);
+        b->sel_epoch = epoch;
+    }
+}
+// The refusals of a selection frame, before anything is staged: no member changes.  hm[k] receives the handle of sel[k].  user_ids is
+// null when the device produces them (rca_duplex_batch_frame).
+static int lm_batch_sel_check(rca_lm_batch* b, const char* who, const int32_t* sel, int n_sel, const int32_t* first_pairs, const int32_t* user_ids, int n_steps,
+                              const int32_t* probe_ids, rca_lm** hm) {
+    const int NM = b->n_members;
+    if (n_sel < 1 || n_sel > NM) return fail(RCA_ERR_ARG, "%s: %d selected members, the batch has %d (1..%d)", who, n_sel, NM, NM);
+    if (n_steps < 1 || n_steps > LM_FRAME_MAX) return fail(RCA_ERR_ARG, "%s: %d steps (1..%d)", who, n_steps, LM_FRAME_MAX);
+    int rc;
+    if ((rc = lm_batch_sel_members(b, who, sel, n_sel, hm)) != RCA_OK) return rc;
     for (int k = 0; k < n_sel; ++k) {
         const rca_lm* h = hm[k];
         const int s = sel[k], V = h->cfg.vocab_size;
-        if (!h->sampler_set) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has no sampler (rca_lm_sampler_init)", who, k, s);
-        if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d was switched to logits_all after the batch was made", who, k, s);
-        if (h->kv_format != b->m[0]->kv_format) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has KV format %d, member 0 has %d", who, k, s, h->kv_format, b->m[0]->kv_format);
-        if (lm_prefill_route(h) != LM_ROUTE_TILE128)
-            return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", who, k, s, lm_prefill_route(h));
+        if ((rc = lm_batch_sel_member_ok(b, who, h, k, s)) != RCA_OK) return rc;
         if (h->n_tokens + 2 * n_steps > h->cfg.n_ctx)
             return fail(RCA_ERR_STATE, "%s: context overflow of sel[%d] = member %d: %d + %d > n_ctx %d", who, k, s, h->n_tokens, 2 * n_steps, h->cfg.n_ctx);
         for (int j = 0; j < 2; ++j)
@@ -6489,14 +6541,7 @@ static int lm_batch_sel_check(rca_lm_batch* b, const char* who, const int32_t* s
 struct LmBatchSelPlan { LmBatchView vw; bool graphs, any_patch; int cls, bucket, nsp, nsp_bucket; };
 static LmBatchSelPlan lm_batch_sel_stage(rca_lm_batch* b, rca_lm* const* hm, int n_sel, const int32_t* first_pairs, const int32_t* user_ids, int n_steps,
                                          const int32_t* probe_ids) {
-    // the graphs hold member 0's workspace and the sampler launches of the chain: they go when a member dropped its own graphs
-    unsigned long long epoch = 0;
-    for (int s = 0; s < b->n_members; ++s) epoch += b->m[s]->drop_epoch;
-    if (epoch != b->sel_epoch) {
-        lm_batch_drop_sel_graphs(b);
-        lm_batch_duplex_drop_graphs(b->dx);
-        b->sel_epoch = epoch;
-    }
+    lm_batch_sel_epoch(b);
     LmBatchSelPlan p{};
     p.cls = lm_batch_class(n_sel);
     p.graphs = true;
@@ -6584,6 +6629,108 @@ extern "C" int rca_lm_batch_frame_sel(rca_lm_batch_t* b, const int32_t* sel, int
     }
     RCA_HIP(hipStreamSynchronize(st));
     return lm_batch_sel_settle(b, hm, n_sel, n_steps, audio_id_floor, probe_ids, out_tokens, n_steps, n_done, probes ? probe_probs : nullptr, st);
+}
+
+// ------------------------------------------------------------------------------------ selection step (rca_lm_batch_step_sel)
+// rca_lm_step_probe for a SUBSET of the members in one pass: the agents' speculative <|end_audio|> step for the members of a tick that
+// owe it, or a server's step of the sessions that are in a text branch.  The selection machinery of the frame above with n = 1 or 2
+// tokens per member: tables of slots 0 .. n_sel - 1 composed for this call, uploaded with the ids and the probe ids as one block inside
+// the replay; the launches cover the class, the live count and the probe count travel in the block.  A selected member ends as
+// rca_lm_batch_step(n) of a batch over the selected members alone leaves it; an unselected member is in no table of the call.
+// upload -> stage -> the pass -> [probes] -> gather -> download, one linear sequence on `st`
+static int lm_batch_step_sel_enqueue(rca_lm_batch* b, const LmBatchView& vw, int n, int nsp_launch, bool probes, hipStream_t st) {
+    const int V = b->m[0]->cfg.vocab_size;
+    hipError_t e = hipMemcpyAsync(b->sel_stage, b->sel_pin, sizeof(LmBatchStepSelStage), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch step_sel upload: %s", hipGetErrorString(e));
+    lm_batch_sel_stage_n_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->sel_stage, b->stt, b->stt_head, n);
+    lm_batch_enqueue_pass(b, vw, n, nsp_launch, st);
+    if (probes) {
+        lm_softmax_slices_batch_kernel<<<dim3(PROBS_SLICES, vw.NM), 1024, 0, st>>>(vw.tab, V, b->probe_part);
+        lm_token_probs_sel_kernel<<<dim3(1, vw.NM), 64, 0, st>>>(vw.tab, V, b->probe_part, b->sel_stage, b->step_out->probs);
+    }
+    lm_batch_tokens_kernel<<<1, LM_BATCH_MAX, 0, st>>>(vw.tab, vw.NM, b->step_out->tokens);
+    RCA_LAUNCH_CHECK();
+    e = hipMemcpyAsync(b->step_out_pin, b->step_out, sizeof(LmBatchStepSelOut), hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch step_sel download: %s", hipGetErrorString(e));
+}
+extern "C" int rca_lm_batch_step_sel(rca_lm_batch_t* b, const int32_t* sel, int32_t n_sel, const int32_t* ids, int32_t n, const int32_t* probe_ids, int32_t n_probe,
+                                     int32_t* tokens, float* probs) {
+    const char* who = "batch_step_sel";
+    if (!b || !sel || !ids || !tokens) return fail(RCA_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > LM_GEMV_M) return fail(RCA_ERR_ARG, "%s: %d tokens per member (1..%d)", who, n, LM_GEMV_M);
+    if (n_probe < 0 || n_probe > LM_STEP_PROBES) return fail(RCA_ERR_ARG, "%s: %d probe ids per member (0..%d)", who, n_probe, LM_STEP_PROBES);
+    if ((n_probe > 0) != (probe_ids != nullptr)) return fail(RCA_ERR_ARG, "%s: probe_ids is null exactly when n_probe is 0 (n_probe %d)", who, n_probe);
+    if (n_probe > 0 && !probs) return fail(RCA_ERR_ARG, "%s: probe_ids without probs", who);
+    if (n_sel < 1 || n_sel > b->n_members) return fail(RCA_ERR_ARG, "%s: %d selected members, the batch has %d (1..%d)", who, n_sel, b->n_members, b->n_members);
+    rca_lm* hm[LM_BATCH_MAX];
+    int rc;
+    // every refusal before anything is staged or enqueued: no member changes
+    if ((rc = lm_batch_sel_members(b, who, sel, n_sel, hm)) != RCA_OK) return rc;
+    for (int k = 0; k < n_sel; ++k) {
+        const rca_lm* h = hm[k];
+        const int s = sel[k], V = h->cfg.vocab_size;
+        if ((rc = lm_batch_sel_member_ok(b, who, h, k, s)) != RCA_OK) return rc;
+        if (h->n_tokens + n > h->cfg.n_ctx)
+            return fail(RCA_ERR_STATE, "%s: context overflow of sel[%d] = member %d: %d + %d > n_ctx %d", who, k, s, h->n_tokens, n, h->cfg.n_ctx);
+        for (int j = 0; j < n; ++j)
+            if (ids[k * n + j] < 0 || ids[k * n + j] >= V)
+                return fail(RCA_ERR_ARG, "%s: token id %d of sel[%d] = member %d at index %d is outside the vocabulary [0, %d)", who, ids[k * n + j], k, s, j, V);
+        for (int i = 0; i < n_probe; ++i)
+            if (probe_ids[k * n_probe + i] < 0 || probe_ids[k * n_probe + i] >= V)
+                return fail(RCA_ERR_ARG, "%s: probe id %d of sel[%d] = member %d at index %d is outside the vocabulary [0, %d)", who, probe_ids[k * n_probe + i], k, s, i, V);
+    }
+    RCA_HIP(hipSetDevice(b->m[0]->device));
+    hipStream_t st = b->m[0]->stream;
+    lm_batch_sel_epoch(b);
+    // the call's block: tables of the selected members in slots 0 .. n_sel - 1 for n tokens each, all-zero entries behind them
+    LmBatchStepSelStage& in = *b->sel_pin;
+    memset(&in, 0, sizeof(in));
+    in.n_live = n_sel;
+    in.n_probe = n_probe;
+    const int cls = lm_batch_class(n_sel);
+    bool graphs = true, any_serial = false, any_patch = false;
+    int bucket = 0, nsp = 1;
+    for (int k = 0; k < n_sel; ++k) {
+        rca_lm* h = hm[k];
+        const bool serial = !h->samp_full;
+        graphs = graphs && h->graphs_enabled && serial;   // a whole-vocabulary sampler has launches of its own with its own pointers: eager
+        any_serial = any_serial || serial;
+        any_patch = any_patch || (serial && h->samp_patch);
+        in.tab[k] = lm_batch_member(h, k * n, serial);
+        for (int j = 0; j < n; ++j) {
+            in.rows[k * n + j] = lm_group_row(h, j, k * n + j);
+            in.in.ids[k * n + j] = ids[k * n + j];
+        }
+        in.in.n_tokens[k] = h->n_tokens;
+        for (int i = 0; i < n_probe; ++i) in.probe_ids[k * n_probe + i] = probe_ids[k * n_probe + i];
+        bucket = std::max(bucket, lm_bucket(h, n, -1).bucket);
+        nsp = std::max(nsp, lm_splits_needed(h, n));
+    }
+    const LmBatchView vw{b->sel_stage->rows, b->sel_stage->tab, 8 << cls, any_serial, any_patch, hm, n_sel};
+    const bool probes = n_probe > 0;
+    if (graphs) {
+        // the bucket's split count over ALL members of the batch: the grid does not depend on who is selected
+        const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? b->nsp_all : std::min(b->nsp_all, 4 << bucket);
+        hipGraphExec_t& gexec = b->ssg[cls][n - 1][bucket][probes ? 1 : 0][any_patch ? 1 : 0];
+        if (!gexec) {
+            if ((rc = lm_capture(st, &gexec, "batch step_sel", [&]() -> int { return lm_batch_step_sel_enqueue(b, vw, n, nsp_bucket, probes, st); })) != RCA_OK) return rc;
+            b->n_captures++;
+        }
+        RCA_HIP(hipGraphLaunch(gexec, st));
+    } else if ((rc = lm_batch_step_sel_enqueue(b, vw, n, nsp, probes, st)) != RCA_OK) {
+        return rc;
+    }
+    RCA_HIP(hipStreamSynchronize(st));
+    const LmBatchStepSelOut& out = *b->step_out_pin;
+    for (int k = 0; k < n_sel; ++k) {
+        rca_lm* h = hm[k];
+        h->n_tokens += n;
+        h->logits_rows = 1;
+        h->rng_host += 1;
+        tokens[k] = out.tokens[k];
+    }
+    if (probes) memcpy(probs, out.probs, sizeof(float) * (size_t)n_sel * n_probe);
+    return RCA_OK;
 }
 
 // ------------------------------------------------------------------------------------ duplex batch frame (rca_duplex_batch_frame)

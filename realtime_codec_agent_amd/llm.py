@@ -904,7 +904,8 @@ class LlamaBatch:
     the arithmetic class of a decode on a tile-built cache, and a member's result does not depend on its slot or companions.
     step() / eval() / sample() on a member, group steps and batch steps mix freely.  Close the batch before its members.
     Sessions that sit a tick out stay members and are left out of the call: frame(members=[...]) and duplex_frame(codec, members, ...)
-    run over a selection and touch no other member; selections of one size class (up to 8, 16, 32, 64) share their graphs, which hold
+    run over a selection and touch no other member, and so does step_probe(members, ...), a 1- or 2-token step with token probabilities
+    (the agents' speculative <|end_audio|> step, or the sessions in a text branch); selections of one size class (up to 8, 16, 32, 64) share their graphs, which hold
     no member's pointers and outlive a member's swap_kv (captures() counts them)."""
 
     def __init__(self, members: Sequence["LlamaForAlternatingCodeChannels"], lib=None):
@@ -991,6 +992,49 @@ class LlamaBatch:
         probs = np.array(pp[:], dtype=np.float32)
         probs[probs < 0.0] = np.nan
         return tokens, probs
+
+    def step_probe(self, members: Sequence[int], tokens_per_member: Sequence[Sequence[int]],
+                   probe_ids_per_member: Optional[Sequence[Sequence[int]]] = None):
+        """step_probe() of the members in `members` (distinct indices, any order) in ONE pass (rca_lm_batch_step_sel): member
+        members[k] evaluates tokens_per_member[k] (all of one length n = 1 or 2) at its own n_tokens, samples with its own sampler and
+        has softmax(its new logits)[probe_ids_per_member[k]] taken (all of one length, up to 8).  Returns (tokens, probs): the sampled
+        token of every selected member and a float32 array [len(members), n_probe], None without probe ids.  A selected member ends
+        as step() of a batch over only the selected members, then token_probs(), would leave it, bit for bit; the others are not
+        touched.  The agents' speculative <|end_audio|> step: roll back with member.n_tokens -= n afterwards.  A refusal raises and
+        leaves every member as it was."""
+        sel = [int(s) for s in members]
+        if not sel or any(s < 0 or s >= len(self.members) for s in sel):
+            raise N.RcaError(f"members {sel}: 1 to {len(self.members)} indices inside the batch's members")
+        nm = len(sel)
+        rows = [[int(t) for t in r] for r in tokens_per_member]
+        if len(rows) != nm:
+            raise ValueError(f"{len(rows)} token lists for {nm} members")
+        n = len(rows[0])
+        if any(len(r) != n for r in rows):
+            raise ValueError("every member evaluates the same number of tokens in a batch step")
+        probes = None if probe_ids_per_member is None else [[int(p) for p in r] for r in probe_ids_per_member]
+        n_probe = 0
+        if probes is not None:
+            if len(probes) != nm:
+                raise ValueError(f"{len(probes)} probe id lists for {nm} members")
+            n_probe = len(probes[0])
+            if any(len(r) != n_probe for r in probes):
+                raise ValueError("every member probes the same number of ids in a batch step")
+        taking = [self.members[s] for s in sel]
+        starts = [m.n_tokens for m in taking]
+        sl = (C.c_int32 * nm)(*sel)
+        arr = (C.c_int32 * max(nm * n, 1))(*[t for r in rows for t in r])
+        pid = (C.c_int32 * (nm * n_probe))(*[p for r in probes for p in r]) if n_probe else None
+        out = (C.c_int32 * nm)()
+        pp = (C.c_float * (nm * n_probe))() if n_probe else None
+        N.check(self._lib.rca_lm_batch_step_sel(self._b, sl, nm, arr, n, pid, n_probe, out, pp), "rca_lm_batch_step_sel")
+        for m, n0, r in zip(taking, starts, rows):
+            m._input_ids[n0:n0 + n] = r
+            m._logits_valid = False
+        toks = [int(t) for t in out]
+        if not n_probe:
+            return toks, None
+        return toks, np.array(pp[:], dtype=np.float32).reshape(nm, n_probe)
 
     def duplex_frame(self, codec_handle, members: Sequence[int], pcm_windows, code_ctxs, n_steps: int, n_samples: int, code_token_base: int,
                      audio_id_floor: int, probe_ids: Optional[Sequence[int]], first_pairs: Sequence[Sequence[int]]) -> List[dict]:

@@ -9,19 +9,29 @@ LlamaBatch.duplex_frame (rca_duplex_batch_frame); every other session with a chu
 A batch frame is in the tile arithmetic class (LlamaBatch): a session inside the batch samples other tokens than the same session
 alone -- equally valid ones; with use_duplex_batch_graph=False the ready group runs the same LM arithmetic through the separate calls
 (tokenize_audio, one LlamaBatch.frame(members=...), detokenize_output_chunk), so the two can be compared, as use_duplex_graph does for
-one session.  Not thread-safe: one caller per tick."""
+one session.
+
+batch_speaker_step=True (off by default) also batches the agents' speculative <|end_audio|> step: the fused members of a tick commit
+with the step deferred, and those that owe it (z-score of P(<|end_audio|>) >= 0) take ONE LlamaBatch.step_probe
+(rca_lm_batch_step_sel) when there are at least min_batch of them, else their own single steps.  That moves the two speaker
+probabilities and the step's throw-away draw into the tile arithmetic class too.  Not thread-safe: one caller per tick."""
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
 
 class RealtimeAgentBatch:
-    def __init__(self, agents: Sequence, min_batch: int = 4, use_duplex_batch_graph: bool = True):
+    def __init__(self, agents: Sequence, min_batch: int = 4, use_duplex_batch_graph: bool = True, batch_speaker_step: bool = False):
         self.agents = list(agents)
-        self.min_batch = max(1, int(min_batch))     # where one batch call starts to win over as many single frames: 4, the smallest size measured (profiles/r16)
+        # where one batch call starts to win over as many single calls: 4, the smallest size measured, for the frame (profiles/r16:
+        # 11.0 against 13.8 ms) and for the speaker step (profiles/r18: 2.64 against 3.29 ms; three single steps are 2.5 ms)
+        self.min_batch = max(1, int(min_batch))
         self.use_duplex_batch_graph = bool(use_duplex_batch_graph)
         self.fused_ticks = 0       # ticks in which at least one group took the batch call
         self.fused_frames = 0      # agent frames that went through it
+        self.batch_speaker_step = bool(batch_speaker_step)
+        self.fused_speaker_calls = 0   # batch step_probe calls for the speculative <|end_audio|> step
+        self.fused_speaker_steps = 0   # agents' speculative steps that went through them
         self._batch = None
         if len(self.agents) < 2:
             raise ValueError("a RealtimeAgentBatch drives at least two agents")
@@ -79,6 +89,8 @@ class RealtimeAgentBatch:
         for i in live:
             if i not in fused:
                 outs[i] = self.agents[i].process_audio(chunks[i])     # settles and advances its own shadow cache
+        if self.batch_speaker_step:
+            self._run_speaker_steps(sorted(fused))
         for i in sorted(fused):
             self.agents[i]._advance_shadow()
         if groups:
@@ -86,8 +98,28 @@ class RealtimeAgentBatch:
             self.fused_frames += len(fused)
         return outs
 
+    def _run_speaker_steps(self, fused: List[int]) -> None:
+        """The speculative <|end_audio|> steps the fused members of this tick deferred (across groups): one batch step_probe for at
+        least min_batch of them, rolled back by one position per member; fewer take their own step."""
+        A = self.agents
+        owed = [i for i in fused if A[i].speaker_step_owed]
+        for i in owed:
+            A[i].speaker_step_owed = False
+        if len(owed) < self.min_batch:
+            for i in owed:
+                A[i].prob_event_speaker_token_id = A[i].get_probable_event_speaker()
+            return
+        _, probs = self._batch.step_probe(owed, [[A[i].end_audio_token_id] for i in owed],
+                                          [[A[i].agent_speaker_token_id, A[i].user_speaker_token_id] for i in owed])
+        for (pa, pu), i in zip(probs, owed):
+            A[i].resources.llm.n_tokens -= 1
+            A[i]._set_probable_event_speaker(pa, pu)
+        self.fused_speaker_calls += 1
+        self.fused_speaker_steps += len(owed)
+
     def _run_group(self, sel: List[int], chunks, plans, outs) -> None:
         A = self.agents
+        defer = self.batch_speaker_step
         first, p0 = A[sel[0]], plans[sel[0]]
         pairs = [A[i].input_ids[-2:] for i in sel]
         probes = [first.end_audio_token_id] * len(sel)
@@ -98,7 +130,7 @@ class RealtimeAgentBatch:
             for k, i in enumerate(sel):
                 a = A[i]
                 with a.profilers.total_profiler:
-                    out = a._replay_commit(chunks[i], plans[i], lambda r=res[k]: r)
+                    out = a._replay_commit(chunks[i], plans[i], lambda r=res[k]: r, defer_speaker=defer)
                 outs[i] = out if a.self_play_mode else out[0]
             return
         # the unfused path: the separate codec calls around ONE selection frame
@@ -118,7 +150,7 @@ class RealtimeAgentBatch:
                     out_ids = a.process_audio_input_ids(user_ids[k], pre=toks[k])
                 out_chunk = a.detokenize_output_chunk(out_ids)
                 a.audio_history_ch2.append(chunks[i])
-                a.measure_event_prob(None if np.isnan(probs[k]) else float(probs[k]))
+                a.measure_event_prob(None if np.isnan(probs[k]) else float(probs[k]), defer_speaker=defer)
                 a.update_inactivity_timers()
             outs[i] = (out_chunk, out_ids) if a.self_play_mode else out_chunk
 
