@@ -5813,17 +5813,19 @@ extern "C" int rca_lm_group_step(rca_lm_group_t* g, const int32_t* ids, int32_t 
 // bit-for-bit promise against rca_lm_step; a row's result does not depend on its slot or its companions.
 #define LM_BATCH_MAX 64
 #define LM_BATCH_ROWS 128   // one token block
-struct LmBatchStage { int n_tokens[LM_BATCH_MAX]; int ids[LM_BATCH_ROWS]; };
-// rca_lm_batch_frame: the step's block (the first pairs in ids), then the user's token of every step and the probe id of every member
+// One staging block serves every call; each struct below is the head of the next, and a call uploads the head it needs.
+// A step: the live count (the members of the pass, in slots 0 .. n_live - 1), their positions and their ids.
+struct LmBatchStage { int n_live; int n_tokens[LM_BATCH_MAX]; int ids[LM_BATCH_ROWS]; };
+// A frame: the step's block (the first pairs in ids), then the user's token of every step and the probe id of every member
 struct LmBatchFrameStage : LmBatchStage { int user[LM_BATCH_MAX * LM_FRAME_MAX]; int probe[LM_BATCH_MAX]; };
 struct LmBatchFrameOut { int tokens[LM_BATCH_MAX * LM_FRAME_MAX]; float probs[LM_BATCH_MAX]; };
-struct LmBatchPin { LmBatchFrameStage in; int tokens[LM_BATCH_MAX]; LmBatchFrameOut frame; };
-// rca_lm_batch_frame_sel: the frame's block over the SELECTED members in slots 0 .. n_live - 1, and the two tables of exactly those
-// slots, composed on the host for every call and uploaded as one block inside the replay: a graph over them holds no member's pointer
+// A selection (rca_lm_batch_frame_sel, rca_duplex_batch_frame): the frame's block over the SELECTED members, and the two tables of
+// exactly those slots, composed on the host for every call and uploaded as one block inside the replay: a graph over them holds no
+// member's pointer
 #define LM_BATCH_CLASSES 4   // launch geometries: 8, 16, 32 or 64 slots
-struct LmBatchSelStage { LmBatchFrameStage in; int n_live; int pad; LmBatchMember tab[LM_BATCH_MAX]; LmGroupRow rows[LM_BATCH_ROWS]; };
+struct LmBatchSelStage : LmBatchFrameStage { LmBatchMember tab[LM_BATCH_MAX]; LmGroupRow rows[LM_BATCH_ROWS]; };
 // rca_lm_batch_step_sel: the selection's block with the step's probe ids behind it (a frame uploads the LmBatchSelStage head only), and
-// what the step gathers for its one download
+// what a step gathers for its one download (rca_lm_batch_step: the tokens only)
 #define LM_STEP_PROBES 8
 struct LmBatchStepSelStage : LmBatchSelStage { int n_probe; int pad2; int probe_ids[LM_BATCH_MAX * LM_STEP_PROBES]; };   // probe_ids[k * n_probe + i]
 struct LmBatchStepSelOut { int tokens[LM_BATCH_MAX]; float probs[LM_BATCH_MAX * LM_STEP_PROBES]; };                    // probs[k * n_probe + i]
@@ -5840,50 +5842,30 @@ struct rca_lm_batch {
     LmDevState* stt = nullptr;        // device: the pass over all rows (m = n_members * n, the rows' ids)
     LmDevState* stt_head = nullptr;   // device: the head's pass (m = n_members)
     float* head_blk = nullptr;        // device, [n_members][V]: the head GEMM's block
-    LmBatchFrameStage* stage = nullptr;   // device copy of pin->in (a step uploads its LmBatchStage head only)
-    int* tokens = nullptr;            // device: the members' sampled tokens, gathered for one download
-    LmBatchPin* pin = nullptr;        // pinned
+    LmBatchStepSelStage* sel_stage = nullptr;   // device copy of sel_pin (a call uploads the head it needs)
+    LmBatchStepSelStage* sel_pin = nullptr;     // pinned: every call's staging block
     hipGraphExec_t g[LM_GEMV_M][LM_GRAPH_BUCKETS] = {};   // (n, largest context bucket among the members)
-    // rca_lm_batch_frame
+    // the frames
     LmBatchFrameOut* frame_out = nullptr;   // device: every step's tokens and the probes, gathered for one download
+    LmBatchFrameOut* frame_pin = nullptr;   // pinned
     float* probe_part = nullptr;            // device, [n_members][PROBS_SLICES (max, sum) pairs]
     hipGraphExec_t fg[LM_FRAME_MAX][LM_GRAPH_BUCKETS][2] = {};   // (n_steps - 1, largest context bucket at the frame's end, probes)
     // rca_lm_batch_frame_sel
-    LmBatchStepSelStage* sel_stage = nullptr;   // device copy of sel_pin
-    LmBatchStepSelStage* sel_pin = nullptr;     // pinned
-    int nsp_all = 1;                        // the largest split count among ALL members: a selection graph's attention grid
+    int nsp_all = 1;                        // the largest split count among ALL members: a graph's attention grid
     unsigned long long sel_epoch = 0;       // sum of the members' drop_epoch the graphs below were captured under
     hipGraphExec_t sg[LM_BATCH_CLASSES][LM_FRAME_MAX][LM_GRAPH_BUCKETS][2][2] = {};   // (class, n_steps - 1, bucket, probes, a patching sampler among them)
     long long n_captures = 0;               // rca_lm_batch_captures
     struct LmBatchDuplex* dx = nullptr;     // rca_duplex_batch_frame: buffers, pinned staging and graphs (made by its first call)
-    // rca_lm_batch_step_sel
-    LmBatchStepSelOut* step_out = nullptr;      // device: the selected members' tokens and probabilities, gathered for one download
+    // the steps
+    LmBatchStepSelOut* step_out = nullptr;      // device: the members' tokens and probe probabilities, gathered for one download
     LmBatchStepSelOut* step_out_pin = nullptr;  // pinned
     hipGraphExec_t ssg[LM_BATCH_CLASSES][LM_GEMV_M][LM_GRAPH_BUCKETS][2][2] = {};   // (class, n - 1, bucket, probes, a patching sampler among them)
 };
-// the pass's state and the selected members' step states from a selection's block; the live count comes from the block, not the launch
-__device__ __forceinline__ void lm_batch_sel_stage_body(const LmBatchSelStage* __restrict__ in, LmDevState* __restrict__ bstt, LmDevState* __restrict__ hstt, int n) {
-    const int t = threadIdx.x, nl = in->n_live;
-    if (t == 0) { bstt->n_tokens = 0; bstt->m = nl * n; hstt->n_tokens = 0; hstt->m = nl; }
-    if (t < nl * n) bstt->ids[t] = in->in.ids[t];
-    if (t < nl) {
-        LmDevState* stt = in->tab[t].stt;
-        stt->n_tokens = in->in.n_tokens[t];
-        stt->m = n;
-        for (int j = 0; j < n; ++j) stt->ids[j] = in->in.ids[t * n + j];
-    }
-}
-__global__ void lm_batch_sel_stage_kernel(const LmBatchSelStage* __restrict__ in, LmDevState* __restrict__ bstt, LmDevState* __restrict__ hstt) {
-    lm_batch_sel_stage_body(in, bstt, hstt, 2);
-}
-// the same for a selection step of n tokens per member (rca_lm_batch_step_sel)
-__global__ void lm_batch_sel_stage_n_kernel(const LmBatchSelStage* __restrict__ in, LmDevState* __restrict__ bstt, LmDevState* __restrict__ hstt, int n) {
-    lm_batch_sel_stage_body(in, bstt, hstt, n);
-}
-// the pass's state and the members' step states, from one staging block
+// the pass's state and the members' step states from the staging block, for n tokens per member; `tab` is the table of the pass (the
+// batch's own, or the block's).  The live count comes from the block, not the launch: a graph serves every selection of its class.
 __global__ void lm_batch_stage_kernel(const LmBatchStage* __restrict__ in, const LmBatchMember* __restrict__ tab, LmDevState* __restrict__ bstt,
-                                      LmDevState* __restrict__ hstt, int n_members, int n) {
-    const int t = threadIdx.x;
+                                      LmDevState* __restrict__ hstt, int n) {
+    const int t = threadIdx.x, n_members = in->n_live;
     if (t == 0) { bstt->n_tokens = 0; bstt->m = n_members * n; hstt->n_tokens = 0; hstt->m = n_members; }
     if (t < n_members * n) bstt->ids[t] = in->ids[t];
     if (t < n_members) {
@@ -6022,19 +6004,16 @@ extern "C" int rca_lm_batch_create(rca_lm_t* const* members, int32_t n_members, 
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->stt_head, sizeof(LmDevState));
     const int n_slots = 8 << lm_batch_class(n_members);   // a selection frame launches at its class's slot count
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->head_blk, (size_t)n_slots * members[0]->cfg.vocab_size * 4);
-    if (rc == RCA_OK) rc = lm_alloc((void**)&b->stage, sizeof(LmBatchFrameStage));
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->frame_out, sizeof(LmBatchFrameOut));
+    if (rc == RCA_OK && hipHostMalloc((void**)&b->frame_pin, sizeof(LmBatchFrameOut), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->probe_part, sizeof(float) * 2 * PROBS_SLICES * n_slots);
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->sel_stage, sizeof(LmBatchStepSelStage));
     if (rc == RCA_OK && hipHostMalloc((void**)&b->sel_pin, sizeof(LmBatchStepSelStage), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
     if (rc == RCA_OK) rc = lm_alloc((void**)&b->step_out, sizeof(LmBatchStepSelOut));
     if (rc == RCA_OK && hipHostMalloc((void**)&b->step_out_pin, sizeof(LmBatchStepSelOut), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
-    if (rc == RCA_OK) rc = lm_alloc((void**)&b->tokens, sizeof(int) * LM_BATCH_MAX);
-    if (rc == RCA_OK && hipHostMalloc((void**)&b->pin, sizeof(LmBatchPin), hipHostMallocDefault) != hipSuccess) rc = fail(RCA_ERR_HIP, "batch_create: pinned staging");
     if (rc == RCA_OK && (hipMemset(b->stt, 0, sizeof(LmDevState)) != hipSuccess || hipMemset(b->stt_head, 0, sizeof(LmDevState)) != hipSuccess))
         rc = fail(RCA_ERR_HIP, "batch_create: clearing the pass states");
     if (rc != RCA_OK) { rca_lm_batch_destroy(b); return rc; }
-    memset(b->pin, 0, sizeof(LmBatchPin));
     memset(b->sel_pin, 0, sizeof(LmBatchStepSelStage));
     for (int s = 0; s < n_members; ++s) b->nsp_all = std::max(b->nsp_all, members[s]->n_splits);
     *out = b;
@@ -6045,10 +6024,10 @@ extern "C" int rca_lm_batch_destroy(rca_lm_batch_t* b) {
     lm_batch_drop_graphs(b);
     lm_batch_drop_sel_graphs(b);
     lm_batch_duplex_destroy(b->dx);
-    for (void* p : {(void*)b->rows, (void*)b->tab, (void*)b->stt, (void*)b->stt_head, (void*)b->head_blk, (void*)b->stage, (void*)b->tokens, (void*)b->frame_out,
-                    (void*)b->probe_part, (void*)b->sel_stage, (void*)b->step_out})
+    for (void* p : {(void*)b->rows, (void*)b->tab, (void*)b->stt, (void*)b->stt_head, (void*)b->head_blk, (void*)b->frame_out, (void*)b->probe_part,
+                    (void*)b->sel_stage, (void*)b->step_out})
         if (p) (void)hipFree(p);
-    if (b->pin) (void)hipHostFree(b->pin);
+    if (b->frame_pin) (void)hipHostFree(b->frame_pin);
     if (b->sel_pin) (void)hipHostFree(b->sel_pin);
     if (b->step_out_pin) (void)hipHostFree(b->step_out_pin);
     delete b;
@@ -6060,9 +6039,6 @@ static int lm_batch_refresh(rca_lm_batch* b) {
     for (int s = 0; s < b->n_members; ++s) same = same && b->epoch[s] == b->m[s]->graph_epoch;
     if (same) return RCA_OK;
     lm_batch_drop_graphs(b);
-    for (int s = 1; s < b->n_members; ++s)
-        if (b->m[s]->kv_format != b->m[0]->kv_format)
-            return fail(RCA_ERR_STATE, "batch: member %d has KV format %d, member 0 has %d", s, b->m[s]->kv_format, b->m[0]->kv_format);
     std::vector<LmGroupRow> rows((size_t)LM_GEMV_M * LM_BATCH_ROWS);
     std::vector<LmBatchMember> tab((size_t)LM_GEMV_M * LM_BATCH_MAX);
     memset(rows.data(), 0, rows.size() * sizeof(LmGroupRow));
@@ -6129,7 +6105,7 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
             launch_gemm128<GEMM_EPI_ROPE_ROWS>(ws, w, dim3(Ns / 128, fq.grid_y, 1), st, ws->xh, ws->xl, Ns, H, H / ss, ws->qkv, QKV, nullptr, nullptr, rope, fq.nseq, bs, grp);
             if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE_ROWS><<<dim3(Ns / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fq.ep_nsplit, fq.ep_grp, Ns, ws->qkv, QKV, nullptr, nullptr, rope, grp);
         }
-        const bool q8kv = lm_kv_q8(ws);   // every member's format (rca_lm_batch_create, lm_batch_member_ok)
+        const bool q8kv = lm_kv_q8(ws);   // every member's format (rca_lm_batch_create, lm_batch_check)
         if (q8kv)   // every member's new rows, ring -> int8 planes, in one launch
             lm_kv_quant_kernel<true><<<dim3(cdiv(4 * c.n_kv_heads, 8), n, NM), 256, 0, st>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, c.n_kv_heads, 0, 0, 0, 3, tab, l);
 #define RCA_BATCH_ATTN(GG)                                                                                                            \
@@ -6171,198 +6147,15 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
 static LmBatchView lm_batch_view(rca_lm_batch* b, int n) {
     return LmBatchView{b->rows + (size_t)(n - 1) * LM_BATCH_ROWS, b->tab + (size_t)(n - 1) * LM_BATCH_MAX, b->n_members, b->any_serial, b->any_patch, b->m, b->n_members};
 }
-// upload of the staged states -> the pass -> download of the tokens, all on `st`, one linear sequence
-static int lm_batch_enqueue(rca_lm_batch* b, int n, int nsp_launch, hipStream_t st) {
-    const LmBatchMember* tab = b->tab + (size_t)(n - 1) * LM_BATCH_MAX;
-    const int NM = b->n_members;
-    hipError_t e = hipMemcpyAsync(b->stage, static_cast<const LmBatchStage*>(&b->pin->in), sizeof(LmBatchStage), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch step upload: %s", hipGetErrorString(e));
-    lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->stage, tab, b->stt, b->stt_head, NM, n);
-    lm_batch_enqueue_pass(b, lm_batch_view(b, n), n, nsp_launch, st);
-    lm_batch_tokens_kernel<<<1, LM_BATCH_MAX, 0, st>>>(tab, NM, b->tokens);
-    RCA_LAUNCH_CHECK();
-    e = hipMemcpyAsync(b->pin->tokens, b->tokens, sizeof(int) * LM_BATCH_MAX, hipMemcpyDeviceToHost, st);
-    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch step download: %s", hipGetErrorString(e));
-}
-// what a step and a frame refuse alike about member s (`who` starts the message), before anything is staged
-static int lm_batch_member_ok(const rca_lm* h, int s, const char* who) {
-    if (!h->sampler_set) return fail(RCA_ERR_STATE, "%s: member %d has no sampler (rca_lm_sampler_init)", who, s);
-    if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "%s: member %d was switched to logits_all after the batch was made", who, s);
-    if (lm_prefill_route(h) != LM_ROUTE_TILE128) return fail(RCA_ERR_STATE, "%s: member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", who, s, lm_prefill_route(h));
-    return RCA_OK;
-}
-extern "C" int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t n, int32_t* tokens) {
-    if (!b || !ids || !tokens) return fail(RCA_ERR_ARG, "batch_step: null argument");
-    const int NM = b->n_members;
-    if (n < 1 || n > LM_GEMV_M) return fail(RCA_ERR_ARG, "batch_step: %d tokens per member (1..%d)", n, LM_GEMV_M);
-    if (NM * n > LM_BATCH_ROWS) return fail(RCA_ERR_ARG, "batch_step: %d members x %d tokens = %d rows, a batch pass is one token block of %d", NM, n, NM * n, LM_BATCH_ROWS);
-    int rc;
-    for (int s = 0; s < NM; ++s)
-        if ((rc = lm_settle(b->m[s])) != RCA_OK) return rc;
-    // every refusal before anything is staged or enqueued: no member changes
-    for (int s = 0; s < NM; ++s) {
-        const rca_lm* h = b->m[s];
-        if ((rc = lm_batch_member_ok(h, s, "batch_step")) != RCA_OK) return rc;
-        if (h->n_tokens + n > h->cfg.n_ctx) return fail(RCA_ERR_STATE, "batch_step: context overflow of member %d: %d + %d > n_ctx %d", s, h->n_tokens, n, h->cfg.n_ctx);
-        for (int j = 0; j < n; ++j)
-            if (ids[s * n + j] < 0 || ids[s * n + j] >= h->cfg.vocab_size)
-                return fail(RCA_ERR_ARG, "batch_step: token id %d of member %d at index %d is outside the vocabulary [0, %d)", ids[s * n + j], s, j, h->cfg.vocab_size);
-    }
-    RCA_HIP(hipSetDevice(b->m[0]->device));
-    hipStream_t st = b->m[0]->stream;
-    if ((rc = lm_batch_refresh(b)) != RCA_OK) return rc;
-    bool graphs = true;
-    int bucket = 0, nsp = 1, nsp_max = 1;
-    for (int s = 0; s < NM; ++s) {
-        const rca_lm* h = b->m[s];
-        graphs = graphs && h->graphs_enabled;
-        b->pin->in.n_tokens[s] = h->n_tokens;
-        for (int j = 0; j < n; ++j) b->pin->in.ids[s * n + j] = ids[s * n + j];
-        bucket = std::max(bucket, lm_bucket(h, n, -1).bucket);
-        nsp = std::max(nsp, lm_splits_needed(h, n));
-        nsp_max = std::max(nsp_max, h->n_splits);
-    }
-    if (graphs) {
-        // the split count of the largest bucket among the members (a split past a member's cache leaves at once)
-        const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? nsp_max : std::min(nsp_max, 4 << bucket);
-        hipGraphExec_t& gexec = b->g[n - 1][bucket];
-        if (!gexec) {
-            if ((rc = lm_capture(st, &gexec, "batch step", [&]() -> int { return lm_batch_enqueue(b, n, nsp_bucket, st); })) != RCA_OK) return rc;
-            b->n_captures++;
-        }
-        RCA_HIP(hipGraphLaunch(gexec, st));
-    } else if ((rc = lm_batch_enqueue(b, n, nsp, st)) != RCA_OK) {
-        return rc;
-    }
-    RCA_HIP(hipStreamSynchronize(st));
-    for (int s = 0; s < NM; ++s) {
-        rca_lm* h = b->m[s];
-        h->n_tokens += n;
-        h->logits_rows = 1;
-        h->rng_host += 1;
-        tokens[s] = b->pin->tokens[s];
-    }
-    return RCA_OK;
-}
 
-// ------------------------------------------------------------------------------------ batch frame (rca_lm_batch_frame)
-// rca_lm_frame for every member of a batch in one launch sequence: n_steps times the batch pass over pairs (lm_batch_enqueue_pass, the
-// launches of a 2-token batch step) with lm_batch_feedback_kernel between them, then the probes.  Every member runs every step -- a
-// row cannot leave a captured graph -- and the host settles afterwards which steps of a member stand, as lm_frame_core does for one.
-static int lm_batch_frame_enqueue(rca_lm_batch* b, int n_steps, int nsp_launch, bool probes, hipStream_t st) {
-    const LmBatchMember* tab = b->tab + (size_t)(2 - 1) * LM_BATCH_MAX;
-    const int NM = b->n_members, V = b->m[0]->cfg.vocab_size;
-    hipError_t e = hipMemcpyAsync(b->stage, &b->pin->in, sizeof(LmBatchFrameStage), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch frame upload: %s", hipGetErrorString(e));
-    lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->stage, tab, b->stt, b->stt_head, NM, 2);
-    for (int i = 0; i < n_steps; ++i) {
-        lm_batch_enqueue_pass(b, lm_batch_view(b, 2), 2, nsp_launch, st);
-        lm_batch_feedback_kernel<<<1, LM_BATCH_MAX, 0, st>>>(b->stage, tab, b->stt, b->frame_out, NM, i);
-    }
-    if (probes) {
-        lm_softmax_slices_batch_kernel<<<dim3(PROBS_SLICES, NM), 1024, 0, st>>>(tab, V, b->probe_part);
-        lm_token_probs_batch_kernel<<<dim3(1, NM), 64, 0, st>>>(tab, V, b->probe_part, b->stage->probe, b->frame_out->probs);
-    }
-    RCA_LAUNCH_CHECK();
-    e = hipMemcpyAsync(&b->pin->frame, b->frame_out, sizeof(LmBatchFrameOut), hipMemcpyDeviceToHost, st);
-    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch frame download: %s", hipGetErrorString(e));
-}
-extern "C" int rca_lm_batch_frame(rca_lm_batch_t* b, const int32_t* first_pairs, const int32_t* user_ids, int32_t n_steps, int32_t audio_id_floor,
-                                  const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done, float* probe_probs) {
-    if (!b || !first_pairs || !user_ids || !out_tokens || !n_done) return fail(RCA_ERR_ARG, "batch_frame: null argument");
-    if (probe_ids && !probe_probs) return fail(RCA_ERR_ARG, "batch_frame: probe_ids without probe_probs");
-    const int NM = b->n_members;
-    if (n_steps < 1 || n_steps > LM_FRAME_MAX) return fail(RCA_ERR_ARG, "batch_frame: %d steps (1..%d)", n_steps, LM_FRAME_MAX);
-    if (NM * 2 > LM_BATCH_ROWS) return fail(RCA_ERR_ARG, "batch_frame: %d members x 2 tokens = %d rows, a batch pass is one token block of %d", NM, NM * 2, LM_BATCH_ROWS);
-    int rc;
-    for (int s = 0; s < NM; ++s)
-        if ((rc = lm_settle(b->m[s])) != RCA_OK) return rc;
-    // every refusal before anything is staged or enqueued: no member changes
-    for (int s = 0; s < NM; ++s) {
-        const rca_lm* h = b->m[s];
-        const int V = h->cfg.vocab_size;
-        if ((rc = lm_batch_member_ok(h, s, "batch_frame")) != RCA_OK) return rc;
-        if (h->n_tokens + 2 * n_steps > h->cfg.n_ctx)
-            return fail(RCA_ERR_STATE, "batch_frame: context overflow of member %d: %d + %d > n_ctx %d", s, h->n_tokens, 2 * n_steps, h->cfg.n_ctx);
-        for (int j = 0; j < 2; ++j)
-            if (first_pairs[s * 2 + j] < 0 || first_pairs[s * 2 + j] >= V)
-                return fail(RCA_ERR_ARG, "batch_frame: token id %d of member %d at index %d of its first pair is outside the vocabulary [0, %d)", first_pairs[s * 2 + j], s, j, V);
-        for (int i = 0; i < n_steps; ++i)
-            if (user_ids[s * n_steps + i] < 0 || user_ids[s * n_steps + i] >= V)
-                return fail(RCA_ERR_ARG, "batch_frame: user token id %d of member %d at step %d is outside the vocabulary [0, %d)", user_ids[s * n_steps + i], s, i, V);
-        if (probe_ids && (probe_ids[s] < -1 || probe_ids[s] >= V))
-            return fail(RCA_ERR_ARG, "batch_frame: probe id %d of member %d is outside the vocabulary [0, %d) (-1: no probe)", probe_ids[s], s, V);
-    }
-    RCA_HIP(hipSetDevice(b->m[0]->device));
-    hipStream_t st = b->m[0]->stream;
-    if ((rc = lm_batch_refresh(b)) != RCA_OK) return rc;
-    const bool probes = probe_ids != nullptr;
-    bool graphs = true;
-    int bucket = 0, nsp = 1, nsp_max = 1;
-    LmBatchFrameStage& in = b->pin->in;
-    for (int s = 0; s < NM; ++s) {
-        const rca_lm* h = b->m[s];
-        graphs = graphs && h->graphs_enabled;
-        in.n_tokens[s] = h->n_tokens;
-        for (int j = 0; j < 2; ++j) in.ids[s * 2 + j] = first_pairs[s * 2 + j];
-        for (int i = 0; i < LM_FRAME_MAX; ++i) in.user[s * LM_FRAME_MAX + i] = i < n_steps ? user_ids[s * n_steps + i] : 0;
-        in.probe[s] = probes ? probe_ids[s] : -1;
-        // the bucket and the splits of the frame's END (as lm_frame_core): a frame that crosses a bucket or a 256-key split inside
-        // itself has the splits its last step needs; its earlier steps leave the extra ones at once
-        bucket = std::max(bucket, lm_bucket(h, 2 * n_steps, -1).bucket);
-        nsp = std::max(nsp, lm_splits_needed(h, 2 * n_steps));
-        nsp_max = std::max(nsp_max, h->n_splits);
-    }
-    if (graphs) {
-        const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? nsp_max : std::min(nsp_max, 4 << bucket);
-        hipGraphExec_t& gexec = b->fg[n_steps - 1][bucket][probes ? 1 : 0];
-        if (!gexec) {
-            if ((rc = lm_capture(st, &gexec, "batch frame", [&]() -> int { return lm_batch_frame_enqueue(b, n_steps, nsp_bucket, probes, st); })) != RCA_OK) return rc;
-            b->n_captures++;
-        }
-        RCA_HIP(hipGraphLaunch(gexec, st));
-    } else if ((rc = lm_batch_frame_enqueue(b, n_steps, nsp, probes, st)) != RCA_OK) {
-        return rc;
-    }
-    RCA_HIP(hipStreamSynchronize(st));
-    const LmBatchFrameOut& out = b->pin->frame;
-    LmBatchCuts cuts;
-    cuts.n = 0;
-    for (int s = 0; s < NM; ++s) {
-        rca_lm* h = b->m[s];
-        int done = n_steps;
-        for (int i = 0; i < n_steps; ++i) {
-            out_tokens[s * n_steps + i] = out.tokens[s * LM_FRAME_MAX + i];
-            if (out_tokens[s * n_steps + i] <= audio_id_floor) { done = i + 1; break; }
-        }
-        for (int i = done; i < n_steps; ++i) out_tokens[s * n_steps + i] = -1;
-        n_done[s] = done;
-        h->n_tokens += 2 * done;
-        // a member cut short holds the logits of a LATER step (evaluated on a wrong-guess pair): nothing may read them
-        h->logits_rows = done < n_steps ? 0 : 1;
-        h->rng_host += (unsigned long long)done;
-        if (done < n_steps) {
-            cuts.member[cuts.n] = s;
-            cuts.counter[cuts.n++] = h->rng_host;
-        }
-        if (probes) probe_probs[s] = done < n_steps || probe_ids[s] < 0 ? -1.0f : out.probs[s];
-    }
-    if (cuts.n) {   // the device drew n_steps times for these: their counters go where the step-by-step loop would be, in one launch
-        lm_batch_counters_kernel<<<1, LM_BATCH_MAX, 0, st>>>(b->tab + (size_t)(2 - 1) * LM_BATCH_MAX, cuts);
-        RCA_LAUNCH_CHECK();
-        RCA_HIP(hipStreamSynchronize(st));
-    }
-    return RCA_OK;
-}
-
-// ------------------------------------------------------------------------------------ selection frame (rca_lm_batch_frame_sel)
-// rca_lm_batch_frame over a SUBSET of the members: sessions sit ticks out (windows still filling, a forced branch, a trim between two
-// steps, a chunk that has not arrived).  The selected members are compacted into slots 0 .. n_sel - 1 of tables composed on the host
-// for THIS call (LmBatchSelStage) and uploaded with the frame's block inside the replay; the launches cover the selection's geometry
-// class (8, 16, 32 or 64 slots).  The live count travels in the block: the row-wise kernels leave on the pass state's m, the table
-// kernels on the all-zero entry of a slot past it.  So a graph holds no member's pointer -- only member 0's workspace and weights --
-// and is keyed by (class, n_steps, bucket, probes, patching samplers): it serves every selection of its class and outlives a member's
-// rca_lm_swap_kv.  An unselected member is not read on the device and not written anywhere.
+// ------------------------------------------------------------------------------------ the batch calls' host sequence
+// rca_lm_batch_step, _frame, _frame_sel, _step_sel and rca_duplex_batch_frame are one sequence on the host: describe the call
+// (LmBatchCall) -> refuse (lm_batch_check) -> fill the pinned block and plan the launches (lm_batch_stage) -> capture / replay or run
+// eagerly (lm_batch_run over lm_batch_enqueue) -> settle.  Two things differ between them.  Where a pass's tables come from: the
+// batch's resident ones, every member in its own slot at exact n_members geometry, refreshed under the members' graph_epoch -- or the
+// call's own block, the selected members in slots 0 .. n_sel - 1 at the geometry of the selection's class, the live count in the block.
+// And what runs between upload and download: one pass of n tokens per member, or n_steps pairs with feedback; the codec tails of a
+// duplex call go around either.
 // (grows a device buffer of rca_duplex_frame / rca_duplex_batch_frame; the old contents are not kept)
 template <class T>
 static int duplex_grow(T** p, size_t* cap, size_t n) {
@@ -6407,7 +6200,7 @@ __global__ void duplex_batch_codes_to_ids_kernel(const long long* __restrict__ c
     const int k = blockIdx.x, i = threadIdx.x;
     if (k >= stage->n_live) return;
     if (i == 0) flags[k] = 0;
-    if (i < n) stage->in.user[k * LM_FRAME_MAX + i] = base + (int)codes[(long)k * n + i];
+    if (i < n) stage->user[k * LM_FRAME_MAX + i] = base + (int)codes[(long)k * n + i];
 }
 // ids -> codes, table form: every live slot's sampled tokens of the frame go behind its row's context codes; a token that is no codec
 // token becomes code 0 and raises the slot's flag bit 0
@@ -6435,67 +6228,73 @@ static void lm_batch_duplex_destroy(LmBatchDuplex* d) {
     delete d;
 }
 
-// upload -> stage -> [encode tails -> codes to ids] -> n_steps x (pass, feedback) -> [ids to codes -> decode tails] -> probes -> download,
-// one linear sequence on `st`; the bracketed parts with a duplex call only
-static int lm_batch_sel_enqueue(rca_lm_batch* b, const LmBatchView& vw, int n_steps, int nsp_launch, bool probes, hipStream_t st,
-                                const LmBatchDuplexCall* dc = nullptr) {
-    const int V = b->m[0]->cfg.vocab_size;
-    LmBatchDuplex* d = b->dx;
-    hipError_t e = hipMemcpyAsync(b->sel_stage, b->sel_pin, sizeof(LmBatchSelStage), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pcm_in, d->pin + dc->pin_pcm, (size_t)dc->slots * dc->T * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->code_win, d->pin + dc->pin_codes, (size_t)dc->slots * (dc->F_ctx + n_steps) * 8, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch frame_sel upload: %s", hipGetErrorString(e));
-    lm_batch_sel_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->sel_stage, b->stt, b->stt_head);
-    if (dc) {
-        const int r = rca_codec_encode_tail_dev(dc->codec, d->pcm_in, dc->slots, dc->T, n_steps, (int64_t*)d->dev->user_codes, st);
-        if (r != RCA_OK) return r;
-        duplex_batch_codes_to_ids_kernel<<<dc->slots, 64, 0, st>>>(d->dev->user_codes, n_steps, dc->base, b->sel_stage, d->dev->flags);
-    }
-    for (int i = 0; i < n_steps; ++i) {
-        lm_batch_enqueue_pass(b, vw, 2, nsp_launch, st);
-        lm_batch_feedback_kernel<<<1, LM_BATCH_MAX, 0, st>>>(&b->sel_stage->in, vw.tab, b->stt, b->frame_out, vw.NM, i);
-    }
-    if (dc) {
-        const int F = dc->F_ctx + n_steps;
-        duplex_batch_tokens_to_codes_kernel<<<dc->slots, 64, 0, st>>>(b->frame_out, b->sel_stage, n_steps, dc->base, dc->n_codes, d->code_win, F, d->dev->flags);
-        const int r = rca_codec_decode_tail_dev(dc->codec, (const int64_t*)d->code_win, dc->slots, F, dc->n_samples, d->pcm_out, st);
-        if (r != RCA_OK) return r;
-    }
-    if (probes) {
-        lm_softmax_slices_batch_kernel<<<dim3(PROBS_SLICES, vw.NM), 1024, 0, st>>>(vw.tab, V, b->probe_part);
-        lm_token_probs_batch_kernel<<<dim3(1, vw.NM), 64, 0, st>>>(vw.tab, V, b->probe_part, b->sel_stage->in.probe, b->frame_out->probs);
-    }
-    RCA_LAUNCH_CHECK();
-    e = hipMemcpyAsync(&b->pin->frame, b->frame_out, sizeof(LmBatchFrameOut), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pin, d->dev, sizeof(LmBatchDuplexDev), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pin + dc->pin_out, d->pcm_out, (size_t)dc->slots * dc->n_samples * 4, hipMemcpyDeviceToHost, st);
-    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch frame_sel download: %s", hipGetErrorString(e));
-}
-// The parts of a selection's refusals that its frame and its step (rca_lm_batch_step_sel) share.  Members: every index in range and
-// selected once, hm[k] receives the handle of sel[k], and the selected members are settled.
-static int lm_batch_sel_members(rca_lm_batch* b, const char* who, const int32_t* sel, int n_sel, rca_lm** hm) {
-    const int NM = b->n_members;
-    int first_k[LM_BATCH_MAX];
-    for (int s = 0; s < NM; ++s) first_k[s] = -1;
-    for (int k = 0; k < n_sel; ++k) {
-        const int s = sel[k];
-        if (s < 0 || s >= NM) return fail(RCA_ERR_ARG, "%s: sel[%d] = member %d is outside the batch's members [0, %d)", who, k, s, NM);
-        if (first_k[s] >= 0) return fail(RCA_ERR_ARG, "%s: sel[%d] = member %d is selected twice (also sel[%d])", who, k, s, first_k[s]);
-        first_k[s] = k;
-        hm[k] = b->m[s];
+// what an entry point was asked to do
+struct LmBatchCall {
+    const char* who;            // the API's name in messages
+    const int32_t* sel;         // the selected members; null: every member in its own slot, the batch's resident tables
+    int n_sel;                  // the members of the pass (lm_batch_check: n_members where sel is null)
+    int n;                      // tokens per member of a pass
+    bool frame;                 // n_steps pairs with feedback; else a step, one pass of n tokens
+    int n_steps;                // 0: a step
+    const int32_t* ids;         // a step's [n_sel][n], a frame's first pairs
+    const int32_t* user_ids;    // a frame's [n_sel][n_steps]; null: the device makes them (rca_duplex_batch_frame)
+    const int32_t* probe_ids;   // [n_sel][n_probe]; a frame has one per member, -1 for none
+    int n_probe;
+    rca_lm* hm[LM_BATCH_MAX];   // the handle of every slot (lm_batch_check)
+};
+// Every refusal of the five calls, before anything is staged or enqueued: no member changes.  Fills n_sel (without a selection) and
+// hm[], and settles the members of the pass.
+static int lm_batch_check(rca_lm_batch* b, LmBatchCall& c) {
+    const int NM = b->n_members, n = c.n;
+    if (c.sel && (c.n_sel < 1 || c.n_sel > NM)) return fail(RCA_ERR_ARG, "%s: %d selected members, the batch has %d (1..%d)", c.who, c.n_sel, NM, NM);
+    if (c.frame && (c.n_steps < 1 || c.n_steps > LM_FRAME_MAX)) return fail(RCA_ERR_ARG, "%s: %d steps (1..%d)", c.who, c.n_steps, LM_FRAME_MAX);
+    if (!c.sel) {
+        if (NM * n > LM_BATCH_ROWS) return fail(RCA_ERR_ARG, "%s: %d members x %d tokens = %d rows, a batch pass is one token block of %d", c.who, NM, n, NM * n, LM_BATCH_ROWS);
+        c.n_sel = NM;
+        for (int s = 0; s < NM; ++s) c.hm[s] = b->m[s];
+    } else {   // every index in range and selected once
+        int first_k[LM_BATCH_MAX];
+        for (int s = 0; s < NM; ++s) first_k[s] = -1;
+        for (int k = 0; k < c.n_sel; ++k) {
+            const int s = c.sel[k];
+            if (s < 0 || s >= NM) return fail(RCA_ERR_ARG, "%s: sel[%d] = member %d is outside the batch's members [0, %d)", c.who, k, s, NM);
+            if (first_k[s] >= 0) return fail(RCA_ERR_ARG, "%s: sel[%d] = member %d is selected twice (also sel[%d])", c.who, k, s, first_k[s]);
+            first_k[s] = k;
+            c.hm[k] = b->m[s];
+        }
     }
     int rc;
-    for (int k = 0; k < n_sel; ++k)
-        if ((rc = lm_settle(hm[k])) != RCA_OK) return rc;
-    return RCA_OK;
-}
-// what makes sel[k] = member s unfit for a selection's pass
-static int lm_batch_sel_member_ok(const rca_lm_batch* b, const char* who, const rca_lm* h, int k, int s) {
-    if (!h->sampler_set) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has no sampler (rca_lm_sampler_init)", who, k, s);
-    if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d was switched to logits_all after the batch was made", who, k, s);
-    if (h->kv_format != b->m[0]->kv_format) return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d has KV format %d, member 0 has %d", who, k, s, h->kv_format, b->m[0]->kv_format);
-    if (lm_prefill_route(h) != LM_ROUTE_TILE128)
-        return fail(RCA_ERR_STATE, "%s: sel[%d] = member %d no longer takes the 128-token tiles (rca_lm_prefill_route %d)", who, k, s, lm_prefill_route(h));
+    for (int k = 0; k < c.n_sel; ++k)
+        if ((rc = lm_settle(c.hm[k])) != RCA_OK) return rc;
+    const int adv = c.frame ? 2 * c.n_steps : n;   // the positions the call advances a member by
+    for (int k = 0; k < c.n_sel; ++k) {
+        const rca_lm* h = c.hm[k];
+        const int V = h->cfg.vocab_size;
+        char label[48];
+        auto m = [&]() -> const char* {   // the member in messages, composed for a refusal only
+            if (c.sel) snprintf(label, sizeof(label), "sel[%d] = member %d", k, c.sel[k]);
+            else snprintf(label, sizeof(label), "member %d", k);
+            return label;
+        };
+        if (!h->sampler_set) return fail(RCA_ERR_STATE, "%s: %s has no sampler (rca_lm_sampler_init)", c.who, m());
+        if (h->cfg.logits_all) return fail(RCA_ERR_STATE, "%s: %s was switched to logits_all after the batch was made", c.who, m());
+        if (h->kv_format != b->m[0]->kv_format) return fail(RCA_ERR_STATE, "%s: %s has KV format %d, member 0 has %d", c.who, m(), h->kv_format, b->m[0]->kv_format);
+        if (lm_prefill_route(h) != LM_ROUTE_TILE128)
+            return fail(RCA_ERR_STATE, "%s: %s no longer takes the 128-token tiles (rca_lm_prefill_route %d)", c.who, m(), lm_prefill_route(h));
+        if (h->n_tokens + adv > h->cfg.n_ctx) return fail(RCA_ERR_STATE, "%s: context overflow of %s: %d + %d > n_ctx %d", c.who, m(), h->n_tokens, adv, h->cfg.n_ctx);
+        for (int j = 0; j < n; ++j)
+            if (c.ids[k * n + j] < 0 || c.ids[k * n + j] >= V)
+                return fail(RCA_ERR_ARG, "%s: token id %d of %s at index %d%s is outside the vocabulary [0, %d)", c.who, c.ids[k * n + j], m(), j,
+                            c.frame ? " of its first pair" : "", V);
+        for (int i = 0; c.user_ids && i < c.n_steps; ++i)
+            if (c.user_ids[k * c.n_steps + i] < 0 || c.user_ids[k * c.n_steps + i] >= V)
+                return fail(RCA_ERR_ARG, "%s: user token id %d of %s at step %d is outside the vocabulary [0, %d)", c.who, c.user_ids[k * c.n_steps + i], m(), i, V);
+        for (int i = 0; i < c.n_probe; ++i) {
+            const int id = c.probe_ids[k * c.n_probe + i];
+            if (c.frame && (id < -1 || id >= V)) return fail(RCA_ERR_ARG, "%s: probe id %d of %s is outside the vocabulary [0, %d) (-1: no probe)", c.who, id, m(), V);
+            if (!c.frame && (id < 0 || id >= V)) return fail(RCA_ERR_ARG, "%s: probe id %d of %s at index %d is outside the vocabulary [0, %d)", c.who, id, m(), i, V);
+        }
+    }
     return RCA_OK;
 }
 // the selection graphs hold member 0's workspace and the sampler launches of the chain: they go when a member dropped its own graphs
@@ -6508,81 +6307,137 @@ static void lm_batch_sel_epoch(rca_lm_batch* b) {
         b->sel_epoch = epoch;
     }
 }
-// The refusals of a selection frame, before anything is staged: no member changes.  hm[k] receives the handle of sel[k].  user_ids is
-// null when the device produces them (rca_duplex_batch_frame).
-static int lm_batch_sel_check(rca_lm_batch* b, const char* who, const int32_t* sel, int n_sel, const int32_t* first_pairs, const int32_t* user_ids, int n_steps,
-                              const int32_t* probe_ids, rca_lm** hm) {
-    const int NM = b->n_members;
-    if (n_sel < 1 || n_sel > NM) return fail(RCA_ERR_ARG, "%s: %d selected members, the batch has %d (1..%d)", who, n_sel, NM, NM);
-    if (n_steps < 1 || n_steps > LM_FRAME_MAX) return fail(RCA_ERR_ARG, "%s: %d steps (1..%d)", who, n_steps, LM_FRAME_MAX);
+// The call's block in pinned memory and what the launches need to know about its members.  Without a selection the tables are the
+// batch's resident ones (lm_batch_refresh), members with a whole-vocabulary sampler included: their own launches may sit in a graph
+// that goes with their graph_epoch.  With one, the tables are composed here for slots 0 .. n_sel - 1, all-zero entries behind them.
+struct LmBatchPlan { LmBatchView vw; bool graphs, any_patch; int cls, bucket, nsp, nsp_bucket; size_t up_bytes; };
+static int lm_batch_stage(rca_lm_batch* b, const LmBatchCall& c, LmBatchPlan* plan) {
+    RCA_HIP(hipSetDevice(b->m[0]->device));
     int rc;
-    if ((rc = lm_batch_sel_members(b, who, sel, n_sel, hm)) != RCA_OK) return rc;
-    for (int k = 0; k < n_sel; ++k) {
-        const rca_lm* h = hm[k];
-        const int s = sel[k], V = h->cfg.vocab_size;
-        if ((rc = lm_batch_sel_member_ok(b, who, h, k, s)) != RCA_OK) return rc;
-        if (h->n_tokens + 2 * n_steps > h->cfg.n_ctx)
-            return fail(RCA_ERR_STATE, "%s: context overflow of sel[%d] = member %d: %d + %d > n_ctx %d", who, k, s, h->n_tokens, 2 * n_steps, h->cfg.n_ctx);
-        for (int j = 0; j < 2; ++j)
-            if (first_pairs[k * 2 + j] < 0 || first_pairs[k * 2 + j] >= V)
-                return fail(RCA_ERR_ARG, "%s: token id %d of sel[%d] = member %d at index %d of its first pair is outside the vocabulary [0, %d)", who,
-                            first_pairs[k * 2 + j], k, s, j, V);
-        for (int i = 0; user_ids && i < n_steps; ++i)
-            if (user_ids[k * n_steps + i] < 0 || user_ids[k * n_steps + i] >= V)
-                return fail(RCA_ERR_ARG, "%s: user token id %d of sel[%d] = member %d at step %d is outside the vocabulary [0, %d)", who,
-                            user_ids[k * n_steps + i], k, s, i, V);
-        if (probe_ids && (probe_ids[k] < -1 || probe_ids[k] >= V))
-            return fail(RCA_ERR_ARG, "%s: probe id %d of sel[%d] = member %d is outside the vocabulary [0, %d) (-1: no probe)", who, probe_ids[k], k, s, V);
-    }
-    return RCA_OK;
-}
-// the call's block in pinned memory -- tables of the selected members in slots 0 .. n_sel - 1, all-zero entries behind them -- and what
-// the launches need to know about the selection
-struct LmBatchSelPlan { LmBatchView vw; bool graphs, any_patch; int cls, bucket, nsp, nsp_bucket; };
-static LmBatchSelPlan lm_batch_sel_stage(rca_lm_batch* b, rca_lm* const* hm, int n_sel, const int32_t* first_pairs, const int32_t* user_ids, int n_steps,
-                                         const int32_t* probe_ids) {
-    lm_batch_sel_epoch(b);
-    LmBatchSelPlan p{};
-    p.cls = lm_batch_class(n_sel);
+    if (c.sel) lm_batch_sel_epoch(b);
+    else if ((rc = lm_batch_refresh(b)) != RCA_OK) return rc;
+    LmBatchPlan p{};
+    const int n = c.n, adv = c.frame ? 2 * c.n_steps : n;
+    p.cls = lm_batch_class(c.n_sel);
     p.graphs = true;
     p.nsp = 1;
+    // the head of the block that the call uploads: a frame does not carry the tables without a selection, nor a step's probe ids
+    p.up_bytes = c.sel ? (c.frame ? sizeof(LmBatchSelStage) : sizeof(LmBatchStepSelStage)) : (c.frame ? sizeof(LmBatchFrameStage) : sizeof(LmBatchStage));
     bool any_serial = false;
-    LmBatchSelStage& in = *b->sel_pin;
-    memset(&in, 0, sizeof(in));   // slots past the selection: all-zero entries, the table kernels leave on them
-    in.n_live = n_sel;
-    for (int k = 0; k < n_sel; ++k) {
-        rca_lm* h = hm[k];
-        const bool serial = !h->samp_full;
-        p.graphs = p.graphs && h->graphs_enabled && serial;   // a whole-vocabulary sampler has launches of its own with its own pointers: eager
-        any_serial = any_serial || serial;
-        p.any_patch = p.any_patch || (serial && h->samp_patch);
-        in.tab[k] = lm_batch_member(h, k * 2, serial);
-        for (int j = 0; j < 2; ++j) {
-            in.rows[k * 2 + j] = lm_group_row(h, j, k * 2 + j);
-            in.in.ids[k * 2 + j] = first_pairs[k * 2 + j];
+    LmBatchStepSelStage& in = *b->sel_pin;
+    memset(&in, 0, p.up_bytes);   // slots past the selection: all-zero entries, the table kernels leave on them
+    in.n_live = c.n_sel;
+    if (p.up_bytes == sizeof(LmBatchStepSelStage)) in.n_probe = c.n_probe;
+    for (int k = 0; k < c.n_sel; ++k) {
+        rca_lm* h = c.hm[k];
+        p.graphs = p.graphs && h->graphs_enabled;
+        if (c.sel) {
+            const bool serial = !h->samp_full;
+            p.graphs = p.graphs && serial;   // a whole-vocabulary sampler has launches of its own with its own pointers: eager
+            any_serial = any_serial || serial;
+            p.any_patch = p.any_patch || (serial && h->samp_patch);
+            in.tab[k] = lm_batch_member(h, k * n, serial);
+            for (int j = 0; j < n; ++j) in.rows[k * n + j] = lm_group_row(h, j, k * n + j);
         }
-        in.in.n_tokens[k] = h->n_tokens;
-        for (int i = 0; user_ids && i < n_steps; ++i) in.in.user[k * LM_FRAME_MAX + i] = user_ids[k * n_steps + i];
-        in.in.probe[k] = probe_ids ? probe_ids[k] : -1;
-        // the bucket and the splits of the frame's END, as rca_lm_batch_frame
-        p.bucket = std::max(p.bucket, lm_bucket(h, 2 * n_steps, -1).bucket);
-        p.nsp = std::max(p.nsp, lm_splits_needed(h, 2 * n_steps));
+        in.n_tokens[k] = h->n_tokens;
+        for (int j = 0; j < n; ++j) in.ids[k * n + j] = c.ids[k * n + j];
+        for (int i = 0; c.user_ids && i < c.n_steps; ++i) in.user[k * LM_FRAME_MAX + i] = c.user_ids[k * c.n_steps + i];
+        if (c.frame) in.probe[k] = c.probe_ids ? c.probe_ids[k] : -1;
+        else for (int i = 0; i < c.n_probe; ++i) in.probe_ids[k * c.n_probe + i] = c.probe_ids[k * c.n_probe + i];
+        // the bucket and the splits of the call's END (as lm_frame_core): a frame that crosses a bucket or a 256-key split inside itself
+        // has the splits its last step needs; its earlier steps leave the extra ones at once
+        p.bucket = std::max(p.bucket, lm_bucket(h, adv, -1).bucket);
+        p.nsp = std::max(p.nsp, lm_splits_needed(h, adv));
     }
-    for (int k = n_sel; k < LM_BATCH_MAX; ++k) in.in.probe[k] = -1;
+    for (int k = c.n_sel; c.frame && k < LM_BATCH_MAX; ++k) in.probe[k] = -1;
     // a graph's split count is the bucket's over ALL members of the batch, so that the grid does not depend on who is selected (a
     // split past a member's cache leaves at once)
     p.nsp_bucket = p.bucket + 1 == LM_GRAPH_BUCKETS ? b->nsp_all : std::min(b->nsp_all, 4 << p.bucket);
-    p.vw = LmBatchView{b->sel_stage->rows, b->sel_stage->tab, 8 << p.cls, any_serial, p.any_patch, hm, n_sel};
-    return p;
+    if (c.sel) p.vw = LmBatchView{b->sel_stage->rows, b->sel_stage->tab, 8 << p.cls, any_serial, p.any_patch, c.hm, c.n_sel};
+    else p.vw = lm_batch_view(b, n);
+    p.any_patch = p.vw.any_patch;
+    *plan = p;
+    return RCA_OK;
 }
-// after the synchronisation: which steps of every selected member stand (rca_lm_batch_frame's settlement, indexed by k)
-static int lm_batch_sel_settle(rca_lm_batch* b, rca_lm* const* hm, int n_sel, int n_steps, int audio_id_floor, const int32_t* probe_ids, int32_t* out_tokens,
-                               int out_stride, int32_t* n_done, float* probe_probs, hipStream_t st) {
-    const LmBatchFrameOut& out = b->pin->frame;
+// upload -> stage -> [encode tails -> codes to ids] -> one pass of n tokens, or n_steps x (pass of pairs, feedback) -> [ids to codes ->
+// decode tails] -> probes -> [a step's token gather] -> download, one linear sequence on `st`; the codec tails with a duplex call only.
+// A captured sequence launches the bucket's splits, an eager one what the members need now.
+static int lm_batch_enqueue(rca_lm_batch* b, const LmBatchCall& c, const LmBatchPlan& p, bool captured, hipStream_t st, const LmBatchDuplexCall* dc = nullptr) {
+    const int V = b->m[0]->cfg.vocab_size, n_steps = c.n_steps, nsp_launch = captured ? p.nsp_bucket : p.nsp;
+    const LmBatchView& vw = p.vw;
+    LmBatchDuplex* d = b->dx;
+    hipError_t e = hipMemcpyAsync(b->sel_stage, b->sel_pin, p.up_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pcm_in, d->pin + dc->pin_pcm, (size_t)dc->slots * dc->T * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->code_win, d->pin + dc->pin_codes, (size_t)dc->slots * (dc->F_ctx + n_steps) * 8, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s upload: %s", c.who, hipGetErrorString(e));
+    lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->sel_stage, vw.tab, b->stt, b->stt_head, c.n);
+    if (dc) {
+        const int r = rca_codec_encode_tail_dev(dc->codec, d->pcm_in, dc->slots, dc->T, n_steps, (int64_t*)d->dev->user_codes, st);
+        if (r != RCA_OK) return r;
+        duplex_batch_codes_to_ids_kernel<<<dc->slots, 64, 0, st>>>(d->dev->user_codes, n_steps, dc->base, b->sel_stage, d->dev->flags);
+    }
+    if (!c.frame) lm_batch_enqueue_pass(b, vw, c.n, nsp_launch, st);
+    for (int i = 0; i < n_steps; ++i) {
+        lm_batch_enqueue_pass(b, vw, 2, nsp_launch, st);
+        lm_batch_feedback_kernel<<<1, LM_BATCH_MAX, 0, st>>>(b->sel_stage, vw.tab, b->stt, b->frame_out, vw.NM, i);
+    }
+    if (dc) {
+        const int F = dc->F_ctx + n_steps;
+        duplex_batch_tokens_to_codes_kernel<<<dc->slots, 64, 0, st>>>(b->frame_out, b->sel_stage, n_steps, dc->base, dc->n_codes, d->code_win, F, d->dev->flags);
+        const int r = rca_codec_decode_tail_dev(dc->codec, (const int64_t*)d->code_win, dc->slots, F, dc->n_samples, d->pcm_out, st);
+        if (r != RCA_OK) return r;
+    }
+    if (c.n_probe) {
+        lm_softmax_slices_batch_kernel<<<dim3(PROBS_SLICES, vw.NM), 1024, 0, st>>>(vw.tab, V, b->probe_part);
+        if (c.frame) lm_token_probs_batch_kernel<<<dim3(1, vw.NM), 64, 0, st>>>(vw.tab, V, b->probe_part, b->sel_stage->probe, b->frame_out->probs);
+        else lm_token_probs_sel_kernel<<<dim3(1, vw.NM), 64, 0, st>>>(vw.tab, V, b->probe_part, b->sel_stage, b->step_out->probs);
+    }
+    if (!c.frame) lm_batch_tokens_kernel<<<1, LM_BATCH_MAX, 0, st>>>(vw.tab, vw.NM, b->step_out->tokens);
+    RCA_LAUNCH_CHECK();
+    // a frame's tokens and probes; a step's tokens, with the probabilities behind them where the call can have any (rca_lm_batch_step_sel)
+    if (c.frame) e = hipMemcpyAsync(b->frame_pin, b->frame_out, sizeof(LmBatchFrameOut), hipMemcpyDeviceToHost, st);
+    else e = hipMemcpyAsync(b->step_out_pin, b->step_out, c.sel ? sizeof(LmBatchStepSelOut) : sizeof(int) * LM_BATCH_MAX, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pin, d->dev, sizeof(LmBatchDuplexDev), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dc) e = hipMemcpyAsync(d->pin + dc->pin_out, d->pcm_out, (size_t)dc->slots * dc->n_samples * 4, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "%s download: %s", c.who, hipGetErrorString(e));
+}
+// Replays the graph of `slot`, capturing it first if the slot is empty (counted: rca_lm_batch_captures), or with graphs off enqueues
+// eagerly; then waits for the stream.  `enqueue(captured)` puts the call's sequence on `st`.
+template <class F>
+static int lm_batch_run(rca_lm_batch* b, hipStream_t st, hipGraphExec_t* slot, const char* tag, bool graphs, F&& enqueue) {
+    int rc;
+    if (graphs) {
+        if (!*slot) {
+            if ((rc = lm_capture(st, slot, tag, [&]() -> int { return enqueue(true); })) != RCA_OK) return rc;
+            b->n_captures++;
+        }
+        RCA_HIP(hipGraphLaunch(*slot, st));
+    } else if ((rc = enqueue(false)) != RCA_OK) {
+        return rc;
+    }
+    RCA_HIP(hipStreamSynchronize(st));
+    return RCA_OK;
+}
+// A step's settlement, after the synchronisation: every member of the pass took n tokens and drew once.
+static void lm_batch_step_settle(rca_lm_batch* b, const LmBatchCall& c, int32_t* tokens) {
+    for (int k = 0; k < c.n_sel; ++k) {
+        rca_lm* h = c.hm[k];
+        h->n_tokens += c.n;
+        h->logits_rows = 1;
+        h->rng_host += 1;
+        tokens[k] = b->step_out_pin->tokens[k];
+    }
+}
+// A frame's settlement, after the synchronisation: which steps of every member of the pass stand, as lm_frame_core settles one handle.
+// `tab` is the table of the pass, where the slot of a cut member is addressed (the device tables still hold this call's members).
+static int lm_batch_sel_settle(rca_lm_batch* b, const LmBatchCall& c, const LmBatchMember* tab, int audio_id_floor, int32_t* out_tokens, int out_stride,
+                               int32_t* n_done, float* probe_probs, hipStream_t st) {
+    const LmBatchFrameOut& out = *b->frame_pin;
+    const int n_steps = c.n_steps;
     LmBatchCuts cuts;
     cuts.n = 0;
-    for (int k = 0; k < n_sel; ++k) {
-        rca_lm* h = hm[k];
+    for (int k = 0; k < c.n_sel; ++k) {
+        rca_lm* h = c.hm[k];
         int done = n_steps;
         for (int i = 0; i < n_steps; ++i) {
             out_tokens[k * out_stride + i] = out.tokens[k * LM_FRAME_MAX + i];
@@ -6591,44 +6446,75 @@ static int lm_batch_sel_settle(rca_lm_batch* b, rca_lm* const* hm, int n_sel, in
         for (int i = done; i < out_stride; ++i) out_tokens[k * out_stride + i] = -1;
         n_done[k] = done;
         h->n_tokens += 2 * done;
+        // a member cut short holds the logits of a LATER step (evaluated on a wrong-guess pair): nothing may read them
         h->logits_rows = done < n_steps ? 0 : 1;
         h->rng_host += (unsigned long long)done;
         if (done < n_steps) {
-            cuts.member[cuts.n] = k;   // the slot: the device tables still hold this call's selection
+            cuts.member[cuts.n] = k;
             cuts.counter[cuts.n++] = h->rng_host;
         }
-        if (probe_probs) probe_probs[k] = done < n_steps || !probe_ids || probe_ids[k] < 0 ? -1.0f : out.probs[k];
+        if (probe_probs) probe_probs[k] = done < n_steps || !c.probe_ids || c.probe_ids[k] < 0 ? -1.0f : out.probs[k];
     }
-    if (cuts.n) {
-        lm_batch_counters_kernel<<<1, LM_BATCH_MAX, 0, st>>>(b->sel_stage->tab, cuts);
+    if (cuts.n) {   // the device drew n_steps times for these: their counters go where the step-by-step loop would be, in one launch
+        lm_batch_counters_kernel<<<1, LM_BATCH_MAX, 0, st>>>(tab, cuts);
         RCA_LAUNCH_CHECK();
         RCA_HIP(hipStreamSynchronize(st));
     }
     return RCA_OK;
 }
+
+// rca_lm_batch_step: every member advances by its n tokens in one pass over the batch's resident tables
+extern "C" int rca_lm_batch_step(rca_lm_batch_t* b, const int32_t* ids, int32_t n, int32_t* tokens) {
+    if (!b || !ids || !tokens) return fail(RCA_ERR_ARG, "batch_step: null argument");
+    if (n < 1 || n > LM_GEMV_M) return fail(RCA_ERR_ARG, "batch_step: %d tokens per member (1..%d)", n, LM_GEMV_M);
+    LmBatchCall c{"batch_step", nullptr, 0, n, false, 0, ids, nullptr, nullptr, 0};
+    LmBatchPlan p;
+    hipStream_t st = b->m[0]->stream;
+    int rc;
+    if ((rc = lm_batch_check(b, c)) != RCA_OK || (rc = lm_batch_stage(b, c, &p)) != RCA_OK) return rc;
+    if ((rc = lm_batch_run(b, st, &b->g[n - 1][p.bucket], "batch step", p.graphs, [&](bool captured) -> int { return lm_batch_enqueue(b, c, p, captured, st); })) != RCA_OK) return rc;
+    lm_batch_step_settle(b, c, tokens);
+    return RCA_OK;
+}
+
+// ------------------------------------------------------------------------------------ batch frame (rca_lm_batch_frame)
+// rca_lm_frame for every member of a batch in one launch sequence: n_steps times the batch pass over pairs (lm_batch_enqueue_pass, the
+// launches of a 2-token batch step) with lm_batch_feedback_kernel between them, then the probes.  Every member runs every step -- a
+// row cannot leave a captured graph -- and the host settles afterwards which steps of a member stand, as lm_frame_core does for one.
+extern "C" int rca_lm_batch_frame(rca_lm_batch_t* b, const int32_t* first_pairs, const int32_t* user_ids, int32_t n_steps, int32_t audio_id_floor,
+                                  const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done, float* probe_probs) {
+    if (!b || !first_pairs || !user_ids || !out_tokens || !n_done) return fail(RCA_ERR_ARG, "batch_frame: null argument");
+    if (probe_ids && !probe_probs) return fail(RCA_ERR_ARG, "batch_frame: probe_ids without probe_probs");
+    LmBatchCall c{"batch_frame", nullptr, 0, 2, true, n_steps, first_pairs, user_ids, probe_ids, probe_ids ? 1 : 0};
+    LmBatchPlan p;
+    hipStream_t st = b->m[0]->stream;
+    int rc;
+    if ((rc = lm_batch_check(b, c)) != RCA_OK || (rc = lm_batch_stage(b, c, &p)) != RCA_OK) return rc;
+    if ((rc = lm_batch_run(b, st, &b->fg[n_steps - 1][p.bucket][c.n_probe], "batch frame", p.graphs, [&](bool captured) -> int { return lm_batch_enqueue(b, c, p, captured, st); })) != RCA_OK)
+        return rc;
+    return lm_batch_sel_settle(b, c, p.vw.tab, audio_id_floor, out_tokens, n_steps, n_done, probe_ids ? probe_probs : nullptr, st);
+}
+
+// ------------------------------------------------------------------------------------ selection frame (rca_lm_batch_frame_sel)
+// rca_lm_batch_frame over a SUBSET of the members: sessions sit ticks out (windows still filling, a forced branch, a trim between two
+// steps, a chunk that has not arrived).  The selected members are compacted into slots 0 .. n_sel - 1 of tables composed on the host
+// for THIS call (LmBatchSelStage) and uploaded with the frame's block inside the replay; the launches cover the selection's geometry
+// class (8, 16, 32 or 64 slots).  The live count travels in the block: the row-wise kernels leave on the pass state's m, the table
+// kernels on the all-zero entry of a slot past it.  So a graph holds no member's pointer -- only member 0's workspace and weights --
+// and is keyed by (class, n_steps, bucket, probes, patching samplers): it serves every selection of its class and outlives a member's
+// rca_lm_swap_kv.  An unselected member is not read on the device and not written anywhere.
 extern "C" int rca_lm_batch_frame_sel(rca_lm_batch_t* b, const int32_t* sel, int32_t n_sel, const int32_t* first_pairs, const int32_t* user_ids, int32_t n_steps,
                                       int32_t audio_id_floor, const int32_t* probe_ids, int32_t* out_tokens, int32_t* n_done, float* probe_probs) {
     if (!b || !sel || !first_pairs || !user_ids || !out_tokens || !n_done) return fail(RCA_ERR_ARG, "batch_frame_sel: null argument");
     if (probe_ids && !probe_probs) return fail(RCA_ERR_ARG, "batch_frame_sel: probe_ids without probe_probs");
-    rca_lm* hm[LM_BATCH_MAX];
-    int rc;
-    if ((rc = lm_batch_sel_check(b, "batch_frame_sel", sel, n_sel, first_pairs, user_ids, n_steps, probe_ids, hm)) != RCA_OK) return rc;
-    RCA_HIP(hipSetDevice(b->m[0]->device));
+    LmBatchCall c{"batch_frame_sel", sel, n_sel, 2, true, n_steps, first_pairs, user_ids, probe_ids, probe_ids ? 1 : 0};
+    LmBatchPlan p;
     hipStream_t st = b->m[0]->stream;
-    const bool probes = probe_ids != nullptr;
-    const LmBatchSelPlan p = lm_batch_sel_stage(b, hm, n_sel, first_pairs, user_ids, n_steps, probe_ids);
-    if (p.graphs) {
-        hipGraphExec_t& gexec = b->sg[p.cls][n_steps - 1][p.bucket][probes ? 1 : 0][p.any_patch ? 1 : 0];
-        if (!gexec) {
-            if ((rc = lm_capture(st, &gexec, "batch frame_sel", [&]() -> int { return lm_batch_sel_enqueue(b, p.vw, n_steps, p.nsp_bucket, probes, st); })) != RCA_OK) return rc;
-            b->n_captures++;
-        }
-        RCA_HIP(hipGraphLaunch(gexec, st));
-    } else if ((rc = lm_batch_sel_enqueue(b, p.vw, n_steps, p.nsp, probes, st)) != RCA_OK) {
-        return rc;
-    }
-    RCA_HIP(hipStreamSynchronize(st));
-    return lm_batch_sel_settle(b, hm, n_sel, n_steps, audio_id_floor, probe_ids, out_tokens, n_steps, n_done, probes ? probe_probs : nullptr, st);
+    int rc;
+    if ((rc = lm_batch_check(b, c)) != RCA_OK || (rc = lm_batch_stage(b, c, &p)) != RCA_OK) return rc;
+    hipGraphExec_t* slot = &b->sg[p.cls][n_steps - 1][p.bucket][c.n_probe][p.any_patch ? 1 : 0];
+    if ((rc = lm_batch_run(b, st, slot, "batch frame_sel", p.graphs, [&](bool captured) -> int { return lm_batch_enqueue(b, c, p, captured, st); })) != RCA_OK) return rc;
+    return lm_batch_sel_settle(b, c, p.vw.tab, audio_id_floor, out_tokens, n_steps, n_done, probe_ids ? probe_probs : nullptr, st);
 }
 
 // ------------------------------------------------------------------------------------ selection step (rca_lm_batch_step_sel)
@@ -6637,22 +6523,6 @@ extern "C" int rca_lm_batch_frame_sel(rca_lm_batch_t* b, const int32_t* sel, int
 // tokens per member: tables of slots 0 .. n_sel - 1 composed for this call, uploaded with the ids and the probe ids as one block inside
 // the replay; the launches cover the class, the live count and the probe count travel in the block.  A selected member ends as
 // rca_lm_batch_step(n) of a batch over the selected members alone leaves it; an unselected member is in no table of the call.
-// upload -> stage -> the pass -> [probes] -> gather -> download, one linear sequence on `st`
-static int lm_batch_step_sel_enqueue(rca_lm_batch* b, const LmBatchView& vw, int n, int nsp_launch, bool probes, hipStream_t st) {
-    const int V = b->m[0]->cfg.vocab_size;
-    hipError_t e = hipMemcpyAsync(b->sel_stage, b->sel_pin, sizeof(LmBatchStepSelStage), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch step_sel upload: %s", hipGetErrorString(e));
-    lm_batch_sel_stage_n_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->sel_stage, b->stt, b->stt_head, n);
-    lm_batch_enqueue_pass(b, vw, n, nsp_launch, st);
-    if (probes) {
-        lm_softmax_slices_batch_kernel<<<dim3(PROBS_SLICES, vw.NM), 1024, 0, st>>>(vw.tab, V, b->probe_part);
-        lm_token_probs_sel_kernel<<<dim3(1, vw.NM), 64, 0, st>>>(vw.tab, V, b->probe_part, b->sel_stage, b->step_out->probs);
-    }
-    lm_batch_tokens_kernel<<<1, LM_BATCH_MAX, 0, st>>>(vw.tab, vw.NM, b->step_out->tokens);
-    RCA_LAUNCH_CHECK();
-    e = hipMemcpyAsync(b->step_out_pin, b->step_out, sizeof(LmBatchStepSelOut), hipMemcpyDeviceToHost, st);
-    return e == hipSuccess ? RCA_OK : fail(RCA_ERR_HIP, "batch step_sel download: %s", hipGetErrorString(e));
-}
 extern "C" int rca_lm_batch_step_sel(rca_lm_batch_t* b, const int32_t* sel, int32_t n_sel, const int32_t* ids, int32_t n, const int32_t* probe_ids, int32_t n_probe,
                                      int32_t* tokens, float* probs) {
     const char* who = "batch_step_sel";
@@ -6661,75 +6531,15 @@ extern "C" int rca_lm_batch_step_sel(rca_lm_batch_t* b, const int32_t* sel, int3
     if (n_probe < 0 || n_probe > LM_STEP_PROBES) return fail(RCA_ERR_ARG, "%s: %d probe ids per member (0..%d)", who, n_probe, LM_STEP_PROBES);
     if ((n_probe > 0) != (probe_ids != nullptr)) return fail(RCA_ERR_ARG, "%s: probe_ids is null exactly when n_probe is 0 (n_probe %d)", who, n_probe);
     if (n_probe > 0 && !probs) return fail(RCA_ERR_ARG, "%s: probe_ids without probs", who);
-    if (n_sel < 1 || n_sel > b->n_members) return fail(RCA_ERR_ARG, "%s: %d selected members, the batch has %d (1..%d)", who, n_sel, b->n_members, b->n_members);
-    rca_lm* hm[LM_BATCH_MAX];
-    int rc;
-    // every refusal before anything is staged or enqueued: no member changes
-    if ((rc = lm_batch_sel_members(b, who, sel, n_sel, hm)) != RCA_OK) return rc;
-    for (int k = 0; k < n_sel; ++k) {
-        const rca_lm* h = hm[k];
-        const int s = sel[k], V = h->cfg.vocab_size;
-        if ((rc = lm_batch_sel_member_ok(b, who, h, k, s)) != RCA_OK) return rc;
-        if (h->n_tokens + n > h->cfg.n_ctx)
-            return fail(RCA_ERR_STATE, "%s: context overflow of sel[%d] = member %d: %d + %d > n_ctx %d", who, k, s, h->n_tokens, n, h->cfg.n_ctx);
-        for (int j = 0; j < n; ++j)
-            if (ids[k * n + j] < 0 || ids[k * n + j] >= V)
-                return fail(RCA_ERR_ARG, "%s: token id %d of sel[%d] = member %d at index %d is outside the vocabulary [0, %d)", who, ids[k * n + j], k, s, j, V);
-        for (int i = 0; i < n_probe; ++i)
-            if (probe_ids[k * n_probe + i] < 0 || probe_ids[k * n_probe + i] >= V)
-                return fail(RCA_ERR_ARG, "%s: probe id %d of sel[%d] = member %d at index %d is outside the vocabulary [0, %d)", who, probe_ids[k * n_probe + i], k, s, i, V);
-    }
-    RCA_HIP(hipSetDevice(b->m[0]->device));
+    LmBatchCall c{who, sel, n_sel, n, false, 0, ids, nullptr, probe_ids, n_probe};
+    LmBatchPlan p;
     hipStream_t st = b->m[0]->stream;
-    lm_batch_sel_epoch(b);
-    // the call's block: tables of the selected members in slots 0 .. n_sel - 1 for n tokens each, all-zero entries behind them
-    LmBatchStepSelStage& in = *b->sel_pin;
-    memset(&in, 0, sizeof(in));
-    in.n_live = n_sel;
-    in.n_probe = n_probe;
-    const int cls = lm_batch_class(n_sel);
-    bool graphs = true, any_serial = false, any_patch = false;
-    int bucket = 0, nsp = 1;
-    for (int k = 0; k < n_sel; ++k) {
-        rca_lm* h = hm[k];
-        const bool serial = !h->samp_full;
-        graphs = graphs && h->graphs_enabled && serial;   // a whole-vocabulary sampler has launches of its own with its own pointers: eager
-        any_serial = any_serial || serial;
-        any_patch = any_patch || (serial && h->samp_patch);
-        in.tab[k] = lm_batch_member(h, k * n, serial);
-        for (int j = 0; j < n; ++j) {
-            in.rows[k * n + j] = lm_group_row(h, j, k * n + j);
-            in.in.ids[k * n + j] = ids[k * n + j];
-        }
-        in.in.n_tokens[k] = h->n_tokens;
-        for (int i = 0; i < n_probe; ++i) in.probe_ids[k * n_probe + i] = probe_ids[k * n_probe + i];
-        bucket = std::max(bucket, lm_bucket(h, n, -1).bucket);
-        nsp = std::max(nsp, lm_splits_needed(h, n));
-    }
-    const LmBatchView vw{b->sel_stage->rows, b->sel_stage->tab, 8 << cls, any_serial, any_patch, hm, n_sel};
-    const bool probes = n_probe > 0;
-    if (graphs) {
-        // the bucket's split count over ALL members of the batch: the grid does not depend on who is selected
-        const int nsp_bucket = bucket + 1 == LM_GRAPH_BUCKETS ? b->nsp_all : std::min(b->nsp_all, 4 << bucket);
-        hipGraphExec_t& gexec = b->ssg[cls][n - 1][bucket][probes ? 1 : 0][any_patch ? 1 : 0];
-        if (!gexec) {
-            if ((rc = lm_capture(st, &gexec, "batch step_sel", [&]() -> int { return lm_batch_step_sel_enqueue(b, vw, n, nsp_bucket, probes, st); })) != RCA_OK) return rc;
-            b->n_captures++;
-        }
-        RCA_HIP(hipGraphLaunch(gexec, st));
-    } else if ((rc = lm_batch_step_sel_enqueue(b, vw, n, nsp, probes, st)) != RCA_OK) {
-        return rc;
-    }
-    RCA_HIP(hipStreamSynchronize(st));
-    const LmBatchStepSelOut& out = *b->step_out_pin;
-    for (int k = 0; k < n_sel; ++k) {
-        rca_lm* h = hm[k];
-        h->n_tokens += n;
-        h->logits_rows = 1;
-        h->rng_host += 1;
-        tokens[k] = out.tokens[k];
-    }
-    if (probes) memcpy(probs, out.probs, sizeof(float) * (size_t)n_sel * n_probe);
+    int rc;
+    if ((rc = lm_batch_check(b, c)) != RCA_OK || (rc = lm_batch_stage(b, c, &p)) != RCA_OK) return rc;
+    hipGraphExec_t* slot = &b->ssg[p.cls][n - 1][p.bucket][n_probe ? 1 : 0][p.any_patch ? 1 : 0];
+    if ((rc = lm_batch_run(b, st, slot, "batch step_sel", p.graphs, [&](bool captured) -> int { return lm_batch_enqueue(b, c, p, captured, st); })) != RCA_OK) return rc;
+    lm_batch_step_settle(b, c, tokens);
+    if (n_probe) memcpy(probs, b->step_out_pin->probs, sizeof(float) * (size_t)n_sel * n_probe);
     return RCA_OK;
 }
 
@@ -6775,9 +6585,10 @@ extern "C" int rca_duplex_batch_frame(rca_lm_batch_t* b, rca_codec_t* codec, con
         return fail(RCA_ERR_ARG, "duplex_batch_frame: null argument");
     const int n = a->n_steps, n_sel = a->n_sel;
     if (a->T < 1 || a->F_ctx < 0 || a->n_samples < 1) return fail(RCA_ERR_ARG, "duplex_batch_frame: bad shape (T=%d F_ctx=%d n_samples=%d)", a->T, a->F_ctx, a->n_samples);
-    rca_lm* hm[LM_BATCH_MAX];
+    LmBatchCall c{"duplex_batch_frame", a->sel, n_sel, 2, true, n, a->first_pairs, nullptr, a->probe_ids, a->probe_ids ? 1 : 0};
+    LmBatchPlan p;
     int rc;
-    if ((rc = lm_batch_sel_check(b, "duplex_batch_frame", a->sel, n_sel, a->first_pairs, nullptr, n, a->probe_ids, hm)) != RCA_OK) return rc;
+    if ((rc = lm_batch_check(b, c)) != RCA_OK) return rc;
     int32_t n_codes = 0, hop = 0;
     if ((rc = rca_codec_codebook_size(codec, &n_codes)) != RCA_OK || (rc = rca_codec_hop(codec, &hop)) != RCA_OK) return rc;
     const int V = b->m[0]->cfg.vocab_size, F = a->F_ctx + n;
@@ -6787,13 +6598,11 @@ extern "C" int rca_duplex_batch_frame(rca_lm_batch_t* b, rca_codec_t* codec, con
     if ((long)a->n_samples > (long)F * hop) return fail(RCA_ERR_ARG, "duplex_batch_frame: %d samples wanted, %d codes give %ld", a->n_samples, F, (long)F * hop);
     for (int k = 0; k < n_sel; ++k)
         for (int i = 0; i < a->F_ctx; ++i) {
-            const long long c = a->code_ctx[(long)k * a->F_ctx + i];
-            if (c < 0 || c >= n_codes) return fail(RCA_ERR_ARG, "duplex_batch_frame: code %lld of sel[%d] = member %d at index %d of its context is out of range [0, %d)", c, k, a->sel[k], i, n_codes);
+            const long long code = a->code_ctx[(long)k * a->F_ctx + i];
+            if (code < 0 || code >= n_codes) return fail(RCA_ERR_ARG, "duplex_batch_frame: code %lld of sel[%d] = member %d at index %d of its context is out of range [0, %d)", code, k, a->sel[k], i, n_codes);
         }
-    RCA_HIP(hipSetDevice(b->m[0]->device));
     hipStream_t st = b->m[0]->stream;
-    const bool probes = a->probe_ids != nullptr;
-    const LmBatchSelPlan p = lm_batch_sel_stage(b, hm, n_sel, a->first_pairs, nullptr, n, a->probe_ids);
+    if ((rc = lm_batch_stage(b, c, &p)) != RCA_OK) return rc;
     const int slots = 8 << p.cls;
     auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     LmBatchDuplexCall dc{codec, slots, a->T, a->F_ctx, a->n_samples, a->code_token_base, n_codes, 0, 0, 0};
@@ -6817,31 +6626,25 @@ extern "C" int rca_duplex_batch_frame(rca_lm_batch_t* b, rca_codec_t* codec, con
         warmed = warmed || (w.cls == p.cls && w.T == a->T && w.F_ctx == a->F_ctx && w.n_steps == n && w.n_samples == a->n_samples && w.codec == (const void*)codec && w.codec_sig == csig);
     // the codec's ordering moves to this stream (nothing of it is in flight elsewhere once this returns)
     if ((rc = rca_codec_stream_handoff(codec, st)) != RCA_OK) return rc;
-    if (p.graphs && warmed) {
-        const LmBatchDuplexKey key{p.cls, a->T, a->F_ctx, n, a->n_samples, probes ? 1 : 0, p.bucket, a->code_token_base, p.any_patch ? 1 : 0, csig, (const void*)codec};
-        LmBatchDuplex::Entry* ent = nullptr;
+    const bool graphs = p.graphs && warmed;
+    hipGraphExec_t* slot = nullptr;   // the keyed entry's
+    if (graphs) {
+        const LmBatchDuplexKey key{p.cls, a->T, a->F_ctx, n, a->n_samples, c.n_probe, p.bucket, a->code_token_base, p.any_patch ? 1 : 0, csig, (const void*)codec};
         for (auto& e : d->graphs)
-            if (e.key == key) ent = &e;
-        if (!ent) {
+            if (e.key == key) slot = &e.exec;
+        if (!slot) {
             if (d->graphs.size() >= 32) lm_batch_duplex_drop_graphs(d);   // stale shapes: start over (the stream is idle between calls)
             d->graphs.push_back(LmBatchDuplex::Entry{key, nullptr});
-            ent = &d->graphs.back();
+            slot = &d->graphs.back().exec;
         }
-        if (!ent->exec) {
-            if ((rc = lm_capture(st, &ent->exec, "duplex batch", [&]() -> int { return lm_batch_sel_enqueue(b, p.vw, n, p.nsp_bucket, probes, st, &dc); })) != RCA_OK) return rc;
-            b->n_captures++;
-        }
-        RCA_HIP(hipGraphLaunch(ent->exec, st));
-    } else if ((rc = lm_batch_sel_enqueue(b, p.vw, n, p.nsp, probes, st, &dc)) != RCA_OK) {
-        return rc;
     }
-    RCA_HIP(hipStreamSynchronize(st));
+    if ((rc = lm_batch_run(b, st, slot, "duplex batch", graphs, [&](bool captured) -> int { return lm_batch_enqueue(b, c, p, captured, st, &dc); })) != RCA_OK) return rc;
     if (!warmed) {   // the eager run sized the codec workspace of this (class, shape): graphs are keyed by the signature after it
         if ((rc = rca_codec_workspace_sig(codec, &csig)) != RCA_OK) return rc;
         if (d->warm.size() >= 32) d->warm.clear();
         d->warm.push_back(LmBatchDuplex::Warm{p.cls, a->T, a->F_ctx, n, a->n_samples, (const void*)codec, csig});
     }
-    if ((rc = lm_batch_sel_settle(b, hm, n_sel, n, a->audio_id_floor, a->probe_ids, out->tokens, LM_FRAME_MAX, out->n_done, out->probe_prob, st)) != RCA_OK) return rc;
+    if ((rc = lm_batch_sel_settle(b, c, p.vw.tab, a->audio_id_floor, out->tokens, LM_FRAME_MAX, out->n_done, out->probe_prob, st)) != RCA_OK) return rc;
     const LmBatchDuplexDev* got = reinterpret_cast<const LmBatchDuplexDev*>(d->pin);
     for (int k = 0; k < n_sel; ++k) {
         for (int i = 0; i < LM_FRAME_MAX; ++i) out->user_codes[k * LM_FRAME_MAX + i] = i < n ? got->user_codes[k * n + i] : 0;
