@@ -391,6 +391,31 @@ int rca_lm_eval(rca_lm_t* h, const int32_t* ids, int32_t n);
  * (prefill tiles even for a handful of tokens), so a cache built piecewise equals the cache of a single rca_lm_eval.  Used to build the post-trim KV cache ahead of the sliding-window
  * trim (realtime_agent_v2.py:187-190,725-733) on a weight-sharing twin while the live handle keeps stepping. */
 int rca_lm_eval_async(rca_lm_t* h, const int32_t* ids, int32_t n);
+/* llama.cpp: one llama_decode over a llama_batch that holds prompt tokens of several sequences (llama-server -np N).
+ * rca_lm_eval_async for hs[0..n_h), 1 to 64 distinct handles over one set of weights (a parent and its rca_lm_create_shared twins),
+ * in shared passes of the 128-token tiles: handle k appends counts[k] >= 1 tokens, taken from `ids` concatenated in handle order, at
+ * its own n_tokens.  `ws` is one more handle over the same weights and NOT among hs: the call uses its activation buffers and its
+ * stream (with its priority) only -- its cache, n_tokens and logits are not touched; make it once with rca_lm_create_shared(parent,
+ * a small n_ctx, 0, ...).
+ *   Packing: a pass holds up to 1024 rows; a handle's tokens of a pass start on a multiple of 32 rows (the rows up to the next
+ *   multiple are pad rows: nothing is stored for them), so eight handles x 128 tokens are exactly one pass.  The host cuts longer
+ *   work greedily into passes; a handle's tokens may continue in the next pass.
+ *   Graphs: upload, staging and the layers of a pass whose geometry (its 128-token blocks, the handles' KV format) ws has seen once
+ *   before are captured and replayed; the upload of the pass's block sits inside the graph and everything per handle comes from that
+ *   block, so the graph holds no handle's pointer and lives and dies with ws's other graphs.  The heads (want_logits) follow it as
+ *   plain launches: which handles end in a pass is not part of its geometry.  With rca_lm_set_graphs(ws, 0) or
+ *   RCA_LM_TILE_GRAPHS=0 every pass runs eagerly.
+ *   Contract: the call returns once its last pass is enqueued.  Every hs[k] ends in exactly the state rca_lm_eval_async(hs[k], its
+ *   ids, counts[k]) leaves: n_tokens, and the K / V rows of every layer bit for bit (fp16 and q8_0 caches); with want_logits != 0
+ *   the logits of its last token, bit for bit, too.  want_logits == 0: no head runs and the handles have no logits afterwards, as
+ *   after rca_lm_reset.  Rows above n_tokens and every other handle are untouched.  Any later call on ws or on an hs[k] first waits
+ *   for the pass (rca_lm_sync, rca_lm_destroy and the batch calls included).
+ *   Refused before anything is staged, with NO handle changed and the handle's index in the message: n_h outside 1..64, a null or
+ *   repeated handle, ws among hs, other weights or another device than ws, a logits_all handle, a handle (or ws) whose
+ *   rca_lm_prefill_route is not 2 (such models keep rca_lm_eval_async), mixed KV formats, a count < 1, context overflow
+ *   (RCA_ERR_STATE), an id outside the vocabulary; and the whole call under RCA_LM_FLASH=0 (the split-attention prefill has no
+ *   table form). */
+int rca_lm_batch_eval(rca_lm_t* ws, rca_lm_t* const* hs, int32_t n_h, const int32_t* ids, const int32_t* counts, int32_t want_logits);
 /* The reference recomputes the KV cache of the surviving context inside the frame that trims (realtime_agent_v2.py:725-733:
  * n_tokens = header, eval(suffix)).  Here a twin handle (rca_lm_create_shared, same n_ctx) can be given the header's KV
  * (rca_lm_copy_kv: positions [0, n_pos) of every layer, device to device), be fed the suffix over the preceding frames, and

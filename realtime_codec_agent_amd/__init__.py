@@ -16,6 +16,7 @@ _LAZY = {
     "LlamaForAlternatingCodeChannels": ".llm",
     "LlamaGroup": ".llm",
     "LlamaBatch": ".llm",
+    "LlamaBatchEval": ".llm",
     "MagiCodecHIP": ".codec",
     "HipCodec": ".codec",
     "CodecConfig": ".codec_model",

@@ -323,6 +323,8 @@ class DuplexBatchOutC(C.Structure):
 # int rca_lm_batch_step_sel(b, sel, n_sel, ids, n, probe_ids, n_probe, tokens, probs), argument for argument as in include/rca.h
 _I32P = C.POINTER(C.c_int32)
 BATCH_STEP_SEL_ARGTYPES = [C.c_void_p, _I32P, C.c_int32, _I32P, C.c_int32, _I32P, C.c_int32, _I32P, C.POINTER(C.c_float)]
+# int rca_lm_batch_eval(ws, hs, n_h, ids, counts, want_logits)
+BATCH_EVAL_ARGTYPES = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, _I32P, _I32P, C.c_int32]
 
 
 def sources() -> List[str]:
@@ -446,6 +448,7 @@ ABI_SYMBOLS = [
     "rca_lm_group_create", "rca_lm_group_destroy", "rca_lm_group_step",
     "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
     "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame", "rca_lm_batch_step_sel",
+    "rca_lm_batch_eval",
 ]
 
 
@@ -471,6 +474,9 @@ def lib():
     _lib.rca_version.restype = C.c_char_p
     _lib.rca_lm_batch_step_sel.argtypes = BATCH_STEP_SEL_ARGTYPES
     _lib.rca_lm_batch_step_sel.restype = C.c_int
+    if hasattr(_lib, "rca_lm_batch_eval"):   # (a library from before the call: build() reports the missing symbol)
+        _lib.rca_lm_batch_eval.argtypes = BATCH_EVAL_ARGTYPES
+        _lib.rca_lm_batch_eval.restype = C.c_int
     return _lib
 
 

@@ -2247,6 +2247,15 @@ struct rca_lm {
     GraphSet gset[2];
     unsigned long long gset_clock = 0;
     bool async_pending = false;   // an rca_lm_eval_async pass may still be running on the stream
+    // rca_lm_batch_eval: a pass on ANOTHER handle's stream (the call's workspace) may still be writing this handle's cache, state and
+    // logits.  The call records be_event (this handle's own, made by its first call) behind its last pass; whatever waits for
+    // async_pending waits for it too (lm_wait_batch_eval), so the event outlives the workspace and nothing points at it.
+    bool be_pending = false;
+    hipEvent_t be_event = nullptr;
+    struct LmEvalStage* be_dev = nullptr;   // as the workspace of rca_lm_batch_eval: the pass's block on the device ...
+    struct LmEvalStage* be_pin = nullptr;   // ... and its pinned staging copy (made by the first call)
+    hipGraphExec_t be_g[LM_MAXM / 128][2] = {};   // ... and its captured passes, per (token blocks of the pass, KV format of the handles)
+    int be_seen[LM_MAXM / 128][2] = {};           //     passes of that geometry so far: the first runs eagerly, the second is captured
     unsigned long long rng_host = 0;   // host mirror of the device's draw counter (restored when a frame graph is cut short)
     bool graphs_enabled = true;
     unsigned long long graph_epoch = 0;   // bumped by whatever invalidates graphs captured over this handle (lm_drop_graphs, rca_lm_swap_kv): a group
@@ -2271,6 +2280,16 @@ struct rca_lm {
     size_t sc_pin_cap = 0;
     hipEvent_t sc_ready = nullptr, sc_free = nullptr;   // base: block logits written; scored handle: block logits consumed
 };
+// an rca_lm_batch_eval pass over this handle may still be running on its workspace's stream: wait for it (every place that waits for
+// the handle's own stream before it reads or changes the handle does)
+static int lm_wait_batch_eval(rca_lm* h) {
+    if (h->be_pending) {
+        RCA_HIP(hipSetDevice(h->device));
+        RCA_HIP(hipEventSynchronize(h->be_event));
+        h->be_pending = false;
+    }
+    return RCA_OK;
+}
 // ---- the two KV formats behind one pair of pointers (kv_layer_stride: elements of a layer = bytes of a layer's int8 plane)
 static bool lm_kv_q8(const rca_lm* h) { return h->kv_format == 1; }
 static size_t lm_kv_plane_bytes(const rca_lm* h) {
@@ -2364,6 +2383,10 @@ static void lm_drop_graphs(rca_lm* h) {
     h->graph_epoch++;
     h->drop_epoch++;
     for (auto& gs : h->gset) lm_drop_graph_set(gs);
+    for (auto& per_tbz : h->be_g)
+        for (hipGraphExec_t& e : per_tbz)
+            if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+    memset(h->be_seen, 0, sizeof(h->be_seen));
     duplex_drop_graphs(h->duplex);
 }
 // the graph set captured over the KV cache that is installed now (evicting the older set if neither matches)
@@ -2403,6 +2426,10 @@ extern "C" int rca_lm_destroy(rca_lm_t* h) {
     if (!h) return RCA_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)lm_wait_batch_eval(h);
+    if (h->be_event) { (void)hipEventDestroy(h->be_event); h->be_event = nullptr; }
+    if (h->be_dev) { (void)hipFree(h->be_dev); h->be_dev = nullptr; }
+    if (h->be_pin) { (void)hipHostFree(h->be_pin); h->be_pin = nullptr; }
     lm_drop_graphs(h);
     duplex_destroy(h->duplex);
     h->duplex = nullptr;
@@ -3419,6 +3446,41 @@ __global__ __launch_bounds__(256) void lm_kv_quant_kernel(const LmDevState* __re
     (tensor ? vq : kq)[((long)pos * nkv) * 64 + hb * 32 + j] = (signed char)(int)roundf(x * inv);
     if (j == 0) (tensor ? vd : kd)[((long)pos * nkv) * 2 + hb] = (f16_t)d;
 }
+// rca_lm_batch_eval: grid (blocks of 8 units, row of the pass).  A row finds its segment through the pass's owner map (one entry per
+// 32 rows) and takes ring, planes, scales, position and context bound from the segment's entry; pad rows leave.  One geometry for
+// every packing of a pass of the same token blocks, so a captured pass holds no segment count.
+__global__ __launch_bounds__(256) void lm_kv_quant_rows_kernel(const LmDevState* __restrict__ pstt, const LmBatchMember* __restrict__ tab,
+                                                               const int* __restrict__ owner, int tab_layer, int nkv) {
+    const int row = blockIdx.y;
+    if (row >= pstt->m) return;
+    const int seg = owner[row >> 5];
+    if (seg < 0) return;
+    const LmBatchMember e = tab[seg];
+    const int tok = row - e.row0;
+    if (tok >= e.stt->m) return;
+    const int pos = e.stt->n_tokens + tok;
+    if (pos >= e.n_ctx) return;
+    // from here on: lm_kv_quant_kernel's arithmetic on the segment's ring, planes and scales
+    const f16_t* ring_k = e.ring_k; const f16_t* ring_v = e.ring_v;
+    const int ring_mask = e.ring_mask, which = 3;
+    signed char* kq = reinterpret_cast<signed char*>(const_cast<f16_t*>(e.kc)) + (long)tab_layer * e.kv_stride;
+    signed char* vq = reinterpret_cast<signed char*>(const_cast<f16_t*>(e.vc)) + (long)tab_layer * e.kv_stride;
+    f16_t* kd = reinterpret_cast<f16_t*>(reinterpret_cast<char*>(const_cast<f16_t*>(e.kc)) + e.sc_off) + (long)tab_layer * (e.kv_stride >> 5);
+    f16_t* vd = reinterpret_cast<f16_t*>(reinterpret_cast<char*>(const_cast<f16_t*>(e.vc)) + e.sc_off) + (long)tab_layer * (e.kv_stride >> 5);
+    const int unit = blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (unit >= 4 * nkv) return;
+    const int tensor = unit / (2 * nkv), hb = unit - tensor * 2 * nkv;   // hb = kv head * 2 + block
+    if (!((which >> tensor) & 1)) return;
+    const int j = threadIdx.x & 31;
+    const float x = (float)(tensor ? ring_v : ring_k)[((long)(pos & ring_mask) * nkv) * 64 + hb * 32 + j];
+    float amax = fabsf(x);
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 32));
+    const float d = amax / 127.0f;
+    const float inv = d != 0.0f ? 1.0f / d : 0.0f;
+    (tensor ? vq : kq)[((long)pos * nkv) * 64 + hb * 32 + j] = (signed char)(int)roundf(x * inv);
+    if (j == 0) (tensor ? vd : kd)[((long)pos * nkv) * 2 + hb] = (f16_t)d;
+}
 // rca_lm_kv_read / rca_lm_gemv_tap on a q8_0 cache: n16 pieces of 16 values, de-quantised by the code attention stages rows with
 __global__ __launch_bounds__(256) void lm_kv_dequant_kernel(const signed char* __restrict__ q, const f16_t* __restrict__ d, f16_t* __restrict__ out, long n16) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -3944,12 +4006,21 @@ __global__ __launch_bounds__(64) void lm_attn_mfma_batch_combine_kernel(const Lm
 // per workgroup: 414 .. 730 key blocks per CU, the last CU done at 135 us against a median of 101); the four tiles of workgroup j
 // are j, 2 n - 1 - j, 2 n + j and 4 n - 1 - j of the head's 4 n tiles, whose causal lengths add up to the same total for every j.
 // KVQ = 1: q8_0 cache (see lm_attn_mfma_kernel): the block in flight is 2 x 16 int8 per lane and tensor plus the blocks' scales
-template <int G, int TEAMS, int KVQ = 0>
+// TAB = true (rca_lm_batch_eval): the rows of the pass are SEGMENTS of several sessions, every segment starting on a multiple of 32
+// rows, so a tile (8 / 16 / 32 tokens) lies inside one segment.  `stt` is the pass's state (m = its padded row count); a tile finds
+// its segment in owner[first row / 32] (-1: pad rows, the team idles as one past the pass does) and takes from tab[segment] what the
+// other instances take from "the" handle: position and token count (the session's own step state), cache (+ layer, q8_0 scales),
+// context bound, and its first row in qkv / hi / lo.  From there on a tile is the tile at the same LOCAL row of that session's own
+// pass -- same keys on the same waves in the same order -- so its rows carry that pass's bits.  kc / vc / kd / vd / n_ctx are unused.
+// The TAB = false instances are the kernel as it was before the table existed.
+template <int G, int TEAMS, int KVQ = 0, bool TAB = false>
 __global__ __launch_bounds__(64 * FLASH_WAVES * TEAMS, 3) void lm_attn_flash_kernel(const LmDevState* __restrict__ stt, const float* __restrict__ qkv,
                                                                         const f16_t* __restrict__ kc, const f16_t* __restrict__ vc,
                                                                         float* __restrict__ attn_out, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo,
                                                                         int nh, int nkv, float scale, int n_ctx,
-                                                                        const f16_t* __restrict__ kd = nullptr, const f16_t* __restrict__ vd = nullptr) {
+                                                                        const f16_t* __restrict__ kd = nullptr, const f16_t* __restrict__ vd = nullptr,
+                                                                        const LmBatchMember* __restrict__ tab = nullptr, const int* __restrict__ owner = nullptr,
+                                                                        int tab_layer = 0) {
     constexpr int HD = 64;
     constexpr int TPB = 32 / G;   // tokens per tile
     constexpr int NWAVES = FLASH_WAVES * TEAMS;
@@ -3967,7 +4038,7 @@ __global__ __launch_bounds__(64 * FLASH_WAVES * TEAMS, 3) void lm_attn_flash_ker
     float (*mrg_l)[32] = mrg_l_all + team * FLASH_WAVES;
     char* const kbytes = reinterpret_cast<char*>(flash_lds) + wave_all * 8192;   // K image of the current key block: [key][128 bytes]
     char* const vbytes = kbytes + 4096;                                          // V image
-    const int M = stt->m;
+    int M = stt->m;
     const int ntiles = (M + TPB - 1) / TPB;
     int tile = blockIdx.y;
     if (TEAMS == 4) {
@@ -3976,15 +4047,42 @@ __global__ __launch_bounds__(64 * FLASH_WAVES * TEAMS, 3) void lm_attn_flash_ker
     } else if (TEAMS == 2) {
         tile = team == 0 ? (int)blockIdx.y : 2 * (int)gridDim.y - 1 - (int)blockIdx.y;
     }
-    const bool active = tile < ntiles;   // team-uniform; an idle team still takes part in the workgroup's barriers
-    if (TEAMS == 1 && !active) return;
-    const int t0 = min(tile, ntiles - 1) * TPB;
+    bool active = tile < ntiles;   // team-uniform; an idle team still takes part in the workgroup's barriers
+    int t0, pos0 = 0;
+    if constexpr (TAB) {
+        // the tile's segment.  An idle team (a tile past the pass, pad rows, the unused tail of a segment) runs the prologue on the first
+        // tile of segment 0 -- every address it forms is a valid one -- with no key blocks, and leaves before the merge.
+        const int seg = active ? owner[(tile * TPB) >> 5] : -1;
+        const LmBatchMember e = tab[max(seg, 0)];
+        t0 = seg >= 0 ? tile * TPB - e.row0 : 0;   // from here on: the row inside the segment
+        M = e.stt->m;
+        active = seg >= 0 && t0 < M;
+        if (!active) t0 = 0;
+        if (TEAMS == 1 && !active) return;
+        pos0 = e.stt->n_tokens;
+        n_ctx = e.n_ctx;
+        qkv += (long)e.row0 * (nh + 2 * nkv) * HD;
+        hi += (long)e.row0 * nh * HD;
+        lo += (long)e.row0 * nh * HD;
+        if constexpr (KVQ) {   // int8 planes: kv_stride in bytes; the scales sc_off bytes behind them (LmBatchMember)
+            kd = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(e.kc) + e.sc_off) + (long)tab_layer * (e.kv_stride >> 5);
+            vd = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(e.vc) + e.sc_off) + (long)tab_layer * (e.kv_stride >> 5);
+            kc = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(e.kc) + (long)tab_layer * e.kv_stride);
+            vc = reinterpret_cast<const f16_t*>(reinterpret_cast<const char*>(e.vc) + (long)tab_layer * e.kv_stride);
+        } else {
+            kc = e.kc + (long)tab_layer * e.kv_stride;
+            vc = e.vc + (long)tab_layer * e.kv_stride;
+        }
+    } else {
+        if (TEAMS == 1 && !active) return;
+        t0 = min(tile, ntiles - 1) * TPB;
+    }
 #ifdef RCA_ATTN_TIMELINE
     long* const ftl = rca_flash_tl ? rca_flash_tl + ((long)(blockIdx.y * gridDim.x + blockIdx.x) * NWAVES + wave_all) * 16 : nullptr;
     long ftl_acc[4] = {0, 0, 0, 0}, ftl_t = 0, ftl_n = 0;
     const long ftl_entry = (long)wall_clock64();
 #endif
-    const int pos0 = stt->n_tokens;
+    if constexpr (!TAB) pos0 = stt->n_tokens;
     const int ntok = min(TPB, M - t0);
     const int tl = min(col / G, ntok - 1), hq = col % G;   // rows past the pass repeat the last valid token's: they are never stored
     const int ld = (nh + 2 * nkv) * HD;
@@ -4305,6 +4403,33 @@ static void launch_attention_flash(rca_lm* h, int M, const f16_t* kc, const f16_
     if (G == 4) launch_attention_flash_g<4>(h, M, kc, vc, st, hi, lo, kd, vd);
     else if (G == 2) launch_attention_flash_g<2>(h, M, kc, vc, st, hi, lo, kd, vd);
     else launch_attention_flash_g<1>(h, M, kc, vc, st, hi, lo, kd, vd);
+}
+// what a pass of rca_lm_batch_eval reads about its segments (device pointers into the block the pass uploaded)
+struct LmEvalTables {
+    const LmGroupRow* rows;      // [padded rows of the pass]: the QKV epilogue's row table; a pad row has n_ctx 0 and stores nothing
+    const LmBatchMember* tab;    // [n_seg]
+    const int* owner;            // [LM_MAXM / 32]: segment of every 32 rows, -1 = pad rows behind the last segment
+    bool q8;
+};
+// the table instance: one launch for every segment of the pass; TEAMS from the pass's total tile count by the rule above
+template <int G>
+static void launch_attention_flash_tab_g(rca_lm* h, int rows, hipStream_t st, bf16_t* hi, bf16_t* lo, const LmEvalTables& t, int l) {
+    const rca_lm_config_t& c = h->cfg;
+    const float scale = 1.0f / sqrtf((float)c.head_dim);
+    const int ntiles = cdiv(rows * G, 32);
+#define RCA_FLASH_TAB(TEAMS, KVQ)                                                                                                       \
+    lm_attn_flash_kernel<G, TEAMS, KVQ, true><<<dim3(c.n_kv_heads, cdiv(ntiles, TEAMS)), 64 * FLASH_WAVES * TEAMS, 0, st>>>(              \
+        h->stt, h->qkv, nullptr, nullptr, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, 0, nullptr, nullptr, t.tab, t.owner, l)
+    if (c.n_kv_heads * cdiv(ntiles, 4) >= h->n_cus) { if (t.q8) RCA_FLASH_TAB(4, 1); else RCA_FLASH_TAB(4, 0); }
+    else if (c.n_kv_heads * cdiv(ntiles, 2) >= h->n_cus) { if (t.q8) RCA_FLASH_TAB(2, 1); else RCA_FLASH_TAB(2, 0); }
+    else { if (t.q8) RCA_FLASH_TAB(1, 1); else RCA_FLASH_TAB(1, 0); }
+#undef RCA_FLASH_TAB
+}
+static void launch_attention_flash_tab(rca_lm* h, int rows, hipStream_t st, bf16_t* hi, bf16_t* lo, const LmEvalTables& t, int l) {
+    const int G = h->cfg.n_heads / h->cfg.n_kv_heads;
+    if (G == 4) launch_attention_flash_tab_g<4>(h, rows, st, hi, lo, t, l);
+    else if (G == 2) launch_attention_flash_tab_g<2>(h, rows, st, hi, lo, t, l);
+    else launch_attention_flash_tab_g<1>(h, rows, st, hi, lo, t, l);
 }
 // the q8_0 quantiser of layer l over the rows the pass has just stored into the ring (nothing to do for an fp16 cache).  m_max: the
 // most tokens the pass can have (the grid); the live count and the position are read on the device
@@ -4958,10 +5083,13 @@ static void launch_gemm128(rca_lm* h, const WMat& w, dim3 grid, hipStream_t st, 
                                                                                                  h->gpart, rope, nseq, grp);
     });
 }
-static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch) {
+// bt (rca_lm_batch_eval): the rows are segments of several sessions packed into h's buffers (h is the call's workspace, h->stt the
+// pass's state; M is the pass's whole token blocks, the launch geometry, and h->stt->m the rows that exist).  The row-wise stages and the GEMMs are the same launches; what is per session -- the QKV epilogue's position and
+// cache, the q8_0 quantiser, attention -- takes it from the pass's tables.
+static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch, const LmEvalTables* bt = nullptr) {
     const rca_lm_config_t& c = h->cfg;
     const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn;
-    GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
+    GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, bt ? 0 : c.n_ctx, 0};   // bt: cache, position and context bound per row
     const int so = g128_splits(H, AO), sg = g128_splits(2 * F, H), sd = g128_splits(H, F);
     const int tbz = cdiv(M, 128);   // token blocks of this pass
     // A projection whose token blocks alone put `seq_min` workgroups on the chip is run with every workgroup walking the k slices itself
@@ -4975,19 +5103,31 @@ static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_
         const LmLayer& L = h->layers[l];
         f16_t* kc = lm_kv_layer(h, h->kc, l);
         f16_t* vc = lm_kv_layer(h, h->vc, l);
-        lm_rope_target(h, l, rope);
+        if (!bt) lm_rope_target(h, l, rope);
         lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.attn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
         for (int seg = 0; seg < (L.split_v ? 2 : 1); ++seg) {   // [q; k; v] as one matrix, or [q; k] and v when their formats differ
             const WMat& w = seg ? L.vseg : L.qkv;
             const int Ns = w.N, ss = g128_splits(Ns, H);
             const G128Form fq = g128_form(Ns, ss, tbz, seq_min);
             rope.row_base = seg ? L.qkv.N : 0;
+            if (bt) {
+                const GemvGroup grp{bt->rows, l};
+                launch_gemm128<GEMM_EPI_ROPE_ROWS>(h, w, dim3(Ns / 128, fq.grid_y, tbz), st, h->xh, h->xl, Ns, H, H / ss, h->qkv, QKV, nullptr, nullptr, rope, fq.nseq, nullptr, grp);
+                if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE_ROWS><<<dim3(Ns / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fq.ep_nsplit, fq.ep_grp, Ns, h->qkv, QKV, nullptr, nullptr, rope, grp);
+                continue;
+            }
             launch_gemm128<GEMM_EPI_ROPE>(h, w, dim3(Ns / 128, fq.grid_y, tbz), st, h->xh, h->xl, Ns, H, H / ss, h->qkv, QKV, nullptr, nullptr, rope, fq.nseq);
             if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE><<<dim3(Ns / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fq.ep_nsplit, fq.ep_grp, Ns, h->qkv, QKV, nullptr, nullptr, rope, nogroup);
         }
         rope.row_base = 0;
-        lm_launch_kv_quant(h, l, M, st);
-        launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, h->xh, h->xl, true);
+        if (bt) {
+            if (bt->q8)   // every segment's new rows, ring -> int8 planes, in one launch
+                lm_kv_quant_rows_kernel<<<dim3(cdiv(4 * c.n_kv_heads, 8), M), 256, 0, st>>>(h->stt, bt->tab, bt->owner, l, c.n_kv_heads);
+            launch_attention_flash_tab(h, M, st, h->xh, h->xl, *bt, l);
+        } else {
+            lm_launch_kv_quant(h, l, M, st);
+            launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, h->xh, h->xl, true);
+        }
         launch_gemm128<GEMM_EPI_RESID>(h, L.o, dim3(H / 128, fo.grid_y, tbz), st, h->xh, h->xl, H, AO, AO / so, x, H, nullptr, nullptr, norope, fo.nseq);
         if (fo.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fo.ep_nsplit, fo.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
         lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.ffn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
@@ -5014,6 +5154,7 @@ static int lm_prefill_route(const rca_lm* h) {
 
 // an rca_lm_eval_async pass may still own the pinned staging block and the activations: wait for it before anything else runs
 static int lm_settle(rca_lm* h) {
+    { const int rc = lm_wait_batch_eval(h); if (rc != RCA_OK) return rc; }
     if (h->async_pending) {
         RCA_HIP(hipSetDevice(h->device));
         RCA_HIP(hipStreamSynchronize(h->stream));
@@ -5070,6 +5211,7 @@ extern "C" int rca_lm_sync(rca_lm_t* h) {
     RCA_HIP(hipSetDevice(h->device));
     RCA_HIP(hipStreamSynchronize(h->stream));
     h->async_pending = false;
+    { const int rc = lm_wait_batch_eval(h); if (rc != RCA_OK) return rc; }
     return RCA_OK;
 }
 
@@ -5086,6 +5228,7 @@ static int lm_eval_impl(rca_lm_t* h, const int32_t* ids, int32_t n, bool wait_la
     hipStream_t st = h->stream;
     int rc;
     if (h->async_pending) { RCA_HIP(hipStreamSynchronize(st)); h->async_pending = false; }
+    if ((rc = lm_wait_batch_eval(h)) != RCA_OK) return rc;
     const bool all = h->cfg.logits_all != 0;
     if (all && n > h->logits_rows_cap) {
         RCA_HIP(hipStreamSynchronize(st));
@@ -5187,6 +5330,7 @@ extern "C" int rca_lm_copy_kv(rca_lm_t* dst, rca_lm_t* src, int32_t n_pos) {
     RCA_HIP(hipSetDevice(dst->device));
     RCA_HIP(hipStreamSynchronize(src->stream));   // everything src has evaluated so far is in its cache
     src->async_pending = false;
+    { int rc; if ((rc = lm_wait_batch_eval(src)) != RCA_OK || (rc = lm_wait_batch_eval(dst)) != RCA_OK) return rc; }
     if (dst->async_pending) { RCA_HIP(hipStreamSynchronize(dst->stream)); dst->async_pending = false; }
     const size_t rows = (size_t)n_pos * src->cfg.n_kv_heads;   // head rows per layer: 128 bytes of fp16, or 64 int8 + two fp16 scales
     const size_t bytes = rows * (lm_kv_q8(src) ? 64 : 64 * sizeof(f16_t));
@@ -5209,6 +5353,7 @@ extern "C" int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b) {
     RCA_HIP(hipStreamSynchronize(a->stream));
     RCA_HIP(hipStreamSynchronize(b->stream));
     a->async_pending = b->async_pending = false;
+    { int rc; if ((rc = lm_wait_batch_eval(a)) != RCA_OK || (rc = lm_wait_batch_eval(b)) != RCA_OK) return rc; }
     std::swap(a->kc, b->kc);
     std::swap(a->vc, b->vc);
     a->graph_epoch++;   // the handles' own graph sets are keyed by the cache; a group's graphs over either handle are not
@@ -5329,6 +5474,7 @@ extern "C" int rca_lm_kv_read(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t 
     RCA_HIP(hipSetDevice(h->device));
     RCA_HIP(hipStreamSynchronize(h->stream));
     h->async_pending = false;
+    { const int rc = lm_wait_batch_eval(h); if (rc != RCA_OK) return rc; }
     const long off = (long)layer * h->kv_layer_stride + (long)pos0 * c.n_kv_heads * 64;
     const size_t bytes = (size_t)n_pos * c.n_kv_heads * 64 * sizeof(f16_t);
     if (lm_kv_q8(h)) {
@@ -5351,6 +5497,7 @@ extern "C" int rca_lm_kv_read_q8(rca_lm_t* h, int32_t layer, int32_t pos0, int32
     RCA_HIP(hipSetDevice(h->device));
     RCA_HIP(hipStreamSynchronize(h->stream));
     h->async_pending = false;
+    { const int rc = lm_wait_batch_eval(h); if (rc != RCA_OK) return rc; }
     const long off = (long)pos0 * c.n_kv_heads * 64;
     const size_t n = (size_t)n_pos * c.n_kv_heads * 64;
     if (!n) return RCA_OK;
@@ -5369,6 +5516,7 @@ extern "C" int rca_lm_kv_write(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t
     RCA_HIP(hipSetDevice(h->device));
     RCA_HIP(hipStreamSynchronize(h->stream));
     h->async_pending = false;
+    { const int rc = lm_wait_batch_eval(h); if (rc != RCA_OK) return rc; }
     const long off = (long)layer * h->kv_layer_stride + (long)pos0 * c.n_kv_heads * 64;
     const size_t bytes = (size_t)n_pos * c.n_kv_heads * 64 * sizeof(f16_t);
     if (lm_kv_q8(h)) {   // through the ring, at most LM_KV_RING positions at a time, at the slots a pass would use
@@ -5401,6 +5549,7 @@ extern "C" int rca_lm_set_low_priority(rca_lm_t* h, int32_t enable) {
     RCA_HIP(hipStreamCreateWithPriority(&ns, hipStreamNonBlocking, enable ? lo : hi));
     RCA_HIP(hipStreamSynchronize(h->stream));
     h->async_pending = false;
+    { const int rc = lm_wait_batch_eval(h); if (rc != RCA_OK) return rc; }
     (void)hipStreamDestroy(h->stream);
     h->stream = ns;
     return RCA_OK;
@@ -5797,6 +5946,193 @@ extern "C" int rca_lm_group_step(rca_lm_group_t* g, const int32_t* ids, int32_t 
         h->rng_host += 1;
         tokens[s] = g->pin->tokens[s];
     }
+    return RCA_OK;
+}
+
+// ------------------------------------------------------------------------------------ batch eval (rca_lm_batch_eval)
+// rca_lm_eval_async for several sessions over ONE set of weights in one pass of the 128-token tiles: the prompt tokens of up to 64
+// handles are packed into the activation buffers of a WORKSPACE handle (one more rca_lm_create_shared twin, whose cache, n_tokens and
+// logits the call never touches) and run on its stream, so every matrix is streamed once per pass, not once per handle.
+// Packing: a handle's tokens of the pass are one SEGMENT, and every segment starts on a multiple of 32 rows: no flash tile (8 / 16 / 32
+// tokens) and no 32-row group of the k-split epilogue spans two handles.  The rows between a segment's last token and the next
+// multiple of 32 are pad rows: they run through the row-wise stages and the GEMMs like any row (a GEMM row depends on its own input
+// row only), their table entry has a context bound of 0, so the QKV epilogue stores nothing for them, and no attention tile owns them.
+// Why a handle ends with the bits of its own rca_lm_eval_async: the row-wise stages and the GEMMs do not know which pass a row is in
+// (the k-split form changes no bit: g128_form), the QKV epilogue and the q8_0 quantiser take position and cache per row / segment, and
+// a query row of the flash kernel depends on its own position only.  How the host cuts the work into passes is free for the same reason.
+#define LM_EVAL_MAXH 64
+#define LM_EVAL_SEGS (LM_MAXM / 32)
+// the block one pass uploads (its head: everything in front of the row table, then one row entry per padded row of the pass)
+struct LmEvalStage {
+    int rows, n_seg;                              // padded rows of the pass; its segments
+    int pos0[LM_EVAL_SEGS], cnt[LM_EVAL_SEGS];    // a segment's first KV position and token count
+    int owner[LM_EVAL_SEGS];                      // rows 32 i .. 32 i + 31 -> segment, -1 behind the pass
+    int ids[LM_MAXM];                             // a pad row carries id 0
+    LmBatchMember tab[LM_EVAL_SEGS];
+    LmGroupRow head[2 * LM_EVAL_SEGS];            // want_logits: the rows of the grouped head launches (2 or 4 entries per launch)
+    LmGroupRow rowtab[LM_MAXM];
+};
+struct LmEvalSeg { int k, done, cnt, row0; };     // handle index, tokens of it evaluated before this pass, tokens in it, first row
+// the pass's state (into the workspace's LmDevState) and every segment's own step state, as lm_push_state would leave it
+__global__ __launch_bounds__(LM_MAXM) void lm_eval_stage_kernel(const LmEvalStage* __restrict__ in, LmDevState* __restrict__ pstt) {
+    const int t = threadIdx.x, rows = in->rows;
+    if (t == 0) { pstt->n_tokens = 0; pstt->m = rows; }
+    if (t >= rows) return;
+    pstt->ids[t] = in->ids[t];
+    const int seg = in->owner[t >> 5];
+    if (seg < 0) return;
+    LmDevState* stt = in->tab[seg].stt;
+    const int j = t - in->tab[seg].row0;
+    if (j == 0) { stt->n_tokens = in->pos0[seg]; stt->m = in->cnt[seg]; }
+    if (j < in->cnt[seg]) stt->ids[j] = in->ids[t];
+}
+// one pass: fill the pinned block, upload, stage, the layers, and the head of every handle whose last token is in this pass
+static int lm_eval_pass(rca_lm* ws, rca_lm* const* hs, const int32_t* const* ids_of, const int32_t* counts, const LmEvalSeg* segs, int n_seg, int rows,
+                        bool want_logits, hipStream_t st) {
+    LmEvalStage& in = *ws->be_pin;
+    memset(&in, 0, offsetof(LmEvalStage, rowtab));
+    in.rows = rows;
+    in.n_seg = n_seg;
+    for (int i = 0; i < LM_EVAL_SEGS; ++i) in.owner[i] = -1;
+    int n_fin = 0;
+    LmGroupRow fin[LM_EVAL_SEGS];   // the last rows of the handles that end in this pass ...
+    rca_lm* fin_h[LM_EVAL_SEGS];    // ... and those handles
+    for (int s = 0; s < n_seg; ++s) {
+        const LmEvalSeg& sg = segs[s];
+        rca_lm* h = hs[sg.k];
+        const int pad = (sg.cnt + 31) & ~31;
+        in.pos0[s] = h->n_tokens + sg.done;
+        in.cnt[s] = sg.cnt;
+        in.tab[s] = lm_batch_member(h, sg.row0, false);
+        for (int r = sg.row0; r < sg.row0 + pad; r += 32) in.owner[r >> 5] = s;
+        for (int j = 0; j < pad; ++j) {
+            const int r = sg.row0 + j;
+            if (j < sg.cnt) {
+                in.ids[r] = ids_of[sg.k][sg.done + j];
+                in.rowtab[r] = lm_group_row(h, j, r);
+            } else {   // a pad row: position 0 of a context of 0 -- the epilogue stores nothing
+                in.rowtab[r] = LmGroupRow{ws->stt, nullptr, nullptr, nullptr, 0, 0, r, 0, 0};
+            }
+        }
+        if (want_logits && sg.done + sg.cnt == counts[sg.k]) {   // its last token: row of x, its own logits buffer
+            fin[n_fin] = lm_group_row(h, sg.cnt - 1, sg.row0 + sg.cnt - 1);
+            fin_h[n_fin++] = h;
+        }
+    }
+    // head launches of 2 or 4 rows: up to LM_GROUP_MAX consecutive handles of one activation format (the head GEMV of a handle's own eval
+    // reads that handle's); a short launch repeats its last row -- same row of x, same destination, same values
+    int n_head = 0, n_launch = 0, head_at[LM_EVAL_SEGS], head_m[LM_EVAL_SEGS];
+    rca_lm* launch_h[LM_EVAL_SEGS];
+    for (int i = 0; i < n_fin;) {
+        int real = 1;
+        while (real < LM_GROUP_MAX && i + real < n_fin && fin_h[i + real]->act_format == fin_h[i]->act_format) ++real;
+        const int m = real <= 2 ? 2 : 4;
+        head_at[n_launch] = n_head;
+        head_m[n_launch] = m;
+        launch_h[n_launch++] = fin_h[i];
+        for (int j = 0; j < m; ++j) in.head[n_head++] = fin[i + std::min(j, real - 1)];
+        i += real;
+    }
+    // upload -> stage -> the layers, launched at the geometry of the pass's whole token blocks (the kernels read the row count from the
+    // state): one sequence for every packing of tbz blocks, captured when the geometry is seen a second time and replayed from then
+    // on.  The upload sits inside it and everything per session comes from the uploaded block: the graph holds the workspace's
+    // pointers only, and goes when the workspace drops its graphs (lm_drop_graphs).
+    const int tbz = cdiv(rows, 128), q8 = lm_kv_q8(hs[segs[0].k]) ? 1 : 0;
+    const size_t up = offsetof(LmEvalStage, rowtab) + (size_t)tbz * 128 * sizeof(LmGroupRow);
+    const LmEvalTables bt{ws->be_dev->rowtab, ws->be_dev->tab, ws->be_dev->owner, q8 != 0};
+    auto layers = [&]() -> int {
+        hipError_t e = hipMemcpyAsync(ws->be_dev, ws->be_pin, up, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch_eval upload: %s", hipGetErrorString(e));
+        lm_eval_stage_kernel<<<1, LM_MAXM, 0, st>>>(ws->be_dev, ws->stt);
+        return lm_enqueue_prefill_tile128(ws, tbz * 128, st, 1, &bt);
+    };
+    static const bool tile_graphs = !(getenv("RCA_LM_TILE_GRAPHS") && atoi(getenv("RCA_LM_TILE_GRAPHS")) == 0);
+    int rc;
+    if (ws->graphs_enabled && tile_graphs && ++ws->be_seen[tbz - 1][q8] >= 2) {
+        hipGraphExec_t& g = ws->be_g[tbz - 1][q8];
+        if (!g && (rc = lm_capture(st, &g, "batch eval", layers)) != RCA_OK) return rc;
+        RCA_HIP(hipGraphLaunch(g, st));
+    } else if ((rc = layers()) != RCA_OK) {
+        return rc;
+    }
+    // the heads run behind it, eagerly: which handles end in a pass is not part of its geometry
+    const rca_lm_config_t& c = ws->cfg;
+    for (int i = 0; i < n_launch; ++i)   // final norm + head on the register GEMV, up to four handles per stream of the head matrix
+        launch_gemv<1, 0, 1>(GEMV_HEAD, launch_h[i], head_m[i], ws->head, nullptr, nullptr, c.vocab_size, c.hidden, c.vocab_size,
+                             GemvPro{ws->x, ws->final_norm, c.rms_eps, 1}, norope, st, GemvGroup{ws->be_dev->head + head_at[i], 0});
+    RCA_LAUNCH_CHECK();
+    return RCA_OK;
+}
+extern "C" int rca_lm_batch_eval(rca_lm_t* ws, rca_lm_t* const* hs, int32_t n_h, const int32_t* ids, const int32_t* counts, int32_t want_logits) {
+    if (!ws || !hs || !ids || !counts) return fail(RCA_ERR_ARG, "batch_eval: null argument");
+    if (n_h < 1 || n_h > LM_EVAL_MAXH) return fail(RCA_ERR_ARG, "batch_eval: %d handles (1..%d)", n_h, LM_EVAL_MAXH);
+    static const bool flash = !(getenv("RCA_LM_FLASH") && atoi(getenv("RCA_LM_FLASH")) == 0);
+    if (!flash) return fail(RCA_ERR_STATE, "batch_eval: RCA_LM_FLASH=0 asks for the split-attention prefill, which has no table form; use rca_lm_eval_async");
+    if (lm_prefill_route(ws) != LM_ROUTE_TILE128)
+        return fail(RCA_ERR_ARG, "batch_eval: the workspace does not take the 128-token tiles (rca_lm_prefill_route %d, the call needs 2)", lm_prefill_route(ws));
+    // every refusal before anything is staged or enqueued: no handle changes
+    const int32_t* ids_of[LM_EVAL_MAXH];
+    long off = 0;
+    for (int k = 0; k < n_h; ++k) {
+        const rca_lm* h = hs[k];
+        if (!h) return fail(RCA_ERR_ARG, "batch_eval: handle %d is null", k);
+        if (h == ws) return fail(RCA_ERR_ARG, "batch_eval: handle %d is the workspace", k);
+        for (int t = 0; t < k; ++t)
+            if (hs[t] == h) return fail(RCA_ERR_ARG, "batch_eval: handle %d is the same handle as handle %d", k, t);
+        if (h->device != ws->device) return fail(RCA_ERR_ARG, "batch_eval: handle %d is on device %d, the workspace on device %d", k, h->device, ws->device);
+        if (lm_weight_owner(h) != lm_weight_owner(ws))
+            return fail(RCA_ERR_ARG, "batch_eval: handle %d does not share the workspace's weights (rca_lm_create_shared makes handles that do)", k);
+        if (h->cfg.logits_all) return fail(RCA_ERR_ARG, "batch_eval: handle %d is a logits_all handle (the call keeps the last position's logits only)", k);
+        if (lm_prefill_route(h) != LM_ROUTE_TILE128)
+            return fail(RCA_ERR_ARG, "batch_eval: handle %d does not take the 128-token tiles (rca_lm_prefill_route %d, the call needs 2); such models keep rca_lm_eval_async",
+                        k, lm_prefill_route(h));
+        if (h->kv_format != hs[0]->kv_format) return fail(RCA_ERR_ARG, "batch_eval: handle %d has KV format %d, handle 0 has %d", k, h->kv_format, hs[0]->kv_format);
+        if (counts[k] < 1) return fail(RCA_ERR_ARG, "batch_eval: handle %d has %d tokens (at least 1)", k, counts[k]);
+        if (h->n_tokens + counts[k] > h->cfg.n_ctx)
+            return fail(RCA_ERR_STATE, "batch_eval: context overflow of handle %d: %d + %d > n_ctx %d", k, h->n_tokens, counts[k], h->cfg.n_ctx);
+        ids_of[k] = ids + off;
+        for (int j = 0; j < counts[k]; ++j)
+            if (ids_of[k][j] < 0 || ids_of[k][j] >= h->cfg.vocab_size)
+                return fail(RCA_ERR_ARG, "batch_eval: token id %d of handle %d at index %d is outside the vocabulary [0, %d)", ids_of[k][j], k, j, h->cfg.vocab_size);
+        off += counts[k];
+    }
+    int rc;
+    if ((rc = lm_settle(ws)) != RCA_OK) return rc;
+    for (int k = 0; k < n_h; ++k)
+        if ((rc = lm_settle(hs[k])) != RCA_OK) return rc;
+    RCA_HIP(hipSetDevice(ws->device));
+    if (!ws->be_dev && (rc = lm_alloc((void**)&ws->be_dev, sizeof(LmEvalStage))) != RCA_OK) return rc;
+    if (!ws->be_pin && hipHostMalloc((void**)&ws->be_pin, sizeof(LmEvalStage), hipHostMallocDefault) != hipSuccess) return fail(RCA_ERR_HIP, "batch_eval: pinned staging");
+    for (int k = 0; k < n_h; ++k)
+        if (!hs[k]->be_event) RCA_HIP(hipEventCreateWithFlags(&hs[k]->be_event, hipEventDisableTiming));
+    hipStream_t st = ws->stream;
+    // greedy cut into passes of up to LM_MAXM rows and LM_EVAL_SEGS segments; a handle's tokens may continue in the next pass
+    LmEvalSeg segs[LM_EVAL_SEGS];
+    int n_seg = 0, rows = 0, n_pass = 0;
+    auto flush = [&]() -> int {
+        if (n_pass++) RCA_HIP(hipStreamSynchronize(st));   // the pinned block is reused: the pass before has consumed its copy
+        const int r = lm_eval_pass(ws, hs, ids_of, counts, segs, n_seg, rows, want_logits != 0, st);
+        n_seg = rows = 0;
+        return r;
+    };
+    for (int k = 0; k < n_h; ++k) {
+        for (int done = 0; done < counts[k];) {
+            if (rows == LM_MAXM || n_seg == LM_EVAL_SEGS) { if ((rc = flush()) != RCA_OK) return rc; }
+            const int take = std::min(counts[k] - done, LM_MAXM - rows);
+            segs[n_seg++] = LmEvalSeg{k, done, take, rows};
+            rows += (take + 31) & ~31;
+            done += take;
+        }
+    }
+    if ((rc = flush()) != RCA_OK) return rc;
+    for (int k = 0; k < n_h; ++k) {   // behind the last pass: what a later call on the handle waits for
+        rca_lm* h = hs[k];
+        RCA_HIP(hipEventRecord(h->be_event, st));
+        h->be_pending = true;
+        h->n_tokens += counts[k];
+        h->logits_rows = want_logits ? 1 : 0;
+    }
+    ws->async_pending = true;
     return RCA_OK;
 }
 
@@ -7070,6 +7406,7 @@ extern "C" int rca_lm_set_logits_all(rca_lm_t* h, int32_t enable) {
     if ((h->cfg.logits_all != 0) != (enable != 0)) {
         RCA_HIP(hipSetDevice(h->device));
         RCA_HIP(hipStreamSynchronize(h->stream));
+        { const int rc = lm_wait_batch_eval(h); if (rc != RCA_OK) return rc; }
         lm_drop_graphs(h);   // a later eval may move the logits buffer; nothing captured before the switch is replayed after it
     }
     h->cfg.logits_all = enable != 0;

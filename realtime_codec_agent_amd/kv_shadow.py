@@ -52,19 +52,30 @@ class KVShadow:
         self.prefix_len, self.src_pos, self.fed = prefix_len, src_pos, []
         self.stats["planned"] += 1
 
+    def next_tile(self, input_ids: List[int]) -> Optional[List[int]]:
+        """The whole tile of the suffix that is due -- already known, the newest keep_back tokens left alone -- or None.  Nothing
+        changes: whoever feeds the tile to the twin (advance, or one LlamaBatchEval call for the twins of many sessions) says so with
+        commit_tile."""
+        if not self.planned:
+            return None
+        a = self.src_pos + len(self.fed)
+        if len(input_ids) - self.keep_back - a < self.tile:
+            return None
+        return input_ids[a:a + self.tile]
+
+    def commit_tile(self, chunk: List[int]) -> None:
+        """`chunk` (a next_tile result) has been handed to the twin."""
+        self.fed.extend(chunk)
+        self.stats["tiles"] += 1
+
     def advance(self, input_ids: List[int], max_tiles: int = 1) -> None:
         """Feed whole tiles of the suffix that are already known (leaving the newest keep_back tokens alone)."""
-        if not self.planned:
-            return
         for _ in range(max_tiles):
-            a = self.src_pos + len(self.fed)
-            avail = len(input_ids) - self.keep_back - a
-            if avail < self.tile:
+            chunk = self.next_tile(input_ids)
+            if chunk is None:
                 return
-            chunk = input_ids[a:a + self.tile]
             self.twin.eval_async(chunk)
-            self.fed.extend(chunk)
-            self.stats["tiles"] += 1
+            self.commit_tile(chunk)
 
     def finish(self, input_ids: List[int], src_pos: int, prefix_len: int, end: int) -> bool:
         """Make the twin hold header + input_ids[src_pos:end] and trade caches with the live handle.  False (nothing touched) when

@@ -1105,6 +1105,65 @@ class LlamaBatch:
             pass
 
 
+class LlamaBatchEval:
+    """eval_async() of several sessions over ONE set of weights in shared passes of the 128-token prefill tiles (rca_lm_batch_eval;
+    llama.cpp: one llama_decode over a llama_batch with prompt tokens of several sequences): every matrix is streamed once per pass of
+    up to 1024 rows instead of once per handle.  The shadow-cache tiles of many sessions, or the prompts of sessions admitted together.
+    Every handle ends exactly as its own eval_async(tokens) would leave it -- n_tokens, KV bits, and with want_logits the logits --
+    so the call mixes freely with everything else on the handles; a later call on a handle waits for the pass first.
+    Owns the workspace, one more weight-sharing twin with a small context whose buffers and (low-priority) stream the passes use.
+    Close it before the handles."""
+
+    WORKSPACE_N_CTX = 256
+
+    @staticmethod
+    def supported(llm) -> bool:
+        """the model takes the 128-token tiles (smaller models keep eval_async) and the library has the call"""
+        return hasattr(llm, "_h") and hasattr(llm, "prefill_route") and hasattr(N.lib(), "rca_lm_batch_eval") and llm.prefill_route() == "gemm128"
+
+    def __init__(self, llm: "LlamaForAlternatingCodeChannels", low_priority: bool = True):
+        self._lib = llm._lib
+        self.ws = LlamaForAlternatingCodeChannels(model_path=llm.model_path, n_ctx=min(self.WORKSPACE_N_CTX, llm._n_ctx), share_weights_with=llm,
+                                                  device=llm._device)
+        if low_priority:
+            N.check(self._lib.rca_lm_set_low_priority(self.ws._h, 1), "rca_lm_set_low_priority")
+
+    def eval_async(self, handles: Sequence["LlamaForAlternatingCodeChannels"], token_lists: Sequence[Sequence[int]], want_logits: bool = False) -> None:
+        """handles[k] appends token_lists[k] (at least one token) at its own n_tokens; returns once the last pass is enqueued.  A refusal
+        raises and leaves every handle as it was.  want_logits=False runs no head: the handles have no logits afterwards."""
+        handles = list(handles)
+        rows = [list(t) for t in token_lists]
+        if len(rows) != len(handles):
+            raise ValueError(f"{len(rows)} token lists for {len(handles)} handles")
+        starts = [h.n_tokens for h in handles]
+        flat = [t for r in rows for t in r]
+        hs = (C.c_void_p * max(len(handles), 1))(*[h._h for h in handles])
+        ids = (C.c_int32 * max(len(flat), 1))(*flat)
+        counts = (C.c_int32 * max(len(rows), 1))(*[len(r) for r in rows])
+        N.check(self._lib.rca_lm_batch_eval(self.ws._h, hs, len(handles), ids, counts, 1 if want_logits else 0), "rca_lm_batch_eval")
+        for h, n0, r in zip(handles, starts, rows):
+            h._input_ids[n0:n0 + len(r)] = r
+            h._logits_valid = False
+
+    def eval(self, handles, token_lists, want_logits: bool = False) -> None:
+        self.eval_async(handles, token_lists, want_logits)
+        self.sync()
+
+    def sync(self) -> None:
+        self.ws.sync()
+
+    def close(self) -> None:
+        if getattr(self, "ws", None) is not None:
+            self.ws.close()
+            self.ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ScoreResult:
     """What score() returns: one numpy array per field of rca_score_row_t, one entry per position.  logprob / lse / max_logit /
     argmax of the scored handle; with a base also kl = KL(P_base || P), base_logprob and base_argmax (None without one).

@@ -14,14 +14,21 @@ one session.
 batch_speaker_step=True (off by default) also batches the agents' speculative <|end_audio|> step: the fused members of a tick commit
 with the step deferred, and those that owe it (z-score of P(<|end_audio|>) >= 0) take ONE LlamaBatch.step_probe
 (rca_lm_batch_step_sel) when there are at least min_batch of them, else their own single steps.  That moves the two speaker
-probabilities and the step's throw-away draw into the tile arithmetic class too.  Not thread-safe: one caller per tick."""
+probabilities and the step's throw-away draw into the tile arithmetic class too.
+
+batch_shadow_tiles=True (off by default) feeds the shadow-cache tiles that fall due in a tick (kv_shadow.py: one 128-token tile per
+session every ~16 ticks) to the sessions' twins in ONE LlamaBatchEval.eval_async (rca_lm_batch_eval) instead of one eval_async per
+session, each a pass over all weights.  A twin ends with the bits of its own eval_async, so tokens, PCM and caches are those of the
+flag off.  LMs without the call (llama.cpp objects, test fakes, models off the 128-token tiles) keep the per-session advance.
+Not thread-safe: one caller per tick."""
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
 
 class RealtimeAgentBatch:
-    def __init__(self, agents: Sequence, min_batch: int = 4, use_duplex_batch_graph: bool = True, batch_speaker_step: bool = False):
+    def __init__(self, agents: Sequence, min_batch: int = 4, use_duplex_batch_graph: bool = True, batch_speaker_step: bool = False,
+                 batch_shadow_tiles: bool = False):
         self.agents = list(agents)
         # where one batch call starts to win over as many single calls: 4, the smallest size measured, for the frame (profiles/r16:
         # 11.0 against 13.8 ms) and for the speaker step (profiles/r18: 2.64 against 3.29 ms; three single steps are 2.5 ms)
@@ -32,7 +39,11 @@ class RealtimeAgentBatch:
         self.batch_speaker_step = bool(batch_speaker_step)
         self.fused_speaker_calls = 0   # batch step_probe calls for the speculative <|end_audio|> step
         self.fused_speaker_steps = 0   # agents' speculative steps that went through them
+        self.batch_shadow_tiles = bool(batch_shadow_tiles)
+        self.fused_shadow_calls = 0    # LlamaBatchEval calls that fed the shadow tiles of several sessions
+        self.fused_shadow_tiles = 0    # tiles that went through them
         self._batch = None
+        self._shadow_pool = None
         if len(self.agents) < 2:
             raise ValueError("a RealtimeAgentBatch drives at least two agents")
         llms = [a.resources.llm for a in self.agents]
@@ -52,6 +63,10 @@ class RealtimeAgentBatch:
                 self._batch = LlamaBatch(llms)
             except N.RcaError as e:       # other weights, another device, a model off the tile route
                 raise ValueError(f"the agents' LMs cannot form one batch: {e}") from e
+        if self.batch_shadow_tiles and all(hasattr(m, "_h") for m in llms):
+            from .llm import LlamaBatchEval
+            if all(LlamaBatchEval.supported(m) for m in llms):
+                self._shadow_pool = LlamaBatchEval(llms[0])
 
     @staticmethod
     def _codec(agent):
@@ -91,12 +106,35 @@ class RealtimeAgentBatch:
                 outs[i] = self.agents[i].process_audio(chunks[i])     # settles and advances its own shadow cache
         if self.batch_speaker_step:
             self._run_speaker_steps(sorted(fused))
-        for i in sorted(fused):
-            self.agents[i]._advance_shadow()
+        self._advance_shadows(sorted(fused))
         if groups:
             self.fused_ticks += 1
             self.fused_frames += len(fused)
         return outs
+
+    def _advance_shadows(self, fused: List[int]) -> None:
+        """The end of a tick for the fused members: every shadow cache is planned as RealtimeAgent._advance_shadow plans it; the tiles
+        that are due go to their twins in one LlamaBatchEval call when there is a pool and more than one of them, else through the
+        session's own advance."""
+        A = self.agents
+        if self._shadow_pool is None or not self.batch_shadow_tiles:
+            for i in fused:
+                A[i]._advance_shadow()
+            return
+        due = []
+        for i in fused:
+            sh = A[i]._plan_shadow()
+            tile = sh.next_tile(A[i].input_ids) if sh is not None else None
+            if tile is not None:
+                due.append((sh, tile, i))
+        if len(due) == 1:
+            due[0][0].advance(A[due[0][2]].input_ids)
+        elif due:
+            self._shadow_pool.eval_async([sh.twin for sh, _, _ in due], [tile for _, tile, _ in due], want_logits=False)
+            for sh, tile, _ in due:
+                sh.commit_tile(tile)
+            self.fused_shadow_calls += 1
+            self.fused_shadow_tiles += len(due)
 
     def _run_speaker_steps(self, fused: List[int]) -> None:
         """The speculative <|end_audio|> steps the fused members of this tick deferred (across groups): one batch step_probe for at
@@ -155,7 +193,10 @@ class RealtimeAgentBatch:
             outs[i] = (out_chunk, out_ids) if a.self_play_mode else out_chunk
 
     def close(self) -> None:
-        """the batch first, then the agents' LM handles (shadow twins included)"""
+        """the batch and the shadow pool first, then the agents' LM handles (shadow twins included)"""
+        if self._shadow_pool is not None:
+            self._shadow_pool.close()
+            self._shadow_pool = None
         if self._batch is not None:
             self._batch.close()
             self._batch = None
