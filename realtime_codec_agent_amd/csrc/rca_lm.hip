@@ -4376,33 +4376,17 @@ __global__ __launch_bounds__(64 * FLASH_WAVES * TEAMS, 3) void lm_attn_flash_ker
         }
     }
 }
-template <int G>
-static void launch_attention_flash_g(rca_lm* h, int M, const f16_t* kc, const f16_t* vc, hipStream_t st, bf16_t* hi, bf16_t* lo, const f16_t* kd, const f16_t* vd) {
-    const rca_lm_config_t& c = h->cfg;
-    const float scale = 1.0f / sqrtf((float)c.head_dim);
-    const int ntiles = cdiv(M * G, 32);
-    // teams per workgroup: 4 (one workgroup per CU) once that still gives every CU of the device a workgroup, else 2, else 1
-    if (kd) {   // q8_0 cache: the same three shapes
-        if (c.n_kv_heads * cdiv(ntiles, 4) >= h->n_cus)
-            lm_attn_flash_kernel<G, 4, 1><<<dim3(c.n_kv_heads, cdiv(ntiles, 4)), 64 * FLASH_WAVES * 4, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx, kd, vd);
-        else if (c.n_kv_heads * cdiv(ntiles, 2) >= h->n_cus)
-            lm_attn_flash_kernel<G, 2, 1><<<dim3(c.n_kv_heads, cdiv(ntiles, 2)), 64 * FLASH_WAVES * 2, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx, kd, vd);
-        else
-            lm_attn_flash_kernel<G, 1, 1><<<dim3(c.n_kv_heads, ntiles), 64 * FLASH_WAVES, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx, kd, vd);
-        return;
-    }
-    if (c.n_kv_heads * cdiv(ntiles, 4) >= h->n_cus)
-        lm_attn_flash_kernel<G, 4><<<dim3(c.n_kv_heads, cdiv(ntiles, 4)), 64 * FLASH_WAVES * 4, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx);
-    else if (c.n_kv_heads * cdiv(ntiles, 2) >= h->n_cus)
-        lm_attn_flash_kernel<G, 2><<<dim3(c.n_kv_heads, cdiv(ntiles, 2)), 64 * FLASH_WAVES * 2, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx);
-    else
-        lm_attn_flash_kernel<G, 1><<<dim3(c.n_kv_heads, ntiles), 64 * FLASH_WAVES, 0, st>>>(h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, c.n_ctx);
+// The one place that turns a head-group size or a team count (4, 2 or 1), or a yes / no, into a template argument (wf_dispatch's way)
+template <class F>
+static void lm_dispatch_421(int v, F&& f) {
+    if (v == 4) f(std::integral_constant<int, 4>{});
+    else if (v == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
 }
-static void launch_attention_flash(rca_lm* h, int M, const f16_t* kc, const f16_t* vc, hipStream_t st, bf16_t* hi, bf16_t* lo, const f16_t* kd, const f16_t* vd) {
-    const int G = h->cfg.n_heads / h->cfg.n_kv_heads;
-    if (G == 4) launch_attention_flash_g<4>(h, M, kc, vc, st, hi, lo, kd, vd);
-    else if (G == 2) launch_attention_flash_g<2>(h, M, kc, vc, st, hi, lo, kd, vd);
-    else launch_attention_flash_g<1>(h, M, kc, vc, st, hi, lo, kd, vd);
+template <class F>
+static void lm_dispatch_bool(bool v, F&& f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
 }
 // what a pass of rca_lm_batch_eval reads about its segments (device pointers into the block the pass uploaded)
 struct LmEvalTables {
@@ -4411,25 +4395,27 @@ struct LmEvalTables {
     const int* owner;            // [LM_MAXM / 32]: segment of every 32 rows, -1 = pad rows behind the last segment
     bool q8;
 };
-// the table instance: one launch for every segment of the pass; TEAMS from the pass's total tile count by the rule above
-template <int G>
-static void launch_attention_flash_tab_g(rca_lm* h, int rows, hipStream_t st, bf16_t* hi, bf16_t* lo, const LmEvalTables& t, int l) {
+// Every flash launch.  The handle's own pass: M tokens on its cache (kc / vc of the layer, kd / vd its q8_0 scales or null).  With t, the
+// table instance: one launch for every segment of a pass of M rows, cache and position per segment from the table (layer l), no
+// cache argument.  Teams per workgroup, from the pass's total tile count: 4 (one workgroup per CU) once that still gives every CU of
+// the device a workgroup, else 2, else 1.
+static void launch_attention_flash(rca_lm* h, int M, const f16_t* kc, const f16_t* vc, hipStream_t st, bf16_t* hi, bf16_t* lo, const f16_t* kd, const f16_t* vd,
+                                   const LmEvalTables* t = nullptr, int l = 0) {
     const rca_lm_config_t& c = h->cfg;
     const float scale = 1.0f / sqrtf((float)c.head_dim);
-    const int ntiles = cdiv(rows * G, 32);
-#define RCA_FLASH_TAB(TEAMS, KVQ)                                                                                                       \
-    lm_attn_flash_kernel<G, TEAMS, KVQ, true><<<dim3(c.n_kv_heads, cdiv(ntiles, TEAMS)), 64 * FLASH_WAVES * TEAMS, 0, st>>>(              \
-        h->stt, h->qkv, nullptr, nullptr, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, 0, nullptr, nullptr, t.tab, t.owner, l)
-    if (c.n_kv_heads * cdiv(ntiles, 4) >= h->n_cus) { if (t.q8) RCA_FLASH_TAB(4, 1); else RCA_FLASH_TAB(4, 0); }
-    else if (c.n_kv_heads * cdiv(ntiles, 2) >= h->n_cus) { if (t.q8) RCA_FLASH_TAB(2, 1); else RCA_FLASH_TAB(2, 0); }
-    else { if (t.q8) RCA_FLASH_TAB(1, 1); else RCA_FLASH_TAB(1, 0); }
-#undef RCA_FLASH_TAB
+    const int G = c.n_heads / c.n_kv_heads;
+    const int ntiles = cdiv(M * G, 32);
+    int teams = 1;
+    if (c.n_kv_heads * cdiv(ntiles, 4) >= h->n_cus) teams = 4;
+    else if (c.n_kv_heads * cdiv(ntiles, 2) >= h->n_cus) teams = 2;
+    lm_dispatch_421(G, [&](auto g) { lm_dispatch_421(teams, [&](auto tm) { lm_dispatch_bool(t ? t->q8 : kd != nullptr, [&](auto q) { lm_dispatch_bool(t != nullptr, [&](auto tb) {
+        constexpr int TEAMS = decltype(tm)::value;
+        lm_attn_flash_kernel<decltype(g)::value, TEAMS, decltype(q)::value ? 1 : 0, decltype(tb)::value><<<dim3(c.n_kv_heads, cdiv(ntiles, TEAMS)), 64 * FLASH_WAVES * TEAMS, 0, st>>>(
+            h->stt, h->qkv, kc, vc, h->attn, hi, lo, c.n_heads, c.n_kv_heads, scale, t ? 0 : c.n_ctx, kd, vd, t ? t->tab : nullptr, t ? t->owner : nullptr, l);
+    }); }); }); });
 }
 static void launch_attention_flash_tab(rca_lm* h, int rows, hipStream_t st, bf16_t* hi, bf16_t* lo, const LmEvalTables& t, int l) {
-    const int G = h->cfg.n_heads / h->cfg.n_kv_heads;
-    if (G == 4) launch_attention_flash_tab_g<4>(h, rows, st, hi, lo, t, l);
-    else if (G == 2) launch_attention_flash_tab_g<2>(h, rows, st, hi, lo, t, l);
-    else launch_attention_flash_tab_g<1>(h, rows, st, hi, lo, t, l);
+    launch_attention_flash(h, rows, nullptr, nullptr, st, hi, lo, nullptr, nullptr, &t, l);
 }
 // the q8_0 quantiser of layer l over the rows the pass has just stored into the ring (nothing to do for an fp16 cache).  m_max: the
 // most tokens the pass can have (the grid); the live count and the position are read on the device
@@ -4446,51 +4432,72 @@ static LmBatchMember lm_batch_member(const rca_lm* h, int row0, bool serial) {
     return LmBatchMember{h->stt, h->kc, h->vc, h->kv_layer_stride, h->att_part, h->logits, h->samp, h->swork, row0, h->n_splits, h->cfg.n_ctx, serial ? 1 : 0,
                          lm_kv_q8(h) ? lm_kv_sc_off(h) : 0, h->ring_k, h->ring_v, LM_KV_RING - 1, 0};
 }
+// RCA_LM_FLASH / RCA_LM_TILE_GRAPHS: unset or non-zero = on; read once per process
+static bool lm_env_on(const char* name) {
+    const char* v = getenv(name);
+    return !(v && atoi(v) == 0);
+}
+static bool lm_env_flash() {   // 0: A/B runs against the split kernel
+    static const bool v = lm_env_on("RCA_LM_FLASH");
+    return v;
+}
+static bool lm_env_tile_graphs() {   // 0: every prefill tile pass is launched eagerly
+    static const bool v = lm_env_on("RCA_LM_TILE_GRAPHS");
+    return v;
+}
+// the dynamic LDS of every instance of the split kernel, once per process; called where a pass is about to launch one eagerly
+static void lm_attn_split_attrs() {
+    static bool done = false;
+    if (done) return;
+    for (int G : {4, 2, 1})
+        lm_dispatch_421(G, [](auto g) {
+            constexpr int GG = decltype(g)::value;
+            (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<GG>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+            (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<GG, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+            (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<GG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+            (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<GG, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
+        });
+    done = true;
+}
+// Every launch of the split kernel.  A handle's own pass (tab null): its state, the layer's cache, and for a q8_0 cache the distance
+// to the scales in tab_layer.  A batch pass: a member per grid z from tab, layer tab_layer, everything else null / 0.  The merge of
+// the splits (in-launch, combine kernel or batch combine kernel) is the caller's.
+static void lm_launch_attn_split(const rca_lm_config_t& c, dim3 grid, bool q8, hipStream_t st, const LmDevState* stt, const float* qkv, const f16_t* kc, const f16_t* vc,
+                                 int n_splits, int n_ctx, float* part, int* arrive, float* attn, const LmBatchMember* tab, int tab_layer) {
+    const float scale = 1.0f / sqrtf((float)c.head_dim);
+    lm_dispatch_421(c.n_heads / c.n_kv_heads, [&](auto g) { lm_dispatch_bool(tab != nullptr, [&](auto tb) { lm_dispatch_bool(q8, [&](auto q) {
+        lm_attn_mfma_kernel<decltype(g)::value, decltype(tb)::value, decltype(q)::value ? 1 : 0><<<grid, 512, ATTM_LDS, st>>>(
+            stt, qkv, kc, vc, c.n_heads, c.n_kv_heads, n_splits, scale, n_ctx, part, arrive, attn, tab, tab_layer);
+    }); }); });
+}
 // split attention on MFMA + merge of the splits, for the M tokens of the current pass
 // qkv / attn: the M query rows and where their outputs go -- the handle's own buffers for its own passes, the rows of ONE member inside the
 // shared buffers of a group step (the flash route, prefill only, reads the handle's)
 static void launch_attention_mfma(rca_lm* h, int M, int nsp_launch, const f16_t* kc, const f16_t* vc, const float* qkv, float* attn, hipStream_t st,
                                   bf16_t* hi = nullptr, bf16_t* lo = nullptr, bool prefill = false) {
     const rca_lm_config_t& c = h->cfg;
-    static const bool flash = !(getenv("RCA_LM_FLASH") && atoi(getenv("RCA_LM_FLASH")) == 0);   // 0: A/B runs against the split kernel
     // q8_0 cache: kc / vc are a layer of the int8 planes (lm_kv_layer); its scales sit at the same element offset / 32 of the scale plane
     const f16_t *kd = nullptr, *vd = nullptr;
     if (lm_kv_q8(h)) {
         kd = lm_kv_scales(h, h->kc, 0) + (((const char*)kc - (const char*)h->kc) >> 5);
         vd = lm_kv_scales(h, h->vc, 0) + (((const char*)vc - (const char*)h->vc) >> 5);
     }
-    if (prefill && flash) {   // every pass of the prefill-tile path, whatever its size: pieces of one long eval must use ONE arithmetic
+    if (prefill && lm_env_flash()) {   // every pass of the prefill-tile path, whatever its size: pieces of one long eval must use ONE arithmetic
         launch_attention_flash(h, M, kc, vc, st, hi, lo, kd, vd);
         return;
     }
     const int G = c.n_heads / c.n_kv_heads;
-    const float scale = 1.0f / sqrtf((float)c.head_dim);
     const int sc_units = kd ? (int)(((const char*)kd - (const char*)kc) >> 4) : 0;   // (lm_kv_alloc keeps a plane below 2^35 bytes)
     dim3 agm(c.n_kv_heads, nsp_launch, cdiv(M * G, 32));
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        attr_done = true;
-    }
+    lm_attn_split_attrs();
     // decode steps: the merge of the splits is fused into the attention launch while the grid is at most one workgroup per CU (the
     // regime the sc1 hand-off is measured for); prefill tiles and longer contexts keep the separate combine launch
     const bool fuse = h->fuse_attn && !hi && agm.z == 1 && c.n_kv_heads * nsp_launch <= 256 && M * G <= 8 && nsp_launch <= ATT_TAG_MAXSP && c.n_kv_heads <= ATT_EPOCH_INTS;
-    int* arrive = fuse ? h->att_arrive : nullptr;
-#define RCA_ATTN_LAUNCH(GG)                                                                                                                        \
-    if (kd) lm_attn_mfma_kernel<GG, false, 1><<<agm, 512, ATTM_LDS, st>>>(h->stt, qkv, kc, vc, c.n_heads, c.n_kv_heads, h->n_splits, scale, c.n_ctx,  \
-                                                                          h->att_part, arrive, attn, nullptr, sc_units);                           \
-    else lm_attn_mfma_kernel<GG><<<agm, 512, ATTM_LDS, st>>>(h->stt, qkv, kc, vc, c.n_heads, c.n_kv_heads, h->n_splits, scale, c.n_ctx, h->att_part, \
-                                                        arrive, attn);                                                                             \
-    if (!fuse) lm_attn_mfma_combine_kernel<GG><<<M * c.n_heads, 64, 0, st>>>(h->stt, h->att_part, attn, c.n_heads, c.n_kv_heads, h->n_splits, nsp_launch, hi, lo);
-    if (G == 4) { RCA_ATTN_LAUNCH(4) }
-    else if (G == 2) { RCA_ATTN_LAUNCH(2) }
-    else { RCA_ATTN_LAUNCH(1) }
-#undef RCA_ATTN_LAUNCH
+    lm_launch_attn_split(c, agm, kd != nullptr, st, h->stt, qkv, kc, vc, h->n_splits, c.n_ctx, h->att_part, fuse ? h->att_arrive : nullptr, attn, nullptr, sc_units);
+    if (!fuse)
+        lm_dispatch_421(G, [&](auto g) {
+            lm_attn_mfma_combine_kernel<decltype(g)::value><<<M * c.n_heads, 64, 0, st>>>(h->stt, h->att_part, attn, c.n_heads, c.n_kv_heads, h->n_splits, nsp_launch, hi, lo);
+        });
 }
 
 // attention split blocks needed by a pass of m tokens on top of the current context
@@ -5065,8 +5072,8 @@ static bool lm_can_gemm128(const rca_lm* h) {
 // one 128-row GEMM launch in the format the matrix is kept in
 template <int EPI>
 static void launch_gemm128(rca_lm* h, const WMat& w, dim3 grid, hipStream_t st, const bf16_t* xh, const bf16_t* xl, int N, int K, int kslice,
-                           float* y, int ldy, bf16_t* oh, bf16_t* ol, GemvRope rope, int nseq, const LmDevState* stt = nullptr,
-                           const GemvGroup& grp = nogroup) {   // stt: the pass's own device state (a batch step's), else the handle's
+                           float* y, int ldy, bf16_t* oh, bf16_t* ol, GemvRope rope, int nseq, const LmDevState* stt,
+                           const GemvGroup& grp = nogroup) {   // stt: the pass's device state (the handle's own, or a batch step's)
     static bool attr_done = false;
     if (!attr_done) {   // the four-tile variants need 80 KB of LDS
         for (int fmt : WF_FORMATS)
@@ -5079,67 +5086,91 @@ static void launch_gemm128(rca_lm* h, const WMat& w, dim3 grid, hipStream_t st, 
     const GemvQ8 qa{w.qs, w.sc, w.dd};
     wf_dispatch(w.fmt, [&](auto wf) {   // bf16 fragments go to the MFMA as they are: three tiles per stage, not four
         constexpr int WF = decltype(wf)::value;
-        lm_gemm128_kernel<EPI, WF><<<grid, 256, WF == WF_BF16 ? G128_LDS_T(3) : G128_LDS_T(4), st>>>(stt ? stt : h->stt, w.wptr(), qa, xh, xl, N, K, kslice, y, ldy, oh, ol,
+        lm_gemm128_kernel<EPI, WF><<<grid, 256, WF == WF_BF16 ? G128_LDS_T(3) : G128_LDS_T(4), st>>>(stt, w.wptr(), qa, xh, xl, N, K, kslice, y, ldy, oh, ol,
                                                                                                  h->gpart, rope, nseq, grp);
     });
 }
-// bt (rca_lm_batch_eval): the rows are segments of several sessions packed into h's buffers (h is the call's workspace, h->stt the
-// pass's state; M is the pass's whole token blocks, the launch geometry, and h->stt->m the rows that exist).  The row-wise stages and the GEMMs are the same launches; what is per session -- the QKV epilogue's position and
-// cache, the q8_0 quantiser, attention -- takes it from the pass's tables.
-static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch, const LmEvalTables* bt = nullptr) {
+// What differs between the callers of the 128-token-tile layer sequence (lm_enqueue_layers128)
+struct LmTilePass {
+    rca_lm* h;                 // whose buffers and weights the pass uses
+    const LmDevState* stt;     // the state the row-wise kernels and the GEMMs read: h->stt, or a batch's own (m = the rows that exist)
+    int rows;                  // sizes the row-wise grids and the k-split epilogues' token groups
+    int tbz;                   // token blocks of the pass: the GEMMs' grid.z, and what their k-split form is chosen for
+    const LmGroupRow* qrows;   // null: the QKV epilogue is GEMM_EPI_ROPE into h's own cache (lm_rope_target, n_ctx bound); else
+                               // GEMM_EPI_ROPE_ROWS, position, cache and bound per row from this table
+};
+// One projection of such a pass: the GEMM and, where its k slices went through HBM, the epilogue that sums them.  A projection whose
+// token blocks alone put `seq_min` workgroups on the chip is run with every workgroup walking the k slices itself (same sums in the
+// same order, no partial sums through HBM, no epilogue launch); RCA_LM_SEQ_MIN_WGS overrides the threshold (0 = never) for A/B runs.
+template <int EPI>
+static void lm_launch_proj128(const LmTilePass& p, const WMat& w, hipStream_t st, const bf16_t* xh, const bf16_t* xl, int N, int K, float* y, int ldy,
+                              bf16_t* oh, bf16_t* ol, const GemvRope& rope = norope, const GemvGroup& grp = nogroup) {
+    const int ns = g128_splits(N, K);
+    const G128Form f = g128_form(N, ns, p.tbz, g128_seq_min());
+    launch_gemm128<EPI>(p.h, w, dim3(N / 128, f.grid_y, p.tbz), st, xh, xl, N, K, K / ns, y, ldy, oh, ol, rope, f.nseq, p.stt, grp);
+    if (f.ep_nsplit)   // (the SwiGLU epilogue has no y and is handed ldy 0, its GEMM the width of the planes)
+        lm_gemm128_epilogue_kernel<EPI><<<dim3(N / 64, cdiv(p.rows, 32)), 256, 0, st>>>(p.stt, p.h->gpart, f.ep_nsplit, f.ep_grp, N, y, EPI == GEMM_EPI_SWIGLU ? 0 : ldy,
+                                                                                         oh, ol, rope, grp);
+}
+// The layers of a pass on the 128-token tiles, behind the caller's embedding launch and in front of its heads: every route that runs
+// these tiles -- a handle's own pass, a pass of rca_lm_batch_eval, the batch step / frame / selection / duplex pass -- runs this one
+// sequence, so a row's bits cannot depend on the route.  attention(l): the caller's q8_0 quantiser and attention launches of layer l,
+// reading h->qkv and writing the hi / lo planes h->xh / h->xl (a template argument: a tile is ~230 eager launches).
+template <class Attn>
+static void lm_enqueue_layers128(const LmTilePass& p, hipStream_t st, Attn&& attention) {
+    rca_lm* h = p.h;
     const rca_lm_config_t& c = h->cfg;
     const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn;
-    GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, bt ? 0 : c.n_ctx, 0};   // bt: cache, position and context bound per row
-    const int so = g128_splits(H, AO), sg = g128_splits(2 * F, H), sd = g128_splits(H, F);
-    const int tbz = cdiv(M, 128);   // token blocks of this pass
-    // A projection whose token blocks alone put `seq_min` workgroups on the chip is run with every workgroup walking the k slices itself
-    // (same sums in the same order, no partial sums through HBM, no epilogue launch); RCA_LM_SEQ_MIN_WGS overrides the threshold
-    // (0 = never) for A/B runs.
-    const int seq_min = g128_seq_min();
-    const G128Form fo = g128_form(H, so, tbz, seq_min), fg = g128_form(2 * F, sg, tbz, seq_min), fd = g128_form(H, sd, tbz, seq_min);
+    GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, p.qrows ? 0 : c.n_ctx, 0};
     float* x = h->x;
-    lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, x, H, c.vocab_size);
+    // SwiGLU epilogue writes the hi/lo split of h straight into the (ffn-wide) split buffers of the down projection:
+    // it reads xh/xl [M][H] and writes [M][F] -- distinct regions are needed, so h goes to the second half of hbuf
+    bf16_t* hh = reinterpret_cast<bf16_t*>(h->hbuf);
+    bf16_t* hl = hh + (long)LM_MAXM * F;
     for (int l = 0; l < c.n_layers; ++l) {
         const LmLayer& L = h->layers[l];
-        f16_t* kc = lm_kv_layer(h, h->kc, l);
-        f16_t* vc = lm_kv_layer(h, h->vc, l);
-        if (!bt) lm_rope_target(h, l, rope);
-        lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.attn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
+        const GemvGroup grp = p.qrows ? GemvGroup{p.qrows, l} : nogroup;
+        if (!p.qrows) lm_rope_target(h, l, rope);
+        lm_add_rmsnorm_kernel<<<p.rows, 64, 0, st>>>(p.stt, x, nullptr, nullptr, 0, 0, L.attn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
         for (int seg = 0; seg < (L.split_v ? 2 : 1); ++seg) {   // [q; k; v] as one matrix, or [q; k] and v when their formats differ
             const WMat& w = seg ? L.vseg : L.qkv;
-            const int Ns = w.N, ss = g128_splits(Ns, H);
-            const G128Form fq = g128_form(Ns, ss, tbz, seq_min);
             rope.row_base = seg ? L.qkv.N : 0;
-            if (bt) {
-                const GemvGroup grp{bt->rows, l};
-                launch_gemm128<GEMM_EPI_ROPE_ROWS>(h, w, dim3(Ns / 128, fq.grid_y, tbz), st, h->xh, h->xl, Ns, H, H / ss, h->qkv, QKV, nullptr, nullptr, rope, fq.nseq, nullptr, grp);
-                if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE_ROWS><<<dim3(Ns / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fq.ep_nsplit, fq.ep_grp, Ns, h->qkv, QKV, nullptr, nullptr, rope, grp);
-                continue;
-            }
-            launch_gemm128<GEMM_EPI_ROPE>(h, w, dim3(Ns / 128, fq.grid_y, tbz), st, h->xh, h->xl, Ns, H, H / ss, h->qkv, QKV, nullptr, nullptr, rope, fq.nseq);
-            if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE><<<dim3(Ns / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fq.ep_nsplit, fq.ep_grp, Ns, h->qkv, QKV, nullptr, nullptr, rope, nogroup);
+            if (p.qrows) lm_launch_proj128<GEMM_EPI_ROPE_ROWS>(p, w, st, h->xh, h->xl, w.N, H, h->qkv, QKV, nullptr, nullptr, rope, grp);
+            else lm_launch_proj128<GEMM_EPI_ROPE>(p, w, st, h->xh, h->xl, w.N, H, h->qkv, QKV, nullptr, nullptr, rope, grp);
         }
-        rope.row_base = 0;
-        if (bt) {
+        attention(l);
+        lm_launch_proj128<GEMM_EPI_RESID>(p, L.o, st, h->xh, h->xl, H, AO, x, H, nullptr, nullptr);
+        lm_add_rmsnorm_kernel<<<p.rows, 64, 0, st>>>(p.stt, x, nullptr, nullptr, 0, 0, L.ffn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
+        lm_launch_proj128<GEMM_EPI_SWIGLU>(p, L.gu, st, h->xh, h->xl, 2 * F, H, nullptr, F, hh, hl);
+        lm_launch_proj128<GEMM_EPI_RESID>(p, L.down, st, hh, hl, H, F, x, H, nullptr, nullptr);
+    }
+}
+// The logits head on the tiles (GEMM_EPI_LOGITS): the 128 normalised rows whose hi / lo planes start at xh / xl -> blk [128][V]; they
+// are rows row_base .. of the pass stt describes.  Every workgroup walks all of K itself (one slice: no partial sums).
+static void lm_launch_logits128(rca_lm* h, const LmDevState* stt, const bf16_t* xh, const bf16_t* xl, int row_base, float* blk, hipStream_t st) {
+    const rca_lm_config_t& c = h->cfg;
+    GemvRope rp = norope;
+    rp.row_base = row_base;
+    launch_gemm128<GEMM_EPI_LOGITS>(h, h->head, dim3(cdiv(c.vocab_size, 128), 1, 1), st, xh, xl, c.vocab_size, c.hidden, c.hidden, blk, c.vocab_size, nullptr, nullptr, rp, 1, stt);
+}
+// A handle's own pass of M tokens.  bt (rca_lm_batch_eval): the rows are segments of several sessions packed into h's buffers (h is the
+// call's workspace, h->stt the pass's state; M is the pass's whole token blocks, the launch geometry, and h->stt->m the rows that
+// exist); what is per session -- the QKV epilogue's position and cache, the q8_0 quantiser, attention -- takes it from the pass's tables.
+static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch, const LmEvalTables* bt = nullptr) {
+    const rca_lm_config_t& c = h->cfg;
+    const LmTilePass p{h, h->stt, M, (int)cdiv(M, 128), bt ? bt->rows : nullptr};
+    lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, h->x, c.hidden, c.vocab_size);
+    if (bt)
+        lm_enqueue_layers128(p, st, [&](int l) {
             if (bt->q8)   // every segment's new rows, ring -> int8 planes, in one launch
                 lm_kv_quant_rows_kernel<<<dim3(cdiv(4 * c.n_kv_heads, 8), M), 256, 0, st>>>(h->stt, bt->tab, bt->owner, l, c.n_kv_heads);
             launch_attention_flash_tab(h, M, st, h->xh, h->xl, *bt, l);
-        } else {
+        });
+    else
+        lm_enqueue_layers128(p, st, [&](int l) {
             lm_launch_kv_quant(h, l, M, st);
-            launch_attention_mfma(h, M, nsp_launch, kc, vc, h->qkv, h->attn, st, h->xh, h->xl, true);
-        }
-        launch_gemm128<GEMM_EPI_RESID>(h, L.o, dim3(H / 128, fo.grid_y, tbz), st, h->xh, h->xl, H, AO, AO / so, x, H, nullptr, nullptr, norope, fo.nseq);
-        if (fo.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fo.ep_nsplit, fo.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
-        lm_add_rmsnorm_kernel<<<M, 64, 0, st>>>(h->stt, x, nullptr, nullptr, 0, 0, L.ffn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
-        // SwiGLU epilogue writes the hi/lo split of h straight into the (ffn-wide) split buffers of the down projection:
-        // it reads xh/xl [M][H] and writes [M][F] -- distinct regions are needed, so h goes to the second half of hbuf
-        bf16_t* hh = reinterpret_cast<bf16_t*>(h->hbuf);
-        bf16_t* hl = hh + (long)LM_MAXM * F;
-        launch_gemm128<GEMM_EPI_SWIGLU>(h, L.gu, dim3(2 * F / 128, fg.grid_y, tbz), st, h->xh, h->xl, 2 * F, H, H / sg, nullptr, F, hh, hl, norope, fg.nseq);
-        if (fg.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_SWIGLU><<<dim3(2 * F / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fg.ep_nsplit, fg.ep_grp, 2 * F, nullptr, 0, hh, hl, norope, nogroup);
-        launch_gemm128<GEMM_EPI_RESID>(h, L.down, dim3(H / 128, fd.grid_y, tbz), st, hh, hl, H, F, F / sd, x, H, nullptr, nullptr, norope, fd.nseq);
-        if (fd.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(M, 32)), 256, 0, st>>>(h->stt, h->gpart, fd.ep_nsplit, fd.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
-    }
+            launch_attention_mfma(h, M, nsp_launch, lm_kv_layer(h, h->kc, l), lm_kv_layer(h, h->vc, l), h->qkv, h->attn, st, h->xh, h->xl, true);
+        });
     RCA_LAUNCH_CHECK();
     return RCA_OK;
 }
@@ -5249,8 +5280,7 @@ static int lm_eval_impl(rca_lm_t* h, const int32_t* ids, int32_t n, bool wait_la
         // of 4.4).  The second pass of a size on this cache is captured and replayed from then on: one launch.  (First: eager --
         // the launchers' one-time attribute calls; the geometry of a pass depends on its token count only, the context is read
         // from the device state.)
-        static const bool tile_graphs = !(getenv("RCA_LM_TILE_GRAPHS") && atoi(getenv("RCA_LM_TILE_GRAPHS")) == 0) &&
-                                        !(getenv("RCA_LM_FLASH") && atoi(getenv("RCA_LM_FLASH")) == 0);   // (the split-attention A/B path launches per context)
+        const bool tile_graphs = lm_env_tile_graphs() && lm_env_flash();   // (the split-attention A/B path launches per context)
         if (!wait_last && big && n <= tile && h->graphs_enabled && tile_graphs) {
             rca_lm::GraphSet& gs = lm_graph_set(h);
             int slot = -1;
@@ -6046,9 +6076,8 @@ static int lm_eval_pass(rca_lm* ws, rca_lm* const* hs, const int32_t* const* ids
         lm_eval_stage_kernel<<<1, LM_MAXM, 0, st>>>(ws->be_dev, ws->stt);
         return lm_enqueue_prefill_tile128(ws, tbz * 128, st, 1, &bt);
     };
-    static const bool tile_graphs = !(getenv("RCA_LM_TILE_GRAPHS") && atoi(getenv("RCA_LM_TILE_GRAPHS")) == 0);
     int rc;
-    if (ws->graphs_enabled && tile_graphs && ++ws->be_seen[tbz - 1][q8] >= 2) {
+    if (ws->graphs_enabled && lm_env_tile_graphs() &&++ws->be_seen[tbz - 1][q8] >= 2) {
         hipGraphExec_t& g = ws->be_g[tbz - 1][q8];
         if (!g && (rc = lm_capture(st, &g, "batch eval", layers)) != RCA_OK) return rc;
         RCA_HIP(hipGraphLaunch(g, st));
@@ -6066,8 +6095,7 @@ static int lm_eval_pass(rca_lm* ws, rca_lm* const* hs, const int32_t* const* ids
 extern "C" int rca_lm_batch_eval(rca_lm_t* ws, rca_lm_t* const* hs, int32_t n_h, const int32_t* ids, const int32_t* counts, int32_t want_logits) {
     if (!ws || !hs || !ids || !counts) return fail(RCA_ERR_ARG, "batch_eval: null argument");
     if (n_h < 1 || n_h > LM_EVAL_MAXH) return fail(RCA_ERR_ARG, "batch_eval: %d handles (1..%d)", n_h, LM_EVAL_MAXH);
-    static const bool flash = !(getenv("RCA_LM_FLASH") && atoi(getenv("RCA_LM_FLASH")) == 0);
-    if (!flash) return fail(RCA_ERR_STATE, "batch_eval: RCA_LM_FLASH=0 asks for the split-attention prefill, which has no table form; use rca_lm_eval_async");
+    if (!lm_env_flash()) return fail(RCA_ERR_STATE, "batch_eval: RCA_LM_FLASH=0 asks for the split-attention prefill, which has no table form; use rca_lm_eval_async");
     if (lm_prefill_route(ws) != LM_ROUTE_TILE128)
         return fail(RCA_ERR_ARG, "batch_eval: the workspace does not take the 128-token tiles (rca_lm_prefill_route %d, the call needs 2)", lm_prefill_route(ws));
     // every refusal before anything is staged or enqueued: no handle changes
@@ -6139,7 +6167,7 @@ extern "C" int rca_lm_batch_eval(rca_lm_t* ws, rca_lm_t* const* hs, int32_t n_h,
 // ------------------------------------------------------------------------------------ batch step (rca_lm_batch_step)
 // 2 to 64 sessions over ONE set of weights advance by n = 1 or 2 tokens each as ONE token block of the 128-token MFMA tiles: the
 // n_members * n rows are a small GEMM, not a GEMV, so a matrix is staged (and de-quantised) once for all of them and the cost of a
-// step grows slowly with the members.  The pass is lm_enqueue_prefill_tile128's for the row-wise stages -- embedding gather, RMSNorm +
+// step grows slowly with the members.  The layers are lm_enqueue_layers128, the prefill tile's own -- RMSNorm +
 // hi / lo split, O, gate / up + SwiGLU, down, with the same k-split forms (functions of the matrix only) -- driven by a batch-owned
 // LmDevState whose m is the row count.  What is per session comes from tables: the QKV epilogue (GEMM_EPI_ROPE_ROWS) takes a row's
 // position and cache from an LmGroupRow, the decode attention (split kernel + separate combine, never the in-launch merge) and the
@@ -6405,70 +6433,27 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
     rca_lm* ws = b->m[0];
     const rca_lm_config_t& c = ws->cfg;
     const int NM = vw.NM, MT = NM * n;
-    const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn, V = c.vocab_size;
-    const int G = c.n_heads / c.n_kv_heads;
-    const LmGroupRow* qrows = vw.rows;
+    const int H = c.hidden, V = c.vocab_size;
     const LmBatchMember* tab = vw.tab;
-    const LmDevState* bs = b->stt;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<4, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<2, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        (void)hipFuncSetAttribute((const void*)lm_attn_mfma_kernel<1, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTM_LDS);
-        attr_done = true;
-    }
-    // the k-split forms of one token block: what an rca_lm_eval_async pass of up to 128 tokens uses, so a row's sums are that pass's
-    const int seq_min = g128_seq_min();
-    const int so = g128_splits(H, AO), sg = g128_splits(2 * F, H), sd = g128_splits(H, F);
-    const G128Form fo = g128_form(H, so, 1, seq_min), fg = g128_form(2 * F, sg, 1, seq_min), fd = g128_form(H, sd, 1, seq_min);
-    GemvRope rope{ws->cos_t, ws->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, 0};   // cache, position and context bound: per row, from the table
-    const float scale = 1.0f / sqrtf((float)c.head_dim);
+    lm_attn_split_attrs();
     const dim3 agm(c.n_kv_heads, nsp_launch, NM);
+    const bool q8kv = lm_kv_q8(ws);   // every member's format (rca_lm_batch_create, lm_batch_check)
     float* x = ws->x;
-    lm_embed_kernel<<<MT, 256, 0, st>>>(bs, ws->embed, ws->embed_f32, x, H, V);
-    for (int l = 0; l < c.n_layers; ++l) {
-        const LmLayer& L = ws->layers[l];
-        const GemvGroup grp{qrows, l};
-        lm_add_rmsnorm_kernel<<<MT, 64, 0, st>>>(bs, x, nullptr, nullptr, 0, 0, L.attn_norm, ws->xn, H, c.rms_eps, ws->xh, ws->xl);
-        for (int seg = 0; seg < (L.split_v ? 2 : 1); ++seg) {
-            const WMat& w = seg ? L.vseg : L.qkv;
-            const int Ns = w.N, ss = g128_splits(Ns, H);
-            const G128Form fq = g128_form(Ns, ss, 1, seq_min);
-            rope.row_base = seg ? L.qkv.N : 0;
-            launch_gemm128<GEMM_EPI_ROPE_ROWS>(ws, w, dim3(Ns / 128, fq.grid_y, 1), st, ws->xh, ws->xl, Ns, H, H / ss, ws->qkv, QKV, nullptr, nullptr, rope, fq.nseq, bs, grp);
-            if (fq.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_ROPE_ROWS><<<dim3(Ns / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fq.ep_nsplit, fq.ep_grp, Ns, ws->qkv, QKV, nullptr, nullptr, rope, grp);
-        }
-        const bool q8kv = lm_kv_q8(ws);   // every member's format (rca_lm_batch_create, lm_batch_check)
+    lm_embed_kernel<<<MT, 256, 0, st>>>(b->stt, ws->embed, ws->embed_f32, x, H, V);
+    // one token block: the k-split forms are what an rca_lm_eval_async pass of up to 128 tokens uses, so a row's sums are that pass's
+    lm_enqueue_layers128(LmTilePass{ws, b->stt, MT, 1, vw.rows}, st, [&](int l) {
         if (q8kv)   // every member's new rows, ring -> int8 planes, in one launch
             lm_kv_quant_kernel<true><<<dim3(cdiv(4 * c.n_kv_heads, 8), n, NM), 256, 0, st>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, c.n_kv_heads, 0, 0, 0, 3, tab, l);
-#define RCA_BATCH_ATTN(GG)                                                                                                            \
-        if (q8kv) lm_attn_mfma_kernel<GG, true, 1><<<agm, 512, ATTM_LDS, st>>>(nullptr, ws->qkv, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, scale, 0, nullptr, \
-                                                                               nullptr, nullptr, tab, l);                                         \
-        else lm_attn_mfma_kernel<GG, true><<<agm, 512, ATTM_LDS, st>>>(nullptr, ws->qkv, nullptr, nullptr, c.n_heads, c.n_kv_heads, 0, scale, 0, nullptr, \
-                                                                  nullptr, nullptr, tab, l);                                                      \
-        lm_attn_mfma_batch_combine_kernel<GG><<<dim3(n * c.n_heads, NM), 64, 0, st>>>(tab, c.n_heads, c.n_kv_heads, nsp_launch, ws->xh, ws->xl);
-        if (G == 4) { RCA_BATCH_ATTN(4) }
-        else if (G == 2) { RCA_BATCH_ATTN(2) }
-        else { RCA_BATCH_ATTN(1) }
-#undef RCA_BATCH_ATTN
-        launch_gemm128<GEMM_EPI_RESID>(ws, L.o, dim3(H / 128, fo.grid_y, 1), st, ws->xh, ws->xl, H, AO, AO / so, x, H, nullptr, nullptr, norope, fo.nseq, bs);
-        if (fo.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fo.ep_nsplit, fo.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
-        lm_add_rmsnorm_kernel<<<MT, 64, 0, st>>>(bs, x, nullptr, nullptr, 0, 0, L.ffn_norm, ws->xn, H, c.rms_eps, ws->xh, ws->xl);
-        bf16_t* hh = reinterpret_cast<bf16_t*>(ws->hbuf);   // the SwiGLU epilogue's hi / lo planes, as in lm_enqueue_prefill_tile128
-        bf16_t* hl = hh + (long)LM_MAXM * F;
-        launch_gemm128<GEMM_EPI_SWIGLU>(ws, L.gu, dim3(2 * F / 128, fg.grid_y, 1), st, ws->xh, ws->xl, 2 * F, H, H / sg, nullptr, F, hh, hl, norope, fg.nseq, bs);
-        if (fg.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_SWIGLU><<<dim3(2 * F / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fg.ep_nsplit, fg.ep_grp, 2 * F, nullptr, 0, hh, hl, norope, nogroup);
-        launch_gemm128<GEMM_EPI_RESID>(ws, L.down, dim3(H / 128, fd.grid_y, 1), st, hh, hl, H, F, F / sd, x, H, nullptr, nullptr, norope, fd.nseq, bs);
-        if (fd.ep_nsplit) lm_gemm128_epilogue_kernel<GEMM_EPI_RESID><<<dim3(H / 64, cdiv(MT, 32)), 256, 0, st>>>(bs, ws->gpart, fd.ep_nsplit, fd.ep_grp, H, x, H, nullptr, nullptr, norope, nogroup);
-    }
+        lm_launch_attn_split(c, agm, q8kv, st, nullptr, ws->qkv, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, tab, l);
+        lm_dispatch_421(c.n_heads / c.n_kv_heads, [&](auto g) {
+            lm_attn_mfma_batch_combine_kernel<decltype(g)::value><<<dim3(n * c.n_heads, NM), 64, 0, st>>>(tab, c.n_heads, c.n_kv_heads, nsp_launch, ws->xh, ws->xl);
+        });
+    });
     // final RMSNorm + head over the last row of every member (one row per member: rows 0 .. NM - 1 of the hi / lo planes), every
     // workgroup walking all of K like rca_lm_score's head; the ragged last row tile of the vocabulary is the logits epilogue's
     if (n > 1) lm_batch_last_rows_kernel<<<NM, 256, 0, st>>>(x, ws->xn, n, H);
     lm_add_rmsnorm_kernel<<<NM, 64, 0, st>>>(b->stt_head, n > 1 ? ws->xn : x, nullptr, nullptr, 0, 0, ws->final_norm, ws->xn, H, c.rms_eps, ws->xh, ws->xl);
-    launch_gemm128<GEMM_EPI_LOGITS>(ws, ws->head, dim3(cdiv(V, 128), 1, 1), st, ws->xh, ws->xl, V, H, H, b->head_blk, V, nullptr, nullptr, norope, 1, b->stt_head);
+    lm_launch_logits128(ws, b->stt_head, ws->xh, ws->xl, 0, b->head_blk, st);
     lm_batch_logits_rows_kernel<<<dim3(std::min((int)cdiv(V, 256), 64), NM), 256, 0, st>>>(tab, b->head_blk, V);
     if (vw.any_serial) {
         if (vw.any_patch) samp_prepare_batch_kernel<<<dim3(1, NM), 128, 0, st>>>(tab, V);
@@ -7941,11 +7926,7 @@ static int lm_score_push(rca_lm* x, size_t* pin_off, const int32_t* ids, int m, 
 // final RMSNorm + head of tokens [tb, tb + 128) of the pass in x->x on the 128-row tiles -> x->sc_blk.  The caller has written the
 // hi / lo split of the normalised rows to x->xh / x->xl.  Every workgroup walks all of K itself (one slice: no partial sums).
 static void lm_launch_head128(rca_lm* x, int tb, hipStream_t st) {
-    const rca_lm_config_t& c = x->cfg;
-    GemvRope rp = norope;
-    rp.row_base = tb;
-    launch_gemm128<GEMM_EPI_LOGITS>(x, x->head, dim3(cdiv(c.vocab_size, 128), 1, 1), st, x->xh + (long)tb * c.hidden, x->xl + (long)tb * c.hidden,
-                                    c.vocab_size, c.hidden, c.hidden, x->sc_blk, c.vocab_size, nullptr, nullptr, rp, 1);
+    lm_launch_logits128(x, x->stt, x->xh + (long)tb * x->cfg.hidden, x->xl + (long)tb * x->cfg.hidden, tb, x->sc_blk, st);
 }
 
 extern "C" int rca_lm_score(rca_lm_t* h, rca_lm_t* base, const int32_t* ids, int32_t n, const int32_t* targets, rca_score_row_t* rows_host) {

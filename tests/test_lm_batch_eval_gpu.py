@@ -12,6 +12,7 @@ The contract, checked here against a SECOND handle taken from the same start thr
 
 Starts come from {0, 1, 31, 32, 255, 256, 257, 300} and n_ctx - count, counts from {1, 7, 8, 9, 31, 32, 33, 127, 128, 129, 200}:
 both sides of a flash tile (8 / 16 / 32 tokens), of the 32-row alignment of a segment, of a 128-token block and of the 256-key split.
+One more case runs the Q4_K_M file of lm_split_v_case (a layer whose V projection is a GEMM of its own) at contexts under 300 tokens.
 
 Every test here fails on a library without rca_lm_batch_eval (the parent commit: LlamaBatchEval does not exist)."""
 import ctypes as C
@@ -23,6 +24,7 @@ import pytest
 import torch
 
 import lm_shape_cases as sc
+import lm_split_v_case as sv
 
 pytestmark = pytest.mark.gpu
 
@@ -43,12 +45,14 @@ FAMILY = 30      # 13 handles and their 13 references, a bystander, spares for t
 
 
 def _ids(name):
-    return MODELS[name].ids().tolist()
+    return sv.ids() if name == sv.NAME else MODELS[name].ids().tolist()
 
 
 @functools.lru_cache(maxsize=None)
 def _family(name, fmt, kv, size=FAMILY):
     from realtime_codec_agent_amd.llm import LlamaForAlternatingCodeChannels as L
+    if name == sv.NAME:
+        return sv.family(6, kv)
     c = MODELS[name]
     parent = L(model_path=f"random:{name}", config=c.config(), n_ctx=c.n_ctx, random_seed=c.seed, init_std=sc.INIT_STD, device=0, weight_format=fmt, kv_format=kv)
     assert parent.weight_format == fmt and parent.prefill_route() == "gemm128" and parent.kv_format == kv
@@ -143,6 +147,14 @@ def _shapes(n_ctx):
 def test_every_handle_ends_with_the_bits_of_its_own_eval_async(name, fmt, kv, shape):
     starts, counts = _shapes(MODELS[name].n_ctx)[shape]
     _run_and_compare(name, fmt, kv, starts, counts)
+
+
+@pytest.mark.parametrize("kv", ("f16", "q8_0"))
+def test_a_file_with_a_v_projection_of_its_own_ends_with_the_bits_of_its_own_eval_async(kv):
+    """the Q4_K_M file of lm_split_v_case (layer 1: V as a GEMM of its own, row base in the row-table epilogue); padded rows
+    160 + 64 + 32, so two token blocks with pad rows inside and behind the segments, then a second call of the same geometry (replay)"""
+    _run_and_compare(sv.NAME, "q4_k", kv, [0, 31, 100], [129, 33, 7])
+    _run_and_compare(sv.NAME, "q4_k", kv, [3, 140, 32], [130, 40, 1])
 
 
 @pytest.mark.parametrize("name,fmt,kv", LONG_CASES, ids=[f"{n}-{f}-kv_{kv}" for n, f, kv in LONG_CASES])

@@ -14,6 +14,7 @@ Start contexts come from {0, 1, 254, 255, 256, 257, 300, 511, 512, LAST}: an emp
 (n = 2 straddles it), and LAST = n_ctx - steps * n, so that the final step of a test starts at n_ctx - n and writes the last slot.  Every
 batch then launches attention splits that some members do not have.  All members of a family evaluate prefixes of ONE id stream, so
 the oracle walks the stream once per (model, format) and every member's steps are a short continuation of a truncated copy.
+One more case (contract 2 and 3) runs the Q4_K_M file of lm_split_v_case, a layer of which has a V projection of its own.
 
 Every test here fails on a library without rca_lm_batch_create / rca_lm_batch_step (the parent commit: LlamaBatch does not exist and
 the symbols are missing)."""
@@ -214,6 +215,43 @@ def test_a_member_does_not_depend_on_slot_companions_or_graphs(name, fmt, t_star
     for tag, other in (("slot 40 of 64", b), ("eager", c)):
         for i, (x, y) in enumerate(zip(a, other)):
             assert np.array_equal(x, y), (name, fmt, tag, "logits" if i == 0 else f"K/V array {i - 1}")
+
+
+def test_a_file_with_a_v_projection_of_its_own_steps_the_same_in_every_batch():
+    """The Q4_K_M file of lm_split_v_case (layer 1: V as a GEMM of its own, row base in the row-table epilogue), 5 x 2 rows of one token
+    block.  The target's token, logits and K / V rows of every layer in slot 0 of 5 (graph replay) equal those in slot 1 of the smallest
+    batch (two members, eager, another companion); its layer-0 rows equal those its own rca_lm_eval_async writes."""
+    import lm_split_v_case as sv
+    from realtime_codec_agent_amd.llm import LlamaBatch
+    fam, ids = sv.family(6), sv.ids()
+    target, twin, t_start, n = fam[4], fam[5], 257, 2
+    cur = [ids[280], ids[281]]
+    outs = []
+    for members, starts, graphs in (([target] + fam[:4], [t_start, 0, 1, 255, 31], True), ([fam[3], target], [130, t_start], False)):
+        _prepare(members, ids, starts, graphs=graphs)
+        rows = [cur if m is target else [ids[(200 + 7 * s + j) % len(ids)] for j in range(n)] for s, m in enumerate(members)]
+        bat = LlamaBatch(members)
+        try:
+            for _ in range(2 if graphs else 1):                      # (with graphs: once more from the same positions, a replay)
+                for m, s in zip(members, starts):
+                    m.n_tokens = s
+                toks = bat.step(rows)
+        finally:
+            bat.close()
+            for m in members:
+                m.set_graphs(True)
+        out = [np.asarray(toks[members.index(target)]), target._scores[-1].copy()]
+        for layer in range(target.config.n_layers):
+            out.extend(_kv_bits(target, layer, t_start, n))
+        outs.append(out)
+    assert all(a.any() for a in outs[0][1:])
+    for i, (x, y) in enumerate(zip(*outs)):
+        assert np.array_equal(x, y), ("token", "logits")[i] if i < 2 else f"K/V array {i - 2}"
+    _prepare([twin], ids, [t_start])
+    twin.eval_async(cur)
+    twin.sync()
+    for got, want in zip(outs[0][2:4], _kv_bits(twin, 0, t_start, n)):
+        assert np.array_equal(got, want), "layer 0 rows differ from eval_async's"
 
 
 @pytest.mark.parametrize("nm,n", ((33, 1), (17, 2)), ids=("33x1", "17x2"))

@@ -187,6 +187,32 @@ def test_bit_exactness_contracts(name, fmt):
         assert np.array_equal(outs[0][1], outs[1][1]), (name, fmt, n, "the caches the two cuts left differ")
 
 
+@pytest.mark.parametrize("kv", ("f16", "q8_0"))
+def test_split_v_file_pieces_and_one_pass_leave_the_same_cache(kv):
+    """A Q4_K_M file whose layer 1 runs its V projection as a GEMM of its own (lm_split_v_case): one pass of 270 tokens (three token
+    blocks, the last ragged) and pieces of 13, 150, 9 and 98 tokens leave the same logits and the same K / V bits in every layer."""
+    import lm_split_v_case as sv
+    ids, n = sv.ids(), 270
+    outs = []
+    for cut in (((0, n),), ((0, 13), (13, 163), (163, 172), (172, n))):
+        llm = sv.family(1, kv)[0]
+        llm.set_mfma_prefill(True)
+        llm.set_graphs(True)
+        llm.reset()
+        for lo, hi in cut:
+            assert hi - lo > sc.LM_PREFILL_MIN
+            llm.eval(ids[lo:hi])
+        state = [llm._scores[-1].copy()]
+        for layer in range(llm.config.n_layers):
+            state += [a.view(np.uint16).copy() for a in llm.kv_read(layer, 0, n)]
+            if kv == "q8_0":
+                state += [a.copy() if a.dtype == np.int8 else a.view(np.uint16).copy() for a in llm.kv_read_q8(layer, 0, n)]
+        outs.append(state)
+    assert len(outs[0]) == len(outs[1]) and all(a.any() for a in outs[0])
+    for i, (a, b) in enumerate(zip(*outs)):
+        assert a.shape == b.shape and np.array_equal(a, b), (kv, "logits" if i == 0 else f"K / V array {i - 1}", "depends on the cut")
+
+
 def test_context_limit_inside_the_last_attention_split():
     """n_ctx = 700 (cache padded to 768 positions): decode and prefill up to within 2 tokens of n_ctx and up to n_ctx itself against
     the oracle; the eval that would pass n_ctx is refused with RCA_ERR_STATE and leaves n_tokens and the logits as they were."""
