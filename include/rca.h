@@ -436,6 +436,24 @@ int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b);
  * frame / duplex graphs stay valid (the cache does not move and positions come from the device state).  The first call that moves
  * rows allocates a staging buffer of 2 x 2 x n_layers x 256 cache rows, freed with the handle. */
 int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1);
+/* The context shift of several handles in one pass: every hs[k] ends exactly as rca_lm_kv_remove(hs[k], p0[k], p1[k]) would leave it,
+ * bit for bit -- n_tokens, the K / V rows [0, n_tokens) of every layer, the last logits still readable, captured step / frame / duplex /
+ * batch graphs still valid, rows at and above the new n_tokens stale.  No byte of a handle outside hs is touched.  Pending
+ * rca_lm_eval_async / rca_lm_batch_eval work of every hs[k] is settled first and the other handles' streams are drained (as
+ * rca_lm_swap_kv does); the launches run on hs[0]'s stream and the call returns after ONE synchronisation.  One launch covers one slab
+ * step of up to RCA_LM_KV_REMOVE_GROUP handles, each with the RoPE rows of its own delta; handles with delta == 0 or p1 == n_tokens
+ * launch nothing.  A handle with delta >= 256 moves its rows cache to cache in slabs of delta rows (source and destination slabs are
+ * disjoint then), without staging; the others take the single call's 256-row slabs through two staging slabs each.  That staging
+ * belongs to the weight owner, is allocated by the first call with such a handle and freed with the weights, and is bounded:
+ * RCA_LM_KV_REMOVE_GROUP x 2 x 2 x n_layers x 256 cache rows (134 MB at 16 layers x 8 KV heads), however many handles a call names --
+ * they are processed in launch groups of RCA_LM_KV_REMOVE_GROUP.  Takes handles, not a batch: it does not need the 128-token tile route.
+ * Refused before anything is enqueued, no handle changed, the message naming k: RCA_ERR_ARG for n_h outside 1..64, a null or repeated
+ * handle, a handle on another device than hs[0], a handle that does not share hs[0]'s weights (the parent and its
+ * rca_lm_create_shared twins do), a span with p0 < 0, p0 > p1 or p1 > n_tokens; RCA_ERR_STATE for a handle with a q8_0 KV cache. */
+#define RCA_LM_KV_REMOVE_GROUP 8
+int rca_lm_kv_remove_many(rca_lm_t* const* hs, int32_t n_h, const int32_t* p0, const int32_t* p1);
+/* Tests and measurements: rca_lm_kv_remove_many with every handle on the staged route, whatever its delta.  Same contract, same bits. */
+int rca_lm_kv_remove_many_staged(rca_lm_t* const* hs, int32_t n_h, const int32_t* p0, const int32_t* p1);
 /* Tests only: raw fp16 rows [n_pos][n_kv_heads][64] of positions [pos0, pos0 + n_pos) (inside n_ctx) of one layer's K and V cache,
  * after draining the handle's stream.  Either pointer may be NULL. */
 int rca_lm_kv_read(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, uint16_t* k_host, uint16_t* v_host);

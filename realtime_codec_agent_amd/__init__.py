@@ -17,6 +17,7 @@ _LAZY = {
     "LlamaGroup": ".llm",
     "LlamaBatch": ".llm",
     "LlamaBatchEval": ".llm",
+    "kv_remove_many": ".llm",
     "MagiCodecHIP": ".codec",
     "HipCodec": ".codec",
     "CodecConfig": ".codec_model",

@@ -325,6 +325,8 @@ _I32P = C.POINTER(C.c_int32)
 BATCH_STEP_SEL_ARGTYPES = [C.c_void_p, _I32P, C.c_int32, _I32P, C.c_int32, _I32P, C.c_int32, _I32P, C.POINTER(C.c_float)]
 # int rca_lm_batch_eval(ws, hs, n_h, ids, counts, want_logits)
 BATCH_EVAL_ARGTYPES = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, _I32P, _I32P, C.c_int32]
+# int rca_lm_kv_remove_many(hs, n_h, p0, p1) (and its staged-route-only form)
+KV_REMOVE_MANY_ARGTYPES = [C.POINTER(C.c_void_p), C.c_int32, _I32P, _I32P]
 
 
 def sources() -> List[str]:
@@ -448,7 +450,7 @@ ABI_SYMBOLS = [
     "rca_lm_group_create", "rca_lm_group_destroy", "rca_lm_group_step",
     "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
     "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame", "rca_lm_batch_step_sel",
-    "rca_lm_batch_eval",
+    "rca_lm_batch_eval", "rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged",
 ]
 
 
@@ -477,6 +479,10 @@ def lib():
     if hasattr(_lib, "rca_lm_batch_eval"):   # (a library from before the call: build() reports the missing symbol)
         _lib.rca_lm_batch_eval.argtypes = BATCH_EVAL_ARGTYPES
         _lib.rca_lm_batch_eval.restype = C.c_int
+    for name in ("rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged"):
+        if hasattr(_lib, name):
+            getattr(_lib, name).argtypes = KV_REMOVE_MANY_ARGTYPES
+            getattr(_lib, name).restype = C.c_int
     return _lib
 
 

@@ -2214,6 +2214,8 @@ struct rca_lm {
     int kv_format = 0;                   // 0 fp16, 1 q8_0 (rca_lm_set_kv_format)
     f16_t *ring_k = nullptr, *ring_v = nullptr;   // q8_0: [LM_KV_RING][nkv][64] fp16 rows of the current pass and layer, what the QKV epilogues store
     f16_t* kv_stage = nullptr;           // rca_lm_kv_remove: two slabs of [K, V][L][ATT_KEYS][nkv][hd], allocated by the first call that moves rows
+    f16_t* kv_stage_many = nullptr;      // rca_lm_kv_remove_many, on the weight OWNER only: RCA_LM_KV_REMOVE_GROUP such pairs of slabs, allocated by the first
+                                         // call with a staged member, freed with the weights (lm_free_weights)
     long kv_layer_stride = 0;
     int n_ctx_pad = 0, n_splits = 0;
     // activations
@@ -2355,11 +2357,12 @@ static void lm_free_weights(rca_lm* h) {
             if (p) (void)hipFree(p);
     }
     h->head.release();
-    for (void* p : {(void*)h->embed, (void*)h->final_norm, (void*)h->cos_t, (void*)h->sin_t})
+    for (void* p : {(void*)h->embed, (void*)h->final_norm, (void*)h->cos_t, (void*)h->sin_t, (void*)h->kv_stage_many})
         if (p) (void)hipFree(p);
     h->layers.clear();
     h->embed = nullptr;
     h->final_norm = h->cos_t = h->sin_t = nullptr;
+    h->kv_stage_many = nullptr;
 }
 
 // The captured step graphs carry the addresses of the logits buffer, the KV cache and the workspace in their kernel nodes:
@@ -5400,50 +5403,79 @@ extern "C" int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b) {
 // the workgroups run in; between launches the stream orders.
 // One unit = one thread = (layer, row of the slab, kv head, quarter q): elements q * 8 .. q * 8 + 7 and their RoPE partners
 // q * 8 + 32 .. q * 8 + 39 (the pairing the QKV epilogues store) of the K row and the same 2 x 16 bytes of the V row.
+// The body of one unit, shared by the single-handle kernel and the table form (rca_lm_kv_remove_many) so that a row's bits cannot
+// differ between them.  stage_w == nullptr is the direct route of the table form: the rotated rows go straight to cache rows
+// dst_pos + r (the host has shown that they are disjoint from every source row of the launch) and there are no kind-B units.
+static __device__ __forceinline__ void lm_kv_shift_unit(f16_t* kc, f16_t* vc, f16_t* stage_w, const f16_t* stage_r,
+                                                        const float* cos_d, const float* sin_d, long layer_stride, int n_layers, int nkv,
+                                                        int src_pos, int n_src, int dst_pos, int n_dst, long u, long ua) {
+    const long stage_v = (long)n_layers * ATT_KEYS * nkv * 64;     // a staging slab holds its K rows first, its V rows stage_v elements later
+    const bool rot = u < ua;
+    long t = rot ? u : u - ua;
+    const int npos = rot ? n_src : n_dst;
+    const int q = (int)(t & 3);
+    t >>= 2;
+    const int kvh = (int)(t % nkv);
+    t /= nkv;
+    const int r = (int)(t % npos), l = (int)(t / npos);
+    const long so = (((long)l * ATT_KEYS + r) * nkv + kvh) * 64 + q * 8;
+    const long co = (long)l * layer_stride + ((long)((rot ? src_pos : dst_pos) + r) * nkv + kvh) * 64 + q * 8;
+    if (rot) {
+        const f16x8 k1 = *reinterpret_cast<const f16x8*>(kc + co), k2 = *reinterpret_cast<const f16x8*>(kc + co + 32);
+        const u32x4 v1 = *reinterpret_cast<const u32x4*>(vc + co), v2 = *reinterpret_cast<const u32x4*>(vc + co + 32);
+        float c[8], s[8];
+        *reinterpret_cast<f32x4*>(c) = *reinterpret_cast<const f32x4*>(cos_d + q * 8);
+        *reinterpret_cast<f32x4*>(c + 4) = *reinterpret_cast<const f32x4*>(cos_d + q * 8 + 4);
+        *reinterpret_cast<f32x4*>(s) = *reinterpret_cast<const f32x4*>(sin_d + q * 8);
+        *reinterpret_cast<f32x4*>(s + 4) = *reinterpret_cast<const f32x4*>(sin_d + q * 8 + 4);
+        f16x8 o1, o2;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float x1 = (float)k1[j], x2 = (float)k2[j];
+            o1[j] = (f16_t)(x1 * c[j] + x2 * s[j]);       // the inverse of the epilogues' x1 c - x2 s, x2 c + x1 s; f32, then fp16 nearest-even
+            o2[j] = (f16_t)(x2 * c[j] - x1 * s[j]);
+        }
+        const long cd = (long)l * layer_stride + ((long)(dst_pos + r) * nkv + kvh) * 64 + q * 8;
+        f16_t* kw = stage_w ? stage_w + so : kc + cd;
+        f16_t* vw = stage_w ? stage_w + stage_v + so : vc + cd;
+        *reinterpret_cast<f16x8*>(kw) = o1;
+        *reinterpret_cast<f16x8*>(kw + 32) = o2;
+        *reinterpret_cast<u32x4*>(vw) = v1;
+        *reinterpret_cast<u32x4*>(vw + 32) = v2;
+    } else {
+        const u32x4 k1 = *reinterpret_cast<const u32x4*>(stage_r + so), k2 = *reinterpret_cast<const u32x4*>(stage_r + so + 32);
+        const u32x4 v1 = *reinterpret_cast<const u32x4*>(stage_r + stage_v + so), v2 = *reinterpret_cast<const u32x4*>(stage_r + stage_v + so + 32);
+        *reinterpret_cast<u32x4*>(kc + co) = k1;
+        *reinterpret_cast<u32x4*>(kc + co + 32) = k2;
+        *reinterpret_cast<u32x4*>(vc + co) = v1;
+        *reinterpret_cast<u32x4*>(vc + co + 32) = v2;
+    }
+}
 __global__ __launch_bounds__(256) void lm_kv_shift_kernel(f16_t* kc, f16_t* vc, f16_t* __restrict__ stage_w, const f16_t* __restrict__ stage_r,
                                                           const float* __restrict__ cos_d, const float* __restrict__ sin_d,   // rows `delta` of the RoPE tables
                                                           long layer_stride, int n_layers, int nkv, int src_pos, int n_src, int dst_pos, int n_dst) {
-    const long stage_v = (long)n_layers * ATT_KEYS * nkv * 64;     // a staging slab holds its K rows first, its V rows stage_v elements later
     const long ua = (long)n_layers * n_src * nkv * 4, ub = (long)n_layers * n_dst * nkv * 4;
-    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < ua + ub; u += (long)gridDim.x * 256) {
-        const bool rot = u < ua;
-        long t = rot ? u : u - ua;
-        const int npos = rot ? n_src : n_dst;
-        const int q = (int)(t & 3);
-        t >>= 2;
-        const int kvh = (int)(t % nkv);
-        t /= nkv;
-        const int r = (int)(t % npos), l = (int)(t / npos);
-        const long so = (((long)l * ATT_KEYS + r) * nkv + kvh) * 64 + q * 8;
-        const long co = (long)l * layer_stride + ((long)((rot ? src_pos : dst_pos) + r) * nkv + kvh) * 64 + q * 8;
-        if (rot) {
-            const f16x8 k1 = *reinterpret_cast<const f16x8*>(kc + co), k2 = *reinterpret_cast<const f16x8*>(kc + co + 32);
-            const u32x4 v1 = *reinterpret_cast<const u32x4*>(vc + co), v2 = *reinterpret_cast<const u32x4*>(vc + co + 32);
-            float c[8], s[8];
-            *reinterpret_cast<f32x4*>(c) = *reinterpret_cast<const f32x4*>(cos_d + q * 8);
-            *reinterpret_cast<f32x4*>(c + 4) = *reinterpret_cast<const f32x4*>(cos_d + q * 8 + 4);
-            *reinterpret_cast<f32x4*>(s) = *reinterpret_cast<const f32x4*>(sin_d + q * 8);
-            *reinterpret_cast<f32x4*>(s + 4) = *reinterpret_cast<const f32x4*>(sin_d + q * 8 + 4);
-            f16x8 o1, o2;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float x1 = (float)k1[j], x2 = (float)k2[j];
-                o1[j] = (f16_t)(x1 * c[j] + x2 * s[j]);       // the inverse of the epilogues' x1 c - x2 s, x2 c + x1 s; f32, then fp16 nearest-even
-                o2[j] = (f16_t)(x2 * c[j] - x1 * s[j]);
-            }
-            *reinterpret_cast<f16x8*>(stage_w + so) = o1;
-            *reinterpret_cast<f16x8*>(stage_w + so + 32) = o2;
-            *reinterpret_cast<u32x4*>(stage_w + stage_v + so) = v1;
-            *reinterpret_cast<u32x4*>(stage_w + stage_v + so + 32) = v2;
-        } else {
-            const u32x4 k1 = *reinterpret_cast<const u32x4*>(stage_r + so), k2 = *reinterpret_cast<const u32x4*>(stage_r + so + 32);
-            const u32x4 v1 = *reinterpret_cast<const u32x4*>(stage_r + stage_v + so), v2 = *reinterpret_cast<const u32x4*>(stage_r + stage_v + so + 32);
-            *reinterpret_cast<u32x4*>(kc + co) = k1;
-            *reinterpret_cast<u32x4*>(kc + co + 32) = k2;
-            *reinterpret_cast<u32x4*>(vc + co) = v1;
-            *reinterpret_cast<u32x4*>(vc + co + 32) = v2;
-        }
-    }
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < ua + ub; u += (long)gridDim.x * 256)
+        lm_kv_shift_unit(kc, vc, stage_w, stage_r, cos_d, sin_d, layer_stride, n_layers, nkv, src_pos, n_src, dst_pos, n_dst, u, ua);
+}
+// The table form: blockIdx.y picks a handle's row, and the row carries everything that differs between handles -- its cache, its
+// staging slabs, the RoPE rows of ITS delta and the positions of this step.  A row whose tail has ended has n_src = n_dst = 0.
+// The table travels by value in the kernel arguments (RCA_LM_KV_REMOVE_GROUP rows of 72 bytes): composed on the host, uploaded with
+// the launch, and nothing of it outlives the launch.
+struct LmShiftRow {
+    f16_t *kc, *vc;
+    f16_t* stage_w;            // nullptr: the direct route (rotated rows to cache rows dst_pos + r, n_dst = 0)
+    const f16_t* stage_r;
+    const float *cos_d, *sin_d;
+    long layer_stride;
+    int src_pos, n_src, dst_pos, n_dst;
+};
+struct LmShiftTable { LmShiftRow row[RCA_LM_KV_REMOVE_GROUP]; };
+__global__ __launch_bounds__(256) void lm_kv_shift_many_kernel(const LmShiftTable tab, int n_layers, int nkv) {
+    const LmShiftRow& w = tab.row[blockIdx.y];
+    const long ua = (long)n_layers * w.n_src * nkv * 4, ub = (long)n_layers * w.n_dst * nkv * 4;
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < ua + ub; u += (long)gridDim.x * 256)
+        lm_kv_shift_unit(w.kc, w.vc, w.stage_w, w.stage_r, w.cos_d, w.sin_d, w.layer_stride, n_layers, nkv, w.src_pos, w.n_src, w.dst_pos, w.n_dst, u, ua);
 }
 extern "C" int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1) {
     if (!h) return fail(RCA_ERR_ARG, "null");
@@ -5480,6 +5512,103 @@ extern "C" int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1) {
     h->n_tokens = n - delta;
     return RCA_OK;
 }
+// ---- the context shift of several handles in one pass (rca_lm_kv_remove_many).  The handles that have rows to move are taken in
+// launch groups of RCA_LM_KV_REMOVE_GROUP; step i of a group is ONE launch of the table form, whose row k holds member k's step i.
+//   staged member (delta < ATT_KEYS): the steps of the single call, slab for slab, through its own two staging slabs (slot k of the
+//     group's staging buffer, which lives on the weight owner and is reused by the next group: the stream orders them).
+//   direct member (delta >= ATT_KEYS): slabs of R = delta rows, rotated from the cache straight into the cache.  Step i reads rows
+//     [p1 + R i, p1 + R (i + 1)) and writes rows [p0 + R i, p0 + R (i + 1)); the write ends at p0 + R (i + 1) = p1 + R i, where the
+//     read starts, so inside a launch no row is both read and written, and every later step reads above what this one wrote.  No
+//     staging, half the traffic, ceil(tail / delta) steps.
+// The values written are those of the single call on either route: the same unit body, the same RoPE rows.
+static rca_lm* lm_weight_root(rca_lm* h) { return h->weights_of ? h->weights_of : h; }
+static int lm_kv_remove_many(rca_lm_t* const* hs, int32_t n_h, const int32_t* p0, const int32_t* p1, bool allow_direct) {
+    if (!hs || !p0 || !p1) return fail(RCA_ERR_ARG, "kv_remove_many: null argument");
+    if (n_h < 1 || n_h > 64) return fail(RCA_ERR_ARG, "kv_remove_many: %d handles (1 to 64)", n_h);
+    for (int k = 0; k < n_h; ++k) {
+        rca_lm* h = hs[k];
+        if (!h) return fail(RCA_ERR_ARG, "kv_remove_many: handle %d is null", k);
+        for (int j = 0; j < k; ++j)
+            if (hs[j] == h) return fail(RCA_ERR_ARG, "kv_remove_many: handle %d is handle %d again", k, j);
+        if (h->device != hs[0]->device) return fail(RCA_ERR_ARG, "kv_remove_many: handle %d is on device %d, handle 0 on device %d", k, h->device, hs[0]->device);
+        if (lm_weight_root(h) != lm_weight_root(hs[0]))
+            return fail(RCA_ERR_ARG, "kv_remove_many: handle %d does not share handle 0's weights (rca_lm_create_shared): RoPE tables and dimensions must be the same", k);
+    }
+    for (int k = 0; k < n_h; ++k)
+        if (lm_kv_q8(hs[k]))
+            return fail(RCA_ERR_STATE, "kv_remove_many: handle %d keeps a q8_0 KV cache (rca_lm_set_kv_format); re-rotating quantised keys would quantise them a second time, "
+                                       "which this version does not do -- use an fp16 cache for the context shift", k);
+    for (int k = 0; k < n_h; ++k) { const int rc = lm_settle(hs[k]); if (rc != RCA_OK) return rc; }
+    for (int k = 0; k < n_h; ++k)
+        if (p0[k] < 0 || p0[k] > p1[k] || p1[k] > hs[k]->n_tokens)
+            return fail(RCA_ERR_ARG, "kv_remove_many: [%d, %d) of handle %d is not a span of its %d cached positions", p0[k], p1[k], k, hs[k]->n_tokens);
+    int act[64], n_act = 0;
+    bool any_staged = false;
+    for (int k = 0; k < n_h; ++k)
+        if (p1[k] > p0[k] && hs[k]->n_tokens > p1[k]) {
+            act[n_act++] = k;
+            any_staged = any_staged || !(allow_direct && p1[k] - p0[k] >= ATT_KEYS);
+        }
+    if (n_act) {
+        rca_lm* const lead = hs[0];
+        rca_lm* const root = lm_weight_root(lead);
+        const rca_lm_config_t& c = lead->cfg;
+        RCA_HIP(hipSetDevice(lead->device));
+        const long slab = 2L * c.n_layers * ATT_KEYS * c.n_kv_heads * 64;      // elements: K rows, then V rows
+        if (any_staged && !root->kv_stage_many) {
+            const int rc = lm_alloc((void**)&root->kv_stage_many, (size_t)slab * 2 * RCA_LM_KV_REMOVE_GROUP * sizeof(f16_t));
+            if (rc != RCA_OK) return rc;
+        }
+        for (int k = 0; k < n_h; ++k)      // whatever the other handles' streams still hold (a step's tail, a copy_kv) is in their caches first
+            if (hs[k]->stream != lead->stream) RCA_HIP(hipStreamSynchronize(hs[k]->stream));
+        for (int g0 = 0; g0 < n_act; g0 += RCA_LM_KV_REMOVE_GROUP) {
+            const int gn = std::min(RCA_LM_KV_REMOVE_GROUP, n_act - g0);
+            int R[RCA_LM_KV_REMOVE_GROUP], steps[RCA_LM_KV_REMOVE_GROUP], n_steps = 0;      // R 0: a staged member
+            for (int j = 0; j < gn; ++j) {
+                const int k = act[g0 + j], delta = p1[k] - p0[k], tail = hs[k]->n_tokens - p1[k];
+                R[j] = allow_direct && delta >= ATT_KEYS ? delta : 0;
+                steps[j] = R[j] ? (tail + R[j] - 1) / R[j] : (tail + ATT_KEYS - 1) / ATT_KEYS + 1;
+                n_steps = std::max(n_steps, steps[j]);
+            }
+            for (int i = 0; i < n_steps; ++i) {
+                LmShiftTable tab;
+                long most = 0;
+                for (int j = 0; j < gn; ++j) {
+                    const int k = act[g0 + j], delta = p1[k] - p0[k], tail = hs[k]->n_tokens - p1[k];
+                    rca_lm* h = hs[k];
+                    LmShiftRow& w = tab.row[j];
+                    w.kc = h->kc; w.vc = h->vc;
+                    w.cos_d = h->cos_t + (long)delta * 32;      // delta < n_tokens <= n_ctx: inside the tables (the owner's, for a borrower)
+                    w.sin_d = h->sin_t + (long)delta * 32;
+                    w.layer_stride = h->kv_layer_stride;
+                    if (R[j]) {
+                        w.stage_w = nullptr; w.stage_r = nullptr;
+                        w.src_pos = p1[k] + R[j] * i; w.dst_pos = p0[k] + R[j] * i;
+                        w.n_src = i < steps[j] ? std::min(R[j], tail - R[j] * i) : 0;
+                        w.n_dst = 0;
+                    } else {
+                        f16_t* st = root->kv_stage_many + (long)j * 2 * slab;
+                        const int nslab = steps[j] - 1;
+                        w.stage_w = st + (long)(i & 1) * slab; w.stage_r = st + (long)((i + 1) & 1) * slab;
+                        w.src_pos = p1[k] + ATT_KEYS * i; w.dst_pos = p0[k] + ATT_KEYS * (i - 1);
+                        w.n_src = i < nslab ? std::min(ATT_KEYS, tail - ATT_KEYS * i) : 0;
+                        w.n_dst = i > 0 && i <= nslab ? std::min(ATT_KEYS, tail - ATT_KEYS * (i - 1)) : 0;
+                    }
+                    most = std::max(most, (long)c.n_layers * (w.n_src + w.n_dst) * c.n_kv_heads * 4);
+                }
+                for (int j = gn; j < RCA_LM_KV_REMOVE_GROUP; ++j) tab.row[j] = LmShiftRow{};
+                const int blocks = (int)std::min<long>((most + 255) / 256, 1024);
+                lm_kv_shift_many_kernel<<<dim3(blocks, gn), 256, 0, lead->stream>>>(tab, c.n_layers, c.n_kv_heads);
+                RCA_LAUNCH_CHECK();
+            }
+        }
+        RCA_HIP(hipStreamSynchronize(lead->stream));
+    }
+    for (int k = 0; k < n_h; ++k) hs[k]->n_tokens -= p1[k] - p0[k];
+    return RCA_OK;
+}
+extern "C" int rca_lm_kv_remove_many(rca_lm_t* const* hs, int32_t n_h, const int32_t* p0, const int32_t* p1) { return lm_kv_remove_many(hs, n_h, p0, p1, true); }
+extern "C" int rca_lm_kv_remove_many_staged(rca_lm_t* const* hs, int32_t n_h, const int32_t* p0, const int32_t* p1) { return lm_kv_remove_many(hs, n_h, p0, p1, false); }
 // q8_0 cache: rows [pos0, pos0 + n_pos) of layer `layer` of one tensor (base = kc or vc), de-quantised into dst_host through a scratch buffer
 static int lm_kv_read_deq(rca_lm* h, const f16_t* base, int layer, int pos0, int n_pos, uint16_t* dst_host) {
     const long n = (long)n_pos * h->cfg.n_kv_heads * 64, off = (long)pos0 * h->cfg.n_kv_heads * 64;

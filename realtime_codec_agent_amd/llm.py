@@ -758,6 +758,11 @@ class LlamaForAlternatingCodeChannels:
         N.check(self._lib.rca_lm_kv_remove(self._h, p0, p1), "rca_lm_kv_remove")
         self._input_ids[p0:n - (p1 - p0)] = self._input_ids[p1:n].copy()
 
+    @staticmethod
+    def kv_remove_many(llms: Sequence["LlamaForAlternatingCodeChannels"], spans: Sequence[Sequence[int]], staged_only: bool = False) -> None:
+        """kv_remove(p0, p1) of several handles over one set of weights in ONE library call (the module function kv_remove_many)."""
+        kv_remove_many(llms, spans, staged_only)
+
     def kv_read(self, layer: int, pos0: int, n_pos: int):
         """Tests only (rca_lm_kv_read): the raw K and V cache rows [n_pos, n_kv_heads, 64] of one layer as float16."""
         k = np.empty((int(n_pos), self.config.n_kv_heads, 64), np.float16)
@@ -848,6 +853,27 @@ class LlamaForAlternatingCodeChannels:
 
     def set_graphs(self, enable: bool) -> None:
         N.check(self._lib.rca_lm_set_graphs(self._h, 1 if enable else 0), "rca_lm_set_graphs")
+
+
+def kv_remove_many(llms: Sequence["LlamaForAlternatingCodeChannels"], spans: Sequence[Sequence[int]], staged_only: bool = False) -> None:
+    """The context shift of 1 to 64 handles over ONE set of weights (a handle and its share_weights_with= twins) in one library call
+    (rca_lm_kv_remove_many): llms[k] ends exactly as llms[k].kv_remove(*spans[k]) would leave it, bit for bit, but the handles' slabs
+    share their launches and the call ends in one synchronisation.  A refusal (a repeated handle, a handle of other weights, a q8_0
+    cache, a span outside a handle's positions) raises and leaves every handle and every mirror as it was.  staged_only (tests and
+    measurements) keeps every handle on the staged route whatever its span."""
+    llms = list(llms)
+    rows = [(int(a), int(b)) for a, b in spans]
+    if len(rows) != len(llms):
+        raise ValueError(f"{len(rows)} spans for {len(llms)} handles")
+    lib = llms[0]._lib if llms else N.lib()
+    ns = [m.n_tokens for m in llms]
+    hs = (C.c_void_p * max(len(llms), 1))(*[m._h for m in llms])
+    p0 = (C.c_int32 * max(len(rows), 1))(*[r[0] for r in rows])
+    p1 = (C.c_int32 * max(len(rows), 1))(*[r[1] for r in rows])
+    call = lib.rca_lm_kv_remove_many_staged if staged_only else lib.rca_lm_kv_remove_many
+    N.check(call(hs, len(llms), p0, p1), "rca_lm_kv_remove_many")
+    for m, n, (a, b) in zip(llms, ns, rows):
+        m._input_ids[a:n - (b - a)] = m._input_ids[b:n].copy()
 
 
 class LlamaGroup:
@@ -1085,6 +1111,14 @@ class LlamaBatch:
             res.append({"user_codes": uc, "tokens": tk, "pcm": pcm[k] if flags[k] == 0 else None,
                         "probe_prob": float(prob[k]) if prob[k] >= 0.0 else None, "flags": int(flags[k])})
         return res
+
+    def kv_remove(self, members: Sequence[int], spans: Sequence[Sequence[int]]) -> None:
+        """kv_remove_many over the members with these indices: member members[k] drops its cache positions spans[k] = (p0, p1)."""
+        idx = [int(s) for s in members]
+        for s in idx:
+            if not 0 <= s < len(self.members):
+                raise ValueError(f"member {s} outside the batch of {len(self.members)}")
+        kv_remove_many([self.members[s] for s in idx], spans)
 
     def captures(self) -> int:
         """graph captures this batch has made so far (rca_lm_batch_captures): selections of one geometry class (up to 8, 16, 32, 64

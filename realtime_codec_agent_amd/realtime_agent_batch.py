@@ -20,6 +20,12 @@ batch_shadow_tiles=True (off by default) feeds the shadow-cache tiles that fall 
 session every ~16 ticks) to the sessions' twins in ONE LlamaBatchEval.eval_async (rca_lm_batch_eval) instead of one eval_async per
 session, each a pass over all weights.  A twin ends with the bits of its own eval_async, so tokens, PCM and caches are those of the
 flag off.  LMs without the call (llama.cpp objects, test fakes, models off the 128-token tiles) keep the per-session advance.
+
+batch_shift_trims=True (off by default) is for sessions in kv_trim_mode="shift": the context shifts that fall due while a tick is
+planned (sessions admitted together reach max_context_secs on the same tick) are recorded instead of issued, and ONE kv_remove_many
+(rca_lm_kv_remove_many) runs them before the tick's first LM call when there are at least two; a single one takes kv_remove.  Every
+cache ends with the bits of its own kv_remove, so tokens, PCM and caches are those of the flag off.  A trim that falls between two
+steps of a frame stays with its session, and so do LM objects without kv_remove_many.
 Not thread-safe: one caller per tick."""
 from typing import List, Optional, Sequence, Tuple
 
@@ -28,7 +34,7 @@ import numpy as np
 
 class RealtimeAgentBatch:
     def __init__(self, agents: Sequence, min_batch: int = 4, use_duplex_batch_graph: bool = True, batch_speaker_step: bool = False,
-                 batch_shadow_tiles: bool = False):
+                 batch_shadow_tiles: bool = False, batch_shift_trims: bool = False):
         self.agents = list(agents)
         # where one batch call starts to win over as many single calls: 4, the smallest size measured, for the frame (profiles/r16:
         # 11.0 against 13.8 ms) and for the speaker step (profiles/r18: 2.64 against 3.29 ms; three single steps are 2.5 ms)
@@ -42,6 +48,9 @@ class RealtimeAgentBatch:
         self.batch_shadow_tiles = bool(batch_shadow_tiles)
         self.fused_shadow_calls = 0    # LlamaBatchEval calls that fed the shadow tiles of several sessions
         self.fused_shadow_tiles = 0    # tiles that went through them
+        self.batch_shift_trims = bool(batch_shift_trims)
+        self.fused_shift_calls = 0     # kv_remove_many calls that ran the context shifts of several sessions
+        self.fused_shift_trims = 0     # trims that went through them
         self._batch = None
         self._shadow_pool = None
         if len(self.agents) < 2:
@@ -95,8 +104,16 @@ class RealtimeAgentBatch:
             self.agents[i]._settle_shadow()
         plans = [None] * len(self.agents)
         if self._batch is not None:
+            sink = [] if self.batch_shift_trims else None
             for i in live:
-                plans[i] = self.agents[i]._replay_plan(chunks[i])
+                a = self.agents[i]
+                a._shift_sink = sink                # the trim check of the plan records its context shift instead of issuing it
+                try:
+                    plans[i] = a._replay_plan(chunks[i])
+                finally:
+                    a._shift_sink = None
+            if sink:
+                self._flush_shift_trims(sink)       # before any LM call of the tick
         groups, _ = self._partition(plans)
         fused = {i for g in groups for i in g}
         for g in groups:
@@ -111,6 +128,18 @@ class RealtimeAgentBatch:
             self.fused_ticks += 1
             self.fused_frames += len(fused)
         return outs
+
+    def _flush_shift_trims(self, due: list) -> None:
+        """The context shifts (llm, p0, p1) the planning loop recorded: one kv_remove_many for two or more of them when every LM object
+        offers it, else every session's own kv_remove, in the order they fell due."""
+        llms = [m for m, _, _ in due]
+        if len(due) >= 2 and all(hasattr(m, "kv_remove_many") for m in llms) and len({id(m) for m in llms}) == len(llms):
+            llms[0].kv_remove_many(llms, [(p0, p1) for _, p0, p1 in due])
+            self.fused_shift_calls += 1
+            self.fused_shift_trims += len(due)
+            return
+        for m, p0, p1 in due:
+            m.kv_remove(p0, p1)
 
     def _advance_shadows(self, fused: List[int]) -> None:
         """The end of a tick for the fused members: every shadow cache is planned as RealtimeAgent._advance_shadow plans it; the tiles
