@@ -60,13 +60,24 @@ typedef struct rca_lm rca_lm_t;
                         writes for most tensors.  A block whose 8 d is not finite in fp16 is refused at load (RCA_ERR_ARG, with the tensor's name) */
 #define RCA_Q4_1 8   /* GGUF block_q4_1: fp16 d, fp16 m, 16 bytes of nibbles (20 bytes); value = d q + m.  What llama-quantize Q4_0 gives some
                         ffn_down tensors when an importance matrix is supplied */
+/* IQ4_NL / IQ4_XS likewise carry three numberings: the tensor dtypes RCA_IQ4_NL = 9 and RCA_IQ4_XS = 10 (next free dtypes),
+   rca_lm_config_t::decode_weights = 7 for IQ4_NL (next free load-time conversion; there is no load-time IQ4_XS) and the ids 8 / 9 that
+   rca_lm_weight_format reports (the library's format ids: 0 bf16, 1 q8_0, 2 f16, 3 q4_k, 4 q6_k, 5 q5_k, 6 q4_0, 7 q4_1, 8 iq4_nl,
+   9 iq4_xs).  Both types index the 16-entry int8 table kvalues_iq4nl = { -127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38,
+   53, 69, 89, 113 } (restated from the published ggml definitions; ggml is not part of this tree: parity with llama-quantize's own
+   bits is not pinned). */
+#define RCA_IQ4_NL 9  /* GGUF block_iq4_nl as stored in the file: per 32 values fp16 d then 16 bytes of nibbles (18 bytes; Q4_0's nibble order);
+                         value = d kv[q]; numel = values.  A block whose d is not finite is refused at load (RCA_ERR_ARG, with the tensor's name) */
+#define RCA_IQ4_XS 10 /* GGUF block_iq4_xs: per 256 values fp16 d, uint16 scales_h, 4 bytes scales_l, 128 bytes of nibbles (136 bytes).  Sub-block
+                         ib = 0..7 of 32 values has the 6-bit scale ls = ((scales_l[ib / 2] >> 4 (ib % 2)) & 15) | (((scales_h >> 2 ib) & 3) << 4)
+                         and value = d (ls - 32) kv[q], nibbles of qs[16 ib ..] in Q4_0's order.  The bulk of a llama-quantize IQ4_XS file */
 
 /* A named host tensor handed to a create() call (weights). */
 typedef struct {
     const char* name;
     const void* data;  /* host pointer */
     int64_t numel;
-    int32_t dtype;     /* RCA_F32, RCA_BF16, RCA_F16, RCA_Q8_0, RCA_Q4_K, RCA_Q5_K, RCA_Q6_K, RCA_Q4_0 or RCA_Q4_1 (the last six: LM matrices and embedding table only) */
+    int32_t dtype;     /* RCA_F32, RCA_BF16, RCA_F16, RCA_Q8_0, RCA_Q4_K, RCA_Q5_K, RCA_Q6_K, RCA_Q4_0, RCA_Q4_1, RCA_IQ4_NL or RCA_IQ4_XS (the last eight: LM matrices and embedding table only) */
 } rca_tensor_t;
 
 const char* rca_last_error(void);
@@ -342,10 +353,14 @@ typedef struct {
                                  Q5_K blocks (31 steps per sub-block instead of 15; 5.6 bits per weight streamed); 5 / 6 = quantise to GGUF Q4_0 /
                                  Q4_1 blocks by ggml's reference rule restated from the published algorithm (Q4_0: d = max / -8 with max the value of
                                  largest magnitude, q = min(15, (int)(x / d + 8.5)); Q4_1: d = (max - min) / 15, q = min(15, (int)((x - min) / d + 0.5));
-                                 5.0 bits per weight streamed; ggml is not part of this tree: parity with llama-quantize's own bits is not pinned).
+                                 5.0 bits per weight streamed; ggml is not part of this tree: parity with llama-quantize's own bits is not pinned);
+                                 7 = quantise to GGUF IQ4_NL blocks by this build's plain rule, which is NOT llama-quantize's result (that is an
+                                 iterative weighted search): per 32 values max = the value of largest magnitude (the first on ties),
+                                 d = fp16(max / -127), every value to the index whose d kv[i] is nearest (ties to the lower index), a block
+                                 whose d is 0 to index 8 (5.0 bits per weight streamed).
                                  Tensors that arrive quantised stay as
                                  they are.  The embedding table is gathered, not streamed, and keeps full precision: f32 rows for RCA_F32 /
-                                 RCA_F16 / RCA_Q8_0 / RCA_Q4_K / RCA_Q5_K / RCA_Q6_K / RCA_Q4_0 / RCA_Q4_1 sources, bf16 rows for RCA_BF16. */
+                                 RCA_F16 / RCA_Q8_0 / RCA_Q4_K / RCA_Q5_K / RCA_Q6_K / RCA_Q4_0 / RCA_Q4_1 / RCA_IQ4_NL / RCA_IQ4_XS sources, bf16 rows for RCA_BF16. */
 } rca_lm_config_t;
 
 typedef struct {
@@ -735,14 +750,14 @@ int rca_lm_set_mfma_prefill(rca_lm_t* h, int32_t enable);
 /* Tests only: the route rca_lm_eval takes for an eval of more than LM_PREFILL_MIN tokens with the
  * current settings: 0 = 8-token GEMV chunks, 1 = 32-token tiles, 2 = 128-token tiles. */
 int rca_lm_prefill_route(const rca_lm_t* h, int32_t* route);
-/* the format the projection matrices are kept and streamed in (0 bf16, 1 q8_0, 2 f16, 3 q4_k, 5 q5_k, 6 q4_0, 7 q4_1) and, optionally, the weight bytes one decode
+/* the format the projection matrices are kept and streamed in (0 bf16, 1 q8_0, 2 f16, 3 q4_k, 5 q5_k, 6 q4_0, 7 q4_1, 8 iq4_nl, 9 iq4_xs) and, optionally, the weight bytes one decode
  * step reads (llama.cpp prints the same two facts at load: file type and model size) */
 int rca_lm_weight_format(const rca_lm_t* h, int32_t* fmt, int64_t* bytes_per_step);
 /* decode steps merge the attention splits inside the attention launch (1, default: the workgroup that publishes its partial last
  * merges them; bit-identical to the separate merge launch) or in a launch of its own (0); tests compare the two */
 int rca_lm_set_attn_fuse(rca_lm_t* h, int32_t enable);
 /* activation format of the decode GEMVs over quantised matrices: 0 = f32 (default), 1 = q8_1 blocks + integer dot products
- * (llama.cpp's GPU mat-vec class).  RCA_ERR_ARG for another value or when no projection matrix of the handle is q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1.
+ * (llama.cpp's GPU mat-vec class).  RCA_ERR_ARG for another value or when no projection matrix of the handle is q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 / IQ4_NL / IQ4_XS.
  * Drops captured graphs when the value changes.  Per handle; rca_lm_create_shared copies the parent's value.
  * q8_1: a row of K activations is cut into blocks of 32 consecutive values; per block d = amax / 127, inv = d != 0 ? 1 / d : 0 (IEEE
  * division), q_j = roundf(x_j * inv) (ties away from zero) as int8, scale used d_x = (float)(fp16 rne of d); an all-zero block is
@@ -751,6 +766,7 @@ int rca_lm_set_attn_fuse(rca_lm_t* h, int32_t enable);
  *   q8_0: (d_w d_x) sum q_w q_x      Q6_K: d_x (s_w0 sum_first16 q_w q_x + s_w1 sum_second16 q_w q_x)
  *   Q4_K: d_x ((d sc_b) sum q_w q_x - (dmin m_b) sum q_x)           Q5_K: the same with the 5-bit q_w
  *   Q4_0 / Q4_1: d_x (s sum q_w q_x - t sum q_x) with (s, t) = (d, 8 d) / (d, -m) as formed at load
+ *   IQ4_NL / IQ4_XS: (s d_x) sum kv[q_w] q_x with s = d / d (ls - 32) as formed at load (|sum| <= 8 * 127 * 127 per chunk)
  * with exact integer sums (v_dot4c_i32_i8 over a lane's 8 values); scaling and the sums across chunks, lanes and waves are f32 in
  * the order of the f32 path.  Matrices kept in bf16 / f16 and the MFMA prefill tiles keep f32 activations; the exact prefill
  * route (rca_lm_set_mfma_prefill(0), evals of up to 8 tokens) is made of decode GEMV passes and follows the mode. */

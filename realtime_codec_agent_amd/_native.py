@@ -24,7 +24,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"
                "-Wno-unused-result", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
 MAX_STAGES = 8
-RCA_F32, RCA_BF16, RCA_Q8_0, RCA_F16, RCA_Q4_K, RCA_Q6_K, RCA_Q5_K, RCA_Q4_0, RCA_Q4_1 = 0, 1, 2, 3, 4, 5, 6, 7, 8
+RCA_F32, RCA_BF16, RCA_Q8_0, RCA_F16, RCA_Q4_K, RCA_Q6_K, RCA_Q5_K, RCA_Q4_0, RCA_Q4_1, RCA_IQ4_NL, RCA_IQ4_XS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
 
 class RcaError(RuntimeError):
@@ -157,6 +157,54 @@ class Q41Blocks(Q40Blocks):
         m = blk[:, 2:4].copy().view(np.float16).astype(np.float32)
         q = self._nibbles(blk[:, 4:20]).astype(np.float32)
         return ((q * d).astype(np.float32) + m).astype(np.float32).reshape(self.shape)
+
+
+KVALUES_IQ4NL = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.int8)   # ggml's kvalues_iq4nl
+
+
+class IQ4NLBlocks(Q40Blocks):
+    """A GGUF IQ4_NL tensor kept as its raw 18-byte blocks (fp16 d, 16 bytes of nibbles per 32 values, nibble order as in Q4_0; a nibble
+    indexes the 16-entry int8 table KVALUES_IQ4NL): raw uint8 [rows, cols / 32 * 18], logical shape (rows, cols)."""
+
+    BLOCK_BYTES = 18
+
+    def dequantize(self) -> np.ndarray:
+        """llama.cpp's dequantize_row_iq4_nl: d * kv[q] in f32 (exact)."""
+        blk = self.raw.reshape(-1, 18)
+        d = blk[:, 0:2].copy().view(np.float16).astype(np.float32)
+        kv = KVALUES_IQ4NL[self._nibbles(blk[:, 2:18])].astype(np.float32)
+        return (d * kv).astype(np.float32).reshape(self.shape)
+
+
+class IQ4XSBlocks(Q40Blocks):
+    """A GGUF IQ4_XS tensor kept as its raw 136-byte super-blocks (fp16 d, uint16 scales_h, 4 bytes scales_l, 128 bytes of nibbles per 256
+    values; sub-block ib of 32 values has the 6-bit scale ls = ((scales_l[ib / 2] >> 4 (ib % 2)) & 15) | (((scales_h >> 2 ib) & 3) << 4) and
+    the nibbles of qs[16 ib : 16 ib + 16] in Q4_0's order): raw uint8 [rows, cols / 256 * 136], logical shape (rows, cols).  The bulk of a
+    llama-quantize IQ4_XS file."""
+
+    BLOCK_BYTES = 136
+
+    def __init__(self, raw: np.ndarray, shape):
+        self.shape = tuple(int(x) for x in shape)
+        self.raw = raw.reshape(self.shape[0], self.shape[1] // 256 * self.BLOCK_BYTES)
+        self.dtype = np.dtype(np.uint8)
+
+    def scales(self) -> np.ndarray:
+        """ls, the 6-bit scale codes: int32 [blocks, 8]"""
+        blk = self.raw.reshape(-1, 136)
+        sh = blk[:, 2:4].copy().view(np.uint16).astype(np.int32)                        # [blocks, 1]
+        ib = np.arange(8)
+        lo = (blk[:, 4:8].astype(np.int32)[:, ib // 2] >> (4 * (ib % 2))) & 15
+        return lo | (((sh >> (2 * ib)) & 3) << 4)
+
+    def dequantize(self) -> np.ndarray:
+        """llama.cpp's dequantize_row_iq4_xs: (d * (ls - 32)) * kv[q] in f32 (both products exact)."""
+        blk = self.raw.reshape(-1, 136)
+        d = blk[:, 0:2].copy().view(np.float16).astype(np.float32)                      # [blocks, 1]
+        dl = (d * (self.scales() - 32).astype(np.float32)).astype(np.float32)           # [blocks, 8]
+        qs = blk[:, 8:136].reshape(-1, 8, 16)
+        kv = KVALUES_IQ4NL[np.concatenate([qs & 0xF, qs >> 4], axis=2)].astype(np.float32)   # [blocks, 8, 32]
+        return (dl[:, :, None] * kv).astype(np.float32).reshape(self.shape)
 
 
 class Q6KBlocks:
@@ -497,11 +545,12 @@ def make_tensors(weights: Dict[str, np.ndarray]) -> Tuple[C.Array, list]:
     keep = []
     arr = (Tensor * len(weights))()
     for i, (name, a) in enumerate(weights.items()):
-        if isinstance(a, (Q8Blocks, Q4KBlocks, Q5KBlocks, Q6KBlocks, Q40Blocks)):      # GGUF q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 blocks, handed over as they sit in the file
+        if isinstance(a, (Q8Blocks, Q4KBlocks, Q5KBlocks, Q6KBlocks, Q40Blocks)):      # GGUF q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 / IQ4_NL / IQ4_XS (subclasses of Q40Blocks) blocks, handed over as they sit in the file
             raw = np.ascontiguousarray(a.raw)
             nb = name.encode()
             keep += [raw, nb]
-            arr[i] = Tensor(nb, raw.ctypes.data, int(np.prod(a.shape)), {Q8Blocks: RCA_Q8_0, Q4KBlocks: RCA_Q4_K, Q5KBlocks: RCA_Q5_K, Q6KBlocks: RCA_Q6_K, Q40Blocks: RCA_Q4_0, Q41Blocks: RCA_Q4_1}[type(a)])
+            arr[i] = Tensor(nb, raw.ctypes.data, int(np.prod(a.shape)), {Q8Blocks: RCA_Q8_0, Q4KBlocks: RCA_Q4_K, Q5KBlocks: RCA_Q5_K, Q6KBlocks: RCA_Q6_K, Q40Blocks: RCA_Q4_0, Q41Blocks: RCA_Q4_1,
+                                                                          IQ4NLBlocks: RCA_IQ4_NL, IQ4XSBlocks: RCA_IQ4_XS}[type(a)])
             continue
         if a.dtype == np.uint16:
             dt = RCA_BF16

@@ -343,6 +343,39 @@ __device__ __forceinline__ float ubyte_to_f32(unsigned w) {
     else asm("v_cvt_f32_ubyte3_e32 %0, %1" : "=v"(f) : "v"(w));
     return f;
 }
+// kvalues_iq4nl, the table of the IQ4_NL / IQ4_XS types (restated from the published ggml definition): signed bytes, four per dword
+#define IQ4_KV0 0xBFAD9881u   // -127 -104  -83  -65
+#define IQ4_KV1 0xF6EADDCFu   //  -49  -35  -22  -10
+#define IQ4_KV2 0x26190D01u   //    1   13   25   38
+#define IQ4_KV3 0x71594535u   //   53   69   89  113
+__host__ __device__ __forceinline__ int iq4_kv(unsigned q) {
+    const unsigned long long t = (q & 8u) ? (((unsigned long long)IQ4_KV3 << 32) | IQ4_KV2) : (((unsigned long long)IQ4_KV1 << 32) | IQ4_KV0);   // constants: no memory
+    return (int)(signed char)((t >> (8 * (q & 7u))) & 0xffu);
+}
+// Four table look-ups without touching memory: byte b of the result is kv[(w >> (8 b + SH)) & 15].  The table stays in four scalar
+// dwords; v_perm_b32 picks a byte of a dword pair by a selector byte 0..7, so one permute reads the table's low half and one its
+// high half with the indices' low three bits, and a third picks, byte by byte, which of the two holds: its selector is b + 4 * bit 3
+// of index b, a bit-field insert of (w >> (SH + 1)) into the constant 0x03020100 under the mask 0x04040404.  Six vector
+// instructions per four weights (and, two permutes, shift, insert, permute; SH = 4: one more shift).
+template <int SH>
+__device__ __forceinline__ unsigned iq4_map4(unsigned w) {
+    const unsigned i3 = (SH ? w >> SH : w) & 0x07070707u;
+    const unsigned lo = __builtin_amdgcn_perm(IQ4_KV1, IQ4_KV0, i3);
+    const unsigned hi = __builtin_amdgcn_perm(IQ4_KV3, IQ4_KV2, i3);
+    const unsigned w1 = w >> (SH + 1);
+    const unsigned sel = (w1 & 0x04040404u) | (0x03020100u & ~0x04040404u);   // v_bfi_b32
+    return __builtin_amdgcn_perm(hi, lo, sel);
+}
+// (float) of SIGNED byte B of a dword as one instruction (the SDWA form of v_cvt_f32_i32 with a sign-extended byte operand)
+template <int B>
+__device__ __forceinline__ float sbyte_to_f32(unsigned w) {
+    float f;
+    if constexpr (B == 0) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0" : "=v"(f) : "v"(w));
+    else if constexpr (B == 1) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1" : "=v"(f) : "v"(w));
+    else if constexpr (B == 2) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2" : "=v"(f) : "v"(w));
+    else asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3" : "=v"(f) : "v"(w));
+    return f;
+}
 struct GemvQ8 {          // the packed (quantised) forms: q8_0, and Q4_K (dd != nullptr)
     const u32x4* qs;      // q8_0: [N / 2][K / 8] 16-byte units.  Q4_K: [N / 4][K / 8] units = 8 nibbles x 4 slots (q4k_* below)
     const unsigned* sc;   // q8_0: [ceil(N / 16)][K / 32][8]: (fp16, fp16) per pair and 32-element block, pairs in groups of 8 -- the scales a
@@ -367,6 +400,12 @@ __host__ __device__ __forceinline__ int q5k_hbit(int slot_in_quad, int j) { retu
 // load (all exact in fp16).  Streamed as the Q4_K nibble layout plus ONE factor dword (fp16 s | fp16 t << 16) per slot and 32-value
 // block, in q8.sc, [ceil(N / 16)][K / 32][16] (q4k_scm_index over dwords): 5.0 bits per weight for both types, no (sc, m) / (d, dmin)
 // unpack and no d * sc / dmin * m products in the body.  Arithmetic as for Q4_K: val += s p - t sum(x).
+// IQ4_NL / IQ4_XS (GGUF block_iq4_nl / block_iq4_xs): 4-bit INDICES into the 16-entry int8 table kvalues_iq4nl, with one fp16 step per 32
+// (IQ4_NL: value = d kv[q]) or an fp16 step per 256 and a 6-bit scale per 32 (IQ4_XS: value = d (ls - 32) kv[q]).  Both are ONE device
+// form, s kv[q], with the f32 factor s = d resp. d (ls - 32) formed once at load (11 x 6 bits: exact; s kv[q] is 17 x 7 bits: exact
+// too, so every weight has one f32 value).  Streamed as the Q4_K nibble layout plus ONE f32 factor per slot and 32-value block, in
+// q8.sc, [ceil(N / 16)][K / 32][16] -- the arrays and sizes of the Q4_0 form: 5.0 bits per weight for both types.  The body maps four
+// nibbles at a time to their table bytes with byte permutes (iq4_map4) and has no minimum term: val += s sum kv[q_j] x_j.
 __host__ __device__ __forceinline__ long q4k_scm_index(long slot, long kblock, long nkb) { return ((slot >> 4) * nkb + kblock) * 16 + (slot & 15); }
 __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, long nkb) { return ((pair >> 3) * nkb + kblock) * 8 + (pair & 7); }
 // The format a projection matrix is kept in (ONE copy per matrix; the decode GEMV streams it, the prefill tiles de-quantise it while
@@ -381,14 +420,16 @@ __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, lon
 #define WF_Q5K 5    // GGUF Q5_K: the Q4_K layout (low nibbles, sc, dd) + one plane of high bits, q5k_hbit() above (5.6 bits per weight streamed)
 #define WF_Q40 6    // GGUF Q4_0: the Q4_K nibble layout + one (fp16 s | fp16 t << 16) dword per slot and 32 values, s = d, t = 8 d (5.0 bits per weight streamed)
 #define WF_Q41 7    // GGUF Q4_1: the same layout with t = -m.  The kernels know one form (template value WF_Q40); the id only tells the two apart in reports
+#define WF_IQ4 8    // GGUF IQ4_NL: the Q4_K nibble layout (table indices) + one f32 factor s = d per slot and 32 values (5.0 bits per weight streamed)
+#define WF_IQ4XS 9  // GGUF IQ4_XS: the same layout with s = d (ls - 32).  The kernels know one form (template value WF_IQ4); the id only tells the two apart in reports
 #define WF_Q6K 4    // GGUF Q6_K re-encoded losslessly: int8 values (the 6-bit value - 32) in the q8_0 pair layout + one f32 scale d * sc per
                     // row and group of 16 ((s_a, s_b) per pair, pairs in groups of 8: [ceil(N / 16)][K / 16][8][2] floats); 10 bits per
                     // weight streamed (the file holds 6.6); d * sc * q is exact in f32, so the values are llama.cpp's dequantize_row_q6_K's
-constexpr bool wf_packed(int fmt) { return fmt == WF_Q8 || fmt == WF_Q4K || fmt == WF_Q6K || fmt == WF_Q5K || fmt == WF_Q40 || fmt == WF_Q41; }
+constexpr bool wf_packed(int fmt) { return fmt == WF_Q8 || fmt == WF_Q4K || fmt == WF_Q6K || fmt == WF_Q5K || fmt == WF_Q40 || fmt == WF_Q41 || fmt == WF_IQ4 || fmt == WF_IQ4XS; }
 // minimum waves per SIMD asked of the register allocator.  The q8_0 bodies otherwise spread over 200+ registers (one wave per
 // SIMD) although their live set is ~130: a streaming kernel wants the occupancy.
 constexpr int gemv_min_waves(int Q, int R, int NIT, int M = 2) {
-    if (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K && Q != WF_Q40) return 1;
+    if (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K && Q != WF_Q40 && Q != WF_IQ4) return 1;
     if (M == 4 && NIT == 4) return 1;   // four rows x four chunks: 128 x values per lane beside the batch (group steps, wide FFN)
     return R * NIT >= 16 ? 2 : 4;
 }
@@ -433,7 +474,7 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
     const int tid = threadIdx.x;
     const int nchunk = K >> 3;
     constexpr bool QA = ACT == 1;
-    static_assert(!QA || Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K || Q == WF_Q40, "q8_1 activations go with the packed weight formats");
+    static_assert(!QA || Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K || Q == WF_Q40 || Q == WF_IQ4, "q8_1 activations go with the packed weight formats");
     const int cpw = QA ? ((((nchunk + 3) >> 2) + 3) & ~3) : (nchunk + 3) >> 2;   // chunks per wave (q8_1: whole 32-blocks)
     const int c0 = wave * cpw;
     const int cn = max(0, min(cpw, nchunk - c0));            // this wave's chunk count (<= 64 * NIT)
@@ -452,14 +493,16 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
     constexpr bool Q6 = Q == WF_Q6K;                 // the q8_0 body with another scale: f32 per group of 16 instead of fp16 per 32
     constexpr bool Q5 = Q == WF_Q5K;                 // the Q4_K body with a fifth bit per value; its plane of high bits arrives as W
     constexpr bool Q40 = Q == WF_Q40;                // Q4_0 / Q4_1: the Q4_K body with (s, t) read from one dword per slot and 32 values
-    constexpr bool Q8 = Q == WF_Q8 || Q6, Q4 = Q == WF_Q4K || Q5 || Q40;
+    constexpr bool IQ4 = Q == WF_IQ4;                // IQ4_NL / IQ4_XS: the Q4_K nibble layout holds table indices, one f32 factor per slot and 32 values, no minimum
+    constexpr bool Q8 = Q == WF_Q8 || Q6, Q4 = Q == WF_Q4K || Q5 || Q40 || IQ4;
     constexpr int NL = Q8 ? R / 2 : (Q4 ? R / 4 : R);   // 16-byte weight loads per chunk: one per row, per slot pair (q8_0 / Q6_K) or per slot quad (Q4_K)
     constexpr int H0 = NL / 2;                // the batch's registers refill in two halves: loads [0, H0) and [H0, NL)
     u32x4 wq[NL][NIT];
-    constexpr bool Q4F = Q4 && !Q40;          // the two-level factors of the K-quants
+    constexpr bool Q4F = Q4 && !Q40 && !IQ4;  // the two-level factors of the K-quants
     uint2 wscm[Q4F ? NIT : 1][Q4F ? NL : 1];  // Q4_K: (sc | m << 8) of a quad's four slots for this lane's 32-element sub-block
     u32x4 wdd[Q4 ? NIT : 1][Q4 ? NL : 1];     //       (d | dmin << 16) of the four slots for this lane's 256-element super-block;
-                                              //       Q4_0 / Q4_1: (s | t << 16) of the four slots for this lane's 32-element block
+                                              //       Q4_0 / Q4_1: (s | t << 16) of the four slots for this lane's 32-element block;
+                                              //       IQ4: the f32 factor s of the four slots for that block
     unsigned wqh[Q5 ? NL : 1][Q5 ? NIT : 1];  // Q5_K: the quad's dword of high bits for this lane's chunk
     unsigned wsc[Q8 ? NIT : 1][Q8 ? R / 2 : 1];   // q8_0: (fp16, fp16) scales of the batch's pairs for this lane's 32-element block
     unsigned wsc2[Q6 ? NIT : 1][Q6 ? R / 2 : 1];  // Q6_K: wsc / wsc2 = the f32 scales (bits) of the pair's first / second row for this lane's group of 16
@@ -476,7 +519,7 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
             for (int it = 0; it < NIT; ++it) {
                 const int c = lane + 64 * it;
                 const int cc = cbase + (c < cn ? c : 0);
-                if constexpr (Q40) {
+                if constexpr (Q40 || IQ4) {
                     wdd[it][r] = *reinterpret_cast<const u32x4*>(q8.sc + q4k_scm_index(4 * quad, cc >> 2, K >> 5));
                 } else {
                     wdd[it][r] = *reinterpret_cast<const u32x4*>(q8.dd + q4k_scm_index(4 * quad, cc >> 5, K >> 8));
@@ -639,7 +682,8 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
     // the block's fp16-rounded scale, and for Q4_K d_x * sum(q_x) of the chunk (the minimum term)
     unsigned xq[QA ? M : 1][QA ? NIT : 1][2];
     float xd[QA ? M : 1][QA ? NIT : 1];
-    float sx[Q4 ? M : 1][Q4 ? NIT : 1];   // Q4_K: sum of this lane's x values per chunk (the minimum term: - (dmin * m) * sum(x))
+    constexpr bool Q4M = Q4 && !IQ4;      // the forms with a minimum term
+    float sx[Q4M ? M : 1][Q4M ? NIT : 1];   // Q4_K: sum of this lane's x values per chunk (the minimum term: - (dmin * m) * sum(x))
     if constexpr (QA) {
 #pragma unroll
         for (int m = 0; m < M; ++m)
@@ -663,12 +707,12 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
                     xq[m][it][1] = qb[4] | (qb[5] << 8) | (qb[6] << 16) | (qb[7] << 24);
                 }
                 xd[m][it] = (float)(f16_t)d;
-                if (Q4) {
+                if (Q4M) {
                     const int s = __builtin_amdgcn_sdot4((int)xq[m][it][1], 0x01010101, __builtin_amdgcn_sdot4((int)xq[m][it][0], 0x01010101, 0, false), false);
                     sx[m][it] = xd[m][it] * (float)s;
                 }
             }
-    } else if (Q4) {
+    } else if (Q4M) {
 #pragma unroll
         for (int m = 0; m < M; ++m)
 #pragma unroll
@@ -698,6 +742,29 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const unsigned w = q8_opaque(aw[i]);
+                    if constexpr (IQ4) {   // kv bytes of nibbles 0, 2, 4, 6 / 1, 3, 5, 7; val += s sum kv[q_j] x_j, products in ascending j
+                        const unsigned klo = iq4_map4<0>(w), khi = iq4_map4<4>(w);
+                        const float s1 = __uint_as_float(dw[i]);
+                        if constexpr (QA) {
+#pragma unroll
+                            for (int m = 0; m < M; ++m) {
+                                const int p = __builtin_amdgcn_sdot4((int)khi, (int)xq[m][it][1], __builtin_amdgcn_sdot4((int)klo, (int)xq[m][it][0], 0, false), false);
+                                val[m * R + 4 * r + i] = __builtin_fmaf(s1 * xd[m][it], (float)p, val[m * R + 4 * r + i]);
+                            }
+                        } else {
+                            float fk[8];
+                            fk[0] = sbyte_to_f32<0>(klo); fk[1] = sbyte_to_f32<0>(khi); fk[2] = sbyte_to_f32<1>(klo); fk[3] = sbyte_to_f32<1>(khi);
+                            fk[4] = sbyte_to_f32<2>(klo); fk[5] = sbyte_to_f32<2>(khi); fk[6] = sbyte_to_f32<3>(klo); fk[7] = sbyte_to_f32<3>(khi);
+#pragma unroll
+                            for (int m = 0; m < M; ++m) {
+                                float pk = 0.0f;
+#pragma unroll
+                                for (int j = 0; j < 8; ++j) pk = __builtin_fmaf(fk[j], xr[m][it][j], pk);
+                                val[m * R + 4 * r + i] = __builtin_fmaf(s1, pk, val[m * R + 4 * r + i]);
+                            }
+                        }
+                        continue;
+                    }
                     unsigned lo = w & 0x0F0F0F0Fu, hi = (w >> 4) & 0x0F0F0F0Fu;   // bytes of lo = nibbles 0, 2, 4, 6; of hi = 1, 3, 5, 7
                     if constexpr (Q5) {   // bit 4 of every byte from the plane (q5k_hbit): slot i's even elements at bits 8 b + 2 i, odd at 8 b + 2 i + 1
                         const unsigned hb = wqh[r][it];
@@ -2004,6 +2071,70 @@ __device__ __forceinline__ float q40_value(unsigned st, unsigned q) {
 __global__ __launch_bounds__(256) void lm_q40_dequant_f32_kernel(const unsigned char* __restrict__ q, const unsigned* __restrict__ st, float* __restrict__ out, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = q40_value(st[i >> 5], q[i]);
 }
+// ---- IQ4_NL / IQ4_XS (18-byte block_iq4_nl = { fp16 d; qs[16] } over 32 values, 136-byte block_iq4_xs = { fp16 d; uint16 scales_h;
+// scales_l[4]; qs[128] } over 256; value j of a 32-value (sub-)block is the low nibble of its qs[j], value j + 16 the high nibble; the
+// 6-bit scale of sub-block ib is ls = ((scales_l[ib / 2] >> 4 (ib % 2)) & 15) | (((scales_h >> 2 ib) & 3) << 4)).  Plain form on the
+// device: q [N][K] one byte per 4-bit index, st [N][K / 32] the f32 factor s (bits) with value = s kv[q]: IQ4_NL s = d, IQ4_XS
+// s = d (ls - 32), exact.  A d that is not finite sets *bad and the load fails.
+template <bool XS>
+__global__ __launch_bounds__(256) void lm_iq4_unblock_kernel(const unsigned char* __restrict__ blocks, long nblocks32, unsigned char* __restrict__ q,
+                                                             unsigned* __restrict__ st, int* __restrict__ bad) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nblocks32 * 32; i += (long)gridDim.x * blockDim.x) {
+        const long blk = i >> 5;   // 32-value (sub-)block
+        const int j = (int)(i & 31);
+        const int ib = XS ? (int)(blk & 7) : 0;
+        const unsigned char* bp = XS ? blocks + (blk >> 3) * 136 : blocks + blk * 18;
+        const unsigned char byte = XS ? bp[8 + 16 * ib + (j & 15)] : bp[2 + (j & 15)];
+        q[i] = j < 16 ? (byte & 0xF) : (byte >> 4);
+        if (j == 0) {
+            const unsigned short dbits = (unsigned short)bp[0] | ((unsigned short)bp[1] << 8);
+            if ((dbits & 0x7c00u) == 0x7c00u) *bad = 1;   // inf or NaN
+            float s = (float)__builtin_bit_cast(f16_t, dbits);
+            if (XS) {
+                const unsigned sh = (unsigned)bp[2] | ((unsigned)bp[3] << 8);
+                const int ls = (int)(((unsigned)bp[4 + (ib >> 1)] >> (4 * (ib & 1))) & 15u) | (int)(((sh >> (2 * ib)) & 3u) << 4);
+                s = s * (float)(ls - 32);
+            }
+            st[blk] = __float_as_uint(s);
+        }
+    }
+}
+// The load-time IQ4_NL rule of this build (NOT llama-quantize's, which is an iterative weighted search): max = the value of largest
+// magnitude (the first on ties), d = fp16(max / -127); every value goes to the index whose d kv[i] is nearest (|v - d kv[i]| in f32,
+// ties to the lower index); a block whose d is zero (all-zero blocks among them) gets index 8 everywhere.
+__global__ __launch_bounds__(256) void lm_iq4nl_quantize_kernel(const bf16_t* __restrict__ w, int is_f16, long nblocks, unsigned char* __restrict__ q,
+                                                                unsigned* __restrict__ st, int* __restrict__ bad) {
+    for (long blk = (long)blockIdx.x * blockDim.x + threadIdx.x; blk < nblocks; blk += (long)gridDim.x * blockDim.x) {
+        float amax = 0.0f, mx = 0.0f;
+        for (int j = 0; j < 32; ++j) {
+            const float v = w16_to_f32(w[blk * 32 + j], is_f16);
+            if (amax < fabsf(v)) { amax = fabsf(v); mx = v; }
+        }
+        const f16_t dh = (f16_t)(mx / -127.0f);
+        const unsigned short dbits = __builtin_bit_cast(unsigned short, dh);
+        if ((dbits & 0x7c00u) == 0x7c00u) *bad = 1;
+        const float d = (float)dh;
+        for (int j = 0; j < 32; ++j) {
+            const float v = w16_to_f32(w[blk * 32 + j], is_f16);
+            int best = 8;
+            if (d != 0.0f) {
+                best = 0;
+                float bd = fabsf(v - d * (float)iq4_kv(0));
+                for (int i = 1; i < 16; ++i) {
+                    const float e = fabsf(v - d * (float)iq4_kv(i));
+                    if (e < bd) { bd = e; best = i; }
+                }
+            }
+            q[blk * 32 + j] = (unsigned char)best;
+        }
+        st[blk] = __float_as_uint(d);
+    }
+}
+// s kv[q] in f32: 17 x 7 bits, exact (dequantize_row_iq4_nl's / _xs's value)
+__device__ __forceinline__ float iq4_value(unsigned st, unsigned q) { return __uint_as_float(st) * (float)iq4_kv(q); }
+__global__ __launch_bounds__(256) void lm_iq4_dequant_f32_kernel(const unsigned char* __restrict__ q, const unsigned* __restrict__ st, float* __restrict__ out, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = iq4_value(st[i >> 5], q[i]);
+}
 // This build's Q4_K quantiser (oracle/q4k_ref.py::quantize_q4_k, operation for operation): per 32 values offset o = -min(0, min w)
 // and step s = (max w + o) / 15; per 256 d = max s / 63, dmin = max o / 63 (fp16); sc = round(s / d), m = round(o / dmin);
 // q = clamp(round((w + dmin m) / (d sc)), 0, 15).  llama-quantize searches for better scales; the FORMAT and its de-quantisation are GGUF's.
@@ -2172,7 +2303,7 @@ struct WMat {
     int N = 0, K = 0;
     bf16_t* w = nullptr;        // WF_BF16 / WF_F16: row-major 16-bit values
     u32x4* qs = nullptr;        // WF_Q8 / WF_Q4K (GemvQ8)
-    unsigned* sc = nullptr;     // WF_Q40 / WF_Q41: the (s | t << 16) factor dwords
+    unsigned* sc = nullptr;     // WF_Q40 / WF_Q41: the (s | t << 16) factor dwords; WF_IQ4 / WF_IQ4XS: the f32 factors s
     unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K
     unsigned* qh = nullptr;     // WF_Q5K: the plane of high bits [N / 4][K / 8]
     void release() {
@@ -2186,7 +2317,7 @@ struct WMat {
     long stream_bytes() const {   // bytes one decode pass reads of it
         const long n = (long)N * K;
         if (fmt == WF_Q5K) return n / 2 + n / 8 + n / 16 + n / 64;   // nibbles, plane, (sc, m), (d, dmin): 5.6 bits per weight
-        if (fmt == WF_Q40 || fmt == WF_Q41) return n / 2 + n / 8;    // nibbles, (s, t): 5.0 bits per weight
+        if (fmt == WF_Q40 || fmt == WF_Q41 || fmt == WF_IQ4 || fmt == WF_IQ4XS) return n / 2 + n / 8;    // nibbles, (s, t) resp. f32 s: 5.0 bits per weight
         return fmt == WF_Q8 ? n + n / 16 : (fmt == WF_Q4K ? n / 2 + n / 16 + n / 64 : (fmt == WF_Q6K ? n + n / 4 : 2 * n));
     }
 };
@@ -2479,7 +2610,7 @@ static int lm_check_cfg(const rca_lm_config_t* c) {
     if (c->ffn > LM_KSLICE * LM_MAXSPLIT) return fail(RCA_ERR_ARG, "ffn > %d unsupported", LM_KSLICE * LM_MAXSPLIT);
     if (c->ffn > LM_KSLICE && c->ffn % LM_KSLICE) return fail(RCA_ERR_ARG, "ffn above %d must be a multiple of it", LM_KSLICE);
     if (c->vocab_size < 2 || c->n_layers < 1 || c->n_ctx < 2) return fail(RCA_ERR_ARG, "bad sizes");
-    if (c->decode_weights < 0 || c->decode_weights > 6) return fail(RCA_ERR_ARG, "decode_weights %d (0 as supplied, 1 q8_0, 2 f16, 3 q4_k, 4 q5_k, 5 q4_0, 6 q4_1)", c->decode_weights);
+    if (c->decode_weights < 0 || c->decode_weights > 7) return fail(RCA_ERR_ARG, "decode_weights %d (0 as supplied, 1 q8_0, 2 f16, 3 q4_k, 4 q5_k, 5 q4_0, 6 q4_1, 7 iq4_nl)", c->decode_weights);
     return RCA_OK;
 }
 
@@ -2491,7 +2622,8 @@ struct RawMat {
     bf16_t* w16 = nullptr;      // WF_BF16 / WF_F16
     signed char* q = nullptr;   // WF_Q8: int8 [rows][cols]; WF_Q4K / WF_Q5K: one byte per 4-bit / 5-bit value (the rest as WF_Q4K)
     f16_t* d = nullptr;         // WF_Q8: fp16 [rows][cols / 32]; WF_Q4K / WF_Q5K: ushort (sc | m << 8) [rows][cols / 32]
-    unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K: (d | dmin << 16) [rows][cols / 256]; WF_Q40 / WF_Q41: (s | t << 16) [rows][cols / 32] (q as WF_Q4K, d unused)
+    unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K: (d | dmin << 16) [rows][cols / 256]; WF_Q40 / WF_Q41: (s | t << 16) [rows][cols / 32] (q as WF_Q4K, d unused);
+                                // WF_IQ4 / WF_IQ4XS: the f32 factor s (bits) [rows][cols / 32] (q: table indices, d unused)
     void release() {
         for (void* p : {(void*)w16, (void*)q, (void*)d, (void*)dd})
             if (p) (void)hipFree(p);
@@ -2500,7 +2632,7 @@ struct RawMat {
     // (array, bytes per row) of every component
     int parts(void** ptr, long* row_bytes) const {
         if (fmt == WF_Q4K || fmt == WF_Q5K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; ptr[2] = dd; row_bytes[2] = cols / 256 * 4; return 3; }
-        if (fmt == WF_Q40 || fmt == WF_Q41) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = dd; row_bytes[1] = cols / 32 * 4; return 2; }
+        if (fmt == WF_Q40 || fmt == WF_Q41 || fmt == WF_IQ4 || fmt == WF_IQ4XS) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = dd; row_bytes[1] = cols / 32 * 4; return 2; }
         if (fmt == WF_Q6K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 16; ptr[2] = dd; row_bytes[2] = cols / 256 * 2; return 3; }   // d: int8 scales, dd: fp16 d
         if (fmt == WF_Q8) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; return 2; }
         ptr[0] = w16; row_bytes[0] = cols * 2;
@@ -2515,8 +2647,8 @@ struct RawMat {
                 (rc = lm_alloc((void**)&dd, (size_t)r * (c / 256) * 4)) != RCA_OK) { release(); return rc; }
             return RCA_OK;
         }
-        if (f == WF_Q40 || f == WF_Q41) {
-            if (c % 256) return fail(RCA_ERR_ARG, "%s needs rows of a multiple of 256 values (got %ld)", f == WF_Q41 ? "Q4_1" : "Q4_0", c);
+        if (f == WF_Q40 || f == WF_Q41 || f == WF_IQ4 || f == WF_IQ4XS) {
+            if (c % 256) return fail(RCA_ERR_ARG, "%s needs rows of a multiple of 256 values (got %ld)", f == WF_IQ4 ? "IQ4_NL" : (f == WF_IQ4XS ? "IQ4_XS" : (f == WF_Q41 ? "Q4_1" : "Q4_0")), c);
             if ((rc = lm_alloc((void**)&q, (size_t)r * c)) != RCA_OK || (rc = lm_alloc((void**)&dd, (size_t)r * (c / 32) * 4)) != RCA_OK) { release(); return rc; }
             return RCA_OK;
         }
@@ -2607,6 +2739,28 @@ static int lm_upload_raw(rca_lm* h, const rca_tensor_t* ts, int nt, const std::s
         if (bad_h) { out->release(); return fail(RCA_ERR_ARG, "tensor '%s': a Q4_0 block's 8 d is not finite in fp16", name.c_str()); }
         return RCA_OK;
     }
+    if (t->dtype == RCA_IQ4_NL || t->dtype == RCA_IQ4_XS) {
+        const bool xs = t->dtype == RCA_IQ4_XS;
+        if ((rc = out->alloc(xs ? WF_IQ4XS : WF_IQ4, rows, cols)) != RCA_OK) return rc;   // rows of whole 256-value blocks
+        const long nblk = numel / 32;
+        const size_t nbytes = xs ? (size_t)(numel / 256) * 136 : (size_t)nblk * 18;
+        unsigned char* raw = nullptr;   // the blocks, then the flag "a block's d is not finite"
+        if ((rc = lm_alloc((void**)&raw, nbytes + 8)) != RCA_OK) { out->release(); return rc; }
+        int* bad = reinterpret_cast<int*>(raw + ((nbytes + 3) & ~(size_t)3));
+        int bad_h = 0;
+        hipError_t e = hipMemcpy(raw, t->data, nbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 4, h->stream);
+        if (e == hipSuccess) {
+            if (xs) lm_iq4_unblock_kernel<true><<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, out->dd, bad);
+            else lm_iq4_unblock_kernel<false><<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, out->dd, bad);
+            e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        }
+        (void)hipFree(raw);
+        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
+        if (bad_h) { out->release(); return fail(RCA_ERR_ARG, "tensor '%s': an %s block's d is not finite", name.c_str(), xs ? "IQ4_XS" : "IQ4_NL"); }
+        return RCA_OK;
+    }
     if (t->dtype == RCA_Q4_K) {
         if ((rc = out->alloc(WF_Q4K, rows, cols)) != RCA_OK) return rc;
         const long nblk = numel / 256;
@@ -2670,13 +2824,15 @@ static int lm_upload_embed(rca_lm* h, const rca_tensor_t* ts, int nt, const std:
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e));
         return RCA_OK;
     }
-    if (t->dtype == RCA_Q8_0 || t->dtype == RCA_Q4_K || t->dtype == RCA_Q6_K || t->dtype == RCA_Q5_K || t->dtype == RCA_Q4_0 || t->dtype == RCA_Q4_1) {
+    if (t->dtype == RCA_Q8_0 || t->dtype == RCA_Q4_K || t->dtype == RCA_Q6_K || t->dtype == RCA_Q5_K || t->dtype == RCA_Q4_0 || t->dtype == RCA_Q4_1 ||
+        t->dtype == RCA_IQ4_NL || t->dtype == RCA_IQ4_XS) {
         RawMat raw;
         if ((rc = lm_upload_raw(h, ts, nt, name, rows, cols, &raw)) != RCA_OK) return rc;
         if (raw.fmt == WF_Q6K) lm_q6k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>(raw.q, (const signed char*)raw.d, (const f16_t*)raw.dd, (float*)h->embed, numel);
         else if (raw.fmt == WF_Q4K || raw.fmt == WF_Q5K)   // the plain byte holds the whole value, 4 or 5 bits
             lm_q4k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, (const unsigned short*)raw.d, raw.dd, (float*)h->embed, numel);
         else if (raw.fmt == WF_Q40 || raw.fmt == WF_Q41) lm_q40_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, raw.dd, (float*)h->embed, numel);
+        else if (raw.fmt == WF_IQ4 || raw.fmt == WF_IQ4XS) lm_iq4_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, raw.dd, (float*)h->embed, numel);
         else lm_q8_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>(raw.q, raw.d, (float*)h->embed, numel);
         hipError_t e = hipStreamSynchronize(h->stream);
         raw.release();
@@ -2708,11 +2864,30 @@ static int lm_upload_f32(const rca_tensor_t* ts, int nt, const std::string& name
 }
 
 // rca_lm_config_t::decode_weights applied to one plain matrix: 1 = quantise to q8_0 the way llama-quantize does, 2 = fp16,
-// 3 / 4 = this build's Q4_K / Q5_K quantiser, 5 / 6 = ggml's reference Q4_0 / Q4_1 rule.
+// 3 / 4 = this build's Q4_K / Q5_K quantiser, 5 / 6 = ggml's reference Q4_0 / Q4_1 rule, 7 = this build's IQ4_NL rule.
 // A matrix that ARRIVED quantised stays what it is.
 static int lm_raw_convert(rca_lm* h, RawMat* m, int want) {
     if (want == 0 || wf_packed(m->fmt)) return RCA_OK;
     int rc;
+    if (want == 7) {
+        RawMat qd;
+        if ((rc = qd.alloc(WF_IQ4, m->rows, m->cols)) != RCA_OK) return rc;
+        int* bad = nullptr;
+        int bad_h = 0;
+        if ((rc = lm_alloc((void**)&bad, 4)) != RCA_OK) { qd.release(); return rc; }
+        hipError_t e = hipMemsetAsync(bad, 0, 4, h->stream);
+        if (e == hipSuccess) {
+            lm_iq4nl_quantize_kernel<<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 32, (unsigned char*)qd.q, qd.dd, bad);
+            e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        }
+        (void)hipFree(bad);
+        m->release();
+        if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "IQ4_NL quantise: %s", hipGetErrorString(e)); }
+        if (bad_h) { qd.release(); return fail(RCA_ERR_ARG, "IQ4_NL quantise: a block's d is not finite in fp16"); }
+        *m = qd;
+        return RCA_OK;
+    }
     if (want == 5 || want == 6) {
         RawMat qd;
         if ((rc = qd.alloc(want == 6 ? WF_Q41 : WF_Q40, m->rows, m->cols)) != RCA_OK) return rc;
@@ -2837,9 +3012,9 @@ static int lm_finish_mat(rca_lm* h, RawMat* raw, int qkv_pairs, WMat* out, const
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s pack of %s: %s", fn, what, hipGetErrorString(e));
         return RCA_OK;
     }
-    if (raw->fmt == WF_Q40 || raw->fmt == WF_Q41) {
+    if (raw->fmt == WF_Q40 || raw->fmt == WF_Q41 || raw->fmt == WF_IQ4 || raw->fmt == WF_IQ4XS) {   // IQ4: the same arrays, the factor dword is an f32
         const int N = out->N, K = out->K;
-        const char* fn = raw->fmt == WF_Q41 ? "Q4_1" : "Q4_0";
+        const char* fn = raw->fmt == WF_IQ4 ? "IQ4_NL" : (raw->fmt == WF_IQ4XS ? "IQ4_XS" : (raw->fmt == WF_Q41 ? "Q4_1" : "Q4_0"));
         if ((K % 256) || (N % 4) || (qkv_pairs && (N % 64))) { raw->release(); return fail(RCA_ERR_ARG, "%s weights: %s is %d x %d (K must be a multiple of 256, N of 4)", fn, what, N, K); }
         int rc;
         const long nquad = N / 4, nchunk = K / 8, g16 = (N + 15) / 16;
@@ -3144,7 +3319,7 @@ extern "C" int rca_lm_create_shared(rca_lm_t* parent, int32_t n_ctx, int32_t log
 // ------------------------------------------------------------------------- forward pass (M tokens)
 // The one place that turns a matrix's runtime format into a template argument: f(std::integral_constant<int, WF_...>{}).  A new
 // format is added here (and to WF_FORMATS) and every launcher below sees it.
-static constexpr int WF_FORMATS[] = {WF_BF16, WF_Q8, WF_F16, WF_Q4K, WF_Q6K, WF_Q5K, WF_Q40};
+static constexpr int WF_FORMATS[] = {WF_BF16, WF_Q8, WF_F16, WF_Q4K, WF_Q6K, WF_Q5K, WF_Q40, WF_IQ4};
 template <class F>
 static void wf_dispatch(int fmt, F&& f) {
     switch (fmt) {
@@ -3152,6 +3327,7 @@ static void wf_dispatch(int fmt, F&& f) {
         case WF_Q4K: return f(std::integral_constant<int, WF_Q4K>{});
         case WF_Q5K: return f(std::integral_constant<int, WF_Q5K>{});
         case WF_Q40: case WF_Q41: return f(std::integral_constant<int, WF_Q40>{});   // one form on the device: the two differ only at load
+        case WF_IQ4: case WF_IQ4XS: return f(std::integral_constant<int, WF_IQ4>{});   // likewise
         case WF_Q8: return f(std::integral_constant<int, WF_Q8>{});
         case WF_F16: return f(std::integral_constant<int, WF_F16>{});
         default: return f(std::integral_constant<int, WF_BF16>{});
@@ -3190,11 +3366,11 @@ static GemvGeom gemv_geom(int kind, int N, bool q8) {
 // projection of a wide FFN: 128 x values) ask the allocator for one wave per SIMD instead of two (gemv_min_waves).  With that every
 // format has its M = 4 instances and none of them uses scratch: profiles/r13/gemv_m4_registers.txt.
 constexpr bool gemv_built(int M, int NIT, int R, int Q) {
-    // Q5_K / Q4_0 at NIT = 4: launch_gemv_q never leaves R = 16 (four quads x four chunks = 16 loads, twice its limit), and the
+    // Q5_K / Q4_0 / IQ4 at NIT = 4: launch_gemv_q never leaves R = 16 (four quads x four chunks = 16 loads, twice its limit), and the
     // instance would not fit the register file (it spills): not built
-    if ((Q == WF_Q5K || Q == WF_Q40) && NIT == 4 && R == 16) return false;
+    if ((Q == WF_Q5K || Q == WF_Q40 || Q == WF_IQ4) && NIT == 4 && R == 16) return false;
     if (M == 4) {   // what gemv_group_r never asks for is not built
-        const bool min8 = Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40 || Q == WF_Q6K;
+        const bool min8 = Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40 || Q == WF_IQ4 || Q == WF_Q6K;
         if (min8 ? (R == 4 || (R == 16 && NIT > 1)) : R * NIT > 16) return false;
     }
     return true;
@@ -3229,9 +3405,9 @@ static void launch_gemv_q(GemvGeom g, rca_lm* h, int M, const WMat& w, const flo
                           const GemvRope& rope, hipStream_t st, const GemvGroup& grp = GemvGroup{nullptr, 0}) {
     const int nit = cdiv(cdiv(K >> 3, 4), 64);
     // 16-byte weight loads in flight per lane: at most 16 (registers); q8_0 needs one load per row PAIR
-    constexpr bool four_bit = Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40;
+    constexpr bool four_bit = Q == WF_Q4K || Q == WF_Q5K || Q == WF_Q40 || Q == WF_IQ4;
     const int lpr = (Q == WF_Q8 || Q == WF_Q6K) ? 2 : (four_bit ? 4 : 1);
-    const int max_loads = four_bit ? 8 : 16;   // Q4_K / Q5_K / Q4_0 also hold the factors of every quad in registers
+    const int max_loads = four_bit ? 8 : 16;   // Q4_K / Q5_K / Q4_0 / IQ4 also hold the factors of every quad in registers
     while (g.R > 4 && (g.R / lpr) * (nit == 3 ? 4 : nit) > max_loads) g.R >>= 1;
     if ((four_bit || Q == WF_Q6K) && g.R < 8) g.R = 8;   // a Q4_K batch is at least two quads (one per register half); Q6_K scale loads cover two pairs
     if (M == 4) g.R = gemv_group_r(g.R, nit == 3 ? 4 : nit, four_bit || Q == WF_Q6K);
@@ -4649,7 +4825,8 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
     const int q4quad = tid >> 3, q4half = tid & 1;
     const int gquad = RAGGED ? min((n0 >> 2) + q4quad, (N >> 2) - 1) : (n0 >> 2) + q4quad;
     const int q4slot = 4 * gquad + 2 * q4half;
-    constexpr bool W40 = WF == WF_Q40;                  // Q4_0 / Q4_1: the Q4_K staging with the (s | t << 16) dword of each slot and stage
+    constexpr bool WIQ = WF == WF_IQ4;                  // IQ4_NL / IQ4_XS: the same staging as Q4_0, the dword is the f32 factor s and the nibbles are table indices
+    constexpr bool W40 = WF == WF_Q40 || WIQ;           // Q4_0 / Q4_1: the Q4_K staging with the (s | t << 16) dword of each slot and stage
     constexpr bool W4 = WF == WF_Q4K || WF == WF_Q5K || W40;   // Q5_K: the Q4_K staging + the quad's dword of high bits (arrives as W)
     const unsigned* gH5 = WF == WF_Q5K ? reinterpret_cast<const unsigned*>(W) + (long)gquad * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3) : nullptr;
     const uint2* gQ4 = W4 ? reinterpret_cast<const uint2*>(q8.qs + (long)gquad * (K >> 3) + (ks >> 3) + ((tid >> 1) & 3)) + q4half : nullptr;
@@ -4723,11 +4900,21 @@ __global__ __launch_bounds__(256, 2) void lm_gemm128_kernel(const LmDevState* __
             for (int c = 0; c < 2; ++c) {
                 const unsigned scm = W40 ? 0u : (rs[ws] >> (16 * c)) & 0xffffu;
                 float wv[8];
+                if constexpr (WIQ) {   // s kv[q], exact: the table stays in scalar registers (iq4_map4), four look-ups per permute triple
+                    const unsigned klo = iq4_map4<0>(qw[c]), khi = iq4_map4<4>(qw[c]);
+                    const float s1 = __uint_as_float(ddw[c]);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    unsigned qv = (qw[c] >> (4 * j)) & 0xFu;
-                    if (WF == WF_Q5K) qv |= ((rw[ws][0].z >> q5k_hbit(2 * q4half + c, j)) & 1u) << 4;
-                    wv[j] = W40 ? q40_value(ddw[c], qv) : q4k_value(ddw[c], scm, qv);   // Q4_0 / Q4_1: s q - t
+                    for (int b = 0; b < 4; ++b) {
+                        wv[2 * b] = s1 * q8_byte_to_f32(klo, b);
+                        wv[2 * b + 1] = s1 * q8_byte_to_f32(khi, b);
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        unsigned qv = (qw[c] >> (4 * j)) & 0xFu;
+                        if (WF == WF_Q5K) qv |= ((rw[ws][0].z >> q5k_hbit(2 * q4half + c, j)) & 1u) << 4;
+                        wv[j] = W40 ? q40_value(ddw[c], qv) : q4k_value(ddw[c], scm, qv);   // Q4_0 / Q4_1: s q - t
+                    }
                 }
                 uint4 hi, lo;
                 split_w8(wv, hi, lo);
@@ -7569,6 +7756,8 @@ extern "C" int rca_lm_mask_head_rows(rca_lm_t* h, int32_t row_begin, int32_t row
         lm_q6k_zero_row_scales_kernel<<<256, 256, 0, h->stream>>>((float*)h->head.sc, h->cfg.hidden / 16, row_begin, row_end);
     if (n > 0 && (h->head.fmt == WF_Q4K || h->head.fmt == WF_Q5K))   // Q4_K / Q5_K: d = dmin = 0 makes every value of the row (0 * sc) * q - (0 * m) = 0
         lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.dd, h->cfg.hidden / 256, row_begin, row_end);
+    if (n > 0 && (h->head.fmt == WF_IQ4 || h->head.fmt == WF_IQ4XS))   // IQ4: s = 0 (the f32's zero bits) makes every value of the row 0 * kv[q] = 0
+        lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.sc, h->cfg.hidden / 32, row_begin, row_end);
     if (n > 0 && (h->head.fmt == WF_Q40 || h->head.fmt == WF_Q41))   // Q4_0 / Q4_1: s = t = 0 makes every value of the row 0 * q - 0 = 0 (the same slot-grouped index, per 32 values)
         lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.sc, h->cfg.hidden / 32, row_begin, row_end);
     if (n > 0 && (h->head.fmt == WF_BF16 || h->head.fmt == WF_F16)) lm_zero_rows_kernel<<<2048, 256, 0, h->stream>>>(h->head.w + (long)row_begin * h->cfg.hidden, n);   // zero bits
@@ -7689,7 +7878,7 @@ extern "C" int rca_lm_set_act_format(rca_lm_t* h, int32_t fmt) {
     if (!h) return fail(RCA_ERR_ARG, "null");
     if (fmt != 0 && fmt != 1) return fail(RCA_ERR_ARG, "set_act_format: %d is neither 0 (f32) nor 1 (q8_1)", fmt);
     if (fmt == 1 && !lm_has_packed_matrix(h))
-        return fail(RCA_ERR_ARG, "set_act_format: q8_1 activations need a q8_0 / Q4_K / Q6_K, Q5_K or Q4_0 / Q4_1 projection matrix, and this handle keeps all of its matrices in 16-bit floats");
+        return fail(RCA_ERR_ARG, "set_act_format: q8_1 activations need a q8_0 / Q4_K / Q6_K, Q5_K, Q4_0 / Q4_1 or IQ4_NL / IQ4_XS projection matrix, and this handle keeps all of its matrices in 16-bit floats");
     { const int src = lm_settle(h); if (src != RCA_OK) return src; }
     if (h->act_format != fmt) {
         RCA_HIP(hipSetDevice(h->device));
@@ -7859,8 +8048,8 @@ extern "C" int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_
     return RCA_OK;
 }
 
-// the format the projection matrices are kept (and streamed) in: 0 bf16, 1 q8_0, 2 f16, 3 q4_k, 5 q5_k, 6 q4_0, 7 q4_1 (4 = Q6_K, which only ever
-// appears next to Q4_K / Q5_K / Q4_0 tensors); bytes = weight bytes one decode step reads
+// the format the projection matrices are kept (and streamed) in: 0 bf16, 1 q8_0, 2 f16, 3 q4_k, 5 q5_k, 6 q4_0, 7 q4_1, 8 iq4_nl, 9 iq4_xs (4 = Q6_K,
+// which only ever appears next to Q4_K / Q5_K / Q4_0 / IQ4 tensors); bytes = weight bytes one decode step reads
 extern "C" int rca_lm_weight_format(const rca_lm_t* h, int32_t* fmt, int64_t* bytes_per_step) {
     if (!h || !fmt) return fail(RCA_ERR_ARG, "null");
     *fmt = h->layers.empty() ? h->head.fmt : h->layers[0].gu.fmt;

@@ -15,7 +15,10 @@ RCA_Q4_K) and Q6_K (210-byte super-blocks: output.weight and the attn_v / ffn_do
 RCA_Q6_K, re-encoded losslessly on the device as int8 values + one f32 scale per 16) -- and Q5_K (176-byte super-blocks, kept packed,
 RCA_Q5_K), which with Q6_K makes up a Q5_K_S / Q5_K_M file.  Of the legacy types, Q4_0 (18-byte blocks of 32 values, RCA_Q4_0: the
 bulk of a llama-quantize Q4_0 file) and Q4_1 (20-byte blocks, RCA_Q4_1: what such a file keeps some ffn_down tensors in) are kept packed
-too.  Q2_K / Q3_K and the legacy 5-bit types Q5_0 / Q5_1 stay refused.
+too.  So are the two non-linear 4-bit types, whose nibbles index the 16-entry int8 table kvalues_iq4nl: IQ4_NL (18-byte blocks of 32 values,
+RCA_IQ4_NL) and IQ4_XS (136-byte super-blocks of 256 values with a 6-bit scale per 32, RCA_IQ4_XS: the bulk of a llama-quantize IQ4_XS
+file, whose other tensors are Q5_K and Q6_K).  Q2_K / Q3_K, the legacy 5-bit types Q5_0 / Q5_1 and the IQ1 / IQ2 / IQ3 grid types stay
+refused.
 
 Two things convert_hf_to_gguf.py does to a Llama checkpoint are undone here:
   * q_proj / k_proj rows are permuted from the rotate-half layout to interleaved pairs (LlamaModel.permute);
@@ -33,8 +36,10 @@ import numpy as np
 
 GGUF_MAGIC = 0x46554747  # "GGUF"
 GGML_F32, GGML_F16, GGML_Q4_0, GGML_Q4_1, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_BF16 = 0, 1, 2, 3, 8, 12, 13, 14, 30
+GGML_IQ4_NL, GGML_IQ4_XS = 20, 23
 _TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 9: "Q8_1", 10: "Q2_K", 11: "Q3_K",
-               12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 15: "Q8_K", 30: "BF16"}
+               12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 15: "Q8_K", 16: "IQ2_XXS", 17: "IQ2_XS", 18: "IQ3_XXS", 19: "IQ1_S", 20: "IQ4_NL", 21: "IQ3_S", 22: "IQ2_S",
+               23: "IQ4_XS", 30: "BF16"}
 # metadata value types
 _U8, _I8, _U16, _I16, _U32, _I32, _F32, _BOOL, _STR, _ARR, _U64, _I64, _F64 = range(13)
 _SCALAR = {_U8: "<B", _I8: "<b", _U16: "<H", _I16: "<h", _U32: "<I", _I32: "<i", _F32: "<f", _BOOL: "<?", _U64: "<Q", _I64: "<q", _F64: "<d"}
@@ -98,6 +103,12 @@ def _dequant(raw: np.ndarray, ttype: int, numel: int) -> np.ndarray:
         from ._native import Q40Blocks, Q41Blocks
         cls = Q41Blocks if ttype == GGML_Q4_1 else Q40Blocks
         return cls(raw[: numel // 32 * cls.BLOCK_BYTES], (numel // 32, 32)).dequantize().reshape(-1)
+    if ttype == GGML_IQ4_NL:
+        from ._native import IQ4NLBlocks
+        return IQ4NLBlocks(raw[: numel // 32 * 18], (numel // 32, 32)).dequantize().reshape(-1)
+    if ttype == GGML_IQ4_XS:
+        from ._native import IQ4XSBlocks
+        return IQ4XSBlocks(raw[: numel // 256 * 136], (numel // 256, 256)).dequantize().reshape(-1)
     if ttype == GGML_Q4_K:
         from ._native import Q4KBlocks
         return Q4KBlocks(raw[: numel // 256 * 144], (numel // 256, 256)).dequantize().reshape(-1)
@@ -107,7 +118,7 @@ def _dequant(raw: np.ndarray, ttype: int, numel: int) -> np.ndarray:
     if ttype == GGML_Q6_K:
         from ._native import Q6KBlocks
         return Q6KBlocks(raw[: numel // 256 * 210], (numel // 256, 256)).dequantize().reshape(-1)
-    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K are)")
+    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS are)")
 
 
 def _nbytes(ttype: int, numel: int) -> int:
@@ -123,6 +134,14 @@ def _nbytes(ttype: int, numel: int) -> int:
         if numel % 32:
             raise GGUFError(f"{_TYPE_NAMES[ttype]} tensor whose size is not a multiple of 32")
         return numel // 32 * (20 if ttype == GGML_Q4_1 else 18)
+    if ttype == GGML_IQ4_NL:
+        if numel % 32:
+            raise GGUFError("IQ4_NL tensor whose size is not a multiple of 32")
+        return numel // 32 * 18
+    if ttype == GGML_IQ4_XS:
+        if numel % 256:
+            raise GGUFError("IQ4_XS tensor whose size is not a multiple of 256")
+        return numel // 256 * 136
     if ttype == GGML_Q4_K:
         if numel % 256:
             raise GGUFError("Q4_K tensor whose size is not a multiple of 256")
@@ -135,8 +154,8 @@ def _nbytes(ttype: int, numel: int) -> int:
         if numel % 256:
             raise GGUFError("Q6_K tensor whose size is not a multiple of 256")
         return numel // 256 * 210
-    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K are: the types "
-                    "of the reference's F16 / Q8_0 / Q4_K_M files and of Q5_K_S / Q5_K_M and Q4_0 ones)")
+    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS are: the types "
+                    "of the reference's F16 / Q8_0 / Q4_K_M files and of Q5_K_S / Q5_K_M and Q4_0 ones, and of IQ4_NL / IQ4_XS ones)")
 
 
 def read_gguf(path: str, keep_q8_0: bool = False) -> Tuple[Dict[str, Any], Dict[str, np.ndarray]]:
@@ -182,6 +201,14 @@ def read_gguf(path: str, keep_q8_0: bool = False) -> Tuple[Dict[str, Any], Dict[
             if keep_q8_0 and ttype in (GGML_Q4_0, GGML_Q4_1) and len(ne) == 2 and ne[0] % 32 == 0:
                 from ._native import Q40Blocks, Q41Blocks
                 tensors[name] = (Q41Blocks if ttype == GGML_Q4_1 else Q40Blocks)(raw, tuple(reversed(ne)))
+                continue
+            if keep_q8_0 and ttype == GGML_IQ4_NL and len(ne) == 2 and ne[0] % 32 == 0:
+                from ._native import IQ4NLBlocks
+                tensors[name] = IQ4NLBlocks(raw, tuple(reversed(ne)))
+                continue
+            if keep_q8_0 and ttype == GGML_IQ4_XS and len(ne) == 2 and ne[0] % 256 == 0:
+                from ._native import IQ4XSBlocks
+                tensors[name] = IQ4XSBlocks(raw, tuple(reversed(ne)))
                 continue
             if keep_q8_0 and ttype == GGML_Q5_K and len(ne) == 2 and ne[0] % 256 == 0:
                 from ._native import Q5KBlocks

@@ -205,8 +205,11 @@ class LlamaForAlternatingCodeChannels:
         (the bulk of the Q4_K_M file of prep_test_model.sh:31), quantised at load with this build's own min / max rule; "q5_k" = the same
         rule into GGUF Q5_K blocks (the bulk of a Q5_K_S / Q5_K_M file), 31 steps per sub-block instead of 15; "q4_0" / "q4_1" = the legacy
         4-bit GGUF blocks of 32 values, quantised at load by ggml's reference rule (the bulk of a llama-quantize Q4_0 file; the
-        importance-matrix search of llama-quantize is not part of it).
-        activation_format: what the decode GEMVs over quantised (q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1) matrices multiply the weights with.  None / "f32"
+        importance-matrix search of llama-quantize is not part of it); "iq4_nl" = GGUF IQ4_NL blocks (32 values: an fp16 step and 4-bit
+        indices into the 16-entry non-linear table kvalues_iq4nl), quantised at load by this build's plain rule -- d = fp16(max / -127)
+        with max the value of largest magnitude, every value to the nearest d * kv[i] -- which is NOT llama-quantize's result (an
+        iterative weighted search); it exists so that random: models and bf16 checkpoints run in the format.  IQ4_XS comes from files only.
+        activation_format: what the decode GEMVs over quantised (q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 / IQ4_NL / IQ4_XS) matrices multiply the weights with.  None / "f32"
         (default) = f32 activations; "q8_1" = activations quantised to 32-value int8 blocks inside the GEMV and integer dot products,
         the arithmetic class of llama.cpp's GPU mat-vec (set_activation_format).  A twin inherits its parent's.
         kv_format: what the KV cache holds.  None / "f16" (default) = fp16 rows; "q8_0" = ggml q8_0 blocks, 68 bytes per head row instead
@@ -215,8 +218,8 @@ class LlamaForAlternatingCodeChannels:
             raise ValueError(f"kv_format {kv_format!r}: None / 'f16' or 'q8_0'")
         if activation_format not in (None,) + ACTIVATION_FORMATS:
             raise ValueError(f"activation_format {activation_format!r}: None / 'f32' or 'q8_1'")
-        if weight_format not in (None, "bf16", "q8_0", "f16", "q4_k", "q5_k", "q4_0", "q4_1"):
-            raise ValueError(f"weight_format {weight_format!r}: None / 'bf16' (as supplied), 'q8_0', 'f16', 'q4_k', 'q5_k', 'q4_0' or 'q4_1'")
+        if weight_format not in (None, "bf16", "q8_0", "f16", "q4_k", "q5_k", "q4_0", "q4_1", "iq4_nl"):
+            raise ValueError(f"weight_format {weight_format!r}: None / 'bf16' (as supplied), 'q8_0', 'f16', 'q4_k', 'q5_k', 'q4_0', 'q4_1' or 'iq4_nl'")
         self._lib = N.lib()
         self.model_path = model_path
         self.verbose = verbose
@@ -258,7 +261,7 @@ class LlamaForAlternatingCodeChannels:
             n_kv_heads=config.n_kv_heads, head_dim=config.head_dim, ffn=config.ffn, n_ctx=self._n_ctx, rms_eps=config.rms_eps,
             rope_theta=config.rope_theta, rope_scaling=1 if config.rope_scaling == "llama3" else 0, rope_factor=config.rope_factor,
             rope_low_freq_factor=config.rope_low_freq_factor, rope_high_freq_factor=config.rope_high_freq_factor,
-            rope_orig_ctx=config.rope_orig_ctx, logits_all=1 if logits_all else 0, decode_weights={"q8_0": 1, "f16": 2, "q4_k": 3, "q5_k": 4, "q4_0": 5, "q4_1": 6}.get(weight_format, 0),
+            rope_orig_ctx=config.rope_orig_ctx, logits_all=1 if logits_all else 0, decode_weights={"q8_0": 1, "f16": 2, "q4_k": 3, "q5_k": 4, "q4_0": 5, "q4_1": 6, "iq4_nl": 7}.get(weight_format, 0),
         )
         self._h = C.c_void_p()
         if random_init:
@@ -366,7 +369,7 @@ class LlamaForAlternatingCodeChannels:
     def _query_format(self):
         fmt, nbytes = C.c_int32(), C.c_int64()
         N.check(self._lib.rca_lm_weight_format(self._h, C.byref(fmt), C.byref(nbytes)), "rca_lm_weight_format")
-        names = {0: "bf16", 1: "q8_0", 2: "f16", 3: "q4_k", 4: "q6_k", 5: "q5_k", 6: "q4_0", 7: "q4_1"}    # 4: a file whose gate / up tensors are Q6_K (llama-quantize Q6_K)
+        names = {0: "bf16", 1: "q8_0", 2: "f16", 3: "q4_k", 4: "q6_k", 5: "q5_k", 6: "q4_0", 7: "q4_1", 8: "iq4_nl", 9: "iq4_xs"}    # 4: a file whose gate / up tensors are Q6_K (llama-quantize Q6_K)
         if fmt.value not in names:
             raise N.RcaError(f"rca_lm_weight_format reported an unknown format id {fmt.value}")
         return names[fmt.value], int(nbytes.value)

@@ -135,7 +135,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--ids", required=True, help=".npy of int32 token ids, or a directory of them")
     ap.add_argument("--window", type=int, default=2048)
     ap.add_argument("--burn_in", type=int, default=None, help="positions discarded at the head of every window (default: window // 2)")
-    ap.add_argument("--weight_format", default=None)
+    ap.add_argument("--weight_format", default=None, help="load-time format of the scored model: bf16, q8_0, f16, q4_k, q5_k, q4_0, q4_1 or iq4_nl (default: as the file supplies it)")
     ap.add_argument("--activation_format", default=None)
     ap.add_argument("--base_weight_format", default=None)
     ap.add_argument("--kv_format", default=None, help="KV cache of the scored model: f16 (default) or q8_0")
