@@ -366,7 +366,9 @@ typedef struct {
 typedef struct {
     int32_t top_k;   /* llama.cpp semantics (llamacpp_utils.py:39-77 passes it straight through): 1..256 = that many ranked candidates on the
                         serial chain (float sums, inverse-CDF draw); <= 0 or >= vocabulary = the whole vocabulary; 257..vocabulary - 1 = a rank
-                        cut found by a radix select, then the whole-vocabulary draw (Gumbel-max).  Never clamped.  temp <= 0 is greedy */
+                        cut found by a radix select, then the whole-vocabulary draw (Gumbel-max).  Never clamped.  temp <= 0 is greedy.
+                        Tokens rank by (value descending, index ascending) on every path: equal logits -- -0.0 and +0.0 are equal -- go to
+                        the lowest index, at the rank cut, at the mass cut and in the greedy pick */
     float top_p;     /* 1.0 = off.  With top_k outside 1..256 the cut is a mass threshold over the sorted vocabulary in 2^-40 fixed point */
     float min_p;     /* 0.0 = off */
     float temp;      /* <=0: greedy */
@@ -851,6 +853,10 @@ int rca_lm_score(rca_lm_t* h, rca_lm_t* base, const int32_t* ids, int32_t n, con
  * base_logits_host may be NULL), targets [M] in [-1, V).  The handle's state is untouched. */
 int rca_lm_score_rows_tap(rca_lm_t* h, const float* logits_host, const float* base_logits_host, const int32_t* targets, int32_t M,
                           rca_score_row_t* rows_host);
+/* Tests only: logits_host [V] replaces the last logits row of the handle (RCA_ERR_STATE "no logits: call eval first" while there is
+ * none); rca_lm_sample, rca_lm_token_probs and rca_lm_get_logits then behave as after an eval that had produced this row.  Nothing
+ * else changes: the sampler's kernels can be driven with hand-made rows at their caps, ties and infinities. */
+int rca_lm_put_logits(rca_lm_t* h, const float* logits_host);
 /* synchronise the handle's stream (timing) */
 int rca_lm_sync(rca_lm_t* h);
 int rca_codec_sync(rca_codec_t* h);

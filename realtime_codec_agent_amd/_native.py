@@ -492,7 +492,7 @@ ABI_SYMBOLS = [
     "rca_lm_persist_codec_embeddings", "rca_lm_create_shared", "rca_lm_eval_async", "rca_lm_copy_kv", "rca_lm_swap_kv",
     "rca_lm_set_low_priority", "rca_lm_frame", "rca_lm_weight_format", "rca_lm_set_attn_fuse", "rca_lm_prefill_route",
     "rca_lm_set_act_format", "rca_lm_get_act_format", "rca_lm_gemv_tap", "rca_lm_kv_remove", "rca_lm_kv_read",
-    "rca_lm_kv_write", "rca_lm_attn_tap", "rca_lm_score", "rca_lm_score_rows_tap",
+    "rca_lm_kv_write", "rca_lm_attn_tap", "rca_lm_score", "rca_lm_score_rows_tap", "rca_lm_put_logits",
     "rca_lm_set_kv_format", "rca_lm_get_kv_format", "rca_lm_kv_bytes_per_position", "rca_lm_kv_read_q8",
     "rca_duplex_frame", "rca_codec_workspace_sig", "rca_codec_stream_handoff", "rca_codec_codebook_size", "rca_codec_set_mfma_mode", "rca_lm_step_probe", "rca_duplex_prepare", "rca_duplex_precapture",
     "rca_lm_group_create", "rca_lm_group_destroy", "rca_lm_group_step",

@@ -1185,12 +1185,14 @@ __device__ __forceinline__ float rca_logf(float x) {
     r = __builtin_fmaf(fe, 0.693359375f, r);
     return r;
 }
+// (value, index) as one unsigned key: larger value first, then the LOWER index.  -0.0 and +0.0 are one value (v + 0.0f turns the
+// first into the second), so a tie between them ranks by index like any other tie; the logits the caller reads keep their signs.
 __device__ __forceinline__ unsigned long long sample_key(float v, unsigned idx) {
-    unsigned u = __float_as_uint(v);
+    unsigned u = __float_as_uint(v + 0.0f);
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
 }
-// the float whose monotone image is the key's upper half (sample_key's inverse: same bits, -0.0 and NaN payloads included)
+// the float whose monotone image is the key's upper half (sample_key's inverse: same bits, NaN payloads included; a zero comes back as +0.0)
 __device__ __forceinline__ float sample_key_value(unsigned long long key) {
     const unsigned u = (unsigned)(key >> 32);
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
@@ -5915,6 +5917,18 @@ extern "C" int rca_lm_get_logits(rca_lm_t* h, float* out_host) {
     if ((rc = rca_lm_logits_dev(h, &src)) != RCA_OK) return rc;
     RCA_HIP(hipSetDevice(h->device));
     RCA_HIP(hipMemcpyAsync(out_host, src, (size_t)h->cfg.vocab_size * 4, hipMemcpyDeviceToHost, h->stream));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    return RCA_OK;
+}
+// Tests only: host-supplied values replace the last logits row, so that the sampler and rca_lm_token_probs can be driven with
+// hand-made rows (caps, ties, infinities) that no model's head produces on demand
+extern "C" int rca_lm_put_logits(rca_lm_t* h, const float* logits_host) {
+    if (!h || !logits_host) return fail(RCA_ERR_ARG, "null");
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    if (h->logits_rows < 1) return fail(RCA_ERR_STATE, "no logits: call eval first");
+    RCA_HIP(hipSetDevice(h->device));
+    RCA_HIP(hipMemcpyAsync(h->logits + (long)(h->logits_rows - 1) * h->cfg.vocab_size, logits_host, (size_t)h->cfg.vocab_size * 4,
+                           hipMemcpyHostToDevice, h->stream));
     RCA_HIP(hipStreamSynchronize(h->stream));
     return RCA_OK;
 }

@@ -439,6 +439,15 @@ class LlamaForAlternatingCodeChannels:
             self._logits_valid = True
         return self._logits_host
 
+    def _put_logits(self, row: np.ndarray) -> None:
+        """Tests only (rca_lm_put_logits): `row` [n_vocab] replaces the last logits row; sample(), token_probs() and _fetch_logits()
+        then behave as after an eval that had produced it."""
+        row = np.ascontiguousarray(row, dtype=np.float32)
+        if row.shape != (self._n_vocab,):
+            raise ValueError(f"_put_logits: the row has {self._n_vocab} logits, got {row.shape}")
+        N.check(self._lib.rca_lm_put_logits(self._h, row.ctypes.data_as(C.POINTER(C.c_float))), "rca_lm_put_logits")
+        self._logits_valid = False
+
     @property
     def _scores(self) -> np.ndarray:
         """Rows of logits of the last eval call (all of them for logits_all handles, else the last)."""
