@@ -305,6 +305,36 @@ int rca_codec_encode_tap(rca_codec_t* h, const float* pcm_host, int32_t B, int32
 int rca_codec_encode_tap_bf16(rca_codec_t* h, const float* pcm_host, int32_t B, int32_t T, int32_t layer,
                               uint16_t* hi_host, uint16_t* lo_host, int64_t numel);
 
+/* Tests only: ONE decoder layer exactly as a decode pass launches it (run_conv with run_decoder's arguments) on a host-supplied input.
+ * layer: 0 = dec.conv_in, 1..n = dec.up.{0..n-1}, n + 1 = dec.conv_out with its clamp.  x_host [B][Cin][Lin], y_host [B][Cout][Lout]
+ * (Lout = Lin * stride for the transposed layers, Lin otherwise), y_numel = B * Cout * Lout.
+ * route 0: the throughput launch of rca_codec_decode_dev (lat_mode off).  route 1: what rca_codec_decode_tail_dev launches under
+ * lat_mode, accepted only for shapes that call can produce: variant >= 1, Lin = F * (product of the strides applied before this
+ * layer) for an integer F >= 1, and B * F <= 64 (RCA_LAT_MAX_FRAMES).  Where the latency launcher declines the shape the tap falls
+ * through as the decode pass does and reports the class that ran.  The handle's current variant and mfma mode apply.
+ * The device output has 256 guard floats on each side; output and guards are filled with NaN before the launch, so an element the
+ * kernel did not write comes back NaN, and *guards_ok is 0 when a guard changed.  The input has the same margins, filled with 1e30.
+ * *kernel_class: the kernel family and tile that ran (the launch helpers record it in the handle):
+ *   1      scalar chain (conv1d_chain_kernel / convtr1d_chain_kernel)
+ *   2..5   f32 MFMA, wave tile (channels x columns) 32 x 32, 64 x 32, 32 x 64, 64 x 64
+ *   6      warp-specialised kernel (variant 2)
+ *   7      bf16 MFMA (mfma mode 1 / 3)
+ *   8      f32 MFMA, any other wave tile (the fused first encoder layer; never a decoder layer)
+ *   16+NW  LDS latency kernel with NW waves per workgroup: 17, 18 or 20
+ * RCA_ERR_ARG before any HIP call for a null pointer, a layer or route out of range, B or Lin < 1, a route-1 shape as above, more
+ * than 2^30 input or output elements, or a y_numel other than B * Cout * Lout. */
+#define RCA_KCLASS_CHAIN 1
+#define RCA_KCLASS_MFMA_32x32 2
+#define RCA_KCLASS_MFMA_64x32 3
+#define RCA_KCLASS_MFMA_32x64 4
+#define RCA_KCLASS_MFMA_64x64 5
+#define RCA_KCLASS_WS 6
+#define RCA_KCLASS_BF16 7
+#define RCA_KCLASS_MFMA_OTHER 8
+#define RCA_KCLASS_LDS 16   /* + NW */
+int rca_codec_decoder_layer_tap(rca_codec_t* h, int32_t layer, int32_t route, const float* x_host, int32_t B, int32_t Lin,
+                                float* y_host, int64_t y_numel, int32_t* kernel_class, int32_t* guards_ok);
+
 /* Kernel-variant switch (parity tests compare variants): 0 = scalar-chain kernels,
  * 1 = MFMA/LDS kernels (default when available). */
 int rca_codec_set_variant(rca_codec_t* h, int32_t variant);

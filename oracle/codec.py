@@ -61,7 +61,33 @@ def lib():
         _lib = C.CDLL(build())
         _lib.oracle_codec_encode.restype = C.c_int
         _lib.oracle_codec_decode.restype = C.c_int
+        for f in (_lib.oracle_conv1d, _lib.oracle_convtr1d):
+            # (x, B, Cin, Lin, w, bias, Cout, k, s, pre_act, slope, y)
+            f.argtypes = [_FP, C.c_int, C.c_int, C.c_int, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _FP]
+            f.restype = None
     return _lib
+
+
+def _layer(fn, x, w, bias, cout, k, s, pre, slope, lout):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    bias = np.ascontiguousarray(bias, dtype=np.float32)
+    B, cin, lin = x.shape
+    assert w.size == cin * cout * k and bias.size == cout
+    y = np.empty((B, cout, lout(lin)), np.float32)
+    fn(_fp(x), B, cin, lin, _fp(w), _fp(bias), cout, k, s, int(bool(pre)), float(slope), _fp(y))
+    return y
+
+
+def conv1d(x: np.ndarray, w: np.ndarray, bias: np.ndarray, s: int, pre: bool, slope: float) -> np.ndarray:
+    """oracle_conv1d: x [B][Cin][Lin] (Lin % s == 0), w [Cout][Cin][k] -> y [B][Cout][Lin / s], the oracle's fma order."""
+    assert x.shape[2] % s == 0
+    return _layer(lib().oracle_conv1d, x, w, bias, w.shape[0], w.shape[2], s, pre, slope, lambda lin: lin // s)
+
+
+def convtr1d(x: np.ndarray, w: np.ndarray, bias: np.ndarray, s: int, pre: bool, slope: float) -> np.ndarray:
+    """oracle_convtr1d: x [B][Cin][Lin], w [Cin][Cout][k] (k = 2 s) -> y [B][Cout][Lin * s], the oracle's fma order."""
+    return _layer(lib().oracle_convtr1d, x, w, bias, w.shape[1], w.shape[2], s, pre, slope, lambda lin: lin * s)
 
 
 def make_cfg(cfg) -> _Cfg:

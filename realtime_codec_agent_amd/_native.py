@@ -375,6 +375,12 @@ BATCH_STEP_SEL_ARGTYPES = [C.c_void_p, _I32P, C.c_int32, _I32P, C.c_int32, _I32P
 BATCH_EVAL_ARGTYPES = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, _I32P, _I32P, C.c_int32]
 # int rca_lm_kv_remove_many(hs, n_h, p0, p1) (and its staged-route-only form)
 KV_REMOVE_MANY_ARGTYPES = [C.POINTER(C.c_void_p), C.c_int32, _I32P, _I32P]
+# int rca_codec_decoder_layer_tap(h, layer, route, x_host, B, Lin, y_host, y_numel, kernel_class, guards_ok)
+DECODER_LAYER_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int64,
+                              _I32P, _I32P]
+# kernel_class of rca_codec_decoder_layer_tap (RCA_KCLASS_* in include/rca.h)
+KCLASS_CHAIN, KCLASS_MFMA_32x32, KCLASS_MFMA_64x32, KCLASS_MFMA_32x64, KCLASS_MFMA_64x64, KCLASS_WS, KCLASS_BF16, KCLASS_MFMA_OTHER = range(1, 9)
+KCLASS_LDS = 16   # + NW
 
 
 def sources() -> List[str]:
@@ -499,6 +505,7 @@ ABI_SYMBOLS = [
     "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
     "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame", "rca_lm_batch_step_sel",
     "rca_lm_batch_eval", "rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged",
+    "rca_codec_decoder_layer_tap",
 ]
 
 
@@ -527,6 +534,9 @@ def lib():
     if hasattr(_lib, "rca_lm_batch_eval"):   # (a library from before the call: build() reports the missing symbol)
         _lib.rca_lm_batch_eval.argtypes = BATCH_EVAL_ARGTYPES
         _lib.rca_lm_batch_eval.restype = C.c_int
+    if hasattr(_lib, "rca_codec_decoder_layer_tap"):
+        _lib.rca_codec_decoder_layer_tap.argtypes = DECODER_LAYER_TAP_ARGTYPES
+        _lib.rca_codec_decoder_layer_tap.restype = C.c_int
     for name in ("rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged"):
         if hasattr(_lib, name):
             getattr(_lib, name).argtypes = KV_REMOVE_MANY_ARGTYPES

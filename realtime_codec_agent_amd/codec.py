@@ -146,6 +146,23 @@ class HipCodec:
         unblock = lambda a: np.ascontiguousarray(a.transpose(0, 1, 3, 2).reshape(B, Cn, L))   # [B][C/16][L][C%16] -> [B][C][L]
         return unblock(hi), (unblock(lo) if lo is not None else None)
 
+    def decoder_layer_tap(self, layer: int, route: int, x: np.ndarray) -> Tuple[np.ndarray, int, bool]:
+        """Tests only (rca_codec_decoder_layer_tap): ONE decoder layer (0 = conv_in, 1..n = up.{0..n-1}, n + 1 = conv_out with its
+        clamp) as a decode pass (route 0) or a streaming tail call (route 1) launches it, on x [B, Cin, Lin].  Returns
+        (y [B, Cout, Lout], kernel class, guards intact); an element the kernel did not write is NaN."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        layers = self.cfg.decoder_layers()
+        if x.ndim != 3 or not 0 <= layer < len(layers) or x.shape[1] != layers[layer]["cin"]:
+            raise ValueError("x must be [B, Cin, Lin] of a decoder layer")
+        ly = layers[layer]
+        B, _, Lin = x.shape
+        y = np.empty((B, ly["cout"], Lin * ly["s"] if ly["tr"] else Lin), np.float32)
+        kclass, guards = C.c_int32(-1), C.c_int32(-1)
+        fp = C.POINTER(C.c_float)
+        N.check(self._lib.rca_codec_decoder_layer_tap(self._h, layer, route, x.ctypes.data_as(fp), B, Lin, y.ctypes.data_as(fp),
+                                                      C.c_int64(y.size), C.byref(kclass), C.byref(guards)), "rca_codec_decoder_layer_tap")
+        return y, kclass.value, bool(guards.value)
+
     # ---- device-pointer API (raw addresses; stream = hipStream_t as int, 0 = handle's own stream)
     def encode_dev(self, pcm_ptr: int, B: int, T: int, codes_ptr: int, stream: int = 0) -> None:
         N.check(self._lib.rca_codec_encode_dev(self._h, C.c_void_p(pcm_ptr), B, T, C.c_void_p(codes_ptr), C.c_void_p(stream)), "rca_codec_encode_dev")

@@ -1952,6 +1952,7 @@ __global__ __launch_bounds__(256) void transpose_df_kernel(const float* __restri
 // =============================================================================================
 struct ConvLayer {
     int cin, cout, k, s, pre, tr;
+    bool dec = false;       // a decoder layer: the f32 matrix instruction in every mfma mode (the mode is an encoder switch, rca.h)
     float* w = nullptr;     // original layout
     float* b = nullptr;
     float* bp = nullptr;    // bias padded with zeros to whole channel tiles (16-byte loads in the MFMA kernel)
@@ -2370,6 +2371,7 @@ struct rca_codec {
     int variant = 1;
     int mfma_mode = 0;          // 0: f32 matrix instruction (bit-exact, default); 1 / 3: bf16 matrix instruction, rounded / hi + lo split (opt-in)
     bool lat_mode = false;      // streaming tail: LDS-staged scalar-chain kernels (set per call)
+    int last_kclass = 0;        // RCA_KCLASS_* of the last run_conv launch (read by rca_codec_decoder_layer_tap)
     // receptive-field margins (whole frames) left of a kept frame / sample, derived from the layer geometry
     int enc_left_frames = 0, dec_left_frames = 0;
     bool window_trim = false;   // batch windows: encode only what the kept frames can see (same codes)
@@ -2638,6 +2640,7 @@ extern "C" int rca_codec_create(const rca_codec_config_t* cfg, const rca_tensor_
             return bail(rc);
     }
     if ((rc = add(h->dec, "dec.conv_out", cfg->channels[0], 1, cfg->k_in, 1, 1, 0, false)) != RCA_OK) return bail(rc);
+    for (ConvLayer& L : h->dec) L.dec = true;
 
     const int J = cfg->codebook_dim, N = cfg->codebook_size, R = cfg->codebook_raw_dim, D = cfg->latent_dim;
     if ((rc = upload(ts, nt, "quantizer.in_proj.weight", (long)J * D, &h->q_in_w)) != RCA_OK) return bail(rc);
@@ -2694,6 +2697,9 @@ extern "C" int rca_codec_sync(rca_codec_t* h) {
     return RCA_OK;
 }
 
+// RCA_KCLASS_* of the conv launch a launch helper made last on this thread; run_conv copies it into the handle
+static thread_local int g_kclass = 0;
+
 // Mixed-tile launch of a plain f32 convolution with whole chunks (the strided encoder layers): the whole rounds of resident waves keep
 // the wave tile WM x WN, the columns behind them run on finer tiles at the end of the same grid (plan and model: rca_conv_balance.h).
 // false: nothing launched -- the plan is the single-shape grid (under one round, no remainder, no modelled gain) or RCA_CONV_BALANCE=0
@@ -2742,6 +2748,8 @@ static void launch_conv_cfg(const ConvLayer& L, const float* wp, int nchunks, co
                             float slope, const FuseIn& fin, const TrInfo& tr, hipStream_t st, int act) {
     constexpr int NT = RCA_CONV_WPB * WN * 32, MT = WM * 32;
     constexpr int lds = RCA_CONV_WPB * 2 * (CIC * S * ConvLds<S>::stride(WN * 32) + 4) * 4;
+    g_kclass = BF ? RCA_KCLASS_BF16 : (WM == 1 && WN == 1) ? RCA_KCLASS_MFMA_32x32 : (WM == 2 && WN == 1) ? RCA_KCLASS_MFMA_64x32
+               : (WM == 1 && WN == 2) ? RCA_KCLASS_MFMA_32x64 : (WM == 2 && WN == 2) ? RCA_KCLASS_MFMA_64x64 : RCA_KCLASS_MFMA_OTHER;
     static_assert(lds <= 65536, "LDS budget");
     // 1-D grid: column tiles padded to a multiple of 8 (one per XCD), times the channel tiles (times the phases)
     const long col_tiles = (cdiv(Ncols, NT) + 7) / 8 * 8;
@@ -2882,6 +2890,7 @@ static void launch_conv_ws(const ConvLayer& L, const float* x, float* y, int Lin
     if (!attr_done) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr_done = true; }
     const long col_tiles = (cdiv(Ncols, 256) + 7) / 8 * 8;
     dim3 grid((unsigned)(col_tiles * cdiv(L.cout, 64)));
+    g_kclass = RCA_KCLASS_WS;
     kern<<<grid, 512, lds, st>>>(x, L.wp2, L.b, y, L.cin, Lin, L.cout, Lout, Ncols, L.nchunks2, L.pre, slope, fin);
 }
 // variant 2 (experimental, slower than variant 1 as measured in round 1): true when the warp-specialised kernel was launched
@@ -2907,6 +2916,7 @@ static void launch_conv_lds(const ConvLayer& L, const float* x, long xbs, int Lv
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, RCA_LDS_BUDGET); attr_done = true; }
     dim3 grid(cdiv(Lout, NC), cdiv(L.cout, NW), B);
+    g_kclass = RCA_KCLASS_LDS + NW;
     kern<<<grid, 64 * NW, lds, st>>>(x, xbs, Lvalid, L.w, L.b, y, L.cin, Lin, L.cout, Lout, NC, W, slope, pre, clamp_out);
 }
 template <int S, int NW>
@@ -2916,6 +2926,7 @@ static void launch_convtr_lds(const ConvLayer& L, const float* x, float* y, int 
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, RCA_LDS_BUDGET); attr_done = true; }
     dim3 grid(cdiv((long)Lin * S, NC), cdiv(L.cout, NW), B);
+    g_kclass = RCA_KCLASS_LDS + NW;
     kern<<<grid, 64 * NW, lds, st>>>(x, L.w, L.w_lat, L.b, y, L.cin, Lin, L.cout, NC, NTI, slope, L.pre);
 }
 static bool try_conv_lds(rca_codec* h, const ConvLayer& L, const float* x, long xbs, int Lvalid, float* y, int B, int Lin, int clamp_out, hipStream_t st) {
@@ -2976,8 +2987,8 @@ static int conv_view_halo(const ConvLayer& L) {
 // LeakyReLU(y) if the kernel that runs can (then *post_done = true and the consumer must be told its input is activated)
 // view > 0 (see conv_view_ok): only the last `view` output columns of every row are computed and y is stored compact,
 // [B][Cout][view].  The view's right edge is the row's, so the zero padding there is the full launch's.
-static int run_conv(rca_codec* h, const ConvLayer& L, const float* x, float* y, int B, int Lin, int clamp_out, hipStream_t st,
-                    bool in_activated = false, bool want_post = false, bool* post_done = nullptr, int view = 0) {
+static int run_conv_launch(rca_codec* h, const ConvLayer& L, const float* x, float* y, int B, int Lin, int clamp_out, hipStream_t st,
+                           bool in_activated, bool want_post, bool* post_done, int view) {
     const float slope = h->cfg.leaky_slope;
     if (post_done) *post_done = false;
     if (view > 0 && !conv_view_ok(h, L, B, Lin, view)) return fail(RCA_ERR_ARG, "internal: column view handed to a kernel without that mode");
@@ -2993,6 +3004,7 @@ static int run_conv(rca_codec* h, const ConvLayer& L, const float* x, float* y, 
     if (L.tr && h->variant >= 1 && L.wp_tr && rows32 && (double)B * L.cin * Lin < 4.0e9 && (double)B * (Lin + 1) < 2.0e9) return launch_convtr_mfma(L, x, y, B, Lin, slope, st);
     if (L.tr) {
         const long total = (long)B * L.cout * Lin * L.s;
+        g_kclass = RCA_KCLASS_CHAIN;
         convtr1d_chain_kernel<<<cdiv(total, 256), 256, 0, st>>>(x, L.w, L.b, y, B, L.cin, Lin, L.cout, L.k, L.s, L.pre, slope);
         RCA_LAUNCH_CHECK();
         return RCA_OK;
@@ -3030,18 +3042,28 @@ static int run_conv(rca_codec* h, const ConvLayer& L, const float* x, float* y, 
         if (h->variant == 2 && try_conv_ws(L, x, y, B, Lin, Lout, slope, st, nullptr)) { RCA_LAUNCH_CHECK(); return RCA_OK; }
         const int act = ((L.pre && !in_activated) ? 1 : 0) | (want_post ? 2 : 0);
         if (post_done) *post_done = want_post;
-        if (L.k == 4 && L.s == 2) return launch_conv_mfma<4, 2, 4>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, h->mfma_mode);
-        if (L.k == 8 && L.s == 4) return launch_conv_mfma<8, 4, RCA_CIC_K8>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, h->mfma_mode);
-        if (L.k == 10 && L.s == 5) return launch_conv_mfma<10, 5, 4>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, h->mfma_mode);
-        if (L.k == 16 && L.s == 8) return launch_conv_mfma<16, 8, RCA_CIC_K16>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, h->mfma_mode);
-        if (L.k == 3 && L.s == 1) return launch_conv_mfma<3, 1, RCA_CIC_K3>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, h->mfma_mode);
+        const int bf = L.dec ? 0 : h->mfma_mode;   // dec.conv_in is packed like an encoder layer; the mode must not reach it
+        if (L.k == 4 && L.s == 2) return launch_conv_mfma<4, 2, 4>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, bf);
+        if (L.k == 8 && L.s == 4) return launch_conv_mfma<8, 4, RCA_CIC_K8>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, bf);
+        if (L.k == 10 && L.s == 5) return launch_conv_mfma<10, 5, 4>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, bf);
+        if (L.k == 16 && L.s == 8) return launch_conv_mfma<16, 8, RCA_CIC_K16>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, bf);
+        if (L.k == 3 && L.s == 1) return launch_conv_mfma<3, 1, RCA_CIC_K3>(L, x, y, B, Lin, Lout, slope, st, nullptr, act, bf);
     }
     if (in_activated) return fail(RCA_ERR_ARG, "internal: activated input handed to a kernel without that mode");
     const long total = (long)B * L.cout * Lout;
     ProfScope ps(h, st, 3, cflops, cbytes);
+    g_kclass = RCA_KCLASS_CHAIN;
     conv1d_chain_kernel<<<cdiv(total, 256), 256, 0, st>>>(x, L.w, L.b, y, B, L.cin, Lin, L.cout, Lout, L.k, L.s, L.pre, slope, clamp_out);
     RCA_LAUNCH_CHECK();
     return RCA_OK;
+}
+
+static int run_conv(rca_codec* h, const ConvLayer& L, const float* x, float* y, int B, int Lin, int clamp_out, hipStream_t st,
+                    bool in_activated = false, bool want_post = false, bool* post_done = nullptr, int view = 0) {
+    g_kclass = 0;
+    const int rc = run_conv_launch(h, L, x, y, B, Lin, clamp_out, st, in_activated, want_post, post_done, view);
+    h->last_kclass = g_kclass;
+    return rc;
 }
 
 // weights of encoder layer li (>= 1) in A-fragment order, rounded to bf16 (hi) + the rounded remainder (lo)
@@ -3803,6 +3825,58 @@ extern "C" int rca_codec_decode_tail_dev(rca_codec_t* h, const int64_t* codes, i
     if (rc != RCA_OK) return rc;
     RCA_HIP(hipMemcpy2DAsync(pcm, (size_t)n_samples * 4, h->tail.as<float>() + (Tt - n_samples), (size_t)Tt * 4, (size_t)n_samples * 4, B,
                              hipMemcpyDeviceToDevice, st));
+    return RCA_OK;
+}
+
+// Tests only (see rca.h): one decoder layer through run_conv, as run_decoder calls it, on a host-supplied input; NaN-filled output
+// between guards.
+extern "C" int rca_codec_decoder_layer_tap(rca_codec_t* h, int32_t layer, int32_t route, const float* x_host, int32_t B, int32_t Lin,
+                                           float* y_host, int64_t y_numel, int32_t* kernel_class, int32_t* guards_ok) {
+    if (!h || !x_host || !y_host || !kernel_class || !guards_ok) return fail(RCA_ERR_ARG, "decoder_layer_tap: null argument");
+    const int n = h->cfg.n_stages;
+    if (layer < 0 || layer > n + 1) return fail(RCA_ERR_ARG, "decoder_layer_tap: layer %d out of range [0, %d]", layer, n + 1);
+    if (route != 0 && route != 1) return fail(RCA_ERR_ARG, "decoder_layer_tap: route %d is neither 0 nor 1", route);
+    if (B < 1 || Lin < 1) return fail(RCA_ERR_ARG, "decoder_layer_tap: bad shape (B=%d Lin=%d)", B, Lin);
+    const ConvLayer& L = h->dec[layer];
+    const bool last = layer == n + 1;
+    const long Lout = L.tr ? (long)Lin * L.s : Lin / L.s;
+    const long x_numel = (long)B * L.cin * Lin, want = (long)B * L.cout * Lout;
+    if (x_numel > (1L << 30) || want > (1L << 30)) return fail(RCA_ERR_ARG, "decoder_layer_tap: more than 2^30 elements (B=%d Lin=%d)", B, Lin);
+    if (want != y_numel) return fail(RCA_ERR_ARG, "decoder_layer_tap: y_numel %ld, expected %ld", (long)y_numel, want);
+    if (route == 1) {
+        long mult = 1;   // samples per frame at this layer's input
+        for (int i = 0; i + 1 < layer && i < n; ++i) mult *= h->cfg.strides[n - 1 - i];
+        if (h->variant < 1) return fail(RCA_ERR_ARG, "decoder_layer_tap: route 1 needs variant >= 1");
+        if (Lin % mult != 0) return fail(RCA_ERR_ARG, "decoder_layer_tap: route 1: Lin %d is no multiple of %ld samples per frame", Lin, mult);
+        if ((long)B * (Lin / mult) > RCA_LAT_MAX_FRAMES)
+            return fail(RCA_ERR_ARG, "decoder_layer_tap: route 1: %ld frames, the tail call takes this route up to %d", (long)B * (Lin / mult), RCA_LAT_MAX_FRAMES);
+    }
+    constexpr long G = 256;
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, h->stream);
+    int rc;
+    if ((rc = h->io_a.ensure((size_t)(x_numel + 2 * G) * 4)) != RCA_OK) return rc;
+    if ((rc = h->io_b.ensure((size_t)(want + 2 * G) * 4)) != RCA_OK) return rc;
+    const float big = 1e30f;
+    const unsigned nan_bits = 0x7FC00000u;
+    RCA_HIP(hipMemsetD32Async((hipDeviceptr_t)h->io_a.p, __builtin_bit_cast(int, big), (size_t)(x_numel + 2 * G), st));
+    RCA_HIP(hipMemsetD32Async((hipDeviceptr_t)h->io_b.p, (int)nan_bits, (size_t)(want + 2 * G), st));
+    float* x = h->io_a.as<float>() + G;
+    float* y = h->io_b.as<float>() + G;
+    RCA_HIP(hipMemcpyAsync(x, x_host, (size_t)x_numel * 4, hipMemcpyHostToDevice, st));
+    h->lat_mode = route == 1;
+    rc = run_conv(h, L, x, y, B, Lin, last ? 1 : 0, st);
+    h->lat_mode = false;
+    if (rc != RCA_OK) return rc;
+    unsigned guards[2 * G];
+    RCA_HIP(hipMemcpyAsync(y_host, y, (size_t)want * 4, hipMemcpyDeviceToHost, st));
+    RCA_HIP(hipMemcpyAsync(guards, y - G, (size_t)G * 4, hipMemcpyDeviceToHost, st));
+    RCA_HIP(hipMemcpyAsync(guards + G, y + want, (size_t)G * 4, hipMemcpyDeviceToHost, st));
+    RCA_HIP(hipStreamSynchronize(st));
+    int ok = 1;
+    for (long i = 0; i < 2 * G; ++i) ok &= guards[i] == nan_bits;
+    *guards_ok = ok;
+    *kernel_class = h->last_kclass;
     return RCA_OK;
 }
 

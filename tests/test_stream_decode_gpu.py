@@ -1,6 +1,7 @@
 """Streamed batch decode on the GPU (MI355X): rca_codec_decode_rows_dev against rca_codec_decode_tail_dev row by row,
 rca_codec_crossfade_join_dev against chained numpy smooth_join, whole streams against the per-chunk loop (tiny codec: the oracle;
-full codec: detokenize_audio + smooth_join on the same handle, which other tests pin to the oracle), and the CLI's two paths.
+full codec: detokenize_audio + smooth_join on the same handle; tests/test_decoder_layers_gpu.py pins the full decoder to the oracle,
+layer by layer and on the 64 x 64 tiles of the B = 257 launches here), and the CLI's two paths.
 Everything is compared bit for bit."""
 import os
 
