@@ -887,6 +887,18 @@ int rca_lm_score_rows_tap(rca_lm_t* h, const float* logits_host, const float* ba
  * none); rca_lm_sample, rca_lm_token_probs and rca_lm_get_logits then behave as after an eval that had produced this row.  Nothing
  * else changes: the sampler's kernels can be driven with hand-made rows at their caps, ties and infinities. */
 int rca_lm_put_logits(rca_lm_t* h, const float* logits_host);
+/* Quantise a host matrix [rows][K] (src_dtype RCA_F32 / RCA_BF16 / RCA_F16, K % 256 == 0) on `device` into raw GGUF blocks, byte for byte
+ * in the file layout: type RCA_Q8_0 (34 bytes per 32 values), RCA_Q4_K (144 per 256), RCA_Q5_K (176) or RCA_Q6_K (210); blocks_host takes
+ * rows * K / values * bytes, which blocks_bytes must equal.  Stand-alone: no LM handle.  rule 1 = the scale searches of ggml's published
+ * reference quantisers (make_qkx2_quants for Q4_K / Q5_K, make_qx_quants for Q6_K) as DESIGN.md "Quantising on the card" restates them
+ * (ggml is not part of this tree: parity with llama-quantize's own bits is not pinned); rule 0 = this build's min / max rules: for
+ * Q4_K / Q5_K the blocks rca_lm_config_t::decode_weights = 3 / 4 keeps, for Q6_K max |x| / 31 per group of 16.  Q8_0 has one rule
+ * (d = amax / 127, ties away from zero: what decode_weights = 1 keeps) under either value.  The source goes up in slabs of at most 64 MiB
+ * (one row at least) on a stream of the call's own; one synchronisation.  RCA_ERR_ARG with a message, before any HIP call, for a null
+ * pointer, an unknown dtype, type or rule, K % 256 != 0, a wrong blocks_bytes; after the run, naming the first such row, for a source
+ * value that is not finite and for a block whose d or dmin is not finite in fp16 (blocks_host then holds no usable result). */
+int rca_quantize_rows(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
+                      void* blocks_host, int64_t blocks_bytes);
 /* synchronise the handle's stream (timing) */
 int rca_lm_sync(rca_lm_t* h);
 int rca_codec_sync(rca_codec_t* h);

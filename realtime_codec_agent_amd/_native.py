@@ -378,6 +378,8 @@ KV_REMOVE_MANY_ARGTYPES = [C.POINTER(C.c_void_p), C.c_int32, _I32P, _I32P]
 # int rca_codec_decoder_layer_tap(h, layer, route, x_host, B, Lin, y_host, y_numel, kernel_class, guards_ok)
 DECODER_LAYER_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int64,
                               _I32P, _I32P]
+# int rca_quantize_rows(device, src_host, src_dtype, rows, K, type, rule, blocks_host, blocks_bytes)
+QUANTIZE_ROWS_ARGTYPES = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
 # kernel_class of rca_codec_decoder_layer_tap (RCA_KCLASS_* in include/rca.h)
 KCLASS_CHAIN, KCLASS_MFMA_32x32, KCLASS_MFMA_64x32, KCLASS_MFMA_32x64, KCLASS_MFMA_64x64, KCLASS_WS, KCLASS_BF16, KCLASS_MFMA_OTHER = range(1, 9)
 KCLASS_LDS = 16   # + NW
@@ -505,7 +507,7 @@ ABI_SYMBOLS = [
     "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
     "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame", "rca_lm_batch_step_sel",
     "rca_lm_batch_eval", "rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged",
-    "rca_codec_decoder_layer_tap",
+    "rca_codec_decoder_layer_tap", "rca_quantize_rows",
 ]
 
 
@@ -537,6 +539,9 @@ def lib():
     if hasattr(_lib, "rca_codec_decoder_layer_tap"):
         _lib.rca_codec_decoder_layer_tap.argtypes = DECODER_LAYER_TAP_ARGTYPES
         _lib.rca_codec_decoder_layer_tap.restype = C.c_int
+    if hasattr(_lib, "rca_quantize_rows"):
+        _lib.rca_quantize_rows.argtypes = QUANTIZE_ROWS_ARGTYPES
+        _lib.rca_quantize_rows.restype = C.c_int
     for name in ("rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged"):
         if hasattr(_lib, name):
             getattr(_lib, name).argtypes = KV_REMOVE_MANY_ARGTYPES

@@ -8379,3 +8379,85 @@ extern "C" int rca_lm_score_rows_tap(rca_lm_t* h, const float* logits_host, cons
     if (e != hipSuccess) return fail(RCA_ERR_HIP, "score_rows_tap: %s", hipGetErrorString(e));
     return RCA_OK;
 }
+
+// ------------------------------------------------------------------------- quantising rows to GGUF blocks (rca_quantize_rows)
+// One lane per super-block of 256 values (Q8_0: per block of 32): the lane runs the whole rule of rca_quant_rows.h over its block, so
+// every sum has the one order the numpy restatement has and no step depends on another lane.  Not a serving path: a 1B model is 8 M
+// super-blocks, enough lanes to fill the chip without splitting a block.  A block that holds a non-finite value, or whose d is not
+// finite in fp16, lowers bad[0] / bad[1] to its row (vector atomicMin); the host refuses the call after its one synchronisation.
+#include "rca_quant_rows.h"
+template <int TYPE, typename T>
+__global__ __launch_bounds__(128) void lm_quant_rows_kernel(const T* __restrict__ src, long nblocks, long blocks_per_row, long row0, int rule,
+                                                            unsigned char* __restrict__ out, int* __restrict__ bad) {
+    constexpr int NV = TYPE == RCA_Q8_0 ? 32 : 256;
+    constexpr int BS = TYPE == RCA_Q8_0 ? 34 : (TYPE == RCA_Q4_K ? 144 : (TYPE == RCA_Q5_K ? 176 : 210));
+    for (long blk = (long)blockIdx.x * blockDim.x + threadIdx.x; blk < nblocks; blk += (long)gridDim.x * blockDim.x) {
+        int status;
+        if (TYPE == RCA_Q4_K) status = rca_quant::quantize_block_qk<15>(src + blk * NV, rule, reinterpret_cast<unsigned*>(out + blk * BS));
+        else if (TYPE == RCA_Q5_K) status = rca_quant::quantize_block_qk<31>(src + blk * NV, rule, reinterpret_cast<unsigned*>(out + blk * BS));
+        else if (TYPE == RCA_Q6_K) status = rca_quant::quantize_block_q6k(src + blk * NV, rule, reinterpret_cast<unsigned short*>(out + blk * BS));
+        else status = rca_quant::quantize_block_q8_0(src + blk * NV, reinterpret_cast<unsigned short*>(out + blk * BS));
+        if (status) {
+            const int row = (int)min((long)INT_MAX - 1, row0 + blk / blocks_per_row);
+            if (status & rca_quant::QS_BAD_INPUT) atomicMin(&bad[0], row);
+            if (status & rca_quant::QS_BAD_D) atomicMin(&bad[1], row);
+        }
+    }
+}
+template <typename T>
+static void lm_launch_quant_rows(int type, const void* src, long nblocks, long blocks_per_row, long row0, int rule, unsigned char* out, int* bad, hipStream_t st) {
+    const unsigned grid = (unsigned)std::min<long>((nblocks + 127) / 128, 1 << 20);
+    const T* s = (const T*)src;
+    if (type == RCA_Q4_K) lm_quant_rows_kernel<RCA_Q4_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad);
+    else if (type == RCA_Q5_K) lm_quant_rows_kernel<RCA_Q5_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad);
+    else if (type == RCA_Q6_K) lm_quant_rows_kernel<RCA_Q6_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad);
+    else lm_quant_rows_kernel<RCA_Q8_0, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad);
+}
+
+#define LM_QUANT_SLAB_BYTES (64l << 20)   // source bytes uploaded per slab (at least one row)
+extern "C" int rca_quantize_rows(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
+                                 void* blocks_host, int64_t blocks_bytes) {
+    if (!src_host || !blocks_host) return fail(RCA_ERR_ARG, "quantize_rows: null pointer");
+    if (src_dtype != RCA_F32 && src_dtype != RCA_BF16 && src_dtype != RCA_F16) return fail(RCA_ERR_ARG, "quantize_rows: source dtype %d (RCA_F32, RCA_BF16 or RCA_F16)", src_dtype);
+    if (type != RCA_Q8_0 && type != RCA_Q4_K && type != RCA_Q5_K && type != RCA_Q6_K) return fail(RCA_ERR_ARG, "quantize_rows: unknown type %d (RCA_Q8_0, RCA_Q4_K, RCA_Q5_K or RCA_Q6_K)", type);
+    if (rule != 0 && rule != 1) return fail(RCA_ERR_ARG, "quantize_rows: unknown rule %d (0 min / max, 1 search)", rule);
+    if (rows < 1 || K < 1 || rows > (1l << 40) / K) return fail(RCA_ERR_ARG, "quantize_rows: %ld rows of %ld values", (long)rows, (long)K);
+    if (K % 256) return fail(RCA_ERR_ARG, "quantize_rows: K = %ld is not a multiple of 256", (long)K);
+    const long nv = type == RCA_Q8_0 ? 32 : 256, bs = type == RCA_Q8_0 ? 34 : (type == RCA_Q4_K ? 144 : (type == RCA_Q5_K ? 176 : 210));
+    const long bpr = K / nv, row_out = bpr * bs, esz = src_dtype == RCA_F32 ? 4 : 2, row_in = K * esz;
+    if (blocks_bytes != rows * row_out) return fail(RCA_ERR_ARG, "quantize_rows: blocks_bytes = %ld, %ld rows of %ld values take %ld", (long)blocks_bytes, (long)rows, (long)K, rows * row_out);
+    RCA_HIP(hipSetDevice(device));
+    const long slab_rows = std::min<long>(rows, std::max<long>(1, LM_QUANT_SLAB_BYTES / row_in));
+    hipStream_t st = nullptr;
+    void* src_d = nullptr;
+    unsigned char* out_d = nullptr;
+    int* bad_d = nullptr;
+    int bad_h[2] = {INT_MAX, INT_MAX};
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(&src_d, (size_t)(slab_rows * row_in));
+    if (e == hipSuccess) e = hipMalloc((void**)&out_d, (size_t)(slab_rows * row_out));
+    if (e == hipSuccess) e = hipMalloc((void**)&bad_d, 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(bad_d, bad_h, 8, hipMemcpyHostToDevice, st);
+    for (long r0 = 0; e == hipSuccess && r0 < rows; r0 += slab_rows) {   // stream order makes the one pair of slab buffers safe to reuse
+        const long nr = std::min(slab_rows, rows - r0);
+        e = hipMemcpyAsync(src_d, (const char*)src_host + r0 * row_in, (size_t)(nr * row_in), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) break;
+        if (src_dtype == RCA_F32) lm_launch_quant_rows<float>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, st);
+        else if (src_dtype == RCA_BF16) lm_launch_quant_rows<rca_quant::bf16_src>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, st);
+        else lm_launch_quant_rows<rca_quant::f16_src>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, st);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)blocks_host + r0 * row_out, out_d, (size_t)(nr * row_out), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(bad_h, bad_d, 8, hipMemcpyDeviceToHost, st);
+    if (st) {
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = es;
+    }
+    for (void* p : {src_d, (void*)out_d, (void*)bad_d})
+        if (p) (void)hipFree(p);
+    if (st) (void)hipStreamDestroy(st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "quantize_rows: %s", hipGetErrorString(e));
+    if (bad_h[0] != INT_MAX) return fail(RCA_ERR_ARG, "quantize_rows: row %d holds a value that is not finite", bad_h[0]);
+    if (bad_h[1] != INT_MAX) return fail(RCA_ERR_ARG, "quantize_rows: row %d: a block's d or dmin is not finite in fp16", bad_h[1]);
+    return RCA_OK;
+}
