@@ -852,6 +852,22 @@ int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const float* x_hos
  * nsp_launch or out_rows, or positions past n_ctx, are refused before anything is touched. */
 int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_t nsp_launch, const float* q_host, int32_t M, float* out_host,
                     int32_t out_rows);
+/* Tests only: ONE projection of a 128-token-tile pass exactly as the layer sequence, rca_lm_score and the batch head launch it (the same
+ * launcher picks the k-slice form, the grids and the epilogue), on host-supplied activations.  Refused (RCA_ERR_ARG) on a handle whose
+ * rca_lm_prefill_route is not 2.  xh_host / xl_host [M][K] are the bf16 hi / lo planes themselves (K = hidden; n_heads*64 for kind 1;
+ * ffn for kind 3).  kind 0 QKV (both segments where the layer keeps V apart; y = the q rows after RoPE [out_rows][n_heads*64]; kv_host,
+ * if not NULL, receives the M new K rows then the M new V rows of `layer`'s fp16 cache, raw; refused on a q8_0 cache), 1 O, 2 gate/up
+ * (y = the hi + lo planes of silu(g)*u as f32 [out_rows][ffn]), 3 down, 4 head (layer and rows ignored; M <= 128 rows that are rows
+ * row_base .. of a pass of row_base + M tokens, row_base a multiple of 128; y [out_rows][V] followed by the 128 values behind the
+ * block's last row, out_rows <= 128).  For kinds 1 and 3 the residual rows are zeroed first, so y is the product alone.  rows is the
+ * pass's launch geometry (M <= rows <= 1024: ceil(rows / 128) token blocks); input rows M .. of those blocks are bf16 NaN.  Output rows
+ * M .. out_rows-1 (M <= out_rows <= 1024) are filled with NaN before the launch and come back NaN unless a kernel wrote them.  seq_min:
+ * the workgroup threshold that picks the k-slice form for this call, -1 = the process value (RCA_LM_SEQ_MIN_WGS).  form, if not NULL,
+ * receives the form that ran: grid.y, slices a workgroup walks, slices the epilogue launch adds (0: none, the GEMM's own epilogue), its
+ * group size.  Positions (kind 0) are n_tokens .. n_tokens+M-1; n_tokens is left as it was; the handle's activation buffers are
+ * overwritten.  A bad layer, kind, M, rows, out_rows or row_base, or positions past n_ctx, are refused before anything is touched. */
+int rca_lm_gemm128_tap(rca_lm_t* h, int32_t layer, int32_t kind, const uint16_t* xh_host, const uint16_t* xl_host, int32_t M, int32_t rows,
+                       int32_t row_base, int32_t seq_min, float* y_host, int32_t out_rows, uint16_t* kv_host, int32_t* form);
 /* One scored position (rca_lm_score): what llama-perplexity and its --kl-divergence mode reduce a row of logits to, reduced on the
  * device so that the logits never leave it.  With P = softmax(logits) of the scored handle and P_base of the base handle:
  * lse = log sum_j exp(logit_j), max_logit / argmax = the largest logit and its LOWEST index, logprob = logit[target] - lse,

@@ -380,6 +380,9 @@ DECODER_LAYER_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_fl
                               _I32P, _I32P]
 # int rca_quantize_rows(device, src_host, src_dtype, rows, K, type, rule, blocks_host, blocks_bytes)
 QUANTIZE_ROWS_ARGTYPES = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+# int rca_lm_gemm128_tap(h, layer, kind, xh_host, xl_host, M, rows, row_base, seq_min, y_host, out_rows, kv_host, form)
+GEMM128_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                        C.c_void_p, C.c_void_p]
 # kernel_class of rca_codec_decoder_layer_tap (RCA_KCLASS_* in include/rca.h)
 KCLASS_CHAIN, KCLASS_MFMA_32x32, KCLASS_MFMA_64x32, KCLASS_MFMA_32x64, KCLASS_MFMA_64x64, KCLASS_WS, KCLASS_BF16, KCLASS_MFMA_OTHER = range(1, 9)
 KCLASS_LDS = 16   # + NW
@@ -507,7 +510,7 @@ ABI_SYMBOLS = [
     "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
     "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame", "rca_lm_batch_step_sel",
     "rca_lm_batch_eval", "rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged",
-    "rca_codec_decoder_layer_tap", "rca_quantize_rows",
+    "rca_codec_decoder_layer_tap", "rca_quantize_rows", "rca_lm_gemm128_tap",
 ]
 
 
@@ -542,6 +545,9 @@ def lib():
     if hasattr(_lib, "rca_quantize_rows"):
         _lib.rca_quantize_rows.argtypes = QUANTIZE_ROWS_ARGTYPES
         _lib.rca_quantize_rows.restype = C.c_int
+    if hasattr(_lib, "rca_lm_gemm128_tap"):
+        _lib.rca_lm_gemm128_tap.argtypes = GEMM128_TAP_ARGTYPES
+        _lib.rca_lm_gemm128_tap.restype = C.c_int
     for name in ("rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged"):
         if hasattr(_lib, name):
             getattr(_lib, name).argtypes = KV_REMOVE_MANY_ARGTYPES

@@ -5290,19 +5290,21 @@ struct LmTilePass {
     int tbz;                   // token blocks of the pass: the GEMMs' grid.z, and what their k-split form is chosen for
     const LmGroupRow* qrows;   // null: the QKV epilogue is GEMM_EPI_ROPE into h's own cache (lm_rope_target, n_ctx bound); else
                                // GEMM_EPI_ROPE_ROWS, position, cache and bound per row from this table
+    int seq_min;               // workgroup threshold of g128_form: g128_seq_min() for every pass (rca_lm_gemm128_tap: the test's own)
 };
 // One projection of such a pass: the GEMM and, where its k slices went through HBM, the epilogue that sums them.  A projection whose
 // token blocks alone put `seq_min` workgroups on the chip is run with every workgroup walking the k slices itself (same sums in the
 // same order, no partial sums through HBM, no epilogue launch); RCA_LM_SEQ_MIN_WGS overrides the threshold (0 = never) for A/B runs.
 template <int EPI>
-static void lm_launch_proj128(const LmTilePass& p, const WMat& w, hipStream_t st, const bf16_t* xh, const bf16_t* xl, int N, int K, float* y, int ldy,
+static G128Form lm_launch_proj128(const LmTilePass& p, const WMat& w, hipStream_t st, const bf16_t* xh, const bf16_t* xl, int N, int K, float* y, int ldy,
                               bf16_t* oh, bf16_t* ol, const GemvRope& rope = norope, const GemvGroup& grp = nogroup) {
     const int ns = g128_splits(N, K);
-    const G128Form f = g128_form(N, ns, p.tbz, g128_seq_min());
+    const G128Form f = g128_form(N, ns, p.tbz, p.seq_min);
     launch_gemm128<EPI>(p.h, w, dim3(N / 128, f.grid_y, p.tbz), st, xh, xl, N, K, K / ns, y, ldy, oh, ol, rope, f.nseq, p.stt, grp);
     if (f.ep_nsplit)   // (the SwiGLU epilogue has no y and is handed ldy 0, its GEMM the width of the planes)
         lm_gemm128_epilogue_kernel<EPI><<<dim3(N / 64, cdiv(p.rows, 32)), 256, 0, st>>>(p.stt, p.h->gpart, f.ep_nsplit, f.ep_grp, N, y, EPI == GEMM_EPI_SWIGLU ? 0 : ldy,
                                                                                          oh, ol, rope, grp);
+    return f;   // (the form that ran: rca_lm_gemm128_tap reports it)
 }
 // The layers of a pass on the 128-token tiles, behind the caller's embedding launch and in front of its heads: every route that runs
 // these tiles -- a handle's own pass, a pass of rca_lm_batch_eval, the batch step / frame / selection / duplex pass -- runs this one
@@ -5350,7 +5352,7 @@ static void lm_launch_logits128(rca_lm* h, const LmDevState* stt, const bf16_t* 
 // exist); what is per session -- the QKV epilogue's position and cache, the q8_0 quantiser, attention -- takes it from the pass's tables.
 static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch, const LmEvalTables* bt = nullptr) {
     const rca_lm_config_t& c = h->cfg;
-    const LmTilePass p{h, h->stt, M, (int)cdiv(M, 128), bt ? bt->rows : nullptr};
+    const LmTilePass p{h, h->stt, M, (int)cdiv(M, 128), bt ? bt->rows : nullptr, g128_seq_min()};
     lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, h->x, c.hidden, c.vocab_size);
     if (bt)
         lm_enqueue_layers128(p, st, [&](int l) {
@@ -6771,7 +6773,7 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
     float* x = ws->x;
     lm_embed_kernel<<<MT, 256, 0, st>>>(b->stt, ws->embed, ws->embed_f32, x, H, V);
     // one token block: the k-split forms are what an rca_lm_eval_async pass of up to 128 tokens uses, so a row's sums are that pass's
-    lm_enqueue_layers128(LmTilePass{ws, b->stt, MT, 1, vw.rows}, st, [&](int l) {
+    lm_enqueue_layers128(LmTilePass{ws, b->stt, MT, 1, vw.rows, g128_seq_min()}, st, [&](int l) {
         if (q8kv)   // every member's new rows, ring -> int8 planes, in one launch
             lm_kv_quant_kernel<true><<<dim3(cdiv(4 * c.n_kv_heads, 8), n, NM), 256, 0, st>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, c.n_kv_heads, 0, 0, 0, 3, tab, l);
         lm_launch_attn_split(c, agm, q8kv, st, nullptr, ws->qkv, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, tab, l);
@@ -8059,6 +8061,121 @@ extern "C" int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_
         auto widen = [](uint16_t b) { const uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; };
         for (size_t i = 0; i < n_out; ++i) out_host[i] = widen(hb[i]) + widen(hb[n_out + i]);
     }
+    return RCA_OK;
+}
+
+// tests only: ONE projection of a 128-token-tile pass, launched by the very calls lm_enqueue_layers128 / rca_lm_score / the batch head make
+// for it (lm_launch_proj128<EPI>, lm_launch_logits128), on host-supplied bf16 hi / lo planes
+extern "C" int rca_lm_gemm128_tap(rca_lm_t* h, int32_t layer, int32_t kind, const uint16_t* xh_host, const uint16_t* xl_host, int32_t M, int32_t rows,
+                                  int32_t row_base, int32_t seq_min, float* y_host, int32_t out_rows, uint16_t* kv_host, int32_t* form) {
+    if (!h || !xh_host || !xl_host || !y_host) return fail(RCA_ERR_ARG, "null");
+    const rca_lm_config_t& c = h->cfg;
+    const int H = c.hidden, QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim, F = c.ffn, V = c.vocab_size;
+    if (lm_prefill_route(h) != LM_ROUTE_TILE128)
+        return fail(RCA_ERR_ARG, "gemm128_tap: the handle does not take the 128-token tiles (rca_lm_prefill_route %d, the call needs 2)", lm_prefill_route(h));
+    if (kind < 0 || kind > 4) return fail(RCA_ERR_ARG, "gemm128_tap: kind %d outside [0, 4]", kind);
+    if (kind != 4 && (layer < 0 || layer >= c.n_layers)) return fail(RCA_ERR_ARG, "gemm128_tap: layer %d outside [0, %d)", layer, c.n_layers);
+    const bool head = kind == 4;
+    if (head) rows = 128;   // the head takes one token block: rows row_base .. row_base + 127 of a pass of row_base + M tokens
+    if (M < 1 || M > (head ? 128 : LM_MAXM)) return fail(RCA_ERR_ARG, "gemm128_tap: M = %d, kind %d takes 1 .. %d rows", M, kind, head ? 128 : LM_MAXM);
+    if (rows < M || rows > LM_MAXM) return fail(RCA_ERR_ARG, "gemm128_tap: rows %d outside [M = %d, %d]", rows, M, LM_MAXM);
+    if (out_rows < M || out_rows > (head ? 128 : LM_MAXM)) return fail(RCA_ERR_ARG, "gemm128_tap: out_rows %d outside [M = %d, %d]", out_rows, M, head ? 128 : LM_MAXM);
+    if (row_base < 0 || row_base % 128 || row_base + 128 > LM_MAXM || (!head && row_base))
+        return fail(RCA_ERR_ARG, "gemm128_tap: row_base %d (a multiple of 128 below %d; 0 for every kind but the head)", row_base, LM_MAXM);
+    if (kind == 0 && lm_kv_q8(h)) return fail(RCA_ERR_ARG, "gemm128_tap: kind 0 writes an fp16 cache; this handle's is q8_0");
+    if (kind == 0 && h->n_tokens + M > c.n_ctx)
+        return fail(RCA_ERR_ARG, "gemm128_tap: positions %d .. %d are outside the context of %d", h->n_tokens, h->n_tokens + M - 1, c.n_ctx);
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    RCA_HIP(hipStreamSynchronize(st));
+    const int tbz = (int)cdiv(rows, 128), in_rows = 128 * tbz;
+    const int in_w[5] = {H, AO, H, F, H}, out_w[5] = {AO, H, F, H, V};
+    const int K = in_w[kind], OW = out_w[kind];
+    const std::vector<int32_t> ids((size_t)row_base + M, 0);
+    int rc;
+    if ((rc = lm_push_state(h, ids.data(), row_base + M, st)) != RCA_OK) return rc;   // m = the rows that exist: the GEMMs' row mask
+    // the planes the projection reads: kind 3 takes the SwiGLU planes in hbuf, the others the split buffers; rows M .. 128 tbz - 1 are bf16 NaN
+    bf16_t* hh = reinterpret_cast<bf16_t*>(h->hbuf);
+    bf16_t* hl = hh + (long)LM_MAXM * F;
+    bf16_t* ih = (kind == 3 ? hh : h->xh) + (long)row_base * K;
+    bf16_t* il = (kind == 3 ? hl : h->xl) + (long)row_base * K;
+    RCA_HIP(hipMemsetAsync(ih, 0xFF, (size_t)in_rows * K * 2, st));
+    RCA_HIP(hipMemsetAsync(il, 0xFF, (size_t)in_rows * K * 2, st));
+    RCA_HIP(hipMemcpyAsync(ih, xh_host, (size_t)M * K * 2, hipMemcpyHostToDevice, st));
+    RCA_HIP(hipMemcpyAsync(il, xl_host, (size_t)M * K * 2, hipMemcpyHostToDevice, st));
+    // NaN sentinel (all bits set) in the output rows a caller may look at, zeros in the residual rows that exist
+    float* blk = nullptr;
+    const size_t head_n = (size_t)128 * V + 128;   // one row tile behind the block: nothing may be written past column V of the last row
+    if (kind == 0) {
+        RCA_HIP(hipMemsetAsync(h->qkv, 0xFF, (size_t)out_rows * QKV * 4, st));
+    } else if (kind == 1 || kind == 3) {
+        RCA_HIP(hipMemsetAsync(h->x, 0xFF, (size_t)out_rows * H * 4, st));
+        RCA_HIP(hipMemsetAsync(h->x, 0, (size_t)M * H * 4, st));
+    } else if (kind == 2) {
+        RCA_HIP(hipMemsetAsync(hh, 0xFF, (size_t)out_rows * F * 2, st));
+        RCA_HIP(hipMemsetAsync(hl, 0xFF, (size_t)out_rows * F * 2, st));
+    } else {
+        if ((rc = lm_alloc((void**)&blk, head_n * 4)) != RCA_OK) return rc;
+        if (hipMemsetAsync(blk, 0xFF, head_n * 4, st) != hipSuccess) { (void)hipFree(blk); return fail(RCA_ERR_HIP, "gemm128_tap: memset"); }
+    }
+    const LmTilePass p{h, h->stt, rows, tbz, nullptr, seq_min < 0 ? g128_seq_min() : seq_min};
+    G128Form f{1, 1, 0, 1};
+    if (kind == 0) {
+        const LmLayer& L = h->layers[layer];
+        GemvRope rope{h->cos_t, h->sin_t, nullptr, nullptr, c.n_heads, c.n_kv_heads, c.n_ctx, 0};
+        lm_rope_target(h, layer, rope);
+        for (int seg = 0; seg < (L.split_v ? 2 : 1); ++seg) {   // as lm_enqueue_layers128 runs them; the form reported is the first segment's
+            const WMat& w = seg ? L.vseg : L.qkv;
+            rope.row_base = seg ? L.qkv.N : 0;
+            const G128Form fs = lm_launch_proj128<GEMM_EPI_ROPE>(p, w, st, h->xh, h->xl, w.N, H, h->qkv, QKV, nullptr, nullptr, rope, nogroup);
+            if (!seg) f = fs;
+        }
+    } else if (kind == 1) {
+        f = lm_launch_proj128<GEMM_EPI_RESID>(p, h->layers[layer].o, st, h->xh, h->xl, H, AO, h->x, H, nullptr, nullptr);
+    } else if (kind == 2) {
+        f = lm_launch_proj128<GEMM_EPI_SWIGLU>(p, h->layers[layer].gu, st, h->xh, h->xl, 2 * F, H, nullptr, F, hh, hl);
+    } else if (kind == 3) {
+        f = lm_launch_proj128<GEMM_EPI_RESID>(p, h->layers[layer].down, st, hh, hl, H, F, h->x, H, nullptr, nullptr);
+    } else {
+        lm_launch_logits128(h, h->stt, ih, il, row_base, blk, st);
+    }
+    hipError_t e = hipGetLastError();
+    const size_t n_out = (size_t)out_rows * OW;
+    std::vector<uint16_t> hb;
+    if (kind == 0) {
+        if (e == hipSuccess) e = hipMemcpy2DAsync(y_host, (size_t)AO * 4, h->qkv, (size_t)QKV * 4, (size_t)AO * 4, out_rows, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && kv_host) {
+            const size_t n = (size_t)M * c.n_kv_heads * 64;
+            const long off = (long)layer * h->kv_layer_stride + (long)h->n_tokens * c.n_kv_heads * 64;
+            e = hipMemcpyAsync(kv_host, h->kc + off, n * 2, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(kv_host + n, h->vc + off, n * 2, hipMemcpyDeviceToHost, st);
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(h->qkv, 0, (size_t)out_rows * QKV * 4, st);
+    } else if (kind == 1 || kind == 3) {
+        if (e == hipSuccess) e = hipMemcpyAsync(y_host, h->x, n_out * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemsetAsync(h->x, 0, n_out * 4, st);
+    } else if (kind == 2) {
+        hb.resize(2 * n_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), hh, n_out * 2, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(hb.data() + n_out, hl, n_out * 2, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemsetAsync(hh, 0, n_out * 2, st);
+        if (e == hipSuccess) e = hipMemsetAsync(hl, 0, n_out * 2, st);
+    } else {   // out_rows rows of the block, then the 128 values behind its last row
+        if (e == hipSuccess) e = hipMemcpyAsync(y_host, blk, n_out * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(y_host + n_out, blk + (size_t)128 * V, 128 * 4, hipMemcpyDeviceToHost, st);
+    }
+    // later passes read the planes in blocks of 128 rows: leave no NaN behind in them
+    if (e == hipSuccess) e = hipMemsetAsync(ih, 0, (size_t)in_rows * K * 2, st);
+    if (e == hipSuccess) e = hipMemsetAsync(il, 0, (size_t)in_rows * K * 2, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (blk) (void)hipFree(blk);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "gemm128_tap: %s", hipGetErrorString(e));
+    if (kind == 2) {
+        auto widen = [](uint16_t b) { const uint32_t u = (uint32_t)b << 16; float v; memcpy(&v, &u, 4); return v; };
+        for (size_t i = 0; i < n_out; ++i) y_host[i] = widen(hb[i]) + widen(hb[n_out + i]);
+    }
+    if (form) { form[0] = f.grid_y; form[1] = f.nseq; form[2] = f.ep_nsplit; form[3] = f.ep_grp; }
     return RCA_OK;
 }
 

@@ -811,6 +811,35 @@ class LlamaForAlternatingCodeChannels:
                                           out.ctypes.data_as(C.POINTER(C.c_float)), out_rows), "rca_lm_attn_tap")
         return out
 
+    def gemm128_tap(self, layer: int, kind: int, xh: np.ndarray, xl: np.ndarray, rows: Optional[int] = None, row_base: int = 0,
+                    seq_min: int = -1, out_rows: Optional[int] = None, want_kv: bool = False, M: Optional[int] = None):
+        """Tests only (rca_lm_gemm128_tap): one projection of a 128-token-tile pass on the bf16 hi / lo planes xh, xl (uint16 [M, K]);
+        kind 0 QKV, 1 O, 2 gate/up, 3 down, 4 head (M <= 128 rows that are rows row_base .. of a pass of row_base + M tokens).  rows: the
+        pass's launch geometry (ceil(rows / 128) token blocks, default M); seq_min: the workgroup threshold that picks the k-slice form, -1 =
+        the process value.  Returns (y, form): y float32 [out_rows, N] whose rows >= M hold the NaN the device rows were filled with
+        before the launch, form = (grid_y, nseq, ep_nsplit, ep_grp).  kind 4 returns (y, form, tail): the 128 values behind the last row
+        of the device block [128, V], NaN unless a kernel wrote past column V.  With want_kv (kind 0) also the new K and V cache rows
+        [M, n_kv_heads * 64] as float16: (y, form, k, v).  M (refusal tests): the row count handed to the library, default xh's."""
+        c = self.config
+        xh, xl = (np.ascontiguousarray(a, dtype=np.uint16) for a in (xh, xl))
+        widths = {0: (c.hidden, c.n_heads * 64), 1: (c.n_heads * 64, c.hidden), 2: (c.hidden, c.ffn), 3: (c.ffn, c.hidden), 4: (c.hidden, c.vocab_size)}
+        K, W = widths.get(kind, widths[1])
+        if xh.ndim != 2 or xh.shape != xl.shape or (kind in widths and xh.shape[1] != K):
+            raise ValueError(f"gemm128_tap: kind {kind} takes two planes of rows of {K} values, got {xh.shape} and {xl.shape}")
+        M = xh.shape[0] if M is None else int(M)
+        rows = M if rows is None else int(rows)
+        out_rows = M if out_rows is None else int(out_rows)
+        pad = 128 if kind == 4 else 0
+        y = np.full(max(out_rows, 1) * W + pad, np.nan, np.float32)
+        kv = np.empty((2, max(M, 1), c.n_kv_heads * 64), np.float16) if (want_kv and kind == 0) else None
+        form = (C.c_int32 * 4)()
+        N.check(self._lib.rca_lm_gemm128_tap(self._h, int(layer), int(kind), xh.ctypes.data, xl.ctypes.data, M, rows, int(row_base), int(seq_min),
+                                             y.ctypes.data, out_rows, kv.ctypes.data if kv is not None else None, form), "rca_lm_gemm128_tap")
+        if kind == 4:
+            return y[:out_rows * W].reshape(out_rows, W), tuple(form), y[out_rows * W:]
+        y = y.reshape(out_rows, W)
+        return (y, tuple(form), kv[0], kv[1]) if kv is not None else (y, tuple(form))
+
     def mask_head_rows(self, row_begin: int, row_end: int) -> None:
         """Zero lm_head rows (random-init models: keep sampling on codec tokens like a trained model in audio mode)."""
         N.check(self._lib.rca_lm_mask_head_rows(self._h, int(row_begin), int(row_end)), "rca_lm_mask_head_rows")
