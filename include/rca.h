@@ -915,6 +915,26 @@ int rca_lm_put_logits(rca_lm_t* h, const float* logits_host);
  * value that is not finite and for a block whose d or dmin is not finite in fp16 (blocks_host then holds no usable result). */
 int rca_quantize_rows(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
                       void* blocks_host, int64_t blocks_bytes);
+/* rca_quantize_rows under importance weights: col_weights [K] (or NULL), one non-negative finite f32 per input COLUMN, the same for every
+ * row -- an importance matrix's in_sum2 / count.  NULL gives rca_quantize_rows' bytes.  With weights, rule must be
+ * 1, and Q4_K / Q5_K / Q6_K follow ggml's published quantize_row_q{4,5,6}_K_impl with quant_weights as DESIGN.md "Weighted K-quant
+ * search" restates them (tests/quant_weighted_ref.py is the definition; parity with llama-quantize's own bits is not pinned): the
+ * sub-block search under w = qw sqrt(sigma2 + x^2) on a finer grid, d and dmin from a weighted search over the eight scales / minima,
+ * Q6_K's group search under w = qw.  A group of 32 (Q6_K: 16) columns whose weights are all 0 takes 1.0 for them.  Uniform weights do
+ * NOT reproduce the unweighted bytes (the rules' parameters differ).  Q8_0 ignores the weights.  The block of a row that starts at
+ * column c reads col_weights + c; the weights go up once per call.  RCA_ERR_ARG before any HIP call, beside rca_quantize_rows' own
+ * refusals: weights with rule 0; a weight that is negative or not finite, naming its column. */
+int rca_quantize_rows_w(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
+                        const float* col_weights, void* blocks_host, int64_t blocks_bytes);
+/* Tests only: the column sums an importance matrix is made of (what llama-imatrix collects: per input column of a projection, the sum
+ * over the tokens of the squared activation), by the kernel meant to follow every launch that writes a projection's bf16 hi / lo input
+ * planes on the 128-token tiles.  No pass launches it yet (DESIGN.md "Importance matrix"): this call runs it alone on host-supplied
+ * planes xh / xl [M][K] (bf16 bits) of which the first m_live rows are live, adding into the caller's double[K].  Per column j:
+ * v_r = f32(hi[r][j]) + f32(lo[r][j]), s_r = v_r * v_r (no fma), the partial of token block b is p_b = ((0.0f + s_r0) + s_r1) + ...
+ * over rows 128 b .. min(128 b + 127, m_live - 1) ascending, acc[j] += (double)p_b for b ascending; rows >= m_live are never read; no
+ * atomics.  1 <= m_live <= M <= 1024.  The handle's state is untouched. */
+int rca_lm_imatrix_rows_tap(rca_lm_t* h, const uint16_t* xh_host, const uint16_t* xl_host, int32_t M, int32_t K, int32_t m_live,
+                            double* acc_inout_host);
 /* synchronise the handle's stream (timing) */
 int rca_lm_sync(rca_lm_t* h);
 int rca_codec_sync(rca_codec_t* h);

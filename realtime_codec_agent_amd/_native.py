@@ -380,6 +380,10 @@ DECODER_LAYER_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_fl
                               _I32P, _I32P]
 # int rca_quantize_rows(device, src_host, src_dtype, rows, K, type, rule, blocks_host, blocks_bytes)
 QUANTIZE_ROWS_ARGTYPES = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+# int rca_quantize_rows_w(device, src_host, src_dtype, rows, K, type, rule, col_weights, blocks_host, blocks_bytes)
+QUANTIZE_ROWS_W_ARGTYPES = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
+# int rca_lm_imatrix_rows_tap(h, xh_host, xl_host, M, K, m_live, acc_inout_host)
+IMATRIX_ARGTYPES = {"rca_lm_imatrix_rows_tap": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]}
 # int rca_lm_gemm128_tap(h, layer, kind, xh_host, xl_host, M, rows, row_base, seq_min, y_host, out_rows, kv_host, form)
 GEMM128_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                         C.c_void_p, C.c_void_p]
@@ -511,6 +515,7 @@ ABI_SYMBOLS = [
     "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame", "rca_lm_batch_step_sel",
     "rca_lm_batch_eval", "rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged",
     "rca_codec_decoder_layer_tap", "rca_quantize_rows", "rca_lm_gemm128_tap",
+    "rca_quantize_rows_w", "rca_lm_imatrix_rows_tap",
 ]
 
 
@@ -545,6 +550,13 @@ def lib():
     if hasattr(_lib, "rca_quantize_rows"):
         _lib.rca_quantize_rows.argtypes = QUANTIZE_ROWS_ARGTYPES
         _lib.rca_quantize_rows.restype = C.c_int
+    if hasattr(_lib, "rca_quantize_rows_w"):
+        _lib.rca_quantize_rows_w.argtypes = QUANTIZE_ROWS_W_ARGTYPES
+        _lib.rca_quantize_rows_w.restype = C.c_int
+    for name, argtypes in IMATRIX_ARGTYPES.items():
+        if hasattr(_lib, name):
+            getattr(_lib, name).argtypes = argtypes
+            getattr(_lib, name).restype = C.c_int
     if hasattr(_lib, "rca_lm_gemm128_tap"):
         _lib.rca_lm_gemm128_tap.argtypes = GEMM128_TAP_ARGTYPES
         _lib.rca_lm_gemm128_tap.restype = C.c_int

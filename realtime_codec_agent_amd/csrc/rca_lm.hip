@@ -8497,6 +8497,68 @@ extern "C" int rca_lm_score_rows_tap(rca_lm_t* h, const float* logits_host, cons
     return RCA_OK;
 }
 
+// ------------------------------------------------------------------------- importance matrix: the column sums (rca_lm_imatrix_rows_tap)
+// Per input column of a projection, the sum over tokens of the squared activation, over the bf16 hi / lo planes the 128-token tile route
+// stages a GEMM input as.  Definition (tests/imatrix_ref.py restates it): planes hi, lo [rows][K] with m live rows, v_r = f32(hi[r][j]) +
+// f32(lo[r][j]), s_r = v_r * v_r (one multiply, no fma), the partial of token block b is p_b = ((0.0f + s_r0) + s_r1) + ... over rows
+// 128 b .. min(128 b + 127, m - 1) in ascending order, and acc[j] += (double)p_b for b ascending.  Rows >= m are never read.  No
+// atomics: one lane owns a (column, token block) pair, the partials of a column meet in LDS, and the lane of block 0 folds them in order.
+// Nothing in a pass launches it yet: only the tap does (DESIGN.md "Importance matrix").
+#define IMX_COLS 64
+__global__ __launch_bounds__(IMX_COLS * (LM_MAXM / 128)) void lm_imatrix_kernel(const bf16_t* __restrict__ xh, const bf16_t* __restrict__ xl, int K, int m,
+                                                                                  double* __restrict__ acc) {
+    __shared__ float part[LM_MAXM / 128][IMX_COLS];
+    const int j = blockIdx.x * IMX_COLS + threadIdx.x, b = threadIdx.y;
+    const int r0 = 128 * b, r1 = min(r0 + 128, m);
+    float p = 0.0f;
+    if (j < K)
+        for (int r = r0; r < r1; ++r) {
+            const float v = __fadd_rn(__uint_as_float((unsigned)xh[(long)r * K + j] << 16), __uint_as_float((unsigned)xl[(long)r * K + j] << 16));
+            p = __fadd_rn(p, __fmul_rn(v, v));
+        }
+    part[b][threadIdx.x] = p;
+    __syncthreads();
+    if (b == 0 && j < K) {
+        double a = acc[j];
+        for (int bb = 0; 128 * bb < m; ++bb) a += (double)part[bb][threadIdx.x];
+        acc[j] = a;
+    }
+}
+static void lm_launch_imatrix(const bf16_t* xh, const bf16_t* xl, int K, int m, double* acc, hipStream_t st) {   // 1 <= m <= LM_MAXM
+    lm_imatrix_kernel<<<cdiv(K, IMX_COLS), dim3(IMX_COLS, LM_MAXM / 128), 0, st>>>(xh, xl, K, m, acc);
+}
+// tests only: the collector alone on host-supplied planes [M][K] of which m_live rows are live, adding into the caller's double[K]
+extern "C" int rca_lm_imatrix_rows_tap(rca_lm_t* h, const uint16_t* xh_host, const uint16_t* xl_host, int32_t M, int32_t K, int32_t m_live,
+                                       double* acc_inout_host) {
+    if (!h || !xh_host || !xl_host || !acc_inout_host) return fail(RCA_ERR_ARG, "imatrix_rows_tap: null pointer");
+    if (M < 1 || M > LM_MAXM || K < 1 || K > (1 << 20)) return fail(RCA_ERR_ARG, "imatrix_rows_tap: planes of %d x %d (1 .. %d rows, 1 .. %d columns)", M, K, LM_MAXM, 1 << 20);
+    if (m_live < 1 || m_live > M) return fail(RCA_ERR_ARG, "imatrix_rows_tap: m_live = %d outside [1, M = %d]", m_live, M);
+    int rc;
+    if ((rc = lm_settle(h)) != RCA_OK) return rc;
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const size_t nb = (size_t)M * K * 2;
+    bf16_t *ph = nullptr, *pl = nullptr;
+    double* acc = nullptr;
+    hipError_t e = hipSuccess;
+    if ((rc = lm_alloc((void**)&ph, nb)) == RCA_OK && (rc = lm_alloc((void**)&pl, nb)) == RCA_OK && (rc = lm_alloc((void**)&acc, (size_t)K * 8)) == RCA_OK) {
+        e = hipMemcpyAsync(ph, xh_host, nb, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pl, xl_host, nb, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(acc, acc_inout_host, (size_t)K * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            lm_launch_imatrix(ph, pl, K, m_live, acc, st);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(acc_inout_host, acc, (size_t)K * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    for (void* p : {(void*)ph, (void*)pl, (void*)acc})
+        if (p) (void)hipFree(p);
+    if (rc != RCA_OK) return rc;
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "imatrix_rows_tap: %s", hipGetErrorString(e));
+    return RCA_OK;
+}
+
 // ------------------------------------------------------------------------- quantising rows to GGUF blocks (rca_quantize_rows)
 // One lane per super-block of 256 values (Q8_0: per block of 32): the lane runs the whole rule of rca_quant_rows.h over its block, so
 // every sum has the one order the numpy restatement has and no step depends on another lane.  Not a serving path: a 1B model is 8 M
@@ -8505,14 +8567,16 @@ extern "C" int rca_lm_score_rows_tap(rca_lm_t* h, const float* logits_host, cons
 #include "rca_quant_rows.h"
 template <int TYPE, typename T>
 __global__ __launch_bounds__(128) void lm_quant_rows_kernel(const T* __restrict__ src, long nblocks, long blocks_per_row, long row0, int rule,
-                                                            unsigned char* __restrict__ out, int* __restrict__ bad) {
+                                                            unsigned char* __restrict__ out, int* __restrict__ bad, const float* __restrict__ col_weights) {
     constexpr int NV = TYPE == RCA_Q8_0 ? 32 : 256;
     constexpr int BS = TYPE == RCA_Q8_0 ? 34 : (TYPE == RCA_Q4_K ? 144 : (TYPE == RCA_Q5_K ? 176 : 210));
     for (long blk = (long)blockIdx.x * blockDim.x + threadIdx.x; blk < nblocks; blk += (long)gridDim.x * blockDim.x) {
         int status;
-        if (TYPE == RCA_Q4_K) status = rca_quant::quantize_block_qk<15>(src + blk * NV, rule, reinterpret_cast<unsigned*>(out + blk * BS));
-        else if (TYPE == RCA_Q5_K) status = rca_quant::quantize_block_qk<31>(src + blk * NV, rule, reinterpret_cast<unsigned*>(out + blk * BS));
-        else if (TYPE == RCA_Q6_K) status = rca_quant::quantize_block_q6k(src + blk * NV, rule, reinterpret_cast<unsigned short*>(out + blk * BS));
+        // rca_quantize_rows_w: a slab starts at a row, so block blk of it covers columns (blk % blocks_per_row) * 256 .. + 255
+        const float* qw = TYPE != RCA_Q8_0 && col_weights ? col_weights + (blk % blocks_per_row) * 256 : nullptr;
+        if (TYPE == RCA_Q4_K) status = rca_quant::quantize_block_qk<15>(src + blk * NV, rule, reinterpret_cast<unsigned*>(out + blk * BS), qw);
+        else if (TYPE == RCA_Q5_K) status = rca_quant::quantize_block_qk<31>(src + blk * NV, rule, reinterpret_cast<unsigned*>(out + blk * BS), qw);
+        else if (TYPE == RCA_Q6_K) status = rca_quant::quantize_block_q6k(src + blk * NV, rule, reinterpret_cast<unsigned short*>(out + blk * BS), qw);
         else status = rca_quant::quantize_block_q8_0(src + blk * NV, reinterpret_cast<unsigned short*>(out + blk * BS));
         if (status) {
             const int row = (int)min((long)INT_MAX - 1, row0 + blk / blocks_per_row);
@@ -8522,18 +8586,19 @@ __global__ __launch_bounds__(128) void lm_quant_rows_kernel(const T* __restrict_
     }
 }
 template <typename T>
-static void lm_launch_quant_rows(int type, const void* src, long nblocks, long blocks_per_row, long row0, int rule, unsigned char* out, int* bad, hipStream_t st) {
+static void lm_launch_quant_rows(int type, const void* src, long nblocks, long blocks_per_row, long row0, int rule, unsigned char* out, int* bad,
+                                 const float* qw, hipStream_t st) {
     const unsigned grid = (unsigned)std::min<long>((nblocks + 127) / 128, 1 << 20);
     const T* s = (const T*)src;
-    if (type == RCA_Q4_K) lm_quant_rows_kernel<RCA_Q4_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad);
-    else if (type == RCA_Q5_K) lm_quant_rows_kernel<RCA_Q5_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad);
-    else if (type == RCA_Q6_K) lm_quant_rows_kernel<RCA_Q6_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad);
-    else lm_quant_rows_kernel<RCA_Q8_0, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad);
+    if (type == RCA_Q4_K) lm_quant_rows_kernel<RCA_Q4_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad, qw);
+    else if (type == RCA_Q5_K) lm_quant_rows_kernel<RCA_Q5_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad, qw);
+    else if (type == RCA_Q6_K) lm_quant_rows_kernel<RCA_Q6_K, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad, qw);
+    else lm_quant_rows_kernel<RCA_Q8_0, T><<<grid, 128, 0, st>>>(s, nblocks, blocks_per_row, row0, rule, out, bad, qw);
 }
 
 #define LM_QUANT_SLAB_BYTES (64l << 20)   // source bytes uploaded per slab (at least one row)
-extern "C" int rca_quantize_rows(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
-                                 void* blocks_host, int64_t blocks_bytes) {
+static int lm_quantize_rows(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
+                            const float* col_weights, void* blocks_host, int64_t blocks_bytes) {
     if (!src_host || !blocks_host) return fail(RCA_ERR_ARG, "quantize_rows: null pointer");
     if (src_dtype != RCA_F32 && src_dtype != RCA_BF16 && src_dtype != RCA_F16) return fail(RCA_ERR_ARG, "quantize_rows: source dtype %d (RCA_F32, RCA_BF16 or RCA_F16)", src_dtype);
     if (type != RCA_Q8_0 && type != RCA_Q4_K && type != RCA_Q5_K && type != RCA_Q6_K) return fail(RCA_ERR_ARG, "quantize_rows: unknown type %d (RCA_Q8_0, RCA_Q4_K, RCA_Q5_K or RCA_Q6_K)", type);
@@ -8543,14 +8608,24 @@ extern "C" int rca_quantize_rows(int32_t device, const void* src_host, int32_t s
     const long nv = type == RCA_Q8_0 ? 32 : 256, bs = type == RCA_Q8_0 ? 34 : (type == RCA_Q4_K ? 144 : (type == RCA_Q5_K ? 176 : 210));
     const long bpr = K / nv, row_out = bpr * bs, esz = src_dtype == RCA_F32 ? 4 : 2, row_in = K * esz;
     if (blocks_bytes != rows * row_out) return fail(RCA_ERR_ARG, "quantize_rows: blocks_bytes = %ld, %ld rows of %ld values take %ld", (long)blocks_bytes, (long)rows, (long)K, rows * row_out);
+    if (col_weights) {   // (Q8_0 has one rule and no use for weights: they are checked and not uploaded)
+        if (rule != 1) return fail(RCA_ERR_ARG, "quantize_rows: column weights need rule 1 (the search), not rule %d", rule);
+        for (long j = 0; j < K; ++j)
+            if (!(col_weights[j] >= 0.0f) || !rca_quant::finite32(col_weights[j]))
+                return fail(RCA_ERR_ARG, "quantize_rows: the weight of column %ld is negative or not finite", j);
+    }
+    const bool weighted = col_weights && type != RCA_Q8_0;
     RCA_HIP(hipSetDevice(device));
     const long slab_rows = std::min<long>(rows, std::max<long>(1, LM_QUANT_SLAB_BYTES / row_in));
     hipStream_t st = nullptr;
     void* src_d = nullptr;
     unsigned char* out_d = nullptr;
     int* bad_d = nullptr;
+    float* qw_d = nullptr;
     int bad_h[2] = {INT_MAX, INT_MAX};
     hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess && weighted) e = hipMalloc((void**)&qw_d, (size_t)K * 4);
+    if (e == hipSuccess && weighted) e = hipMemcpyAsync(qw_d, col_weights, (size_t)K * 4, hipMemcpyHostToDevice, st);   // once per call
     if (e == hipSuccess) e = hipMalloc(&src_d, (size_t)(slab_rows * row_in));
     if (e == hipSuccess) e = hipMalloc((void**)&out_d, (size_t)(slab_rows * row_out));
     if (e == hipSuccess) e = hipMalloc((void**)&bad_d, 8);
@@ -8559,9 +8634,9 @@ extern "C" int rca_quantize_rows(int32_t device, const void* src_host, int32_t s
         const long nr = std::min(slab_rows, rows - r0);
         e = hipMemcpyAsync(src_d, (const char*)src_host + r0 * row_in, (size_t)(nr * row_in), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) break;
-        if (src_dtype == RCA_F32) lm_launch_quant_rows<float>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, st);
-        else if (src_dtype == RCA_BF16) lm_launch_quant_rows<rca_quant::bf16_src>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, st);
-        else lm_launch_quant_rows<rca_quant::f16_src>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, st);
+        if (src_dtype == RCA_F32) lm_launch_quant_rows<float>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, qw_d, st);
+        else if (src_dtype == RCA_BF16) lm_launch_quant_rows<rca_quant::bf16_src>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, qw_d, st);
+        else lm_launch_quant_rows<rca_quant::f16_src>(type, src_d, nr * bpr, bpr, r0, rule, out_d, bad_d, qw_d, st);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync((char*)blocks_host + r0 * row_out, out_d, (size_t)(nr * row_out), hipMemcpyDeviceToHost, st);
     }
@@ -8570,11 +8645,19 @@ extern "C" int rca_quantize_rows(int32_t device, const void* src_host, int32_t s
         const hipError_t es = hipStreamSynchronize(st);
         if (e == hipSuccess) e = es;
     }
-    for (void* p : {src_d, (void*)out_d, (void*)bad_d})
+    for (void* p : {src_d, (void*)out_d, (void*)bad_d, (void*)qw_d})
         if (p) (void)hipFree(p);
     if (st) (void)hipStreamDestroy(st);
     if (e != hipSuccess) return fail(RCA_ERR_HIP, "quantize_rows: %s", hipGetErrorString(e));
     if (bad_h[0] != INT_MAX) return fail(RCA_ERR_ARG, "quantize_rows: row %d holds a value that is not finite", bad_h[0]);
     if (bad_h[1] != INT_MAX) return fail(RCA_ERR_ARG, "quantize_rows: row %d: a block's d or dmin is not finite in fp16", bad_h[1]);
     return RCA_OK;
+}
+extern "C" int rca_quantize_rows(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
+                                 void* blocks_host, int64_t blocks_bytes) {
+    return lm_quantize_rows(device, src_host, src_dtype, rows, K, type, rule, nullptr, blocks_host, blocks_bytes);
+}
+extern "C" int rca_quantize_rows_w(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
+                                   const float* col_weights, void* blocks_host, int64_t blocks_bytes) {
+    return lm_quantize_rows(device, src_host, src_dtype, rows, K, type, rule, col_weights, blocks_host, blocks_bytes);
 }

@@ -498,6 +498,19 @@ class LlamaForAlternatingCodeChannels:
                 llm._logits_valid = False
         return ScoreResult(rows, base is not None)
 
+    def imatrix_rows_tap(self, xh: np.ndarray, xl: np.ndarray, m_live: int, acc: np.ndarray) -> np.ndarray:
+        """Tests only (rca_lm_imatrix_rows_tap): the importance matrix's column-sum kernel alone on planes xh / xl [M, K] (uint16 bf16 bits) whose first m_live rows are
+        live; returns acc (float64 [K]) with their sums added."""
+        xh, xl = np.ascontiguousarray(xh, np.uint16), np.ascontiguousarray(xl, np.uint16)
+        if xh.ndim != 2 or xh.shape != xl.shape:
+            raise ValueError(f"imatrix_rows_tap: planes {xh.shape} / {xl.shape}")
+        out = np.array(acc, np.float64)
+        if out.shape != (xh.shape[1],):
+            raise ValueError(f"imatrix_rows_tap: {out.shape} accumulators for {xh.shape[1]} columns")
+        N.check(self._lib.rca_lm_imatrix_rows_tap(self._h, xh.ctypes.data, xl.ctypes.data, xh.shape[0], xh.shape[1], int(m_live), out.ctypes.data),
+                "rca_lm_imatrix_rows_tap")
+        return out
+
     def score_rows_tap(self, logits: np.ndarray, targets: Sequence[int], base_logits: Optional[np.ndarray] = None) -> "ScoreResult":
         """Tests only (rca_lm_score_rows_tap): the row reduction of score() alone on host-supplied logits [M, n_vocab]."""
         logits = np.ascontiguousarray(logits, dtype=np.float32)

@@ -5,12 +5,16 @@ This module goes from an HF directory, an .npz (llm.save_npz) or an F32 / F16 / 
 model, in memory (`quantize_weights`, handed to LlamaForAlternatingCodeChannels(weights=..., config=...)) or as a file (`write_llama_gguf`,
 read back by gguf.load_llama_gguf; laid out as convert_hf_to_gguf.py lays one out, though no llama.cpp was at hand to open one):
 
-    python -m realtime_codec_agent_amd.quantize --model IN --out OUT.gguf --type q4_k_m [--rule search|minmax] [--device N]
+    python -m realtime_codec_agent_amd.quantize --model IN --out OUT.gguf --type q4_k_m [--rule search|minmax] [--imatrix F.gguf] [--device N]
 
 The quantisers run on the device (rca_quantize_rows, csrc/rca_quant_rows.h).  rule="search" restates the scale searches of ggml's published
 reference quantisers (make_qkx2_quants for Q4_K / Q5_K, make_qx_quants for Q6_K; DESIGN.md "Quantising on the card"); ggml is not part of this
 tree, so parity with llama-quantize's own bits is not pinned -- every block written de-quantises by GGUF's rule, which is what a reader
-depends on.  rule="minmax" is this build's plain rule, the one weight_format="q4_k" / "q5_k" applies at load.  No importance matrix.
+depends on.  rule="minmax" is this build's plain rule, the one weight_format="q4_k" / "q5_k" applies at load.
+
+--imatrix / imatrix=: an importance matrix (a GGUF imatrix file, realtime_codec_agent_amd.imatrix: per input column of every projection,
+the mean squared activation over a corpus) turns the search into the weighted one (rca_quantize_rows_w; DESIGN.md "Weighted K-quant search"): the error
+of a column counts by how strongly the corpus drives it.  What llama-quantize --imatrix does, restated; parity with its bits is not pinned.
 
 The "q4_k_m" / "q5_k_m" recipes are llama-quantize's type mix (llama_tensor_get_type for LLAMA_FTYPE_MOSTLY_Q4_K_M / Q5_K_M on a model
 without MoE / GQA special cases): Q6_K for output.weight and for attn_v / ffn_down in the layers use_more_bits() picks, Q4_K resp. Q5_K for
@@ -77,10 +81,12 @@ def gguf_name(hf_name: str) -> str:
     raise ValueError(f"tensor {hf_name!r} has no place in a llama-architecture GGUF")
 
 
-def quantize_matrix(w: np.ndarray, type: str, rule: str = "search", device: int = 0, name: str = "tensor"):
+def quantize_matrix(w: np.ndarray, type: str, rule: str = "search", device: int = 0, name: str = "tensor",
+                    col_weights: Optional[np.ndarray] = None):
     """w [N, K] (float32, float16, or uint16 holding bf16 bits; K % 256 == 0) -> the _native blocks object of `type` ("q8_0", "q4_k", "q5_k",
     "q6_k": Q8Blocks / Q4KBlocks / Q5KBlocks / Q6KBlocks, what the GGUF loader produces for such a tensor), quantised on `device`.
-    A value that is not finite, or a block whose d / dmin is not finite in fp16, is refused (RcaError naming `name` and the row)."""
+    A value that is not finite, or a block whose d / dmin is not finite in fp16, is refused (RcaError naming `name` and the row).
+    col_weights: one non-negative float32 per input column [K] -> the weighted rules (rule "search" only; "q8_0" ignores them)."""
     if type not in TYPES:
         raise ValueError(f"type {type!r}: one of {', '.join(TYPES)}")
     if rule not in RULES:
@@ -100,10 +106,17 @@ def quantize_matrix(w: np.ndarray, type: str, rule: str = "search", device: int 
     if K % 256:
         raise N.RcaError(f"{name}: K = {K} is not a multiple of 256")
     out = np.empty((rows, K // nv * nbytes), np.uint8)
-    rc = N.lib().rca_quantize_rows(int(device), w.ctypes.data, dt, rows, K, rca_type, RULES[rule], out.ctypes.data, out.nbytes)
+    entry = "rca_quantize_rows" if col_weights is None else "rca_quantize_rows_w"
+    if col_weights is None:
+        rc = N.lib().rca_quantize_rows(int(device), w.ctypes.data, dt, rows, K, rca_type, RULES[rule], out.ctypes.data, out.nbytes)
+    else:
+        qw = np.ascontiguousarray(col_weights, np.float32)
+        if qw.shape != (K,):
+            raise ValueError(f"{name}: {qw.shape} column weights for K = {K}")
+        rc = N.lib().rca_quantize_rows_w(int(device), w.ctypes.data, dt, rows, K, rca_type, RULES[rule], qw.ctypes.data, out.ctypes.data, out.nbytes)
     if rc != 0:
         msg = N.lib().rca_last_error()
-        raise N.RcaError(f"{name}: rca_quantize_rows failed (rc={rc}): {msg.decode(errors='replace') if msg else ''}")
+        raise N.RcaError(f"{name}: {entry} failed (rc={rc}): {msg.decode(errors='replace') if msg else ''}")
     return cls(out, (rows, K))
 
 
@@ -113,6 +126,7 @@ class QuantizedWeights(dict):
     recipe: Optional[str] = None
     types: Dict[str, str]
     seconds: Dict[str, float]
+    imatrix_meta: Optional[Dict[str, Any]] = None       # the quantize.imatrix.* keys write_llama_gguf adds (quantised under an imatrix)
 
 
 def _to_f32(a: np.ndarray) -> np.ndarray:
@@ -122,11 +136,25 @@ def _to_f32(a: np.ndarray) -> np.ndarray:
     return a.astype(np.float32)
 
 
+def imatrix_vector(imatrix, name: str) -> Optional[np.ndarray]:
+    """The column weights of GGUF tensor `name` under an importance matrix {name: (in_sum2 [K], count)}: float32(in_sum2 / count), or None
+    where it has no entry (or no token was collected)."""
+    e = imatrix.get(name)
+    if e is None or int(e[1]) <= 0:
+        return None
+    return (np.asarray(e[0], np.float64).reshape(-1) / float(int(e[1]))).astype(np.float32)
+
+
 def quantize_weights(cfg, weights: Dict[str, Any], recipe: str, rule: str = "search", device: int = 0,
-                     quantize_matrix: Callable = quantize_matrix, report: Optional[Callable[[str], None]] = None) -> QuantizedWeights:
+                     quantize_matrix: Callable = quantize_matrix, report: Optional[Callable[[str], None]] = None,
+                     imatrix: Optional[Dict[str, Any]] = None) -> QuantizedWeights:
     """cfg: LMConfig; weights: HF-named arrays (float32 / float16 / bf16 bits; a missing lm_head.weight is tied to the embedding table) ->
     a weights dict LlamaForAlternatingCodeChannels(weights=..., config=cfg) takes as it is.  A source that is already quantised (blocks
-    objects) is refused.  quantize_matrix: the matrix quantiser (tests substitute a host one)."""
+    objects) is refused.  quantize_matrix: the matrix quantiser (tests substitute a host one).
+    imatrix: {GGUF tensor name: (in_sum2 [K], count)} (imatrix.read_imatrix_gguf): every matrix with an entry is quantised
+    under the column weights float32(in_sum2 / count) (rule "search" only).  The embedding table has no vector by construction; any other
+    matrix without an entry is quantised unweighted with one warning naming it; a vector whose length is not the matrix's K is refused
+    before any work."""
     if recipe not in RECIPES:
         raise ValueError(f"recipe {recipe!r}: one of {', '.join(RECIPES)}")
     out = QuantizedWeights()
@@ -140,6 +168,24 @@ def quantize_weights(cfg, weights: Dict[str, Any], recipe: str, rule: str = "sea
                              "first (a quantised table cannot take them afterwards)")
         if hasattr(v, "dequantize"):
             raise ValueError(f"{k} is already quantised ({type(v).__name__}): re-quantising a quantised source is not supported")
+    vectors: Dict[str, np.ndarray] = {}
+    if imatrix is not None:
+        if rule != "search":
+            raise ValueError(f"an importance matrix needs rule 'search', not {rule!r}")
+        for k, v in src.items():
+            if k == "rope.inv_freq" or k.startswith("codec.") or np.asarray(v).ndim != 2:
+                continue
+            qw = imatrix_vector(imatrix, gguf_name(k))
+            if qw is not None:
+                if qw.shape != (np.asarray(v).shape[1],):
+                    raise ValueError(f"{k}: the importance matrix holds {qw.shape[0]} columns for {gguf_name(k)}, the matrix has K = {np.asarray(v).shape[1]}")
+                if not np.all(np.isfinite(qw)) or np.any(qw < 0):
+                    raise ValueError(f"{k}: the importance matrix's vector for {gguf_name(k)} holds a value that is negative or not finite")
+                vectors[k] = qw
+        out.imatrix_meta = {"quantize.imatrix.file": str(getattr(imatrix, "file", "") or ""),
+                            "quantize.imatrix.dataset": str((list(getattr(imatrix, "datasets", [])) or [""])[0]),
+                            "quantize.imatrix.entries_count": int(len(imatrix)),
+                            "quantize.imatrix.chunks_count": int(getattr(imatrix, "chunk_count", 0) or 0)}
     for k, v in src.items():
         if k == "rope.inv_freq" or k.startswith("codec."):
             out[k] = v
@@ -155,7 +201,12 @@ def quantize_weights(cfg, weights: Dict[str, Any], recipe: str, rule: str = "sea
             out[k], out.types[k] = (a if a.dtype == np.float16 else _to_f32(a).astype(np.float16)), "f16"
             continue
         t0 = time.perf_counter()
-        out[k] = quantize_matrix(a, t, rule=rule, device=device, name=k)
+        if k in vectors:
+            out[k] = quantize_matrix(a, t, rule=rule, device=device, name=k, col_weights=vectors[k])
+        else:
+            if imatrix is not None and k != "model.embed_tokens.weight":
+                warnings.warn(f"{k} ({gguf_name(k)}) has no entry in the importance matrix: it is quantised unweighted")
+            out[k] = quantize_matrix(a, t, rule=rule, device=device, name=k)
         out.seconds[k] = time.perf_counter() - t0
         out.types[k] = t
         if report:
@@ -278,8 +329,9 @@ def write_llama_gguf(path: str, cfg, weights: Dict[str, Any], meta: Optional[Dic
     kv = dict(own)
     kv.setdefault("llama.context_length", int((meta or {}).get("llama.context_length", 131072 if cfg.rope_scaling else 2048)))
     for k, v in (meta or {}).items():
-        if k not in kv and k != "gguf.version":
+        if k not in kv and k != "gguf.version" and not k.startswith("quantize.imatrix."):
             kv[k] = v
+    kv.update(getattr(weights, "imatrix_meta", None) or {})
     ts = [("token_embd.weight", weights["model.embed_tokens.weight"]), ("output_norm.weight", _to_f32(weights["model.norm.weight"])),
           ("output.weight", lm_head)]
     inv = weights.get("rope.inv_freq")
@@ -340,13 +392,21 @@ def main(argv=None) -> int:
     ap.add_argument("--out", required=True, help="the GGUF file to write")
     ap.add_argument("--type", required=True, choices=RECIPES)
     ap.add_argument("--rule", default="search", choices=sorted(RULES))
+    ap.add_argument("--imatrix", default=None, help="an importance matrix (a GGUF imatrix file): weighted search")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.imatrix is not None and a.rule != "search":
+        ap.error("--imatrix needs --rule search")
+    imx = None
+    if a.imatrix is not None:
+        from .imatrix import read_imatrix_gguf
+        imx = read_imatrix_gguf(a.imatrix)
+        print(f"{a.imatrix}: {len(imx)} entries, {imx.chunk_count} chunks of {imx.chunk_size} tokens")
     t0 = time.perf_counter()
     cfg, w, meta = load_source(a.model)
     t1 = time.perf_counter()
     print(f"{a.model}: {cfg.n_layers} layers, hidden {cfg.hidden}, vocab {cfg.vocab_size}; loaded in {t1 - t0:.2f} s")
-    q = quantize_weights(cfg, w, a.type, rule=a.rule, device=a.device, report=print)
+    q = quantize_weights(cfg, w, a.type, rule=a.rule, device=a.device, report=print, imatrix=imx)
     t2 = time.perf_counter()
     n_val = sum(int(np.prod(v.shape)) for k, v in q.items() if k in q.types)
     n_bytes = sum((v.raw.nbytes if hasattr(v, "raw") else v.nbytes) for k, v in q.items() if k in q.types)
