@@ -928,13 +928,35 @@ int rca_quantize_rows_w(int32_t device, const void* src_host, int32_t src_dtype,
                         const float* col_weights, void* blocks_host, int64_t blocks_bytes);
 /* Tests only: the column sums an importance matrix is made of (what llama-imatrix collects: per input column of a projection, the sum
  * over the tokens of the squared activation), by the kernel meant to follow every launch that writes a projection's bf16 hi / lo input
- * planes on the 128-token tiles.  No pass launches it yet (DESIGN.md "Importance matrix"): this call runs it alone on host-supplied
+ * planes on the 128-token tiles of a collecting pass (rca_lm_imatrix_chunk).  This call runs it alone on host-supplied
  * planes xh / xl [M][K] (bf16 bits) of which the first m_live rows are live, adding into the caller's double[K].  Per column j:
  * v_r = f32(hi[r][j]) + f32(lo[r][j]), s_r = v_r * v_r (no fma), the partial of token block b is p_b = ((0.0f + s_r0) + s_r1) + ...
  * over rows 128 b .. min(128 b + 127, m_live - 1) ascending, acc[j] += (double)p_b for b ascending; rows >= m_live are never read; no
  * atomics.  1 <= m_live <= M <= 1024.  The handle's state is untouched. */
 int rca_lm_imatrix_rows_tap(rca_lm_t* h, const uint16_t* xh_host, const uint16_t* xl_host, int32_t M, int32_t K, int32_t m_live,
                             double* acc_inout_host);
+/* Collecting an importance matrix (what llama-imatrix does), on handles whose long evals take the 128-token tiles.
+ * rca_lm_imatrix_begin allocates and zeroes the handle's own accumulators (never shared with a twin): double, per layer the vectors of
+ * kind 0 (width hidden: the input of attn_q / attn_k / attn_v), 1 (n_heads * head_dim: attn_output), 2 (hidden: ffn_gate / ffn_up) and
+ * 3 (ffn: ffn_down), and one of kind 4 (hidden: output.weight) -- plus a token count.  RCA_ERR_STATE: the handle's long evals do not
+ * take the 128-token tiles (rca_lm_set_mfma_prefill off, or weights / dimensions off them); the handle is already collecting.
+ * rca_lm_imatrix_chunk appends n >= 1 tokens at n_tokens exactly as rca_lm_score walks them (passes of up to 1024 rows on the tiles, any
+ * n), each pass summing every projection's bf16 hi / lo input planes right behind the launch that wrote them, by the definition at
+ * rca_lm_imatrix_rows_tap (m_live = the pass's rows), and the final norm's planes of all its rows for kind 4; no logits but the last
+ * position's are computed.  n_tokens, the K / V rows and the last logits are left bit for bit as rca_lm_score leaves them; the count
+ * grows by n.  Refusals as rca_lm_score's (context overflow: RCA_ERR_STATE; an id outside the vocabulary: RCA_ERR_ARG), RCA_ERR_STATE
+ * when the handle is not collecting; a refused call leaves sums and count untouched.  NO OTHER CALL COLLECTS: eval, eval_async, step,
+ * score and the batch calls on a collecting handle leave sums and count as they are.
+ * rca_lm_imatrix_get downloads the K sums of (layer, kind) (layer is ignored for kind 4) and, where count_out is not NULL, the count.
+ * RCA_ERR_ARG for a layer or kind that does not exist, or a K that is not the kind's width (the message names it).
+ * rca_lm_imatrix_end frees the accumulators (no-op when not collecting); so does rca_lm_destroy. */
+int rca_lm_imatrix_begin(rca_lm_t* h);
+int rca_lm_imatrix_chunk(rca_lm_t* h, const int32_t* ids, int32_t n);
+int rca_lm_imatrix_get(rca_lm_t* h, int32_t layer, int32_t kind, double* sums_out, int32_t K, int64_t* count_out);
+int rca_lm_imatrix_end(rca_lm_t* h);
+/* Tests only: rca_lm_imatrix_chunk for ONE pass (1 <= n <= 1024) that also copies the planes of (layer, kind), device to device, right
+ * behind their collection launch, and downloads their first n rows to xh_out / xl_out [n][K] (bf16 bits, K = the kind's width). */
+int rca_lm_imatrix_chunk_tap(rca_lm_t* h, const int32_t* ids, int32_t n, int32_t layer, int32_t kind, uint16_t* xh_out, uint16_t* xl_out);
 /* synchronise the handle's stream (timing) */
 int rca_lm_sync(rca_lm_t* h);
 int rca_codec_sync(rca_codec_t* h);

@@ -383,7 +383,13 @@ QUANTIZE_ROWS_ARGTYPES = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64
 # int rca_quantize_rows_w(device, src_host, src_dtype, rows, K, type, rule, col_weights, blocks_host, blocks_bytes)
 QUANTIZE_ROWS_W_ARGTYPES = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
 # int rca_lm_imatrix_rows_tap(h, xh_host, xl_host, M, K, m_live, acc_inout_host)
-IMATRIX_ARGTYPES = {"rca_lm_imatrix_rows_tap": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]}
+# int rca_lm_imatrix_begin(h) / _end(h) / _chunk(h, ids, n) / _chunk_tap(h, ids, n, layer, kind, xh_out, xl_out) /
+# _get(h, layer, kind, sums_out, K, count_out)
+IMATRIX_ARGTYPES = {"rca_lm_imatrix_rows_tap": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+                    "rca_lm_imatrix_begin": [C.c_void_p], "rca_lm_imatrix_end": [C.c_void_p],
+                    "rca_lm_imatrix_chunk": [C.c_void_p, C.c_void_p, C.c_int32],
+                    "rca_lm_imatrix_chunk_tap": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+                    "rca_lm_imatrix_get": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]}
 # int rca_lm_gemm128_tap(h, layer, kind, xh_host, xl_host, M, rows, row_base, seq_min, y_host, out_rows, kv_host, form)
 GEMM128_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                         C.c_void_p, C.c_void_p]
@@ -516,6 +522,7 @@ ABI_SYMBOLS = [
     "rca_lm_batch_eval", "rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged",
     "rca_codec_decoder_layer_tap", "rca_quantize_rows", "rca_lm_gemm128_tap",
     "rca_quantize_rows_w", "rca_lm_imatrix_rows_tap",
+    "rca_lm_imatrix_begin", "rca_lm_imatrix_chunk", "rca_lm_imatrix_get", "rca_lm_imatrix_end", "rca_lm_imatrix_chunk_tap",
 ]
 
 

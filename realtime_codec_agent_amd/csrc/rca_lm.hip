@@ -2414,6 +2414,11 @@ struct rca_lm {
     char* sc_pin = nullptr;                  // pinned: the (n_tokens, m, ids) block of EVERY pass of a call, so no pass waits for the one before
     size_t sc_pin_cap = 0;
     hipEvent_t sc_ready = nullptr, sc_free = nullptr;   // base: block logits written; scored handle: block logits consumed
+    // rca_lm_imatrix_begin .. rca_lm_imatrix_end: the importance matrix's accumulators -- this handle's own, never a twin's
+    double* imx_acc = nullptr;               // n_layers * (H + AO + H + F) + H column sums (lm_imx_slot); null: not collecting
+    long imx_count = 0;                      // tokens summed
+    int imx_tap_layer = -1, imx_tap_kind = -1;            // rca_lm_imatrix_chunk_tap: the planes of this (layer, kind) are copied to
+    bf16_t *imx_tap_h = nullptr, *imx_tap_l = nullptr;    // these buffers right behind their collection launch
 };
 // an rca_lm_batch_eval pass over this handle may still be running on its workspace's stream: wait for it (every place that waits for
 // the handle's own stream before it reads or changes the handle does)
@@ -2582,6 +2587,7 @@ extern "C" int rca_lm_destroy(rca_lm_t* h) {
         if (p) (void)hipFree(p);
     h->sc_blk = nullptr; h->sc_rows = nullptr; h->sc_tgt = nullptr;
     if (h->sc_pin) { (void)hipHostFree(h->sc_pin); h->sc_pin = nullptr; }
+    if (h->imx_acc) { (void)hipFree(h->imx_acc); h->imx_acc = nullptr; }
     if (h->sc_ready) { (void)hipEventDestroy(h->sc_ready); h->sc_ready = nullptr; }
     if (h->sc_free) { (void)hipEventDestroy(h->sc_free); h->sc_free = nullptr; }
     if (h->stream) { (void)hipStreamDestroy(h->stream); h->stream = nullptr; }
@@ -5291,7 +5297,33 @@ struct LmTilePass {
     const LmGroupRow* qrows;   // null: the QKV epilogue is GEMM_EPI_ROPE into h's own cache (lm_rope_target, n_ctx bound); else
                                // GEMM_EPI_ROPE_ROWS, position, cache and bound per row from this table
     int seq_min;               // workgroup threshold of g128_form: g128_seq_min() for every pass (rca_lm_gemm128_tap: the test's own)
+    double* imx = nullptr;     // a collecting pass (rca_lm_imatrix_chunk): the accumulator base of h; null for every other caller, whose
+                               // launch sequence then is what it was
 };
+// The importance matrix's accumulators of a handle: per layer the vectors of kind 0 (width H: the input of attn_q / attn_k / attn_v),
+// 1 (AO: attn_output), 2 (H: ffn_gate / ffn_up), 3 (F: ffn_down), and behind the layers kind 4 (H: output.weight; `layer` is ignored).
+// Returns the offset of (layer, kind) and its width in *K; -1 for a layer or kind that does not exist.
+static long lm_imx_slot(const rca_lm_config_t& c, int layer, int kind, int* K) {
+    const long H = c.hidden, AO = (long)c.n_heads * c.head_dim, F = c.ffn, per_layer = H + AO + H + F;
+    if (kind == 4) { *K = (int)H; return per_layer * c.n_layers; }
+    if (kind < 0 || kind > 4 || layer < 0 || layer >= c.n_layers) return -1;
+    const long off[4] = {0, H, H + AO, H + AO + H};
+    *K = (int)(kind == 1 ? AO : kind == 3 ? F : H);
+    return per_layer * layer + off[kind];
+}
+static void lm_launch_imatrix(const bf16_t* xh, const bf16_t* xl, int K, int m, double* acc, hipStream_t st);
+// Behind a launch of a collecting pass that wrote a projection's input planes xh / xl (row stride = the projection's K; the pass's
+// p.rows rows are all live): their column sums into the slot of (l, kind); rca_lm_imatrix_chunk_tap's copy of the planes follows it.
+static void lm_collect_planes(const LmTilePass& p, hipStream_t st, int l, int kind, const bf16_t* xh, const bf16_t* xl) {
+    if (!p.imx) return;
+    int K = 0;
+    const long off = lm_imx_slot(p.h->cfg, l, kind, &K);
+    lm_launch_imatrix(xh, xl, K, p.rows, p.imx + off, st);
+    if (p.h->imx_tap_kind == kind && (kind == 4 || p.h->imx_tap_layer == l)) {
+        (void)hipMemcpyAsync(p.h->imx_tap_h, xh, (size_t)p.rows * K * 2, hipMemcpyDeviceToDevice, st);
+        (void)hipMemcpyAsync(p.h->imx_tap_l, xl, (size_t)p.rows * K * 2, hipMemcpyDeviceToDevice, st);
+    }
+}
 // One projection of such a pass: the GEMM and, where its k slices went through HBM, the epilogue that sums them.  A projection whose
 // token blocks alone put `seq_min` workgroups on the chip is run with every workgroup walking the k slices itself (same sums in the
 // same order, no partial sums through HBM, no epilogue launch); RCA_LM_SEQ_MIN_WGS overrides the threshold (0 = never) for A/B runs.
@@ -5326,6 +5358,7 @@ static void lm_enqueue_layers128(const LmTilePass& p, hipStream_t st, Attn&& att
         const GemvGroup grp = p.qrows ? GemvGroup{p.qrows, l} : nogroup;
         if (!p.qrows) lm_rope_target(h, l, rope);
         lm_add_rmsnorm_kernel<<<p.rows, 64, 0, st>>>(p.stt, x, nullptr, nullptr, 0, 0, L.attn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
+        lm_collect_planes(p, st, l, 0, h->xh, h->xl);
         for (int seg = 0; seg < (L.split_v ? 2 : 1); ++seg) {   // [q; k; v] as one matrix, or [q; k] and v when their formats differ
             const WMat& w = seg ? L.vseg : L.qkv;
             rope.row_base = seg ? L.qkv.N : 0;
@@ -5333,9 +5366,12 @@ static void lm_enqueue_layers128(const LmTilePass& p, hipStream_t st, Attn&& att
             else lm_launch_proj128<GEMM_EPI_ROPE>(p, w, st, h->xh, h->xl, w.N, H, h->qkv, QKV, nullptr, nullptr, rope, grp);
         }
         attention(l);
+        lm_collect_planes(p, st, l, 1, h->xh, h->xl);
         lm_launch_proj128<GEMM_EPI_RESID>(p, L.o, st, h->xh, h->xl, H, AO, x, H, nullptr, nullptr);
         lm_add_rmsnorm_kernel<<<p.rows, 64, 0, st>>>(p.stt, x, nullptr, nullptr, 0, 0, L.ffn_norm, h->xn, H, c.rms_eps, h->xh, h->xl);
+        lm_collect_planes(p, st, l, 2, h->xh, h->xl);
         lm_launch_proj128<GEMM_EPI_SWIGLU>(p, L.gu, st, h->xh, h->xl, 2 * F, H, nullptr, F, hh, hl);
+        lm_collect_planes(p, st, l, 3, hh, hl);
         lm_launch_proj128<GEMM_EPI_RESID>(p, L.down, st, hh, hl, H, F, x, H, nullptr, nullptr);
     }
 }
@@ -5350,9 +5386,10 @@ static void lm_launch_logits128(rca_lm* h, const LmDevState* stt, const bf16_t* 
 // A handle's own pass of M tokens.  bt (rca_lm_batch_eval): the rows are segments of several sessions packed into h's buffers (h is the
 // call's workspace, h->stt the pass's state; M is the pass's whole token blocks, the launch geometry, and h->stt->m the rows that
 // exist); what is per session -- the QKV epilogue's position and cache, the q8_0 quantiser, attention -- takes it from the pass's tables.
-static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch, const LmEvalTables* bt = nullptr) {
+// imx (rca_lm_imatrix_chunk alone; M = m, no bt): the pass collects into these accumulators.
+static int lm_enqueue_prefill_tile128(rca_lm* h, int M, hipStream_t st, int nsp_launch, const LmEvalTables* bt = nullptr, double* imx = nullptr) {
     const rca_lm_config_t& c = h->cfg;
-    const LmTilePass p{h, h->stt, M, (int)cdiv(M, 128), bt ? bt->rows : nullptr, g128_seq_min()};
+    const LmTilePass p{h, h->stt, M, (int)cdiv(M, 128), bt ? bt->rows : nullptr, g128_seq_min(), imx};
     lm_embed_kernel<<<M, 256, 0, st>>>(h->stt, h->embed, h->embed_f32, h->x, c.hidden, c.vocab_size);
     if (bt)
         lm_enqueue_layers128(p, st, [&](int l) {
@@ -8340,6 +8377,14 @@ static size_t lm_score_pin_bytes(int n, int step) {   // every pass's state bloc
     for (int off = 0; off < n; off += step) b += (lm_state_bytes(std::min(step, n - off)) + 15) / 16 * 16;
     return b;
 }
+static int lm_score_reserve_pin(rca_lm* h, size_t pin_bytes) {   // the pinned block alone (rca_lm_imatrix_chunk scores nothing)
+    if (pin_bytes > h->sc_pin_cap) {
+        if (h->sc_pin) { (void)hipHostFree(h->sc_pin); h->sc_pin = nullptr; h->sc_pin_cap = 0; }
+        RCA_HIP(hipHostMalloc((void**)&h->sc_pin, pin_bytes, hipHostMallocDefault));
+        h->sc_pin_cap = pin_bytes;
+    }
+    return RCA_OK;
+}
 static int lm_score_reserve(rca_lm* h, long n_rows, size_t pin_bytes) {
     int rc;
     if (!h->sc_blk && (rc = lm_alloc((void**)&h->sc_blk, (size_t)128 * h->cfg.vocab_size * 4)) != RCA_OK) return rc;
@@ -8353,12 +8398,7 @@ static int lm_score_reserve(rca_lm* h, long n_rows, size_t pin_bytes) {
         if ((rc = lm_alloc((void**)&h->sc_tgt, (size_t)n_rows * 4)) != RCA_OK) return rc;
         h->sc_rows_cap = n_rows;
     }
-    if (pin_bytes > h->sc_pin_cap) {
-        if (h->sc_pin) { (void)hipHostFree(h->sc_pin); h->sc_pin = nullptr; h->sc_pin_cap = 0; }
-        RCA_HIP(hipHostMalloc((void**)&h->sc_pin, pin_bytes, hipHostMallocDefault));
-        h->sc_pin_cap = pin_bytes;
-    }
-    return RCA_OK;
+    return lm_score_reserve_pin(h, pin_bytes);
 }
 // the next pass of a scoring call as the device will read it, from this pass's OWN pinned block (lm_push_state reuses one)
 static int lm_score_push(rca_lm* x, size_t* pin_off, const int32_t* ids, int m, hipStream_t st) {
@@ -8502,30 +8542,62 @@ extern "C" int rca_lm_score_rows_tap(rca_lm_t* h, const float* logits_host, cons
 // stages a GEMM input as.  Definition (tests/imatrix_ref.py restates it): planes hi, lo [rows][K] with m live rows, v_r = f32(hi[r][j]) +
 // f32(lo[r][j]), s_r = v_r * v_r (one multiply, no fma), the partial of token block b is p_b = ((0.0f + s_r0) + s_r1) + ... over rows
 // 128 b .. min(128 b + 127, m - 1) in ascending order, and acc[j] += (double)p_b for b ascending.  Rows >= m are never read.  No
-// atomics: one lane owns a (column, token block) pair, the partials of a column meet in LDS, and the lane of block 0 folds them in order.
-// Nothing in a pass launches it yet: only the tap does (DESIGN.md "Importance matrix").
-#define IMX_COLS 64
-__global__ __launch_bounds__(IMX_COLS * (LM_MAXM / 128)) void lm_imatrix_kernel(const bf16_t* __restrict__ xh, const bf16_t* __restrict__ xl, int K, int m,
-                                                                                  double* __restrict__ acc) {
+// atomics: one lane owns a (column pair, token block), the partials of a column meet in LDS, and one lane per column folds them in order.
+// The adds of a column are a serial chain, so what a lane can do is keep loads in flight: it takes both columns of a pair with one
+// 32-bit load per plane and row, and requests IMX_ROWS rows (clamped to its last live row) before the ordered adds of those rows.
+// An odd K has no aligned pairs: its lanes load their two columns 2 bytes at a time.  Every collecting pass launches it
+// (lm_collect_planes, rca_lm_imatrix_chunk) and the tap runs it alone (DESIGN.md "Importance matrix").
+#define IMX_COLS 64    // columns per workgroup: 32 lanes of column pairs x 8 token blocks = 4 waves
+#define IMX_ROWS 32    // rows requested before their adds
+__global__ __launch_bounds__(IMX_COLS / 2 * (LM_MAXM / 128)) void lm_imatrix_kernel(const bf16_t* __restrict__ xh, const bf16_t* __restrict__ xl, int K, int m,
+                                                                                      double* __restrict__ acc) {
     __shared__ float part[LM_MAXM / 128][IMX_COLS];
-    const int j = blockIdx.x * IMX_COLS + threadIdx.x, b = threadIdx.y;
+    const int j = blockIdx.x * IMX_COLS + 2 * threadIdx.x, b = threadIdx.y;
     const int r0 = 128 * b, r1 = min(r0 + 128, m);
-    float p = 0.0f;
-    if (j < K)
+    float p0 = 0.0f, p1 = 0.0f;
+    if (!(K & 1)) {
+        if (j < K)   // (K even, j even: column j + 1 exists and the pair is 4-byte aligned in every row)
+            for (int r = r0; r < r1; r += IMX_ROWS) {
+                unsigned a[IMX_ROWS], c[IMX_ROWS];
+#pragma unroll
+                for (int u = 0; u < IMX_ROWS; ++u) {
+                    const long at = (long)min(r + u, r1 - 1) * K + j;
+                    a[u] = *reinterpret_cast<const unsigned*>(xh + at);
+                    c[u] = *reinterpret_cast<const unsigned*>(xl + at);
+                }
+#pragma unroll
+                for (int u = 0; u < IMX_ROWS; ++u)
+                    if (r + u < r1) {
+                        const float v0 = __fadd_rn(__uint_as_float(a[u] << 16), __uint_as_float(c[u] << 16));
+                        const float v1 = __fadd_rn(__uint_as_float(a[u] & 0xFFFF0000u), __uint_as_float(c[u] & 0xFFFF0000u));
+                        p0 = __fadd_rn(p0, __fmul_rn(v0, v0));
+                        p1 = __fadd_rn(p1, __fmul_rn(v1, v1));
+                    }
+            }
+    } else {
         for (int r = r0; r < r1; ++r) {
-            const float v = __fadd_rn(__uint_as_float((unsigned)xh[(long)r * K + j] << 16), __uint_as_float((unsigned)xl[(long)r * K + j] << 16));
-            p = __fadd_rn(p, __fmul_rn(v, v));
+            if (j < K) {
+                const float v = __fadd_rn(__uint_as_float((unsigned)xh[(long)r * K + j] << 16), __uint_as_float((unsigned)xl[(long)r * K + j] << 16));
+                p0 = __fadd_rn(p0, __fmul_rn(v, v));
+            }
+            if (j + 1 < K) {
+                const float v = __fadd_rn(__uint_as_float((unsigned)xh[(long)r * K + j + 1] << 16), __uint_as_float((unsigned)xl[(long)r * K + j + 1] << 16));
+                p1 = __fadd_rn(p1, __fmul_rn(v, v));
+            }
         }
-    part[b][threadIdx.x] = p;
+    }
+    part[b][2 * threadIdx.x] = p0;
+    part[b][2 * threadIdx.x + 1] = p1;
     __syncthreads();
-    if (b == 0 && j < K) {
-        double a = acc[j];
-        for (int bb = 0; 128 * bb < m; ++bb) a += (double)part[bb][threadIdx.x];
-        acc[j] = a;
+    const int t = threadIdx.y * (IMX_COLS / 2) + threadIdx.x, jc = blockIdx.x * IMX_COLS + t;   // the first wave: one lane per column
+    if (t < IMX_COLS && jc < K) {
+        double s = acc[jc];
+        for (int bb = 0; 128 * bb < m; ++bb) s += (double)part[bb][t];
+        acc[jc] = s;
     }
 }
 static void lm_launch_imatrix(const bf16_t* xh, const bf16_t* xl, int K, int m, double* acc, hipStream_t st) {   // 1 <= m <= LM_MAXM
-    lm_imatrix_kernel<<<cdiv(K, IMX_COLS), dim3(IMX_COLS, LM_MAXM / 128), 0, st>>>(xh, xl, K, m, acc);
+    lm_imatrix_kernel<<<cdiv(K, IMX_COLS), dim3(IMX_COLS / 2, LM_MAXM / 128), 0, st>>>(xh, xl, K, m, acc);
 }
 // tests only: the collector alone on host-supplied planes [M][K] of which m_live rows are live, adding into the caller's double[K]
 extern "C" int rca_lm_imatrix_rows_tap(rca_lm_t* h, const uint16_t* xh_host, const uint16_t* xl_host, int32_t M, int32_t K, int32_t m_live,
@@ -8556,6 +8628,121 @@ extern "C" int rca_lm_imatrix_rows_tap(rca_lm_t* h, const uint16_t* xh_host, con
         if (p) (void)hipFree(p);
     if (rc != RCA_OK) return rc;
     if (e != hipSuccess) return fail(RCA_ERR_HIP, "imatrix_rows_tap: %s", hipGetErrorString(e));
+    return RCA_OK;
+}
+
+// ------------------------------------------------------------------------- importance matrix: the collector (rca_lm_imatrix_begin .. _end)
+// A handle between begin and end holds n_layers * (H + AO + H + F) + H double accumulators (lm_imx_slot) and a token count.  Only
+// rca_lm_imatrix_chunk adds to them: it walks its tokens as rca_lm_score does -- passes of up to LM_MAXM rows on the 128-token tiles,
+// enqueued eagerly, the last position's logits behind the last pass -- with the pass's LmTilePass::imx set, so lm_enqueue_layers128
+// sums every projection's input planes right behind the launch that wrote them, and sums the final norm's planes of all live rows for
+// output.weight.  No per-block head GEMM runs.  Every other call builds its passes with imx null and leaves sums and count alone.
+static long lm_imx_values(const rca_lm_config_t& c) { int K; return lm_imx_slot(c, 0, 4, &K) + K; }
+extern "C" int rca_lm_imatrix_begin(rca_lm_t* h) {
+    if (!h) return fail(RCA_ERR_ARG, "imatrix_begin: null handle");
+    if (h->imx_acc) return fail(RCA_ERR_STATE, "imatrix_begin: the handle is already collecting (rca_lm_imatrix_end ends a collection)");
+    if (lm_score_route(h) != LM_ROUTE_TILE128)
+        return fail(RCA_ERR_STATE, "imatrix_begin: the handle's long evals do not take the 128-token tiles (%s): the collector sums the tiles' input planes",
+                    h->mfma_prefill ? "its weights or dimensions are off them" : "rca_lm_set_mfma_prefill is off");
+    int rc;
+    if ((rc = lm_settle(h)) != RCA_OK) return rc;
+    RCA_HIP(hipSetDevice(h->device));
+    const size_t nb = (size_t)lm_imx_values(h->cfg) * 8;
+    double* acc = nullptr;
+    if ((rc = lm_alloc((void**)&acc, nb)) != RCA_OK) return rc;
+    hipError_t e = hipMemsetAsync(acc, 0, nb, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { (void)hipFree(acc); return fail(RCA_ERR_HIP, "imatrix_begin: %s", hipGetErrorString(e)); }
+    h->imx_acc = acc;
+    h->imx_count = 0;
+    h->imx_tap_layer = h->imx_tap_kind = -1;
+    return RCA_OK;
+}
+extern "C" int rca_lm_imatrix_end(rca_lm_t* h) {
+    if (!h) return fail(RCA_ERR_ARG, "imatrix_end: null handle");
+    if (!h->imx_acc) return RCA_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(h->imx_acc);
+    h->imx_acc = nullptr;
+    h->imx_count = 0;
+    return RCA_OK;
+}
+static int lm_imatrix_chunk_impl(rca_lm* h, const char* who, const int32_t* ids, int n) {
+    if (n < 1 || !ids) return fail(RCA_ERR_ARG, "%s: bad argument (n = %d tokens)", who, n);
+    if (!h->imx_acc) return fail(RCA_ERR_STATE, "%s: the handle is not collecting (rca_lm_imatrix_begin starts a collection)", who);
+    const rca_lm_config_t& c = h->cfg;
+    if (h->n_tokens + n > c.n_ctx) return fail(RCA_ERR_STATE, "%s: context overflow: %d + %d > n_ctx %d", who, h->n_tokens, n, c.n_ctx);
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= c.vocab_size)
+            return fail(RCA_ERR_ARG, "%s: token id %d at index %d is outside the vocabulary [0, %d)", who, ids[i], i, c.vocab_size);
+    if (lm_score_route(h) != LM_ROUTE_TILE128)
+        return fail(RCA_ERR_STATE, "%s: the handle's long evals no longer take the 128-token tiles (rca_lm_set_mfma_prefill is off)", who);
+    int rc;
+    if ((rc = lm_settle(h)) != RCA_OK) return rc;
+    RCA_HIP(hipSetDevice(h->device));
+    if ((rc = lm_score_reserve_pin(h, lm_score_pin_bytes(n, LM_MAXM))) != RCA_OK) return rc;
+    hipStream_t st = h->stream;
+    size_t pin_off = 0;
+    for (int off = 0; off < n; off += LM_MAXM) {
+        const int m = std::min((int)LM_MAXM, n - off);
+        if ((rc = lm_score_push(h, &pin_off, ids + off, m, st)) != RCA_OK) return rc;
+        if ((rc = lm_enqueue_prefill_tile128(h, m, st, lm_splits_needed(h, m), nullptr, h->imx_acc)) != RCA_OK) return rc;
+        if (off + m >= n) lm_launch_head(h, 1, st, h->logits, true);   // the last position's logits, as rca_lm_score leaves them
+        lm_add_rmsnorm_kernel<<<m, 64, 0, st>>>(h->stt, h->x, nullptr, nullptr, 0, 0, h->final_norm, h->xn, c.hidden, c.rms_eps, h->xh, h->xl);
+        lm_collect_planes(LmTilePass{h, h->stt, m, (int)cdiv(m, 128), nullptr, g128_seq_min(), h->imx_acc}, st, 0, 4, h->xh, h->xl);
+        RCA_LAUNCH_CHECK();
+        h->n_tokens += m;
+    }
+    h->logits_rows = 1;
+    RCA_HIP(hipStreamSynchronize(st));
+    h->imx_count += n;
+    return RCA_OK;
+}
+extern "C" int rca_lm_imatrix_chunk(rca_lm_t* h, const int32_t* ids, int32_t n) {
+    if (!h) return fail(RCA_ERR_ARG, "imatrix_chunk: null handle");
+    return lm_imatrix_chunk_impl(h, "imatrix_chunk", ids, n);
+}
+// tests only: one pass of the call above with the planes of (layer, kind) copied right behind their collection launch
+extern "C" int rca_lm_imatrix_chunk_tap(rca_lm_t* h, const int32_t* ids, int32_t n, int32_t layer, int32_t kind, uint16_t* xh_out, uint16_t* xl_out) {
+    if (!h || !xh_out || !xl_out) return fail(RCA_ERR_ARG, "imatrix_chunk_tap: null pointer");
+    if (n > LM_MAXM) return fail(RCA_ERR_ARG, "imatrix_chunk_tap: %d tokens are more than one pass of %d", n, LM_MAXM);
+    int K = 0;
+    if (lm_imx_slot(h->cfg, layer, kind, &K) < 0) return fail(RCA_ERR_ARG, "imatrix_chunk_tap: no layer %d / kind %d (%d layers, kinds 0 .. 4)", layer, kind, h->cfg.n_layers);
+    if (n < 1) return fail(RCA_ERR_ARG, "imatrix_chunk_tap: bad argument (n = %d tokens)", n);
+    RCA_HIP(hipSetDevice(h->device));
+    const size_t nb = (size_t)n * K * 2;
+    int rc;
+    if ((rc = lm_alloc((void**)&h->imx_tap_h, nb)) == RCA_OK && (rc = lm_alloc((void**)&h->imx_tap_l, nb)) == RCA_OK) {
+        h->imx_tap_layer = layer;
+        h->imx_tap_kind = kind;
+        rc = lm_imatrix_chunk_impl(h, "imatrix_chunk_tap", ids, n);
+        h->imx_tap_layer = h->imx_tap_kind = -1;
+        if (rc == RCA_OK) {   // (the call has waited for the stream)
+            hipError_t e = hipMemcpy(xh_out, h->imx_tap_h, nb, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(xl_out, h->imx_tap_l, nb, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(RCA_ERR_HIP, "imatrix_chunk_tap: %s", hipGetErrorString(e));
+        }
+    }
+    for (bf16_t** p : {&h->imx_tap_h, &h->imx_tap_l}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    return rc;
+}
+extern "C" int rca_lm_imatrix_get(rca_lm_t* h, int32_t layer, int32_t kind, double* sums_out, int32_t K, int64_t* count_out) {
+    if (!h || !sums_out) return fail(RCA_ERR_ARG, "imatrix_get: null pointer");
+    if (!h->imx_acc) return fail(RCA_ERR_STATE, "imatrix_get: the handle is not collecting (rca_lm_imatrix_begin starts a collection)");
+    int want = 0;
+    const long off = lm_imx_slot(h->cfg, layer, kind, &want);
+    if (off < 0) return fail(RCA_ERR_ARG, "imatrix_get: no layer %d / kind %d (%d layers, kinds 0 .. 4)", layer, kind, h->cfg.n_layers);
+    if (K != want) return fail(RCA_ERR_ARG, "imatrix_get: K = %d, but kind %d has a width of %d", K, kind, want);
+    int rc;
+    if ((rc = lm_settle(h)) != RCA_OK) return rc;
+    RCA_HIP(hipSetDevice(h->device));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    RCA_HIP(hipMemcpy(sums_out, h->imx_acc + off, (size_t)K * 8, hipMemcpyDeviceToHost));
+    if (count_out) *count_out = h->imx_count;
     return RCA_OK;
 }
 

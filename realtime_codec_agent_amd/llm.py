@@ -511,6 +511,69 @@ class LlamaForAlternatingCodeChannels:
                 "rca_lm_imatrix_rows_tap")
         return out
 
+    # ------------------------------------------------------------------ importance matrix (rca_lm_imatrix_*; imatrix.collect walks a corpus)
+    def imatrix_begin(self) -> None:
+        """Start collecting an importance matrix on this handle (its own accumulators, zeroed).  Only imatrix_chunk() adds to them."""
+        N.check(self._lib.rca_lm_imatrix_begin(self._h), "rca_lm_imatrix_begin")
+
+    def imatrix_end(self) -> None:
+        """Free the accumulators (close() does too)."""
+        N.check(self._lib.rca_lm_imatrix_end(self._h), "rca_lm_imatrix_end")
+
+    def imatrix_chunk(self, tokens: Sequence[int]) -> None:
+        """Append `tokens` at n_tokens as score() does, on the 128-token tiles, summing every projection's input planes; context, K / V
+        rows and the last position's logits are left as score() leaves them."""
+        arr = np.ascontiguousarray(tokens, dtype=np.int32).reshape(-1)
+        if arr.size == 0:
+            return
+        n0 = self.n_tokens
+        N.check(self._lib.rca_lm_imatrix_chunk(self._h, arr.ctypes.data, int(arr.size)), "rca_lm_imatrix_chunk")
+        self._input_ids[n0:n0 + arr.size] = arr
+        self._logits_valid = False
+
+    def _imatrix_width(self, kind: int) -> int:
+        c = self.config
+        return {1: c.n_heads * c.head_dim, 3: c.ffn}.get(int(kind), c.hidden)
+
+    def imatrix_chunk_tap(self, tokens: Sequence[int], layer: int, kind: int):
+        """Tests only (rca_lm_imatrix_chunk_tap): imatrix_chunk() for one pass; returns the planes (xh, xl) [n, K] (uint16 bf16 bits) of
+        (layer, kind) as they stood right behind their collection launch."""
+        arr = np.ascontiguousarray(tokens, dtype=np.int32).reshape(-1)
+        K = self._imatrix_width(kind)
+        xh, xl = np.zeros((max(arr.size, 1), K), np.uint16), np.zeros((max(arr.size, 1), K), np.uint16)
+        n0 = self.n_tokens
+        N.check(self._lib.rca_lm_imatrix_chunk_tap(self._h, arr.ctypes.data, int(arr.size), int(layer), int(kind), xh.ctypes.data, xl.ctypes.data),
+                "rca_lm_imatrix_chunk_tap")
+        self._input_ids[n0:n0 + arr.size] = arr
+        self._logits_valid = False
+        return xh[:arr.size], xl[:arr.size]
+
+    def imatrix_get(self, layer: int, kind: int, width: Optional[int] = None):
+        """(sums float64 [K], token count) of one accumulator: kind 0 the attn_q / attn_k / attn_v input, 1 attn_output's, 2 ffn_gate /
+        ffn_up's, 3 ffn_down's, 4 output.weight's (layer ignored)."""
+        K = self._imatrix_width(kind) if width is None else int(width)
+        out, count = np.zeros(max(K, 1), np.float64), C.c_int64(0)
+        N.check(self._lib.rca_lm_imatrix_get(self._h, int(layer), int(kind), out.ctypes.data, K, C.byref(count)), "rca_lm_imatrix_get")
+        return out[:K], int(count.value)
+
+    def imatrix_read(self):
+        """The collection so far as an imatrix.Imatrix: 7 * n_layers + 1 entries under GGUF names, a shared vector under each of its
+        names, the head's under output.weight (the name quantize looks up, tied embeddings or not)."""
+        from .imatrix import KIND_NAMES, Imatrix
+        out = Imatrix()
+        for l in range(self.config.n_layers):
+            for kind, names in KIND_NAMES.items():
+                sums, count = self.imatrix_get(l, kind)
+                if not np.isfinite(sums).all():
+                    raise ValueError(f"imatrix_read: layer {l}, kind {kind} ({names[0]}): a sum is not finite")
+                for name in names:
+                    out[f"blk.{l}.{name}.weight"] = (sums.copy(), count)
+        sums, count = self.imatrix_get(0, 4)
+        if not np.isfinite(sums).all():
+            raise ValueError("imatrix_read: output.weight: a sum is not finite")
+        out["output.weight"] = (sums, count)
+        return out
+
     def score_rows_tap(self, logits: np.ndarray, targets: Sequence[int], base_logits: Optional[np.ndarray] = None) -> "ScoreResult":
         """Tests only (rca_lm_score_rows_tap): the row reduction of score() alone on host-supplied logits [M, n_vocab]."""
         logits = np.ascontiguousarray(logits, dtype=np.float32)
