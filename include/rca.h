@@ -838,9 +838,17 @@ int rca_lm_kv_read_q8(rca_lm_t* h, int32_t layer, int32_t pos0, int32_t n_pos, i
  * receives the M new K rows then the M new V rows of `layer`'s cache as raw fp16), 1 O (x [M][AO]), 2 gate/up (y = silu(g)*u [M][ffn]),
  * 3 down (x [M][ffn]), 4 head (layer ignored; y [M][V]).  For the residual-add stages (1, 3) the residual is zeroed first, so y is
  * the product alone.  Positions are n_tokens .. n_tokens+M-1; n_tokens is left as it was.  M is 1 or 2.  The handle's activation
- * buffers and the cache rows at those positions are overwritten. */
+ * buffers and the cache rows at those positions are overwritten.  For kinds 0, 2 and 4 the device region that is read back is filled
+ * with NaN before the launch, so an element the stage does not write comes back NaN (kinds 1 and 3 add to the zeroed residual: a
+ * skipped element comes back 0).  The head's temporary output carries a guard of 64 floats behind row M - 1: RCA_ERR_STATE when the
+ * launch changed it. */
 int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const float* x_host, int32_t M, float* y_host, int64_t y_numel,
                     uint16_t* kv_host);
+/* Tests only: the instance and grid of the last decode GEMV launch of the handle, recorded on the host (rca_lm_gemv_tap clears the
+ * record before its launch): form[0..7] = M, NIT (16-byte chunks per lane and wave), R (rows per batch), batches per workgroup, grid,
+ * format id of the matrix (rca_lm_weight_format's numbering, 4 = q6_k), ACT (0 f32 / 1 q8_1 activations), N (rows of the launch).  A
+ * stage of two launches (a layer that keeps V in a format of its own) leaves the second launch's record. */
+int rca_lm_gemv_tap_form(const rca_lm_t* h, int32_t* form);
 /* Tests only: the attention of ONE layer exactly as a pass launches it (the same launcher picks the kernel, the grid and the merge), for
  * M query tokens at positions n_tokens .. n_tokens+M-1 over whatever the layer's cache holds (rca_lm_kv_write).  q_host [M][n_heads*64]
  * f32 are the query rows after RoPE.  route 0: the decode launch (M 1..2, follows rca_lm_set_attn_fuse); 1: the prefill launch with f32

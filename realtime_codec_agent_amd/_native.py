@@ -523,6 +523,7 @@ ABI_SYMBOLS = [
     "rca_codec_decoder_layer_tap", "rca_quantize_rows", "rca_lm_gemm128_tap",
     "rca_quantize_rows_w", "rca_lm_imatrix_rows_tap",
     "rca_lm_imatrix_begin", "rca_lm_imatrix_chunk", "rca_lm_imatrix_get", "rca_lm_imatrix_end", "rca_lm_imatrix_chunk_tap",
+    "rca_lm_gemv_tap_form",
 ]
 
 

@@ -264,7 +264,8 @@ __global__ __launch_bounds__(64) void lm_add_rmsnorm_kernel(const LmDevState* __
 //     rows of 16 -- R * M / 4 + ... instead of R * M butterflies; lane 0 of row q then holds value i + (V/4)(q&1) + (V/2)(q>>1);
 //   * the 4 waves' sums meet in LDS (double-buffered by batch parity: one barrier per batch) and are added in wave order by
 //     the first V threads, which run the fused epilogue.
-// Any (R, batches per workgroup) gives the same bits: a value's reduction sequence does not depend on its slot.
+// Any (R, batches per workgroup) gives the same bits: a value's reduction sequence does not depend on its slot
+// (tests/test_gemv_gpu.py runs "4,1" and "8,4" against the defaults in child processes).
 //   PRO 1: prologue = RMSNorm of the residual row(s): each wave squares its own K range, the 4 partial sums are added in
 //          wave order; xs = (v * rstd) * norm_w.  only_last: the single row handled is the pass's last token (head).
 //   EPI 0: store (logits)          EPI 1: rows (2i, 2i+1) = (gate_i, up_i): h = silu(g) * u
@@ -569,7 +570,10 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
             const int c = lane + 64 * it;
             const int cc = cbase + (c < cn ? c : 0);
             const unsigned* sp = q8.sc + q8_sc_index(p0, cc >> 2, K >> 5);   // a batch never crosses a group of 8 pairs (R <= 16)
-            if (R / 2 >= 4) {   // four pairs per 16-byte load (groups are padded to 8 pairs: always in bounds and aligned)
+            // R = 16 only: four pairs per 16-byte load, one load per register half (groups are padded to 8 pairs: always in bounds and
+            // aligned).  At R = 8 such a load would span BOTH halves: the refill of the first half for batch b + 1 then replaced the
+            // scales of the second half of batch b before it was consumed ("Decode GEMVs alone"), so R = 8 loads per pair.
+            if (R / 2 >= 8) {
 #pragma unroll
                 for (int s4 = 0; s4 < R / 8; ++s4) {
                     if (4 * s4 < s_beg || 4 * s4 >= s_end) continue;
@@ -2400,6 +2404,7 @@ struct rca_lm {
     bool mfma_prefill = true;   // evals longer than LM_PREFILL_MIN tokens use the bf16 MFMA tiles
     bool fuse_attn = true;      // decode steps merge the attention splits inside the attention launch (rca_lm_set_attn_fuse)
     int act_format = 0;         // activations of the decode GEMVs over packed matrices: 0 f32, 1 q8_1 blocks + integer dots (rca_lm_set_act_format)
+    int gemv_last[8] = {};      // tests only (rca_lm_gemv_tap_form): M, NIT, R, batches per workgroup, grid, format, ACT and N of the last launch_gemv_r
     // weight sharing (rca_lm_create_shared): a borrower points at the handle that owns the weights and the RoPE tables; an owner
     // destroyed while borrowers are alive keeps those allocations (and its struct) until the last borrower is gone
     rca_lm* weights_of = nullptr;
@@ -3388,6 +3393,7 @@ static void launch_gemv_r(const GemvGeom& g, rca_lm* h, const WMat& w, const flo
                           const GemvRope& rope, hipStream_t st, const GemvGroup& grp = GemvGroup{nullptr, 0}) {
     const int grid = cdiv(cdiv(N, g.R), g.bpw);
     const GemvQ8 qa{w.qs, w.sc, w.dd};
+    if (h) { const int rec[8] = {M, NIT, g.R, g.bpw, grid, w.fmt, ACT, N}; memcpy(h->gemv_last, rec, sizeof rec); }   // host side only: what rca_lm_gemv_tap_form reports
     auto go = [&](auto rr) {
         constexpr int R = decltype(rr)::value;
         if constexpr (gemv_built(M, NIT, R, Q)) {
@@ -8002,7 +8008,14 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
     const float* yd = nullptr;
     int ldy = out_w[kind];
     float* head_out = nullptr;
+    // The region read back is filled with NaN (all bits set) before the launch: an element the stage does not write comes back as NaN.
+    // Kinds 1 and 3 add to a residual that must be zero, so they cannot be pre-filled: there the caller uses data whose every output
+    // is non-zero.  The head's temporary buffer carries a guard of GEMV_TAP_GUARD floats of another pattern behind row M - 1.
+    constexpr int GEMV_TAP_GUARD = 64;
+    constexpr unsigned GEMV_TAP_SENTINEL = 0x7fa5a5a5u;   // a NaN with a payload no kernel produces
+    memset(h->gemv_last, 0, sizeof h->gemv_last);
     if (kind == 0) {
+        RCA_HIP(hipMemsetAsync(h->qkv, 0xff, (size_t)M * QKV * 4, st));
         lm_launch_qkv(h, layer, M, st);
         yd = h->qkv; ldy = QKV;
     } else if (kind == 1) {
@@ -8010,6 +8023,7 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
         lm_launch_o(h, layer, M, st);
         yd = h->x;
     } else if (kind == 2) {
+        RCA_HIP(hipMemsetAsync(h->hbuf, 0xff, (size_t)M * F * 4, st));
         lm_launch_gu(h, layer, M, st);
         yd = h->hbuf;
     } else if (kind == 3) {
@@ -8017,11 +8031,16 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
         lm_launch_down(h, layer, M, st);
         yd = h->x;
     } else {
-        if ((rc = lm_alloc((void**)&head_out, (size_t)M * V * 4)) != RCA_OK) return rc;   // the handle's own logits buffer may hold one row only
+        if ((rc = lm_alloc((void**)&head_out, ((size_t)M * V + GEMV_TAP_GUARD) * 4)) != RCA_OK) return rc;   // the handle's own logits buffer may hold one row only
+        hipError_t eh = hipMemsetAsync(head_out, 0xff, (size_t)M * V * 4, st);
+        if (eh == hipSuccess) eh = hipMemsetD32Async((hipDeviceptr_t)(head_out + (size_t)M * V), (int)GEMV_TAP_SENTINEL, GEMV_TAP_GUARD, st);
+        if (eh != hipSuccess) { (void)hipFree(head_out); return fail(RCA_ERR_HIP, "gemv_tap: %s", hipGetErrorString(eh)); }
         lm_launch_head(h, M, st, head_out, false);
         yd = head_out;
     }
+    unsigned guard[GEMV_TAP_GUARD];
     hipError_t e = hipGetLastError();
+    if (e == hipSuccess && head_out) e = hipMemcpyAsync(guard, head_out + (size_t)M * V, sizeof guard, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpy2DAsync(y_host, (size_t)out_w[kind] * 4, yd, (size_t)ldy * 4, (size_t)out_w[kind] * 4, M, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && kind == 0 && kv_host && lm_kv_q8(h)) {   // the de-quantised rows, as rca_lm_kv_read gives them
         const size_t n = (size_t)M * c.n_kv_heads * 64;
@@ -8037,6 +8056,17 @@ extern "C" int rca_lm_gemv_tap(rca_lm_t* h, int32_t layer, int32_t kind, const f
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (head_out) (void)hipFree(head_out);
     if (e != hipSuccess) return fail(RCA_ERR_HIP, "gemv_tap: %s", hipGetErrorString(e));
+    if (kind == 4)
+        for (int i = 0; i < GEMV_TAP_GUARD; ++i)
+            if (guard[i] != GEMV_TAP_SENTINEL) return fail(RCA_ERR_STATE, "gemv_tap: the head wrote behind row %d of its output: guard float %d holds 0x%08x", M - 1, i, guard[i]);
+    return RCA_OK;
+}
+// tests only: the instance and grid of the last decode GEMV the handle launched (rca_lm_gemv_tap sets the record to zeros before its
+// launch): M, NIT, R, batches per workgroup, grid, format id (WF_*), ACT, N.  A stage of two launches (a layer that keeps V apart)
+// leaves the second one's.
+extern "C" int rca_lm_gemv_tap_form(const rca_lm_t* h, int32_t* form) {
+    if (!h || !form) return fail(RCA_ERR_ARG, "null");
+    for (int i = 0; i < 8; ++i) form[i] = h->gemv_last[i];
     return RCA_OK;
 }
 // tests only: the attention of one layer alone, launched by the very call the passes make for it (launch_attention_mfma), for M host-supplied

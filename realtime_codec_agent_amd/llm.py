@@ -366,6 +366,12 @@ class LlamaForAlternatingCodeChannels:
                                           kv.ctypes.data_as(C.POINTER(C.c_uint16)) if kv is not None else None), "rca_lm_gemv_tap")
         return (y, kv[0], kv[1]) if kv is not None else y
 
+    def gemv_tap_form(self) -> dict:
+        """Tests only (rca_lm_gemv_tap_form): the instance and grid of the handle's last decode GEMV launch."""
+        form = (C.c_int32 * 8)()
+        N.check(self._lib.rca_lm_gemv_tap_form(self._h, form), "rca_lm_gemv_tap_form")
+        return dict(zip(("M", "NIT", "R", "batches", "grid", "format", "ACT", "N"), (int(v) for v in form)))
+
     def _query_format(self):
         fmt, nbytes = C.c_int32(), C.c_int64()
         N.check(self._lib.rca_lm_weight_format(self._h, C.byref(fmt), C.byref(nbytes)), "rca_lm_weight_format")
