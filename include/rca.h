@@ -481,7 +481,9 @@ int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b);
  * n_tokens - delta; rows at and above it are stale, the last logits stay readable, as after rca_lm_set_n_tokens.  delta == 0 and
  * p1 == n_tokens (pure truncation) launch nothing.  Runs on the handle's stream and returns after one synchronisation; captured step /
  * frame / duplex graphs stay valid (the cache does not move and positions come from the device state).  The first call that moves
- * rows allocates a staging buffer of 2 x 2 x n_layers x 256 cache rows, freed with the handle. */
+ * rows allocates a staging buffer of 2 x 2 x n_layers x 256 cache rows, freed with the handle.
+ * A q8_0 handle (rca_lm_set_kv_format) refuses the call (RCA_ERR_STATE, nothing touched) unless rca_lm_set_kv_shift_requant(h, 1)
+ * has allowed it; then everything above holds with the rows as blocks, under the contract stated at rca_lm_set_kv_shift_requant. */
 int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1);
 /* The context shift of several handles in one pass: every hs[k] ends exactly as rca_lm_kv_remove(hs[k], p0[k], p1[k]) would leave it,
  * bit for bit -- n_tokens, the K / V rows [0, n_tokens) of every layer, the last logits still readable, captured step / frame / duplex /
@@ -496,7 +498,10 @@ int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1);
  * they are processed in launch groups of RCA_LM_KV_REMOVE_GROUP.  Takes handles, not a batch: it does not need the 128-token tile route.
  * Refused before anything is enqueued, no handle changed, the message naming k: RCA_ERR_ARG for n_h outside 1..64, a null or repeated
  * handle, a handle on another device than hs[0], a handle that does not share hs[0]'s weights (the parent and its
- * rca_lm_create_shared twins do), a span with p0 < 0, p0 > p1 or p1 > n_tokens; RCA_ERR_STATE for a handle with a q8_0 KV cache. */
+ * rca_lm_create_shared twins do), a span with p0 < 0, p0 > p1 or p1 > n_tokens; RCA_ERR_STATE for a handle with a q8_0 KV cache that
+ * rca_lm_set_kv_shift_requant has not allowed to shift; then RCA_ERR_ARG for a handle whose KV format differs from hs[0]'s (one
+ * launch runs one unit body).  Over q8_0 handles with the permission the call is the same schedule over blocks: each handle ends with
+ * the bits of its own rca_lm_kv_remove, and the staging buffers are the ones described above (a block row needs 68 of their 128 bytes). */
 #define RCA_LM_KV_REMOVE_GROUP 8
 int rca_lm_kv_remove_many(rca_lm_t* const* hs, int32_t n_h, const int32_t* p0, const int32_t* p1);
 /* Tests and measurements: rca_lm_kv_remove_many with every handle on the staged route, whatever its delta.  Same contract, same bits. */
@@ -822,11 +827,28 @@ int rca_lm_get_act_format(const rca_lm_t* h, int32_t* fmt);
  * for all layers, about 2 MB at 8 kv heads) and one small launch per layer quantises the rows of the pass before attention runs.
  * Every eval / step / frame / score / duplex / group / batch call works on a q8_0 handle.  rca_lm_copy_kv / rca_lm_swap_kv between
  * handles of different formats, and groups or batches whose members differ in format, are refused.  rca_lm_kv_remove on a q8_0 handle
- * is refused (RCA_ERR_STATE, n_tokens unchanged): re-rotating quantised keys would quantise them a second time.
+ * is refused (RCA_ERR_STATE, n_tokens unchanged): re-rotating quantised keys would quantise them a second time -- unless that has been
+ * asked for by name (rca_lm_set_kv_shift_requant below).  rca_lm_set_kv_format(h, 0) clears that permission.
  * Tests-only calls on a q8_0 handle: rca_lm_kv_write quantises the given fp16 rows with the kernel the passes use; rca_lm_kv_read and
  * rca_lm_gemv_tap's kv_host return the de-quantised fp16 rows, exactly the values attention stages; rca_lm_kv_read_q8 the raw blocks. */
 int rca_lm_set_kv_format(rca_lm_t* h, int32_t fmt);
 int rca_lm_get_kv_format(const rca_lm_t* h, int32_t* fmt);
+/* Opt-in: the context shift (rca_lm_kv_remove, rca_lm_kv_remove_many, rca_lm_kv_remove_many_staged) on a q8_0 KV cache, what llama.cpp's
+ * K-shift does on a quantised cache: de-quantise, rotate, re-quantise.  on = 1 allows it, 0 (default) keeps the refusal.  A permission
+ * only: allowed at any n_tokens, no cache is touched, no graph is dropped.  RCA_ERR_ARG for another value, RCA_ERR_STATE on an fp16
+ * handle.  rca_lm_create_shared copies the parent's value; rca_lm_set_kv_format(h, 0) clears it.
+ * CONTRACT of a shifted q8_0 cache (positions, n_tokens, stale rows, logits, graphs, the one synchronisation: as rca_lm_kv_remove):
+ *   V rows: the two blocks of every moved head row (64 int8 + 2 fp16 scales) are copied bit for bit.
+ *   K rows: x = fp16_rne((float)d16 * q) is the de-quantised row, the one attention stages.  The new row is Q8(fp16_rne(R(x))) with R the
+ *     rotation of rca_lm_kv_remove (the pair at elements j and j + 32, in f32, rows `delta` of the handle's cos / sin tables, the same
+ *     sequence of f32 operations as on an fp16 cache) and Q8 the RULE above: per block of 32, d = amax / 127, inv = d != 0 ? 1 / d : 0,
+ *     q = roundf(y * inv), d16 = fp16_rne(d).
+ *   So a shifted q8_0 cache holds exactly what an fp16 cache holding the de-quantised rows would hold after its own rca_lm_kv_remove,
+ *   quantised; "cache row == Q8(an fp16 row)" survives any number of shifts, and every shift costs the surviving keys one fp16
+ *   rounding, as on the fp16 cache, PLUS one q8_0 quantisation (about 2^-8 of the block's largest value) -- the price this switch names.
+ *   A row whose de-quantised values or rotation are not finite is treated as the quantiser treats such an fp16 row. */
+int rca_lm_set_kv_shift_requant(rca_lm_t* h, int32_t on);
+int rca_lm_get_kv_shift_requant(const rca_lm_t* h, int32_t* on);
 /* bytes one cached position takes in the handle's KV format (all layers, K and V); ring_positions (may be NULL): positions of the
  * fp16 staging ring of a q8_0 cache, 0 for an fp16 cache */
 int rca_lm_kv_bytes_per_position(const rca_lm_t* h, int64_t* bytes, int32_t* ring_positions);

@@ -524,6 +524,7 @@ ABI_SYMBOLS = [
     "rca_quantize_rows_w", "rca_lm_imatrix_rows_tap",
     "rca_lm_imatrix_begin", "rca_lm_imatrix_chunk", "rca_lm_imatrix_get", "rca_lm_imatrix_end", "rca_lm_imatrix_chunk_tap",
     "rca_lm_gemv_tap_form",
+    "rca_lm_set_kv_shift_requant", "rca_lm_get_kv_shift_requant",
 ]
 
 

@@ -2349,6 +2349,7 @@ struct rca_lm {
                                          // behind it, the fp16 scales [L][n_ctx_pad][nkv][2] -- so whatever exchanges or keys caches by these two
                                          // pointers (rca_lm_swap_kv, the graph sets, rca_duplex_precapture) holds for either format
     int kv_format = 0;                   // 0 fp16, 1 q8_0 (rca_lm_set_kv_format)
+    int kv_shift_requant = 0;            // q8_0 only: rca_lm_kv_remove may re-quantise the rotated keys (rca_lm_set_kv_shift_requant); a permission, no state
     f16_t *ring_k = nullptr, *ring_v = nullptr;   // q8_0: [LM_KV_RING][nkv][64] fp16 rows of the current pass and layer, what the QKV epilogues store
     f16_t* kv_stage = nullptr;           // rca_lm_kv_remove: two slabs of [K, V][L][ATT_KEYS][nkv][hd], allocated by the first call that moves rows
     f16_t* kv_stage_many = nullptr;      // rca_lm_kv_remove_many, on the weight OWNER only: RCA_LM_KV_REMOVE_GROUP such pairs of slabs, allocated by the first
@@ -3323,6 +3324,7 @@ extern "C" int rca_lm_create_shared(rca_lm_t* parent, int32_t n_ctx, int32_t log
     h->mfma_prefill = parent->mfma_prefill;
     h->act_format = parent->act_format;
     h->kv_format = parent->kv_format;   // (lm_common_init below allocates the cache in it)
+    h->kv_shift_requant = parent->kv_shift_requant;
     owner->borrowers++;
     if ((rc = lm_common_init(h, nullptr, 0, owner)) != RCA_OK) { rca_lm_destroy(h); return rc; }
     *out = h;
@@ -5640,6 +5642,16 @@ extern "C" int rca_lm_swap_kv(rca_lm_t* a, rca_lm_t* b) {
 // The body of one unit, shared by the single-handle kernel and the table form (rca_lm_kv_remove_many) so that a row's bits cannot
 // differ between them.  stage_w == nullptr is the direct route of the table form: the rotated rows go straight to cache rows
 // dst_pos + r (the host has shown that they are disjoint from every source row of the launch) and there are no kind-B units.
+// The rotation of one RoPE pair (x1 at element j, x2 at element j + 32) by -delta positions, c / s = cos / sin of the table row
+// `delta`: the inverse of the epilogues' x1 c - x2 s, x2 c + x1 s.  ONE helper for the fp16 unit and the q8_0 unit, its four products
+// and two sums spelled as separate f32 operations that may not be contracted, so that the two instantiations round alike: a q8_0
+// cache shifts to Q8 of what an fp16 cache holding its de-quantised rows shifts to, bit for bit.
+static __device__ __forceinline__ void lm_kv_unrotate(const float x1, const float x2, const float c, const float s, float& o1, float& o2) {
+#pragma clang fp contract(off)
+    const float x1c = x1 * c, x2s = x2 * s, x2c = x2 * c, x1s = x1 * s;
+    o1 = x1c + x2s;
+    o2 = x2c - x1s;
+}
 static __device__ __forceinline__ void lm_kv_shift_unit(f16_t* kc, f16_t* vc, f16_t* stage_w, const f16_t* stage_r,
                                                         const float* cos_d, const float* sin_d, long layer_stride, int n_layers, int nkv,
                                                         int src_pos, int n_src, int dst_pos, int n_dst, long u, long ua) {
@@ -5665,9 +5677,10 @@ static __device__ __forceinline__ void lm_kv_shift_unit(f16_t* kc, f16_t* vc, f1
         f16x8 o1, o2;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float x1 = (float)k1[j], x2 = (float)k2[j];
-            o1[j] = (f16_t)(x1 * c[j] + x2 * s[j]);       // the inverse of the epilogues' x1 c - x2 s, x2 c + x1 s; f32, then fp16 nearest-even
-            o2[j] = (f16_t)(x2 * c[j] - x1 * s[j]);
+            float r1, r2;
+            lm_kv_unrotate((float)k1[j], (float)k2[j], c[j], s[j], r1, r2);
+            o1[j] = (f16_t)r1;                            // f32, then fp16 nearest-even
+            o2[j] = (f16_t)r2;
         }
         const long cd = (long)l * layer_stride + ((long)(dst_pos + r) * nkv + kvh) * 64 + q * 8;
         f16_t* kw = stage_w ? stage_w + so : kc + cd;
@@ -5711,9 +5724,118 @@ __global__ __launch_bounds__(256) void lm_kv_shift_many_kernel(const LmShiftTabl
     for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < ua + ub; u += (long)gridDim.x * 256)
         lm_kv_shift_unit(w.kc, w.vc, w.stage_w, w.stage_r, w.cos_d, w.sin_d, w.layer_stride, n_layers, nkv, w.src_pos, w.n_src, w.dst_pos, w.n_dst, u, ua);
 }
+// ---- the context shift of a q8_0 cache (opt-in: rca_lm_set_kv_shift_requant).  Host schedule, slabs, unit numbering and the proofs
+// that a launch reads no byte it writes are those of the fp16 shift above -- they speak of cache POSITIONS, and a position's int8
+// rows and scale pairs move together; only the unit body and the addressing differ.
+//   V: the 64 int8 and the two fp16 scales of every moved head row, bit for bit.
+//   K: x = fp16_rne((float)d16 * q), the row attention stages (kvq8_deq16's arithmetic); y = fp16_rne(lm_kv_unrotate(x)), the row an
+//      fp16 cache holding x would hold after its own shift; new blocks = Q8(y) by lm_kv_quant_kernel's arithmetic, operation for
+//      operation.  So "cache row == Q8(an fp16 row)" survives any number of shifts, and each shift costs the surviving keys one fp16
+//      rounding (as on the fp16 cache) plus one q8_0 quantisation.  Non-finite x or y: whatever lm_kv_quant_kernel makes of such a row.
+// Unit = thread = (layer, row of the slab, kv head, quarter q) as above: bytes q * 8 .. q * 8 + 7 of block 0 and of block 1 (8-byte
+// loads and stores; lane-per-value, the quantiser's own mapping, would move single bytes), which are each other's RoPE partners, so a
+// thread needs both scales of the head and no value of another thread.  The four threads of a head row are four neighbouring lanes
+// with neighbouring unit numbers (unit counts are multiples of 4): they leave the loop together and take the same branch, and the
+// block maxima are reduced over them with two shuffles of width 4.  V: 16 bytes per thread; thread 0 of a row moves the K scale pair,
+// thread 1 the V scale pair.
+// kc / vc: the tensor's allocation (int8 planes [L][n_ctx_pad][nkv][64], the scale planes [L][n_ctx_pad][nkv][2] n_layers * layer_stride
+// bytes behind).  A staging slab holds finished blocks: K int8 [L][ATT_KEYS][nkv][64], V int8, K scale pairs, V scale pairs -- 136
+// bytes per head row inside the 256 the fp16 slab has.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+static __device__ __forceinline__ void lm_kv_shift_unit_q8(char* kc, char* vc, char* stage_w, const char* stage_r,
+                                                           const float* cos_d, const float* sin_d, long layer_stride, int n_layers, int nkv,
+                                                           int src_pos, int n_src, int dst_pos, int n_dst, long u, long ua) {
+    const long srows = (long)n_layers * ATT_KEYS * nkv;          // head rows of a staging slab
+    const long sc_off = (long)n_layers * layer_stride;           // bytes from the int8 planes to the scale planes
+    const long s_vq = srows * 64, s_kd = srows * 128, s_vd = srows * 132;
+    const bool rot = u < ua;
+    long t = rot ? u : u - ua;
+    const int npos = rot ? n_src : n_dst;
+    const int q = (int)(t & 3);
+    t >>= 2;
+    const int kvh = (int)(t % nkv);
+    t /= nkv;
+    const int r = (int)(t % npos), l = (int)(t / npos);
+    const long sr = ((long)l * ATT_KEYS + r) * nkv + kvh;                                                       // head row in a slab
+    const long cr = (long)l * (layer_stride >> 6) + (long)((rot ? src_pos : dst_pos) + r) * nkv + kvh;          // head row in the cache
+    if (rot) {
+        const u32x2 a = *reinterpret_cast<const u32x2*>(kc + cr * 64 + q * 8), b = *reinterpret_cast<const u32x2*>(kc + cr * 64 + 32 + q * 8);
+        const f16x2 kd = *reinterpret_cast<const f16x2*>(kc + sc_off + cr * 4);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(vc + cr * 64 + q * 16);
+        const unsigned vd = *reinterpret_cast<const unsigned*>(vc + sc_off + cr * 4);
+        float c[8], s[8];
+        *reinterpret_cast<f32x4*>(c) = *reinterpret_cast<const f32x4*>(cos_d + q * 8);
+        *reinterpret_cast<f32x4*>(c + 4) = *reinterpret_cast<const f32x4*>(cos_d + q * 8 + 4);
+        *reinterpret_cast<f32x4*>(s) = *reinterpret_cast<const f32x4*>(sin_d + q * 8);
+        *reinterpret_cast<f32x4*>(s + 4) = *reinterpret_cast<const f32x4*>(sin_d + q * 8 + 4);
+        const float d0 = (float)kd[0], d1 = (float)kd[1];
+        float y1[8], y2[8], am0 = 0.0f, am1 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float x1 = (float)(_Float16)((float)(int)(signed char)(a[j >> 2] >> (8 * (j & 3))) * d0);      // kvq8_deq16
+            const float x2 = (float)(_Float16)((float)(int)(signed char)(b[j >> 2] >> (8 * (j & 3))) * d1);
+            float r1, r2;
+            lm_kv_unrotate(x1, x2, c[j], s[j], r1, r2);
+            y1[j] = (float)(f16_t)r1;                                                                           // the fp16 row, widened as the quantiser reads it
+            y2[j] = (float)(f16_t)r2;
+            am0 = j ? fmaxf(am0, fabsf(y1[j])) : fabsf(y1[j]);
+            am1 = j ? fmaxf(am1, fabsf(y2[j])) : fabsf(y2[j]);
+        }
+#pragma unroll
+        for (int o = 2; o >= 1; o >>= 1) {
+            am0 = fmaxf(am0, __shfl_xor(am0, o, 4));
+            am1 = fmaxf(am1, __shfl_xor(am1, o, 4));
+        }
+        // lm_kv_quant_kernel's arithmetic per block
+        const float e0 = am0 / 127.0f, e1 = am1 / 127.0f;
+        const float inv0 = e0 != 0.0f ? 1.0f / e0 : 0.0f, inv1 = e1 != 0.0f ? 1.0f / e1 : 0.0f;
+        u32x2 oa = {0u, 0u}, ob = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            oa[j >> 2] |= (unsigned)(unsigned char)(signed char)(int)roundf(y1[j] * inv0) << (8 * (j & 3));
+            ob[j >> 2] |= (unsigned)(unsigned char)(signed char)(int)roundf(y2[j] * inv1) << (8 * (j & 3));
+        }
+        f16x2 od;
+        od[0] = (f16_t)e0;
+        od[1] = (f16_t)e1;
+        const long cd = (long)l * (layer_stride >> 6) + (long)(dst_pos + r) * nkv + kvh;
+        char* kqw = stage_w ? stage_w + sr * 64 : kc + cd * 64;
+        char* vqw = stage_w ? stage_w + s_vq + sr * 64 : vc + cd * 64;
+        char* kdw = stage_w ? stage_w + s_kd + sr * 4 : kc + sc_off + cd * 4;
+        char* vdw = stage_w ? stage_w + s_vd + sr * 4 : vc + sc_off + cd * 4;
+        *reinterpret_cast<u32x2*>(kqw + q * 8) = oa;
+        *reinterpret_cast<u32x2*>(kqw + 32 + q * 8) = ob;
+        *reinterpret_cast<u32x4*>(vqw + q * 16) = v;
+        if (q == 0) *reinterpret_cast<f16x2*>(kdw) = od;
+        if (q == 1) *reinterpret_cast<unsigned*>(vdw) = vd;
+    } else {
+        const u32x2 a = *reinterpret_cast<const u32x2*>(stage_r + sr * 64 + q * 8), b = *reinterpret_cast<const u32x2*>(stage_r + sr * 64 + 32 + q * 8);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(stage_r + s_vq + sr * 64 + q * 16);
+        *reinterpret_cast<u32x2*>(kc + cr * 64 + q * 8) = a;
+        *reinterpret_cast<u32x2*>(kc + cr * 64 + 32 + q * 8) = b;
+        *reinterpret_cast<u32x4*>(vc + cr * 64 + q * 16) = v;
+        if (q == 0) *reinterpret_cast<unsigned*>(kc + sc_off + cr * 4) = *reinterpret_cast<const unsigned*>(stage_r + s_kd + sr * 4);
+        if (q == 1) *reinterpret_cast<unsigned*>(vc + sc_off + cr * 4) = *reinterpret_cast<const unsigned*>(stage_r + s_vd + sr * 4);
+    }
+}
+__global__ __launch_bounds__(256) void lm_kv_shift_q8_kernel(char* kc, char* vc, char* __restrict__ stage_w, const char* __restrict__ stage_r,
+                                                             const float* __restrict__ cos_d, const float* __restrict__ sin_d,
+                                                             long layer_stride, int n_layers, int nkv, int src_pos, int n_src, int dst_pos, int n_dst) {
+    const long ua = (long)n_layers * n_src * nkv * 4, ub = (long)n_layers * n_dst * nkv * 4;
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < ua + ub; u += (long)gridDim.x * 256)
+        lm_kv_shift_unit_q8(kc, vc, stage_w, stage_r, cos_d, sin_d, layer_stride, n_layers, nkv, src_pos, n_src, dst_pos, n_dst, u, ua);
+}
+// the table form over q8_0 handles: LmShiftRow's pointers are the allocations of the q8_0 cache and of the staging slabs, taken as bytes
+__global__ __launch_bounds__(256) void lm_kv_shift_many_q8_kernel(const LmShiftTable tab, int n_layers, int nkv) {
+    const LmShiftRow& w = tab.row[blockIdx.y];
+    const long ua = (long)n_layers * w.n_src * nkv * 4, ub = (long)n_layers * w.n_dst * nkv * 4;
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < ua + ub; u += (long)gridDim.x * 256)
+        lm_kv_shift_unit_q8(reinterpret_cast<char*>(w.kc), reinterpret_cast<char*>(w.vc), reinterpret_cast<char*>(w.stage_w), reinterpret_cast<const char*>(w.stage_r),
+                            w.cos_d, w.sin_d, w.layer_stride, n_layers, nkv, w.src_pos, w.n_src, w.dst_pos, w.n_dst, u, ua);
+}
 extern "C" int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1) {
     if (!h) return fail(RCA_ERR_ARG, "null");
-    if (lm_kv_q8(h))
+    if (lm_kv_q8(h) && !h->kv_shift_requant)
         return fail(RCA_ERR_STATE, "kv_remove: this handle keeps a q8_0 KV cache (rca_lm_set_kv_format); re-rotating quantised keys would quantise them a second time, "
                                    "which this version does not do -- use an fp16 cache for the context shift");
     { const int rc = lm_settle(h); if (rc != RCA_OK) return rc; }
@@ -5736,9 +5858,15 @@ extern "C" int rca_lm_kv_remove(rca_lm_t* h, int32_t p0, int32_t p1) {
             const int n_dst = i > 0 ? std::min(ATT_KEYS, tail - ATT_KEYS * (i - 1)) : 0;
             const long units = (long)c.n_layers * (n_src + n_dst) * c.n_kv_heads * 4;
             const int blocks = (int)std::min<long>((units + 255) / 256, 2048);
-            lm_kv_shift_kernel<<<blocks, 256, 0, h->stream>>>(h->kc, h->vc, h->kv_stage + (long)(i & 1) * slab, h->kv_stage + (long)((i + 1) & 1) * slab,
-                                                              cos_d, sin_d, h->kv_layer_stride, c.n_layers, c.n_kv_heads,
-                                                              p1 + ATT_KEYS * i, n_src, p0 + ATT_KEYS * (i - 1), n_dst);
+            f16_t* const sw = h->kv_stage + (long)(i & 1) * slab;
+            const f16_t* const sr = h->kv_stage + (long)((i + 1) & 1) * slab;
+            if (lm_kv_q8(h))   // the same steps over blocks (68 of a slab's 128 bytes per head row and tensor are used)
+                lm_kv_shift_q8_kernel<<<blocks, 256, 0, h->stream>>>(reinterpret_cast<char*>(h->kc), reinterpret_cast<char*>(h->vc), reinterpret_cast<char*>(sw),
+                                                                     reinterpret_cast<const char*>(sr), cos_d, sin_d, h->kv_layer_stride, c.n_layers, c.n_kv_heads,
+                                                                     p1 + ATT_KEYS * i, n_src, p0 + ATT_KEYS * (i - 1), n_dst);
+            else
+                lm_kv_shift_kernel<<<blocks, 256, 0, h->stream>>>(h->kc, h->vc, sw, sr, cos_d, sin_d, h->kv_layer_stride, c.n_layers, c.n_kv_heads,
+                                                                  p1 + ATT_KEYS * i, n_src, p0 + ATT_KEYS * (i - 1), n_dst);
             RCA_LAUNCH_CHECK();
         }
         RCA_HIP(hipStreamSynchronize(h->stream));
@@ -5769,9 +5897,12 @@ static int lm_kv_remove_many(rca_lm_t* const* hs, int32_t n_h, const int32_t* p0
             return fail(RCA_ERR_ARG, "kv_remove_many: handle %d does not share handle 0's weights (rca_lm_create_shared): RoPE tables and dimensions must be the same", k);
     }
     for (int k = 0; k < n_h; ++k)
-        if (lm_kv_q8(hs[k]))
+        if (lm_kv_q8(hs[k]) && !hs[k]->kv_shift_requant)
             return fail(RCA_ERR_STATE, "kv_remove_many: handle %d keeps a q8_0 KV cache (rca_lm_set_kv_format); re-rotating quantised keys would quantise them a second time, "
                                        "which this version does not do -- use an fp16 cache for the context shift", k);
+    for (int k = 1; k < n_h; ++k)      // one launch runs one unit body
+        if (hs[k]->kv_format != hs[0]->kv_format)
+            return fail(RCA_ERR_ARG, "kv_remove_many: handle %d has KV format %d, handle 0 has %d (rca_lm_set_kv_format)", k, hs[k]->kv_format, hs[0]->kv_format);
     for (int k = 0; k < n_h; ++k) { const int rc = lm_settle(hs[k]); if (rc != RCA_OK) return rc; }
     for (int k = 0; k < n_h; ++k)
         if (p0[k] < 0 || p0[k] > p1[k] || p1[k] > hs[k]->n_tokens)
@@ -5832,7 +5963,8 @@ static int lm_kv_remove_many(rca_lm_t* const* hs, int32_t n_h, const int32_t* p0
                 }
                 for (int j = gn; j < RCA_LM_KV_REMOVE_GROUP; ++j) tab.row[j] = LmShiftRow{};
                 const int blocks = (int)std::min<long>((most + 255) / 256, 1024);
-                lm_kv_shift_many_kernel<<<dim3(blocks, gn), 256, 0, lead->stream>>>(tab, c.n_layers, c.n_kv_heads);
+                if (lm_kv_q8(lead)) lm_kv_shift_many_q8_kernel<<<dim3(blocks, gn), 256, 0, lead->stream>>>(tab, c.n_layers, c.n_kv_heads);
+                else lm_kv_shift_many_kernel<<<dim3(blocks, gn), 256, 0, lead->stream>>>(tab, c.n_layers, c.n_kv_heads);
                 RCA_LAUNCH_CHECK();
             }
         }
@@ -7968,7 +8100,23 @@ extern "C" int rca_lm_set_kv_format(rca_lm_t* h, int32_t fmt) {
     h->kv_format = fmt;
     const int rc = lm_kv_alloc(h);
     if (rc != RCA_OK) { h->kv_format = old; (void)lm_kv_alloc(h); return rc; }
+    if (fmt == 0) h->kv_shift_requant = 0;   // the permission belongs to the q8_0 cache that has just gone
     RCA_HIP(hipStreamSynchronize(h->stream));
+    return RCA_OK;
+}
+// q8_0 handles only: 1 lets rca_lm_kv_remove / rca_lm_kv_remove_many de-quantise, rotate and RE-QUANTISE the keys they move (the comment
+// above lm_kv_shift_unit_q8); 0 (default) keeps their refusal.  A permission and nothing else: allowed at any n_tokens, no cache is
+// touched, no graph is dropped.
+extern "C" int rca_lm_set_kv_shift_requant(rca_lm_t* h, int32_t on) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    if (on != 0 && on != 1) return fail(RCA_ERR_ARG, "set_kv_shift_requant: %d is neither 0 nor 1", on);
+    if (!lm_kv_q8(h)) return fail(RCA_ERR_STATE, "set_kv_shift_requant: this handle keeps an fp16 KV cache, whose context shift quantises nothing (rca_lm_set_kv_format)");
+    h->kv_shift_requant = on;
+    return RCA_OK;
+}
+extern "C" int rca_lm_get_kv_shift_requant(const rca_lm_t* h, int32_t* on) {
+    if (!h || !on) return fail(RCA_ERR_ARG, "null");
+    *on = h->kv_shift_requant;
     return RCA_OK;
 }
 extern "C" int rca_lm_get_kv_format(const rca_lm_t* h, int32_t* fmt) {

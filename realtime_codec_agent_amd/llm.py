@@ -196,6 +196,7 @@ class LlamaForAlternatingCodeChannels:
         weight_format: Optional[str] = None,
         activation_format: Optional[str] = None,
         kv_format: Optional[str] = None,
+        kv_shift_requant: Optional[bool] = None,
         **_ignored,
     ):
         """weight_format: the format every projection matrix and lm_head is KEPT in (one copy: the decode step streams it, the prefill
@@ -213,9 +214,14 @@ class LlamaForAlternatingCodeChannels:
         (default) = f32 activations; "q8_1" = activations quantised to 32-value int8 blocks inside the GEMV and integer dot products,
         the arithmetic class of llama.cpp's GPU mat-vec (set_activation_format).  A twin inherits its parent's.
         kv_format: what the KV cache holds.  None / "f16" (default) = fp16 rows; "q8_0" = ggml q8_0 blocks, 68 bytes per head row instead
-        of 128 (llama-cpp-python's type_k = type_v = GGML_TYPE_Q8_0 next to flash_attn=True; set_kv_format).  A twin inherits its parent's."""
+        of 128 (llama-cpp-python's type_k = type_v = GGML_TYPE_Q8_0 next to flash_attn=True; set_kv_format).  A twin inherits its parent's.
+        kv_shift_requant: True lets kv_remove / kv_remove_many shift a "q8_0" cache by de-quantising, rotating and RE-QUANTISING the moved
+        keys (llama.cpp's K-shift on --cache-type-k q8_0; set_kv_shift_requant).  None / False (default): a "q8_0" handle refuses the
+        shift.  Needs kv_format="q8_0"; a twin inherits its parent's."""
         if kv_format not in (None,) + KV_FORMATS:
             raise ValueError(f"kv_format {kv_format!r}: None / 'f16' or 'q8_0'")
+        if kv_shift_requant and share_weights_with is None and kv_format != "q8_0":
+            raise ValueError(f"kv_shift_requant=True needs kv_format='q8_0' (got {kv_format!r}): the shift of an fp16 cache quantises nothing")
         if activation_format not in (None,) + ACTIVATION_FORMATS:
             raise ValueError(f"activation_format {activation_format!r}: None / 'f32' or 'q8_1'")
         if weight_format not in (None, "bf16", "q8_0", "f16", "q4_k", "q5_k", "q4_0", "q4_1", "iq4_nl"):
@@ -246,7 +252,7 @@ class LlamaForAlternatingCodeChannels:
             self.activation_format = self._query_activation_format()   # rca_lm_create_shared copied the parent's
             self._init_activation_format(activation_format)
             self.kv_format = self._query_kv_format()                   # and the parent's KV format
-            self._init_kv_format(kv_format)
+            self._init_kv_format(kv_format, kv_shift_requant)
             return
         random_init = weights is None and (model_path is None or str(model_path).startswith("random:"))
         if weights is None and not random_init:
@@ -281,13 +287,14 @@ class LlamaForAlternatingCodeChannels:
         self.activation_format = "f32"
         self._init_activation_format(activation_format)
         self.kv_format = "f16"
-        self._init_kv_format(kv_format)
+        self._init_kv_format(kv_format, kv_shift_requant)
 
-    def _init_kv_format(self, kv_format: Optional[str]) -> None:
-        if kv_format is None:
-            return
+    def _init_kv_format(self, kv_format: Optional[str], kv_shift_requant: Optional[bool] = None) -> None:
         try:
-            self.set_kv_format(kv_format)
+            if kv_format is not None:
+                self.set_kv_format(kv_format)
+            if kv_shift_requant is not None and (kv_shift_requant or self.kv_format == "q8_0"):
+                self.set_kv_shift_requant(kv_shift_requant)
         except Exception:
             self.close()
             raise
@@ -299,11 +306,27 @@ class LlamaForAlternatingCodeChannels:
 
     def set_kv_format(self, kv_format: str) -> None:
         """"f16" or "q8_0" (see the constructor).  Only an empty handle (n_tokens == 0) can change: the cache is re-allocated and captured
-        graphs are dropped.  kv_remove (the context-shift trim) is refused on a "q8_0" handle."""
+        graphs are dropped.  kv_remove (the context-shift trim) is refused on a "q8_0" handle unless set_kv_shift_requant(True) allows
+        it; switching to "f16" clears that permission."""
         if kv_format not in KV_FORMATS:
             raise ValueError(f"kv_format {kv_format!r}: 'f16' or 'q8_0'")
         N.check(self._lib.rca_lm_set_kv_format(self._h, KV_FORMATS.index(kv_format)), "rca_lm_set_kv_format")
         self.kv_format = kv_format
+
+    def set_kv_shift_requant(self, on: bool) -> None:
+        """Allow (True) or refuse again (False) the context shift of this handle's "q8_0" cache (rca_lm_set_kv_shift_requant): kv_remove
+        then de-quantises the moved keys, rotates them as on an fp16 cache and quantises them again -- every shift costs the surviving
+        keys one q8_0 quantisation on top of the fp16 rounding.  A permission only, allowed at any n_tokens; an "f16" handle refuses it."""
+        N.check(self._lib.rca_lm_set_kv_shift_requant(self._h, 1 if on else 0), "rca_lm_set_kv_shift_requant")
+
+    @property
+    def kv_shift_requant(self) -> bool:
+        """whether kv_remove may shift this handle's "q8_0" cache, read from the library (a twin carries its parent's value)"""
+        if not getattr(self, "_h", None):
+            return False
+        on = C.c_int32()
+        N.check(self._lib.rca_lm_get_kv_shift_requant(self._h, C.byref(on)), "rca_lm_get_kv_shift_requant")
+        return bool(on.value)
 
     def kv_bytes_per_position(self) -> int:
         """Bytes one cached position takes (all layers, K and V) in the handle's KV format."""
@@ -847,7 +870,8 @@ class LlamaForAlternatingCodeChannels:
         """llama.cpp's context shift (rca_lm_kv_remove): drop cache positions [p0, p1) and slide positions [p1, n_tokens) down by
         p1 - p0, re-rotating their keys; n_tokens shrinks by p1 - p0 and the last logits stay readable.  Logits after a kv_remove
         are those of a shifted cache, not those of a recompute: the surviving keys and values of every layer above the first were
-        computed while attending to the removed tokens, and each shift adds one fp16 rounding to the surviving keys."""
+        computed while attending to the removed tokens, and each shift adds one fp16 rounding to the surviving keys.  On a "q8_0"
+        cache the call needs set_kv_shift_requant(True) and adds one q8_0 quantisation of the surviving keys as well."""
         p0, p1, n = int(p0), int(p1), self.n_tokens
         N.check(self._lib.rca_lm_kv_remove(self._h, p0, p1), "rca_lm_kv_remove")
         self._input_ids[p0:n - (p1 - p0)] = self._input_ids[p1:n].copy()
@@ -982,8 +1006,9 @@ def kv_remove_many(llms: Sequence["LlamaForAlternatingCodeChannels"], spans: Seq
     """The context shift of 1 to 64 handles over ONE set of weights (a handle and its share_weights_with= twins) in one library call
     (rca_lm_kv_remove_many): llms[k] ends exactly as llms[k].kv_remove(*spans[k]) would leave it, bit for bit, but the handles' slabs
     share their launches and the call ends in one synchronisation.  A refusal (a repeated handle, a handle of other weights, a q8_0
-    cache, a span outside a handle's positions) raises and leaves every handle and every mirror as it was.  staged_only (tests and
-    measurements) keeps every handle on the staged route whatever its span."""
+    cache without set_kv_shift_requant(True), handles of different KV formats, a span outside a handle's positions) raises and leaves
+    every handle and every mirror as it was.  staged_only (tests and measurements) keeps every handle on the staged route whatever its
+    span."""
     llms = list(llms)
     rows = [(int(a), int(b)) for a, b in spans]
     if len(rows) != len(llms):

@@ -32,12 +32,14 @@ class RealtimeAgentResources:
         llm_weight_format: Optional[str] = None,
         llm_activation_format: Optional[str] = None,
         llm_kv_format: Optional[str] = None,
+        llm_kv_shift_requant: Optional[bool] = None,
     ):
         self.llm_model_dir = os.path.dirname(llm_model_path) if not llm_model_path.startswith("random:") else ""
         kw = dict(model_path=llm_model_path, n_ctx=llm_n_ctx, n_gpu_layers=-1, verbose=False, flash_attn=True,
                   config=llm_config, random_seed=llm_random_seed, weight_format=llm_weight_format,
                   activation_format=llm_activation_format,   # "q8_1": integer-dot decode over quantised weights; the twins below inherit it
-                  kv_format=llm_kv_format)                   # "q8_0": quantised KV cache; twins (aux_llm, self-play clones, KV shadows) inherit it
+                  kv_format=llm_kv_format,                   # "q8_0": quantised KV cache; twins (aux_llm, self-play clones, KV shadows) inherit it
+                  kv_shift_requant=llm_kv_shift_requant)     # True: kv_trim_mode="shift" may re-quantise the keys of a "q8_0" cache; twins inherit it
         if share_llm_weights_with is not None:   # clone_for_self_play: a fresh model state over the weights already on the device
             self.llm = LlamaForAlternatingCodeChannels(model_path=llm_model_path, n_ctx=llm_n_ctx, share_weights_with=share_llm_weights_with)
         else:

@@ -3,8 +3,10 @@ another, N = 2 .. 64, at the trims of scripts/kv_shift_timing.py (150-token head
 with 1 650 removed), with the batched call on its own routing (delta >= 256: the direct route) and held on the staged route; (b) a
 RealtimeAgentBatch tick of 64 sessions that start together in kv_trim_mode="shift" with batch_shift_trims off and on, and the same
 sessions in the default recompute / shadow mode.
-1B dims, random-init weights, bf16, fp16 cache, the default codec, weight-sharing handles, graphs on.
-usage: kv_shift_many.py [CONTEXT ...]     (RCA_PROBE_PARTS=call|driver: one part only; contexts default to 2200 6600 for (a), 2200 for (b))
+1B dims, random-init weights, bf16, the default codec, weight-sharing handles, graphs on.  The KV cache is fp16, or with RCA_LM_KV=q8_0
+q8_0 blocks with the shift allowed (kv_shift_requant=True: the moved keys are re-quantised).
+usage: kv_shift_many.py [CONTEXT ...]     (RCA_PROBE_PARTS=call|driver: one part only; RCA_PROBE_SHAPES=2,8,64: the N of (a);
+                                           RCA_PROBE_MODES=shift: the modes of (b); contexts default to 2200 6600 for (a), 2200 for (b))
 (a) The three legs alternate inside one process (single, many, many-staged, single, ... REPEATS times each); a timed leg is CALLS calls
 behind one untimed call of the same leg, each around a host clock with every stream idle before it; n_tokens is put back between
 calls (the rows above are stale but still there: the same work again).  Bytes are the cache bytes read + written once (the staged
@@ -26,9 +28,12 @@ from realtime_codec_agent_amd.realtime_agent_v2 import RealtimeAgent
 contexts = [int(a) for a in sys.argv[1:]]
 parts = (os.environ.get("RCA_PROBE_PARTS") or "call,driver").split(",")
 REPEATS, CALLS, NB, TRIMS, HEADER = 3, 5, 64, 3, 150
-SHAPES = (2, 4, 8, 16, 32, 64)
+SHAPES = tuple(int(x) for x in (os.environ.get("RCA_PROBE_SHAPES") or "2,4,8,16,32,64").split(","))
+MODES = (os.environ.get("RCA_PROBE_MODES") or "shift,recompute").split(",")
+KV = os.environ.get("RCA_LM_KV") or None                          # None / "f16" / "q8_0"
+KV_ARGS = dict(kv_format=KV, kv_shift_requant=True) if KV == "q8_0" else dict(kv_format=KV)
 cfg = LMConfig.llama_3_2_1b()
-row_bytes = cfg.n_layers * cfg.n_kv_heads * 64 * 2 * 2            # one position: K and V of every layer, fp16
+row_bytes = cfg.n_layers * cfg.n_kv_heads * (68 if KV == "q8_0" else 64 * 2) * 2      # one position: K and V of every layer, fp16 rows or q8_0 blocks
 
 
 def mmm(v):
@@ -37,7 +42,9 @@ def mmm(v):
 
 def call_legs(ctxs):
     n_ctx = (max(ctxs) + 511) // 256 * 256
-    parent = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=n_ctx, random_seed=0, device=0)
+    parent = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=n_ctx, random_seed=0, device=0, **KV_ARGS)
+    assert parent.kv_bytes_per_position() == row_bytes
+    print(f"KV cache {parent.kv_format}: {row_bytes} bytes per position", flush=True)
     twins = [parent.make_kv_shadow(low_priority=False) for _ in range(max(SHAPES))]
     ids = np.random.default_rng(5).integers(128266, 259338, max(ctxs)).tolist()
     for n in ctxs:
@@ -100,8 +107,12 @@ def driver_legs(ctx, mode):
     limit_chunks = (ctx - HEADER) // per_chunk
     period = limit_chunks // 4                          # a quarter of the context per trim
     n_ctx = (ctx + 767) // 256 * 256
-    res = [RealtimeAgentResources(llm_model_path="random:Llama-3.2-1B-codec", llm_n_ctx=n_ctx, llm_config=cfg, with_aux_llm=False, llm_random_seed=0)]
+    res = [RealtimeAgentResources(llm_model_path="random:Llama-3.2-1B-codec", llm_n_ctx=n_ctx, llm_config=cfg, with_aux_llm=False, llm_random_seed=0,
+                                  **{"llm_" + k: v for k, v in KV_ARGS.items()})]
     res += [res[0].clone_for_self_play() for _ in range(NB - 1)]
+    bpp = res[0].llm.kv_bytes_per_position()
+    print(f"(b) KV cache {res[0].llm.kv_format}: {bpp} bytes per position, {bpp * ctx / 1e6:.1f} MB per session and cache at {ctx} positions "
+          f"({mode}: {'one cache' if mode == 'shift' else 'two caches, live and shadow'} per session)", flush=True)
     agents = []
     for s, r in enumerate(res):
         c = RealtimeAgentConfig(chunk_size_secs=0.08, use_whisper=False, top_k=100, temperature=1.0, seed=42 + s,
@@ -168,5 +179,5 @@ if "call" in parts:
     call_legs(contexts or [2200, 6600])
 if "driver" in parts:
     for ctx in (contexts or [2200]):
-        driver_legs(ctx, "shift")
-        driver_legs(ctx, "recompute")
+        for mode in MODES:
+            driver_legs(ctx, mode)

@@ -2,6 +2,7 @@
 after its own stream synchronisation, so the figure holds the launches and the synchronisation, not the kernels alone) for the trims of a session with a 150-token header -- 2.2 k context with 550 positions removed, 6.6 k context with
 1 650 removed -- the cache bytes it moves over that time, and, for information, max |dlogit| of a decode step on the shifted cache
 against the same step on a cache recomputed from header + suffix.
+RCA_LM_KV=q8_0: the same on a q8_0 cache with the shift allowed (kv_shift_requant=True: the moved keys are re-quantised).
 usage: kv_shift_timing.py [repeats]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,9 +11,12 @@ from realtime_codec_agent_amd.llm import LlamaForAlternatingCodeChannels, LMConf
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 cfg = LMConfig.llama_3_2_1b()
-llm = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=16384, random_seed=0, device=0)
+KV = os.environ.get("RCA_LM_KV") or None
+llm = LlamaForAlternatingCodeChannels(model_path="random:1b", config=cfg, n_ctx=16384, random_seed=0, device=0,
+                                      **(dict(kv_format=KV, kv_shift_requant=True) if KV == "q8_0" else dict(kv_format=KV)))
 ids = np.random.default_rng(5).integers(128266, 259338, 7000).tolist()
-row_bytes = cfg.n_layers * cfg.n_kv_heads * 64 * 2 * 2            # one position: K and V of every layer, fp16
+row_bytes = llm.kv_bytes_per_position()                           # one position: K and V of every layer, fp16 rows or q8_0 blocks
+print(f"KV cache {llm.kv_format}: {row_bytes} bytes per position")
 header = 150
 for n, cut in ((2200, 550), (6600, 1650)):
     llm.reset()
