@@ -288,7 +288,11 @@ int rca_codec_codebook_dev(rca_codec_t* h, const float** out_dev);
 int rca_codec_codebook(rca_codec_t* h, float* out_host);
 
 /* Debug/parity taps (tests only): run the encoder and copy the activation after
- * layer `layer` (0=conv_in, 1..n=down, n+1=conv_out, n+2=in_proj z) to the host. */
+ * layer `layer` (0=conv_in, 1..n=down, n+1=conv_out, n+2=in_proj z) to the host.
+ * A tapped pass (layer <= n+1) is NOT the pass encode() runs: it runs without the LeakyReLU
+ * hand-off between layers (no layer stores an activated output, none reads one), without the
+ * kept-frames view of conv_out and, for layer 0, without the fusion of conv_in into the first
+ * strided layer.  Those launches are reached by rca_codec_encoder_layer_tap below. */
 int rca_codec_encode_tap(rca_codec_t* h, const float* pcm_host, int32_t B, int32_t T, int32_t layer,
                          float* out_host, int64_t out_numel);
 
@@ -320,7 +324,11 @@ int rca_codec_encode_tap_bf16(rca_codec_t* h, const float* pcm_host, int32_t B, 
  *   6      warp-specialised kernel (variant 2)
  *   7      bf16 MFMA (mfma mode 1 / 3)
  *   8      f32 MFMA, any other wave tile (the fused first encoder layer; never a decoder layer)
+ *   9      conv_first_mfma_kernel: the fused first encoder layer with conv_in on the matrix pipe (never a decoder layer)
  *   16+NW  LDS latency kernel with NW waves per workgroup: 17, 18 or 20
+ *   +32    the launch was conv1d_mfma_mixed_kernel: whole rounds on the tile the low bits name (4 or 5), the remaining columns on
+ *          finer tiles of the same grid.  Only the strided encoder layers with k >= 8 have it; never a decoder layer.
+ * conv_in_kernel (the encoder's first layer alone) reports 1.
  * RCA_ERR_ARG before any HIP call for a null pointer, a layer or route out of range, B or Lin < 1, a route-1 shape as above, more
  * than 2^30 input or output elements, or a y_numel other than B * Cout * Lout. */
 #define RCA_KCLASS_CHAIN 1
@@ -331,9 +339,33 @@ int rca_codec_encode_tap_bf16(rca_codec_t* h, const float* pcm_host, int32_t B, 
 #define RCA_KCLASS_WS 6
 #define RCA_KCLASS_BF16 7
 #define RCA_KCLASS_MFMA_OTHER 8
+#define RCA_KCLASS_FIRST_MFMA 9
 #define RCA_KCLASS_LDS 16   /* + NW */
+#define RCA_KCLASS_MIXED 32 /* ORed onto 4 or 5 */
 int rca_codec_decoder_layer_tap(rca_codec_t* h, int32_t layer, int32_t route, const float* x_host, int32_t B, int32_t Lin,
                                 float* y_host, int64_t y_numel, int32_t* kernel_class, int32_t* guards_ok);
+
+/* Tests only: ONE encoder layer through the code an encode pass runs it with, on a host-supplied input.
+ * layer: 0 = enc.conv_in, 1..n = enc.down.{0..n-1}, n + 1 = enc.conv_out.
+ * route 0: the throughput launch of encode() and the batch entry points.  route 1: what rca_codec_encode_tail_dev launches under
+ * lat_mode: variant >= 1, at most 64 (RCA_LAT_MAX_FRAMES) frames in all rows together, no flag, no view.
+ * flags: 1 = x_host already holds LeakyReLU(x) and the launch must not apply it again; 2 = store LeakyReLU(y); 4 (layer 1 only) =
+ * x_host is PCM and the launch is conv_in fused into the first strided layer.  view: 0, or the trailing columns per row the last
+ * layer computes and stores compact.  Each is accepted only where the pass itself decides so for this shape, by the same code:
+ * 1 needs the hand-off into `layer` (layer >= 2: neither conv_in nor the fusion's own conv_in stores an activated output), 2 the
+ * hand-off into layer + 1, 4 the fusion predicate, a view (halo < view < Lout, layer n + 1) the kept-frames rule with
+ * keep = view - halo.  RCA_CONV_BALANCE, RCA_CONV_BALANCE_PLAN, RCA_FUSE_MFMA_IN and RCA_HEAD_KEEP are read per call as in a pass;
+ * the handle's variant and mfma mode apply.
+ * Layer 0 and flag 4 take PCM x_host [B][Lin] for any Lin >= 1 and pad to whole frames as a pass does (L = frames * hop; on route 1
+ * Lin is the kernel's Lvalid).  Other layers take x_host [B][Cin][Lin] with Lin a whole number of frames times the strides still to
+ * come.  y_host [B][Cout][Lout] (Lout = L / stride), or [B][Cout][view]; y_numel is its element count.
+ * Guards and fills as in rca_codec_decoder_layer_tap: 256 guard floats around the device output, NaN in output and guards before the
+ * launch, 1e30 in the input margins.  *kernel_class as documented there, *post_done = 1 when the launch stored LeakyReLU(y).
+ * RCA_ERR_ARG before any HIP call for a null pointer, a layer, route or flag out of range, a flag or view the pass would not use, a
+ * bad shape, more than 2^30 elements or a wrong y_numel. */
+int rca_codec_encoder_layer_tap(rca_codec_t* h, int32_t layer, int32_t route, int32_t flags, int32_t view, const float* x_host,
+                                int32_t B, int32_t Lin, float* y_host, int64_t y_numel, int32_t* kernel_class, int32_t* post_done,
+                                int32_t* guards_ok);
 
 /* Kernel-variant switch (parity tests compare variants): 0 = scalar-chain kernels,
  * 1 = MFMA/LDS kernels (default when available). */

@@ -395,7 +395,12 @@ GEMM128_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p
                         C.c_void_p, C.c_void_p]
 # kernel_class of rca_codec_decoder_layer_tap (RCA_KCLASS_* in include/rca.h)
 KCLASS_CHAIN, KCLASS_MFMA_32x32, KCLASS_MFMA_64x32, KCLASS_MFMA_32x64, KCLASS_MFMA_64x64, KCLASS_WS, KCLASS_BF16, KCLASS_MFMA_OTHER = range(1, 9)
+KCLASS_FIRST_MFMA = 9   # conv_first_mfma_kernel (the fused first encoder layer with conv_in on the matrix pipe)
 KCLASS_LDS = 16   # + NW
+KCLASS_MIXED = 32   # ORed onto KCLASS_MFMA_32x64 / 64x64: conv1d_mfma_mixed_kernel (strided encoder layers with k >= 8)
+# int rca_codec_encoder_layer_tap(h, layer, route, flags, view, x_host, B, Lin, y_host, y_numel, kernel_class, post_done, guards_ok)
+ENCODER_LAYER_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32,
+                              C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
 
 
 def sources() -> List[str]:
@@ -520,7 +525,7 @@ ABI_SYMBOLS = [
     "rca_lm_batch_create", "rca_lm_batch_destroy", "rca_lm_batch_step", "rca_lm_batch_frame",
     "rca_lm_batch_frame_sel", "rca_lm_batch_captures", "rca_duplex_batch_frame", "rca_lm_batch_step_sel",
     "rca_lm_batch_eval", "rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged",
-    "rca_codec_decoder_layer_tap", "rca_quantize_rows", "rca_lm_gemm128_tap",
+    "rca_codec_decoder_layer_tap", "rca_codec_encoder_layer_tap", "rca_quantize_rows", "rca_lm_gemm128_tap",
     "rca_quantize_rows_w", "rca_lm_imatrix_rows_tap",
     "rca_lm_imatrix_begin", "rca_lm_imatrix_chunk", "rca_lm_imatrix_get", "rca_lm_imatrix_end", "rca_lm_imatrix_chunk_tap",
     "rca_lm_gemv_tap_form",
@@ -556,6 +561,9 @@ def lib():
     if hasattr(_lib, "rca_codec_decoder_layer_tap"):
         _lib.rca_codec_decoder_layer_tap.argtypes = DECODER_LAYER_TAP_ARGTYPES
         _lib.rca_codec_decoder_layer_tap.restype = C.c_int
+    if hasattr(_lib, "rca_codec_encoder_layer_tap"):
+        _lib.rca_codec_encoder_layer_tap.argtypes = ENCODER_LAYER_TAP_ARGTYPES
+        _lib.rca_codec_encoder_layer_tap.restype = C.c_int
     if hasattr(_lib, "rca_quantize_rows"):
         _lib.rca_quantize_rows.argtypes = QUANTIZE_ROWS_ARGTYPES
         _lib.rca_quantize_rows.restype = C.c_int

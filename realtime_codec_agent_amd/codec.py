@@ -163,6 +163,35 @@ class HipCodec:
                                                       C.c_int64(y.size), C.byref(kclass), C.byref(guards)), "rca_codec_decoder_layer_tap")
         return y, kclass.value, bool(guards.value)
 
+    def encoder_layer_tap(self, layer: int, route: int, x: np.ndarray, flags: int = 0, view: int = 0) -> Tuple[np.ndarray, int, bool, bool]:
+        """Tests only (rca_codec_encoder_layer_tap): ONE encoder layer (0 = conv_in, 1..n = down.{0..n-1}, n + 1 = conv_out) as an
+        encode pass (route 0) or a streaming tail call (route 1) launches it.  x is PCM [B, T] for layer 0 and for flags & 4 (the
+        fused first layer), else [B, Cin, Lin].  flags: 1 = x holds LeakyReLU(x), 2 = store LeakyReLU(y), 4 = fused first layer;
+        view: trailing columns per row of the last layer (0 = all).  Returns (y [B, Cout, Lout or view], kernel class, the launch
+        stored LeakyReLU(y), guards intact); an element the kernel did not write is NaN."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        layers = self.cfg.encoder_layers()
+        if not 0 <= layer < len(layers):
+            raise ValueError("layer out of range")
+        ly = layers[layer]
+        if layer == 0 or flags & 4:
+            if x.ndim != 2:
+                raise ValueError("x must be PCM [B, T] for conv_in and the fused first layer")
+            B, Lin = x.shape
+            L = -(-Lin // self.hop) * self.hop
+        else:
+            if x.ndim != 3 or x.shape[1] != ly["cin"]:
+                raise ValueError("x must be [B, Cin, Lin] of an encoder layer")
+            B, _, Lin = x.shape
+            L = Lin
+        y = np.empty((B, ly["cout"], view if view else L // ly["s"]), np.float32)
+        kclass, post, guards = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        fp = C.POINTER(C.c_float)
+        N.check(self._lib.rca_codec_encoder_layer_tap(self._h, layer, route, flags, view, x.ctypes.data_as(fp), B, Lin, y.ctypes.data_as(fp),
+                                                      C.c_int64(y.size), C.byref(kclass), C.byref(post), C.byref(guards)),
+                "rca_codec_encoder_layer_tap")
+        return y, kclass.value, bool(post.value), bool(guards.value)
+
     # ---- device-pointer API (raw addresses; stream = hipStream_t as int, 0 = handle's own stream)
     def encode_dev(self, pcm_ptr: int, B: int, T: int, codes_ptr: int, stream: int = 0) -> None:
         N.check(self._lib.rca_codec_encode_dev(self._h, C.c_void_p(pcm_ptr), B, T, C.c_void_p(codes_ptr), C.c_void_p(stream)), "rca_codec_encode_dev")

@@ -2371,7 +2371,7 @@ struct rca_codec {
     int variant = 1;
     int mfma_mode = 0;          // 0: f32 matrix instruction (bit-exact, default); 1 / 3: bf16 matrix instruction, rounded / hi + lo split (opt-in)
     bool lat_mode = false;      // streaming tail: LDS-staged scalar-chain kernels (set per call)
-    int last_kclass = 0;        // RCA_KCLASS_* of the last run_conv launch (read by rca_codec_decoder_layer_tap)
+    int last_kclass = 0;        // RCA_KCLASS_* of the last run_conv / run_encoder_first launch (read by the two layer taps)
     // receptive-field margins (whole frames) left of a kept frame / sample, derived from the layer geometry
     int enc_left_frames = 0, dec_left_frames = 0;
     bool window_trim = false;   // batch windows: encode only what the kept frames can see (same codes)
@@ -2740,6 +2740,7 @@ static bool launch_conv_balanced(const ConvLayer& L, const float* wp, int nchunk
         conv1d_mfma_mixed_kernel<KS, S, CIC, WM, WN, 1, (WM * WN == 4 ? 2 : 1), 1><<<grid, 64 * RCA_CONV_WPB, lds, st>>>(x, wp, L.bp, y, L.cin, Lin, L.cout, Lc, Ncols, nchunks, act, slope, (unsigned)n_bulk_wg, fine_col0);
     else
         conv1d_mfma_mixed_kernel<KS, S, CIC, WM, WN, 1, 1, 1><<<grid, 64 * RCA_CONV_WPB, lds, st>>>(x, wp, L.bp, y, L.cin, Lin, L.cout, Lc, Ncols, nchunks, act, slope, (unsigned)n_bulk_wg, fine_col0);
+    g_kclass |= RCA_KCLASS_MIXED;   // on top of the bulk tile's class, which launch_conv_cfg has set
     return true;
 }
 
@@ -2839,6 +2840,7 @@ static int launch_conv_mfma(const ConvLayer& L, const float* x, float* y, int B,
                 const long col_tiles = (cdiv(Ncols, NWN * 32) + 7) / 8 * 8;
                 const dim3 grid((unsigned)(col_tiles * (L.cout / 64)));
                 constexpr int lds = 32 * 136 * 4;
+                g_kclass = RCA_KCLASS_FIRST_MFMA;
                 if (act & 1) conv_first_mfma_kernel<NWN, true><<<grid, 64, lds, st>>>(L.wp, L.bp, y, L.cout, Lout, Ncols, act & 2, slope, *fuse);
                 else conv_first_mfma_kernel<NWN, false><<<grid, 64, lds, st>>>(L.wp, L.bp, y, L.cout, Lout, Ncols, act & 2, slope, *fuse);
                 RCA_LAUNCH_CHECK();
@@ -3217,6 +3219,68 @@ static int run_encoder_bf16(rca_codec* h, RowSrc src, int B, int Tp, size_t max_
     return RCA_OK;
 }
 
+// The three decisions of an encode pass that are not run_conv's, shared with rca_codec_encoder_layer_tap (tap_layer as in run_encoder).
+// conv_in fused into the first strided layer (MFMA variant, 7-tap conv_in, layer 0 not tapped); L = padded samples per row
+// (the fused kernel addresses the PCM of the two batch rows a wave can touch with 32-bit offsets from the lower one,
+//  and assumes a row is longer than a wave's window of columns)
+static bool enc_fuse01(const rca_codec* h, const RowSrc& src, int B, int L, int tap_layer) {
+    const ConvLayer& E0 = h->enc[0];
+    const ConvLayer& E1 = h->enc[1];
+    return !h->lat_mode && h->variant >= 1 && tap_layer != 0 && E0.k == 7 && E1.wp && E1.k == 2 * E1.s && (double)B * E1.cin * L < 4.0e9 &&
+           ((E1.k == 4 && E1.s == 2) || (E1.k == 8 && E1.s == 4) || (E1.k == 16 && E1.s == 8)) && L / E1.s >= 67 &&
+           (double)E1.cout * (L / E1.s) < 2.6e8 &&
+           (src.row_off ? (double)src.span : (double)src.C * (double)std::labs(src.chan_stride) + (double)std::labs(src.win_stride) + src.T) < 5.0e8;
+}
+// LeakyReLU hand-off: when layer `next` is pre-activated and runs on conv1d_mfma_kernel over rows of Lnext samples, the layer before
+// it stores LeakyReLU(y) and `next` skips the activation while staging (max(v, slope*v) of the same value either way: bit-identical,
+// but applied once per element instead of once per element per consuming workgroup per chunk).  Off when a layer output is tapped.
+static bool enc_handoff(const rca_codec* h, int tap_layer, size_t next, int B, int Lnext) {
+    return tap_layer < 0 && h->variant == 1 && !h->lat_mode && next < h->enc.size() && h->enc[next].pre && mfma_conv_ok(h, h->enc[next], B, Lnext, 0);
+}
+// Columns per row the LAST layer runs over when the caller reads `keep` trailing frames of rows of L samples: keep + halo as run_conv's
+// view, or 0 for the whole row (short windows, kernels without the view, RCA_HEAD_KEEP=0).
+static int enc_last_view(const rca_codec* h, const ConvLayer& Ly, int B, int L, int keep) {
+    if (keep <= 0 || Ly.tr) return 0;
+    const char* hk = getenv("RCA_HEAD_KEEP");
+    const int want = keep + conv_view_halo(Ly);
+    return (!(hk && hk[0] == '0') && want < L / Ly.s && conv_view_ok(h, Ly, B, L, want)) ? want : 0;   // short windows take the whole row
+}
+
+// The first launch of an encode pass, into y: conv_in fused into the first strided layer (fuse: enc_fuse01 holds; want_post as in
+// run_conv: y = LeakyReLU of that layer's output), else conv_in alone over rows of L samples -- under lat_mode through the latency
+// kernel (rows straight from the caller's window) where it takes them.  Leaves the launch's class in h->last_kclass.
+static int run_encoder_first(rca_codec* h, const RowSrc& src, int B, int L, hipStream_t st, float* y, bool fuse, bool want_post) {
+    const ConvLayer& E0 = h->enc[0];
+    const ConvLayer& E1 = h->enc[1];
+    int rc = RCA_OK;
+    g_kclass = 0;
+    if (fuse) {
+        FuseIn fin{src, E0.w, E0.b};
+        const float slope = h->cfg.leaky_slope;
+        const int Lout = L / E1.s;
+        ProfScope ps(h, st, 0, 2.0 * E1.cin * E1.k * E1.cout * (double)B * Lout + 2.0 * E0.k * E0.cout * (double)B * L,
+                     4.0 * ((double)B * src.T + (double)B * E1.cout * Lout + (double)E1.cin * E1.k * E1.cout));
+        const int act = (E1.pre ? 1 : 0) | (want_post ? 2 : 0);
+        if (h->variant == 2 && try_conv_ws(E1, nullptr, y, B, L, Lout, slope, st, &fin)) { rc = RCA_OK; RCA_LAUNCH_CHECK(); }
+        else if (E1.k == 4) rc = launch_conv_mfma<4, 2, 4>(E1, nullptr, y, B, L, Lout, slope, st, &fin, act, h->mfma_mode);
+        else if (E1.k == 8) rc = launch_conv_mfma<8, 4, RCA_CIC_K8>(E1, nullptr, y, B, L, Lout, slope, st, &fin, act, h->mfma_mode);
+        else rc = launch_conv_mfma<16, 8, RCA_CIC_K16>(E1, nullptr, y, B, L, Lout, slope, st, &fin, act, h->mfma_mode);
+    } else if (h->lat_mode && !src.row_off && src.win_stride == 0 && src.C == B &&
+               try_conv_lds(h, E0, src.base, src.chan_stride, src.T, y, B, L, 0, st)) {
+        RCA_LAUNCH_CHECK();   // streaming tail: conv_in through the same latency kernel (rows straight from the caller's window)
+    } else {
+        const long total = (long)B * L;
+        ProfScope ps(h, st, 2, 2.0 * E0.k * E0.cout * (double)total, 4.0 * ((double)total + (double)total * E0.cout));
+        g_kclass = RCA_KCLASS_CHAIN;
+        if (E0.k == 7) conv_in_kernel<7><<<cdiv(total, 256), 256, 0, st>>>(src, E0.w, E0.b, y, B, E0.cout, L);
+        else if (E0.k == 5) conv_in_kernel<5><<<cdiv(total, 256), 256, 0, st>>>(src, E0.w, E0.b, y, B, E0.cout, L);
+        else conv_in_kernel<3><<<cdiv(total, 256), 256, 0, st>>>(src, E0.w, E0.b, y, B, E0.cout, L);
+        RCA_LAUNCH_CHECK();
+    }
+    h->last_kclass = g_kclass;
+    return rc;
+}
+
 // encoder stack: rows described by src -> ze [B][D][F] left in *ze_out (a workspace buffer).
 // tap_layer >= 0 copies that layer's output (device->device) into tap_dev.
 // bf16_tap >= 0: see run_encoder_bf16; RCA_ERR_ARG when this call would not take the blocked bf16 pipeline.
@@ -3251,54 +3315,21 @@ static int run_encoder(rca_codec* h, RowSrc src, int B, hipStream_t st, float** 
     int cur = 0;
     int L = Tp;
     size_t first = 1;
-    const ConvLayer& E0 = h->enc[0];
     const ConvLayer& E1 = h->enc[1];
-    // conv_in fused into the first strided layer (MFMA variant, 7-tap conv_in, layer 0 not tapped)
-    // (the fused kernel addresses the PCM of the two batch rows a wave can touch with 32-bit offsets from the lower one,
-    //  and assumes a row is longer than a wave's window of columns)
-    const bool fuse01 = !h->lat_mode && h->variant >= 1 && tap_layer != 0 && E0.k == 7 && E1.wp && E1.k == 2 * E1.s && (double)B * E1.cin * L < 4.0e9 &&
-                        ((E1.k == 4 && E1.s == 2) || (E1.k == 8 && E1.s == 4) || (E1.k == 16 && E1.s == 8)) && L / E1.s >= 67 &&
-                        (double)E1.cout * (L / E1.s) < 2.6e8 &&
-                        (src.row_off ? (double)src.span : (double)src.C * (double)std::labs(src.chan_stride) + (double)std::labs(src.win_stride) + src.T) < 5.0e8;
-    // LeakyReLU hand-off: when layer li+1 is pre-activated and runs on conv1d_mfma_kernel, layer li stores LeakyReLU(y) and
-    // li+1 skips the activation while staging (max(v, slope*v) of the same value either way: bit-identical, but applied once
-    // per element instead of once per element per consuming workgroup per chunk).  Off when a layer output is tapped.
+    const bool fuse01 = enc_fuse01(h, src, B, L, tap_layer);
     bool prev_post = false;
-    auto handoff = [&](size_t next, int Lnext) {
-        return tap_layer < 0 && h->variant == 1 && !h->lat_mode && next < h->enc.size() && h->enc[next].pre && mfma_conv_ok(h, h->enc[next], B, Lnext, 0);
-    };
-    if (fuse01) {
+    auto handoff = [&](size_t next, int Lnext) { return enc_handoff(h, tap_layer, next, B, Lnext); };
+    {
         float* y = h->act[cur].as<float>();
-        FuseIn fin{src, E0.w, E0.b};
-        const float slope = c.leaky_slope;
-        const int Lout = L / E1.s;
-        {
-            ProfScope ps(h, st, 0, 2.0 * E1.cin * E1.k * E1.cout * (double)B * Lout + 2.0 * E0.k * E0.cout * (double)B * L,
-                         4.0 * ((double)B * src.T + (double)B * E1.cout * Lout + (double)E1.cin * E1.k * E1.cout));
-            prev_post = handoff(2, Lout);
-            const int act = (E1.pre ? 1 : 0) | (prev_post ? 2 : 0);
-            if (h->variant == 2 && try_conv_ws(E1, nullptr, y, B, L, Lout, slope, st, &fin)) { rc = RCA_OK; RCA_LAUNCH_CHECK(); }
-            else if (E1.k == 4) rc = launch_conv_mfma<4, 2, 4>(E1, nullptr, y, B, L, Lout, slope, st, &fin, act, h->mfma_mode);
-            else if (E1.k == 8) rc = launch_conv_mfma<8, 4, RCA_CIC_K8>(E1, nullptr, y, B, L, Lout, slope, st, &fin, act, h->mfma_mode);
-            else rc = launch_conv_mfma<16, 8, RCA_CIC_K16>(E1, nullptr, y, B, L, Lout, slope, st, &fin, act, h->mfma_mode);
+        if (fuse01) prev_post = handoff(2, L / E1.s);
+        if ((rc = run_encoder_first(h, src, B, L, st, y, fuse01, prev_post)) != RCA_OK) return rc;
+        if (fuse01) {
+            L /= E1.s;
+            first = 2;
+            if (tap_layer == 1) RCA_HIP(hipMemcpyAsync(tap_dev, y, (size_t)B * E1.cout * L * 4, hipMemcpyDeviceToDevice, st));
+        } else if (tap_layer == 0) {   // (no tapped pass runs under lat_mode)
+            RCA_HIP(hipMemcpyAsync(tap_dev, y, (size_t)B * h->enc[0].cout * L * 4, hipMemcpyDeviceToDevice, st));
         }
-        if (rc != RCA_OK) return rc;
-        L = Lout;
-        first = 2;
-        if (tap_layer == 1) RCA_HIP(hipMemcpyAsync(tap_dev, y, (size_t)B * E1.cout * L * 4, hipMemcpyDeviceToDevice, st));
-    } else if (h->lat_mode && !src.row_off && src.win_stride == 0 && src.C == B &&
-               try_conv_lds(h, h->enc[0], src.base, src.chan_stride, src.T, h->act[cur].as<float>(), B, L, 0, st)) {
-        RCA_LAUNCH_CHECK();   // streaming tail: conv_in through the same latency kernel (rows straight from the caller's window)
-    } else {
-        const ConvLayer& L0 = h->enc[0];
-        const long total = (long)B * L;
-        float* y = h->act[cur].as<float>();
-        ProfScope ps(h, st, 2, 2.0 * L0.k * L0.cout * (double)total, 4.0 * ((double)total + (double)total * L0.cout));
-        if (L0.k == 7) conv_in_kernel<7><<<cdiv(total, 256), 256, 0, st>>>(src, L0.w, L0.b, y, B, L0.cout, L);
-        else if (L0.k == 5) conv_in_kernel<5><<<cdiv(total, 256), 256, 0, st>>>(src, L0.w, L0.b, y, B, L0.cout, L);
-        else conv_in_kernel<3><<<cdiv(total, 256), 256, 0, st>>>(src, L0.w, L0.b, y, B, L0.cout, L);
-        RCA_LAUNCH_CHECK();
-        if (tap_layer == 0) RCA_HIP(hipMemcpyAsync(tap_dev, y, (size_t)B * L0.cout * L * 4, hipMemcpyDeviceToDevice, st));
     }
     for (size_t li = first; li < h->enc.size(); ++li) {
         const ConvLayer& Ly = h->enc[li];
@@ -3306,11 +3337,7 @@ static int run_encoder(rca_codec* h, RowSrc src, int B, hipStream_t st, float** 
         float* y = h->act[cur ^ 1].as<float>();
         bool done = false;
         int view = 0;
-        if (li + 1 == h->enc.size() && Fz_out && keep > 0 && tap_layer < 0 && !Ly.tr) {
-            const char* hk = getenv("RCA_HEAD_KEEP");
-            const int want = keep + conv_view_halo(Ly);
-            if (!(hk && hk[0] == '0') && want < L / Ly.s && conv_view_ok(h, Ly, B, L, want)) view = want;   // short windows take the whole row
-        }
+        if (li + 1 == h->enc.size() && Fz_out && tap_layer < 0) view = enc_last_view(h, Ly, B, L, keep);
         if ((rc = run_conv(h, Ly, x, y, B, L, 0, st, prev_post, handoff(li + 1, L / Ly.s), &done, view)) != RCA_OK) return rc;
         if (view) *Fz_out = view;
         prev_post = done;
@@ -3877,6 +3904,92 @@ extern "C" int rca_codec_decoder_layer_tap(rca_codec_t* h, int32_t layer, int32_
     for (long i = 0; i < 2 * G; ++i) ok &= guards[i] == nan_bits;
     *guards_ok = ok;
     *kernel_class = h->last_kclass;
+    return RCA_OK;
+}
+
+// Tests only (see rca.h): one encoder layer through the code an encode pass runs it with -- run_encoder_first for conv_in and the fused
+// first layer, run_conv with run_encoder's arguments behind them -- on a host-supplied input; NaN-filled output between guards.  A flag
+// or view is taken only where the predicate of run_encoder (enc_fuse01, enc_handoff, enc_last_view) holds for this shape.
+extern "C" int rca_codec_encoder_layer_tap(rca_codec_t* h, int32_t layer, int32_t route, int32_t flags, int32_t view, const float* x_host,
+                                           int32_t B, int32_t Lin, float* y_host, int64_t y_numel, int32_t* kernel_class,
+                                           int32_t* post_done, int32_t* guards_ok) {
+    if (!h || !x_host || !y_host || !kernel_class || !post_done || !guards_ok) return fail(RCA_ERR_ARG, "encoder_layer_tap: null argument");
+    const int n = h->cfg.n_stages;
+    if (layer < 0 || layer > n + 1) return fail(RCA_ERR_ARG, "encoder_layer_tap: layer %d out of range [0, %d]", layer, n + 1);
+    if (route != 0 && route != 1) return fail(RCA_ERR_ARG, "encoder_layer_tap: route %d is neither 0 nor 1", route);
+    if (flags < 0 || flags > 7) return fail(RCA_ERR_ARG, "encoder_layer_tap: flags %d out of range [0, 7]", flags);
+    if (B < 1 || Lin < 1 || view < 0) return fail(RCA_ERR_ARG, "encoder_layer_tap: bad shape (B=%d Lin=%d view=%d)", B, Lin, view);
+    const bool in_act = flags & 1, want_post = flags & 2, fused = flags & 4;
+    if (fused && (layer != 1 || in_act)) return fail(RCA_ERR_ARG, "encoder_layer_tap: flag 4 (fused first layer) goes with layer 1 and a PCM input");
+    if (route == 1 && (flags || view)) return fail(RCA_ERR_ARG, "encoder_layer_tap: route 1 takes no flag and no view (the streaming tail has neither)");
+    if (route == 1 && h->variant < 1) return fail(RCA_ERR_ARG, "encoder_layer_tap: route 1 needs variant >= 1");
+    const bool pcm_in = layer == 0 || fused;
+    const ConvLayer& Ly = h->enc[layer];
+    long frames, L;      // frames per row; samples per row at the input of the launch (a PCM row padded to whole frames)
+    if (pcm_in) {
+        frames = ((long)Lin + h->hop - 1) / h->hop;
+        L = frames * h->hop;
+    } else {
+        long mult = 1;   // input samples per frame: the strides still to come
+        for (int i = layer - 1; i < n; ++i) mult *= h->cfg.strides[i];
+        if (Lin % mult != 0) return fail(RCA_ERR_ARG, "encoder_layer_tap: Lin %d is no multiple of %ld samples per frame", Lin, mult);
+        frames = Lin / mult;
+        L = Lin;
+    }
+    if (route == 1 && (long)B * frames > RCA_LAT_MAX_FRAMES)
+        return fail(RCA_ERR_ARG, "encoder_layer_tap: route 1: %ld frames, the tail call takes this route up to %d", (long)B * frames, RCA_LAT_MAX_FRAMES);
+    const long Lout = L / Ly.s;   // conv_in has stride 1; the fused launch stores layer 1's output
+    const long x_numel = pcm_in ? (long)B * Lin : (long)B * Ly.cin * Lin;
+    const long want = (long)B * Ly.cout * (view ? view : Lout);
+    if (x_numel > (1L << 30) || (long)B * (pcm_in ? 1 : Ly.cin) * L > (1L << 30) || (long)B * Ly.cout * Lout > (1L << 30))
+        return fail(RCA_ERR_ARG, "encoder_layer_tap: more than 2^30 elements (B=%d Lin=%d)", B, Lin);
+    if (want != y_numel) return fail(RCA_ERR_ARG, "encoder_layer_tap: y_numel %ld, expected %ld", (long)y_numel, want);
+    // the predicates of the pass (none of them makes a HIP call or reads through the row pointer)
+    RowSrc src{nullptr, B, (long)Lin, 0, Lin};
+    h->lat_mode = route == 1;
+    const bool can_fuse = enc_fuse01(h, src, B, (int)L, -1);
+    const bool can_in = layer >= 2 && enc_handoff(h, -1, (size_t)layer, B, (int)L);   // layer 1's producers (conv_in, the fusion's own) never store activated
+    const bool can_post = layer >= 1 && enc_handoff(h, -1, (size_t)layer + 1, B, (int)Lout);
+    const bool can_view = view > 0 && layer == n + 1 && view > conv_view_halo(Ly) && enc_last_view(h, Ly, B, (int)L, view - conv_view_halo(Ly)) == view;
+    h->lat_mode = false;
+    if (fused && !can_fuse) return fail(RCA_ERR_ARG, "encoder_layer_tap: flag 4: an encode pass of B=%d T=%d does not fuse the first layer", B, Lin);
+    if (in_act && !can_in) return fail(RCA_ERR_ARG, "encoder_layer_tap: flag 1: no encode pass hands layer %d an activated input at B=%d Lin=%d", layer, B, Lin);
+    if (want_post && !can_post) return fail(RCA_ERR_ARG, "encoder_layer_tap: flag 2: no encode pass has layer %d store an activated output at B=%d Lin=%d", layer, B, Lin);
+    if (view && !can_view) return fail(RCA_ERR_ARG, "encoder_layer_tap: no encode pass runs layer %d over a view of %d columns at B=%d Lin=%d", layer, view, B, Lin);
+    constexpr long G = 256;
+    RCA_HIP(hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, h->stream);
+    int rc;
+    if ((rc = h->io_a.ensure((size_t)(x_numel + 2 * G) * 4)) != RCA_OK) return rc;
+    if ((rc = h->io_b.ensure((size_t)(want + 2 * G) * 4)) != RCA_OK) return rc;
+    const float big = 1e30f;
+    const unsigned nan_bits = 0x7FC00000u;
+    RCA_HIP(hipMemsetD32Async((hipDeviceptr_t)h->io_a.p, __builtin_bit_cast(int, big), (size_t)(x_numel + 2 * G), st));
+    RCA_HIP(hipMemsetD32Async((hipDeviceptr_t)h->io_b.p, (int)nan_bits, (size_t)(want + 2 * G), st));
+    float* x = h->io_a.as<float>() + G;
+    float* y = h->io_b.as<float>() + G;
+    RCA_HIP(hipMemcpyAsync(x, x_host, (size_t)x_numel * 4, hipMemcpyHostToDevice, st));
+    bool done = false;
+    h->lat_mode = route == 1;
+    if (pcm_in) {
+        src.base = x;
+        rc = run_encoder_first(h, src, B, (int)L, st, y, fused, want_post);
+        done = fused && want_post;
+    } else {
+        rc = run_conv(h, Ly, x, y, B, Lin, 0, st, in_act, want_post, &done, view);
+    }
+    h->lat_mode = false;
+    if (rc != RCA_OK) return rc;
+    unsigned guards[2 * G];
+    RCA_HIP(hipMemcpyAsync(y_host, y, (size_t)want * 4, hipMemcpyDeviceToHost, st));
+    RCA_HIP(hipMemcpyAsync(guards, y - G, (size_t)G * 4, hipMemcpyDeviceToHost, st));
+    RCA_HIP(hipMemcpyAsync(guards + G, y + want, (size_t)G * 4, hipMemcpyDeviceToHost, st));
+    RCA_HIP(hipStreamSynchronize(st));
+    int ok = 1;
+    for (long i = 0; i < 2 * G; ++i) ok &= guards[i] == nan_bits;
+    *guards_ok = ok;
+    *kernel_class = h->last_kclass;
+    *post_done = done ? 1 : 0;
     return RCA_OK;
 }
 
