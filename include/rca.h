@@ -914,6 +914,23 @@ int rca_lm_gemv_tap_form(const rca_lm_t* h, int32_t* form);
  * nsp_launch or out_rows, or positions past n_ctx, are refused before anything is touched. */
 int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_t nsp_launch, const float* q_host, int32_t M, float* out_host,
                     int32_t out_rows);
+/* Tests only: the decode attention of ONE layer for the members of a batch pass, exactly as rca_lm_batch_step / _frame / their _sel forms
+ * and rca_duplex_batch_frame launch it (one helper makes the split launch over the member table and the merge for the pass and for
+ * this call), for n = 1 or 2 query tokens per member at positions n_tokens .. n_tokens+n-1 of each member, over whatever the members'
+ * caches hold at `layer` (rca_lm_kv_write).  sel NULL: the batch's own table, every member in its slot (n_sel ignored); else the
+ * selection table of rca_lm_batch_frame_sel, the n_sel members sel[0..n_sel-1] in slots 0 .. n_sel-1 at the slot count of the
+ * selection's class (8 / 16 / 32 / 64), the slots behind them all zero.  With NM the members of the pass, q_host [NM*n][n_heads*64] f32
+ * are the query rows after RoPE, member k's token j in row k*n + j; out_host [out_rows][n_heads*64], NM*n <= out_rows <= 128, is the
+ * f32 value bf16 hi + lo of the planes the O projection reads (route 2 of rca_lm_attn_tap).  The members are checked and staged as a
+ * step's are (every member needs a sampler; the ids are dummies).  nsp_launch: the 256-key splits the launch covers, 0 = the most any
+ * member of the pass needs, else a value from there up to the largest split count among ALL members of the batch (the graphs' buckets).
+ * Before the launch the first out_rows rows of the planes are filled with NaN (all bits set), so the rows of dead slots and rows >=
+ * NM*n come back NaN unless a kernel wrote them, and every partial buffer of a member of the pass is filled with NaN as a whole: a
+ * partial the merge uses although no workgroup of this launch wrote it shows as NaN.  The planes are zeroed afterwards.  Every
+ * member's n_tokens is left as it was; member 0's activation buffers are overwritten.  A bad layer, n, nsp_launch, out_rows or
+ * selection, a member a step would refuse, or positions past a member's n_ctx are refused before anything is touched. */
+int rca_lm_batch_attn_tap(rca_lm_batch_t* b, int32_t layer, int32_t n, int32_t nsp_launch, const int32_t* sel, int32_t n_sel,
+                          const float* q_host, float* out_host, int32_t out_rows);
 /* Tests only: ONE projection of a 128-token-tile pass exactly as the layer sequence, rca_lm_score and the batch head launch it (the same
  * launcher picks the k-slice form, the grids and the epilogue), on host-supplied activations.  Refused (RCA_ERR_ARG) on a handle whose
  * rca_lm_prefill_route is not 2.  xh_host / xl_host [M][K] are the bf16 hi / lo planes themselves (K = hidden; n_heads*64 for kind 1;

@@ -393,6 +393,8 @@ IMATRIX_ARGTYPES = {"rca_lm_imatrix_rows_tap": [C.c_void_p, C.c_void_p, C.c_void
 # int rca_lm_gemm128_tap(h, layer, kind, xh_host, xl_host, M, rows, row_base, seq_min, y_host, out_rows, kv_host, form)
 GEMM128_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                         C.c_void_p, C.c_void_p]
+# int rca_lm_batch_attn_tap(b, layer, n, nsp_launch, sel, n_sel, q_host, out_host, out_rows)
+BATCH_ATTN_TAP_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
 # kernel_class of rca_codec_decoder_layer_tap (RCA_KCLASS_* in include/rca.h)
 KCLASS_CHAIN, KCLASS_MFMA_32x32, KCLASS_MFMA_64x32, KCLASS_MFMA_32x64, KCLASS_MFMA_64x64, KCLASS_WS, KCLASS_BF16, KCLASS_MFMA_OTHER = range(1, 9)
 KCLASS_FIRST_MFMA = 9   # conv_first_mfma_kernel (the fused first encoder layer with conv_in on the matrix pipe)
@@ -530,6 +532,7 @@ ABI_SYMBOLS = [
     "rca_lm_imatrix_begin", "rca_lm_imatrix_chunk", "rca_lm_imatrix_get", "rca_lm_imatrix_end", "rca_lm_imatrix_chunk_tap",
     "rca_lm_gemv_tap_form",
     "rca_lm_set_kv_shift_requant", "rca_lm_get_kv_shift_requant",
+    "rca_lm_batch_attn_tap",
 ]
 
 
@@ -577,6 +580,9 @@ def lib():
     if hasattr(_lib, "rca_lm_gemm128_tap"):
         _lib.rca_lm_gemm128_tap.argtypes = GEMM128_TAP_ARGTYPES
         _lib.rca_lm_gemm128_tap.restype = C.c_int
+    if hasattr(_lib, "rca_lm_batch_attn_tap"):
+        _lib.rca_lm_batch_attn_tap.argtypes = BATCH_ATTN_TAP_ARGTYPES
+        _lib.rca_lm_batch_attn_tap.restype = C.c_int
     for name in ("rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged"):
         if hasattr(_lib, name):
             getattr(_lib, name).argtypes = KV_REMOVE_MANY_ARGTYPES

@@ -3076,6 +3076,8 @@ static int lm_finish_mat(rca_lm* h, RawMat* raw, int qkv_pairs, WMat* out, const
 
 static int g128_splits(int N, int K);
 static bool lm_can_gemm128(const rca_lm* h);
+// the split partials of a handle: {m, l, o[64]} per query row (LM_MAXM tokens x up to 4 q heads of a kv head), kv head and split
+static size_t lm_att_part_bytes(const rca_lm* h) { return (size_t)(LM_MAXM / 2) * h->cfg.n_kv_heads * h->n_splits * 8 * 66 * 4; }
 static int lm_common_init(rca_lm* h, const rca_tensor_t* ts, int nt, const rca_lm* rope_src = nullptr) {
     const rca_lm_config_t& c = h->cfg;
     int rc;
@@ -3127,7 +3129,7 @@ static int lm_common_init(rca_lm* h, const rca_tensor_t* ts, int nt, const rca_l
     if ((rc = lm_alloc((void**)&h->qkv, (size_t)LM_MAXM * QKV * 4)) != RCA_OK) return rc;
     if ((rc = lm_alloc((void**)&h->attn, (size_t)LM_MAXM * AO * 4)) != RCA_OK) return rc;
     if ((rc = lm_alloc((void**)&h->hbuf, (size_t)LM_MAXM * c.ffn * 4)) != RCA_OK) return rc;
-    if ((rc = lm_alloc((void**)&h->att_part, (size_t)(LM_MAXM / 2) * c.n_kv_heads * h->n_splits * 8 * 66 * 4)) != RCA_OK) return rc;
+    if ((rc = lm_alloc((void**)&h->att_part, lm_att_part_bytes(h))) != RCA_OK) return rc;
     h->logits_rows_cap = c.logits_all ? 64 : 1;
     if ((rc = lm_alloc((void**)&h->logits, (size_t)h->logits_rows_cap * c.vocab_size * 4)) != RCA_OK) return rc;
     if ((rc = lm_alloc((void**)&h->probs_dev, (64 + 2 * PROBS_SLICES) * 4)) != RCA_OK) return rc;   // [64 probs][slice (max, sum) pairs]
@@ -6934,6 +6936,15 @@ static int lm_batch_refresh(rca_lm_batch* b) {
     b->tabs_valid = true;
     return RCA_OK;
 }
+// The decode attention of layer l for every slot of a pass's table: the split kernel with a member per grid z over the q rows in
+// member 0's qkv, then the merge into the members' rows of the bf16 hi / lo planes.  The pass's launches and rca_lm_batch_attn_tap's.
+static void lm_batch_launch_attn(rca_lm* ws, const LmBatchMember* tab, int NM, int n, int nsp_launch, bool q8kv, int l, hipStream_t st) {
+    const rca_lm_config_t& c = ws->cfg;
+    lm_launch_attn_split(c, dim3(c.n_kv_heads, nsp_launch, NM), q8kv, st, nullptr, ws->qkv, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, tab, l);
+    lm_dispatch_421(c.n_heads / c.n_kv_heads, [&](auto g) {
+        lm_attn_mfma_batch_combine_kernel<decltype(g)::value><<<dim3(n * c.n_heads, NM), 64, 0, st>>>(tab, c.n_heads, c.n_kv_heads, nsp_launch, ws->xh, ws->xl);
+    });
+}
 // embedding -> the layers -> head -> samplers over the device states as they stand (staged by lm_batch_stage_kernel, or left by
 // lm_batch_feedback_kernel): the part a step and every step of a frame share
 static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n, int nsp_launch, hipStream_t st) {
@@ -6943,7 +6954,6 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
     const int H = c.hidden, V = c.vocab_size;
     const LmBatchMember* tab = vw.tab;
     lm_attn_split_attrs();
-    const dim3 agm(c.n_kv_heads, nsp_launch, NM);
     const bool q8kv = lm_kv_q8(ws);   // every member's format (rca_lm_batch_create, lm_batch_check)
     float* x = ws->x;
     lm_embed_kernel<<<MT, 256, 0, st>>>(b->stt, ws->embed, ws->embed_f32, x, H, V);
@@ -6951,10 +6961,7 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
     lm_enqueue_layers128(LmTilePass{ws, b->stt, MT, 1, vw.rows, g128_seq_min()}, st, [&](int l) {
         if (q8kv)   // every member's new rows, ring -> int8 planes, in one launch
             lm_kv_quant_kernel<true><<<dim3(cdiv(4 * c.n_kv_heads, 8), n, NM), 256, 0, st>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, c.n_kv_heads, 0, 0, 0, 3, tab, l);
-        lm_launch_attn_split(c, agm, q8kv, st, nullptr, ws->qkv, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, tab, l);
-        lm_dispatch_421(c.n_heads / c.n_kv_heads, [&](auto g) {
-            lm_attn_mfma_batch_combine_kernel<decltype(g)::value><<<dim3(n * c.n_heads, NM), 64, 0, st>>>(tab, c.n_heads, c.n_kv_heads, nsp_launch, ws->xh, ws->xl);
-        });
+        lm_batch_launch_attn(ws, tab, NM, n, nsp_launch, q8kv, l, st);
     });
     // final RMSNorm + head over the last row of every member (one row per member: rows 0 .. NM - 1 of the hi / lo planes), every
     // workgroup walking all of K like rca_lm_score's head; the ragged last row tile of the vocabulary is the logits epilogue's
@@ -8276,6 +8283,58 @@ extern "C" int rca_lm_attn_tap(rca_lm_t* h, int32_t layer, int32_t route, int32_
         auto widen = [](uint16_t b) { const uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; };
         for (size_t i = 0; i < n_out; ++i) out_host[i] = widen(hb[i]) + widen(hb[n_out + i]);
     }
+    return RCA_OK;
+}
+
+// tests only: the decode attention of one layer for the members of a batch pass, launched by the very call the pass makes for it
+// (lm_batch_launch_attn) over tables staged the way the five batch calls stage theirs (lm_batch_check / lm_batch_stage), for
+// host-supplied post-RoPE query rows over whatever the members' caches hold (rca_lm_kv_write)
+extern "C" int rca_lm_batch_attn_tap(rca_lm_batch_t* b, int32_t layer, int32_t n, int32_t nsp_launch, const int32_t* sel, int32_t n_sel, const float* q_host,
+                                     float* out_host, int32_t out_rows) {
+    if (!b || !q_host || !out_host) return fail(RCA_ERR_ARG, "batch_attn_tap: null argument");
+    rca_lm* ws = b->m[0];
+    const rca_lm_config_t& c = ws->cfg;
+    const int QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim;
+    if (layer < 0 || layer >= c.n_layers) return fail(RCA_ERR_ARG, "batch_attn_tap: layer %d outside [0, %d)", layer, c.n_layers);
+    if (n < 1 || n > LM_GEMV_M) return fail(RCA_ERR_ARG, "batch_attn_tap: %d tokens per member (1..%d)", n, LM_GEMV_M);
+    const int32_t ids[LM_BATCH_ROWS] = {};
+    LmBatchCall call{"batch_attn_tap", sel, sel ? n_sel : 0, n, false, 0, ids, nullptr, nullptr, 0};
+    int rc;
+    if ((rc = lm_batch_check(b, call)) != RCA_OK) return rc;
+    const int MT = call.n_sel * n;
+    if (out_rows < MT || out_rows > LM_BATCH_ROWS) return fail(RCA_ERR_ARG, "batch_attn_tap: out_rows %d outside [%d rows of the pass, %d]", out_rows, MT, LM_BATCH_ROWS);
+    int need = 1;
+    for (int k = 0; k < call.n_sel; ++k) need = std::max(need, lm_splits_needed(call.hm[k], n));
+    if (nsp_launch == 0) nsp_launch = need;
+    if (nsp_launch < need || nsp_launch > b->nsp_all)
+        return fail(RCA_ERR_ARG, "batch_attn_tap: nsp_launch %d outside [%d needed, %d splits of the batch]", nsp_launch, need, b->nsp_all);
+    LmBatchPlan p;
+    if ((rc = lm_batch_stage(b, call, &p)) != RCA_OK) return rc;
+    hipStream_t st = ws->stream;
+    RCA_HIP(hipStreamSynchronize(st));
+    RCA_HIP(hipMemcpyAsync(b->sel_stage, b->sel_pin, p.up_bytes, hipMemcpyHostToDevice, st));
+    lm_batch_stage_kernel<<<1, LM_BATCH_ROWS, 0, st>>>(b->sel_stage, p.vw.tab, b->stt, b->stt_head, n);
+    // member k's rows are rows k * n + j of the pass (its table entry's row0 = k * n): the q columns of member 0's qkv
+    RCA_HIP(hipMemcpy2DAsync(ws->qkv, (size_t)QKV * 4, q_host, (size_t)AO * 4, (size_t)AO * 4, MT, hipMemcpyHostToDevice, st));
+    // NaN sentinel (all bits set) in the output rows a caller may look at, and in every partial a live member owns: a partial that the
+    // merge uses although no workgroup of this launch wrote it shows as NaN
+    const size_t n_out = (size_t)out_rows * AO;
+    RCA_HIP(hipMemsetAsync(ws->xh, 0xFF, n_out * 2, st));
+    RCA_HIP(hipMemsetAsync(ws->xl, 0xFF, n_out * 2, st));
+    for (int k = 0; k < call.n_sel; ++k) RCA_HIP(hipMemsetAsync(call.hm[k]->att_part, 0xFF, lm_att_part_bytes(call.hm[k]), st));
+    lm_attn_split_attrs();
+    lm_batch_launch_attn(ws, p.vw.tab, p.vw.NM, n, nsp_launch, lm_kv_q8(ws), layer, st);
+    hipError_t e = hipGetLastError();
+    std::vector<uint16_t> hb(2 * n_out);
+    if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), ws->xh, n_out * 2, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hb.data() + n_out, ws->xl, n_out * 2, hipMemcpyDeviceToHost, st);
+    // later passes read the split buffers in blocks of 128 rows: leave no NaN behind in them
+    if (e == hipSuccess) e = hipMemsetAsync(ws->xh, 0, n_out * 2, st);
+    if (e == hipSuccess) e = hipMemsetAsync(ws->xl, 0, n_out * 2, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "batch_attn_tap: %s", hipGetErrorString(e));
+    auto widen = [](uint16_t v) { const uint32_t u = (uint32_t)v << 16; float f; memcpy(&f, &u, 4); return f; };
+    for (size_t i = 0; i < n_out; ++i) out_host[i] = widen(hb[i]) + widen(hb[n_out + i]);
     return RCA_OK;
 }
 

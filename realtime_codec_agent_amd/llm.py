@@ -1268,6 +1268,25 @@ class LlamaBatch:
                 raise ValueError(f"member {s} outside the batch of {len(self.members)}")
         kv_remove_many([self.members[s] for s in idx], spans)
 
+    def attn_tap(self, layer: int, q: np.ndarray, n: int, nsp_launch: int = 0, sel: Optional[Sequence[int]] = None,
+                 out_rows: Optional[int] = None) -> np.ndarray:
+        """Tests only (rca_lm_batch_attn_tap): the batch pass's decode attention of one layer alone, for n = 1 or 2 post-RoPE query
+        tokens per member, q [members of the pass * n, n_heads * 64] with member k's token j in row k * n + j, at each member's own
+        n_tokens over whatever its cache holds.  sel None: the batch's own table; else the selection table of frame(members=sel).
+        nsp_launch 0: the splits the members need.  Returns [out_rows, n_heads * 64] float32 (the bf16 hi + lo the O projection
+        reads); rows the launch did not write hold NaN.  Every member's n_tokens is left as it was."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        width = self.members[0].config.n_heads * 64
+        nm = len(self.members) if sel is None else len(sel)
+        if q.ndim != 2 or q.shape != (nm * int(n), width):
+            raise ValueError(f"attn_tap: q is [{nm} members x {n} tokens, {width}], got {q.shape}")
+        out_rows = q.shape[0] if out_rows is None else int(out_rows)
+        out = np.empty((max(out_rows, 0), width), np.float32)
+        sl = None if sel is None else (C.c_int32 * max(nm, 1))(*[int(s) for s in sel])
+        N.check(self._lib.rca_lm_batch_attn_tap(self._b, int(layer), int(n), int(nsp_launch), sl, nm if sel is not None else 0, q.ctypes.data,
+                                                out.ctypes.data, out_rows), "rca_lm_batch_attn_tap")
+        return out
+
     def captures(self) -> int:
         """graph captures this batch has made so far (rca_lm_batch_captures): selections of one geometry class (up to 8, 16, 32, 64
         members) share one capture per (steps, context bucket, probes), also after a member's swap_kv"""

@@ -1,6 +1,8 @@
 """Float64 reference, input builders and the error bound of the LM attention kernels run alone (rca_lm_attn_tap), shared by
 tests/test_attn_cpu.py (is the reference the oracle's attention, do the inputs meet their conditions, does the bound have teeth?)
-and tests/test_attn_gpu.py (do lm_attn_mfma_kernel + its two merges and lm_attn_flash_kernel compute it?).
+and tests/test_attn_gpu.py (do lm_attn_mfma_kernel + its two merges and lm_attn_flash_kernel compute it?); the batch pass's table
+instances (rca_lm_batch_attn_tap) are route 3 of the bound, with their ragged batch cases at the end of this file
+(tests/test_attn_batch_gpu.py).
 
 Conventions (rca_lm.hip): q [M][n_heads][64] f32 after RoPE, K / V [T][n_kv_heads][64] fp16 cache rows; the token at index t sits at
 position pos0 + t and sees keys 0 .. pos0 + t; q head h reads kv head h // G; score = q . k / 8; out [M][n_heads * 64].
@@ -40,8 +42,16 @@ not promise round-to-nearest there, a whole ulp covers truncation), X = 2^-22 (v
   FIN: decode O / L, one division: u.  Flash 1 / L and a product: 3 u (a reciprocal within one ulp).  Route 2 stores bf16 hi + lo,
     each rounded to nearest (8-bit significands): 2^-16, and their f32 sum rounds once more: u.
 
+ROUTE 3, "batch decode" (rca_lm_batch_attn_tap: lm_attn_mfma_kernel<G, TAB = true, KVQ> + lm_attn_mfma_batch_combine_kernel<G>).  The
+table instance of the split kernel is the decode kernel with its pointers read from a table, and the batch merge is attn_merge_row,
+the decode route's merge as a launch of its own: score, exp argument, En / FLOOR, ACC and DEN are the decode terms, unchanged, with
+NSPLIT the number of splits the ROW's positions need (splits that are launched beyond them, for a bucket or for a companion with a
+longer context, enter the merge with weight exactly 0).  What differs is the store: O / L (u), then bf16 hi + lo, each rounded to
+nearest (2^-16, as on route 2), and the f32 sum of the two read back (u): FIN = u + 2^-16 + u.  Derived, like the rest.
+
 Nothing here is fitted to a device's output: a correct kernel outside this bound means a missing term, which is to be found and named.
 """
+import functools
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -52,7 +62,8 @@ ATT_KEYS = 256
 u = 2.0 ** -24
 U = 2.0 ** -23
 X = 2.0 ** -22
-ROUTES = {0: "decode", 1: "flash f32", 2: "flash bf16"}
+ROUTES = {0: "decode", 1: "flash f32", 2: "flash bf16", 3: "batch decode"}
+BATCH_ROUTE = 3
 
 
 # ------------------------------------------------------------------ the reference
@@ -68,8 +79,9 @@ class Wrong:
 
 
 def attention(q, K, V, pos0, wrong: Optional[Wrong] = None, with_bound_for: Optional[int] = None):
-    """q [M, nh, 64] f32, K / V [T >= pos0 + M, nkv, 64] fp16 -> out [M, nh * 64] float64; with_bound_for = route (0 / 1 / 2) also
+    """q [M, nh, 64] f32, K / V [T >= pos0 + M, nkv, 64] fp16 -> out [M, nh * 64] float64; with_bound_for = route (a key of ROUTES) also
     returns the bound, same shape."""
+    assert with_bound_for is None or with_bound_for in ROUTES
     q = np.asarray(q)
     M, nh, hd = q.shape
     nkv = K.shape[1]
@@ -120,7 +132,7 @@ def attention(q, K, V, pos0, wrong: Optional[Wrong] = None, with_bound_for: Opti
 
 def _bound(route, Qg, Kg, Vg, S, m, W, L, o, qpos, mask):
     """the module docstring, for the rows of one kv head"""
-    flash = route != 0
+    flash = route in (1, 2)
     T = Kg.shape[0]
     absqk = np.abs(Qg) @ np.abs(Kg).T
     sumk = np.abs(Kg).sum(1)[None, :]
@@ -141,7 +153,7 @@ def _bound(route, Qg, Kg, Vg, S, m, W, L, o, qpos, mask):
         En, floor = 2.0 ** -22, 2.0 ** -25
         acc = 64 * U + (8 + nsp) * u
         den = (17 + 8 + nsp) * u
-        fin = u
+        fin = u + ((2.0 ** -16 + u) if route == BATCH_ROUTE else 0.0)
     a = W * Ec
     Sa = a.sum(1, keepdims=True)
     assert float(Sa.max()) < 0.5, "the weights' relative error bound is not small: the first-order form does not apply"
@@ -318,3 +330,126 @@ def long_case(geom, nsplits, pattern, M=2):
         q = dominant_q(seed + 1, M, nh)
     assert splits_needed(T - M, M) == nsplits
     return K, V, q, T - M
+
+
+# ------------------------------------------------------------------ the batch pass's attention (route 3; test_attn_batch_gpu.py)
+BATCH_GEOMS = {"g1": (12, 12), "g2": (6, 3), "g4": (12, 3)}     # the k768 models of test_lm_batch_gpu.py: name -> (q heads, kv heads)
+# the n_ctx of the 64 twins of a family, in slot order: the first six are all different, 1 / 3 / 33 / 65 / 4 / 3 splits
+BATCH_FAMILY_CTX = (700, 256, 8448, 16640, 1024, 520) + tuple((256, 700, 1024)[i % 3] for i in range(57)) + (520,)
+BATCH_ONEHOT_SHAPES = ((2, 1), (2, 2), (5, 1), (5, 2), (33, 1), (33, 2), (64, 1), (64, 2))      # (members, tokens per member)
+BATCH_BUCKETS = 8                                                                # LM_GRAPH_BUCKETS
+
+
+@dataclass(frozen=True)
+class BatchMember:
+    """one member of a ragged batch case: its own cache size, where its n tokens start, and what its cache and query rows hold --
+    kind "onehot", a name of SCORE_CLASSES (with `offset`), "dominant first" or "dominant last" -- from `seed`"""
+    n_ctx: int
+    pos0: int
+    kind: str
+    seed: int
+    offset: float = 0.0
+
+
+@functools.lru_cache(maxsize=48)
+def _batch_kv(nkv, T, n, kind, seed, offset):
+    if kind == "onehot":
+        return onehot_kv(seed, T, nkv)
+    if kind in SCORE_CLASSES:
+        return class_kv(seed, T, nkv, offset)
+    assert kind in ("dominant first", "dominant last") and T >= 110
+    return dominant_kv(seed, T, nkv, 100 if kind == "dominant first" else T - n - 2)
+
+
+def batch_onehot_targets(seed, n, n_heads, pos0):
+    """[n, n_heads] keys, all different: every token targets its own position on one head; the seams of the 32-key blocks and of the
+    256-key splits, the first key of the token's last split and the key before its own where it sees them; random visible keys
+    for the rest"""
+    assert pos0 + 1 >= 2 * n_heads
+    rng = np.random.default_rng(seed + 7)
+    tg = np.empty((n, n_heads), np.int64)
+    used = set()
+    for j in range(n):
+        last = pos0 + j
+        must = list(dict.fromkeys(k for k in (0, 31, 32, 255, 256, 511, 512, (last // ATT_KEYS) * ATT_KEYS, last - 1) if 0 <= k < last and k not in used))
+        rng.shuffle(must)
+        row = [last] + must[:n_heads - 1]
+        free = np.array([k for k in range(last) if k not in used and k not in row])
+        row += rng.choice(free, n_heads - len(row), replace=False).tolist()
+        tg[j] = rng.permutation(row)
+        used |= set(row)
+    return tg
+
+
+def batch_member_inputs(geom, n, mb):
+    """(K, V, q, targets): K / V [pos0 + n, nkv, 64] fp16, the rows the member's cache holds from position 0 on; q [n, nh, 64] f32;
+    targets [n, nh] for a one-hot member, else None"""
+    nh, nkv = BATCH_GEOMS[geom]
+    assert 0 <= mb.pos0 and mb.pos0 + n <= mb.n_ctx
+    K, V = _batch_kv(nkv, mb.pos0 + n, n, mb.kind, mb.seed, mb.offset)
+    if mb.kind == "onehot":
+        tg = batch_onehot_targets(mb.seed, n, nh, mb.pos0)
+        return K, V, onehot_q(K, tg, nh), tg
+    if mb.kind in SCORE_CLASSES:
+        return K, V, class_q(mb.seed + 1, n, nh, SCORE_CLASSES[mb.kind], mb.offset), None
+    return K, V, dominant_q(mb.seed + 1, n, nh), None
+
+
+def batch_reference(geom, n, members, kv=None, wrong=None):
+    """(want, bound) [len(members) * n, nh * 64] of a batch case on route 3, member k's token j in row k * n + j; kv: the rows the
+    caches really hold, [(K, V)] per member (a q8_0 cache: the de-quantised rows), instead of the planted ones"""
+    outs = []
+    for k, mb in enumerate(members):
+        K, V, q, _ = batch_member_inputs(geom, n, mb)
+        if kv is not None:
+            K, V = kv[k]
+        outs.append(attention(q, K, V, mb.pos0, wrong, with_bound_for=BATCH_ROUTE))
+    return np.concatenate([o for o, _ in outs]), np.concatenate([b for _, b in outs])
+
+
+def batch_onehot_members(nm, n):
+    """the first nm twins of a family, every one with a seed of its own, started at the seams of the blocks and splits or at its
+    last slot"""
+    out = []
+    for s, c in enumerate(BATCH_FAMILY_CTX[:nm]):
+        pool = (24, 25, 254, 255, 256, 257, 300, 511, 512, c - n)
+        p = pool[s % len(pool)]
+        out.append(BatchMember(c, p if p + n <= c else c - n, "onehot", 9000 + s))
+    return out
+
+
+def batch_class_members(cls, offset):
+    """n = 2; five members with inputs of their own: 642 / 702 keys, the last slots of a 700 and a 1024 cache (the context limit inside
+    / at the end of the last split), and the split seam of a long cache"""
+    seed = 12000 + 97 * list(SCORE_CLASSES).index(cls) + 11 * OFFSETS.index(offset)
+    return [BatchMember(c, p, cls, seed + 2 * k, offset) for k, (c, p) in enumerate(((700, 640), (1024, 700), (700, 698), (8448, 255), (1024, 1022)))]
+
+
+def batch_seam_members(n):
+    """every start of {0, 1, 254, 255, 256, 257, 511, 512, n_ctx - n}: n = 2 straddles a split at 255 (token 0 in one split, token 1
+    in two) and at 511, and ends on the context limit of every cache size"""
+    spec = ((256, 0), (700, 1), (700, 254), (700, 255), (1024, 256), (520, 257), (700, 511), (1024, 512),
+            (700, 700 - n), (256, 256 - n), (1024, 1024 - n), (520, 520 - n))
+    return [BatchMember(c, p, "moderate", 13000 + 2 * k) for k, (c, p) in enumerate(spec)]
+
+
+BATCH_RAGGED = ("last", "short", "mixed")
+
+
+def batch_ragged_members(n, variant):
+    """caches of 1, 3, 33 and 65 splits in one batch.  last: every member at its last slot.  short: the long caches at short contexts
+    (launched splits beyond their context: the empty-split path).  mixed: the 65-split cache at exactly 32 splits of context next to
+    the 33-split cache at its end."""
+    spec = {"last": ((256, 256 - n, "moderate"), (700, 700 - n, "moderate"), (8448, 8448 - n, "dominant first"), (16640, 16640 - n, "dominant last")),
+            "short": ((256, 256 - n, "moderate"), (700, 511, "moderate"), (8448, 300, "dominant last"), (16640, 255, "dominant first")),
+            "mixed": ((256, 100, "moderate"), (700, 256, "moderate"), (8448, 8448 - n, "dominant last"), (16640, 8192 - n, "dominant first"))}[variant]
+    return [BatchMember(c, p, kind, 14000 + 10 * BATCH_RAGGED.index(variant) + 2 * k) for k, (c, p, kind) in enumerate(spec)]
+
+
+def batch_launches(members, n):
+    """the split counts a batch pass over these members can be launched with: what they need now (0) and every graph bucket's
+    min(all members' splits, 4 << bucket) from there up; the last bucket launches all"""
+    need = max(splits_needed(mb.pos0, n) for mb in members)
+    nsp_all = max(-(-mb.n_ctx // ATT_KEYS) for mb in members)
+    buckets = {nsp_all if b + 1 == BATCH_BUCKETS else min(nsp_all, 4 << b) for b in range(BATCH_BUCKETS)}
+    return [0] + sorted(x for x in buckets if x >= need)

@@ -1,7 +1,9 @@
 """tests/attn_ref.py checked on the host: the float64 reference is the attention inside oracle.lm_ref.LMRef, every input builder meets
 the conditions its docstring states, and the derived bound has teeth: on the very inputs tests/test_attn_gpu.py uses, wrong
 attentions (exchanged V rows, a dropped key, a mask off by one, exchanged kv heads, a dropped split, a missing max) lie at least
-PROBE_FACTOR bounds away from the right one."""
+PROBE_FACTOR bounds away from the right one.  The same for the batch pass's attention (route 3, tests/test_attn_batch_gpu.py): every
+ragged batch case meets the bound's precondition and its own conditions, and the wrong attentions, another member's cache, a
+neighbour's rows and token 1 in token 0's row are all seen."""
 import functools
 
 import numpy as np
@@ -192,3 +194,123 @@ def test_bound_sees_a_dropped_split_on_the_long_inputs(geom):
             r = _probe(("long", geom, nsp, pattern), q, K, V, pos0, 0, Wrong(drop_split=drop))
             print(f"{geom} {nsp} splits, {pattern}: split {drop} dropped = {r:.3g} bounds")
             assert r >= PROBE_FACTOR, (geom, nsp, pattern, r)
+
+
+# ------------------------------------------------------------------ the batch pass's attention (route 3)
+def _batch_cases():
+    """(tag, n, members) of every case tests/test_attn_batch_gpu.py plants"""
+    for nm, n in ar.BATCH_ONEHOT_SHAPES:
+        yield ("onehot", nm, n), n, ar.batch_onehot_members(nm, n)
+    for cls in ar.SCORE_CLASSES:
+        for off in ar.OFFSETS:
+            yield ("class", cls, off), 2, ar.batch_class_members(cls, off)
+    for n in (1, 2):
+        yield ("seams", n), n, ar.batch_seam_members(n)
+        for variant in ar.BATCH_RAGGED:
+            yield ("ragged", variant, n), n, ar.batch_ragged_members(n, variant)
+
+
+@functools.lru_cache(maxsize=None)
+def _batch_right(geom, n, mb):
+    K, V, q, _ = ar.batch_member_inputs(geom, n, mb)
+    return ar.attention(q, K, V, mb.pos0, with_bound_for=ar.BATCH_ROUTE)
+
+
+def _batch_probe(geom, n, mb, wrong, rows=slice(None)):
+    K, V, q, _ = ar.batch_member_inputs(geom, n, mb)
+    o, b = _batch_right(geom, n, mb)
+    with np.errstate(invalid="ignore"):       # a token that is left without a visible key comes out NaN: infinitely far
+        return ar.far(ar.attention(q, K, V, mb.pos0, wrong)[rows], o[rows], b[rows])
+
+
+@pytest.mark.parametrize("geom", list(ar.BATCH_GEOMS))
+def test_batch_cases_meet_the_bounds_precondition_and_their_own_conditions(geom):
+    """every member of every batch case: the bound's first-order form applies (attention() asserts S_a < 0.5 where it forms the
+    bound); it fits its cache; one-hot members lead by 40 nats with targets that all differ, each token's own position among them;
+    the ragged cases launch both sides of CMB_PRE = 32 and of the merge's 64-split tail; the family has a twin for every member"""
+    nh, nkv = ar.BATCH_GEOMS[geom]
+    lead, splits = np.inf, set()
+    for tag, n, members in _batch_cases():
+        assert len(members) * n <= 128 and 2 <= len(members) <= 64
+        pool = list(ar.BATCH_FAMILY_CTX)
+        for mb in members:
+            pool.remove(mb.n_ctx)                                             # ValueError: the family has no twin left with this n_ctx
+            K, V, q, tg = ar.batch_member_inputs(geom, n, mb)
+            want, bound = _batch_right(geom, n, mb)
+            assert np.isfinite(want).all() and np.isfinite(bound).all() and (bound > 0).all(), (tag, mb)
+            if tg is not None:
+                assert len(set(tg.ravel().tolist())) == tg.size and all(mb.pos0 + j in tg[j] for j in range(n)), (tag, mb)
+                lead = min(lead, ar.onehot_lead(K, tg, nh, mb.pos0))
+                heads = np.arange(nh) // (nh // nkv)
+                assert np.abs(want - V[tg, heads[None, :]].astype(np.float64).reshape(want.shape)).max() < 1e-9
+            if tag[0] == "ragged":
+                splits.add(ar.splits_needed(mb.pos0, n))
+        if tag[0] == "ragged":
+            splits |= set(ar.batch_launches(members, n))
+    print(f"{geom}: smallest one-hot lead of the batch members {lead:.1f} nats; ragged split counts {sorted(splits)}")
+    assert lead >= 40.0                                                       # if this fails: reseed, do not lower 40
+    assert {1, 3, 32, 33, 64, 65} <= splits
+    for n in (1, 2):                                                          # -1: the member's last slot, n_ctx - n
+        starts = [mb.pos0 if mb.pos0 + n < mb.n_ctx else -1 for mb in ar.batch_seam_members(n)]
+        assert set(starts) == {0, 1, 254, 255, 256, 257, 511, 512, -1} and starts.count(-1) == 4, starts
+
+
+@pytest.mark.parametrize("geom", list(ar.BATCH_GEOMS))
+def test_batch_bound_sees_the_wrong_attentions(geom):
+    """the route-3 bound has teeth on the batch cases, each wrong variant where it can bite: one-hot members (the target's V row
+    exchanged inside its 32-key block, the target dropped, the mask one short at the row that targets its own position), class
+    members (kv heads exchanged, a split dropped; the flat class without offset: the mask one long), long ragged members (the split
+    that holds the dominant key dropped)"""
+    nh, nkv = ar.BATCH_GEOMS[geom]
+    worst = {}
+
+    def note(k, r):
+        worst[k] = min(worst.get(k, np.inf), r)
+
+    for nm, n in ((5, 2), (33, 1)):
+        for mb in ar.batch_onehot_members(nm, n)[::4]:
+            tg = ar.batch_member_inputs(geom, n, mb)[3]
+            for t in {int(tg[0, 0]), int(tg[-1, -1]), mb.pos0, mb.pos0 + n - 1}:
+                other = t ^ 1 if (t ^ 1) < mb.pos0 + n else t - 1
+                note("swap_v", _batch_probe(geom, n, mb, Wrong(swap_v=(t, other))))
+                note("drop_key", _batch_probe(geom, n, mb, Wrong(drop_key=t)))
+            note("mask_shift -1", _batch_probe(geom, n, mb, Wrong(mask_shift=-1)))
+    for cls in ar.SCORE_CLASSES:
+        for off in ar.OFFSETS:
+            for mb in ar.batch_class_members(cls, off):
+                note("swap_kv_heads", _batch_probe(geom, 2, mb, Wrong(swap_kv_heads=(0, 1))))
+                for sp in range(ar.splits_needed(mb.pos0, 1)):           # every split both tokens see keys of
+                    note("drop_split", _batch_probe(geom, 2, mb, Wrong(drop_split=sp)))
+                if cls == "flat" and off == 0:
+                    note("mask_shift +1", _batch_probe(geom, 2, mb, Wrong(mask_shift=1), rows=slice(0, 1)))
+                    note("mask_shift -1", _batch_probe(geom, 2, mb, Wrong(mask_shift=-1)))
+    for variant in ar.BATCH_RAGGED:
+        for mb in ar.batch_ragged_members(2, variant):
+            if mb.kind.startswith("dominant"):
+                sp = 0 if mb.kind == "dominant first" else (mb.pos0 - 2) // ar.ATT_KEYS
+                note("drop_split (dominant)", _batch_probe(geom, 2, mb, Wrong(drop_split=sp)))
+    print(f"{geom} batch probes, in bounds: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert set(worst) == {"swap_v", "drop_key", "mask_shift -1", "mask_shift +1", "swap_kv_heads", "drop_split", "drop_split (dominant)"}
+    assert min(worst.values()) >= PROBE_FACTOR, worst
+
+
+@pytest.mark.parametrize("geom", list(ar.BATCH_GEOMS))
+def test_batch_bound_sees_a_wrong_table_entry_and_a_wrong_row0(geom):
+    """what only a batch can get wrong: member A's rows computed over member B's cache and position (a wrong table entry), the
+    rows of a member written where its neighbour's belong (a wrong row0), token 1 written over token 0 (row0 + m without the m)"""
+    worst = {"table": np.inf, "row0": np.inf, "token": np.inf}
+    for tag, n, members in _batch_cases():
+        if tag[0] == "onehot" and tag[1] > 5:
+            continue
+        want, bound = ar.batch_reference(geom, n, members)
+        for k, mb in enumerate(members):
+            other = members[(k + 1) % len(members)]
+            rows, orows = slice(k * n, k * n + n), slice(((k + 1) % len(members)) * n, ((k + 1) % len(members)) * n + n)
+            worst["row0"] = min(worst["row0"], ar.far(want[orows], want[rows], bound[rows]))
+            q = ar.batch_member_inputs(geom, n, mb)[2]
+            Ko, Vo = ar.batch_member_inputs(geom, n, other)[:2]
+            worst["table"] = min(worst["table"], ar.far(ar.attention(q, Ko, Vo, other.pos0), want[rows], bound[rows]))
+            if n == 2 and not mb.kind.startswith("dominant"):     # (both tokens of a dominant member attend to the one planted key)
+                worst["token"] = min(worst["token"], ar.far(want[k * n + 1], want[k * n], bound[k * n]))
+    print(f"{geom} batch-only probes, in bounds: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert min(worst.values()) >= PROBE_FACTOR, worst
