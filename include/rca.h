@@ -559,6 +559,25 @@ int rca_lm_logits_dev(rca_lm_t* h, const float** out_dev);
 
 /* init_sampler_for_generate (llamacpp_utils.py:39-77) */
 int rca_lm_sampler_init(rca_lm_t* h, const rca_sampler_params_t* p);
+/* The two members of llama-cpp-python's chain that rca_sampler_params_t does not carry (llamacpp_utils.py:39-77 forwards typical_p,
+ * mirostat_mode, mirostat_tau, mirostat_eta).  Valid after rca_lm_sampler_init, which resets both to off; each settles the stream,
+ * and a change of the sampler's launches drops the captured graphs.  Restated from the published definitions: tests/samp_ext_ref.py is
+ * the definition, parity with llama.cpp is not pinned ("typical_p and mirostat v2").
+ * rca_lm_sampler_set_typical: llama.cpp's locally typical cut between top_k and top_p on the serial chain (temp > 0, top_k 1..256):
+ *   over the top_k candidates, keep the shortest prefix in order of |-ln p - H| (ties to the better rank) whose mass exceeds
+ *   typical_p, at least one token; the survivors go on to top_p / min_p / temp as a fresh candidate list.  typical_p >= 1 or 0 = off;
+ *   temp <= 0 (greedy) and mirostat v2 ignore it.  RCA_ERR_ARG, naming the value: negative or NaN; typical_p < 1 with temp > 0 and
+ *   top_k outside 1..256 (the whole vocabulary is not sorted by typicality).
+ * rca_lm_sampler_set_mirostat: mode 0 = off, 2 = mirostat v2 -- the chain is then logit bias -> penalties -> temp -> mirostat, and
+ *   top_k, top_p, min_p and typical_p are IGNORED, as llama-cpp-python leaves them out.  Per draw: the whole vocabulary cut at a
+ *   surprise (-log2 p) of mu, the top token always kept; the draw by the Gumbel-max rule of the whole-vocabulary sampler with the same
+ *   keyed RNG; mu <- mu - eta (observed surprise - tau).  Sums over the vocabulary are 2^-40 fixed point.  mu = 2 tau after this call.
+ *   mu is a function of the draw counter: whatever rewinds the counter (a cut rca_lm_frame, a cut batch frame) rewinds mu.
+ *   temp <= 0 stays greedy.  RCA_ERR_ARG: mode 1 (v1 is not built), any other mode, tau or eta negative, NaN or infinite.
+ * rca_lm_sampler_get_mirostat_mu: settles the stream; the mu the next draw will read.  RCA_ERR_STATE when mirostat is off. */
+int rca_lm_sampler_set_typical(rca_lm_t* h, float typical_p);
+int rca_lm_sampler_set_mirostat(rca_lm_t* h, int32_t mode, float tau, float eta);
+int rca_lm_sampler_get_mirostat_mu(rca_lm_t* h, float* mu);
 /* sample() (llamacpp_utils.py:79-95): draw from the last logits */
 int rca_lm_sample(rca_lm_t* h, int32_t* token);
 /* next(generate(tokens, reset=False)) (llamacpp_utils.py:145-161; realtime_agent_v2.py:355):

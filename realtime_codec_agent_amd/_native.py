@@ -533,7 +533,14 @@ ABI_SYMBOLS = [
     "rca_lm_gemv_tap_form",
     "rca_lm_set_kv_shift_requant", "rca_lm_get_kv_shift_requant",
     "rca_lm_batch_attn_tap",
+    "rca_lm_sampler_set_typical", "rca_lm_sampler_set_mirostat", "rca_lm_sampler_get_mirostat_mu",
 ]
+# float arguments by value: without a prototype ctypes would pass them as ints
+SAMPLER_EXT_ARGTYPES = {
+    "rca_lm_sampler_set_typical": [C.c_void_p, C.c_float],
+    "rca_lm_sampler_set_mirostat": [C.c_void_p, C.c_int32, C.c_float, C.c_float],
+    "rca_lm_sampler_get_mirostat_mu": [C.c_void_p, C.POINTER(C.c_float)],
+}
 
 
 def lib():
@@ -586,6 +593,10 @@ def lib():
     for name in ("rca_lm_kv_remove_many", "rca_lm_kv_remove_many_staged"):
         if hasattr(_lib, name):
             getattr(_lib, name).argtypes = KV_REMOVE_MANY_ARGTYPES
+            getattr(_lib, name).restype = C.c_int
+    for name, argtypes in SAMPLER_EXT_ARGTYPES.items():
+        if hasattr(_lib, name):
+            getattr(_lib, name).argtypes = argtypes
             getattr(_lib, name).restype = C.c_int
     return _lib
 

@@ -73,6 +73,10 @@ struct SamplerDev {
     int patch;      // 1: logit bias and / or penalties are applied IN PLACE by samp_prepare_kernel and undone by the sampler's last kernel
     int big_k;      // > 0: the "big" path cuts at this rank (top_k > SAMP_MAXK); 0: no rank cut
     int big_p;      // 1: the "big" path cuts at top_p of the candidates' mass (fixed point)
+    // ---- rca_lm_sampler_set_typical / _set_mirostat (appended: the kernels from before them read none of these)
+    float typical_p;   // in (0, 1): samp_final_typ_kernel cuts the serial chain's candidates to the locally typical set; anything else = off
+    int miro;          // 2: mirostat v2 (the samp_miro_* launches); 0 = off
+    float miro_tau, miro_eta;
 };
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -1229,6 +1233,10 @@ struct SampWork {
     float ov_orig[SAMP_OV_CAP];
     unsigned long long rhist[2][SAMP_LEVELS][SAMP_BINS];   // [0] rank (counts) / [1] mass (2^-40 fixed point) histograms of the radix selects
     unsigned long long rstate[2][SAMP_LEVELS][2];          // after level l: {key prefix fixed so far, what is still needed inside it}
+    // ---- mirostat v2
+    float mu_ring[SAMP_RING];              // mu BEFORE draw c sits in mu_ring[c % SAMP_RING]: draw c reads its slot and writes the next, so whatever
+                                           // rewinds LmDevState::rng_counter rewinds mu with it (like `ring`, a cut frame only rewinds the counter)
+    unsigned long long miro_part[2][64];   // per slice: [0] mass of the slice, [1] mass of its kept tokens (2^-40 fixed point)
 };
 
 // The value the sampler sees for token i.  Logit bias and penalties are NOT applied here any more: samp_prepare_kernel writes the
@@ -1401,6 +1409,83 @@ struct SampTail {
     float* x;
     int H;
 };
+// llama.cpp's locally typical sampler (llama_sampler_typical_apply) between top_k and top_p, restated in float32 over the cnt sorted
+// candidates of the serial chain (tests/samp_ext_ref.py is the definition; parity with llama.cpp is not pinned).  With
+// d_i = v_i - v_0, e_i = rca_expf(d_i), tot = e_0 + e_1 + ... (serial, in rank order) and L = rca_logf(tot):
+//   -ln p_i = L - d_i (no logarithm of a small p),  p_i = e_i * (1 / tot),  H = sum of p_i * (L - d_i) (serial, in rank order),
+//   s_i = |(L - d_i) - H|.  A candidate with e_i == 0 (a -inf logit, or d_i < -87) adds nothing to H and has s_i = +inf.
+// Order by (s ascending, rank ascending) -- a counting rank -- and keep the shortest prefix whose serial sum of e exceeds
+// typical_p * tot.  The survivors go on in logit order as a fresh candidate list: both exponentials are taken again relative to the
+// survivors' maximum (llama.cpp's re-sort and softmax inside top_p), so top_p sees their total mass and min_p their best token.
+// Called by every thread of the workgroup; returns the number of survivors (cnt when the cut is off).  No product feeds a sum inside
+// one expression, and contraction is off, so that the restatement's single float32 operations are these.
+__device__ __forceinline__ int samp_typical_cut(const SamplerDev* __restrict__ sp, int cnt, unsigned long long* cand, float* cval, float* e_plain,
+                                                float* e_temp) {
+#pragma clang fp contract(off)
+    __shared__ float t_nl[SAMP_MAXK], t_term[SAMP_MAXK], t_s[SAMP_MAXK];
+    __shared__ int t_order[SAMP_MAXK], t_keep[SAMP_MAXK];
+    __shared__ float t_tot, t_H;
+    __shared__ int t_cnt;
+    const int tid = threadIdx.x;
+    const float typ = sp->typical_p;
+    if (!(sp->temp > 0.0f) || cnt <= 1 || !(typ > 0.0f && typ < 1.0f)) return cnt;
+    if (tid == 0) {
+        float tot = 0.0f;
+        for (int i = 0; i < cnt; ++i) tot += e_plain[i];
+        t_tot = tot;
+    }
+    __syncthreads();
+    const float tot = t_tot, L = rca_logf(tot), inv = 1.0f / tot;
+    if (tid < cnt) {
+        const float e = e_plain[tid];
+        const float nl = L - (cval[tid] - cval[0]);
+        const float p = e * inv;
+        t_nl[tid] = nl;
+        t_term[tid] = e > 0.0f ? p * nl : 0.0f;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float H = 0.0f;
+        for (int i = 0; i < cnt; ++i) H += t_term[i];
+        t_H = H;
+    }
+    __syncthreads();
+    if (tid < cnt) { t_s[tid] = e_plain[tid] > 0.0f ? fabsf(t_nl[tid] - t_H) : INFINITY; t_keep[tid] = 0; }
+    __syncthreads();
+    if (tid < cnt) {
+        const float si = t_s[tid];
+        int rank = 0;
+        for (int j = 0; j < cnt; ++j) rank += (t_s[j] < si || (t_s[j] == si && j < tid)) ? 1 : 0;
+        t_order[rank] = tid;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const float need = typ * tot;
+        float cum = 0.0f;
+        for (int r = 0; r < cnt; ++r) {
+            const int i = t_order[r];
+            cum += e_plain[i];
+            t_keep[i] = 1;
+            if (cum > need) break;
+        }
+        int m = 0;
+        for (int i = 0; i < cnt; ++i)
+            if (t_keep[i]) { cand[m] = cand[i]; cval[m] = cval[i]; ++m; }
+        t_cnt = m;
+    }
+    __syncthreads();
+    const int m = t_cnt;
+    if (tid < m) {
+        const float d = cval[tid] - cval[0];
+        e_plain[tid] = rca_expf(d);
+        e_temp[tid] = rca_expf(d * (1.0f / sp->temp));
+    }
+    __syncthreads();
+    return m;
+}
+// TYP: the instance behind samp_final_typ_kernel, which a handle launches only with rca_lm_sampler_set_typical in force; the <false>
+// instance holds no trace of the typical cut.
+template <bool TYP>
 __device__ __forceinline__ void samp_final_body(float* logits, int V, const SamplerDev* __restrict__ sp,
                                                 LmDevState* __restrict__ stt, SampWork* __restrict__ w, const SampTail& tail) {
     __shared__ unsigned long long s_draw;
@@ -1505,8 +1590,10 @@ __device__ __forceinline__ void samp_final_body(float* logits, int V, const Samp
         e_temp[tid] = rca_expf((cval[tid] - mx) * (1.0f / sp->temp));
     }
     __syncthreads();
+    int typ_cnt = 0;
+    if constexpr (TYP) typ_cnt = samp_typical_cut(sp, min(n, k), cand, cval, e_plain, e_temp);
     if (tid == 0) {
-        int cnt = min(n, k);
+        int cnt = TYP ? typ_cnt : min(n, k);
         int pick = 0;
         if (!greedy && cnt > 1) {
             if (sp->top_p < 1.0f) {  // smallest prefix whose probability mass reaches top_p
@@ -1568,7 +1655,7 @@ __device__ __forceinline__ void samp_final_body(float* logits, int V, const Samp
 }
 __global__ __launch_bounds__(1024) void samp_final_kernel(float* logits, int V, const SamplerDev* __restrict__ sp,
                                                           LmDevState* __restrict__ stt, SampWork* __restrict__ w, SampTail tail) {
-    samp_final_body(logits, V, sp, stt, w, tail);
+    samp_final_body<false>(logits, V, sp, stt, w, tail);
 }
 
 // ---- top_k <= 0: llama.cpp's "whole vocabulary" (its top-k sampler is then a no-op; llamacpp_utils.py:39-77 passes top_k straight
@@ -2374,6 +2461,9 @@ struct rca_lm {
     bool sampler_set = false;
     bool samp_full = false;     // top_k <= 0 or > SAMP_MAXK: the whole-vocabulary (Gumbel-max) sampler launches instead of the top-k ones
     bool samp_patch = false, samp_big_k = false, samp_big_p = false;   // which other sampler launches a captured step holds (rca_lm_sampler_init)
+    bool samp_typ = false;      // rca_lm_sampler_set_typical in force on the serial chain: samp_final_typ_kernel closes it
+    bool samp_miro = false;     // rca_lm_sampler_set_mirostat(2) in force (temp > 0): the samp_miro_* launches, whatever top_k says
+    SamplerDev samp_host = {};  // what h->samp holds (rca_lm_sampler_init; the two calls above change single fields)
     // captured steady-state steps (n = 1, 2)
     // decode-step graphs per (tokens 1..2, context bucket): bucket b launches min(n_splits, 4 << b) attention splits
     // Two sets: the handle's KV cache can be exchanged with a twin's (rca_lm_swap_kv) and the cache address is baked into the
@@ -6151,17 +6241,90 @@ extern "C" int rca_lm_sampler_init(rca_lm_t* h, const rca_sampler_params_t* p) {
     RCA_HIP(hipMemcpy(&h->stt->rng_counter, &zero, 8, hipMemcpyHostToDevice));
     h->rng_host = 0;
     h->sampler_set = true;
-    if (full != h->samp_full || patch != h->samp_patch || big_k != h->samp_big_k || big_p != h->samp_big_p)
+    if (full != h->samp_full || patch != h->samp_patch || big_k != h->samp_big_k || big_p != h->samp_big_p || h->samp_typ || h->samp_miro)
         lm_drop_graphs(h);   // the captured steps hold another set of sampler launches
     h->samp_full = full; h->samp_patch = patch; h->samp_big_k = big_k; h->samp_big_p = big_p;
+    h->samp_typ = h->samp_miro = false;   // both options are off after every init (s.typical_p = 0, s.miro = 0)
+    h->samp_host = s;
     return RCA_OK;
 }
 
+// typical_p and mirostat v2 ride on the sampler rca_lm_sampler_init set up: one field of SamplerDev each, and the choice of launches
+static int lm_sampler_route(rca_lm* h, const SamplerDev& s) {
+    const bool stoch = s.temp > 0.0f;
+    const bool miro = stoch && s.miro == 2;
+    const bool typ = stoch && !miro && s.typical_p > 0.0f && s.typical_p < 1.0f;
+    if (typ && (s.top_k < 1 || s.top_k > SAMP_MAXK))
+        return fail(RCA_ERR_ARG, "sampler: typical_p %g needs top_k in 1..%d (top_k is %d): the whole vocabulary is not sorted by typicality",
+                    (double)s.typical_p, SAMP_MAXK, s.top_k);
+    RCA_HIP(hipSetDevice(h->device));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    RCA_HIP(hipMemcpy(h->samp, &s, sizeof(s), hipMemcpyHostToDevice));
+    if (typ != h->samp_typ || miro != h->samp_miro) lm_drop_graphs(h);
+    h->samp_typ = typ; h->samp_miro = miro;
+    h->samp_host = s;
+    return RCA_OK;
+}
+extern "C" int rca_lm_sampler_set_typical(rca_lm_t* h, float typical_p) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    if (!h->sampler_set) return fail(RCA_ERR_STATE, "sampler not initialised");
+    if (!(typical_p >= 0.0f)) return fail(RCA_ERR_ARG, "sampler: typical_p %g must be 0 (unset) or positive", (double)typical_p);
+    SamplerDev s = h->samp_host;
+    s.typical_p = typical_p;
+    return lm_sampler_route(h, s);
+}
+extern "C" int rca_lm_sampler_set_mirostat(rca_lm_t* h, int32_t mode, float tau, float eta) {
+    if (!h) return fail(RCA_ERR_ARG, "null");
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    if (!h->sampler_set) return fail(RCA_ERR_STATE, "sampler not initialised");
+    if (mode == 1) return fail(RCA_ERR_ARG, "sampler: mirostat_mode 1 (v1) is not built: its k is computed per draw and can land on any route; use 0 or 2");
+    if (mode != 0 && mode != 2) return fail(RCA_ERR_ARG, "sampler: mirostat_mode %d is none of 0 (off), 2 (v2)", mode);
+    if (mode == 2 && !(tau >= 0.0f && tau <= 3.0e38f)) return fail(RCA_ERR_ARG, "sampler: mirostat_tau %g must be finite and not negative", (double)tau);
+    if (mode == 2 && !(eta >= 0.0f && eta <= 3.0e38f)) return fail(RCA_ERR_ARG, "sampler: mirostat_eta %g must be finite and not negative", (double)eta);
+    SamplerDev s = h->samp_host;
+    s.miro = mode; s.miro_tau = mode == 2 ? tau : 0.0f; s.miro_eta = mode == 2 ? eta : 0.0f;
+    const int rc = lm_sampler_route(h, s);
+    if (rc != RCA_OK) return rc;
+    if (mode == 2) {   // mu = 2 tau before the next draw, whichever it is (llamacpp_utils.py:60): every slot, so the counter need not be read
+        std::vector<float> mu(SAMP_RING, 2.0f * tau);
+        RCA_HIP(hipMemcpy(h->swork->mu_ring, mu.data(), sizeof(float) * SAMP_RING, hipMemcpyHostToDevice));
+    }
+    return RCA_OK;
+}
+extern "C" int rca_lm_sampler_get_mirostat_mu(rca_lm_t* h, float* mu) {
+    if (!h || !mu) return fail(RCA_ERR_ARG, "null");
+    { const int src = lm_settle(h); if (src != RCA_OK) return src; }
+    if (!h->sampler_set || h->samp_host.miro != 2) return fail(RCA_ERR_STATE, "mirostat is off (rca_lm_sampler_set_mirostat)");
+    RCA_HIP(hipSetDevice(h->device));
+    RCA_HIP(hipStreamSynchronize(h->stream));
+    unsigned long long c = 0;
+    RCA_HIP(hipMemcpy(&c, &h->stt->rng_counter, 8, hipMemcpyDeviceToHost));
+    RCA_HIP(hipMemcpy(mu, &h->swork->mu_ring[c % SAMP_RING], 4, hipMemcpyDeviceToHost));
+    return RCA_OK;
+}
+
+// (the kernels of the two opt-in samplers are defined at the end of this file, behind every kernel that was here before them, so that
+// the code object lays those out as it did)
+__global__ void samp_final_typ_kernel(float* logits, int V, const SamplerDev* __restrict__ sp, LmDevState* __restrict__ stt, SampWork* __restrict__ w,
+                                      SampTail tail);
+__global__ void samp_miro_mass_kernel(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp, SampWork* __restrict__ w);
+__global__ void samp_miro_pick_kernel(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp, const LmDevState* __restrict__ stt,
+                                      SampWork* __restrict__ w);
+__global__ void samp_miro_final_kernel(float* logits, int V, const SamplerDev* __restrict__ sp, LmDevState* __restrict__ stt, SampWork* __restrict__ w,
+                                       SampTail tail);
 // frame_i >= 0: step i of a frame graph -- the sampler's tail also advances the device state and gathers the next pair's embeddings
 static void lm_enqueue_sample(rca_lm* h, float* lg, hipStream_t st, int frame_i = -1) {
     const int V = h->cfg.vocab_size;
     const SampTail tail{frame_i, h->embed, h->embed_f32, h->x, h->cfg.hidden};
     if (h->samp_patch) samp_prepare_kernel<<<1, 128, 0, st>>>(lg, V, h->samp, h->stt, h->swork);   // logit bias / penalties, in place
+    if (h->samp_miro) {   // mirostat v2: the whole vocabulary cut at a surprise of mu, whatever top_k / top_p / min_p / typical_p say
+        samp_full_max_kernel<<<SAMPF_SLICES, 1024, 0, st>>>(lg, V, h->samp, h->swork);
+        samp_miro_mass_kernel<<<SAMPF_SLICES, 1024, 0, st>>>(lg, V, h->samp, h->swork);
+        samp_miro_pick_kernel<<<SAMPF_SLICES, 1024, 0, st>>>(lg, V, h->samp, h->stt, h->swork);
+        samp_miro_final_kernel<<<1, 1024, 0, st>>>(lg, V, h->samp, h->stt, h->swork, tail);
+        return;
+    }
     if (h->samp_full) {   // top_k <= 0 or > SAMP_MAXK: whole vocabulary (Gumbel-max), with a rank and / or mass threshold on the big path
         samp_full_max_kernel<<<SAMPF_SLICES, 1024, 0, st>>>(lg, V, h->samp, h->swork);
         if (h->samp_big_k || h->samp_big_p) {
@@ -6179,8 +6342,11 @@ static void lm_enqueue_sample(rca_lm* h, float* lg, hipStream_t st, int frame_i 
     }
     samp_hist_kernel<<<128, 256, 0, st>>>(lg, V, h->samp, h->swork);
     samp_gather_kernel<<<128, 256, 0, st>>>(lg, V, h->samp, h->swork);
-    samp_final_kernel<<<1, 1024, 0, st>>>(lg, V, h->samp, h->stt, h->swork, tail);
+    if (h->samp_typ) samp_final_typ_kernel<<<1, 1024, 0, st>>>(lg, V, h->samp, h->stt, h->swork, tail);
+    else samp_final_kernel<<<1, 1024, 0, st>>>(lg, V, h->samp, h->stt, h->swork, tail);
 }
+// a member of a batch whose sampler the table kernels do not run: its own launches follow the pass (lm_enqueue_sample)
+static inline bool lm_samp_own_launches(const rca_lm* h) { return h->samp_full || h->samp_typ || h->samp_miro; }
 
 static int lm_fetch_token(rca_lm* h, int32_t* token, hipStream_t st) {
     RCA_HIP(hipMemcpyAsync(&h->h_stt->out_token, &h->stt->out_token, 4, hipMemcpyDeviceToHost, st));
@@ -6781,7 +6947,7 @@ __global__ __launch_bounds__(256) void samp_gather_batch_kernel(const LmBatchMem
 __global__ __launch_bounds__(1024) void samp_final_batch_kernel(const LmBatchMember* __restrict__ tab, int V) {
     const LmBatchMember e = tab[blockIdx.y];
     if (!e.serial) return;
-    samp_final_body(e.logits, V, e.samp, e.stt, e.swork, SampTail{-1, nullptr, 0, nullptr, 0});
+    samp_final_body<false>(e.logits, V, e.samp, e.stt, e.swork, SampTail{-1, nullptr, 0, nullptr, 0});
 }
 __global__ void lm_batch_tokens_kernel(const LmBatchMember* __restrict__ tab, int n_members, int* __restrict__ out) {
     if ((int)threadIdx.x < n_members && tab[threadIdx.x].stt) out[threadIdx.x] = tab[threadIdx.x].stt->out_token;
@@ -6921,7 +7087,7 @@ static int lm_batch_refresh(rca_lm_batch* b) {
         for (int s = 0; s < b->n_members; ++s) {
             rca_lm* h = b->m[s];
             if (s * n + n > LM_BATCH_ROWS) break;   // (more rows than a token block: refused by the step before anything reads the table)
-            const bool serial = h->sampler_set && !h->samp_full;
+            const bool serial = h->sampler_set && !lm_samp_own_launches(h);
             tab[(size_t)(n - 1) * LM_BATCH_MAX + s] = lm_batch_member(h, s * n, serial);
             b->any_serial = b->any_serial || serial;
             b->any_patch = b->any_patch || (serial && h->samp_patch);
@@ -6976,7 +7142,7 @@ static void lm_batch_enqueue_pass(rca_lm_batch* b, const LmBatchView& vw, int n,
         samp_final_batch_kernel<<<dim3(1, NM), 1024, 0, st>>>(tab, V);
     }
     for (int s = 0; s < vw.n_hm; ++s)
-        if (vw.hm[s]->samp_full) lm_enqueue_sample(vw.hm[s], vw.hm[s]->logits, st);
+        if (lm_samp_own_launches(vw.hm[s])) lm_enqueue_sample(vw.hm[s], vw.hm[s]->logits, st);
 }
 // the batch's own tables for n tokens per member, every member in its slot
 static LmBatchView lm_batch_view(rca_lm_batch* b, int n) {
@@ -7167,7 +7333,7 @@ static int lm_batch_stage(rca_lm_batch* b, const LmBatchCall& c, LmBatchPlan* pl
         rca_lm* h = c.hm[k];
         p.graphs = p.graphs && h->graphs_enabled;
         if (c.sel) {
-            const bool serial = !h->samp_full;
+            const bool serial = !lm_samp_own_launches(h);
             p.graphs = p.graphs && serial;   // a whole-vocabulary sampler has launches of its own with its own pointers: eager
             any_serial = any_serial || serial;
             p.any_patch = p.any_patch || (serial && h->samp_patch);
@@ -9084,4 +9250,150 @@ extern "C" int rca_quantize_rows(int32_t device, const void* src_host, int32_t s
 extern "C" int rca_quantize_rows_w(int32_t device, const void* src_host, int32_t src_dtype, int64_t rows, int64_t K, int32_t type, int32_t rule,
                                    const float* col_weights, void* blocks_host, int64_t blocks_bytes) {
     return lm_quantize_rows(device, src_host, src_dtype, rows, K, type, rule, col_weights, blocks_host, blocks_bytes);
+}
+
+// ------------------------------------------------------------------------------------ the opt-in samplers' kernels (declared in front of lm_enqueue_sample)
+__global__ __launch_bounds__(1024) void samp_final_typ_kernel(float* logits, int V, const SamplerDev* __restrict__ sp,
+                                                              LmDevState* __restrict__ stt, SampWork* __restrict__ w, SampTail tail) {
+    samp_final_body<true>(logits, V, sp, stt, w, tail);
+}
+
+// ---- mirostat v2 (llama_sampler_mirostat_v2_apply; llama-cpp-python's chain is then logit bias -> penalties -> temp -> mirostat:
+// top_k, typical, top_p and min_p are left out).  tests/samp_ext_ref.py is the definition.  Per draw c, with mx the row's maximum,
+// x_i = (v_i - mx) * (1 / temp), e_i = rca_expf(x_i) and masses w_i = trunc(e_i * 2^40):
+//   S   = sum of w_i over the vocabulary (integer: the same whatever the slices), lnS = rca_logf((float)S * 2^-40);
+//   kept: surprise_i = (lnS - x_i) * log2(e) <= mu, mu = SampWork::mu_ring[c % SAMP_RING].  When not even the top token passes, the
+//         lowest index among the maxima alone is kept (and drawn);
+//   draw: the whole-vocabulary sampler's Gumbel-max pick over the kept tokens, same keyed RNG;
+//   S'  = sum of w_i over the kept tokens, observed = (rca_logf((float)S' * 2^-40) - x_tok) * log2(e),
+//   mu_ring[(c + 1) % SAMP_RING] = mu - eta * (observed - tau).
+// Four launches: slice maxima (samp_full_max_kernel), slice masses, slice picks + kept masses, one-workgroup merge + the common tail.
+// Contraction is off in all of them: every product and sum above is one float32 operation, as in the restatement.
+#define SAMP_LOG2E 1.44269504f
+#define SAMP_FX_INV 9.094947017729282e-13f   // 2^-40
+__device__ __forceinline__ float samp_slices_max(const SampWork* __restrict__ w) {
+    const float* smax = reinterpret_cast<const float*>(w->hist);
+    float mx = smax[0];
+    for (int k = 1; k < SAMPF_SLICES; ++k) mx = fmaxf(mx, smax[k]);
+    return mx;
+}
+__device__ __forceinline__ unsigned long long samp_block_sum_u64(unsigned long long v, unsigned long long* red) {   // valid in thread 0
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long s = 0ull;
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 16; ++k) s += red[k];
+    return s;
+}
+__device__ __forceinline__ unsigned long long samp_miro_total(const SampWork* __restrict__ w, int which) {
+    unsigned long long s = 0ull;
+    for (int k = 0; k < SAMPF_SLICES; ++k) s += w->miro_part[which][k];
+    return s;
+}
+__global__ __launch_bounds__(1024) void samp_miro_mass_kernel(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
+                                                              SampWork* __restrict__ w) {
+#pragma clang fp contract(off)
+    __shared__ unsigned long long red[16];
+    const float mx = samp_slices_max(w), inv_t = 1.0f / sp->temp;
+    const int per = (V + SAMPF_SLICES - 1) / SAMPF_SLICES;
+    const int i0 = blockIdx.x * per, i1 = min(V, i0 + per);
+    unsigned long long acc = 0ull;
+    for (int i = i0 + threadIdx.x; i < i1; i += 1024) {
+        const float x = (samp_value(logits, sp, i) - mx) * inv_t;
+        acc += samp_mass_fx(x);
+    }
+    acc = samp_block_sum_u64(acc, red);
+    if (threadIdx.x == 0) w->miro_part[0][blockIdx.x] = acc;
+}
+__global__ __launch_bounds__(1024) void samp_miro_pick_kernel(const float* __restrict__ logits, int V, const SamplerDev* __restrict__ sp,
+                                                              const LmDevState* __restrict__ stt, SampWork* __restrict__ w) {
+#pragma clang fp contract(off)
+    __shared__ unsigned long long red[16], redm[16];
+    const float mx = samp_slices_max(w), inv_t = 1.0f / sp->temp;
+    const unsigned long long c = stt->rng_counter;
+    const float mu = w->mu_ring[c % SAMP_RING];
+    const float lnS = rca_logf((float)samp_miro_total(w, 0) * SAMP_FX_INV);
+    const bool top_only = !(lnS * SAMP_LOG2E <= mu);
+    const unsigned long long draw = splitmix(sp->seed, c);
+    const int per = (V + SAMPF_SLICES - 1) / SAMPF_SLICES;
+    const int i0 = blockIdx.x * per, i1 = min(V, i0 + per);
+    unsigned long long best = 0ull, mass = 0ull;
+    for (int i = i0 + threadIdx.x; i < i1; i += 1024) {
+        const float v = samp_value(logits, sp, i);
+        const float d = v - mx;
+        unsigned long long key;
+        if (top_only) {
+            if (!(v == mx)) continue;
+            key = sample_key(0.0f, (unsigned)i);
+        } else {
+            const float x = d * inv_t;
+            const float surprise = (lnS - x) * SAMP_LOG2E;
+            if (!(surprise <= mu)) continue;
+            mass += samp_mass_fx(x);
+            const unsigned long long z = splitmix(draw, (unsigned long long)i);
+            const float u = (float)(unsigned)(((z >> 41) << 1) | 1ull) * 5.9604644775390625e-08f;
+            const float g = -rca_logf(-rca_logf(u));
+            key = sample_key(__builtin_fmaf(d, inv_t, g), (unsigned)i);
+        }
+        best = key > best ? key : best;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(best, off);
+        best = o > best ? o : best;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    mass = samp_block_sum_u64(mass, redm);   // (its barrier also publishes red)
+    if (threadIdx.x == 0) {
+        unsigned long long b = red[0];
+        for (int k = 1; k < 16; ++k) b = red[k] > b ? red[k] : b;
+        w->cand[blockIdx.x] = b;
+        w->miro_part[1][blockIdx.x] = mass;
+    }
+}
+__global__ __launch_bounds__(1024) void samp_miro_final_kernel(float* logits, int V, const SamplerDev* __restrict__ sp, LmDevState* __restrict__ stt,
+                                                               SampWork* __restrict__ w, SampTail tail) {
+#pragma clang fp contract(off)
+    __shared__ int s_tok;
+    __shared__ unsigned long long s_draw;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        unsigned long long b = w->cand[0];
+        for (int k = 1; k < SAMPF_SLICES; ++k) b = w->cand[k] > b ? w->cand[k] : b;
+        const int tok = (int)(0xFFFFFFFFu - (unsigned)(b & 0xFFFFFFFFull));
+        const unsigned long long c = stt->rng_counter;
+        const float mx = samp_slices_max(w), inv_t = 1.0f / sp->temp;
+        const float mu = w->mu_ring[c % SAMP_RING];
+        const float lnS = rca_logf((float)samp_miro_total(w, 0) * SAMP_FX_INV);
+        const bool top_only = !(lnS * SAMP_LOG2E <= mu);
+        const unsigned long long kept = top_only ? (1ull << 40) : samp_miro_total(w, 1);
+        const float x_tok = (logits[tok < 0 ? 0 : (tok >= V ? V - 1 : tok)] - mx) * inv_t;   // (the row is still patched: the value the passes saw)
+        const float observed = (rca_logf((float)kept * SAMP_FX_INV) - x_tok) * SAMP_LOG2E;
+        const float err = observed - sp->miro_tau;
+        const float step = sp->miro_eta * err;
+        w->mu_ring[(c + 1ull) % SAMP_RING] = mu - step;
+        s_draw = c;
+        stt->rng_counter = c + 1ull;
+        stt->out_token = tok;
+        if (tail.frame_i >= 0) {
+            stt->frame_out[tail.frame_i] = tok;
+            stt->n_tokens += 2;
+            stt->ids[0] = tok;
+            stt->ids[1] = stt->ids[LM_FRAME_USER0 + tail.frame_i];
+        }
+        s_tok = tok;
+    }
+    __syncthreads();
+    samp_accept_and_restore(logits, sp, w, s_draw, s_tok, tid);
+    for (int b = tid; b < SAMPF_SLICES; b += 1024) w->hist[b] = 0u;   // the top-k sampler expects a zeroed histogram
+    if (tail.frame_i >= 0) {   // lm_embed_kernel for the next pair (m = 2), as in samp_final_kernel
+        const int id1 = stt->ids[LM_FRAME_USER0 + tail.frame_i];
+        for (int e = tid; e < 2 * tail.H; e += 1024) {
+            const int m = e / tail.H, hh = e - m * tail.H;
+            int id = m == 0 ? s_tok : id1;
+            id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+            tail.x[e] = tail.f32tab ? reinterpret_cast<const float*>(tail.table)[(long)id * tail.H + hh]
+                                    : __uint_as_float((unsigned)reinterpret_cast<const bf16_t*>(tail.table)[(long)id * tail.H + hh] << 16);
+        }
+    }
 }

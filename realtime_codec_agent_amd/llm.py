@@ -412,6 +412,7 @@ class LlamaForAlternatingCodeChannels:
         self._sampler = None
         self._seed = seed
         self._sampler_params = None
+        self._sampler_ext = False      # set_sampler_extensions: typical_p and mirostat v2 are refused, as they always were, until asked for
         self._mfma_prefill = True
         self.last_n_tokens_size = 64      # llama_cpp.Llama's default penalty window (the reference never overrides it)
 
@@ -677,11 +678,34 @@ class LlamaForAlternatingCodeChannels:
         logit_bias: Optional[Dict[int, float]] = None,
     ) -> None:
         """llamacpp_utils.py:39-77.  The chain llama-cpp-python builds for these arguments, on the device: logit bias (the logits
-        processor) -> penalties over the last 64 accepted tokens (repeat / frequency / presence) -> top_k -> top_p -> min_p -> temp ->
-        dist -- every member the agent's config forwards (realtime_agent_v2.py:172-185, realtime_agent_config.py:11-20), top_k anywhere
-        from 1 to the vocabulary or <= 0.  typical_p, mirostat and grammars are not part of the duplex path and are refused."""
-        if typical_p != 1.0 or mirostat_mode != 0 or grammar is not None:
-            raise NotImplementedError("typical_p / mirostat / grammar samplers are not implemented (the duplex agent never sets them)")
+        processor) -> penalties over the last 64 accepted tokens (repeat / frequency / presence) -> top_k -> typical -> top_p -> min_p ->
+        temp -> dist -- every member the agent's config forwards (realtime_agent_v2.py:172-185, realtime_agent_config.py:11-20), top_k
+        anywhere from 1 to the vocabulary or <= 0.  typical_p < 1 needs top_k in 1..256 (the whole vocabulary is not sorted by
+        typicality; refused otherwise).  mirostat_mode 2: logit bias -> penalties -> temp -> mirostat v2, with top_k, top_p, min_p and
+        typical_p ignored as llama-cpp-python leaves them out of that chain; mu starts at 2 * mirostat_tau (mirostat_mu() reads it).
+        temp <= 0 is greedy and ignores both.  Both are restated from their published definitions (tests/samp_ext_ref.py); parity with
+        llama.cpp is not pinned.  mirostat_mode 1 (its k is computed per draw and can land on any of the three sampler routes) and
+        grammars are refused.  Both options are opt-in per handle: until set_sampler_extensions(True) any typical_p other than 1.0
+        and any mirostat_mode other than 0 raise NotImplementedError, as they always did."""
+        if grammar is not None:
+            raise NotImplementedError("grammar samplers are not implemented (the duplex agent never sets one)")
+        if (typical_p != 1.0 or mirostat_mode != 0) and not getattr(self, "_sampler_ext", False):
+            raise NotImplementedError("typical_p / mirostat samplers are off on this handle (the duplex agent never sets them): "
+                                      "call set_sampler_extensions(True) first; mirostat_mode 1 and grammars are not implemented")
+        mirostat_mode = int(mirostat_mode)
+        if mirostat_mode == 1:
+            raise NotImplementedError("mirostat_mode 1 (mirostat v1) is not implemented: its k is computed on the device per draw and can "
+                                      "land on any of the three sampler routes; mirostat_mode 2 is")
+        if mirostat_mode not in (0, 2):
+            raise ValueError(f"mirostat_mode {mirostat_mode} is none of 0 (off), 2 (v2)")
+        typical_p = float(typical_p)
+        if not typical_p >= 0.0:
+            raise ValueError(f"typical_p {typical_p} must be 0 (unset) or positive")
+        typical_on = 0.0 < typical_p < 1.0 and temp > 0.0 and mirostat_mode != 2
+        if typical_on and not 1 <= int(top_k) <= 256:
+            raise ValueError(f"typical_p {typical_p} needs top_k in 1..256 (top_k is {top_k}): the whole vocabulary is not sorted by typicality")
+        if mirostat_mode == 2 and not (0.0 <= float(mirostat_tau) < float("inf") and 0.0 <= float(mirostat_eta) < float("inf")):
+            raise ValueError(f"mirostat_tau {mirostat_tau} and mirostat_eta {mirostat_eta} must be finite and not negative")
         self.set_seed(seed if seed is not None else -1)
         bias = dict(logit_bias or {})
         if logits_processor is not None:
@@ -696,9 +720,26 @@ class LlamaForAlternatingCodeChannels:
                              freq_penalty=float(frequency_penalty), presence_penalty=float(presence_penalty),
                              penalty_last_n=int(getattr(self, "last_n_tokens_size", 64)))
         N.check(self._lib.rca_lm_sampler_init(self._h, C.byref(p)), "rca_lm_sampler_init")
+        # (rca_lm_sampler_init has reset both options to off)
+        if typical_on:
+            N.check(self._lib.rca_lm_sampler_set_typical(self._h, typical_p), "rca_lm_sampler_set_typical")
+        if mirostat_mode == 2:
+            N.check(self._lib.rca_lm_sampler_set_mirostat(self._h, 2, float(mirostat_tau), float(mirostat_eta)), "rca_lm_sampler_set_mirostat")
         self._sampler = True
         self._sampler_params = dict(top_k=top_k, top_p=top_p, min_p=min_p, temp=temp, seed=self._seed, logit_bias=bias,
-                                    repeat_penalty=repeat_penalty, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
+                                    repeat_penalty=repeat_penalty, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
+                                    typical_p=typical_p, mirostat_mode=mirostat_mode, mirostat_tau=mirostat_tau, mirostat_eta=mirostat_eta)
+
+    def set_sampler_extensions(self, enable: bool) -> None:
+        """Opt in to (or out of) typical_p and mirostat v2 in init_sampler_for_generate.  Off, the default, the call refuses both
+        keywords exactly as it did before they existed; the sampler in force is not touched either way."""
+        self._sampler_ext = bool(enable)
+
+    def mirostat_mu(self) -> float:
+        """mirostat v2's mu as the next draw will read it (settles the stream); an error when mirostat is off"""
+        mu = C.c_float()
+        N.check(self._lib.rca_lm_sampler_get_mirostat_mu(self._h, C.byref(mu)), "rca_lm_sampler_get_mirostat_mu")
+        return float(mu.value)
 
     def sample(self, idx: Optional[int] = None) -> int:
         assert self.n_tokens > 0
