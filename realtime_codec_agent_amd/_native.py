@@ -238,6 +238,10 @@ class Q6KBlocks:
         return Q6KBlocks(np.ascontiguousarray(r), (r.shape[0], self.shape[1]))
 
 
+# the rca_tensor_t dtype each class of blocks is handed over as (make_tensors)
+BLOCK_DTYPES = {Q8Blocks: RCA_Q8_0, Q4KBlocks: RCA_Q4_K, Q5KBlocks: RCA_Q5_K, Q6KBlocks: RCA_Q6_K, Q40Blocks: RCA_Q4_0, Q41Blocks: RCA_Q4_1,
+                IQ4NLBlocks: RCA_IQ4_NL, IQ4XSBlocks: RCA_IQ4_XS}
+
 RCA_PCM_F32, RCA_PCM_S16 = 0, 1
 # rca_ingest_row_t as a numpy record: a row table is one array of these, handed over as its host copy and its device twin
 INGEST_ROW = np.dtype([("src_off", "<i8"), ("n_in", "<i8"), ("dst_off", "<i8"), ("src_stride", "<i4"), ("n_mix", "<i4")])
@@ -612,12 +616,11 @@ def make_tensors(weights: Dict[str, np.ndarray]) -> Tuple[C.Array, list]:
     keep = []
     arr = (Tensor * len(weights))()
     for i, (name, a) in enumerate(weights.items()):
-        if isinstance(a, (Q8Blocks, Q4KBlocks, Q5KBlocks, Q6KBlocks, Q40Blocks)):      # GGUF q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 / IQ4_NL / IQ4_XS (subclasses of Q40Blocks) blocks, handed over as they sit in the file
+        if type(a) in BLOCK_DTYPES:      # GGUF blocks, handed over as they sit in the file
             raw = np.ascontiguousarray(a.raw)
             nb = name.encode()
             keep += [raw, nb]
-            arr[i] = Tensor(nb, raw.ctypes.data, int(np.prod(a.shape)), {Q8Blocks: RCA_Q8_0, Q4KBlocks: RCA_Q4_K, Q5KBlocks: RCA_Q5_K, Q6KBlocks: RCA_Q6_K, Q40Blocks: RCA_Q4_0, Q41Blocks: RCA_Q4_1,
-                                                                          IQ4NLBlocks: RCA_IQ4_NL, IQ4XSBlocks: RCA_IQ4_XS}[type(a)])
+            arr[i] = Tensor(nb, raw.ctypes.data, int(np.prod(a.shape)), BLOCK_DTYPES[type(a)])
             continue
         if a.dtype == np.uint16:
             dt = RCA_BF16

@@ -19,6 +19,7 @@
 //   position, input ids and RNG counter live in device memory so the graph replays unchanged.
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 #include <cmath>
 #include <climits>
 
@@ -430,14 +431,74 @@ __host__ __device__ __forceinline__ long q8_sc_index(long pair, long kblock, lon
 #define WF_Q6K 4    // GGUF Q6_K re-encoded losslessly: int8 values (the 6-bit value - 32) in the q8_0 pair layout + one f32 scale d * sc per
                     // row and group of 16 ((s_a, s_b) per pair, pairs in groups of 8: [ceil(N / 16)][K / 16][8][2] floats); 10 bits per
                     // weight streamed (the file holds 6.6); d * sc * q is exact in f32, so the values are llama.cpp's dequantize_row_q6_K's
-constexpr bool wf_packed(int fmt) { return fmt == WF_Q8 || fmt == WF_Q4K || fmt == WF_Q6K || fmt == WF_Q5K || fmt == WF_Q40 || fmt == WF_Q41 || fmt == WF_IQ4 || fmt == WF_IQ4XS; }
+// What the HOST load path knows of a format, one row per WF_* id (WF_TABLE[id]): upload, conversion, packing and the reports read
+// their constants here, the way the launchers get their template argument from wf_dispatch.  A component is an array holding
+// `bytes` bytes per `per` values of a row.
+enum { WA_NONE = 0, WA_W16, WA_Q, WA_D, WA_DD, WA_QS, WA_SC, WA_QH };   // arrays of RawMat (w16, q, d, dd) and of WMat (w, qs, sc, dd, qh)
+struct WfPart { int arr, per, bytes; };
+struct WfInfo {
+    int id;
+    const char* name;       // as the messages print it
+    int device;             // the form the kernels are launched as (wf_dispatch's template value)
+    int dtype;              // the RCA_* type its file blocks (16-bit formats: its values) arrive as ...
+    int blk_vals, blk_bytes;   // ... values and bytes per block ...
+    bool bad_flag;          // ... and whether its unblock / quantise kernels report a block whose factor is not finite
+    WfPart plain[3];        // RawMat: the components, in the order parts() lists them
+    int row_mult;           // RawMat: a row is a multiple of this many values
+    int k_mult, n_mult;     // WMat (packed formats; k_mult 0: a 16-bit format, kept as it is) ...
+    const char* n_word;     // ... and how the refusal words the multiple of N
+    WfPart packed[4];       // WMat: the arrays lm_finish_mat allocates, in that order; sc / dd cover whole groups of 16 rows, zero padded
+    int stream64;           // bytes one decode pass reads, in 64ths of a byte per weight (a packed matrix holds a multiple of 64 weights)
+    WfPart mask;            // rca_lm_mask_head_rows: the array whose entries of a row are zeroed, `per` values to an entry
+};
+#define WF_PLAIN_4BIT {{WA_Q, 1, 1}, {WA_DD, 32, 4}}                       // a byte per value + one factor dword per 32
+#define WF_PLAIN_K {{WA_Q, 1, 1}, {WA_D, 32, 2}, {WA_DD, 256, 4}}          // a byte per value + (sc | m << 8) per 32 + (d | dmin << 16) per 256
+#define WF_PACKED_4BIT {{WA_QS, 2, 1}, {WA_SC, 32, 4}}
+constexpr WfInfo WF_TABLE[] = {
+    {WF_BF16, "bf16", WF_BF16, RCA_BF16, 1, 2, false, {{WA_W16, 1, 2}}, 1, 0, 0, "", {}, 128, {WA_W16, 1, 2}},
+    {WF_Q8, "q8_0", WF_Q8, RCA_Q8_0, 32, 34, false, {{WA_Q, 1, 1}, {WA_D, 32, 2}}, 32, 32, 2, "even", {{WA_QS, 1, 1}, {WA_SC, 32, 2}}, 64 + 4, {WA_SC, 32, 2}},
+    {WF_F16, "f16", WF_F16, RCA_F16, 1, 2, false, {{WA_W16, 1, 2}}, 1, 0, 0, "", {}, 128, {WA_W16, 1, 2}},
+    {WF_Q4K, "Q4_K", WF_Q4K, RCA_Q4_K, 256, 144, false, WF_PLAIN_K, 256, 256, 4, "of 4", {{WA_QS, 2, 1}, {WA_SC, 32, 2}, {WA_DD, 256, 4}}, 32 + 4 + 1, {WA_DD, 256, 4}},
+    // Q6_K: d holds the int8 scales per 16, dd the fp16 d per 256; packed with one f32 scale per row and 16 values
+    {WF_Q6K, "Q6_K", WF_Q6K, RCA_Q6_K, 256, 210, false, {{WA_Q, 1, 1}, {WA_D, 16, 1}, {WA_DD, 256, 2}}, 256, 256, 2, "even", {{WA_QS, 1, 1}, {WA_SC, 16, 4}}, 64 + 16, {WA_SC, 16, 4}},
+    {WF_Q5K, "Q5_K", WF_Q5K, RCA_Q5_K, 256, 176, false, WF_PLAIN_K, 256, 256, 4, "of 4", {{WA_QS, 2, 1}, {WA_SC, 32, 2}, {WA_DD, 256, 4}, {WA_QH, 8, 1}}, 32 + 8 + 4 + 1, {WA_DD, 256, 4}},
+    {WF_Q40, "Q4_0", WF_Q40, RCA_Q4_0, 32, 18, true, WF_PLAIN_4BIT, 256, 256, 4, "of 4", WF_PACKED_4BIT, 32 + 8, {WA_SC, 32, 4}},
+    {WF_Q41, "Q4_1", WF_Q40, RCA_Q4_1, 32, 20, true, WF_PLAIN_4BIT, 256, 256, 4, "of 4", WF_PACKED_4BIT, 32 + 8, {WA_SC, 32, 4}},
+    {WF_IQ4, "IQ4_NL", WF_IQ4, RCA_IQ4_NL, 32, 18, true, WF_PLAIN_4BIT, 256, 256, 4, "of 4", WF_PACKED_4BIT, 32 + 8, {WA_SC, 32, 4}},
+    {WF_IQ4XS, "IQ4_XS", WF_IQ4, RCA_IQ4_XS, 256, 136, true, WF_PLAIN_4BIT, 256, 256, 4, "of 4", WF_PACKED_4BIT, 32 + 8, {WA_SC, 32, 4}},
+};
+constexpr int WF_COUNT = sizeof(WF_TABLE) / sizeof(WF_TABLE[0]);
+constexpr bool wf_table_in_id_order() {
+    for (int i = 0; i < WF_COUNT; ++i)
+        if (WF_TABLE[i].id != i) return false;
+    return true;
+}
+static_assert(wf_table_in_id_order(), "WF_TABLE[id] is the row of format id");
+constexpr bool wf_packed(int fmt) { return fmt >= 0 && fmt < WF_COUNT && WF_TABLE[fmt].k_mult != 0; }
+// rca_lm_config_t::decode_weights: the format a 16-bit matrix is brought into at load (a matrix that arrived quantised stays what it is)
+enum { DW_AS_SUPPLIED = 0, DW_Q8_0, DW_F16, DW_Q4_K, DW_Q5_K, DW_Q4_0, DW_Q4_1, DW_IQ4_NL, DW_COUNT };
+constexpr int DW_FORMAT[DW_COUNT] = {-1, WF_Q8, WF_F16, WF_Q4K, WF_Q5K, WF_Q40, WF_Q41, WF_IQ4};
 // minimum waves per SIMD asked of the register allocator.  The q8_0 bodies otherwise spread over 200+ registers (one wave per
 // SIMD) although their live set is ~130: a streaming kernel wants the occupancy.
 constexpr int gemv_min_waves(int Q, int R, int NIT, int M = 2) {
-    if (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K && Q != WF_Q40 && Q != WF_IQ4) return 1;
+    if (!wf_packed(Q) || WF_TABLE[Q].device != Q) return 1;   // the packed forms the kernels are instantiated for
     if (M == 4 && NIT == 4) return 1;   // four rows x four chunks: 128 x values per lane beside the batch (group steps, wide FFN)
     return R * NIT >= 16 ? 2 : 4;
 }
+// the two helpers against the hand-written format lists they replaced, at every argument the kernels are instantiated with
+constexpr bool wf_helpers_match_their_lists() {
+    for (int Q = 0; Q <= 9; ++Q) {
+        if (wf_packed(Q) != (Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K || Q == WF_Q40 || Q == WF_Q41 || Q == WF_IQ4 || Q == WF_IQ4XS)) return false;
+        for (int R = 1; R <= 8; R *= 2)
+            for (int NIT = 1; NIT <= 4; ++NIT)
+                for (int M = 1; M <= 4; M *= 2) {
+                    const int was = (Q != WF_Q8 && Q != WF_Q4K && Q != WF_Q6K && Q != WF_Q5K && Q != WF_Q40 && Q != WF_IQ4) ? 1 : ((M == 4 && NIT == 4) ? 1 : (R * NIT >= 16 ? 2 : 4));
+                    if (gemv_min_waves(Q, R, NIT, M) != was) return false;
+                }
+    }
+    return gemv_min_waves(WF_Q8, 4, 1) == 4 && !wf_packed(-1) && !wf_packed(WF_COUNT);
+}
+static_assert(wf_helpers_match_their_lists(), "wf_packed / gemv_min_waves changed value");
 // ACT = 1 (rca_lm_set_act_format, packed formats only): the activations are quantised to q8_1 blocks -- 32 consecutive values, int8 +
 // one scale, ggml's quantize_row_q8_1 restated: d = amax / 127, inv = d != 0 ? 1 / d : 0 (IEEE division), q = roundf(x * inv), scale used
 // d_x = (float)(fp16 rne of d) -- and the products run on the signed byte dot (v_dot4c_i32_i8), llama.cpp's GPU mat-vec class:
@@ -479,7 +540,7 @@ __device__ __forceinline__ void lm_gemv_body(const LmDevState* __restrict__ stt,
     const int tid = threadIdx.x;
     const int nchunk = K >> 3;
     constexpr bool QA = ACT == 1;
-    static_assert(!QA || Q == WF_Q8 || Q == WF_Q4K || Q == WF_Q6K || Q == WF_Q5K || Q == WF_Q40 || Q == WF_IQ4, "q8_1 activations go with the packed weight formats");
+    static_assert(!QA || wf_packed(Q), "q8_1 activations go with the packed weight formats");
     const int cpw = QA ? ((((nchunk + 3) >> 2) + 3) & ~3) : (nchunk + 3) >> 2;   // chunks per wave (q8_1: whole 32-blocks)
     const int c0 = wave * cpw;
     const int cn = max(0, min(cpw, nchunk - c0));            // this wave's chunk count (<= 64 * NIT)
@@ -2407,11 +2468,9 @@ struct WMat {
     // the kernels' 16-bit weight pointer: the packed formats do not use it, and Q5_K hands its plane over in that argument (the
     // argument list, and with it the 14 preloaded dwords, stays what it is for every format)
     const bf16_t* wptr() const { return fmt == WF_Q5K ? reinterpret_cast<const bf16_t*>(qh) : w; }
-    long stream_bytes() const {   // bytes one decode pass reads of it
-        const long n = (long)N * K;
-        if (fmt == WF_Q5K) return n / 2 + n / 8 + n / 16 + n / 64;   // nibbles, plane, (sc, m), (d, dmin): 5.6 bits per weight
-        if (fmt == WF_Q40 || fmt == WF_Q41 || fmt == WF_IQ4 || fmt == WF_IQ4XS) return n / 2 + n / 8;    // nibbles, (s, t) resp. f32 s: 5.0 bits per weight
-        return fmt == WF_Q8 ? n + n / 16 : (fmt == WF_Q4K ? n / 2 + n / 16 + n / 64 : (fmt == WF_Q6K ? n + n / 4 : 2 * n));
+    long stream_bytes() const { return (long)N * K * WF_TABLE[fmt].stream64 / 64; }   // bytes one decode pass reads of it
+    void** array(int arr) {   // the member a WA_* id of the table names
+        return arr == WA_W16 ? (void**)&w : (arr == WA_QS ? (void**)&qs : (arr == WA_SC ? (void**)&sc : (arr == WA_DD ? (void**)&dd : (void**)&qh)));
     }
 };
 struct LmLayer {
@@ -2714,7 +2773,7 @@ static int lm_check_cfg(const rca_lm_config_t* c) {
     if (c->ffn > LM_KSLICE * LM_MAXSPLIT) return fail(RCA_ERR_ARG, "ffn > %d unsupported", LM_KSLICE * LM_MAXSPLIT);
     if (c->ffn > LM_KSLICE && c->ffn % LM_KSLICE) return fail(RCA_ERR_ARG, "ffn above %d must be a multiple of it", LM_KSLICE);
     if (c->vocab_size < 2 || c->n_layers < 1 || c->n_ctx < 2) return fail(RCA_ERR_ARG, "bad sizes");
-    if (c->decode_weights < 0 || c->decode_weights > 7) return fail(RCA_ERR_ARG, "decode_weights %d (0 as supplied, 1 q8_0, 2 f16, 3 q4_k, 4 q5_k, 5 q4_0, 6 q4_1, 7 iq4_nl)", c->decode_weights);
+    if (c->decode_weights < 0 || c->decode_weights >= DW_COUNT) return fail(RCA_ERR_ARG, "decode_weights %d (0 as supplied, 1 q8_0, 2 f16, 3 q4_k, 4 q5_k, 5 q4_0, 6 q4_1, 7 iq4_nl)", c->decode_weights);
     return RCA_OK;
 }
 
@@ -2728,157 +2787,143 @@ struct RawMat {
     f16_t* d = nullptr;         // WF_Q8: fp16 [rows][cols / 32]; WF_Q4K / WF_Q5K: ushort (sc | m << 8) [rows][cols / 32]
     unsigned* dd = nullptr;     // WF_Q4K / WF_Q5K: (d | dmin << 16) [rows][cols / 256]; WF_Q40 / WF_Q41: (s | t << 16) [rows][cols / 32] (q as WF_Q4K, d unused);
                                 // WF_IQ4 / WF_IQ4XS: the f32 factor s (bits) [rows][cols / 32] (q: table indices, d unused)
+    RawMat() = default;
+    RawMat(const RawMat&) = delete;
+    RawMat& operator=(const RawMat&) = delete;
+    RawMat(RawMat&& o) noexcept { *this = std::move(o); }
+    RawMat& operator=(RawMat&& o) noexcept {
+        if (this != &o) {
+            release();
+            fmt = o.fmt; rows = o.rows; cols = o.cols;
+            w16 = o.w16; q = o.q; d = o.d; dd = o.dd;
+            o.w16 = nullptr; o.q = nullptr; o.d = nullptr; o.dd = nullptr;
+        }
+        return *this;
+    }
+    ~RawMat() { release(); }
     void release() {
         for (void* p : {(void*)w16, (void*)q, (void*)d, (void*)dd})
             if (p) (void)hipFree(p);
         w16 = nullptr; q = nullptr; d = nullptr; dd = nullptr;
     }
+    void** array(int arr) const {   // the member a WA_* id of the table names
+        return arr == WA_W16 ? (void**)&w16 : (arr == WA_Q ? (void**)&q : (arr == WA_D ? (void**)&d : (void**)&dd));
+    }
     // (array, bytes per row) of every component
     int parts(void** ptr, long* row_bytes) const {
-        if (fmt == WF_Q4K || fmt == WF_Q5K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; ptr[2] = dd; row_bytes[2] = cols / 256 * 4; return 3; }
-        if (fmt == WF_Q40 || fmt == WF_Q41 || fmt == WF_IQ4 || fmt == WF_IQ4XS) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = dd; row_bytes[1] = cols / 32 * 4; return 2; }
-        if (fmt == WF_Q6K) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 16; ptr[2] = dd; row_bytes[2] = cols / 256 * 2; return 3; }   // d: int8 scales, dd: fp16 d
-        if (fmt == WF_Q8) { ptr[0] = q; row_bytes[0] = cols; ptr[1] = d; row_bytes[1] = cols / 32 * 2; return 2; }
-        ptr[0] = w16; row_bytes[0] = cols * 2;
-        return 1;
+        int n = 0;
+        for (const WfPart& p : WF_TABLE[fmt].plain)
+            if (p.arr != WA_NONE) { ptr[n] = *array(p.arr); row_bytes[n++] = cols / p.per * p.bytes; }
+        return n;
     }
     int alloc(int f, long r, long c) {
+        const WfInfo& info = WF_TABLE[f];
         fmt = f; rows = r; cols = c;
+        if (c % info.row_mult) return fail(RCA_ERR_ARG, "%s needs rows of a multiple of %d values (got %ld)", info.name, info.row_mult, c);
         int rc;
-        if (f == WF_Q4K || f == WF_Q5K) {
-            if (c % 256) return fail(RCA_ERR_ARG, "%s needs rows of a multiple of 256 values (got %ld)", f == WF_Q5K ? "Q5_K" : "Q4_K", c);
-            if ((rc = lm_alloc((void**)&q, (size_t)r * c)) != RCA_OK || (rc = lm_alloc((void**)&d, (size_t)r * (c / 32) * 2)) != RCA_OK ||
-                (rc = lm_alloc((void**)&dd, (size_t)r * (c / 256) * 4)) != RCA_OK) { release(); return rc; }
-            return RCA_OK;
-        }
-        if (f == WF_Q40 || f == WF_Q41 || f == WF_IQ4 || f == WF_IQ4XS) {
-            if (c % 256) return fail(RCA_ERR_ARG, "%s needs rows of a multiple of 256 values (got %ld)", f == WF_IQ4 ? "IQ4_NL" : (f == WF_IQ4XS ? "IQ4_XS" : (f == WF_Q41 ? "Q4_1" : "Q4_0")), c);
-            if ((rc = lm_alloc((void**)&q, (size_t)r * c)) != RCA_OK || (rc = lm_alloc((void**)&dd, (size_t)r * (c / 32) * 4)) != RCA_OK) { release(); return rc; }
-            return RCA_OK;
-        }
-        if (f == WF_Q6K) {
-            if (c % 256) return fail(RCA_ERR_ARG, "Q6_K needs rows of a multiple of 256 values (got %ld)", c);
-            if ((rc = lm_alloc((void**)&q, (size_t)r * c)) != RCA_OK || (rc = lm_alloc((void**)&d, (size_t)r * (c / 16))) != RCA_OK ||
-                (rc = lm_alloc((void**)&dd, (size_t)r * (c / 256) * 2)) != RCA_OK) { release(); return rc; }
-            return RCA_OK;
-        }
-        if (f == WF_Q8) {
-            if (c % 32) return fail(RCA_ERR_ARG, "q8_0 needs rows of a multiple of 32 values (got %ld)", c);
-            if ((rc = lm_alloc((void**)&q, (size_t)r * c)) != RCA_OK || (rc = lm_alloc((void**)&d, (size_t)r * (c / 32) * 2)) != RCA_OK) { release(); return rc; }
-            return RCA_OK;
-        }
-        return lm_alloc((void**)&w16, (size_t)r * c * 2);
+        for (const WfPart& p : info.plain)
+            if (p.arr != WA_NONE && (rc = lm_alloc(array(p.arr), (size_t)r * (c / p.per * p.bytes))) != RCA_OK) { release(); return rc; }
+        return RCA_OK;
     }
 };
+// A device scratch buffer of the load path, freed when its scope ends.
+struct DevScratch {
+    void* p = nullptr;
+    DevScratch() = default;
+    DevScratch(const DevScratch&) = delete;
+    DevScratch& operator=(const DevScratch&) = delete;
+    ~DevScratch() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) { return lm_alloc(&p, bytes); }
+    void* take() { void* r = p; p = nullptr; return r; }
+};
 
+static const WfInfo* wf_of_blocks(int dtype) {   // the format a tensor of file blocks arrives as
+    for (const WfInfo& f : WF_TABLE)
+        if (wf_packed(f.id) && f.dtype == dtype) return &f;
+    return nullptr;
+}
+// The kernels of a verb keep their own signatures: one switch per verb picks the launch.
+static void lm_launch_unblock(hipStream_t s, int fmt, const unsigned char* blocks, long numel, RawMat* out, int* bad) {
+    switch (fmt) {
+        case WF_Q8: lm_q8_unblock_kernel<<<4096, 256, 0, s>>>(blocks, numel / 32, out->q, out->d); break;
+        case WF_Q6K: lm_q6k_unblock_kernel<<<4096, 256, 0, s>>>(blocks, numel / 256, out->q, (signed char*)out->d, (f16_t*)out->dd); break;
+        case WF_Q5K: lm_q5k_unblock_kernel<<<4096, 256, 0, s>>>(blocks, numel / 256, (unsigned char*)out->q, (unsigned short*)out->d, out->dd); break;
+        case WF_Q4K: lm_q4k_unblock_kernel<<<4096, 256, 0, s>>>(blocks, numel / 256, (unsigned char*)out->q, (unsigned short*)out->d, out->dd); break;
+        case WF_Q40: lm_q40_unblock_kernel<false><<<4096, 256, 0, s>>>(blocks, numel / 32, (unsigned char*)out->q, out->dd, bad); break;
+        case WF_Q41: lm_q40_unblock_kernel<true><<<4096, 256, 0, s>>>(blocks, numel / 32, (unsigned char*)out->q, out->dd, bad); break;
+        case WF_IQ4: lm_iq4_unblock_kernel<false><<<4096, 256, 0, s>>>(blocks, numel / 32, (unsigned char*)out->q, out->dd, bad); break;
+        case WF_IQ4XS: lm_iq4_unblock_kernel<true><<<4096, 256, 0, s>>>(blocks, numel / 32, (unsigned char*)out->q, out->dd, bad); break;   // counts 32-value sub-blocks too
+    }
+}
+static void lm_launch_dequant_f32(hipStream_t s, const RawMat& m, float* out, long numel) {
+    switch (WF_TABLE[m.fmt].device) {
+        case WF_Q8: lm_q8_dequant_f32_kernel<<<4096, 256, 0, s>>>(m.q, m.d, out, numel); break;
+        case WF_Q6K: lm_q6k_dequant_f32_kernel<<<4096, 256, 0, s>>>(m.q, (const signed char*)m.d, (const f16_t*)m.dd, out, numel); break;
+        case WF_Q4K: case WF_Q5K:   // the plain byte holds the whole value, 4 or 5 bits
+            lm_q4k_dequant_f32_kernel<<<4096, 256, 0, s>>>((const unsigned char*)m.q, (const unsigned short*)m.d, m.dd, out, numel); break;
+        case WF_Q40: lm_q40_dequant_f32_kernel<<<4096, 256, 0, s>>>((const unsigned char*)m.q, m.dd, out, numel); break;
+        case WF_IQ4: lm_iq4_dequant_f32_kernel<<<4096, 256, 0, s>>>((const unsigned char*)m.q, m.dd, out, numel); break;
+    }
+}
+static void lm_launch_quantize(hipStream_t s, int fmt, const RawMat& m, RawMat* qd, int* bad) {
+    const int f16 = m.fmt == WF_F16;
+    const long n = m.rows * m.cols;
+    switch (fmt) {
+        case WF_Q8: lm_q8_quantize_kernel<<<4096, 256, 0, s>>>(m.w16, f16, n / 32, qd->q, qd->d); break;
+        case WF_Q4K: lm_q4k_quantize_kernel<15><<<4096, 256, 0, s>>>(m.w16, f16, n / 256, (unsigned char*)qd->q, (unsigned short*)qd->d, qd->dd); break;
+        case WF_Q5K: lm_q4k_quantize_kernel<31><<<4096, 256, 0, s>>>(m.w16, f16, n / 256, (unsigned char*)qd->q, (unsigned short*)qd->d, qd->dd); break;
+        case WF_Q40: lm_q40_quantize_kernel<false><<<4096, 256, 0, s>>>(m.w16, f16, n / 32, (unsigned char*)qd->q, qd->dd, bad); break;
+        case WF_Q41: lm_q40_quantize_kernel<true><<<4096, 256, 0, s>>>(m.w16, f16, n / 32, (unsigned char*)qd->q, qd->dd, bad); break;
+        case WF_IQ4: lm_iq4nl_quantize_kernel<<<4096, 256, 0, s>>>(m.w16, f16, n / 32, (unsigned char*)qd->q, qd->dd, bad); break;
+    }
+}
+static void lm_launch_pack(hipStream_t s, const RawMat& m, int qkv_pairs, WMat* out) {
+    const int N = out->N, K = out->K;
+    switch (WF_TABLE[m.fmt].device) {
+        case WF_Q8: lm_q8_pack_kernel<<<4096, 256, 0, s>>>(m.q, m.d, N, K, qkv_pairs, out->qs, out->sc); break;
+        case WF_Q6K: lm_q6k_pack_kernel<<<4096, 256, 0, s>>>(m.q, (const signed char*)m.d, (const f16_t*)m.dd, N, K, qkv_pairs, out->qs, (float*)out->sc); break;
+        case WF_Q4K:
+            lm_q4k_pack_kernel<WF_Q4K><<<4096, 256, 0, s>>>((const unsigned char*)m.q, (const unsigned short*)m.d, m.dd, N, K, qkv_pairs, out->qs, (unsigned short*)out->sc, out->dd, nullptr);
+            break;
+        case WF_Q5K:
+            lm_q4k_pack_kernel<WF_Q5K><<<4096, 256, 0, s>>>((const unsigned char*)m.q, (const unsigned short*)m.d, m.dd, N, K, qkv_pairs, out->qs, (unsigned short*)out->sc, out->dd, out->qh);
+            break;
+        case WF_Q40: case WF_IQ4:   // IQ4: the same arrays, the factor dword is an f32
+            lm_q4k_pack_kernel<WF_Q40><<<4096, 256, 0, s>>>((const unsigned char*)m.q, nullptr, m.dd, N, K, qkv_pairs, out->qs, nullptr, out->sc, nullptr); break;
+    }
+}
+
+// A tensor of file blocks (the GGUF blocks as they sit in the file) is unblocked into its plain form.
+static int lm_upload_blocks(rca_lm* h, const rca_tensor_t* t, const WfInfo& info, long rows, long cols, RawMat* out) {
+    int rc;
+    if ((rc = out->alloc(info.id, rows, cols)) != RCA_OK) return rc;
+    const long numel = rows * cols;
+    const size_t nbytes = (size_t)(numel / info.blk_vals) * info.blk_bytes;
+    DevScratch raw;   // the blocks, then (bad_flag) the flag "a block's factor is not finite in the form the kernels keep it in"
+    if ((rc = raw.alloc(info.bad_flag ? nbytes + 8 : nbytes)) != RCA_OK) return rc;
+    int* bad = info.bad_flag ? reinterpret_cast<int*>((unsigned char*)raw.p + ((nbytes + 3) & ~(size_t)3)) : nullptr;
+    int bad_h = 0;
+    hipError_t e = hipMemcpy(raw.p, t->data, nbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && bad) e = hipMemsetAsync(bad, 0, 4, h->stream);
+    if (e == hipSuccess) {
+        lm_launch_unblock(h->stream, info.id, (const unsigned char*)raw.p, numel, out, bad);
+        if (bad) e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    }
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "upload '%s': %s", t->name, hipGetErrorString(e));
+    if (bad_h && info.device == WF_Q40) return fail(RCA_ERR_ARG, "tensor '%s': a Q4_0 block's 8 d is not finite in fp16", t->name);   // Q4_1 is refused in these words too
+    if (bad_h) return fail(RCA_ERR_ARG, "tensor '%s': an %s block's d is not finite", t->name, info.name);
+    return RCA_OK;
+}
 // Uploads a matrix.  RCA_BF16 / RCA_F16 stay what they are; RCA_F32 is rounded to bf16 (nearest even: this build's storage format
-// for 32-bit checkpoints); RCA_Q8_0 (the 34-byte GGUF blocks as they sit in the file) is unblocked.
+// for 32-bit checkpoints); the quantised types go through lm_upload_blocks.
 static int lm_upload_raw(rca_lm* h, const rca_tensor_t* ts, int nt, const std::string& name, long rows, long cols, RawMat* out) {
     const rca_tensor_t* t = find_tensor(ts, nt, name);
     const long numel = rows * cols;
     if (!t) return fail(RCA_ERR_MISSING, "tensor '%s' missing", name.c_str());
     if (t->numel != numel) return fail(RCA_ERR_ARG, "tensor '%s': numel %ld, expected %ld", name.c_str(), (long)t->numel, numel);
     int rc;
-    if (t->dtype == RCA_Q8_0) {
-        if ((rc = out->alloc(WF_Q8, rows, cols)) != RCA_OK) return rc;
-        const long nblk = numel / 32;
-        unsigned char* raw = nullptr;
-        if ((rc = lm_alloc((void**)&raw, (size_t)nblk * 34)) != RCA_OK) { out->release(); return rc; }
-        hipError_t e = hipMemcpy(raw, t->data, (size_t)nblk * 34, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            lm_q8_unblock_kernel<<<4096, 256, 0, h->stream>>>(raw, nblk, out->q, out->d);
-            e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(raw);
-        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
-        return RCA_OK;
-    }
-    if (t->dtype == RCA_Q6_K) {
-        if ((rc = out->alloc(WF_Q6K, rows, cols)) != RCA_OK) return rc;
-        const long nblk = numel / 256;
-        unsigned char* raw = nullptr;
-        if ((rc = lm_alloc((void**)&raw, (size_t)nblk * 210)) != RCA_OK) { out->release(); return rc; }
-        hipError_t e = hipMemcpy(raw, t->data, (size_t)nblk * 210, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            lm_q6k_unblock_kernel<<<4096, 256, 0, h->stream>>>(raw, nblk, out->q, (signed char*)out->d, (f16_t*)out->dd);
-            e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(raw);
-        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
-        return RCA_OK;
-    }
-    if (t->dtype == RCA_Q5_K) {
-        if ((rc = out->alloc(WF_Q5K, rows, cols)) != RCA_OK) return rc;
-        const long nblk = numel / 256;
-        unsigned char* raw = nullptr;
-        if ((rc = lm_alloc((void**)&raw, (size_t)nblk * 176)) != RCA_OK) { out->release(); return rc; }
-        hipError_t e = hipMemcpy(raw, t->data, (size_t)nblk * 176, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            lm_q5k_unblock_kernel<<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, (unsigned short*)out->d, out->dd);
-            e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(raw);
-        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
-        return RCA_OK;
-    }
-    if (t->dtype == RCA_Q4_0 || t->dtype == RCA_Q4_1) {
-        const bool q41 = t->dtype == RCA_Q4_1;
-        if ((rc = out->alloc(q41 ? WF_Q41 : WF_Q40, rows, cols)) != RCA_OK) return rc;
-        const long nblk = numel / 32;
-        const size_t nbytes = (size_t)nblk * (q41 ? 20 : 18);
-        unsigned char* raw = nullptr;   // the blocks, then the flag "a block's 8 d overflows fp16"
-        if ((rc = lm_alloc((void**)&raw, nbytes + 8)) != RCA_OK) { out->release(); return rc; }
-        int* bad = reinterpret_cast<int*>(raw + ((nbytes + 3) & ~(size_t)3));
-        int bad_h = 0;
-        hipError_t e = hipMemcpy(raw, t->data, nbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 4, h->stream);
-        if (e == hipSuccess) {
-            if (q41) lm_q40_unblock_kernel<true><<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, out->dd, bad);
-            else lm_q40_unblock_kernel<false><<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, out->dd, bad);
-            e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(raw);
-        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
-        if (bad_h) { out->release(); return fail(RCA_ERR_ARG, "tensor '%s': a Q4_0 block's 8 d is not finite in fp16", name.c_str()); }
-        return RCA_OK;
-    }
-    if (t->dtype == RCA_IQ4_NL || t->dtype == RCA_IQ4_XS) {
-        const bool xs = t->dtype == RCA_IQ4_XS;
-        if ((rc = out->alloc(xs ? WF_IQ4XS : WF_IQ4, rows, cols)) != RCA_OK) return rc;   // rows of whole 256-value blocks
-        const long nblk = numel / 32;
-        const size_t nbytes = xs ? (size_t)(numel / 256) * 136 : (size_t)nblk * 18;
-        unsigned char* raw = nullptr;   // the blocks, then the flag "a block's d is not finite"
-        if ((rc = lm_alloc((void**)&raw, nbytes + 8)) != RCA_OK) { out->release(); return rc; }
-        int* bad = reinterpret_cast<int*>(raw + ((nbytes + 3) & ~(size_t)3));
-        int bad_h = 0;
-        hipError_t e = hipMemcpy(raw, t->data, nbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 4, h->stream);
-        if (e == hipSuccess) {
-            if (xs) lm_iq4_unblock_kernel<true><<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, out->dd, bad);
-            else lm_iq4_unblock_kernel<false><<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, out->dd, bad);
-            e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(raw);
-        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
-        if (bad_h) { out->release(); return fail(RCA_ERR_ARG, "tensor '%s': an %s block's d is not finite", name.c_str(), xs ? "IQ4_XS" : "IQ4_NL"); }
-        return RCA_OK;
-    }
-    if (t->dtype == RCA_Q4_K) {
-        if ((rc = out->alloc(WF_Q4K, rows, cols)) != RCA_OK) return rc;
-        const long nblk = numel / 256;
-        unsigned char* raw = nullptr;
-        if ((rc = lm_alloc((void**)&raw, (size_t)nblk * 144)) != RCA_OK) { out->release(); return rc; }
-        hipError_t e = hipMemcpy(raw, t->data, (size_t)nblk * 144, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            lm_q4k_unblock_kernel<<<4096, 256, 0, h->stream>>>(raw, nblk, (unsigned char*)out->q, (unsigned short*)out->d, out->dd);
-            e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(raw);
-        if (e != hipSuccess) { out->release(); return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e)); }
-        return RCA_OK;
-    }
+    if (const WfInfo* info = wf_of_blocks(t->dtype)) return lm_upload_blocks(h, t, *info, rows, cols, out);
     if (t->dtype == RCA_BF16 || t->dtype == RCA_F16) {
         if ((rc = out->alloc(t->dtype == RCA_F16 ? WF_F16 : WF_BF16, rows, cols)) != RCA_OK) return rc;
         RCA_HIP(hipMemcpy(out->w16, t->data, (size_t)numel * 2, hipMemcpyHostToDevice));
@@ -2886,14 +2931,13 @@ static int lm_upload_raw(rca_lm* h, const rca_tensor_t* ts, int nt, const std::s
     }
     if (t->dtype != RCA_F32) return fail(RCA_ERR_ARG, "tensor '%s': dtype %d is not supported for a projection matrix", name.c_str(), t->dtype);
     if ((rc = out->alloc(WF_BF16, rows, cols)) != RCA_OK) return rc;
-    float* tmp = nullptr;
-    if ((rc = lm_alloc((void**)&tmp, (size_t)numel * 4)) != RCA_OK) return rc;
-    hipError_t e = hipMemcpy(tmp, t->data, (size_t)numel * 4, hipMemcpyHostToDevice);
+    DevScratch tmp;
+    if ((rc = tmp.alloc((size_t)numel * 4)) != RCA_OK) return rc;
+    hipError_t e = hipMemcpy(tmp.p, t->data, (size_t)numel * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        lm_f32_to_bf16_kernel<<<2048, 256, 0, h->stream>>>(tmp, out->w16, numel);
+        lm_f32_to_bf16_kernel<<<2048, 256, 0, h->stream>>>((const float*)tmp.p, out->w16, numel);
         e = hipStreamSynchronize(h->stream);
     }
-    (void)hipFree(tmp);
     if (e != hipSuccess) return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e));
     return RCA_OK;
 }
@@ -2917,29 +2961,21 @@ static int lm_upload_embed(rca_lm* h, const rca_tensor_t* ts, int nt, const std:
         return RCA_OK;
     }
     if (t->dtype == RCA_F16) {
-        f16_t* tmp = nullptr;
-        if ((rc = lm_alloc((void**)&tmp, (size_t)numel * 2)) != RCA_OK) return rc;
-        hipError_t e = hipMemcpy(tmp, t->data, (size_t)numel * 2, hipMemcpyHostToDevice);
+        DevScratch tmp;
+        if ((rc = tmp.alloc((size_t)numel * 2)) != RCA_OK) return rc;
+        hipError_t e = hipMemcpy(tmp.p, t->data, (size_t)numel * 2, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-            lm_f16_to_f32_kernel<<<4096, 256, 0, h->stream>>>(tmp, (float*)h->embed, numel);
+            lm_f16_to_f32_kernel<<<4096, 256, 0, h->stream>>>((const f16_t*)tmp.p, (float*)h->embed, numel);
             e = hipStreamSynchronize(h->stream);
         }
-        (void)hipFree(tmp);
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e));
         return RCA_OK;
     }
-    if (t->dtype == RCA_Q8_0 || t->dtype == RCA_Q4_K || t->dtype == RCA_Q6_K || t->dtype == RCA_Q5_K || t->dtype == RCA_Q4_0 || t->dtype == RCA_Q4_1 ||
-        t->dtype == RCA_IQ4_NL || t->dtype == RCA_IQ4_XS) {
+    if (const WfInfo* info = wf_of_blocks(t->dtype)) {
         RawMat raw;
-        if ((rc = lm_upload_raw(h, ts, nt, name, rows, cols, &raw)) != RCA_OK) return rc;
-        if (raw.fmt == WF_Q6K) lm_q6k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>(raw.q, (const signed char*)raw.d, (const f16_t*)raw.dd, (float*)h->embed, numel);
-        else if (raw.fmt == WF_Q4K || raw.fmt == WF_Q5K)   // the plain byte holds the whole value, 4 or 5 bits
-            lm_q4k_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, (const unsigned short*)raw.d, raw.dd, (float*)h->embed, numel);
-        else if (raw.fmt == WF_Q40 || raw.fmt == WF_Q41) lm_q40_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, raw.dd, (float*)h->embed, numel);
-        else if (raw.fmt == WF_IQ4 || raw.fmt == WF_IQ4XS) lm_iq4_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>((const unsigned char*)raw.q, raw.dd, (float*)h->embed, numel);
-        else lm_q8_dequant_f32_kernel<<<4096, 256, 0, h->stream>>>(raw.q, raw.d, (float*)h->embed, numel);
+        if ((rc = lm_upload_blocks(h, t, *info, rows, cols, &raw)) != RCA_OK) return rc;
+        lm_launch_dequant_f32(h->stream, raw, (float*)h->embed, numel);
         hipError_t e = hipStreamSynchronize(h->stream);
-        raw.release();
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "upload '%s': %s", name.c_str(), hipGetErrorString(e));
         return RCA_OK;
     }
@@ -2967,91 +3003,43 @@ static int lm_upload_f32(const rca_tensor_t* ts, int nt, const std::string& name
     return RCA_OK;
 }
 
-// rca_lm_config_t::decode_weights applied to one plain matrix: 1 = quantise to q8_0 the way llama-quantize does, 2 = fp16,
-// 3 / 4 = this build's Q4_K / Q5_K quantiser, 5 / 6 = ggml's reference Q4_0 / Q4_1 rule, 7 = this build's IQ4_NL rule.
+// rca_lm_config_t::decode_weights (DW_*) applied to one plain matrix: q8_0 is quantised the way llama-quantize does, Q4_K / Q5_K by this
+// build's quantiser, Q4_0 / Q4_1 by ggml's reference rule, IQ4_NL by this build's rule; DW_F16 converts bf16 to fp16.
 // A matrix that ARRIVED quantised stays what it is.
 static int lm_raw_convert(rca_lm* h, RawMat* m, int want) {
-    if (want == 0 || wf_packed(m->fmt)) return RCA_OK;
+    if (want == DW_AS_SUPPLIED || wf_packed(m->fmt)) return RCA_OK;
     int rc;
-    if (want == 7) {
-        RawMat qd;
-        if ((rc = qd.alloc(WF_IQ4, m->rows, m->cols)) != RCA_OK) return rc;
-        int* bad = nullptr;
-        int bad_h = 0;
-        if ((rc = lm_alloc((void**)&bad, 4)) != RCA_OK) { qd.release(); return rc; }
-        hipError_t e = hipMemsetAsync(bad, 0, 4, h->stream);
-        if (e == hipSuccess) {
-            lm_iq4nl_quantize_kernel<<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 32, (unsigned char*)qd.q, qd.dd, bad);
-            e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(bad);
-        m->release();
-        if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "IQ4_NL quantise: %s", hipGetErrorString(e)); }
-        if (bad_h) { qd.release(); return fail(RCA_ERR_ARG, "IQ4_NL quantise: a block's d is not finite in fp16"); }
-        *m = qd;
-        return RCA_OK;
-    }
-    if (want == 5 || want == 6) {
-        RawMat qd;
-        if ((rc = qd.alloc(want == 6 ? WF_Q41 : WF_Q40, m->rows, m->cols)) != RCA_OK) return rc;
-        int* bad = nullptr;
-        int bad_h = 0;
-        if ((rc = lm_alloc((void**)&bad, 4)) != RCA_OK) { qd.release(); return rc; }
-        hipError_t e = hipMemsetAsync(bad, 0, 4, h->stream);
-        if (e == hipSuccess) {
-            if (want == 6) lm_q40_quantize_kernel<true><<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 32, (unsigned char*)qd.q, qd.dd, bad);
-            else lm_q40_quantize_kernel<false><<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 32, (unsigned char*)qd.q, qd.dd, bad);
-            e = hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        }
-        (void)hipFree(bad);
-        m->release();
-        if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "%s quantise: %s", want == 6 ? "Q4_1" : "Q4_0", hipGetErrorString(e)); }
-        if (bad_h) { qd.release(); return fail(RCA_ERR_ARG, "Q4_0 quantise: a block's 8 d is not finite in fp16"); }
-        *m = qd;
-        return RCA_OK;
-    }
-    if (want == 3) {
-        RawMat qd;
-        if ((rc = qd.alloc(WF_Q4K, m->rows, m->cols)) != RCA_OK) return rc;
-        lm_q4k_quantize_kernel<15><<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 256, (unsigned char*)qd.q, (unsigned short*)qd.d, qd.dd);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        m->release();
-        if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "Q4_K quantise: %s", hipGetErrorString(e)); }
-        *m = qd;
-        return RCA_OK;
-    }
-    if (want == 4) {
-        RawMat qd;
-        if ((rc = qd.alloc(WF_Q5K, m->rows, m->cols)) != RCA_OK) return rc;
-        lm_q4k_quantize_kernel<31><<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 256, (unsigned char*)qd.q, (unsigned short*)qd.d, qd.dd);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        m->release();
-        if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "Q5_K quantise: %s", hipGetErrorString(e)); }
-        *m = qd;
-        return RCA_OK;
-    }
-    if (want == 1) {
-        RawMat qd;
-        if ((rc = qd.alloc(WF_Q8, m->rows, m->cols)) != RCA_OK) return rc;
-        lm_q8_quantize_kernel<<<4096, 256, 0, h->stream>>>(m->w16, m->fmt == WF_F16, m->rows * m->cols / 32, qd.q, qd.d);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        m->release();
-        if (e != hipSuccess) { qd.release(); return fail(RCA_ERR_HIP, "q8_0 quantise: %s", hipGetErrorString(e)); }
-        *m = qd;
-        return RCA_OK;
-    }
-    if (want == 2 && m->fmt == WF_BF16) {
-        f16_t* out = nullptr;
-        if ((rc = lm_alloc((void**)&out, (size_t)m->rows * m->cols * 2)) != RCA_OK) return rc;
-        lm_bf16_to_f16_kernel<<<4096, 256, 0, h->stream>>>(m->w16, out, m->rows * m->cols);
+    if (want == DW_F16) {
+        if (m->fmt != WF_BF16) return RCA_OK;
+        DevScratch out;
+        if ((rc = out.alloc((size_t)m->rows * m->cols * 2)) != RCA_OK) return rc;
+        lm_bf16_to_f16_kernel<<<4096, 256, 0, h->stream>>>(m->w16, (f16_t*)out.p, m->rows * m->cols);
         hipError_t e = hipStreamSynchronize(h->stream);
         (void)hipFree(m->w16);
-        m->w16 = reinterpret_cast<bf16_t*>(out);
+        m->w16 = reinterpret_cast<bf16_t*>(out.take());
         m->fmt = WF_F16;
         if (e != hipSuccess) return fail(RCA_ERR_HIP, "fp16 conversion: %s", hipGetErrorString(e));
+        return RCA_OK;
     }
+    const WfInfo& info = WF_TABLE[DW_FORMAT[want]];
+    RawMat qd;
+    if ((rc = qd.alloc(info.id, m->rows, m->cols)) != RCA_OK) return rc;
+    DevScratch bad;   // (bad_flag) the flag "a block's factor is not finite in fp16"
+    int bad_h = 0;
+    hipError_t e = hipSuccess;
+    if (info.bad_flag) {
+        if ((rc = bad.alloc(4)) != RCA_OK) return rc;
+        e = hipMemsetAsync(bad.p, 0, 4, h->stream);
+    }
+    if (e == hipSuccess) {
+        lm_launch_quantize(h->stream, info.id, *m, &qd, (int*)bad.p);
+        if (info.bad_flag) e = hipMemcpyAsync(&bad_h, bad.p, 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    }
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s quantise: %s", info.name, hipGetErrorString(e));
+    // (worded after the device form: Q4_1 is refused as Q4_0 is)
+    if (bad_h) return fail(RCA_ERR_ARG, "%s quantise: a block's %sd is not finite in fp16", WF_TABLE[info.device].name, info.device == WF_Q40 ? "8 " : "");
+    *m = std::move(qd);
     return RCA_OK;
 }
 // rows of `parts` stacked (q; k; v).  Parts of different formats cannot be fused.
@@ -3091,76 +3079,30 @@ static int lm_raw_interleave(rca_lm* h, RawMat* a, RawMat* b, RawMat* out, const
     return RCA_OK;
 }
 // plain -> the layout the decode GEMV streams.  Takes ownership of `raw` (released or moved into `out`).
-static int lm_finish_mat(rca_lm* h, RawMat* raw, int qkv_pairs, WMat* out, const char* what) {
-    out->fmt = raw->fmt; out->N = (int)raw->rows; out->K = (int)raw->cols;
-    if (raw->fmt == WF_Q4K || raw->fmt == WF_Q5K) {
-        const int N = out->N, K = out->K;
-        const bool q5 = raw->fmt == WF_Q5K;
-        const char* fn = q5 ? "Q5_K" : "Q4_K";
-        if ((K % 256) || (N % 4) || (qkv_pairs && (N % 64))) { raw->release(); return fail(RCA_ERR_ARG, "%s weights: %s is %d x %d (K must be a multiple of 256, N of 4)", fn, what, N, K); }
-        int rc;
-        const long nquad = N / 4, nchunk = K / 8, g16 = (N + 15) / 16;
-        const size_t scm_bytes = (size_t)g16 * (K / 32) * 16 * 2, dd_bytes = (size_t)g16 * (K / 256) * 16 * 4;
-        if ((rc = lm_alloc((void**)&out->qs, (size_t)nquad * nchunk * 16)) != RCA_OK || (rc = lm_alloc((void**)&out->sc, scm_bytes)) != RCA_OK ||
-            (rc = lm_alloc((void**)&out->dd, dd_bytes)) != RCA_OK || (q5 && (rc = lm_alloc((void**)&out->qh, (size_t)nquad * nchunk * 4)) != RCA_OK)) { raw->release(); return rc; }
-        (void)hipMemsetAsync(out->sc, 0, scm_bytes, h->stream);
-        (void)hipMemsetAsync(out->dd, 0, dd_bytes, h->stream);
-        if (q5)
-            lm_q4k_pack_kernel<WF_Q5K><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
-                                                                  (unsigned short*)out->sc, out->dd, out->qh);
-        else
-            lm_q4k_pack_kernel<WF_Q4K><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, (const unsigned short*)raw->d, raw->dd, N, K, qkv_pairs, out->qs,
-                                                                   (unsigned short*)out->sc, out->dd, nullptr);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        raw->release();
-        if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s pack of %s: %s", fn, what, hipGetErrorString(e));
+static int lm_finish_mat(rca_lm* h, RawMat* src, int qkv_pairs, WMat* out, const char* what) {
+    RawMat raw = std::move(*src);   // freed when this returns
+    const WfInfo& info = WF_TABLE[raw.fmt];
+    const int N = (int)raw.rows, K = (int)raw.cols;
+    out->fmt = raw.fmt; out->N = N; out->K = K;
+    if (!wf_packed(raw.fmt)) {
+        out->w = raw.w16;
+        raw.w16 = nullptr;
         return RCA_OK;
     }
-    if (raw->fmt == WF_Q40 || raw->fmt == WF_Q41 || raw->fmt == WF_IQ4 || raw->fmt == WF_IQ4XS) {   // IQ4: the same arrays, the factor dword is an f32
-        const int N = out->N, K = out->K;
-        const char* fn = raw->fmt == WF_IQ4 ? "IQ4_NL" : (raw->fmt == WF_IQ4XS ? "IQ4_XS" : (raw->fmt == WF_Q41 ? "Q4_1" : "Q4_0"));
-        if ((K % 256) || (N % 4) || (qkv_pairs && (N % 64))) { raw->release(); return fail(RCA_ERR_ARG, "%s weights: %s is %d x %d (K must be a multiple of 256, N of 4)", fn, what, N, K); }
-        int rc;
-        const long nquad = N / 4, nchunk = K / 8, g16 = (N + 15) / 16;
-        const size_t st_bytes = (size_t)g16 * (K / 32) * 16 * 4;   // groups of 16 slots, zero padded
-        if ((rc = lm_alloc((void**)&out->qs, (size_t)nquad * nchunk * 16)) != RCA_OK || (rc = lm_alloc((void**)&out->sc, st_bytes)) != RCA_OK) { raw->release(); return rc; }
-        (void)hipMemsetAsync(out->sc, 0, st_bytes, h->stream);
-        lm_q4k_pack_kernel<WF_Q40><<<4096, 256, 0, h->stream>>>((const unsigned char*)raw->q, nullptr, raw->dd, N, K, qkv_pairs, out->qs, nullptr, out->sc, nullptr);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        raw->release();
-        if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s pack of %s: %s", fn, what, hipGetErrorString(e));
-        return RCA_OK;
-    }
-    if (raw->fmt == WF_Q6K) {
-        const int N = out->N, K = out->K;
-        if ((K % 256) || (N % 2) || (qkv_pairs && (N % 64))) { raw->release(); return fail(RCA_ERR_ARG, "Q6_K weights: %s is %d x %d (K must be a multiple of 256, N even)", what, N, K); }
-        int rc;
-        const long npairs = N / 2, nchunk = K / 8;
-        const size_t sc_bytes = (size_t)((npairs + 7) / 8) * (K / 16) * 8 * 2 * 4;
-        if ((rc = lm_alloc((void**)&out->qs, (size_t)npairs * nchunk * 16)) != RCA_OK || (rc = lm_alloc((void**)&out->sc, sc_bytes)) != RCA_OK) { raw->release(); return rc; }
-        (void)hipMemsetAsync(out->sc, 0, sc_bytes, h->stream);
-        lm_q6k_pack_kernel<<<4096, 256, 0, h->stream>>>(raw->q, (const signed char*)raw->d, (const f16_t*)raw->dd, N, K, qkv_pairs, out->qs, (float*)out->sc);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        raw->release();
-        if (e != hipSuccess) return fail(RCA_ERR_HIP, "Q6_K pack of %s: %s", what, hipGetErrorString(e));
-        return RCA_OK;
-    }
-    if (raw->fmt != WF_Q8) {
-        out->w = raw->w16;
-        raw->w16 = nullptr;
-        return RCA_OK;
-    }
-    const int N = out->N, K = out->K;
-    if ((K % 32) || (N % 2) || (qkv_pairs && (N % 64))) { raw->release(); return fail(RCA_ERR_ARG, "q8_0 weights: %s is %d x %d (K must be a multiple of 32, N even)", what, N, K); }
-    int rc;
-    const long npairs = N / 2, nchunk = K / 8;
-    if ((rc = lm_alloc((void**)&out->qs, (size_t)npairs * nchunk * 16)) != RCA_OK ||
-        (rc = lm_alloc((void**)&out->sc, (size_t)((npairs + 7) / 8) * (K / 32) * 8 * 4)) != RCA_OK) { raw->release(); return rc; }   // groups of 8 pairs, zero padded
-    (void)hipMemsetAsync(out->sc, 0, (size_t)((npairs + 7) / 8) * (K / 32) * 8 * 4, h->stream);
-    lm_q8_pack_kernel<<<4096, 256, 0, h->stream>>>(raw->q, raw->d, N, K, qkv_pairs, out->qs, out->sc);
+    if ((K % info.k_mult) || (N % info.n_mult) || (qkv_pairs && (N % 64)))
+        return fail(RCA_ERR_ARG, "%s weights: %s is %d x %d (K must be a multiple of %d, N %s)", info.name, what, N, K, info.k_mult, info.n_word);
+    for (int zero = 0; zero < 2; ++zero)   // every array is allocated, then the factor arrays are zeroed
+        for (const WfPart& p : info.packed) {
+            if (p.arr == WA_NONE) continue;
+            const bool padded = p.arr == WA_SC || p.arr == WA_DD;   // the factor arrays: whole groups of 16 rows, zero padded
+            const size_t bytes = (size_t)(padded ? (N + 15) / 16 * 16 : N) * (K / p.per * p.bytes);
+            int rc;
+            if (!zero && (rc = lm_alloc(out->array(p.arr), bytes)) != RCA_OK) return rc;
+            if (zero && padded) (void)hipMemsetAsync(*out->array(p.arr), 0, bytes, h->stream);
+        }
+    lm_launch_pack(h->stream, raw, qkv_pairs, out);
     hipError_t e = hipStreamSynchronize(h->stream);
-    raw->release();
-    if (e != hipSuccess) return fail(RCA_ERR_HIP, "q8_0 pack of %s: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RCA_ERR_HIP, "%s pack of %s: %s", info.name, what, hipGetErrorString(e));
     return RCA_OK;
 }
 
@@ -3287,22 +3229,20 @@ static int lm_build_layer(rca_lm* h, LmLayer& L, RawMat& q, RawMat& k, RawMat& v
     const int want = h->cfg.decode_weights;
     int rc = RCA_OK;
     RawMat qkv, gu;
-    auto done = [&](int code) { for (RawMat* m : {&q, &k, &v, &o, &g, &u, &dn, &qkv, &gu}) m->release(); return code; };
     for (RawMat* m : {&q, &k, &v, &o, &g, &u, &dn})
-        if ((rc = lm_raw_convert(h, m, want)) != RCA_OK) return done(rc);
+        if ((rc = lm_raw_convert(h, m, want)) != RCA_OK) return rc;
     if (q.fmt == k.fmt && k.fmt != v.fmt) {   // llama-quantize Q4_K_M: attn_v is Q6_K in the layers use_more_bits() picks, attn_q / attn_k Q4_K
-        if ((rc = lm_raw_concat(h, {&q, &k}, &qkv, "the fused QK projection")) != RCA_OK) return done(rc);
-        if ((rc = lm_finish_mat(h, &v, 1, &L.vseg, "v_proj")) != RCA_OK) return done(rc);
+        if ((rc = lm_raw_concat(h, {&q, &k}, &qkv, "the fused QK projection")) != RCA_OK) return rc;
+        if ((rc = lm_finish_mat(h, &v, 1, &L.vseg, "v_proj")) != RCA_OK) return rc;
         L.split_v = true;
-    } else if ((rc = lm_raw_concat(h, {&q, &k, &v}, &qkv, "the fused QKV projection")) != RCA_OK) return done(rc);
-    q.release(); k.release(); v.release();
-    if ((rc = lm_raw_interleave(h, &g, &u, &gu, "the fused gate/up projection")) != RCA_OK) return done(rc);
+    } else if ((rc = lm_raw_concat(h, {&q, &k, &v}, &qkv, "the fused QKV projection")) != RCA_OK) return rc;
+    q.release(); k.release(); v.release();   // (before the next matrices are built: the peak of device memory at load)
+    if ((rc = lm_raw_interleave(h, &g, &u, &gu, "the fused gate/up projection")) != RCA_OK) return rc;
     g.release(); u.release();
-    if ((rc = lm_finish_mat(h, &qkv, 1, &L.qkv, "the fused QKV projection")) != RCA_OK) return done(rc);
-    if ((rc = lm_finish_mat(h, &o, 0, &L.o, "o_proj")) != RCA_OK) return done(rc);
-    if ((rc = lm_finish_mat(h, &gu, 0, &L.gu, "the fused gate/up projection")) != RCA_OK) return done(rc);
-    if ((rc = lm_finish_mat(h, &dn, 0, &L.down, "down_proj")) != RCA_OK) return done(rc);
-    return done(RCA_OK);
+    if ((rc = lm_finish_mat(h, &qkv, 1, &L.qkv, "the fused QKV projection")) != RCA_OK) return rc;
+    if ((rc = lm_finish_mat(h, &o, 0, &L.o, "o_proj")) != RCA_OK) return rc;
+    if ((rc = lm_finish_mat(h, &gu, 0, &L.gu, "the fused gate/up projection")) != RCA_OK) return rc;
+    return lm_finish_mat(h, &dn, 0, &L.down, "down_proj");
 }
 
 extern "C" int rca_lm_create(const rca_lm_config_t* cfg, const rca_tensor_t* ts, int32_t nt, int32_t device, rca_lm_t** out) {
@@ -3317,7 +3257,7 @@ extern "C" int rca_lm_create(const rca_lm_config_t* cfg, const rca_tensor_t* ts,
     {
         RawMat ph;
         if ((rc = lm_upload_raw(h, ts, nt, "lm_head.weight", V, H, &ph)) != RCA_OK) return bail(rc);
-        if ((rc = lm_raw_convert(h, &ph, c.decode_weights)) != RCA_OK) { ph.release(); return bail(rc); }
+        if ((rc = lm_raw_convert(h, &ph, c.decode_weights)) != RCA_OK) return bail(rc);
         if ((rc = lm_finish_mat(h, &ph, 0, &h->head, "lm_head")) != RCA_OK) return bail(rc);
     }
     if ((rc = lm_upload_f32(ts, nt, "model.norm.weight", H, &h->final_norm)) != RCA_OK) return bail(rc);
@@ -3331,10 +3271,8 @@ extern "C" int rca_lm_create(const rca_lm_config_t* cfg, const rca_tensor_t* ts,
             (rc = lm_upload_raw(h, ts, nt, p + "self_attn.o_proj.weight", H, Q, &o)) != RCA_OK ||
             (rc = lm_upload_raw(h, ts, nt, p + "mlp.gate_proj.weight", F, H, &g)) != RCA_OK ||
             (rc = lm_upload_raw(h, ts, nt, p + "mlp.up_proj.weight", F, H, &u)) != RCA_OK ||
-            (rc = lm_upload_raw(h, ts, nt, p + "mlp.down_proj.weight", H, F, &dn)) != RCA_OK) {
-            for (RawMat* m : {&q, &k, &v, &o, &g, &u, &dn}) m->release();
+            (rc = lm_upload_raw(h, ts, nt, p + "mlp.down_proj.weight", H, F, &dn)) != RCA_OK)
             return bail(rc);
-        }
         if ((rc = lm_build_layer(h, L, q, k, v, o, g, u, dn)) != RCA_OK) return bail(rc);
         if ((rc = lm_upload_f32(ts, nt, p + "input_layernorm.weight", H, &L.attn_norm)) != RCA_OK) return bail(rc);
         if ((rc = lm_upload_f32(ts, nt, p + "post_attention_layernorm.weight", H, &L.ffn_norm)) != RCA_OK) return bail(rc);
@@ -3361,7 +3299,7 @@ extern "C" int rca_lm_create_random(const rca_lm_config_t* cfg, uint64_t seed, f
         int r = m.alloc(WF_BF16, rows, cols);
         if (r != RCA_OK) return r;
         lm_random_bf16_kernel<<<4096, 256, 0, h->stream>>>(m.w16, rows * cols, seed, tid++, scale);
-        if ((r = lm_raw_convert(h, &m, c.decode_weights)) != RCA_OK) { m.release(); return r; }
+        if ((r = lm_raw_convert(h, &m, c.decode_weights)) != RCA_OK) return r;
         return lm_finish_mat(h, &m, qkv_pairs, dst, what);
     };
     auto ones = [&](float** p, long n) -> int {
@@ -8116,17 +8054,18 @@ extern "C" int rca_lm_mask_head_rows(rca_lm_t* h, int32_t row_begin, int32_t row
     if (!h || row_begin < 0 || row_end > h->cfg.vocab_size || row_begin > row_end) return fail(RCA_ERR_ARG, "mask_head_rows: bad range");
     RCA_HIP(hipSetDevice(h->device));
     const long n = (long)(row_end - row_begin) * h->cfg.hidden;
-    if (n > 0 && h->head.fmt == WF_Q6K)   // Q6_K (what a Q4_K_M file keeps output.weight in): the row's f32 scales
-        lm_q6k_zero_row_scales_kernel<<<256, 256, 0, h->stream>>>((float*)h->head.sc, h->cfg.hidden / 16, row_begin, row_end);
-    if (n > 0 && (h->head.fmt == WF_Q4K || h->head.fmt == WF_Q5K))   // Q4_K / Q5_K: d = dmin = 0 makes every value of the row (0 * sc) * q - (0 * m) = 0
-        lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.dd, h->cfg.hidden / 256, row_begin, row_end);
-    if (n > 0 && (h->head.fmt == WF_IQ4 || h->head.fmt == WF_IQ4XS))   // IQ4: s = 0 (the f32's zero bits) makes every value of the row 0 * kv[q] = 0
-        lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.sc, h->cfg.hidden / 32, row_begin, row_end);
-    if (n > 0 && (h->head.fmt == WF_Q40 || h->head.fmt == WF_Q41))   // Q4_0 / Q4_1: s = t = 0 makes every value of the row 0 * q - 0 = 0 (the same slot-grouped index, per 32 values)
-        lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>(h->head.sc, h->cfg.hidden / 32, row_begin, row_end);
-    if (n > 0 && (h->head.fmt == WF_BF16 || h->head.fmt == WF_F16)) lm_zero_rows_kernel<<<2048, 256, 0, h->stream>>>(h->head.w + (long)row_begin * h->cfg.hidden, n);   // zero bits
-    if (n > 0 && h->head.fmt == WF_Q8)   // the packed q8_0 head: a row is zero when its block scales are
-        lm_q8_zero_row_scales_kernel<<<256, 256, 0, h->stream>>>(h->head.sc, h->cfg.hidden / 32, row_begin, row_end);
+    // a row of a packed head is zero when its factors are: the table names their array and how many values share one
+    const WfInfo& info = WF_TABLE[h->head.fmt];
+    void* arr = *h->head.array(info.mask.arr);
+    const int per_row = h->cfg.hidden / info.mask.per;
+    if (n > 0) switch (info.device) {
+        case WF_BF16: case WF_F16: lm_zero_rows_kernel<<<2048, 256, 0, h->stream>>>(h->head.w + (long)row_begin * h->cfg.hidden, n); break;   // zero bits
+        case WF_Q8: lm_q8_zero_row_scales_kernel<<<256, 256, 0, h->stream>>>((unsigned*)arr, per_row, row_begin, row_end); break;   // the block scales
+        case WF_Q6K: lm_q6k_zero_row_scales_kernel<<<256, 256, 0, h->stream>>>((float*)arr, per_row, row_begin, row_end); break;   // the row's f32 scales
+        // Q4_K / Q5_K: d = dmin = 0 makes every value of the row (0 * sc) * q - (0 * m) = 0.  Q4_0 / Q4_1: s = t = 0 gives 0 * q - 0 = 0, IQ4: s = 0
+        // (the f32's zero bits) gives 0 * kv[q] = 0 (the same slot-grouped index, per 32 values)
+        default: lm_q4k_zero_row_factors_kernel<<<256, 256, 0, h->stream>>>((unsigned*)arr, per_row, row_begin, row_end); break;
+    }
     RCA_LAUNCH_CHECK();
     RCA_HIP(hipStreamSynchronize(h->stream));
     return RCA_OK;

@@ -34,6 +34,8 @@ from typing import Any, BinaryIO, Dict, Tuple
 
 import numpy as np
 
+from . import _native as N
+
 GGUF_MAGIC = 0x46554747  # "GGUF"
 GGML_F32, GGML_F16, GGML_Q4_0, GGML_Q4_1, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_BF16 = 0, 1, 2, 3, 8, 12, 13, 14, 30
 GGML_IQ4_NL, GGML_IQ4_XS = 20, 23
@@ -85,82 +87,40 @@ def _read_value(f: BinaryIO, t: int):
     raise GGUFError(f"unknown metadata value type {t}")
 
 
+# ggml type -> (name, values per block, bytes per block, numpy view of a plain type | the _native class that keeps the blocks)
+_TYPES = {
+    GGML_F32: ("F32", 1, 4, np.float32), GGML_F16: ("F16", 1, 2, np.float16), GGML_BF16: ("BF16", 1, 2, np.uint16),   # BF16: the bits
+    GGML_Q8_0: ("Q8_0", 32, 34, N.Q8Blocks), GGML_Q4_0: ("Q4_0", 32, 18, N.Q40Blocks), GGML_Q4_1: ("Q4_1", 32, 20, N.Q41Blocks),
+    GGML_Q4_K: ("Q4_K", 256, 144, N.Q4KBlocks), GGML_Q5_K: ("Q5_K", 256, 176, N.Q5KBlocks), GGML_Q6_K: ("Q6_K", 256, 210, N.Q6KBlocks),
+    GGML_IQ4_NL: ("IQ4_NL", 32, 18, N.IQ4NLBlocks), GGML_IQ4_XS: ("IQ4_XS", 256, 136, N.IQ4XSBlocks),
+}
+_SUPPORTED = "F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS are"
+
+
+def _type(ttype: int, which: str = ""):
+    if ttype not in _TYPES:
+        raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported ({_SUPPORTED}{which})")
+    return _TYPES[ttype]
+
+
 def _dequant(raw: np.ndarray, ttype: int, numel: int) -> np.ndarray:
     """-> float32 [numel] (or uint16 bf16 bits for BF16 / float16 for F16, which the loader uploads as they are)."""
-    if ttype == GGML_F32:
-        return raw.view(np.float32)[:numel]
-    if ttype == GGML_F16:
-        return raw.view(np.float16)[:numel]
-    if ttype == GGML_BF16:
-        return raw.view(np.uint16)[:numel]
-    if ttype == GGML_Q8_0:  # blocks of 32: f16 scale + 32 x int8
-        nb = numel // 32
-        blk = raw[: nb * 34].reshape(nb, 34)
-        d = blk[:, :2].copy().view(np.float16).astype(np.float32)          # [nb,1]
-        q = blk[:, 2:].view(np.int8).astype(np.float32)                    # [nb,32]
-        return (q * d).reshape(-1)
-    if ttype in (GGML_Q4_0, GGML_Q4_1):
-        from ._native import Q40Blocks, Q41Blocks
-        cls = Q41Blocks if ttype == GGML_Q4_1 else Q40Blocks
-        return cls(raw[: numel // 32 * cls.BLOCK_BYTES], (numel // 32, 32)).dequantize().reshape(-1)
-    if ttype == GGML_IQ4_NL:
-        from ._native import IQ4NLBlocks
-        return IQ4NLBlocks(raw[: numel // 32 * 18], (numel // 32, 32)).dequantize().reshape(-1)
-    if ttype == GGML_IQ4_XS:
-        from ._native import IQ4XSBlocks
-        return IQ4XSBlocks(raw[: numel // 256 * 136], (numel // 256, 256)).dequantize().reshape(-1)
-    if ttype == GGML_Q4_K:
-        from ._native import Q4KBlocks
-        return Q4KBlocks(raw[: numel // 256 * 144], (numel // 256, 256)).dequantize().reshape(-1)
-    if ttype == GGML_Q5_K:
-        from ._native import Q5KBlocks
-        return Q5KBlocks(raw[: numel // 256 * 176], (numel // 256, 256)).dequantize().reshape(-1)
-    if ttype == GGML_Q6_K:
-        from ._native import Q6KBlocks
-        return Q6KBlocks(raw[: numel // 256 * 210], (numel // 256, 256)).dequantize().reshape(-1)
-    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS are)")
+    _, vals, nbytes, kind = _type(ttype)
+    if vals == 1:
+        return raw.view(kind)[:numel]
+    return kind(raw[: numel // vals * nbytes], (numel // vals, vals)).dequantize().reshape(-1)
 
 
 def _nbytes(ttype: int, numel: int) -> int:
-    if ttype == GGML_F32:
-        return 4 * numel
-    if ttype in (GGML_F16, GGML_BF16):
-        return 2 * numel
-    if ttype == GGML_Q8_0:
-        if numel % 32:
-            raise GGUFError("Q8_0 tensor whose size is not a multiple of 32")
-        return numel // 32 * 34
-    if ttype in (GGML_Q4_0, GGML_Q4_1):
-        if numel % 32:
-            raise GGUFError(f"{_TYPE_NAMES[ttype]} tensor whose size is not a multiple of 32")
-        return numel // 32 * (20 if ttype == GGML_Q4_1 else 18)
-    if ttype == GGML_IQ4_NL:
-        if numel % 32:
-            raise GGUFError("IQ4_NL tensor whose size is not a multiple of 32")
-        return numel // 32 * 18
-    if ttype == GGML_IQ4_XS:
-        if numel % 256:
-            raise GGUFError("IQ4_XS tensor whose size is not a multiple of 256")
-        return numel // 256 * 136
-    if ttype == GGML_Q4_K:
-        if numel % 256:
-            raise GGUFError("Q4_K tensor whose size is not a multiple of 256")
-        return numel // 256 * 144
-    if ttype == GGML_Q5_K:
-        if numel % 256:
-            raise GGUFError("Q5_K tensor whose size is not a multiple of 256")
-        return numel // 256 * 176
-    if ttype == GGML_Q6_K:
-        if numel % 256:
-            raise GGUFError("Q6_K tensor whose size is not a multiple of 256")
-        return numel // 256 * 210
-    raise GGUFError(f"tensor type {_TYPE_NAMES.get(ttype, ttype)} is not supported (F32, F16, BF16, Q8_0, Q4_0, Q4_1, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS are: the types "
-                    "of the reference's F16 / Q8_0 / Q4_K_M files and of Q5_K_S / Q5_K_M and Q4_0 ones, and of IQ4_NL / IQ4_XS ones)")
+    name, vals, nbytes, _ = _type(ttype, ": the types of the reference's F16 / Q8_0 / Q4_K_M files and of Q5_K_S / Q5_K_M and Q4_0 ones, and of IQ4_NL / IQ4_XS ones")
+    if numel % vals:
+        raise GGUFError(f"{name} tensor whose size is not a multiple of {vals}")
+    return numel // vals * nbytes
 
 
 def read_gguf(path: str, keep_q8_0: bool = False) -> Tuple[Dict[str, Any], Dict[str, np.ndarray]]:
-    """-> (metadata, tensors).  Tensors keep their GGUF names; shapes are row-major (reversed `ne`).  keep_q8_0: 2-D Q8_0 tensors
-    come back as _native.Q8Blocks (the raw 34-byte blocks) instead of being de-quantised."""
+    """-> (metadata, tensors).  Tensors keep their GGUF names; shapes are row-major (reversed `ne`).  keep_q8_0: 2-D tensors of a
+    quantised type come back as the _native.*Blocks class of _TYPES (the raw blocks; Q8_0: Q8Blocks) instead of being de-quantised."""
     with open(path, "rb") as f:
         if _read(f, "<I") != GGUF_MAGIC:
             raise GGUFError(f"{path}: not a GGUF file")
@@ -190,35 +150,11 @@ def read_gguf(path: str, keep_q8_0: bool = False) -> Tuple[Dict[str, Any], Dict[
             if base + off + nb > mm.shape[0]:
                 raise GGUFError(f"tensor '{name}' runs past the end of the file")
             raw = np.asarray(mm[base + off: base + off + nb])
-            if keep_q8_0 and ttype == GGML_Q8_0 and len(ne) == 2 and ne[0] % 32 == 0:
-                from ._native import Q8Blocks
-                tensors[name] = Q8Blocks(raw, tuple(reversed(ne)))
-                continue
-            if keep_q8_0 and ttype == GGML_Q4_K and len(ne) == 2 and ne[0] % 256 == 0:
-                from ._native import Q4KBlocks
-                tensors[name] = Q4KBlocks(raw, tuple(reversed(ne)))
-                continue
-            if keep_q8_0 and ttype in (GGML_Q4_0, GGML_Q4_1) and len(ne) == 2 and ne[0] % 32 == 0:
-                from ._native import Q40Blocks, Q41Blocks
-                tensors[name] = (Q41Blocks if ttype == GGML_Q4_1 else Q40Blocks)(raw, tuple(reversed(ne)))
-                continue
-            if keep_q8_0 and ttype == GGML_IQ4_NL and len(ne) == 2 and ne[0] % 32 == 0:
-                from ._native import IQ4NLBlocks
-                tensors[name] = IQ4NLBlocks(raw, tuple(reversed(ne)))
-                continue
-            if keep_q8_0 and ttype == GGML_IQ4_XS and len(ne) == 2 and ne[0] % 256 == 0:
-                from ._native import IQ4XSBlocks
-                tensors[name] = IQ4XSBlocks(raw, tuple(reversed(ne)))
-                continue
-            if keep_q8_0 and ttype == GGML_Q5_K and len(ne) == 2 and ne[0] % 256 == 0:
-                from ._native import Q5KBlocks
-                tensors[name] = Q5KBlocks(raw, tuple(reversed(ne)))
-                continue
-            if keep_q8_0 and ttype == GGML_Q6_K and len(ne) == 2 and ne[0] % 256 == 0:
-                from ._native import Q6KBlocks
-                tensors[name] = Q6KBlocks(raw, tuple(reversed(ne)))
-                continue
-            tensors[name] = _dequant(raw, ttype, numel).reshape(tuple(reversed(ne)) if ne else ())
+            _, vals, _, kind = _TYPES[ttype]
+            if keep_q8_0 and vals > 1 and len(ne) == 2 and ne[0] % vals == 0:   # a matrix of whole blocks per row stays packed
+                tensors[name] = kind(raw, tuple(reversed(ne)))
+            else:
+                tensors[name] = _dequant(raw, ttype, numel).reshape(tuple(reversed(ne)) if ne else ())
         return meta, tensors
 
 

@@ -102,6 +102,10 @@ def bf16_bits_to_f32(b: np.ndarray) -> np.ndarray:
 
 ACTIVATION_FORMATS = ("f32", "q8_1")          # rca_lm_set_act_format's 0 / 1
 KV_FORMATS = ("f16", "q8_0")                  # rca_lm_set_kv_format's 0 / 1
+# the library's format ids, as rca_lm_weight_format reports them (4: a file whose gate / up tensors are Q6_K, llama-quantize Q6_K) ...
+WEIGHT_FORMAT_NAMES = ("bf16", "q8_0", "f16", "q4_k", "q6_k", "q5_k", "q4_0", "q4_1", "iq4_nl", "iq4_xs")
+# ... and rca_lm_config_t::decode_weights, the load-time conversions of a 16-bit checkpoint (0: as supplied)
+DECODE_WEIGHTS = {"q8_0": 1, "f16": 2, "q4_k": 3, "q5_k": 4, "q4_0": 5, "q4_1": 6, "iq4_nl": 7}
 CODEC_PREFIX = "model.embed_codec_tokens."   # CodecLlamaCodecEmbedding's tensors (codec_llama.py:46-69)
 
 
@@ -224,7 +228,7 @@ class LlamaForAlternatingCodeChannels:
             raise ValueError(f"kv_shift_requant=True needs kv_format='q8_0' (got {kv_format!r}): the shift of an fp16 cache quantises nothing")
         if activation_format not in (None,) + ACTIVATION_FORMATS:
             raise ValueError(f"activation_format {activation_format!r}: None / 'f32' or 'q8_1'")
-        if weight_format not in (None, "bf16", "q8_0", "f16", "q4_k", "q5_k", "q4_0", "q4_1", "iq4_nl"):
+        if weight_format not in (None, "bf16") + tuple(DECODE_WEIGHTS):
             raise ValueError(f"weight_format {weight_format!r}: None / 'bf16' (as supplied), 'q8_0', 'f16', 'q4_k', 'q5_k', 'q4_0', 'q4_1' or 'iq4_nl'")
         self._lib = N.lib()
         self.model_path = model_path
@@ -267,7 +271,7 @@ class LlamaForAlternatingCodeChannels:
             n_kv_heads=config.n_kv_heads, head_dim=config.head_dim, ffn=config.ffn, n_ctx=self._n_ctx, rms_eps=config.rms_eps,
             rope_theta=config.rope_theta, rope_scaling=1 if config.rope_scaling == "llama3" else 0, rope_factor=config.rope_factor,
             rope_low_freq_factor=config.rope_low_freq_factor, rope_high_freq_factor=config.rope_high_freq_factor,
-            rope_orig_ctx=config.rope_orig_ctx, logits_all=1 if logits_all else 0, decode_weights={"q8_0": 1, "f16": 2, "q4_k": 3, "q5_k": 4, "q4_0": 5, "q4_1": 6, "iq4_nl": 7}.get(weight_format, 0),
+            rope_orig_ctx=config.rope_orig_ctx, logits_all=1 if logits_all else 0, decode_weights=DECODE_WEIGHTS.get(weight_format, 0),
         )
         self._h = C.c_void_p()
         if random_init:
@@ -398,10 +402,9 @@ class LlamaForAlternatingCodeChannels:
     def _query_format(self):
         fmt, nbytes = C.c_int32(), C.c_int64()
         N.check(self._lib.rca_lm_weight_format(self._h, C.byref(fmt), C.byref(nbytes)), "rca_lm_weight_format")
-        names = {0: "bf16", 1: "q8_0", 2: "f16", 3: "q4_k", 4: "q6_k", 5: "q5_k", 6: "q4_0", 7: "q4_1", 8: "iq4_nl", 9: "iq4_xs"}    # 4: a file whose gate / up tensors are Q6_K (llama-quantize Q6_K)
-        if fmt.value not in names:
+        if not 0 <= fmt.value < len(WEIGHT_FORMAT_NAMES):
             raise N.RcaError(f"rca_lm_weight_format reported an unknown format id {fmt.value}")
-        return names[fmt.value], int(nbytes.value)
+        return WEIGHT_FORMAT_NAMES[fmt.value], int(nbytes.value)
 
     def _finish_init(self, seed: int) -> None:
         self._ctx = _Ctx(self)
